@@ -15,6 +15,11 @@ With --gpus N > 1 and no WORLD_SIZE in the environment this process only LAUNCHE
 HIP call is made it starts N fresh children (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set), relays rank 0's JSON line
 and exits non-zero if any child did.  RTFHE_BENCH_BACKEND=gloo rehearses the N > 1 path on a box with fewer GPUs
 (ranks share the cards; collectives run on the CPU).
+
+A plain run measures the headline only: set-up, W warm-up steps, K timed steps, the line.  --full adds what is measured
+after the headline (the CPU baseline, the secondary measurements: the other BASELINE configs, both exact backends, the
+batch sweep; the cargo probe).  --dump-outputs DIR writes the output ciphertexts of the last timed step (rank 0's) as
+DIR/gate_outputs.npy; the inputs and keys are seeded, so two builds given the same arguments can be compared word for word.
 """
 import argparse
 import hashlib
@@ -430,6 +435,24 @@ def xfft_dp_wave_instr_per_cmux(N=1024, l=3):
     return {**per_wave, "per_wave": sum(per_wave.values()), "total": 2 * sum(per_wave.values())}
 
 
+DUMP_MAX_BYTES = 64 * 10**6                    # both files, .npy headers (128 bytes each) included
+
+
+def dump_outputs(out_dir, name, words, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: writes output ciphertexts (one row of n + 1 torus words per gate) as out_dir/<name>.npy, every word as its signed
+    32-bit value in float64 (exact; a word near 0 and one near 2^32 are neighbours as numbers too).  A batch larger than max_bytes is
+    sampled: a fixed seeded choice of rows in gate order, with their gate indices in out_dir/<name>_rows.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = np.ascontiguousarray(words).view(np.int32)
+    keep = max(1, (max_bytes - 256) // (rows.shape[1] * 8 + 8))
+    if rows.shape[0] > keep:
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))
+        rows = rows[idx]
+        np.save(os.path.join(out_dir, name + "_rows.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, name + ".npy"), rows.astype(np.float64))
+
+
 def fp64_frac(dp_per_cmux, n, gates, seconds):
     """fraction of the FP64 vector-issue ceiling a launch of `gates` gates taking `seconds` reaches"""
     return round(dp_per_cmux * n * 64 * gates / seconds / FP64_VALU_PEAK, 4)
@@ -731,16 +754,16 @@ def run_rank(args):
     mirror = args.backend == "fft64-mirror"
     G = args.gates if args.gates else (8192 if config3 else 1024)      # gates per GPU per step
     params = R.Params()
-    # ---- everything that needs no GPU comes first: keys (rank 0), this rank's inputs, and -- N = 1 only -- the CPU baseline's own
+    # ---- everything that needs no GPU comes first: keys (rank 0), this rank's inputs, and -- N = 1, --full only -- the CPU baseline's own
     # process, started BEFORE this process makes its first GPU call and left waiting on its stdin until the timed region is over
     t_key = time.perf_counter()
     if rank == 0:
         key0, key1, bk, ksk = R.keygen(params, 20211003)
     else:
         key0, bk, ksk = np.empty(params.n, np.int32), np.empty(params.bk_words, np.uint32), np.empty(params.ksk_words, np.uint32)
-    cargo_info = cargo_probe() if rank == 0 else None      # (may start `cargo`: before this process touches the GPU, like the child below)
+    cargo_info = cargo_probe() if rank == 0 and args.full else None      # (may start `cargo`: before this process touches the GPU, like the child below)
     cpu_child = None
-    want_cpu = world == 1 and not args.no_cpu_baseline and mirror and not config3 and not under_profiler()
+    want_cpu = args.full and world == 1 and not args.no_cpu_baseline and mirror and not config3 and not under_profiler()
     if want_cpu:
         rng = np.random.default_rng(1000 + rank)
         b0, b1 = rng.integers(0, 2, G).astype(np.uint8), rng.integers(0, 2, G).astype(np.uint8)
@@ -911,6 +934,8 @@ def run_rank(args):
         elapsed = time.perf_counter() - t0
         out = d_out.cpu().numpy().view(np.uint32)
         ok = bool(np.array_equal(R.decrypt_bits(params, key0, out), 1 - (b0 & b1)))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "gate_outputs", out)
 
     t = torch.tensor([elapsed, 0.0 if ok else 1.0, kern_ms], dtype=torch.float64, device=comm)
     if dist is not None:
@@ -999,11 +1024,12 @@ def run_rank(args):
         # The headline above is complete at this point, and nothing below may cost it.  Under supervise() (plain `python bench.py`, N = 1) the
         # line goes out NOW, marked provisional, and again after every side leg: if this process then dies of a native crash in a side
         # kernel or library, the supervisor prints the last line it saw and exits 0.  The CPU baseline runs in a process of its own.
-        line["cargo"] = cargo_info
+        if args.full:
+            line["cargo"] = cargo_info
         pending = []
         if isinstance(cpu_child, (CpuBaselineChild, dict)):
             pending.append("cpu_baseline")
-        want_secondary = n_gpus == 1 and not args.no_secondary and mirror and not config3 and not args.gates
+        want_secondary = args.full and n_gpus == 1 and not args.no_secondary and mirror and not config3 and not args.gates
         if want_secondary:
             pending.append("secondary")
 
@@ -1105,6 +1131,8 @@ def run_config3_c_abi(args):
             eng.gate_batch_dev(R.NAND, d0, d1, do, G, st)
         eng.sync(st)
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, "gate_outputs", do.cpu().numpy())
         # the entries' phases of one more (untimed) step: pull from the primary, bootstrap, push back -- events on each entry's own stream
         eng.gate_batch_dev(R.NAND, d0, d1, do, G, st); eng.sync(st)
         for d in range(1, len(devs)):
@@ -1144,8 +1172,12 @@ def main():
     ap.add_argument("--backend", choices=["fft64-mirror", "ntt-exact", "split-fft-exact"], default="fft64-mirror",
                     help="fft64-mirror (default): bit-identical to the reference CPU path; ntt-exact: exact-integer NTT; split-fft-exact: the same "
                          "exact products through an FMA FP64 FFT with the key in 16-bit halves")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other BASELINE configs / NTT backend measured after the headline")
+    ap.add_argument("--full", action="store_true", help="after the headline also measure the CPU baseline and the secondary measurements "
+                    "(other BASELINE configs, both exact backends, batch sweep) and probe for cargo; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the output ciphertexts of the last timed step (rank 0's) as "
+                    "DIR/gate_outputs.npy, float64, at most 64 MB (a larger batch: a seeded sample of gates, their indices in gate_outputs_rows.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the other BASELINE configs / NTT backend measured after the headline")
     ap.add_argument("--cpu-gates-per-thread", type=int, default=24, help="least number of gates every thread of the all-core CPU baseline runs")
     ap.add_argument("--settle-max", type=int, default=0, help="untimed clock-settle launches BEFORE the caller's warm-up steps, at most this many "
                     "(default 0: exactly --warmup untimed steps, the driver's contract; > 0: launches until three in a row agree within 1 %%)")
@@ -1155,6 +1187,8 @@ def main():
         sys.exit(cpu_baseline_child(args.cpu_baseline_child, args.cpu_gates_per_thread))
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.workload == "config3-c-abi":
         sys.exit(run_config3_c_abi(args))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:

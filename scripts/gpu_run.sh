@@ -5,8 +5,8 @@
 #   tests            the GPU suite (pytest -m gpu, one process)
 #   testfile:<file>  one file of it
 #   smoke            __graft_entry__.smoke()
-#   bench            python bench.py (default flags: headline + cpu baseline + secondary)
-#   bench20          python bench.py --steps 20 --warmup 5 (the driver's flags)
+#   bench            python bench.py --full (headline + cpu baseline + secondary)
+#   bench20          python bench.py --full --steps 20 --warmup 5 (the driver's flags)
 #   config3[:D]      bench.py --workload config3 on one GPU (RCCL harness); with D: --workload config3-c-abi over D entries naming GPU 0 (C-ABI sharding)
 #   ntt              bench.py --backend ntt-exact
 #   sweep[:N[:backend]]   scripts/sweep.py over the usual batch sizes (N = 1024 default, 2048; backend fft|ntt|xfft)
@@ -36,8 +36,8 @@ for step in "$@"; do
     testfile) run "tests $a1" bash -c "timeout -k 10 900 python -m pytest tests/$a1 -m gpu -x -q > $O/pytest_$a1.log 2>&1; rc=\$?; tail -15 $O/pytest_$a1.log; exit \$rc" ;;
     tests)   run tests bash -c "timeout -k 10 1100 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; rc=\$?; tail -3 $O/pytest_gpu.log; exit \$rc" ;;
     smoke)   run smoke bash -c "timeout -k 10 300 python -c 'import __graft_entry__ as g; g.smoke()' > $O/smoke.log 2>&1; rc=\$?; tail -2 $O/smoke.log; exit \$rc" ;;
-    bench)   run bench bash -c "timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err; rc=\$?; cut -c1-400 $O/bench.json; exit \$rc" ;;
-    bench20) run bench20 bash -c "timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench_steps20_warmup5.json 2> $O/bench20.err; rc=\$?; cut -c1-400 $O/bench_steps20_warmup5.json; exit \$rc" ;;
+    bench)   run bench bash -c "timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err; rc=\$?; cut -c1-400 $O/bench.json; exit \$rc" ;;
+    bench20) run bench20 bash -c "timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_steps20_warmup5.json 2> $O/bench20.err; rc=\$?; cut -c1-400 $O/bench_steps20_warmup5.json; exit \$rc" ;;
     config3) if [ -n "$a1" ]; then devs=$(python3 -c "print(','.join(['0'] * $a1))")
                run "config3 c-abi x$a1" bash -c "timeout -k 10 300 python bench.py --workload config3-c-abi --devices $devs --steps 3 --warmup 1 > $O/bench_config3_c_abi_$a1.json 2> $O/bench_config3_c_abi.err; rc=\$?; cut -c1-400 $O/bench_config3_c_abi_$a1.json; exit \$rc"
              else run config3 bash -c "timeout -k 10 300 python bench.py --workload config3 --steps 3 --warmup 1 > $O/bench_config3_1gpu.json 2> $O/bench_config3.err; rc=\$?; cut -c1-300 $O/bench_config3_1gpu.json; exit \$rc"; fi ;;

@@ -349,7 +349,7 @@ def test_bench_headline_survives_an_abort_in_a_side_leg(where):
     dying in a side leg is "ok": false + side_leg_crash and, under RTFHE_BENCH_STRICT=1 (what scripts/gpu_run.sh exports), exit code 86."""
     import bench
     env = dict(os.environ, RTFHE_BENCH_TEST_ABORT=where, RTFHE_BENCH_STRICT="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-gates-per-thread", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-gates-per-thread", "1"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == (0 if where == "cpu_child" else bench.SIDE_LEG_CRASH_RC), r.stderr[-2000:]
     lines = [ln for ln in r.stdout.split("\n") if ln.strip()]
@@ -362,3 +362,63 @@ def test_bench_headline_survives_an_abort_in_a_side_leg(where):
         assert line["ok"] is False
         assert line["side_leg_crash"]["signal"] == "SIGABRT" and line["side_leg_crash"]["legs_not_completed"] == ["secondary"]
         assert "value" in line["cpu_baseline"] or "error" in line["cpu_baseline"]
+
+
+# ---- a plain run is the headline only; --dump-outputs writes what its last timed step computed ----------------------------------------
+def test_dump_outputs_writes_exact_words_and_samples_a_large_batch(tmp_path):
+    import numpy as np
+    import bench
+    words = np.random.default_rng(5).integers(0, 2**32, (40, 636), dtype=np.uint64).astype(np.uint32)
+    bench.dump_outputs(str(tmp_path / "all"), "gate_outputs", words)
+    got = np.load(tmp_path / "all" / "gate_outputs.npy")
+    assert got.dtype == np.float64 and got.shape == words.shape
+    assert np.array_equal(got.astype(np.int64) % 2**32, words)
+    assert not (tmp_path / "all" / "gate_outputs_rows.npy").exists()
+    cap = 10 * (636 * 8 + 8) + 256                            # room for 10 rows, their indices and two .npy headers
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), "gate_outputs", words, max_bytes=cap)
+    got, rows = np.load(tmp_path / "s1" / "gate_outputs.npy"), np.load(tmp_path / "s1" / "gate_outputs_rows.npy")
+    assert got.shape == (10, 636) and rows.dtype == np.float64
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in ("gate_outputs.npy", "gate_outputs_rows.npy")) <= cap
+    assert np.all(np.diff(rows) > 0) and np.array_equal(got.astype(np.int64) % 2**32, words[rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "s2" / "gate_outputs_rows.npy"), rows)      # the same sample every run
+
+
+def test_bench_refuses_a_run_without_timed_steps():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr and "{" not in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_bench_is_the_headline_only_and_dumps_the_oracles_words(tmp_path, orc):
+    """A plain run prints the headline line without --full's legs; --dump-outputs holds the output ciphertexts of its last step, and they are
+    the CPU oracle's words for bench.py's seeded keys and inputs."""
+    import ctypes as C
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.split("\n") if ln.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "gates/s" and line["higher_is_better"] is True and line["dtype"] == "f64" and line["metric"].startswith("HomNAND")
+    assert line["ok"] is True and line["outputs_decrypt_correctly"] is True
+    assert not {"cpu_baseline", "secondary", "cargo"} & set(line), sorted(line)
+    import rustfhe_amd as R
+    params = R.Params()
+    got = np.load(tmp_path / "gate_outputs.npy")
+    assert got.dtype == np.float64 and got.shape == (1024, params.n + 1)
+    words = (got.astype(np.int64) % 2**32).astype(np.uint32)
+    # bench.py's inputs, restated: keys of seed 20211003, bits from default_rng(1000), encryption seeds 5000 / 5001
+    key0, _, bk, ksk = R.keygen(params, 20211003)
+    rng = np.random.default_rng(1000)
+    b0, b1 = rng.integers(0, 2, 1024).astype(np.uint8), rng.integers(0, 2, 1024).astype(np.uint8)
+    in0, in1 = R.encrypt_bits(params, key0, b0, 5000), R.encrypt_bits(params, key0, b1, 5001)
+    assert list(R.decrypt_bits(params, key0, words)) == list(1 - (b0 & b1))
+    p = orc.Params()
+    pl = orc.Plan(p.N)
+    bk_f = np.empty(bk.size, np.float64)
+    orc.lib().orc_trgsw_to_fft(pl.h, bk.ctypes.data_as(C.POINTER(C.c_uint32)), bk_f.ctypes.data_as(C.POINTER(C.c_double)), bk.size // p.N)
+    for g in (0, 1, 517, 1023):
+        assert np.array_equal(words[g], orc.gate(p, pl, orc.NAND, bk_f, None, ksk, in0[g], in1[g])), g

@@ -1,6 +1,6 @@
 """CPU: pins the oracle's FP64 transform (i) against the committed golden vectors that were produced by the
-reference's own compiled spqlios and (ii), where oracle/_ref has been built (this container), against that
-library live, bit for bit."""
+reference's own compiled spqlios and (ii) against that library's outputs on a longer seeded sequence: live, where
+oracle/_ref has been built, and always against a recording of them (tests/golden/spqlios_live_N<N>.npz), bit for bit."""
 import subprocess
 import sys
 
@@ -35,40 +35,57 @@ def test_whole_gate_golden(orc, params, keys, gold_gate):
     assert np.array_equal(mux, gold_gate["mux_out"])
 
 
+# argv: N, tests dir, mode, recording.  live: against oracle/_ref; record: the same, and the library's outputs saved to the recording
+# (FNV-1a 64 digests of the exact outputs, Spqlios_poly_mul's words whole); replay: against the recording
 _LIVE = r"""
 import sys, numpy as np
 sys.path.insert(0, sys.argv[2])
 import orc
-N = int(sys.argv[1])
-R = orc.ref_lib(); h = R.Spqlios_new(N); pl = orc.Plan(N)
+N, mode, path = int(sys.argv[1]), sys.argv[3], sys.argv[4]
+pl = orc.Plan(N)
+if mode == "replay":
+    rec = np.load(path)
+else:
+    R = orc.ref_lib(); h = R.Spqlios_new(N)
+    rec = {"fwd": np.zeros(60, np.uint64), "inv": np.zeros(60, np.uint64), "poly_mul": np.empty(N, np.uint32)}
 rng = np.random.default_rng(N)
 for t in range(60):
     src = [rng.integers(-32, 32, N), rng.integers(-2**31, 2**31, N), rng.integers(0, 2, N)][t % 3].astype(np.int32)
-    ref = np.empty(N); R.Spqlios_ifft_i32(h, ref.ctypes.data, src.ctypes.data)
     mine = pl.ifft_i32(src)
-    assert mine.tobytes() == ref.tobytes(), ("forward", t)
+    if mode != "replay":
+        ref = np.empty(N); R.Spqlios_ifft_i32(h, ref.ctypes.data, src.ctypes.data)
+        assert mine.tobytes() == ref.tobytes(), ("forward", t)
+        rec["fwd"][t] = orc.fnv64(ref)
+    assert orc.fnv64(mine) == int(rec["fwd"][t]), ("forward", t)
     spec = np.ascontiguousarray(mine * float(rng.integers(1, 2**20)))
-    r2 = np.empty(N, np.uint32); R.Spqlios_fft_u32(h, r2.ctypes.data, spec.ctypes.data)
-    assert np.array_equal(pl.fft_u32(spec), r2), ("inverse", t)
+    if mode != "replay":
+        r2 = np.empty(N, np.uint32); R.Spqlios_fft_u32(h, r2.ctypes.data, spec.ctypes.data)
+        assert np.array_equal(pl.fft_u32(spec), r2), ("inverse", t)
+        rec["inv"][t] = orc.fnv64(r2)
+    assert orc.fnv64(pl.fft_u32(spec)) == int(rec["inv"][t]), ("inverse", t)
 a = rng.integers(0, 2**32, N, dtype=np.uint64).astype(np.uint32); b = rng.integers(0, 64, N).astype(np.uint32)
-r3 = np.empty(N, np.uint32); R.Spqlios_poly_mul(h, r3.ctypes.data, a.ctypes.data, b.ctypes.data)
+if mode != "replay":
+    R.Spqlios_poly_mul(h, rec["poly_mul"].ctypes.data, a.ctypes.data, b.ctypes.data)
+r3 = rec["poly_mul"]
 # Spqlios_poly_mul (off the hot path; only the reference's N=16 unit test calls it) is C++ built with the reference's
 # -Ofast -march=native, where g++ contracts a*b-c to FMA: machine-dependent bits, so +-1 LSB is all that can be pinned.
 d = (pl.poly_mul(a, b).astype(np.int64) - r3.astype(np.int64) + 2**31) % 2**32 - 2**31
 assert np.abs(d).max() <= 1, d
+if mode == "record":
+    np.savez_compressed(path, **rec)
 print("ok")
 """
 
 
 @pytest.mark.parametrize("N", [16, 1024, 2048])
 def test_mirror_matches_live_reference_library(orc, N):
-    if not orc.have_ref():
-        pytest.skip("oracle/_ref not built (no reference checkout here); golden vectors cover this")
     import os
     tests_dir = os.path.dirname(os.path.abspath(__file__))
-    # one N per process: the reference caches 2/N in a function-local static (SURVEY H7)
-    out = subprocess.run([sys.executable, "-c", _LIVE, str(N), tests_dir], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
+    recording = os.path.join(tests_dir, "golden", "spqlios_live_N%d.npz" % N)
+    for mode in (["live"] if orc.have_ref() else []) + ["replay"]:
+        # one N per process: the reference caches 2/N in a function-local static (SURVEY H7)
+        out = subprocess.run([sys.executable, "-c", _LIVE, str(N), tests_dir, mode, recording], capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0 and "ok" in out.stdout, (mode, out.stderr[-2000:])
 
 
 def test_whole_gate_with_live_reference_fft(orc, params, keys, gold_gate):

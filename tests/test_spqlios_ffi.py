@@ -48,14 +48,18 @@ def test_unsupported_degree_or_no_device_gives_null():
 @pytest.mark.gpu
 @pytest.mark.parametrize("N", [16, 32, 512, 1024, 2048])      # 16: the size of the reference's own unit test (spqlios.rs:243-276)
 def test_c_host_gets_the_reference_bytes_through_both_libraries(tmp_path, N):
-    ref = os.path.join(ROOT, "oracle", "_ref", "libspqlios_ref.so")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref/libspqlios_ref.so not built (needs the reference checkout at build time)")
+    """Against a recording of the reference library's outputs for this host's inputs (tests/golden/spqlios_ffi_N<N>.bin, in the format of
+    the host's --record mode) and, where oracle/_ref has been built, against the live library too."""
     import rustfhe_amd.build as b
     exe = str(tmp_path / "spqlios_ffi")
     subprocess.check_call(["gcc", "-O1", "-std=gnu99", "-Wall", os.path.join(ROOT, "tests", "c", "spqlios_ffi_main.c"), "-o", exe, "-ldl"])
-    out = subprocess.run([exe, b.LIB, ref, str(N)], capture_output=True, text=True, timeout=300)     # one N per process (H7)
-    assert out.returncode == 0 and "spqlios ffi ok" in out.stdout, out.stdout + out.stderr
+    ref = os.path.join(ROOT, "oracle", "_ref", "libspqlios_ref.so")
+    recording = os.path.join(ROOT, "tests", "golden", "spqlios_ffi_N%d.bin" % N)
+    runs = [[ref, str(N)]] if os.path.exists(ref) else []
+    runs.append(["-", str(N), recording])
+    for args in runs:
+        out = subprocess.run([exe, b.LIB] + args, capture_output=True, text=True, timeout=300)     # one N per process (H7)
+        assert out.returncode == 0 and "spqlios ffi ok" in out.stdout, (args, out.stdout + out.stderr)
 
 
 @pytest.mark.gpu
