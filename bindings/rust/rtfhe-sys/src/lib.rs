@@ -31,6 +31,7 @@ pub struct rtfhe_peer_info {
 }
 pub enum rtfhe_ctx {}
 pub enum rtfhe_circuit {}
+pub enum rtfhe_lut {}
 pub enum rtfhe_fft_plan {}
 
 pub const RTFHE_NAND: c_int = 0;
@@ -99,6 +100,12 @@ extern "C" {
                                 wave_offsets: *const i32, num_waves: i32, d_wires: *mut c_void, num_wires: usize, out: *mut *mut rtfhe_circuit) -> c_int;
     pub fn rtfhe_circuit_launch(c: *mut rtfhe_circuit, stream: *mut c_void) -> c_int;
     pub fn rtfhe_circuit_destroy(c: *mut rtfhe_circuit);
+    // programmable bootstrapping: caller-supplied test polynomials [n_lut][N]; lut_idx null = table 0 for every gate
+    pub fn rtfhe_lut_create(ctx: *mut rtfhe_ctx, tv: *const u32, n_lut: i32, out: *mut *mut rtfhe_lut) -> c_int;
+    pub fn rtfhe_lut_destroy(lut: *mut rtfhe_lut);
+    pub fn rtfhe_pbs_batch(ctx: *mut rtfhe_ctx, lut: *const rtfhe_lut, lut_idx: *const i32, tlwe: *const u32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_pbs_batch_dev(ctx: *mut rtfhe_ctx, lut: *const rtfhe_lut, d_lut_idx: *const c_void, d_tlwe: *const c_void, d_out: *mut c_void,
+                               count: usize, stream: *mut c_void) -> c_int;
     pub fn rtfhe_sync(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_begin(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_end(ctx: *mut rtfhe_ctx, stream: *mut c_void, ms: *mut f64, launches: *mut i64) -> c_int;
@@ -129,12 +136,14 @@ extern "C" {
     pub fn rtfhe_keygen(p: *const rtfhe_params, key0: *mut i32, key1: *mut i32, bk: *mut u32, ksk: *mut u32) -> c_int;
     pub fn rtfhe_keygen_with_keys(p: *const rtfhe_params, key0: *const i32, key1: *const i32, bk: *mut u32, ksk: *mut u32) -> c_int;
     pub fn rtfhe_tlwe_encrypt_bits(p: *const rtfhe_params, key0: *const i32, bits: *const u8, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_tlwe_encrypt_torus(p: *const rtfhe_params, key0: *const i32, mu: *const u32, out: *mut u32, count: usize) -> c_int;
     // TEST ONLY (seeded xoshiro256**, not secure)
     pub fn rtfhe_ksk_expand_ref(p: *const rtfhe_params, key0: *const i32, key1: *const i32, ksk: *const u32, ksk_ref: *mut u32) -> c_int;
     pub fn rtfhe_ksk_expand_ref_deterministic(p: *const rtfhe_params, seed: u64, key0: *const i32, key1: *const i32, ksk: *const u32, ksk_ref: *mut u32) -> c_int;
     pub fn rtfhe_keygen_deterministic(p: *const rtfhe_params, seed: u64, key0: *mut i32, key1: *mut i32, bk: *mut u32, ksk: *mut u32) -> c_int;
     pub fn rtfhe_keygen_with_keys_deterministic(p: *const rtfhe_params, seed: u64, key0: *const i32, key1: *const i32, bk: *mut u32, ksk: *mut u32) -> c_int;
     pub fn rtfhe_tlwe_encrypt_bits_deterministic(p: *const rtfhe_params, key0: *const i32, seed: u64, bits: *const u8, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_tlwe_encrypt_torus_deterministic(p: *const rtfhe_params, key0: *const i32, seed: u64, mu: *const u32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_tlwe_decrypt_bits(p: *const rtfhe_params, key0: *const i32, input: *const u32, bits: *mut u8, count: usize) -> c_int;
     pub fn rtfhe_keys_write(path: *const c_char, p: *const rtfhe_params, key0: *const i32, key1: *const i32, bk: *const u32, ksk: *const u32) -> c_int;
     pub fn rtfhe_keys_read_header(path: *const c_char, p: *mut rtfhe_params, flags: *mut u32) -> c_int;

@@ -22,6 +22,8 @@
  *   rtfhe_circuit_create / _launch   <- the same evaluation, all levels of a netlist recorded once and replayed as one submission
  *   rtfhe_bootstrap_batch[_dev]      <- TFHE::bootstrap (tfhe.rs:73-80)
  *   rtfhe_blind_rotate_batch         <- TFHE::blind_rotate with the gate test vector (tfhe.rs:81-113)
+ *   rtfhe_lut_* / rtfhe_pbs_batch[_dev]  (no reference counterpart: its test vector is fixed to 1/8) the same bootstrap with
+ *                                       caller-supplied test polynomials: programmable bootstrapping
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch           <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -226,6 +228,31 @@ int rtfhe_circuit_create(rtfhe_ctx *ctx, const void *d_ops, const void *d_idx0, 
                          const int32_t *wave_offsets, int32_t num_waves, void *d_wires, size_t num_wires, rtfhe_circuit **out);
 int rtfhe_circuit_launch(rtfhe_circuit *c, void *stream);
 void rtfhe_circuit_destroy(rtfhe_circuit *c);
+/* ---- programmable bootstrapping (PBS): the bootstrap with a test polynomial the caller chooses ----
+ * For an input t = (a_0 .. a_{n-1}, b) in the lvl0 layout, SH = 32 - log2(N) - 1, gate g of a batch computes
+ *     bbar = b >> SH ;  abar_i = (a_i + 2^(SH-1)) >> SH                 (the gates' own mod switch)
+ *     acc  = X^{-bbar} (tv, 0),  tv = row lut_idx[g] of the table:  acc[c] = e < N ? tv[e] : -tv[e-N],  e = (c + bbar) mod 2N
+ *     for i in 0 .. n:  acc = CMUX(bk_i, X^{abar_i} acc, acc)
+ *     out[g] = identity_key_switch(sample_extract_0(acc))
+ * With tv = 0x20000000 at every position the output equals rtfhe_bootstrap_batch's words (every batch shape, every count).
+ * A table is uploaded once by rtfhe_lut_create, to every device of the context (each entry of an rtfhe_ctx_create_multi context holds a
+ * copy); a PBS call allocates nothing for it, so rtfhe_pbs_batch_dev may sit inside a stream capture under the rule of
+ * rtfhe_bootstrap_batch_dev (an eager batch of at least `count` gates must have run on that stream before).  A table is normally destroyed
+ * before its context; if the context goes first, its device copies are released with it, a later PBS call with it fails with
+ * RTFHE_ERR_STATE and rtfhe_lut_destroy only frees the handle.  lut_idx NULL = table 0 for every gate.
+ *   rtfhe_pbs_batch      checks lut_idx against [0, n_lut) on the host: RTFHE_ERR_INVALID before anything is launched.
+ *   rtfhe_pbs_batch_dev  checks each index on the device: a gate with a bad index is skipped (its output row is not a valid ciphertext)
+ *                        and the next rtfhe_sync returns RTFHE_ERR_INVALID, as for netlist waves.
+ * On a multi-device context both calls shard the batch as rtfhe_bootstrap_batch[_dev] do, each range with its own lut_idx range.
+ * The FP64 mirror backend only: on RTFHE_BACKEND_NTT_EXACT / RTFHE_BACKEND_FFT_SPLIT_EXACT both calls fail with RTFHE_ERR_INVALID
+ * (the context stays usable). */
+typedef struct rtfhe_lut rtfhe_lut;
+int rtfhe_lut_create(rtfhe_ctx *ctx, const uint32_t *tv /* [n_lut][N] */, int32_t n_lut, rtfhe_lut **out);
+void rtfhe_lut_destroy(rtfhe_lut *lut);
+int rtfhe_pbs_batch(rtfhe_ctx *ctx, const rtfhe_lut *lut, const int32_t *lut_idx /* [count] or NULL */,
+                    const uint32_t *tlwe /* [count][n+1] */, uint32_t *out /* [count][n+1] */, size_t count);
+int rtfhe_pbs_batch_dev(rtfhe_ctx *ctx, const rtfhe_lut *lut, const void *d_lut_idx /* int32[count] or NULL */,
+                        const void *d_tlwe, void *d_out, size_t count, void *stream);
 /* waits for `stream`; also reports (once) a netlist gate skipped since the previous call */
 int rtfhe_sync(rtfhe_ctx *ctx, void *stream);
 /* device-side timing of the launches enqueued by the *_dev calls between begin and end (HIP events on
@@ -282,6 +309,10 @@ int rtfhe_keygen(const rtfhe_params *p, int32_t *key0 /* [n] */, int32_t *key1 /
 int rtfhe_keygen_with_keys(const rtfhe_params *p, const int32_t *key0, const int32_t *key1, uint32_t *bk, uint32_t *ksk);
 int rtfhe_tlwe_encrypt_bits(const rtfhe_params *p, const int32_t *key0, const uint8_t *bits, uint32_t *out /* [count][n+1] */,
                             size_t count);
+/* rtfhe_tlwe_encrypt_bits with the plaintext torus words mu[count] given directly (same CSPRNG, same noise alpha = 2^-15): multi-bit
+ * messages for rtfhe_pbs_batch */
+int rtfhe_tlwe_encrypt_torus(const rtfhe_params *p, const int32_t *key0, const uint32_t *mu, uint32_t *out /* [count][n+1] */,
+                             size_t count);
 /* the reference's KeySwitchingKey shape from the compact one: entries t = 1 .. base-1 of every level copied, entry t = base =
  * TLWE(base * s_i / 2^(basebit (l+1))) freshly encrypted as KeySwitchingKey::new fills it (hom_nand/src/tlwe.rs:252-274) */
 int rtfhe_ksk_expand_ref(const rtfhe_params *p, const int32_t *key0, const int32_t *key1,
@@ -296,6 +327,8 @@ int rtfhe_ksk_expand_ref_deterministic(const rtfhe_params *p, uint64_t seed, con
                                        const uint32_t *ksk, uint32_t *ksk_ref);
 int rtfhe_tlwe_encrypt_bits_deterministic(const rtfhe_params *p, const int32_t *key0, uint64_t seed,
                                           const uint8_t *bits, uint32_t *out /* [count][n+1] */, size_t count);
+int rtfhe_tlwe_encrypt_torus_deterministic(const rtfhe_params *p, const int32_t *key0, uint64_t seed,
+                                            const uint32_t *mu, uint32_t *out /* [count][n+1] */, size_t count);
 int rtfhe_tlwe_decrypt_bits(const rtfhe_params *p, const int32_t *key0, const uint32_t *in,
                             uint8_t *bits, size_t count);
 int rtfhe_tlwe_phase(const rtfhe_params *p, const int32_t *key0, const uint32_t *in, uint32_t *phase, size_t count);

@@ -89,6 +89,10 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "rtfhe_circuit_launch": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rtfhe_circuit_destroy": (None, [C.c_void_p]),
+    "rtfhe_lut_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "rtfhe_lut_destroy": (None, [C.c_void_p]),
+    "rtfhe_pbs_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rtfhe_pbs_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtfhe_sync": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rtfhe_timer_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rtfhe_timer_end": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -114,11 +118,13 @@ _SIGNATURES = {
     "rtfhe_keygen": (C.c_int, ["PP", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtfhe_keygen_with_keys": (C.c_int, ["PP", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtfhe_tlwe_encrypt_bits": (C.c_int, ["PP", C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rtfhe_tlwe_encrypt_torus": (C.c_int, ["PP", C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "rtfhe_ksk_expand_ref": (C.c_int, ["PP", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtfhe_ksk_expand_ref_deterministic": (C.c_int, ["PP", C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtfhe_keygen_deterministic": (C.c_int, ["PP", C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtfhe_keygen_with_keys_deterministic": (C.c_int, ["PP", C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtfhe_tlwe_encrypt_bits_deterministic": (C.c_int, ["PP", C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rtfhe_tlwe_encrypt_torus_deterministic": (C.c_int, ["PP", C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t]),
     "rtfhe_tlwe_decrypt_bits": (C.c_int, ["PP", C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "rtfhe_tlwe_phase": (C.c_int, ["PP", C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "rtfhe_keys_write": (C.c_int, [C.c_char_p, "PP", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -26,7 +26,8 @@ int ensure_tlwe1(rtfhe_ctx* ctx, rtfhe_ctx::Tlwe1& b, size_t gates) {
 }
 
 int launch_bootstrap(rtfhe_ctx* ctx, int op, int mode, int steps, const void* d_in0, const void* d_in1, void* d_out,
-                     size_t count, hipStream_t s, const int32_t* d_ops, const int32_t* d_idx0, const int32_t* d_idx1, const int32_t* d_idx_out, int32_t num_wires) {
+                     size_t count, hipStream_t s, const int32_t* d_ops, const int32_t* d_idx0, const int32_t* d_idx1, const int32_t* d_idx_out, int32_t num_wires,
+                     const LutRef& lut) {
     if (!ctx->has_bk) return fail(ctx, RTFHE_ERR_STATE, "bootstrapping key not loaded");
     if (mode == MODE_GATE && !ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "key-switching key not loaded");
     if (count == 0) return 0;
@@ -58,6 +59,8 @@ int launch_bootstrap(rtfhe_ctx* ctx, int op, int mode, int steps, const void* d_
             }
         }
     }
+    if (lut.tv && ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
+        return fail(ctx, RTFHE_ERR_INVALID, "programmable bootstrapping runs on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR)");
     if (ctx->backend == RTFHE_BACKEND_NTT_EXACT) {
         if (int rc = ntt_prepare(ctx)) return rc;
         return launch_bootstrap_ntt(ctx, a, s);
@@ -66,7 +69,7 @@ int launch_bootstrap(rtfhe_ctx* ctx, int op, int mode, int steps, const void* d_
         if (int rc = xfft_prepare(ctx)) return rc;
         return launch_bootstrap_xfft(ctx, a, s);
     }
-    return launch_bootstrap_fft(ctx, a, s);
+    return launch_bootstrap_fft(ctx, a, s, lut);
 }
 
 int run_host_bootstrap_one(rtfhe_ctx* ctx, int op, int mode, int steps, const uint32_t* in0, const uint32_t* in1,
@@ -85,6 +88,24 @@ int run_host_bootstrap_one(rtfhe_ctx* ctx, int op, int mode, int steps, const ui
     }
     if (int rc = launch_bootstrap(ctx, op, mode, steps, ctx->d_a, d1, ctx->d_c, count, ctx->stream)) return rc;
     return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+}
+
+int run_host_pbs_one(rtfhe_ctx* ctx, const LutRef& lut, const int32_t* lut_idx, const uint32_t* in, uint32_t* out, size_t count) {
+    if (int rc = use(ctx)) return rc;
+    if (count == 0) return 0;
+    const size_t bytes = count * ((size_t)ctx->p.n + 1) * 4;
+    if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, bytes)) return rc;
+    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, bytes)) return rc;
+    if (int rc = copy_in(ctx, ctx->d_a, in, bytes, 0)) return rc;
+    LutRef l = lut;
+    if (lut_idx) {      // the indices ride in the second operand's staging buffer (a bootstrap has one operand)
+        if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, count * 4)) return rc;
+        if (int rc = copy_in(ctx, ctx->d_b, lut_idx, count * 4, 1)) return rc;
+        l.idx = (const int32_t*)ctx->d_b;
+    }
+    if (int rc = launch_bootstrap(ctx, RTFHE_COPY, MODE_GATE, ctx->p.n, ctx->d_a, nullptr, ctx->d_c, count, ctx->stream, nullptr, nullptr, nullptr, nullptr, 0, l))
+        return rc;
+    return copy_out(ctx, out, ctx->d_c, bytes, 2);
 }
 
 // hom_mux (tfhe.rs:27-40): i1 = AND(c, in1); i0 = AND(-c, in0); bootstrap(i1 + i0 + 1/8) -- the last line is hom_or(i1, i0).
@@ -173,15 +194,109 @@ int rtfhe_mux_batch_dev(rtfhe_ctx* ctx, const void* d_c, const void* d_in0, cons
     return mux_dev_one(ctx, d_c, d_in0, d_in1, d_out, count, (hipStream_t)stream);
 }
 
+// ---- programmable bootstrapping (include/rtfhe.h) ----
+int rtfhe_lut_create(rtfhe_ctx* ctx, const uint32_t* tv, int32_t n_lut, rtfhe_lut** out) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!tv || !out || n_lut < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_create: null argument or n_lut < 1");
+    *out = nullptr;
+    const size_t bytes = (size_t)n_lut * ctx->p.N * 4;
+    rtfhe_lut* lut = new rtfhe_lut();
+    lut->n_lut = n_lut;
+    const int entries = 1 + (int)ctx->peers.size();
+    int rc = 0;
+    for (int d = 0; d < entries && !rc; d++) {
+        rtfhe_ctx* c = d ? ctx->peers[d - 1] : ctx;
+        void* p = nullptr;
+        rc = use(c);
+        if (!rc && hipMalloc(&p, bytes) != hipSuccess) rc = fail(c, RTFHE_ERR_HIP, "rtfhe_lut_create: hipMalloc");
+        if (p) lut->d_tv.push_back((uint32_t*)p);
+        if (!rc && hipMemcpy(p, tv, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, RTFHE_ERR_HIP, "rtfhe_lut_create: hipMemcpy");
+        if (rc && c != ctx) rc = fail(ctx, rc, "device " + std::to_string(c->device) + ": " + c->err);
+    }
+    (void)hipSetDevice(ctx->device);
+    if (rc) {
+        (void)hipGetLastError();
+        for (size_t d = 0; d < lut->d_tv.size(); d++) {
+            (void)hipSetDevice(d ? ctx->peers[d - 1]->device : ctx->device);
+            (void)hipFree(lut->d_tv[d]);
+        }
+        (void)hipSetDevice(ctx->device);
+        delete lut;
+        return rc;
+    }
+    lut->ctx = ctx;
+    ctx->luts.push_back(lut);
+    *out = lut;
+    return 0;
+}
+
+void rtfhe_lut_destroy(rtfhe_lut* lut) {
+    if (!lut) return;
+    if (rtfhe_ctx* ctx = lut->ctx) {     // still attached (a context destroyed first has already freed the tables and detached us)
+        auto& v = ctx->luts;
+        for (size_t i = 0; i < v.size(); i++) if (v[i] == lut) { v.erase(v.begin() + i); break; }
+        rtfhe_host::lut_release(lut);
+    }
+    delete lut;
+}
+
+// what both PBS entries check before anything is launched
+static int pbs_ready(rtfhe_ctx* ctx, const rtfhe_lut* lut) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!lut) return fail(ctx, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
+    if (!lut->ctx) return fail(ctx, RTFHE_ERR_STATE, "the table's context has been destroyed");
+    if (lut->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the table belongs to another context");
+    if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
+        return fail(ctx, RTFHE_ERR_INVALID, "programmable bootstrapping runs on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR); "
+                                            "select it with rtfhe_set_backend");
+    if (!ctx->has_bk) return fail(ctx, RTFHE_ERR_STATE, "bootstrapping key not loaded");
+    if (!ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "key-switching key not loaded");
+    return 0;
+}
+
+int rtfhe_pbs_batch(rtfhe_ctx* ctx, const rtfhe_lut* lut, const int32_t* lut_idx, const uint32_t* tlwe, uint32_t* out, size_t count) {
+    if (int rc = pbs_ready(ctx, lut)) return rc;
+    if (!tlwe || !out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (count > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "count too large");
+    if (lut_idx)
+        for (size_t g = 0; g < count; g++)
+            if ((uint32_t)lut_idx[g] >= (uint32_t)lut->n_lut)
+                return fail(ctx, RTFHE_ERR_INVALID, "lut_idx[" + std::to_string(g) + "] = " + std::to_string(lut_idx[g]) + " is outside [0, " + std::to_string(lut->n_lut) + ")");
+    return sharded_host_pbs(ctx, lut, lut_idx, tlwe, out, count);
+}
+
+int rtfhe_pbs_batch_dev(rtfhe_ctx* ctx, const rtfhe_lut* lut, const void* d_lut_idx, const void* d_tlwe, void* d_out, size_t count, void* stream) {
+    if (int rc = pbs_ready(ctx, lut)) return rc;
+    if (int rc = use(ctx)) return rc;
+    if (!d_tlwe || !d_out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (!gpu_accessible(ctx, d_tlwe) || !gpu_accessible(ctx, d_out) || (d_lut_idx && !gpu_accessible(ctx, d_lut_idx)))
+        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_pbs_batch_dev needs device pointers (got memory the GPU cannot address)");
+    if (count > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "count too large");
+    if (!ctx->peers.empty())
+        return sharded_dev_batch(ctx, RTFHE_COPY, nullptr, d_tlwe, nullptr, d_out, count, (hipStream_t)stream, lut, (const int32_t*)d_lut_idx);
+    return launch_bootstrap(ctx, RTFHE_COPY, MODE_GATE, ctx->p.n, d_tlwe, nullptr, d_out, count, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, 0,
+                            lut_on(lut, 0, (const int32_t*)d_lut_idx));
+}
+
 int rtfhe_sync(rtfhe_ctx* ctx, void* stream) {
     if (int rc = use(ctx)) return rc;
     HIPCHECK(ctx, hipStreamSynchronize((hipStream_t)stream));
     // netlist waves validate their indices on the device; a skipped gate is reported here, once
     int32_t fault = 0;
     HIPCHECK(ctx, hipMemcpy(&fault, ctx->d_fault, 4, hipMemcpyDeviceToHost));
+    if (fault) HIPCHECK(ctx, hipMemset(ctx->d_fault, 0, 4));
+    // the peers' shares of a sharded programmable bootstrap check their table indices on their own devices (the caller's stream has waited for them)
+    for (rtfhe_ctx* peer : ctx->peers) {
+        int32_t f = 0;
+        HIPCHECK(ctx, hipSetDevice(peer->device));
+        HIPCHECK(ctx, hipMemcpy(&f, peer->d_fault, 4, hipMemcpyDeviceToHost));
+        if (f) HIPCHECK(ctx, hipMemset(peer->d_fault, 0, 4));
+        fault |= f;
+    }
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
     if (fault) {
-        HIPCHECK(ctx, hipMemset(ctx->d_fault, 0, 4));
-        return fail(ctx, RTFHE_ERR_INVALID, "netlist wave: wire index or opcode out of range (those gates were skipped)");
+        return fail(ctx, RTFHE_ERR_INVALID, "netlist wave: wire index or opcode out of range, or programmable bootstrap: table index out of range "
+                                            "(those gates were skipped)");
     }
     return 0;
 }

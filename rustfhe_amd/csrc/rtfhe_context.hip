@@ -66,6 +66,16 @@ int ensure(rtfhe_ctx* ctx, void** ptr, size_t* cap, size_t bytes) {
     return 0;
 }
 
+void lut_release(rtfhe_lut* lut) {
+    rtfhe_ctx* ctx = lut->ctx;
+    for (size_t d = 0; d < lut->d_tv.size(); d++) {
+        (void)hipSetDevice(d ? ctx->peers[d - 1]->device : ctx->device);
+        (void)hipFree(lut->d_tv[d]);
+    }
+    lut->d_tv.clear();
+    (void)hipSetDevice(ctx->device);
+}
+
 int allow_lds_raw(rtfhe_ctx* ctx, const void* key, size_t bytes) {
     auto it = ctx->lds_allowed.find(key);
     if (it != ctx->lds_allowed.end() && it->second >= bytes) return 0;          // this context has already seen >= bytes granted
@@ -322,6 +332,10 @@ extern "C" int rtfhe_debug_read_wg_times(rtfhe_ctx* ctx, unsigned long long* out
 
 void rtfhe_ctx_destroy(rtfhe_ctx* ctx) {
     if (!ctx) return;
+    // tables that outlive their context: their device copies go now (while the peers' devices are still known), the handles stay valid
+    // for rtfhe_lut_destroy (which then only frees them) and the PBS calls (which then fail with RTFHE_ERR_STATE)
+    for (rtfhe_lut* l : ctx->luts) { lut_release(l); l->ctx = nullptr; }
+    ctx->luts.clear();
     for (rtfhe_ctx* peer : ctx->peers) rtfhe_ctx_destroy(peer);
     ctx->peers.clear();
     (void)hipSetDevice(ctx->device);

@@ -13,102 +13,82 @@ using namespace rtfhe_host;
 
 namespace {
 
-template <int LOGN, int W>
-int launch_bootstrap_w(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
-    auto k = k_bootstrap<LOGN, 3, 6, 8, 2, KSQ, W>;
-    const size_t lds = bootstrap_lds_bytes<LOGN>(W, a.npad, bootstrap_dual_xbuf(LOGN, W));
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    const int grid = (a.count + W - 1) / W;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * W), lds, s, a);
+// One launch of a kernel family: the gate kernel (k_bootstrap_*) or, for a programmable bootstrap (lut.tv set), its twin (k_pbs_*) with the
+// family's own arguments wrapped in LutArgs.  The twins share shapes, LDS and key layouts, so every choice below is made once for both.
+template <typename A, typename KG, typename KP>
+int launch_twin(rtfhe_ctx* ctx, KG kg, KP kp, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A& a, const LutRef& lut) {
+    if (lut.tv) {
+        if (int rc = allow_lds(ctx, kp, lds)) return rc;
+        const LutArgs<A> p{a, lut.tv, lut.idx, lut.n_tv};
+        hipLaunchKernelGGL(kp, grid, block, lds, s, p);
+    } else {
+        if (int rc = allow_lds(ctx, kg, lds)) return rc;
+        hipLaunchKernelGGL(kg, grid, block, lds, s, a);
+    }
     HIPCHECK(ctx, hipGetLastError());
     ctx->launches++;
     return 0;
 }
 
-int launch_bootstrap_wg10(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
-    auto k = k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>;
-    const size_t lds = WgLds<10, 3>::bytes(a.npad);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    hipLaunchKernelGGL(k, dim3(a.count), dim3(512), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
+template <int LOGN, int W>
+int launch_bootstrap_w(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
+    const size_t lds = bootstrap_lds_bytes<LOGN>(W, a.npad, bootstrap_dual_xbuf(LOGN, W));
+    const int grid = (a.count + W - 1) / W;
+    return launch_twin(ctx, k_bootstrap<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs<LOGN, 3, 6, 8, 2, KSQ, W>, dim3(grid), dim3(64 * W), lds, s, a, lut);
+}
+
+int launch_bootstrap_wg10(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
+    return launch_twin(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_wg<10, 3, 6, 8, 2, KSQ>, dim3(a.count), dim3(512), WgLds<10, 3>::bytes(a.npad), s, a, lut);
 }
 
 template <int GATES>
-int launch_bootstrap_pair10_g(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
-    auto k = k_bootstrap_pair<3, 6, 8, 2, KSQ, GATES>;
-    const size_t lds = PairLds::bytes(GATES, a.npad);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    hipLaunchKernelGGL(k, dim3((a.count + GATES - 1) / GATES), dim3(128 * GATES), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
+int launch_bootstrap_pair10_g(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
+    return launch_twin(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_pair<3, 6, 8, 2, KSQ, GATES>, dim3((a.count + GATES - 1) / GATES), dim3(128 * GATES),
+                       PairLds::bytes(GATES, a.npad), s, a, lut);
 }
-int launch_bootstrap_pair10(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) { return launch_bootstrap_pair10_g<4>(ctx, a, s); }
+int launch_bootstrap_pair10(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) { return launch_bootstrap_pair10_g<4>(ctx, a, s, lut); }
 // 4 x CUs < count <= rr x CUs gates on the four wave pairs of every CU, time-sliced (rtfhe_kernels_pair_rr.hpp)
 bool rr_applies(const rtfhe_ctx* ctx, size_t count) {
     const size_t cus = (size_t)ctx->num_cus, round = 4 * cus, rem = count % round;
     const int rr = ctx->rr > PairRrLds::GMAX ? PairRrLds::GMAX : ctx->rr;
     return rr > 4 && !ctx->force_waves && count > round && rem != 0 && round + rem <= (size_t)rr * cus;
 }
-int launch_bootstrap_pair_rr(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
-    auto k = k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>;
+int launch_bootstrap_pair_rr(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
     const int wgs = ctx->num_cus, most = (a.count + wgs - 1) / wgs;
     if (a.count < 4 * wgs || most > PairRrLds::GMAX)
         return fail(ctx, RTFHE_ERR_STATE, "k_bootstrap_pair_rr: " + std::to_string(a.count) + " gates on " + std::to_string(wgs) + " CUs is not a shape it serves");
-    const size_t lds = PairRrLds::bytes(most, a.npad);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    hipLaunchKernelGGL(k, dim3(wgs), dim3(512), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
+    return launch_twin(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_pair_rr<3, 6, 8, 2, KSQ>, dim3(wgs), dim3(512), PairRrLds::bytes(most, a.npad), s, a, lut);
 }
 // four waves per gate, (polynomial, parity): up to two gates per CU (rtfhe_kernels_pair4.hpp); no fused key switch
 template <int GATES>
-int launch_bootstrap_pair4_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s) {
-    auto k = k_bootstrap_pair4<3, 6, GATES>;
-    const size_t lds = Pair4Lds::bytes(GATES, b.npad);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    Pair4Args a{b, ctx->d_p4bk};
-    hipLaunchKernelGGL(k, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
+int launch_bootstrap_pair4_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
+    const Pair4Args a{b, ctx->d_p4bk};
+    return launch_twin(ctx, k_bootstrap_pair4<3, 6, GATES>, k_pbs_pair4<3, 6, GATES>, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES),
+                       Pair4Lds::bytes(GATES, b.npad), s, a, lut);
 }
 
 // N = 2048: two waves per transform, split by the parity of the point index (rtfhe_kernels_eo.hpp)
 template <int GATES>
-int launch_bootstrap_eo11_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s) {
-    auto k = k_bootstrap_eo<3, 6, 8, 2, KSQ, GATES>;
-    const size_t lds = EoLds::bytes(GATES, b.npad);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    EoArgs a{b, ctx->d_etw, ctx->d_ebk};
-    hipLaunchKernelGGL(k, dim3((b.count + GATES - 1) / GATES), dim3(128 * GATES), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
+int launch_bootstrap_eo11_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
+    const EoArgs a{b, ctx->d_etw, ctx->d_ebk};
+    return launch_twin(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_eo<3, 6, 8, 2, KSQ, GATES>, dim3((b.count + GATES - 1) / GATES), dim3(128 * GATES),
+                       EoLds::bytes(GATES, b.npad), s, a, lut);
 }
 // four waves per gate, (polynomial, parity): batches of up to two gates per CU (rtfhe_kernels_eo4.hpp); no fused key switch
 template <int GATES>
-int launch_bootstrap_eo4_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s) {
-    auto k = k_bootstrap_eo4<3, 6, GATES>;
-    const size_t lds = Eo4Lds::bytes(GATES, b.npad);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    EoArgs a{b, ctx->d_etw, ctx->d_ebk};
-    hipLaunchKernelGGL(k, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
+int launch_bootstrap_eo4_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
+    const EoArgs a{b, ctx->d_etw, ctx->d_ebk};
+    return launch_twin(ctx, k_bootstrap_eo4<3, 6, GATES>, k_pbs_eo4<3, 6, GATES>, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES),
+                       Eo4Lds::bytes(GATES, b.npad), s, a, lut);
 }
 template <int GATES>
-int launch_bootstrap_n2048_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s) {
+int launch_bootstrap_n2048_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
     // up to two gates per CU: four waves per gate, so that no SIMD is left with a lone wave (single gate 9.78 -> 5.84 ms, 512 gates 9.91 -> 7.8 ms,
     // profiles/r04/n2048_four_waves_per_gate_ab.log); the fused key switch and a forced split stay on the two-wave kernels
     if constexpr (GATES <= 2) {
-        if (ctx->eo4 && (b.mode == MODE_EXTRACT || b.mode == MODE_BLIND_ROTATE)) return launch_bootstrap_eo4_g<GATES>(ctx, b, s);
+        if (ctx->eo4 && (b.mode == MODE_EXTRACT || b.mode == MODE_BLIND_ROTATE)) return launch_bootstrap_eo4_g<GATES>(ctx, b, s, lut);
     }
-    return launch_bootstrap_eo11_g<GATES>(ctx, b, s);
+    return launch_bootstrap_eo11_g<GATES>(ctx, b, s, lut);
 }
 
 // Kernel shape by batch size (N = 1024), measured in profiles/r01_pair/shape_sweep.log:
@@ -118,16 +98,19 @@ int launch_bootstrap_n2048_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s) {
 //                                    gate still has its two waves, which then share their SIMDs with fewer (or no) other waves
 //   a larger remainder             : one more (partly filled) round of 4 gates per CU
 // The segments are queued back to back on the caller's stream.  RTFHE_FORCE_WAVES=1|2|4|8 forces one shape for the
-// whole batch (4, 8: one gate per wave in 4- / 8-wave workgroups).
+// whole batch (4, 8: one gate per wave in 4- / 8-wave workgroups).  A programmable bootstrap takes the same shapes on the k_pbs_* twins;
+// its table indices travel with the ciphertexts of each segment.
 template <int LOGN>
-int launch_bootstrap_t(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
+int launch_bootstrap_t(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
+    auto seg = [&](size_t off, size_t cnt, size_t out_words) { return batch_segment(ctx, a, off, cnt, out_words); };
+    auto rotate = [&lut](rtfhe_ctx* c, BootstrapArgs b, hipStream_t st) { return launch_bootstrap_t<LOGN>(c, b, st, lut); };
     if constexpr (LOGN == 10) {
         const int force = ctx->force_waves;
-        if (force == 1) return launch_bootstrap_wg10(ctx, a, s);
-        if (force == 2) return launch_bootstrap_pair10(ctx, a, s);
-        if (force == 8) return launch_bootstrap_w<10, 8>(ctx, a, s);
-        if (force == 4) return launch_bootstrap_w<10, 4>(ctx, a, s);
-        if (split_ok(ctx, a, s)) return launch_split(ctx, a, s, launch_bootstrap_t<10>);     // comes back here in MODE_EXTRACT
+        if (force == 1) return launch_bootstrap_wg10(ctx, a, s, lut);
+        if (force == 2) return launch_bootstrap_pair10(ctx, a, s, lut);
+        if (force == 8) return launch_bootstrap_w<10, 8>(ctx, a, s, lut);
+        if (force == 4) return launch_bootstrap_w<10, 4>(ctx, a, s, lut);
+        if (split_ok(ctx, a, s)) return launch_split(ctx, a, s, rotate);     // comes back here in MODE_EXTRACT
         const size_t out_words = mode_out_words(a, 1 << LOGN);
         const size_t round = (size_t)4 * ctx->num_cus, count = (size_t)a.count;
         const size_t full = count / round * round, rem = count - full;
@@ -138,37 +121,39 @@ int launch_bootstrap_t(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
             // the last whole round and the remainder as ONE launch of five or six gates per CU: (4 + rem / CUs) / 4 rounds instead of 2
             // (1,280 gates 9.3 -> 8.2 ms; profiles/r06/pair_rr_sweep.log)
             if (full > round)
-                if (int rc = launch_bootstrap_pair10(ctx, batch_segment(ctx, a, 0, full - round, out_words), s)) return rc;
-            return launch_bootstrap_pair_rr(ctx, batch_segment(ctx, a, full - round, round + rem, out_words), s);
+                if (int rc = launch_bootstrap_pair10(ctx, seg(0, full - round, out_words), s, lut)) return rc;
+            return launch_bootstrap_pair_rr(ctx, seg(full - round, round + rem, out_words), s, lut_segment(lut, full - round));
         }
         if (full)
-            if (int rc = launch_bootstrap_pair10(ctx, batch_segment(ctx, a, 0, full, out_words), s)) return rc;
+            if (int rc = launch_bootstrap_pair10(ctx, seg(0, full, out_words), s, lut)) return rc;
         if (rem) {
-            const BootstrapArgs tail = batch_segment(ctx, a, full, rem, out_words);
-            if (rem <= (size_t)ctx->wg_max) return launch_bootstrap_wg10(ctx, tail, s);
-            if (rem <= (size_t)2 * ctx->num_cus) return (p4 && ctx->pair4 >= 2) ? launch_bootstrap_pair4_g<2>(ctx, tail, s) : launch_bootstrap_pair10_g<2>(ctx, tail, s);
-            if (rem <= (size_t)3 * ctx->num_cus) return (p4 && ctx->pair4 >= 3) ? launch_bootstrap_pair4_g<3>(ctx, tail, s) : launch_bootstrap_pair10_g<3>(ctx, tail, s);
-            return launch_bootstrap_pair10(ctx, tail, s);
+            const BootstrapArgs tail = seg(full, rem, out_words);
+            const LutRef tl = lut_segment(lut, full);
+            if (rem <= (size_t)ctx->wg_max) return launch_bootstrap_wg10(ctx, tail, s, tl);
+            if (rem <= (size_t)2 * ctx->num_cus) return (p4 && ctx->pair4 >= 2) ? launch_bootstrap_pair4_g<2>(ctx, tail, s, tl) : launch_bootstrap_pair10_g<2>(ctx, tail, s, tl);
+            if (rem <= (size_t)3 * ctx->num_cus) return (p4 && ctx->pair4 >= 3) ? launch_bootstrap_pair4_g<3>(ctx, tail, s, tl) : launch_bootstrap_pair10_g<3>(ctx, tail, s, tl);
+            return launch_bootstrap_pair10(ctx, tail, s, tl);
         }
         return 0;
     } else {
         // two waves per transform (two waves per SIMD, no AGPR traffic); RTFHE_FORCE_WAVES=4 selects one wave per gate
         // (inverse pass-1/untwist twiddles in global memory: 4 gates per CU fit)
-        if (!(ctx->d_etw && ctx->ebk_valid) || ctx->force_waves == 4) return launch_bootstrap_w<11, 4>(ctx, a, s);
+        if (!(ctx->d_etw && ctx->ebk_valid) || ctx->force_waves == 4) return launch_bootstrap_w<11, 4>(ctx, a, s, lut);
         // whole rounds of 4 gates per CU in one launch; a remainder with 1 / 2 / 3 gates per workgroup, one workgroup per CU
         // (a gate's two waves then share their SIMDs with fewer other waves: a single gate takes 0.67 x a full round)
-        if (split_ok(ctx, a, s)) return launch_split(ctx, a, s, launch_bootstrap_t<11>);
+        if (split_ok(ctx, a, s)) return launch_split(ctx, a, s, rotate);
         const size_t out_words = mode_out_words(a, 1 << LOGN);
         const size_t cus = (size_t)ctx->num_cus, round = 4 * cus, count = (size_t)a.count;
         const size_t full = count / round * round, rem = count - full;
         if (full)
-            if (int rc = launch_bootstrap_n2048_g<4>(ctx, batch_segment(ctx, a, 0, full, out_words), s)) return rc;
+            if (int rc = launch_bootstrap_n2048_g<4>(ctx, seg(0, full, out_words), s, lut)) return rc;
         if (!rem) return 0;
-        const BootstrapArgs tail = batch_segment(ctx, a, full, rem, out_words);
-        if (rem <= cus) return launch_bootstrap_n2048_g<1>(ctx, tail, s);
-        if (rem <= 2 * cus) return launch_bootstrap_n2048_g<2>(ctx, tail, s);
-        if (rem <= 3 * cus) return launch_bootstrap_n2048_g<3>(ctx, tail, s);
-        return launch_bootstrap_n2048_g<4>(ctx, tail, s);
+        const BootstrapArgs tail = seg(full, rem, out_words);
+        const LutRef tl = lut_segment(lut, full);
+        if (rem <= cus) return launch_bootstrap_n2048_g<1>(ctx, tail, s, tl);
+        if (rem <= 2 * cus) return launch_bootstrap_n2048_g<2>(ctx, tail, s, tl);
+        if (rem <= 3 * cus) return launch_bootstrap_n2048_g<3>(ctx, tail, s, tl);
+        return launch_bootstrap_n2048_g<4>(ctx, tail, s, tl);
     }
 }
 
@@ -263,8 +248,8 @@ std::vector<cplx> HostTw::q4_table() const {
 
 namespace rtfhe_host {
 
-int launch_bootstrap_fft(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
-    return ctx->logn == 10 ? launch_bootstrap_t<10>(ctx, a, s) : launch_bootstrap_t<11>(ctx, a, s);
+int launch_bootstrap_fft(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
+    return ctx->logn == 10 ? launch_bootstrap_t<10>(ctx, a, s, lut) : launch_bootstrap_t<11>(ctx, a, s, lut);
 }
 
 // The key spectra once more in the layout a kernel family reads (derived from d_bk on this context's device), built by the first batch whose
@@ -311,14 +296,19 @@ int rebuild_derived_keys(rtfhe_ctx* ctx) {
     return 0;
 }
 
-// grants every bootstrap kernel of this context's parameter set its dynamic LDS once, at context creation
+// grants every bootstrap kernel of this context's parameter set, and its programmable-bootstrap twin, its dynamic LDS once, at context creation
+template <typename KG, typename KP>
+static int allow_twins(rtfhe_ctx* ctx, KG kg, KP kp, size_t bytes) {
+    if (int rc = allow_lds(ctx, kg, bytes)) return rc;
+    return allow_lds(ctx, kp, bytes);
+}
 int prime_fft_kernels(rtfhe_ctx* ctx) {
     const int npad = (ctx->p.n + 1 + 63) / 64 * 64;
     if (ctx->logn == 10) {
-        if (int rc = allow_lds(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 4>, PairLds::bytes(4, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 3>, PairLds::bytes(3, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 2>, PairLds::bytes(2, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, WgLds<10, 3>::bytes(npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_pair<3, 6, 8, 2, KSQ, 4>, PairLds::bytes(4, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_pair<3, 6, 8, 2, KSQ, 3>, PairLds::bytes(3, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_pair<3, 6, 8, 2, KSQ, 2>, PairLds::bytes(2, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_wg<10, 3, 6, 8, 2, KSQ>, WgLds<10, 3>::bytes(npad))) return rc;
         // the time-sliced launch: as many gates per CU (five or six) as this mask length leaves room for in 160 KiB of LDS
         {
             int fit = 0;
@@ -326,20 +316,20 @@ int prime_fft_kernels(rtfhe_ctx* ctx) {
                 if (PairRrLds::bytes(g, npad) <= (size_t)160 * 1024) fit = g;
             if (ctx->rr > fit) ctx->rr = fit;
             if (ctx->rr >= 5)
-                if (int rc = allow_lds(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, PairRrLds::bytes(ctx->rr, npad))) return rc;
+                if (int rc = allow_twins(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_pair_rr<3, 6, 8, 2, KSQ>, PairRrLds::bytes(ctx->rr, npad))) return rc;
         }
-        if (int rc = allow_lds(ctx, k_bootstrap_pair4<3, 6, 3>, Pair4Lds::bytes(3, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_pair4<3, 6, 2>, Pair4Lds::bytes(2, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 4>, bootstrap_lds_bytes<10>(4, npad, bootstrap_dual_xbuf(10, 4)))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 8>, bootstrap_lds_bytes<10>(8, npad, bootstrap_dual_xbuf(10, 8)))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair4<3, 6, 3>, k_pbs_pair4<3, 6, 3>, Pair4Lds::bytes(3, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair4<3, 6, 2>, k_pbs_pair4<3, 6, 2>, Pair4Lds::bytes(2, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 4>, k_pbs<10, 3, 6, 8, 2, KSQ, 4>, bootstrap_lds_bytes<10>(4, npad, bootstrap_dual_xbuf(10, 4)))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 8>, k_pbs<10, 3, 6, 8, 2, KSQ, 8>, bootstrap_lds_bytes<10>(8, npad, bootstrap_dual_xbuf(10, 8)))) return rc;
     } else {
-        if (int rc = allow_lds(ctx, k_bootstrap<11, 3, 6, 8, 2, KSQ, 4>, bootstrap_lds_bytes<11>(4, npad, bootstrap_dual_xbuf(11, 4)))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 4>, EoLds::bytes(4, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 3>, EoLds::bytes(3, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 2>, EoLds::bytes(2, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 1>, EoLds::bytes(1, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_eo4<3, 6, 2>, Eo4Lds::bytes(2, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_eo4<3, 6, 1>, Eo4Lds::bytes(1, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap<11, 3, 6, 8, 2, KSQ, 4>, k_pbs<11, 3, 6, 8, 2, KSQ, 4>, bootstrap_lds_bytes<11>(4, npad, bootstrap_dual_xbuf(11, 4)))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_eo<3, 6, 8, 2, KSQ, 4>, EoLds::bytes(4, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_eo<3, 6, 8, 2, KSQ, 3>, EoLds::bytes(3, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_eo<3, 6, 8, 2, KSQ, 2>, EoLds::bytes(2, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_eo<3, 6, 8, 2, KSQ, 1>, EoLds::bytes(1, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo4<3, 6, 2>, k_pbs_eo4<3, 6, 2>, Eo4Lds::bytes(2, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo4<3, 6, 1>, k_pbs_eo4<3, 6, 1>, Eo4Lds::bytes(1, npad))) return rc;
     }
     return 0;
 }

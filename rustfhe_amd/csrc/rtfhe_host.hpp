@@ -48,6 +48,7 @@ struct HostTw {
 };
 
 struct rtfhe_circuit;
+struct rtfhe_lut;
 struct rtfhe_ctx {
     rtfhe_params p{};
     int device = 0;
@@ -113,6 +114,7 @@ struct rtfhe_ctx {
     // the set.  Keys are loaded once on this context and copied device-to-device; batches are sharded (rtfhe_multi.hip).
     std::vector<rtfhe_ctx*> peers;
     std::vector<rtfhe_circuit*> circuits;   // live HIP-graph circuits of this context: orphaned (not freed) by rtfhe_ctx_destroy
+    std::vector<rtfhe_lut*> luts;           // live PBS tables of this context (primary only): their device copies go with it, the handles stay
     // device intermediates (i1, i0) of a MUX batch: one pair per stream a MUX batch was ever launched on, as the lvl1 samples above (two MUX
     // batches on different streams of one context may overlap).  A pair whose addresses went into a caller's capture is never freed or replaced
     // while the context lives (`captured`): a later, larger eager batch on that stream gets a new pair and the old one moves to mux_retired.
@@ -138,9 +140,24 @@ struct rtfhe_circuit {
     bool stale = false;        // recorded on an exact backend whose key form could not follow a key change (rebuild_derived_keys)
 };
 
+// the test polynomials of a programmable bootstrap (rtfhe_lut_create), one copy on every entry of the context
+struct rtfhe_lut {
+    rtfhe_ctx* ctx = nullptr;           // the primary; null once the context has been destroyed (the handle then only remains to be freed)
+    std::vector<uint32_t*> d_tv;        // [entry] u32[n_lut][N] on entry d of the context (0: the primary, d: peers[d - 1])
+    int32_t n_lut = 0;
+};
+
 namespace rtfhe_host {
 
 using rtfhe::BootstrapArgs;
+
+// what a bootstrap launch reads its test polynomials from: tv null = the gates' own (k_bootstrap_*), else the k_pbs_* twins with table
+// idx[g] of tv (idx null: table 0) for gate g of the launch
+struct LutRef { const uint32_t* tv = nullptr; const int32_t* idx = nullptr; int32_t n_tv = 0; };
+inline LutRef lut_segment(LutRef l, size_t off) { if (l.idx) l.idx += off; return l; }     // ... for the segment starting at gate `off`
+inline LutRef lut_on(const rtfhe_lut* lut, int entry, const int32_t* d_idx) {
+    return lut ? LutRef{lut->d_tv[entry], d_idx, lut->n_lut} : LutRef{};
+}
 using rtfhe::cplx;
 
 constexpr int KSQ = 3;        // uint4 loads per lane per key-switch row: rows up to 768 words
@@ -171,6 +188,7 @@ bool is_pinned_host(const void* p);
 int copy_in(rtfhe_ctx* ctx, void* dst, const void* src, size_t bytes, int slot);      // host -> device on ctx->stream
 int copy_out(rtfhe_ctx* ctx, void* dst, const void* src, size_t bytes, int slot);     // device -> host on ctx->stream, synchronous on return
 void circuit_release(rtfhe_circuit* c);                                   // rtfhe_circuit.hip
+void lut_release(rtfhe_lut* lut);                                         // frees a table's device copies (rtfhe_context.hip)
 
 // ---- twiddles (rtfhe_twiddles.hip) ----
 bool unit_twiddles_ok(const HostTw& tw);
@@ -178,7 +196,7 @@ int upload_twiddles(rtfhe_ctx* ctx);
 
 // ---- FP64 mirror backend (rtfhe_dispatch_fft.hip) ----
 int prime_fft_kernels(rtfhe_ctx* ctx);                                    // grants every bootstrap kernel of the parameter set its dynamic LDS
-int launch_bootstrap_fft(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s);
+int launch_bootstrap_fft(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut);
 // builds (outside any stream capture) the second key layouts the dispatch of a `count`-gate batch in `mode` will read; no-op when they stand
 int ensure_bk_layouts(rtfhe_ctx* ctx, size_t count, int mode);
 int rebuild_derived_keys(rtfhe_ctx* ctx);                               // after a key change: every derived key form that already exists, in place, now
@@ -208,10 +226,12 @@ int launch_key_switch_mm(rtfhe_ctx* ctx, const BootstrapArgs& a, const uint32_t*
 // ---- batches (rtfhe_batch.hip) ----
 int launch_bootstrap(rtfhe_ctx* ctx, int op, int mode, int steps, const void* d_in0, const void* d_in1, void* d_out,
                      size_t count, hipStream_t s, const int32_t* d_ops = nullptr, const int32_t* d_idx0 = nullptr,
-                     const int32_t* d_idx1 = nullptr, const int32_t* d_idx_out = nullptr, int32_t num_wires = 0);
+                     const int32_t* d_idx1 = nullptr, const int32_t* d_idx_out = nullptr, int32_t num_wires = 0, const LutRef& lut = LutRef{});
 int ensure_tlwe1(rtfhe_ctx* ctx, rtfhe_ctx::Tlwe1& b, size_t gates);
 int run_host_bootstrap_one(rtfhe_ctx* ctx, int op, int mode, int steps, const uint32_t* in0, const uint32_t* in1, uint32_t* out, size_t count, size_t out_words);
 int mux_host_one(rtfhe_ctx* ctx, const uint32_t* c, const uint32_t* in0, const uint32_t* in1, uint32_t* out, size_t count);
+// a programmable bootstrap of host buffers on one device (lut_idx already checked; null = table 0)
+int run_host_pbs_one(rtfhe_ctx* ctx, const LutRef& lut, const int32_t* lut_idx, const uint32_t* in, uint32_t* out, size_t count);
 int mux_dev_one(rtfhe_ctx* ctx, const void* d_c, const void* d_in0, const void* d_in1, void* d_out, size_t count, hipStream_t s);
 
 // ---- several GPUs (rtfhe_multi.hip) ----
@@ -220,7 +240,10 @@ int replicate(rtfhe_ctx* ctx, rtfhe_ctx* peer, const void* src, void** dst_of_pe
 int sharded_host_bootstrap(rtfhe_ctx* ctx, int op, int mode, int steps, const uint32_t* in0, const uint32_t* in1, uint32_t* out, size_t count, size_t out_words);
 int sharded_host_mux(rtfhe_ctx* ctx, const uint32_t* c, const uint32_t* in0, const uint32_t* in1, uint32_t* out, size_t count);
 // a batch that LIVES ON THE PRIMARY DEVICE, sharded over the context's devices: op < 0 = MUX (d_c, d_in0, d_in1), else a gate batch (d_in0, d_in1)
-int sharded_dev_batch(rtfhe_ctx* ctx, int op, const void* d_c, const void* d_in0, const void* d_in1, void* d_out, size_t count, hipStream_t s);
+// (lut: a programmable bootstrap, op = RTFHE_COPY, d_lut_idx its int32[count] indices on the primary or null)
+int sharded_dev_batch(rtfhe_ctx* ctx, int op, const void* d_c, const void* d_in0, const void* d_in1, void* d_out, size_t count, hipStream_t s,
+                      const rtfhe_lut* lut = nullptr, const int32_t* d_lut_idx = nullptr);
+int sharded_host_pbs(rtfhe_ctx* ctx, const rtfhe_lut* lut, const int32_t* lut_idx, const uint32_t* in, uint32_t* out, size_t count);
 
 // words per gate of the output buffer, by mode (MODE_EXTRACT: the final TLWE rows; the lvl1 samples go to `ext`)
 inline size_t mode_out_words(const BootstrapArgs& a, int N) { return a.mode == rtfhe::MODE_BLIND_ROTATE ? (size_t)2 * N : (size_t)a.n + 1; }

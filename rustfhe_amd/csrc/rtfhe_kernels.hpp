@@ -95,6 +95,56 @@ __device__ __forceinline__ GateIo gate_io(const BootstrapArgs& a, int g) {
     return io;
 }
 
+// Where the accumulator of gate g starts: acc = X^{-bbar} * (tv, 0), coefficient c = tv_word<LOGN>(row, (c + bbar) mod 2N).  Every bootstrap
+// kernel family has one body (rtfhe_body_*.hpp) included into two __global__ entries that differ only in this source: k_bootstrap_* with
+// TvGate, the gates' test vector (1/8, ..., 1/8) -- its row is always valid and its words are constants, so those kernels compile to what
+// they were before the twins existed -- and k_pbs_* with TvLut, the programmable bootstrap's caller-supplied tables (include/rtfhe.h).
+struct TvGate {
+    struct Row { __device__ __forceinline__ bool ok() const { return true; } };
+};
+__device__ __forceinline__ TvGate::Row tv_row(const TvGate&, int, int) { return TvGate::Row{}; }
+template <int LOGN>
+__device__ __forceinline__ uint32_t tv_word(const TvGate::Row&, int e) { return (e >> LOGN) ? 0xE0000000u : 0x20000000u; }
+
+// the k_pbs_* kernels' arguments: the family's own struct, unchanged (its kernarg offsets stay those of the k_bootstrap_* twin), then the tables
+template <typename A>
+struct LutArgs {
+    A base;
+    const uint32_t* tv;        // [n_tv][N] test polynomials
+    const int32_t* tv_idx;     // [count] the table of gate g (null: table 0 for every gate)
+    int32_t n_tv;
+};
+// A gate whose index lies outside [0, n_tv) is skipped like a netlist gate with a bad wire (it runs on table 0 and stores nothing) and
+// reported through *fault.  The index is read once per gate before the pre-step (and once more in k_bootstrap_pair_rr's epilogue).
+struct TvLut {
+    const uint32_t* tv; const int32_t* idx; int32_t n_tv; int32_t* fault;
+    struct Row {
+        const uint32_t* p; bool good;
+        __device__ __forceinline__ bool ok() const { return good; }
+    };
+};
+__device__ __forceinline__ TvLut::Row tv_row(const TvLut& t, int g, int N) {
+    const int k = t.idx ? t.idx[g] : 0;
+    const bool good = (unsigned)k < (unsigned)t.n_tv;
+    if (!good && t.fault) *t.fault = 1;
+    return TvLut::Row{t.tv + (size_t)(good ? k : 0) * N, good};
+}
+// where and whether gate g stores, for a body that derives it again after the step loop (k_bootstrap_pair_rr's epilogue): gate_io's rule,
+// and for a programmable bootstrap also the table index's (an extra term in the gate kernel's own expression would change its code)
+__device__ __forceinline__ GateIo gate_io(const BootstrapArgs& a, int g, const TvGate&) { return gate_io(a, g); }
+__device__ __forceinline__ GateIo gate_io(const BootstrapArgs& a, int g, const TvLut& t) {
+    GateIo io = gate_io(a, g);
+    if (!tv_row(t, g, 0).ok()) io.ok = false;
+    return io;
+}
+template <int LOGN>
+__device__ __forceinline__ uint32_t tv_word(const TvLut::Row& r, int e) {      // the negacyclic extension: X^N = -1
+    const uint32_t v = r.p[e & ((1 << LOGN) - 1)];
+    return (e >> LOGN) ? 0u - v : v;
+}
+template <typename A>
+__device__ __forceinline__ TvLut tv_lut(const LutArgs<A>& p, int32_t* fault) { return TvLut{p.tv, p.tv_idx, p.n_tv, fault}; }
+
 // One external product / CMUX on the wave-private accumulator in LDS.
 //   CMUX = true : acc <- cross(bk_i, X^r * acc - acc) + acc      (trgsw.rs:319-321, tfhe.rs:103-110)
 //   CMUX = false: acc <- cross(bk_i, acc)                          (trgsw.rs:264-306)
@@ -286,78 +336,14 @@ __host__ __device__ constexpr size_t bootstrap_lds_bytes(int waves, int npad, bo
 // of `count` independent gates in ONE launch; wave w of block b owns gate b * WAVES + w from start to end.
 template <int LOGN, int L, int BGBIT, int KS_T, int KS_BB, int KSQ, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_bootstrap(const BootstrapArgs a) {
-    typedef Geo<LOGN> G;
-    constexpr int N = G::N, R = G::R;
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    cplx* tw = reinterpret_cast<cplx*>(smem);
-    TwStage<LOGN>::stage(tw, a.tw, tid, 64 * WAVES);
-    __syncthreads();
-    // from here on waves never synchronise with each other
-
-    const int g = blockIdx.x * WAVES + wave;
-    if (g >= a.count) return;
-
-    constexpr bool DUAL = bootstrap_dual_xbuf(LOGN, WAVES);
-    unsigned char* wbase = smem + (size_t)TwStage<LOGN>::LDS_CPLX * sizeof(cplx) + (size_t)wave * bootstrap_wave_lds_bytes<LOGN>(a.npad, DUAL);
-    double* xbuf = reinterpret_cast<double*>(wbase);
-    uint32_t* accbuf = reinterpret_cast<uint32_t*>(wbase + (size_t)G::XSLOTS * sizeof(double) * (DUAL ? 2 : 1));
-    uint32_t* abar = accbuf + 2 * N;
-    const cplx* twf = TwStage<LOGN>::fwd(tw);
-    const cplx* twi = TwStage<LOGN>::inv_small(tw);
-    const cplx* twi_big = TwStage<LOGN>::inv_big(tw, a.tw);
-
-    const int n = a.n;
-    // pre-step + mod switch (tfhe.rs:97, 107-108): b floor, a_i rounded, both to [0, 2N)
-    const GateIo io = gate_io(a, g);
-    if (!io.ok) return;
-    {
-        constexpr int SH = 32 - LOGN - 1;
-        for (int i = lane; i <= n; i += 64) {
-            const uint32_t t = gate_linear(io.op, io.p0[i], io.p1[i], i == n);
-            abar[i] = (i == n) ? (t >> SH) : ((t + (1u << (SH - 1))) >> SH);
-        }
-    }
-    wave_lds_sync();
-    // acc = X^{-bbar} * testvec, testvec = (1/8, ..., 1/8 ; 0)   (tfhe.rs:85, 98-106)
-    {
-        const int bbar = (int)abar[n];
-#pragma unroll
-        for (int mm = 0; mm < 2 * R; mm++) {
-            const int c = lane + 64 * mm;
-            const int e = (c + bbar) & (2 * N - 1);
-            accbuf[c] = (e >> LOGN) ? 0xE0000000u : 0x20000000u;
-            accbuf[N + c] = 0u;
-        }
-    }
-    wave_lds_sync();
-
-    const size_t trgsw_cplx = (size_t)2 * L * 2 * R * 64;
-#pragma unroll 1
-    for (int i = 0; i < a.steps; i++) {
-        const int r = __builtin_amdgcn_readfirstlane((int)abar[i]);
-        cmux_step<LOGN, L, BGBIT, true, DUAL>(accbuf, r, a.bk + (size_t)i * trgsw_cplx, twf, twi, twi_big, xbuf, lane);
-    }
-
-    if (a.mode == MODE_BLIND_ROTATE) {
-        uint32_t* o = a.out + (size_t)g * 2 * N;
-        for (int c = lane; c < 2 * N; c += 64) o[c] = accbuf[c];
-        return;
-    }
-
-    // sample extract index 0 (trlwe.rs:110-121): a'_0 = a_0, a'_k = -a_{N-k}; b' = b_0
-    uint32_t av[2 * R];
-#pragma unroll
-    for (int mm = 0; mm < 2 * R; mm++) av[mm] = accbuf[N + lane + 64 * mm];
-    const uint32_t bprime = accbuf[0];
-    wave_lds_sync();
-#pragma unroll
-    for (int mm = 0; mm < 2 * R; mm++) {
-        const int c = lane + 64 * mm;
-        accbuf[N + ((N - c) & (N - 1))] = (c == 0) ? av[mm] : (0u - av[mm]);
-    }
-    wave_lds_sync();
-    key_switch_wave<LOGN, KS_T, KS_BB, KSQ>(accbuf + N, bprime, a.ksk, a.ksw, n, io.out, lane);
+    const TvGate tvs{};
+#include "rtfhe_body_wave.hpp"
+}
+template <int LOGN, int L, int BGBIT, int KS_T, int KS_BB, int KSQ, int WAVES>
+__global__ __launch_bounds__(64 * WAVES, 1) void k_pbs(const LutArgs<BootstrapArgs> p) {
+    const BootstrapArgs& a = p.base;
+    const TvLut tvs = tv_lut(p, a.fault);
+#include "rtfhe_body_wave.hpp"
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -235,6 +235,12 @@ int encrypt_bits(const rtfhe_params* p, Rng& r, const int32_t* key0, const uint8
     return 0;
 }
 
+// the same with the plaintext torus words given directly (multi-bit messages for the programmable bootstrap)
+int encrypt_torus(const rtfhe_params* p, Rng& r, const int32_t* key0, const uint32_t* mu, uint32_t* out, size_t count) {
+    for (size_t g = 0; g < count; g++) tlwe_encrypt(r, p->n, key0, mu[g], 1.0f / 32768.0f, out + g * ((size_t)p->n + 1));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -267,6 +273,14 @@ int rtfhe_tlwe_encrypt_bits(const rtfhe_params* p, const int32_t* key0, const ui
     return encrypt_bits(p, r, key0, bits, out, count);
 }
 
+int rtfhe_tlwe_encrypt_torus(const rtfhe_params* p, const int32_t* key0, const uint32_t* mu, uint32_t* out, size_t count) {
+    if (!valid(p) || !key0 || !mu || !out) return RTFHE_ERR_INVALID;
+    Source src;
+    if (!Source::from_os(src)) return RTFHE_ERR_STATE;
+    ChaCha r(src.key, 0);
+    return encrypt_torus(p, r, key0, mu, out, count);
+}
+
 int rtfhe_ksk_expand_ref(const rtfhe_params* p, const int32_t* key0, const int32_t* key1, const uint32_t* ksk, uint32_t* ksk_ref) {
     if (!valid(p) || !key0 || !key1 || !ksk || !ksk_ref) return RTFHE_ERR_INVALID;
     Source src;
@@ -297,6 +311,12 @@ int rtfhe_tlwe_encrypt_bits_deterministic(const rtfhe_params* p, const int32_t* 
     if (!valid(p) || !key0 || !bits || !out) return RTFHE_ERR_INVALID;
     Xoshiro r(seed);
     return encrypt_bits(p, r, key0, bits, out, count);
+}
+
+int rtfhe_tlwe_encrypt_torus_deterministic(const rtfhe_params* p, const int32_t* key0, uint64_t seed, const uint32_t* mu, uint32_t* out, size_t count) {
+    if (!valid(p) || !key0 || !mu || !out) return RTFHE_ERR_INVALID;
+    Xoshiro r(seed);
+    return encrypt_torus(p, r, key0, mu, out, count);
 }
 
 int rtfhe_tlwe_phase(const rtfhe_params* p, const int32_t* key0, const uint32_t* in, uint32_t* phase, size_t count) {

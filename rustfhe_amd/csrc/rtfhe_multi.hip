@@ -59,6 +59,17 @@ int sharded_host_bootstrap(rtfhe_ctx* ctx, int op, int mode, int steps, const ui
     });
 }
 
+// programmable bootstrap of host buffers: the same ranges, each with its range of lut_idx and the table copy of its device
+int sharded_host_pbs(rtfhe_ctx* ctx, const rtfhe_lut* lut, const int32_t* lut_idx, const uint32_t* in, uint32_t* out, size_t count) {
+    if (ctx->peers.empty()) return run_host_pbs_one(ctx, lut_on(lut, 0, nullptr), lut_idx, in, out, count);
+    const int n_dev = 1 + (int)ctx->peers.size();
+    const size_t w = (size_t)ctx->p.n + 1;
+    return for_each_device(ctx, [&](rtfhe_ctx* c, int d) {
+        const size_t b = shard_begin(count, d, n_dev), e = shard_begin(count, d + 1, n_dev);
+        return run_host_pbs_one(c, lut_on(lut, d, nullptr), lut_idx ? lut_idx + b : nullptr, in + b * w, out + b * w, e - b);
+    });
+}
+
 int sharded_host_mux(rtfhe_ctx* ctx, const uint32_t* c, const uint32_t* in0, const uint32_t* in1, uint32_t* out, size_t count) {
     if (ctx->peers.empty()) return mux_host_one(ctx, c, in0, in1, out, count);
     const int n_dev = 1 + (int)ctx->peers.size();
@@ -86,19 +97,23 @@ int sharded_host_mux(rtfhe_ctx* ctx, const uint32_t* c, const uint32_t* in0, con
 // hipMemcpyAsync(hipMemcpyDefault) instead, which lets the runtime find out where they live.
 // Volumes are negligible next to the compute (config 3: 65,536 gates = 333 MB in, 167 MB out against 53 ms of bootstrapping per 8,192 gates).
 // Inside a stream capture on s the whole batch stays on the primary (the staging buffers of a peer are not the capture's to bake in).
+// A programmable bootstrap (lut) ships each peer its range of d_lut_idx next to its ciphertexts, into the staging buffer of the second operand.
 // A failure part-way leaves nothing dangling: s still waits for every peer already launched (they may be writing d_out), the current device is
 // the primary's again, and the first error is what the call returns.
-int sharded_dev_batch(rtfhe_ctx* ctx, int op, const void* d_c, const void* d_in0, const void* d_in1, void* d_out, size_t count, hipStream_t s) {
+int sharded_dev_batch(rtfhe_ctx* ctx, int op, const void* d_c, const void* d_in0, const void* d_in1, void* d_out, size_t count, hipStream_t s,
+                      const rtfhe_lut* lut, const int32_t* d_lut_idx) {
     if (int rc = use(ctx)) return rc;
     const bool mux = op < 0;
-    auto run = [&](rtfhe_ctx* c, const void* cc, const void* i0, const void* i1, void* o, size_t cnt, hipStream_t st) {
-        return mux ? mux_dev_one(c, cc, i0, i1, o, cnt, st) : launch_bootstrap(c, op, MODE_GATE, c->p.n, i0, i1, o, cnt, st);
+    auto run = [&](rtfhe_ctx* c, int d, const void* cc, const void* i0, const void* i1, void* o, size_t cnt, hipStream_t st, const int32_t* idx) {
+        return mux ? mux_dev_one(c, cc, i0, i1, o, cnt, st)
+                   : launch_bootstrap(c, op, MODE_GATE, c->p.n, i0, i1, o, cnt, st, nullptr, nullptr, nullptr, nullptr, 0, lut_on(lut, d, idx));
     };
+    const bool ship_idx = lut && d_lut_idx;
     if (count == 0) return 0;
     if (count > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "count too large");
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-    if (cs != hipStreamCaptureStatusNone) return run(ctx, d_c, d_in0, d_in1, d_out, count, s);
+    if (cs != hipStreamCaptureStatusNone) return run(ctx, 0, d_c, d_in0, d_in1, d_out, count, s, d_lut_idx);
     const int n_dev = 1 + (int)ctx->peers.size();
     const size_t w = (size_t)ctx->p.n + 1;
     auto at = [&](const void* p, size_t gate) { return p ? (const void*)((const uint32_t*)p + gate * w) : nullptr; };
@@ -108,7 +123,8 @@ int sharded_dev_batch(rtfhe_ctx* ctx, int op, const void* d_c, const void* d_in0
         if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
         return a.type == hipMemoryTypeDevice && a.device == ctx->device;
     };
-    const bool peer_copies = on_primary(d_in0) && (!d_in1 || on_primary(d_in1)) && (!d_c || on_primary(d_c)) && on_primary(d_out);
+    const bool peer_copies = on_primary(d_in0) && (!d_in1 || on_primary(d_in1)) && (!d_c || on_primary(d_c)) && on_primary(d_out) &&
+                             (!ship_idx || on_primary(d_lut_idx));
     // staging of every peer first (it may allocate, i.e. synchronise a device), then nothing but asynchronous calls
     for (int d = 1; d < n_dev; d++) {
         rtfhe_ctx* peer = ctx->peers[d - 1];
@@ -117,14 +133,14 @@ int sharded_dev_batch(rtfhe_ctx* ctx, int op, const void* d_c, const void* d_in0
         if (!bytes) continue;
         int rc = use(peer);
         if (!rc) rc = ensure(peer, &peer->d_a, &peer->cap_a, bytes);
-        if (!rc && (d_in1 || mux)) rc = ensure(peer, &peer->d_b, &peer->cap_b, bytes);
+        if (!rc && (d_in1 || mux || ship_idx)) rc = ensure(peer, &peer->d_b, &peer->cap_b, bytes);
         if (!rc) rc = ensure(peer, &peer->d_c, &peer->cap_c, bytes);
         if (rc) { (void)hipSetDevice(ctx->device); return fail(ctx, rc, peer->err); }
     }
     if (int rc = use(ctx)) return rc;
     HIPCHECK(ctx, hipEventRecord(ctx->ev_shard, s));
     if (const size_t own = shard_begin(count, 1, n_dev))
-        if (int rc = run(ctx, d_c, d_in0, d_in1, d_out, own, s)) return rc;
+        if (int rc = run(ctx, 0, d_c, d_in0, d_in1, d_out, own, s, d_lut_idx)) return rc;
     // from here on an error may not return before s has been made to wait for the peers already launched
     int first_rc = 0;
     std::string first_err;
@@ -150,10 +166,12 @@ int sharded_dev_batch(rtfhe_ctx* ctx, int op, const void* d_c, const void* d_in0
         ok = ok && hip(pull(peer, peer->d_a, at(mux ? d_c : d_in0, b), bytes), "copy of the first operand to the peer");
         if (ok && d_in1) ok = hip(pull(peer, peer->d_b, at(d_in1, b), bytes), "copy of the second operand to the peer");
         if (ok && mux) ok = hip(pull(peer, peer->d_c, at(d_in0, b), bytes), "copy of the third operand to the peer");
+        if (ok && ship_idx) ok = hip(pull(peer, peer->d_b, d_lut_idx + b, cnt * 4), "copy of the table indices to the peer");
         ok = ok && hip(hipEventRecord(peer->ev_sh[1], peer->stream), "hipEventRecord");
         if (ok) {
-            const int rc = mux ? run(peer, peer->d_a, peer->d_c, peer->d_b, peer->d_a, cnt, peer->stream)
-                               : run(peer, nullptr, peer->d_a, d_in1 ? peer->d_b : nullptr, peer->d_c, cnt, peer->stream);
+            const int rc = mux ? run(peer, d, peer->d_a, peer->d_c, peer->d_b, peer->d_a, cnt, peer->stream, nullptr)
+                               : run(peer, d, nullptr, peer->d_a, d_in1 ? peer->d_b : nullptr, peer->d_c, cnt, peer->stream,
+                                     ship_idx ? (const int32_t*)peer->d_b : nullptr);
             if (rc) { first_rc = rc; first_err = "device " + std::to_string(peer->device) + ": " + peer->err; ok = false; }
         }
         ok = ok && hip(hipEventRecord(peer->ev_sh[2], peer->stream), "hipEventRecord");

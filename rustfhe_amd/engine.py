@@ -233,6 +233,28 @@ class Engine:
         self._ck(self.L.rtfhe_timer_end_detail(self.h, C.c_void_p(stream) if stream else None, C.byref(ms), C.byref(ks), C.byref(n)))
         return ms.value, ks.value, n.value
 
+    # ---- programmable bootstrapping (include/rtfhe.h: rtfhe_lut_create, rtfhe_pbs_batch[_dev]) -------------------------------
+    def lut(self, tv):
+        """Uploads test polynomials u32[n_lut][N] (or one u32[N]) to every device of the context; a Lut, closed by Lut.close() or a with block.
+        rustfhe_amd.lut_polynomial builds one for a function of a small integer."""
+        return Lut(self, tv)
+
+    def pbs_batch(self, lut, tlwe, lut_idx=None):
+        """One programmable bootstrap per ciphertext: gate g evaluates table lut_idx[g] (None: table 0).  Indices are checked here:
+        one outside [0, n_lut) raises RtfheError before anything runs."""
+        tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)
+        idx = None if lut_idx is None else _np(lut_idx, np.int32).reshape(-1)
+        assert idx is None or idx.size == tlwe.shape[0], "one table index per ciphertext"
+        out = np.empty_like(tlwe)
+        self._ck(self.L.rtfhe_pbs_batch(self.h, lut.h, _ptr(idx), _ptr(tlwe), _ptr(out), tlwe.shape[0]))
+        return out
+
+    def pbs_batch_dev(self, lut, d_tlwe, d_out, count, d_lut_idx=None, stream=None):
+        """... on device buffers (d_lut_idx: int32[count] on the device or None), asynchronous on `stream`.  Indices are checked on the device:
+        a gate with a bad one is skipped and the next sync() raises RtfheError."""
+        self._ck(self.L.rtfhe_pbs_batch_dev(self.h, lut.h, self._dev(d_lut_idx), self._dev(d_tlwe), self._dev(d_out), count,
+                                            C.c_void_p(stream) if stream else None))
+
     # ---- stage level ------------------------------------------------------------------------
     def blind_rotate_batch(self, tlwe, steps=None):
         tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)
@@ -288,6 +310,37 @@ class Engine:
         res = np.empty(src.shape, np.uint32)
         self._ck(self.L.rtfhe_fft_u32_batch(self.h, _ptr(src), _ptr(res), src.shape[0]))
         return res
+
+
+class Lut:
+    """Test polynomials of a programmable bootstrap on an Engine's devices (rtfhe_lut).  Closing it frees the device copies; a Lut whose Engine was
+    closed first only frees its handle."""
+
+    def __init__(self, engine, tv):
+        tv = _np(tv, np.uint32)
+        tv = tv.reshape(-1, engine.p.N)
+        self.engine = engine
+        self.n_lut = tv.shape[0]
+        h = C.c_void_p()
+        engine._ck(engine.L.rtfhe_lut_create(engine.h, _ptr(tv), self.n_lut, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.engine.L.rtfhe_lut_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class FftPlan:
@@ -409,6 +462,22 @@ def encrypt_bits(params, key0, bits, seed=None):
         rc = L.rtfhe_tlwe_encrypt_bits_deterministic(C.byref(params), _ptr(key0), seed, _ptr(bits), _ptr(out), bits.size)
     if rc != 0:
         raise RtfheError(rc, "rtfhe_tlwe_encrypt_bits failed")
+    return out
+
+
+def encrypt_torus(params, key0, mu, seed=None):
+    """encrypt_bits with the plaintext torus words mu (u32) given directly, e.g. encode_msgs(m, p) for programmable bootstrapping.
+    seed None (production): OS CSPRNG; an integer seed = TEST-ONLY deterministic encryption."""
+    L = _ffi.load()
+    mu = _np(mu, np.uint32).reshape(-1)
+    key0 = _np(key0, np.int32)
+    out = np.empty((mu.size, params.n + 1), np.uint32)
+    if seed is None:
+        rc = L.rtfhe_tlwe_encrypt_torus(C.byref(params), _ptr(key0), _ptr(mu), _ptr(out), mu.size)
+    else:
+        rc = L.rtfhe_tlwe_encrypt_torus_deterministic(C.byref(params), _ptr(key0), seed, _ptr(mu), _ptr(out), mu.size)
+    if rc != 0:
+        raise RtfheError(rc, "rtfhe_tlwe_encrypt_torus failed")
     return out
 
 
