@@ -106,6 +106,11 @@ extern "C" {
     pub fn rtfhe_pbs_batch(ctx: *mut rtfhe_ctx, lut: *const rtfhe_lut, lut_idx: *const i32, tlwe: *const u32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_pbs_batch_dev(ctx: *mut rtfhe_ctx, lut: *const rtfhe_lut, d_lut_idx: *const c_void, d_tlwe: *const c_void, d_out: *mut c_void,
                                count: usize, stream: *mut c_void) -> c_int;
+    // many-LUT PBS: n_out (1, 2, 4, 8) outputs per gate from one blind rotation, out [count][n_out][n+1]
+    pub fn rtfhe_pbs_many_batch(ctx: *mut rtfhe_ctx, lut: *const rtfhe_lut, n_out: i32, lut_idx: *const i32, tlwe: *const u32, out: *mut u32,
+                                count: usize) -> c_int;
+    pub fn rtfhe_pbs_many_batch_dev(ctx: *mut rtfhe_ctx, lut: *const rtfhe_lut, n_out: i32, d_lut_idx: *const c_void, d_tlwe: *const c_void,
+                                    d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
     pub fn rtfhe_sync(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_begin(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_end(ctx: *mut rtfhe_ctx, stream: *mut c_void, ms: *mut f64, launches: *mut i64) -> c_int;

@@ -24,6 +24,8 @@
  *   rtfhe_blind_rotate_batch         <- TFHE::blind_rotate with the gate test vector (tfhe.rs:81-113)
  *   rtfhe_lut_* / rtfhe_pbs_batch[_dev]  (no reference counterpart: its test vector is fixed to 1/8) the same bootstrap with
  *                                       caller-supplied test polynomials: programmable bootstrapping
+ *   rtfhe_pbs_many_batch[_dev]       (no reference counterpart) several tables from one blind rotation: sample extract at indices
+ *                                       0 .. n_out-1 (TRLWERep::sample_extract_index, hom_nand/src/trlwe.rs:110-121)
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch           <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -253,6 +255,27 @@ int rtfhe_pbs_batch(rtfhe_ctx *ctx, const rtfhe_lut *lut, const int32_t *lut_idx
                     const uint32_t *tlwe /* [count][n+1] */, uint32_t *out /* [count][n+1] */, size_t count);
 int rtfhe_pbs_batch_dev(rtfhe_ctx *ctx, const rtfhe_lut *lut, const void *d_lut_idx /* int32[count] or NULL */,
                         const void *d_tlwe, void *d_out, size_t count, void *stream);
+/* ---- many-LUT PBS: n_out = 2^t functions of one value from ONE blind rotation ----
+ * Take an input t = (a_0 … a_{n−1}, b) and n_out = ϑ = 2^t with t ∈ {0,1,2,3}. Let SH = 32 − log2 N − 1 and S = SH + t.
+ *
+ *     bbar   = (b >> S) << t                                      (floor, as the gates)
+ *     abar_i = (((a_i + 2^(S-1)) mod 2^32) >> S) << t            (round, as the gates; all values in [0, 2N), multiples of ϑ)
+ *     acc    = X^{-bbar} (tv, 0),  tv = row lut_idx[g] of the table   (exactly as rtfhe_pbs_batch)
+ *     for i in 0 .. n:  acc = CMUX(bk_i, X^{abar_i} acc, acc)
+ *     out[g][j] = identity_key_switch(sample_extract_index(acc, j))   for j = 0 .. ϑ-1
+ *
+ * sample_extract_index(acc, j) is the reference's TRLWERep::sample_extract_index(j) (hom_nand/src/trlwe.rs:110-121):
+ * a'_i = acc_a[j−i] for i ≤ j, −acc_a[N+j−i] otherwise, b' = acc_b[j].  With ϑ = 1 this is exactly rtfhe_pbs_batch.
+ * A table for ϑ functions interleaves them: coefficient k ϑ + j serves function j (rustfhe_amd.pbs.many_lut_polynomial builds one).
+ * n_out must be 1, 2, 4 or 8 (anything else: RTFHE_ERR_INVALID).  Outputs are [count][n_out][n+1]: the n_out rows of a gate lie together.
+ * Tables, index checks (on the host before any launch / on the device, reported at the next rtfhe_sync), sharding over the entries of an
+ * rtfhe_ctx_create_multi context and the refusal on the exact backends are rtfhe_pbs_batch[_dev]'s.  Inside a stream capture
+ * rtfhe_pbs_many_batch_dev allocates nothing: an eager rtfhe_pbs_many_batch_dev of at least `count` gates and at least this n_out must have run
+ * on that stream first (else RTFHE_ERR_STATE). */
+int rtfhe_pbs_many_batch(rtfhe_ctx *ctx, const rtfhe_lut *lut, int32_t n_out, const int32_t *lut_idx /* [count] or NULL */,
+                         const uint32_t *tlwe /* [count][n+1] */, uint32_t *out /* [count][n_out][n+1] */, size_t count);
+int rtfhe_pbs_many_batch_dev(rtfhe_ctx *ctx, const rtfhe_lut *lut, int32_t n_out, const void *d_lut_idx /* int32[count] or NULL */,
+                             const void *d_tlwe, void *d_out /* [count][n_out][n+1] */, size_t count, void *stream);
 /* waits for `stream`; also reports (once) a netlist gate skipped since the previous call */
 int rtfhe_sync(rtfhe_ctx *ctx, void *stream);
 /* device-side timing of the launches enqueued by the *_dev calls between begin and end (HIP events on

@@ -6,8 +6,8 @@ package is the thin Python host side above it.  There is no CPU fallback anywher
 from ._ffi import AND, ANDNY, COPY, NAND, NOT, OR, XOR, Params, load  # noqa: F401
 from .engine import (Engine, FftPlan, Lut, RtfheError, decrypt_bits, device_link, encrypt_bits, encrypt_torus, keygen, ksk_expand_ref, load_keys,  # noqa: F401
                      load_tlwe, phases, pinned_empty, save_keys, save_tlwe, shard_range)
-from .pbs import decode_msgs, encode_msgs, lut_polynomial  # noqa: F401
+from .pbs import decode_msgs, encode_msgs, lut_polynomial, many_lut_polynomial  # noqa: F401
 
 __all__ = ["Engine", "FftPlan", "Params", "RtfheError", "keygen", "ksk_expand_ref", "encrypt_bits", "decrypt_bits", "phases", "save_keys", "load_keys", "save_tlwe", "load_tlwe", "pinned_empty", "shard_range", "device_link",
-           "Lut", "encrypt_torus", "encode_msgs", "decode_msgs", "lut_polynomial",
+           "Lut", "encrypt_torus", "encode_msgs", "decode_msgs", "lut_polynomial", "many_lut_polynomial",
            "NAND", "AND", "OR", "XOR", "NOT", "COPY", "ANDNY", "load"]

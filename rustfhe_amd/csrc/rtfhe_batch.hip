@@ -17,8 +17,9 @@ int backend_prepare(rtfhe_ctx* ctx) {
 int ensure_tlwe1(rtfhe_ctx* ctx, rtfhe_ctx::Tlwe1& b, size_t gates) {
     if (b.cap >= gates) return 0;
     HIPCHECK(ctx, hipDeviceSynchronize());            // earlier launches may still read the old buffer
-    if (b.d) HIPCHECK(ctx, hipFree(b.d));
-    b.d = nullptr; b.cap = 0;
+    if (b.d && b.captured) ctx->mux_retired.push_back(b.d);      // a caller's graph holds its address: kept until the context goes
+    else if (b.d) HIPCHECK(ctx, hipFree(b.d));
+    b.d = nullptr; b.cap = 0; b.captured = false;
     const size_t cap = ((gates < 1024 ? 1024 : gates) + 15) / 16 * 16;      // whole tiles of 16 gates (rtfhe::ext_slot): 16 N + 16 words each
     HIPCHECK(ctx, hipMalloc((void**)&b.d, cap * ((size_t)ctx->p.N + 1) * 4));
     b.cap = cap;
@@ -93,9 +94,9 @@ int run_host_bootstrap_one(rtfhe_ctx* ctx, int op, int mode, int steps, const ui
 int run_host_pbs_one(rtfhe_ctx* ctx, const LutRef& lut, const int32_t* lut_idx, const uint32_t* in, uint32_t* out, size_t count) {
     if (int rc = use(ctx)) return rc;
     if (count == 0) return 0;
-    const size_t bytes = count * ((size_t)ctx->p.n + 1) * 4;
+    const size_t bytes = count * ((size_t)ctx->p.n + 1) * 4, out_bytes = lut.shift > 0 ? bytes << lut.shift : bytes;
     if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, bytes)) return rc;
-    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, bytes)) return rc;
+    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
     if (int rc = copy_in(ctx, ctx->d_a, in, bytes, 0)) return rc;
     LutRef l = lut;
     if (lut_idx) {      // the indices ride in the second operand's staging buffer (a bootstrap has one operand)
@@ -103,9 +104,55 @@ int run_host_pbs_one(rtfhe_ctx* ctx, const LutRef& lut, const int32_t* lut_idx, 
         if (int rc = copy_in(ctx, ctx->d_b, lut_idx, count * 4, 1)) return rc;
         l.idx = (const int32_t*)ctx->d_b;
     }
-    if (int rc = launch_bootstrap(ctx, RTFHE_COPY, MODE_GATE, ctx->p.n, ctx->d_a, nullptr, ctx->d_c, count, ctx->stream, nullptr, nullptr, nullptr, nullptr, 0, l))
+    if (l.shift >= 0) {
+        if (int rc = launch_pbs_many(ctx, l, ctx->d_a, ctx->d_c, count, ctx->stream)) return rc;
+    } else if (int rc = launch_bootstrap(ctx, RTFHE_COPY, MODE_GATE, ctx->p.n, ctx->d_a, nullptr, ctx->d_c, count, ctx->stream, nullptr, nullptr, nullptr,
+                                         nullptr, 0, l)) {
         return rc;
-    return copy_out(ctx, out, ctx->d_c, bytes, 2);
+    }
+    return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+}
+
+// Many-LUT PBS on one device (include/rtfhe.h: rtfhe_pbs_many_batch): the bootstrap kernels' many-LUT twins in MODE_EXTRACT write the 2^shift
+// samples of every gate into this stream's sample buffer at batch-wide rows (gate << shift) + j, then ONE batch key switch of count << shift
+// rows writes [count][2^shift][n+1] -- with the matrix form of the key as the split path does (into the zeroed output), else one wave per
+// sample.  Outside a stream capture the sample buffer grows and the second key layout is built here; inside one (never rtfhe_circuit_create's:
+// circuits hold no PBS) nothing may be allocated: this stream's buffer must already hold count << shift samples -- an eager many-PBS of at least
+// `count` gates and at least this many outputs on the stream first -- and is then kept for as long as the context lives (Tlwe1::captured).
+int launch_pbs_many(rtfhe_ctx* ctx, const LutRef& lut, const void* d_in, void* d_out, size_t count, hipStream_t s) {
+    if (!ctx->has_bk) return fail(ctx, RTFHE_ERR_STATE, "bootstrapping key not loaded");
+    if (!ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "key-switching key not loaded");
+    if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
+        return fail(ctx, RTFHE_ERR_INVALID, "programmable bootstrapping runs on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR)");
+    if (count == 0) return 0;
+    const size_t rows = count << lut.shift;
+    if (rows > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "count << log2(n_out) too large");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
+    rtfhe_ctx::Tlwe1* buf = tlwe1_of(ctx, s);
+    if (cs != hipStreamCaptureStatusNone) {
+        if (!buf || buf->cap < rows)
+            return fail(ctx, RTFHE_ERR_STATE, "a many-LUT PBS inside a stream capture needs this stream's sample buffer to exist already: run one eager "
+                                              "rtfhe_pbs_many_batch_dev of at least this many gates and outputs on the stream before capturing");
+        buf->captured = true;
+    } else {
+        if (int rc = ensure_bk_layouts(ctx, count, MODE_EXTRACT)) return rc;
+        if (int rc = ensure_tlwe1(ctx, ctx->tlwe1[s], rows)) return rc;
+        buf = &ctx->tlwe1[s];
+    }
+    BootstrapArgs a{};
+    a.tw = ctx->d_tw; a.bk = ctx->d_bk; a.ksk = ctx->d_ksk;
+    a.in0 = (const uint32_t*)d_in; a.in1 = a.in0; a.out = (uint32_t*)d_out;
+    a.count = (int)count; a.op = RTFHE_COPY; a.n = ctx->p.n; a.steps = ctx->p.n; a.mode = MODE_EXTRACT; a.ksw = ctx->ksw;
+    a.npad = (ctx->p.n + 1 + 63) / 64 * 64;
+    a.fault = ctx->d_fault; a.dbg = ctx->d_dbg;
+    a.ext = buf->d; a.ext_first = 0;
+    if (int rc = launch_bootstrap_fft(ctx, a, s, lut)) return rc;
+    if (!ctx->d_ksmat) return launch_key_switch_ext(ctx, buf->d, (uint32_t*)d_out, rows, s);
+    HIPCHECK(ctx, hipMemsetAsync(d_out, 0, rows * ((size_t)ctx->p.n + 1) * 4, s));      // the K-slices add into it
+    BootstrapArgs k = a;
+    k.count = (int32_t)rows;
+    return launch_key_switch_mm(ctx, k, buf->d, s);
 }
 
 // hom_mux (tfhe.rs:27-40): i1 = AND(c, in1); i0 = AND(-c, in0); bootstrap(i1 + i0 + 1/8) -- the last line is hom_or(i1, i0).
@@ -276,6 +323,41 @@ int rtfhe_pbs_batch_dev(rtfhe_ctx* ctx, const rtfhe_lut* lut, const void* d_lut_
         return sharded_dev_batch(ctx, RTFHE_COPY, nullptr, d_tlwe, nullptr, d_out, count, (hipStream_t)stream, lut, (const int32_t*)d_lut_idx);
     return launch_bootstrap(ctx, RTFHE_COPY, MODE_GATE, ctx->p.n, d_tlwe, nullptr, d_out, count, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, 0,
                             lut_on(lut, 0, (const int32_t*)d_lut_idx));
+}
+
+// ---- many-LUT PBS: 2^t outputs of one blind rotation (include/rtfhe.h) ----
+static int many_shift(rtfhe_ctx* ctx, int32_t n_out, int32_t* shift) {
+    for (int t = 0; t <= 3; t++)
+        if (n_out == (1 << t)) { *shift = t; return 0; }
+    return fail(ctx, RTFHE_ERR_INVALID, "n_out = " + std::to_string(n_out) + ": a many-LUT PBS gives 1, 2, 4 or 8 outputs per gate");
+}
+
+int rtfhe_pbs_many_batch(rtfhe_ctx* ctx, const rtfhe_lut* lut, int32_t n_out, const int32_t* lut_idx, const uint32_t* tlwe, uint32_t* out, size_t count) {
+    if (int rc = pbs_ready(ctx, lut)) return rc;
+    int32_t shift = 0;
+    if (int rc = many_shift(ctx, n_out, &shift)) return rc;
+    if (!tlwe || !out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (count > ((size_t)0x7fffffff >> shift)) return fail(ctx, RTFHE_ERR_INVALID, "count too large");
+    if (lut_idx)
+        for (size_t g = 0; g < count; g++)
+            if ((uint32_t)lut_idx[g] >= (uint32_t)lut->n_lut)
+                return fail(ctx, RTFHE_ERR_INVALID, "lut_idx[" + std::to_string(g) + "] = " + std::to_string(lut_idx[g]) + " is outside [0, " + std::to_string(lut->n_lut) + ")");
+    return sharded_host_pbs(ctx, lut, lut_idx, tlwe, out, count, shift);
+}
+
+int rtfhe_pbs_many_batch_dev(rtfhe_ctx* ctx, const rtfhe_lut* lut, int32_t n_out, const void* d_lut_idx, const void* d_tlwe, void* d_out, size_t count,
+                             void* stream) {
+    if (int rc = pbs_ready(ctx, lut)) return rc;
+    if (int rc = use(ctx)) return rc;
+    int32_t shift = 0;
+    if (int rc = many_shift(ctx, n_out, &shift)) return rc;
+    if (!d_tlwe || !d_out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (!gpu_accessible(ctx, d_tlwe) || !gpu_accessible(ctx, d_out) || (d_lut_idx && !gpu_accessible(ctx, d_lut_idx)))
+        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_pbs_many_batch_dev needs device pointers (got memory the GPU cannot address)");
+    if (count > ((size_t)0x7fffffff >> shift)) return fail(ctx, RTFHE_ERR_INVALID, "count too large");
+    if (!ctx->peers.empty())
+        return sharded_dev_batch(ctx, RTFHE_COPY, nullptr, d_tlwe, nullptr, d_out, count, (hipStream_t)stream, lut, (const int32_t*)d_lut_idx, shift);
+    return launch_pbs_many(ctx, lut_on(lut, 0, (const int32_t*)d_lut_idx, shift), d_tlwe, d_out, count, (hipStream_t)stream);
 }
 
 int rtfhe_sync(rtfhe_ctx* ctx, void* stream) {

@@ -1,7 +1,7 @@
 // rtfhe_body_eo4.hpp -- the body of k_bootstrap_eo4 and of its programmable-bootstrap twin k_pbs_eo4 (rtfhe_kernels_eo4.hpp), included inside the braces of both
-// kernels: they declare `ea` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut, rtfhe_kernels.hpp).
+// kernels: they declare `ea` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap_eo4 compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included twice.
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included three times (k_pbs_many_*: the many-LUT PBS).
     constexpr int LOGN = 11, N = 2048, P = 1024, R = 8, NT = 256 * GATES;
     typedef Geo<10> G;   // geometry of a parity's 512-point sub-network
     constexpr uint32_t M = decomp_mask(L, BGBIT);
@@ -51,7 +51,8 @@
         constexpr int SH = 32 - LOGN - 1;
         for (int i = lane0 + 64 * q; i <= n; i += 256) {
             const uint32_t t = gate_linear(io.op, io.p0[i], io.p1[i], i == n);
-            abar[i] = (uint16_t)((i == n) ? (t >> SH) : ((t + (1u << (SH - 1))) >> SH));
+            if constexpr (decltype(tvs)::MANY) abar[i] = (uint16_t)mod_switch<SH>(t, i == n, tv_shift(tvs));   // many-LUT: at SH + t, scaled back
+            else abar[i] = (uint16_t)((i == n) ? (t >> SH) : ((t + (1u << (SH - 1))) >> SH));
         }
     }
     __syncthreads();
@@ -303,6 +304,10 @@
     }
     __syncthreads();
     // MODE_EXTRACT: the key switch of the whole batch follows as its own launch (k_key_switch_mm)
+    if constexpr (decltype(tvs)::MANY) {      // many-LUT PBS: every output (the batch key switch writes the output rows)
+        if (live) many_extract<N>(a.ext, a.ext_first + g, tv_shift(tvs), accbuf, q * (N / 4) + lane0, (q + 1) * (N / 4), 64, q ? -1 : lane0);
+        return;
+    }
     if (live) {
         const int ge = a.ext_first + g;      // batch-wide gate number: the sample buffer is laid out for the key switch (ext_slot)
         for (int c = q * (N / 4) + lane0; c < (q + 1) * (N / 4); c += 64) *ext_slot(a.ext, ge, c, N) = accbuf[N + c];

@@ -1,7 +1,7 @@
 // rtfhe_body_pair_rr.hpp -- the body of k_bootstrap_pair_rr and of its programmable-bootstrap twin k_pbs_pair_rr (rtfhe_kernels_pair_rr.hpp), included inside the braces of both
-// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut, rtfhe_kernels.hpp).
+// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap_pair_rr compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included twice.
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included three times (k_pbs_many_*: the many-LUT PBS).
     typedef PairRrLds S;
     constexpr int LOGN = 10, SLOTS = S::SLOTS;
     typedef Geo<LOGN> G;
@@ -46,7 +46,8 @@
         uint16_t* ab = reinterpret_cast<uint16_t*>(gates0 + gl * gate_bytes + (size_t)2 * N * 4);
         for (int i = tid; i <= n; i += NT) {
             const uint32_t t = gate_linear(io.op, io.p0[i], io.p1[i], i == n);
-            ab[i] = (uint16_t)((i == n) ? (t >> SH) : ((t + (1u << (SH - 1))) >> SH));
+            if constexpr (decltype(tvs)::MANY) ab[i] = (uint16_t)mod_switch<SH>(t, i == n, tv_shift(tvs));   // many-LUT: at SH + t, scaled back
+            else ab[i] = (uint16_t)((i == n) ? (t >> SH) : ((t + (1u << (SH - 1))) >> SH));
         }
     }
     __syncthreads();
@@ -217,6 +218,10 @@
         }
         RR_PAIR_SYNC();
         if (a.mode == MODE_EXTRACT) {      // the key switch of the whole batch follows as its own launch (k_key_switch_mm)
+            if constexpr (decltype(tvs)::MANY) {      // many-LUT PBS: every output (the batch key switch writes the output rows)
+                if (live) many_extract<N>(a.ext, a.ext_first + g, tv_shift(tvs), accbuf, side * (N / 2) + lane, (side + 1) * (N / 2), 64, side ? -1 : lane);
+                continue;
+            }
             if (live) {
                 const int ge = a.ext_first + g;
                 for (int c = side * (N / 2) + lane; c < (side + 1) * (N / 2); c += 64) *ext_slot(a.ext, ge, c, N) = accbuf[N + c];

@@ -1,7 +1,7 @@
 // rtfhe_body_wave.hpp -- the body of k_bootstrap and of its programmable-bootstrap twin k_pbs (rtfhe_kernels.hpp), included inside the braces of both
-// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut, rtfhe_kernels.hpp).
+// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included twice.
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included three times (k_pbs_many_*: the many-LUT PBS).
     typedef Geo<LOGN> G;
     constexpr int N = G::N, R = G::R;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -32,7 +32,8 @@
         constexpr int SH = 32 - LOGN - 1;
         for (int i = lane; i <= n; i += 64) {
             const uint32_t t = gate_linear(io.op, io.p0[i], io.p1[i], i == n);
-            abar[i] = (i == n) ? (t >> SH) : ((t + (1u << (SH - 1))) >> SH);
+            if constexpr (decltype(tvs)::MANY) abar[i] = mod_switch<SH>(t, i == n, tv_shift(tvs));   // many-LUT: at SH + t, scaled back
+            else abar[i] = (i == n) ? (t >> SH) : ((t + (1u << (SH - 1))) >> SH);
         }
     }
     wave_lds_sync();
@@ -74,4 +75,8 @@
         accbuf[N + ((N - c) & (N - 1))] = (c == 0) ? av[mm] : (0u - av[mm]);
     }
     wave_lds_sync();
+    if constexpr (decltype(tvs)::MANY) {      // many-LUT PBS (MODE_EXTRACT only): every output to the batch key switch's operand
+        many_extract<N>(a.ext, a.ext_first + g, tv_shift(tvs), accbuf, lane, N, 64, lane);
+        return;
+    }
     key_switch_wave<LOGN, KS_T, KS_BB, KSQ>(accbuf + N, bprime, a.ksk, a.ksw, n, io.out, lane);

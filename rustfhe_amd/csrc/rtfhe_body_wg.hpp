@@ -1,7 +1,7 @@
 // rtfhe_body_wg.hpp -- the body of k_bootstrap_wg and of its programmable-bootstrap twin k_pbs_wg (rtfhe_kernels_wg.hpp), included inside the braces of both
-// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut, rtfhe_kernels.hpp).
+// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap_wg compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included twice.
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included three times (k_pbs_many_*: the many-LUT PBS).
     typedef Geo<LOGN> G;
     typedef WgLds<LOGN, L> S;
     constexpr int N = G::N, P = G::P, R = G::R, NW = S::NW, ROWS = 2 * L;
@@ -28,7 +28,8 @@
         constexpr int SH = 32 - LOGN - 1;
         for (int i = tid; i <= n; i += 64 * NW) {
             const uint32_t t = gate_linear(io.op, io.p0[i], io.p1[i], i == n);
-            abar[i] = (i == n) ? (t >> SH) : ((t + (1u << (SH - 1))) >> SH);
+            if constexpr (decltype(tvs)::MANY) abar[i] = mod_switch<SH>(t, i == n, tv_shift(tvs));   // many-LUT: at SH + t, scaled back
+            else abar[i] = (i == n) ? (t >> SH) : ((t + (1u << (SH - 1))) >> SH);
         }
     }
     __syncthreads();
@@ -217,6 +218,10 @@
         accbuf[N + ((N - c) & (N - 1))] = (c == 0) ? av[k] : (0u - av[k]);
     }
     __syncthreads();
+    if constexpr (decltype(tvs)::MANY) {      // many-LUT PBS (MODE_EXTRACT only): every output (the batch key switch writes the output rows)
+        many_extract<N>(a.ext, a.ext_first + g, tv_shift(tvs), accbuf, tid, N, 64 * NW, tid);
+        return;
+    }
     if (a.mode == MODE_EXTRACT) {      // the key switch of the whole batch follows as its own launch (k_key_switch_mm)
         const int ge = a.ext_first + g;      // batch-wide gate number: the sample buffer is laid out for the key switch (ext_slot)
         for (int c = tid; c < N; c += 64 * NW) *ext_slot(a.ext, ge, c, N) = accbuf[N + c];

@@ -81,7 +81,9 @@ struct rtfhe_ctx {
     size_t ksk_bytes = 0, ksmat_bytes = 0;
     // lvl1 samples between the two launches of the split path: ONE buffer per stream a batch was ever launched on (launches of one stream are
     // ordered, launches on different streams of one context may overlap and must not share it), plus a circuit's own during its capture
-    struct Tlwe1 { uint32_t* d = nullptr; size_t cap = 0; };     // cap in gates
+    // cap in gates (samples); captured: a many-LUT PBS inside a caller's stream capture baked d into a graph -- never freed while the context
+    // lives (a larger eager batch retires it to mux_retired and gets a new one)
+    struct Tlwe1 { uint32_t* d = nullptr; size_t cap = 0; bool captured = false; };
     std::unordered_map<hipStream_t, Tlwe1> tlwe1;
     Tlwe1* tlwe1_capture = nullptr;   // set by rtfhe_circuit_create around its capture: the circuit's buffer
     bool foreign_capture = false;     // set by launch_bootstrap for the duration of a call made inside a stream capture that is NOT
@@ -120,7 +122,7 @@ struct rtfhe_ctx {
     // while the context lives (`captured`): a later, larger eager batch on that stream gets a new pair and the old one moves to mux_retired.
     struct MuxBuf { void* m[2] = {nullptr, nullptr}; size_t cap = 0; bool captured = false; };
     std::unordered_map<hipStream_t, MuxBuf> mux;
-    std::vector<void*> mux_retired;
+    std::vector<void*> mux_retired;        // (and sample buffers of the split path that a caller's capture holds: Tlwe1::captured)
     int num_cus = 256;
     int force_waves = 0;   // RTFHE_FORCE_WAVES=1|2|4|8: one kernel shape for every batch (the parity tests' second opinions)
     int wg_max = 512;      // RTFHE_WG_MAX_GATES: largest batch routed to the workgroup-per-gate kernel
@@ -153,10 +155,11 @@ using rtfhe::BootstrapArgs;
 
 // what a bootstrap launch reads its test polynomials from: tv null = the gates' own (k_bootstrap_*), else the k_pbs_* twins with table
 // idx[g] of tv (idx null: table 0) for gate g of the launch
-struct LutRef { const uint32_t* tv = nullptr; const int32_t* idx = nullptr; int32_t n_tv = 0; };
+// (shift >= 0: a many-LUT PBS with 2^shift outputs per gate, the k_pbs_many_* kernels in MODE_EXTRACT, launch_pbs_many)
+struct LutRef { const uint32_t* tv = nullptr; const int32_t* idx = nullptr; int32_t n_tv = 0; int32_t shift = -1; };
 inline LutRef lut_segment(LutRef l, size_t off) { if (l.idx) l.idx += off; return l; }     // ... for the segment starting at gate `off`
-inline LutRef lut_on(const rtfhe_lut* lut, int entry, const int32_t* d_idx) {
-    return lut ? LutRef{lut->d_tv[entry], d_idx, lut->n_lut} : LutRef{};
+inline LutRef lut_on(const rtfhe_lut* lut, int entry, const int32_t* d_idx, int32_t shift = -1) {
+    return lut ? LutRef{lut->d_tv[entry], d_idx, lut->n_lut, shift} : LutRef{};
 }
 using rtfhe::cplx;
 
@@ -222,6 +225,8 @@ int launch_ksk_combine(rtfhe_ctx* ctx, const uint32_t* d_raw, hipStream_t s);
 int launch_ksmat_build(rtfhe_ctx* ctx, const uint32_t* d_raw, int colgroups, hipStream_t s);
 // the identity key switch of a whole batch as one exact i8 contraction (second launch of the split path)
 int launch_key_switch_mm(rtfhe_ctx* ctx, const BootstrapArgs& a, const uint32_t* samples, hipStream_t s);
+// the same key switch one wave per sample from the gathered key rows (k_key_switch_ext): contexts without the matrix form (RTFHE_KS_MM_MIN=0)
+int launch_key_switch_ext(rtfhe_ctx* ctx, uint32_t* samples, uint32_t* d_out, size_t count, hipStream_t s);
 
 // ---- batches (rtfhe_batch.hip) ----
 int launch_bootstrap(rtfhe_ctx* ctx, int op, int mode, int steps, const void* d_in0, const void* d_in1, void* d_out,
@@ -231,7 +236,10 @@ int ensure_tlwe1(rtfhe_ctx* ctx, rtfhe_ctx::Tlwe1& b, size_t gates);
 int run_host_bootstrap_one(rtfhe_ctx* ctx, int op, int mode, int steps, const uint32_t* in0, const uint32_t* in1, uint32_t* out, size_t count, size_t out_words);
 int mux_host_one(rtfhe_ctx* ctx, const uint32_t* c, const uint32_t* in0, const uint32_t* in1, uint32_t* out, size_t count);
 // a programmable bootstrap of host buffers on one device (lut_idx already checked; null = table 0)
+// (lut.shift >= 0: a many-LUT PBS, out [count][2^shift][n+1])
 int run_host_pbs_one(rtfhe_ctx* ctx, const LutRef& lut, const int32_t* lut_idx, const uint32_t* in, uint32_t* out, size_t count);
+// a many-LUT PBS (lut.shift >= 0) of device buffers on one device: the k_pbs_many_* launch(es), then the key switch of count << shift samples
+int launch_pbs_many(rtfhe_ctx* ctx, const LutRef& lut, const void* d_in, void* d_out, size_t count, hipStream_t s);
 int mux_dev_one(rtfhe_ctx* ctx, const void* d_c, const void* d_in0, const void* d_in1, void* d_out, size_t count, hipStream_t s);
 
 // ---- several GPUs (rtfhe_multi.hip) ----
@@ -240,10 +248,11 @@ int replicate(rtfhe_ctx* ctx, rtfhe_ctx* peer, const void* src, void** dst_of_pe
 int sharded_host_bootstrap(rtfhe_ctx* ctx, int op, int mode, int steps, const uint32_t* in0, const uint32_t* in1, uint32_t* out, size_t count, size_t out_words);
 int sharded_host_mux(rtfhe_ctx* ctx, const uint32_t* c, const uint32_t* in0, const uint32_t* in1, uint32_t* out, size_t count);
 // a batch that LIVES ON THE PRIMARY DEVICE, sharded over the context's devices: op < 0 = MUX (d_c, d_in0, d_in1), else a gate batch (d_in0, d_in1)
-// (lut: a programmable bootstrap, op = RTFHE_COPY, d_lut_idx its int32[count] indices on the primary or null)
+// (lut: a programmable bootstrap, op = RTFHE_COPY, d_lut_idx its int32[count] indices on the primary or null; shift >= 0: a many-LUT PBS,
+// 2^shift output rows per gate)
 int sharded_dev_batch(rtfhe_ctx* ctx, int op, const void* d_c, const void* d_in0, const void* d_in1, void* d_out, size_t count, hipStream_t s,
-                      const rtfhe_lut* lut = nullptr, const int32_t* d_lut_idx = nullptr);
-int sharded_host_pbs(rtfhe_ctx* ctx, const rtfhe_lut* lut, const int32_t* lut_idx, const uint32_t* in, uint32_t* out, size_t count);
+                      const rtfhe_lut* lut = nullptr, const int32_t* d_lut_idx = nullptr, int32_t shift = -1);
+int sharded_host_pbs(rtfhe_ctx* ctx, const rtfhe_lut* lut, const int32_t* lut_idx, const uint32_t* in, uint32_t* out, size_t count, int32_t shift = -1);
 
 // words per gate of the output buffer, by mode (MODE_EXTRACT: the final TLWE rows; the lvl1 samples go to `ext`)
 inline size_t mode_out_words(const BootstrapArgs& a, int N) { return a.mode == rtfhe::MODE_BLIND_ROTATE ? (size_t)2 * N : (size_t)a.n + 1; }

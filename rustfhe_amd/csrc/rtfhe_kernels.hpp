@@ -100,6 +100,7 @@ __device__ __forceinline__ GateIo gate_io(const BootstrapArgs& a, int g) {
 // TvGate, the gates' test vector (1/8, ..., 1/8) -- its row is always valid and its words are constants, so those kernels compile to what
 // they were before the twins existed -- and k_pbs_* with TvLut, the programmable bootstrap's caller-supplied tables (include/rtfhe.h).
 struct TvGate {
+    static constexpr bool MANY = false;      // one output per gate (k_pbs_many_*: several, see TvMany)
     struct Row { __device__ __forceinline__ bool ok() const { return true; } };
 };
 __device__ __forceinline__ TvGate::Row tv_row(const TvGate&, int, int) { return TvGate::Row{}; }
@@ -117,6 +118,7 @@ struct LutArgs {
 // A gate whose index lies outside [0, n_tv) is skipped like a netlist gate with a bad wire (it runs on table 0 and stores nothing) and
 // reported through *fault.  The index is read once per gate before the pre-step (and once more in k_bootstrap_pair_rr's epilogue).
 struct TvLut {
+    static constexpr bool MANY = false;
     const uint32_t* tv; const int32_t* idx; int32_t n_tv; int32_t* fault;
     struct Row {
         const uint32_t* p; bool good;
@@ -144,6 +146,47 @@ __device__ __forceinline__ uint32_t tv_word(const TvLut::Row& r, int e) {      /
 }
 template <typename A>
 __device__ __forceinline__ TvLut tv_lut(const LutArgs<A>& p, int32_t* fault) { return TvLut{p.tv, p.tv_idx, p.n_tv, fault}; }
+
+// Many-LUT PBS (k_pbs_many_*, the third inclusion of every body): the tables of TvLut, whose rows interleave 2^t functions, and a mod switch
+// rounded at SH + t and scaled back by 2^t, so that every rotation is a multiple of 2^t and coefficients 0 .. 2^t - 1 of the rotated
+// accumulator hold the 2^t outputs (include/rtfhe.h: rtfhe_pbs_many_batch).  Such a kernel runs in MODE_EXTRACT only: sample extract
+// index j (trlwe.rs:110-121) of every output goes to batch-wide row (gate << t) + j of the batch key switch's operand (many_extract).
+template <typename A>
+struct ManyArgs : LutArgs<A> {
+    int32_t t;                 // log2 of the outputs per gate, 0 .. 3
+};
+struct TvMany : TvLut {
+    static constexpr bool MANY = true;
+    int32_t t;
+};
+template <typename A>
+__device__ __forceinline__ TvMany tv_many(const ManyArgs<A>& p, int32_t* fault) { return TvMany{{p.tv, p.tv_idx, p.n_tv, fault}, p.t}; }
+
+// The mod switch (tfhe.rs:97, 107-108) of one pre-stepped word at SH + k, scaled back by 2^k: b floor, a_i rounded, both to multiples of 2^k
+// in [0, 2N).  k = tv_shift(tvs): t for many-LUT, 0 otherwise.  The bodies call it under `if constexpr (MANY)` and keep their own k = 0
+// expression for the gates' and the PBS's kernels: routed through this function (k a compile-time 0) those kernels' code changed by a few
+// instructions.
+__device__ __forceinline__ int tv_shift(const TvGate&) { return 0; }
+__device__ __forceinline__ int tv_shift(const TvLut&) { return 0; }
+__device__ __forceinline__ int tv_shift(const TvMany& t) { return t.t; }
+template <int SH>
+__device__ __forceinline__ uint32_t mod_switch(uint32_t x, bool isb, int k) {
+    return isb ? ((x >> (SH + k)) << k) : (((x + (1u << (SH + k - 1))) >> (SH + k)) << k);
+}
+
+// Many-LUT epilogue: sample extract index j = 0 .. 2^t - 1 of the rotated accumulator acc (LDS: b-poly at [0, N), and at [N, 2N) the index-0
+// sample a'_0[c] = a_0, -a_{N-c} the body has already put there) into the key switch's operand rows (ge << t) + j.  Index j is a'_0 times
+// X^j, negacyclically: a'_j[c] = a_{j-c} for c <= j, -a_{N+j-c} above (trlwe.rs:110-121), i.e. a'_0[c - j] for c >= j and -a'_0[N + c - j]
+// below; b'_j = b_j.  This thread stores coefficients c0, c0 + step, ... < c1 of every output and, if 0 <= bl < 2^t, b' of output bl.
+template <int N>
+__device__ __forceinline__ void many_extract(uint32_t* ext, int ge, int t, const uint32_t* acc, int c0, int c1, int step, int bl) {
+    const int outs = 1 << t;
+    for (int j = 0; j < outs; j++) {
+        const int row = (ge << t) + j;
+        for (int c = c0; c < c1; c += step) *ext_slot(ext, row, c, N) = c >= j ? acc[N + c - j] : 0u - acc[2 * N + c - j];
+    }
+    if (bl >= 0 && bl < outs) *ext_slot(ext, (ge << t) + bl, N, N) = acc[bl];
+}
 
 // One external product / CMUX on the wave-private accumulator in LDS.
 //   CMUX = true : acc <- cross(bk_i, X^r * acc - acc) + acc      (trgsw.rs:319-321, tfhe.rs:103-110)
@@ -345,6 +388,12 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_pbs(const LutArgs<BootstrapAr
     const TvLut tvs = tv_lut(p, a.fault);
 #include "rtfhe_body_wave.hpp"
 }
+template <int LOGN, int L, int BGBIT, int KS_T, int KS_BB, int KSQ, int WAVES>
+__global__ __launch_bounds__(64 * WAVES, 1) void k_pbs_many(const ManyArgs<BootstrapArgs> p) {
+    const BootstrapArgs& a = p.base;
+    const TvMany tvs = tv_many(p, a.fault);
+#include "rtfhe_body_wave.hpp"
+}
 
 // ------------------------------------------------------------------------------------------------
 // stage-level kernels (one wave per item)
@@ -534,6 +583,27 @@ struct KeySwitchArgs {
     uint32_t* out;           // [count][n+1]
     int32_t count, n, ksw;
 };
+
+// the identity key switch of `count` lvl1 samples laid out for k_key_switch_mm (ext_slot), one wave each: a many-LUT PBS's batch key switch on a
+// context without the matrix form of the key (RTFHE_KS_MM_MIN=0)
+struct KeySwitchExtArgs {
+    const uint32_t* ksk;
+    uint32_t* ext;           // tiles of 16 samples (ext_slot); read only
+    uint32_t* out;           // [count][n+1]
+    int32_t count, n, ksw;
+};
+template <int LOGN, int KS_T, int KS_BB, int KSQ, int WAVES>
+__global__ __launch_bounds__(64 * WAVES, 1) void k_key_switch_ext(const KeySwitchExtArgs a) {
+    constexpr int N = 1 << LOGN;
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = blockIdx.x * WAVES + wave;
+    if (g >= a.count) return;
+    uint32_t* ap = reinterpret_cast<uint32_t*>(smem) + (size_t)wave * N;
+    for (int c = lane; c < N; c += 64) ap[c] = *ext_slot(a.ext, g, c, N);
+    wave_lds_sync();
+    key_switch_wave<LOGN, KS_T, KS_BB, KSQ>(ap, *ext_slot(a.ext, g, N, N), a.ksk, a.ksw, a.n, a.out + (size_t)g * (a.n + 1), lane);
+}
 
 template <int LOGN, int KS_T, int KS_BB, int KSQ, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_key_switch(const KeySwitchArgs a) {

@@ -55,5 +55,11 @@ __global__ __launch_bounds__(256 * GATES, 1) void k_pbs_eo4(const LutArgs<EoArgs
     const TvLut tvs = tv_lut(p, ea.b.fault);
 #include "rtfhe_body_eo4.hpp"
 }
+template <int L, int BGBIT, int GATES>
+__global__ __launch_bounds__(256 * GATES, 1) void k_pbs_many_eo4(const ManyArgs<EoArgs> p) {
+    const EoArgs& ea = p.base;
+    const TvMany tvs = tv_many(p, ea.b.fault);
+#include "rtfhe_body_eo4.hpp"
+}
 
 }  // namespace rtfhe

@@ -43,5 +43,11 @@ __global__ __launch_bounds__(512, 1) void k_pbs_pair_rr(const LutArgs<BootstrapA
     const TvLut tvs = tv_lut(p, a.fault);
 #include "rtfhe_body_pair_rr.hpp"
 }
+template <int L, int BGBIT, int KS_T, int KS_BB, int KSQ>
+__global__ __launch_bounds__(512, 1) void k_pbs_many_pair_rr(const ManyArgs<BootstrapArgs> p) {
+    const BootstrapArgs& a = p.base;
+    const TvMany tvs = tv_many(p, a.fault);
+#include "rtfhe_body_pair_rr.hpp"
+}
 
 }  // namespace rtfhe

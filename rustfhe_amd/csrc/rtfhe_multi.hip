@@ -60,13 +60,14 @@ int sharded_host_bootstrap(rtfhe_ctx* ctx, int op, int mode, int steps, const ui
 }
 
 // programmable bootstrap of host buffers: the same ranges, each with its range of lut_idx and the table copy of its device
-int sharded_host_pbs(rtfhe_ctx* ctx, const rtfhe_lut* lut, const int32_t* lut_idx, const uint32_t* in, uint32_t* out, size_t count) {
-    if (ctx->peers.empty()) return run_host_pbs_one(ctx, lut_on(lut, 0, nullptr), lut_idx, in, out, count);
+// (shift >= 0: a many-LUT PBS, the 2^shift output rows of a gate stay together)
+int sharded_host_pbs(rtfhe_ctx* ctx, const rtfhe_lut* lut, const int32_t* lut_idx, const uint32_t* in, uint32_t* out, size_t count, int32_t shift) {
+    if (ctx->peers.empty()) return run_host_pbs_one(ctx, lut_on(lut, 0, nullptr, shift), lut_idx, in, out, count);
     const int n_dev = 1 + (int)ctx->peers.size();
-    const size_t w = (size_t)ctx->p.n + 1;
+    const size_t w = (size_t)ctx->p.n + 1, ow = shift > 0 ? w << shift : w;
     return for_each_device(ctx, [&](rtfhe_ctx* c, int d) {
         const size_t b = shard_begin(count, d, n_dev), e = shard_begin(count, d + 1, n_dev);
-        return run_host_pbs_one(c, lut_on(lut, d, nullptr), lut_idx ? lut_idx + b : nullptr, in + b * w, out + b * w, e - b);
+        return run_host_pbs_one(c, lut_on(lut, d, nullptr, shift), lut_idx ? lut_idx + b : nullptr, in + b * w, out + b * ow, e - b);
     });
 }
 
@@ -101,10 +102,11 @@ int sharded_host_mux(rtfhe_ctx* ctx, const uint32_t* c, const uint32_t* in0, con
 // A failure part-way leaves nothing dangling: s still waits for every peer already launched (they may be writing d_out), the current device is
 // the primary's again, and the first error is what the call returns.
 int sharded_dev_batch(rtfhe_ctx* ctx, int op, const void* d_c, const void* d_in0, const void* d_in1, void* d_out, size_t count, hipStream_t s,
-                      const rtfhe_lut* lut, const int32_t* d_lut_idx) {
+                      const rtfhe_lut* lut, const int32_t* d_lut_idx, int32_t shift) {
     if (int rc = use(ctx)) return rc;
-    const bool mux = op < 0;
+    const bool mux = op < 0, many = lut && shift >= 0;
     auto run = [&](rtfhe_ctx* c, int d, const void* cc, const void* i0, const void* i1, void* o, size_t cnt, hipStream_t st, const int32_t* idx) {
+        if (many) return launch_pbs_many(c, lut_on(lut, d, idx, shift), i0, o, cnt, st);
         return mux ? mux_dev_one(c, cc, i0, i1, o, cnt, st)
                    : launch_bootstrap(c, op, MODE_GATE, c->p.n, i0, i1, o, cnt, st, nullptr, nullptr, nullptr, nullptr, 0, lut_on(lut, d, idx));
     };
@@ -115,7 +117,7 @@ int sharded_dev_batch(rtfhe_ctx* ctx, int op, const void* d_c, const void* d_in0
     if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
     if (cs != hipStreamCaptureStatusNone) return run(ctx, 0, d_c, d_in0, d_in1, d_out, count, s, d_lut_idx);
     const int n_dev = 1 + (int)ctx->peers.size();
-    const size_t w = (size_t)ctx->p.n + 1;
+    const size_t w = (size_t)ctx->p.n + 1, ow = many ? w << shift : w;      // words per gate in, out
     auto at = [&](const void* p, size_t gate) { return p ? (const void*)((const uint32_t*)p + gate * w) : nullptr; };
     // is p device memory of the primary?  (only then may hipMemcpyPeerAsync be told so)
     auto on_primary = [&](const void* p) {
@@ -134,7 +136,7 @@ int sharded_dev_batch(rtfhe_ctx* ctx, int op, const void* d_c, const void* d_in0
         int rc = use(peer);
         if (!rc) rc = ensure(peer, &peer->d_a, &peer->cap_a, bytes);
         if (!rc && (d_in1 || mux || ship_idx)) rc = ensure(peer, &peer->d_b, &peer->cap_b, bytes);
-        if (!rc) rc = ensure(peer, &peer->d_c, &peer->cap_c, bytes);
+        if (!rc) rc = ensure(peer, &peer->d_c, &peer->cap_c, bytes / w * ow);
         if (rc) { (void)hipSetDevice(ctx->device); return fail(ctx, rc, peer->err); }
     }
     if (int rc = use(ctx)) return rc;
@@ -176,9 +178,11 @@ int sharded_dev_batch(rtfhe_ctx* ctx, int op, const void* d_c, const void* d_in0
         }
         ok = ok && hip(hipEventRecord(peer->ev_sh[2], peer->stream), "hipEventRecord");
         if (ok) {
-            void* dst = (uint32_t*)d_out + b * w;
+            void* dst = (uint32_t*)d_out + b * ow;
             const void* src = mux ? peer->d_a : peer->d_c;
-            ok = hip(peer_copies ? hipMemcpyPeerAsync(dst, ctx->device, src, peer->device, bytes, peer->stream) : hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, peer->stream),
+            const size_t out_bytes = cnt * ow * 4;
+            ok = hip(peer_copies ? hipMemcpyPeerAsync(dst, ctx->device, src, peer->device, out_bytes, peer->stream)
+                                 : hipMemcpyAsync(dst, src, out_bytes, hipMemcpyDefault, peer->stream),
                      "copy of the outputs to the primary");
         }
         // whatever was enqueued on the peer's stream so far is fenced by this event, complete or not

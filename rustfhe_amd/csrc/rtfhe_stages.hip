@@ -53,6 +53,17 @@ int launch_keyswitch_t(rtfhe_ctx* ctx, KeySwitchArgs a, hipStream_t s) {
 }
 
 template <int LOGN>
+int launch_keyswitch_ext_t(rtfhe_ctx* ctx, KeySwitchExtArgs a, hipStream_t s) {
+    constexpr int W = 4;
+    auto k = k_key_switch_ext<LOGN, 8, 2, KSQ, W>;
+    const size_t lds = (size_t)W * (1 << LOGN) * 4;
+    hipLaunchKernelGGL(k, dim3((a.count + W - 1) / W), dim3(64 * W), lds, s, a);
+    HIPCHECK(ctx, hipGetLastError());
+    ctx->launches++;
+    return 0;
+}
+
+template <int LOGN>
 int launch_permute_t(rtfhe_ctx* ctx, const double* src, double* dst, size_t count, int dir, int rows, hipStream_t s) {
     hipLaunchKernelGGL(k_bk_permute<LOGN>, dim3(2048), dim3(256), 0, s, src, dst, count, dir, rows);
     HIPCHECK(ctx, hipGetLastError());
@@ -141,6 +152,11 @@ int launch_key_switch_mm(rtfhe_ctx* ctx, const BootstrapArgs& a, const uint32_t*
     if (ev_b) HIPCHECK(ctx, hipEventRecord(ev_b, s));
     ctx->launches++;
     return 0;
+}
+
+int launch_key_switch_ext(rtfhe_ctx* ctx, uint32_t* samples, uint32_t* d_out, size_t count, hipStream_t s) {
+    const KeySwitchExtArgs a{ctx->d_ksk, samples, d_out, (int32_t)count, ctx->p.n, ctx->ksw};
+    return ctx->logn == 10 ? launch_keyswitch_ext_t<10>(ctx, a, s) : launch_keyswitch_ext_t<11>(ctx, a, s);
 }
 
 }  // namespace rtfhe_host

@@ -255,6 +255,22 @@ class Engine:
         self._ck(self.L.rtfhe_pbs_batch_dev(self.h, lut.h, self._dev(d_lut_idx), self._dev(d_tlwe), self._dev(d_out), count,
                                             C.c_void_p(stream) if stream else None))
 
+    def pbs_many_batch(self, lut, tlwe, n_out, lut_idx=None):
+        """Many-LUT PBS (include/rtfhe.h: rtfhe_pbs_many_batch): n_out (1, 2, 4 or 8) functions of each ciphertext from ONE blind rotation,
+        u32[count][n_out][n+1].  Tables interleave the functions (rustfhe_amd.many_lut_polynomial); indices are checked as in pbs_batch."""
+        tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)
+        idx = None if lut_idx is None else _np(lut_idx, np.int32).reshape(-1)
+        assert idx is None or idx.size == tlwe.shape[0], "one table index per ciphertext"
+        out = np.empty((tlwe.shape[0], max(int(n_out), 0), self.p.n + 1), np.uint32)
+        self._ck(self.L.rtfhe_pbs_many_batch(self.h, lut.h, int(n_out), _ptr(idx), _ptr(tlwe), _ptr(out), tlwe.shape[0]))
+        return out
+
+    def pbs_many_batch_dev(self, lut, d_tlwe, d_out, count, n_out, d_lut_idx=None, stream=None):
+        """... on device buffers (d_out: [count][n_out][n+1] words), asynchronous on `stream`; bad indices are reported by the next sync().
+        Inside a stream capture an eager call of at least `count` gates and this n_out must have run on the stream first."""
+        self._ck(self.L.rtfhe_pbs_many_batch_dev(self.h, lut.h, int(n_out), self._dev(d_lut_idx), self._dev(d_tlwe), self._dev(d_out), count,
+                                                 C.c_void_p(stream) if stream else None))
+
     # ---- stage level ------------------------------------------------------------------------
     def blind_rotate_batch(self, tlwe, steps=None):
         tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)

@@ -1,4 +1,4 @@
-"""Encoding of small integers for programmable bootstrapping (Engine.pbs_batch): messages, test polynomials, decoding.
+"""Encoding of small integers for programmable bootstrapping (Engine.pbs_batch, Engine.pbs_many_batch): messages, test polynomials, decoding.
 
 One padding bit: a message m in [0, 2^p) is the torus word m * 2^(32-p-1), so every valid phase lies in the upper half-circle's
 complement [0, 1/2) and the blind rotation never needs the negacyclic half of the test polynomial for it.
@@ -64,3 +64,37 @@ def lut_polynomial(f, N, msg_bits, out_bits=None, raw=False):
     top = j >= N - B // 2
     tv[top] = (np.uint64(1 << 32) - enc[0]) & np.uint64(0xFFFFFFFF)
     return tv.astype(np.uint32)
+
+
+def many_lut_polynomial(fs, N, msg_bits, out_bits=None, raw=False):
+    """The test polynomial (u32[N]) of a many-LUT PBS (Engine.pbs_many_batch with n_out = len(fs)): theta = len(fs) functions of the same
+    message, interleaved.  Each f in fs is what lut_polynomial takes (a callable or 2^msg_bits values); out_bits and raw apply to all of them.
+
+    Why this computes all of them.  The many-LUT PBS rounds the mod switch to multiples of theta = 2^t: the rotation is k ~ m * B with k a
+    multiple of theta (B = N / 2^p as in the module docstring), and output j is coefficient j of X^{-k} * tv,
+
+        tv[k + j]          for 0 <= k + j < N
+        -tv[k + j - N]     for N <= k + j < 2N
+
+    so the block of theta coefficients k .. k + theta - 1 carries one value of every function.  If theta divides B / 2 (theta <= N / 2^(p+1)),
+    the box edges m B - B/2 are multiples of theta and no block straddles two boxes: a message m > 0 lands in a block inside
+    [m B - B/2, m B + B/2), so tv[i] = enc_out(f_{i mod theta}(floor((i - i mod theta + B/2) / B))) for i - i mod theta < N - B/2.  Message 0
+    also lands in a block k in [2N - B/2, 2N) (k + j < 2N, since k <= 2N - theta): coefficient j is -tv[k + j - N], k + j - N in
+    [N - B/2, N), which must be enc_out(f_j(0)) -- hence tv[i] = -enc_out(f_{i mod theta}(0)) on the top half-box.  In short
+    tv[i] = lut_polynomial(f_{i mod theta})[i - i mod theta]: with one function this is lut_polynomial's table exactly.  The coarser rounding
+    multiplies the input's mod-switch error by theta (include/rtfhe.h)."""
+    fs = list(fs)
+    th = len(fs)
+    if th not in (1, 2, 4, 8):
+        raise ValueError("a many-LUT PBS takes 1, 2, 4 or 8 functions (got %d)" % th)
+    if (1 << msg_bits) > N // 2:
+        raise ValueError("a box must hold at least two coefficients: msg_bits <= log2(N) - 1")
+    if th > N >> (msg_bits + 1):
+        raise ValueError("%d functions need half a box of at least %d coefficients: msg_bits <= log2(N) - 1 - log2(len(fs))" % (th, th))
+    tabs = [lut_polynomial(f, N, msg_bits, out_bits=out_bits, raw=raw) for f in fs]
+    i = np.arange(N)
+    base = i - i % th
+    tv = np.empty(N, np.uint32)
+    for j in range(th):
+        tv[j::th] = tabs[j][base[j::th]]
+    return tv
