@@ -111,6 +111,10 @@ extern "C" {
                                 count: usize) -> c_int;
     pub fn rtfhe_pbs_many_batch_dev(ctx: *mut rtfhe_ctx, lut: *const rtfhe_lut, n_out: i32, d_lut_idx: *const c_void, d_tlwe: *const c_void,
                                     d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
+    // LUT circuits: waves of many-LUT bootstraps of weighted wire sums, recorded into one graph (replay / free with rtfhe_circuit_launch / _destroy)
+    pub fn rtfhe_lut_circuit_create(ctx: *mut rtfhe_ctx, lut: *const rtfhe_lut, fan_in: i32, in_idx: *const i32, weights: *const i32, cst: *const u32,
+                                    lut_idx: *const i32, wave_offsets: *const i32, wave_n_out: *const i32, num_waves: i32, out_idx: *const i32,
+                                    d_wires: *mut c_void, num_wires: usize, out: *mut *mut rtfhe_circuit) -> c_int;
     pub fn rtfhe_sync(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_begin(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_end(ctx: *mut rtfhe_ctx, stream: *mut c_void, ms: *mut f64, launches: *mut i64) -> c_int;

@@ -26,6 +26,8 @@
  *                                       caller-supplied test polynomials: programmable bootstrapping
  *   rtfhe_pbs_many_batch[_dev]       (no reference counterpart) several tables from one blind rotation: sample extract at indices
  *                                       0 .. n_out-1 (TRLWERep::sample_extract_index, hom_nand/src/trlwe.rs:110-121)
+ *   rtfhe_lut_circuit_create         (no reference counterpart) netlists of many-LUT bootstraps of weighted wire sums, recorded once and
+ *                                       replayed through rtfhe_circuit_launch
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch           <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -123,7 +125,7 @@ int rtfhe_ctx_create_multi(const rtfhe_params *p, const int *device_ids, int n_d
 int rtfhe_ctx_device_count(const rtfhe_ctx *ctx);      /* devices behind this context (1 for rtfhe_ctx_create) */
 /* device memory entry d (0 = primary) of the context holds right now, in bytes: the keys in every form built so far (second layouts of
  * the bootstrapping key are built by the first batch whose kernel shape reads them), staging and scratch buffers.  Not counted: the twiddle
- * tables (a few hundred KiB) and the sample buffers of live circuits. */
+ * tables (a few hundred KiB), the sample buffers of live circuits and the buffers of live LUT circuits (rtfhe_lut_circuit_create). */
 int rtfhe_ctx_memory_bytes(const rtfhe_ctx *ctx, int d, size_t *bytes);
 /* What the runtime reported about entry d (1 <= d < rtfhe_ctx_device_count) of a multi-device context against entry 0, the primary, when
  * rtfhe_ctx_create_multi set it up -- peer access is queried in both directions and enabled explicitly there, never left to a first copy -- and
@@ -276,6 +278,41 @@ int rtfhe_pbs_many_batch(rtfhe_ctx *ctx, const rtfhe_lut *lut, int32_t n_out, co
                          const uint32_t *tlwe /* [count][n+1] */, uint32_t *out /* [count][n_out][n+1] */, size_t count);
 int rtfhe_pbs_many_batch_dev(rtfhe_ctx *ctx, const rtfhe_lut *lut, int32_t n_out, const void *d_lut_idx /* int32[count] or NULL */,
                              const void *d_tlwe, void *d_out /* [count][n_out][n+1] */, size_t count, void *stream);
+/* ---- LUT circuits: netlists of many-LUT bootstraps, recorded once and replayed as one submission ----
+ * A LUT circuit works on the wire table d_wires, u32[num_wires][n+1] lvl0 ciphertexts in device memory, as a gate circuit does.  It is a
+ * sequence of waves: wave w holds nodes wave_offsets[w] .. wave_offsets[w+1] (host array, num_waves + 1 entries, strictly increasing from
+ * >= 0, as for rtfhe_circuit_create) and one n_out ϑ = wave_n_out[w] ∈ {1, 2, 4, 8}.  Node g of wave w computes
+ *
+ *     t     = Σ_k weights[g][k] · wire[in_idx[g][k]]     k = 0 .. fan_in-1; wrapping u32 arithmetic on all n+1 words; in_idx -1 = unused slot
+ *     t.b  += cst[g]                                      a torus constant on the b word only (cst NULL: 0)
+ *     out   = many-LUT PBS of t with table lut_idx[g] and ϑ outputs      (exactly rtfhe_pbs_many_batch; lut_idx NULL: table 0)
+ *     wire[out_idx[r + j]] = out[j],  j = 0 .. ϑ-1,  r = Σ_{v<w} (nodes of v) · ϑ_v + (g - wave_offsets[w]) · ϑ
+ *
+ * i.e. out_idx lists the output wires wave by wave, node by node, starting with the first node of wave 0.  Every node of a wave reads the wire
+ * table as it stood before the wave, so a wave may overwrite a wire it also reads (a carry updated in place); two nodes of one wave must not
+ * write the same wire.  All description arrays are host memory (in_idx, weights: [nodes][fan_in] with fan_in 1 .. 8, indexed by the absolute
+ * node number g; cst, lut_idx: [nodes]).  They are checked completely before anything is allocated or captured -- every index in range, each
+ * n_out 1, 2, 4 or 8, no wire written twice in one wave, the wave_offsets rules -- and a failed check returns RTFHE_ERR_INVALID naming the wave
+ * and the node, with nothing launched.  The FP64 mirror backend only: on either exact backend creation fails with RTFHE_ERR_INVALID.
+ *
+ * Each wave is recorded as three steps of one single-stream capture on the primary device: k_lut_gather writes the wave's sums into a
+ * circuit-owned buffer, the many-LUT PBS (bootstrap in sample-extract mode, then the batch key switch) writes [count][ϑ][n+1] into another,
+ * k_lut_scatter copies the rows to their wires.  The returned handle is an ordinary rtfhe_circuit: rtfhe_circuit_launch replays it (asynchronous),
+ * rtfhe_circuit_destroy frees it, and the rules for a context destroyed first are rtfhe_circuit_create's.  Keys are read in place: a key
+ * loaded on the context later is what the next replay computes with.  The wire table must stay alive and in place while the circuit exists;
+ * nothing else must: the circuit owns its own copy of the description and of the table rows, so the rtfhe_lut may be destroyed right after
+ * creation.  Its device footprint, not counted by rtfhe_ctx_memory_bytes (as for gate circuits' sample buffers):
+ *     description      4 · (nodes · (2 fan_in + 2) + Σ_w nodes_w · ϑ_w)  bytes
+ *     gathered inputs  4 · (n+1) · max_w nodes_w
+ *     key-switched     4 · (n+1) · max_w nodes_w · ϑ_w
+ *     sample buffer    4 · (N+1) · max(1024, max_w nodes_w · ϑ_w) rounded up to 16
+ *     table rows       4 · N · n_lut */
+int rtfhe_lut_circuit_create(rtfhe_ctx *ctx, const rtfhe_lut *lut, int32_t fan_in /* 1 .. 8 */,
+                             const int32_t *in_idx /* [nodes][fan_in] */, const int32_t *weights /* [nodes][fan_in] */,
+                             const uint32_t *cst /* [nodes] or NULL */, const int32_t *lut_idx /* [nodes] or NULL */,
+                             const int32_t *wave_offsets /* [num_waves + 1] node offsets */, const int32_t *wave_n_out /* [num_waves] */,
+                             int32_t num_waves, const int32_t *out_idx /* [Σ over nodes of its wave's n_out] */, void *d_wires,
+                             size_t num_wires, rtfhe_circuit **out);
 /* waits for `stream`; also reports (once) a netlist gate skipped since the previous call */
 int rtfhe_sync(rtfhe_ctx *ctx, void *stream);
 /* device-side timing of the launches enqueued by the *_dev calls between begin and end (HIP events on

@@ -7,7 +7,8 @@ from ._ffi import AND, ANDNY, COPY, NAND, NOT, OR, XOR, Params, load  # noqa: F4
 from .engine import (Engine, FftPlan, Lut, RtfheError, decrypt_bits, device_link, encrypt_bits, encrypt_torus, keygen, ksk_expand_ref, load_keys,  # noqa: F401
                      load_tlwe, phases, pinned_empty, save_keys, save_tlwe, shard_range)
 from .pbs import decode_msgs, encode_msgs, lut_polynomial, many_lut_polynomial  # noqa: F401
+from .lut_circuit import LutCircuitRunner, LutNetlist, lut_ripple_adder  # noqa: F401
 
 __all__ = ["Engine", "FftPlan", "Params", "RtfheError", "keygen", "ksk_expand_ref", "encrypt_bits", "decrypt_bits", "phases", "save_keys", "load_keys", "save_tlwe", "load_tlwe", "pinned_empty", "shard_range", "device_link",
-           "Lut", "encrypt_torus", "encode_msgs", "decode_msgs", "lut_polynomial", "many_lut_polynomial",
+           "Lut", "encrypt_torus", "encode_msgs", "decode_msgs", "lut_polynomial", "many_lut_polynomial", "LutNetlist", "LutCircuitRunner", "lut_ripple_adder",
            "NAND", "AND", "OR", "XOR", "NOT", "COPY", "ANDNY", "load"]

@@ -116,10 +116,11 @@ int run_host_pbs_one(rtfhe_ctx* ctx, const LutRef& lut, const int32_t* lut_idx, 
 // Many-LUT PBS on one device (include/rtfhe.h: rtfhe_pbs_many_batch): the bootstrap kernels' many-LUT twins in MODE_EXTRACT write the 2^shift
 // samples of every gate into this stream's sample buffer at batch-wide rows (gate << shift) + j, then ONE batch key switch of count << shift
 // rows writes [count][2^shift][n+1] -- with the matrix form of the key as the split path does (into the zeroed output), else one wave per
-// sample.  Outside a stream capture the sample buffer grows and the second key layout is built here; inside one (never rtfhe_circuit_create's:
-// circuits hold no PBS) nothing may be allocated: this stream's buffer must already hold count << shift samples -- an eager many-PBS of at least
-// `count` gates and at least this many outputs on the stream first -- and is then kept for as long as the context lives (Tlwe1::captured).
-int launch_pbs_many(rtfhe_ctx* ctx, const LutRef& lut, const void* d_in, void* d_out, size_t count, hipStream_t s) {
+// sample.  Outside a stream capture the sample buffer grows and the second key layout is built here; inside one nothing may be allocated: the
+// sample buffer is rtfhe_lut_circuit_create's own (handed over through tlwe1_capture), or else this stream's, which must already hold
+// count << shift samples -- an eager many-PBS of at least `count` gates and at least this many outputs on the stream first -- and is then kept
+// for as long as the context lives (Tlwe1::captured).
+int launch_pbs_many(rtfhe_ctx* ctx, const LutRef& lut, const void* d_in, void* d_out, size_t count, hipStream_t s, bool zero_out) {
     if (!ctx->has_bk) return fail(ctx, RTFHE_ERR_STATE, "bootstrapping key not loaded");
     if (!ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "key-switching key not loaded");
     if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
@@ -149,7 +150,7 @@ int launch_pbs_many(rtfhe_ctx* ctx, const LutRef& lut, const void* d_in, void* d
     a.ext = buf->d; a.ext_first = 0;
     if (int rc = launch_bootstrap_fft(ctx, a, s, lut)) return rc;
     if (!ctx->d_ksmat) return launch_key_switch_ext(ctx, buf->d, (uint32_t*)d_out, rows, s);
-    HIPCHECK(ctx, hipMemsetAsync(d_out, 0, rows * ((size_t)ctx->p.n + 1) * 4, s));      // the K-slices add into it
+    if (zero_out) HIPCHECK(ctx, hipMemsetAsync(d_out, 0, rows * ((size_t)ctx->p.n + 1) * 4, s));      // the K-slices add into it
     BootstrapArgs k = a;
     k.count = (int32_t)rows;
     return launch_key_switch_mm(ctx, k, buf->d, s);

@@ -1,6 +1,8 @@
 // rtfhe_circuit.hip -- levelised netlists (BASELINE config 4): one dependency wave per call, or every wave of a netlist recorded once into a
-// HIP graph and replayed as one submission.  Replaces eval_logic_expr over impl Logip for TFHE (nander/src/lib.rs:40-89).
+// HIP graph and replayed as one submission.  Replaces eval_logic_expr over impl Logip for TFHE (nander/src/lib.rs:40-89).  LUT circuits
+// (rtfhe_lut_circuit_create): netlists of many-LUT bootstraps of weighted wire sums, recorded the same way.
 #include "rtfhe_host.hpp"
+#include "rtfhe_kernels_lutc.hpp"
 
 #include <algorithm>
 
@@ -15,8 +17,49 @@ void circuit_release(rtfhe_circuit* c) {
     if (c->exec) (void)hipGraphExecDestroy(c->exec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     if (c->d_samples) (void)hipFree(c->d_samples);
-    c->exec = nullptr; c->graph = nullptr; c->d_samples = nullptr;
+    for (void* d : c->d_owned) (void)hipFree(d);
+    c->exec = nullptr; c->graph = nullptr; c->d_samples = nullptr; c->d_owned.clear();
 }
+
+// ---- LUT circuits: the gather / scatter launches around a wave's many-LUT PBS ----
+namespace {
+
+template <int F>
+int launch_lut_gather_f(rtfhe_ctx* ctx, bool vec, const LutGatherArgs& a, hipStream_t s) {
+    const dim3 grid((a.count + LUTC_WAVES - 1) / LUTC_WAVES), block(64 * LUTC_WAVES);
+    if (vec) hipLaunchKernelGGL((k_lut_gather<F, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_lut_gather<F, false>), grid, block, 0, s, a);
+    HIPCHECK(ctx, hipGetLastError());
+    ctx->launches++;
+    return 0;
+}
+
+int launch_lut_gather(rtfhe_ctx* ctx, int fan_in, bool vec, const LutGatherArgs& a, hipStream_t s) {
+    switch (fan_in) {
+        case 1: return launch_lut_gather_f<1>(ctx, vec, a, s);
+        case 2: return launch_lut_gather_f<2>(ctx, vec, a, s);
+        case 3: return launch_lut_gather_f<3>(ctx, vec, a, s);
+        case 4: return launch_lut_gather_f<4>(ctx, vec, a, s);
+        case 5: return launch_lut_gather_f<5>(ctx, vec, a, s);
+        case 6: return launch_lut_gather_f<6>(ctx, vec, a, s);
+        case 7: return launch_lut_gather_f<7>(ctx, vec, a, s);
+        case 8: return launch_lut_gather_f<8>(ctx, vec, a, s);
+        default: return fail(ctx, RTFHE_ERR_INVALID, "fan_in out of range");
+    }
+}
+
+int launch_lut_scatter(rtfhe_ctx* ctx, bool vec, const LutScatterArgs& a, hipStream_t s) {
+    const dim3 grid((a.rows + LUTC_WAVES - 1) / LUTC_WAVES), block(64 * LUTC_WAVES);
+    if (vec) hipLaunchKernelGGL((k_lut_scatter<true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_lut_scatter<false>), grid, block, 0, s, a);
+    HIPCHECK(ctx, hipGetLastError());
+    ctx->launches++;
+    return 0;
+}
+
+std::string at(int32_t w, int64_t g) { return "wave " + std::to_string(w) + ", node " + std::to_string(g) + ": "; }
+
+}  // namespace
 
 }  // namespace rtfhe_host
 
@@ -80,6 +123,136 @@ int rtfhe_circuit_create(rtfhe_ctx* ctx, const void* d_ops, const void* d_idx0, 
     if (e != hipSuccess) { circuit_release(c); delete c; return fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e)); }
     e = hipGraphInstantiate(&c->exec, c->graph, nullptr, nullptr, 0);
     if (e != hipSuccess) { circuit_release(c); delete c; return fail(ctx, RTFHE_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
+    ctx->circuits.push_back(c);
+    *out = c;
+    return 0;
+}
+
+// ---- a LUT circuit: waves of "weighted sum of wires, then a many-LUT PBS", recorded like rtfhe_circuit_create ----
+int rtfhe_lut_circuit_create(rtfhe_ctx* ctx, const rtfhe_lut* lut, int32_t fan_in, const int32_t* in_idx, const int32_t* weights, const uint32_t* cst,
+                             const int32_t* lut_idx, const int32_t* wave_offsets, const int32_t* wave_n_out, int32_t num_waves, const int32_t* out_idx,
+                             void* d_wires, size_t num_wires, rtfhe_circuit** out) {
+    if (int rc = use(ctx)) return rc;
+    if (!out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!lut) return fail(ctx, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
+    if (!lut->ctx) return fail(ctx, RTFHE_ERR_STATE, "the table's context has been destroyed");
+    if (lut->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the table belongs to another context");
+    if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
+        return fail(ctx, RTFHE_ERR_INVALID, "LUT circuits (programmable bootstrapping) run on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR); "
+                                            "select it with rtfhe_set_backend");
+    if (!in_idx || !weights || !wave_offsets || !wave_n_out || !out_idx || !d_wires) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (fan_in < 1 || fan_in > 8) return fail(ctx, RTFHE_ERR_INVALID, "fan_in = " + std::to_string(fan_in) + " is outside [1, 8]");
+    if (num_waves < 1 || num_wires == 0 || num_wires > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "num_waves / num_wires out of range");
+    // the whole description is checked before anything is allocated, captured or launched
+    const int32_t nw = (int32_t)num_wires;
+    std::vector<int32_t> written(num_wires, -1);          // the wave that last wrote each wire
+    std::vector<int32_t> out_base(num_waves + 1, 0);      // first row of each wave in out_idx
+    size_t widest = 0, widest_rows = 0;
+    for (int32_t w = 0; w < num_waves; w++) {
+        if (wave_offsets[w] < 0 || wave_offsets[w + 1] <= wave_offsets[w])
+            return fail(ctx, RTFHE_ERR_INVALID, "wave " + std::to_string(w) + ": wave_offsets must be strictly increasing from >= 0");
+        const int32_t th = wave_n_out[w];
+        if (th != 1 && th != 2 && th != 4 && th != 8)
+            return fail(ctx, RTFHE_ERR_INVALID, "wave " + std::to_string(w) + ": n_out = " + std::to_string(th) + ": a many-LUT PBS gives 1, 2, 4 or 8 outputs per node");
+        const size_t cnt = (size_t)(wave_offsets[w + 1] - wave_offsets[w]);
+        if ((size_t)out_base[w] + cnt * th > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "wave " + std::to_string(w) + ": too many output rows");
+        out_base[w + 1] = out_base[w] + (int32_t)(cnt * th);
+        widest = std::max(widest, cnt);
+        widest_rows = std::max(widest_rows, cnt * th);
+        for (int32_t g = wave_offsets[w]; g < wave_offsets[w + 1]; g++) {
+            for (int32_t k = 0; k < fan_in; k++) {
+                const int32_t i = in_idx[(size_t)g * fan_in + k];
+                if (i < -1 || i >= nw)
+                    return fail(ctx, RTFHE_ERR_INVALID, at(w, g) + "in_idx[" + std::to_string(g) + "][" + std::to_string(k) + "] = " + std::to_string(i) +
+                                                        " is outside [-1, num_wires)");
+            }
+            if (lut_idx && (uint32_t)lut_idx[g] >= (uint32_t)lut->n_lut)
+                return fail(ctx, RTFHE_ERR_INVALID, at(w, g) + "lut_idx[" + std::to_string(g) + "] = " + std::to_string(lut_idx[g]) + " is outside [0, " +
+                                                    std::to_string(lut->n_lut) + ")");
+            for (int32_t j = 0; j < th; j++) {
+                const size_t r = (size_t)out_base[w] + (size_t)(g - wave_offsets[w]) * th + j;
+                const int32_t o = out_idx[r];
+                if (o < 0 || o >= nw)
+                    return fail(ctx, RTFHE_ERR_INVALID, at(w, g) + "out_idx[" + std::to_string(r) + "] = " + std::to_string(o) + " is outside [0, num_wires)");
+                if (written[o] == w) return fail(ctx, RTFHE_ERR_INVALID, at(w, g) + "wire " + std::to_string(o) + " is written twice in this wave");
+                written[o] = w;
+            }
+        }
+    }
+    if (!ctx->has_bk || !ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "keys not loaded");
+    if (!gpu_accessible(ctx, d_wires)) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_circuit_create needs a device pointer for the wire table");
+    // everything that allocates or synchronises happens now, outside the capture: the key layouts the waves' dispatches read, the sample buffer,
+    // the circuit's own copies of the description and the table rows, the gathered inputs and the key-switched outputs
+    for (int32_t w = 0; w < num_waves; w++)
+        if (int rc = ensure_bk_layouts(ctx, (size_t)(wave_offsets[w + 1] - wave_offsets[w]), MODE_EXTRACT)) return rc;
+    const int32_t first = wave_offsets[0], nodes = wave_offsets[num_waves] - first, rows = out_base[num_waves];
+    const size_t n1 = (size_t)ctx->p.n + 1;
+    rtfhe_circuit* c = new (std::nothrow) rtfhe_circuit();
+    if (!c) return fail(ctx, RTFHE_ERR_NOMEM, "out of host memory");
+    c->ctx = ctx; c->device = ctx->device; c->waves = num_waves; c->backend = ctx->backend;
+    auto bail = [&](int rc) { circuit_release(c); delete c; return rc; };
+    rtfhe_ctx::Tlwe1 cbuf;
+    if (int rc = ensure_tlwe1(ctx, cbuf, widest_rows)) return bail(rc);
+    c->d_samples = cbuf.d;
+    // description: in_idx, weights [nodes][fan_in] | cst, lut_idx [nodes] | out_idx [rows]
+    const size_t desc_words = (size_t)nodes * (2 * fan_in + 2) + rows;
+    std::vector<int32_t> desc(desc_words, 0);
+    int32_t* h_in = desc.data();
+    int32_t* h_wt = h_in + (size_t)nodes * fan_in;
+    int32_t* h_cst = h_wt + (size_t)nodes * fan_in;
+    int32_t* h_lut = h_cst + nodes;
+    int32_t* h_out = h_lut + nodes;
+    std::memcpy(h_in, in_idx + (size_t)first * fan_in, (size_t)nodes * fan_in * 4);
+    std::memcpy(h_wt, weights + (size_t)first * fan_in, (size_t)nodes * fan_in * 4);
+    if (cst) std::memcpy(h_cst, cst + first, (size_t)nodes * 4);
+    if (lut_idx) std::memcpy(h_lut, lut_idx + first, (size_t)nodes * 4);
+    std::memcpy(h_out, out_idx, (size_t)rows * 4);
+    void *d_desc = nullptr, *d_gather = nullptr, *d_ks = nullptr, *d_tv = nullptr;
+    const size_t tv_bytes = (size_t)lut->n_lut * ctx->p.N * 4;
+    const std::pair<void**, size_t> bufs[] = {{&d_desc, desc_words * 4}, {&d_gather, widest * n1 * 4}, {&d_ks, widest_rows * n1 * 4}, {&d_tv, tv_bytes}};
+    for (const auto& [pp, bytes] : bufs) {
+        if (hipMalloc(pp, bytes) != hipSuccess) { (void)hipGetLastError(); return bail(fail(ctx, RTFHE_ERR_HIP, "rtfhe_lut_circuit_create: hipMalloc")); }
+        c->d_owned.push_back(*pp);
+    }
+    if (hipMemcpy(d_desc, desc.data(), desc_words * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_tv, lut->d_tv[0], tv_bytes, hipMemcpyDeviceToDevice) != hipSuccess ||
+        hipMemset(d_ks, 0, widest_rows * n1 * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return bail(fail(ctx, RTFHE_ERR_HIP, "rtfhe_lut_circuit_create: hipMemcpy / hipMemset"));
+    }
+    const int32_t* d_in = (const int32_t*)d_desc;
+    const int32_t* d_wt = d_in + (size_t)nodes * fan_in;
+    const uint32_t* d_cst = (const uint32_t*)(d_wt + (size_t)nodes * fan_in);
+    const int32_t* d_lut = (const int32_t*)d_cst + nodes;
+    const int32_t* d_out = d_lut + nodes;
+    const bool vec = n1 % 4 == 0 && (uintptr_t)d_wires % 16 == 0;      // (the circuit's own buffers come from hipMalloc)
+    const int64_t before = ctx->launches;
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return bail(fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e)));
+    e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) return bail(fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e)));
+    int rc = 0;
+    ctx->tlwe1_capture = &cbuf;
+    for (int32_t w = 0; w < num_waves && !rc; w++) {
+        const int32_t off = wave_offsets[w] - first, cnt = wave_offsets[w + 1] - wave_offsets[w], th = wave_n_out[w];
+        const int32_t shift = th == 1 ? 0 : th == 2 ? 1 : th == 4 ? 2 : 3;
+        const LutGatherArgs ga{(const uint32_t*)d_wires, (uint32_t*)d_gather, d_in + (size_t)off * fan_in, d_wt + (size_t)off * fan_in, d_cst + off, cnt,
+                               (int32_t)n1, nw};
+        rc = launch_lut_gather(ctx, fan_in, vec, ga, ctx->stream);
+        if (!rc) rc = launch_pbs_many(ctx, LutRef{(const uint32_t*)d_tv, lut_idx ? d_lut + off : nullptr, lut->n_lut, shift}, d_gather, d_ks, (size_t)cnt,
+                                      ctx->stream, false);      // (d_ks is zero: cleared at creation and by every scatter, no memset node)
+        const LutScatterArgs sa{(uint32_t*)d_ks, (uint32_t*)d_wires, d_out + out_base[w], cnt * th, (int32_t)n1, nw};
+        if (!rc) rc = launch_lut_scatter(ctx, vec, sa, ctx->stream);
+    }
+    ctx->tlwe1_capture = nullptr;
+    e = hipStreamEndCapture(ctx->stream, &c->graph);
+    c->launches = ctx->launches - before;
+    ctx->launches = before;
+    if (rc) return bail(rc);
+    if (e != hipSuccess) return bail(fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e)));
+    e = hipGraphInstantiate(&c->exec, c->graph, nullptr, nullptr, 0);
+    if (e != hipSuccess) return bail(fail(ctx, RTFHE_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)));
     ctx->circuits.push_back(c);
     *out = c;
     return 0;

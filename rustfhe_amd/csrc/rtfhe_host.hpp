@@ -136,6 +136,8 @@ struct rtfhe_circuit {
     hipGraphExec_t exec = nullptr;
     int device = 0;            // kept here: the context may be destroyed before the circuit
     uint32_t* d_samples = nullptr;   // the circuit's own lvl1 sample buffer (split path): replays on any stream never share one with other work
+    std::vector<void*> d_owned;      // a LUT circuit's other device buffers (rtfhe_lut_circuit_create): description, gathered inputs, key-switched
+                                     // outputs, its copy of the table rows
     int32_t waves = 0;
     int64_t launches = 0;      // kernel launches one replay stands for
     int backend = RTFHE_BACKEND_FFT64_MIRROR;   // the backend it was recorded on
@@ -239,7 +241,8 @@ int mux_host_one(rtfhe_ctx* ctx, const uint32_t* c, const uint32_t* in0, const u
 // (lut.shift >= 0: a many-LUT PBS, out [count][2^shift][n+1])
 int run_host_pbs_one(rtfhe_ctx* ctx, const LutRef& lut, const int32_t* lut_idx, const uint32_t* in, uint32_t* out, size_t count);
 // a many-LUT PBS (lut.shift >= 0) of device buffers on one device: the k_pbs_many_* launch(es), then the key switch of count << shift samples
-int launch_pbs_many(rtfhe_ctx* ctx, const LutRef& lut, const void* d_in, void* d_out, size_t count, hipStream_t s);
+// (zero_out = false: d_out is zero already and is not cleared first -- a LUT circuit's key-switched buffer, which k_lut_scatter clears)
+int launch_pbs_many(rtfhe_ctx* ctx, const LutRef& lut, const void* d_in, void* d_out, size_t count, hipStream_t s, bool zero_out = true);
 int mux_dev_one(rtfhe_ctx* ctx, const void* d_c, const void* d_in0, const void* d_in1, void* d_out, size_t count, hipStream_t s);
 
 // ---- several GPUs (rtfhe_multi.hip) ----

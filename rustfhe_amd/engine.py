@@ -210,6 +210,21 @@ class Engine:
                                              C.byref(h)))
         return h
 
+    def lut_circuit_create(self, lut, fan_in, in_idx, weights, cst, lut_idx, wave_offsets, wave_n_out, out_idx, d_wires, num_wires):
+        """Records a LUT circuit (include/rtfhe.h: rtfhe_lut_circuit_create): waves of many-LUT bootstraps of weighted wire sums over the wire
+        table d_wires (num_wires rows of n+1 words).  The description arrays are host arrays (numpy), copied by the library, and so is the
+        table: `lut` may be closed afterwards.  cst / lut_idx may be None.  Returns a handle for circuit_launch / circuit_destroy."""
+        i32 = lambda a: None if a is None else _np(a, np.int32).reshape(-1)      # noqa: E731
+        in_idx, weights, lut_idx, out_idx = i32(in_idx), i32(weights), i32(lut_idx), i32(out_idx)
+        cst = None if cst is None else _np(np.asarray(cst, np.int64) & 0xFFFFFFFF, np.uint32).reshape(-1)
+        offs, n_out = i32(wave_offsets), i32(wave_n_out)
+        assert n_out.size == offs.size - 1, "one n_out per wave"
+        h = C.c_void_p()
+        self._ck(self.L.rtfhe_lut_circuit_create(self.h, lut.h, int(fan_in), _ptr(in_idx), _ptr(weights), _ptr(cst), _ptr(lut_idx),
+                                                 offs.ctypes.data_as(C.POINTER(C.c_int32)), n_out.ctypes.data_as(C.POINTER(C.c_int32)), n_out.size,
+                                                 _ptr(out_idx), self._dev(d_wires), num_wires, C.byref(h)))
+        return h
+
     def circuit_launch(self, circuit, stream=None):
         self._ck(self.L.rtfhe_circuit_launch(circuit, C.c_void_p(stream) if stream else None))
 
