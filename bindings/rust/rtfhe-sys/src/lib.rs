@@ -115,6 +115,8 @@ extern "C" {
     pub fn rtfhe_lut_circuit_create(ctx: *mut rtfhe_ctx, lut: *const rtfhe_lut, fan_in: i32, in_idx: *const i32, weights: *const i32, cst: *const u32,
                                     lut_idx: *const i32, wave_offsets: *const i32, wave_n_out: *const i32, num_waves: i32, out_idx: *const i32,
                                     d_wires: *mut c_void, num_wires: usize, out: *mut *mut rtfhe_circuit) -> c_int;
+    // encrypted tables: rows TRLWE [n_lut][2][N] under key1, accepted by the PBS entries and rtfhe_lut_circuit_create (freed by rtfhe_lut_destroy)
+    pub fn rtfhe_lut_create_encrypted(ctx: *mut rtfhe_ctx, trlwe: *const u32, n_lut: i32, out: *mut *mut rtfhe_lut) -> c_int;
     pub fn rtfhe_sync(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_begin(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_end(ctx: *mut rtfhe_ctx, stream: *mut c_void, ms: *mut f64, launches: *mut i64) -> c_int;
@@ -146,6 +148,8 @@ extern "C" {
     pub fn rtfhe_keygen_with_keys(p: *const rtfhe_params, key0: *const i32, key1: *const i32, bk: *mut u32, ksk: *mut u32) -> c_int;
     pub fn rtfhe_tlwe_encrypt_bits(p: *const rtfhe_params, key0: *const i32, bits: *const u8, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_tlwe_encrypt_torus(p: *const rtfhe_params, key0: *const i32, mu: *const u32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trlwe_encrypt_torus(p: *const rtfhe_params, key1: *const i32, mu: *const u32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trlwe_phase(p: *const rtfhe_params, key1: *const i32, ct: *const u32, phase: *mut u32, count: usize) -> c_int;
     // TEST ONLY (seeded xoshiro256**, not secure)
     pub fn rtfhe_ksk_expand_ref(p: *const rtfhe_params, key0: *const i32, key1: *const i32, ksk: *const u32, ksk_ref: *mut u32) -> c_int;
     pub fn rtfhe_ksk_expand_ref_deterministic(p: *const rtfhe_params, seed: u64, key0: *const i32, key1: *const i32, ksk: *const u32, ksk_ref: *mut u32) -> c_int;
@@ -153,6 +157,7 @@ extern "C" {
     pub fn rtfhe_keygen_with_keys_deterministic(p: *const rtfhe_params, seed: u64, key0: *const i32, key1: *const i32, bk: *mut u32, ksk: *mut u32) -> c_int;
     pub fn rtfhe_tlwe_encrypt_bits_deterministic(p: *const rtfhe_params, key0: *const i32, seed: u64, bits: *const u8, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_tlwe_encrypt_torus_deterministic(p: *const rtfhe_params, key0: *const i32, seed: u64, mu: *const u32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trlwe_encrypt_torus_deterministic(p: *const rtfhe_params, key1: *const i32, seed: u64, mu: *const u32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_tlwe_decrypt_bits(p: *const rtfhe_params, key0: *const i32, input: *const u32, bits: *mut u8, count: usize) -> c_int;
     pub fn rtfhe_keys_write(path: *const c_char, p: *const rtfhe_params, key0: *const i32, key1: *const i32, bk: *const u32, ksk: *const u32) -> c_int;
     pub fn rtfhe_keys_read_header(path: *const c_char, p: *mut rtfhe_params, flags: *mut u32) -> c_int;

@@ -28,6 +28,8 @@
  *                                       0 .. n_out-1 (TRLWERep::sample_extract_index, hom_nand/src/trlwe.rs:110-121)
  *   rtfhe_lut_circuit_create         (no reference counterpart) netlists of many-LUT bootstraps of weighted wire sums, recorded once and
  *                                       replayed through rtfhe_circuit_launch
+ *   rtfhe_lut_create_encrypted       (no reference counterpart) tables the server holds only as TRLWE ciphertexts: the blind rotation
+ *                                       starts from TRLWERep encryptions (hom_nand/src/trlwe.rs) instead of the trivial (tv, 0)
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch           <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -278,6 +280,26 @@ int rtfhe_pbs_many_batch(rtfhe_ctx *ctx, const rtfhe_lut *lut, int32_t n_out, co
                          const uint32_t *tlwe /* [count][n+1] */, uint32_t *out /* [count][n_out][n+1] */, size_t count);
 int rtfhe_pbs_many_batch_dev(rtfhe_ctx *ctx, const rtfhe_lut *lut, int32_t n_out, const void *d_lut_idx /* int32[count] or NULL */,
                              const void *d_tlwe, void *d_out /* [count][n_out][n+1] */, size_t count, void *stream);
+/* ---- encrypted tables: the test polynomial as a TRLWE ciphertext the server cannot read ----
+ * An encrypted table holds n_lut rows, each a TRLWE u32[2][N] in the TRLWE layout (b(X) then a(X)) under the lvl1 key key1, e.g. from
+ * rtfhe_trlwe_encrypt_torus of test polynomials built as for rtfhe_lut_create / rtfhe_pbs_many_batch.  For gate g with row (tb, ta)
+ * everything is exactly rtfhe_pbs_many_batch -- the same bbar and abar_i (mod switch at SH + t for ϑ = 2^t outputs), the same n CMUX
+ * steps, out[g][j] = identity_key_switch(sample_extract_index(acc, j)) -- except where the accumulator starts:
+ *
+ *     acc_b[c] = e < N ? tb[e] : -tb[e-N],   acc_a[c] = e < N ? ta[e] : -ta[e-N],   e = (c + bbar) mod 2N
+ *
+ * i.e. acc = X^{-bbar} (tb, ta).  A trivial encryption (ta = 0, tb = tv) gives word for word what the plain table tv gives through
+ * rtfhe_pbs_batch[_dev] and rtfhe_pbs_many_batch[_dev] (every n_out, every batch shape).  The outputs decrypt under key0 as before; their
+ * noise is the plain table's plus the table's own (alpha = 2^-25 from rtfhe_trlwe_encrypt_torus), carried through the rotation unchanged.
+ * What the server learns: n_lut, each call's n_out, and which row each gate uses (lut_idx stays plaintext) -- not the rows' contents.
+ *
+ * rtfhe_lut_create_encrypted returns an ordinary rtfhe_lut: uploaded to every entry of the context as rtfhe_lut_create does, freed by
+ * rtfhe_lut_destroy under the same lifetime rules, and accepted without a signature change by rtfhe_pbs_batch[_dev],
+ * rtfhe_pbs_many_batch[_dev] and rtfhe_lut_circuit_create, with the same index checks, sharding and refusal on the exact backends.
+ * rtfhe_pbs_batch[_dev] runs an encrypted table as rtfhe_pbs_many_batch[_dev] with n_out = 1 (MODE_EXTRACT, then the batch key switch);
+ * so inside a stream capture rtfhe_pbs_batch_dev with an encrypted table follows rtfhe_pbs_many_batch_dev's capture rule: an eager call of
+ * at least `count` gates (and, for the many entry, at least this n_out) must have run on that stream first (else RTFHE_ERR_STATE). */
+int rtfhe_lut_create_encrypted(rtfhe_ctx *ctx, const uint32_t *trlwe /* [n_lut][2][N] */, int32_t n_lut, rtfhe_lut **out);
 /* ---- LUT circuits: netlists of many-LUT bootstraps, recorded once and replayed as one submission ----
  * A LUT circuit works on the wire table d_wires, u32[num_wires][n+1] lvl0 ciphertexts in device memory, as a gate circuit does.  It is a
  * sequence of waves: wave w holds nodes wave_offsets[w] .. wave_offsets[w+1] (host array, num_waves + 1 entries, strictly increasing from
@@ -306,7 +328,7 @@ int rtfhe_pbs_many_batch_dev(rtfhe_ctx *ctx, const rtfhe_lut *lut, int32_t n_out
  *     gathered inputs  4 · (n+1) · max_w nodes_w
  *     key-switched     4 · (n+1) · max_w nodes_w · ϑ_w
  *     sample buffer    4 · (N+1) · max(1024, max_w nodes_w · ϑ_w) rounded up to 16
- *     table rows       4 · N · n_lut */
+ *     table rows       4 · N · n_lut  (an encrypted table: 4 · 2N · n_lut) */
 int rtfhe_lut_circuit_create(rtfhe_ctx *ctx, const rtfhe_lut *lut, int32_t fan_in /* 1 .. 8 */,
                              const int32_t *in_idx /* [nodes][fan_in] */, const int32_t *weights /* [nodes][fan_in] */,
                              const uint32_t *cst /* [nodes] or NULL */, const int32_t *lut_idx /* [nodes] or NULL */,
@@ -373,6 +395,13 @@ int rtfhe_tlwe_encrypt_bits(const rtfhe_params *p, const int32_t *key0, const ui
  * messages for rtfhe_pbs_batch */
 int rtfhe_tlwe_encrypt_torus(const rtfhe_params *p, const int32_t *key0, const uint32_t *mu, uint32_t *out /* [count][n+1] */,
                              size_t count);
+/* TRLWE encryptions under key1 [N] of the polynomials mu[count][N] (OS CSPRNG, noise alpha = 2^-25 as the bootstrapping key's rows,
+ * TRLWERep::encrypt / trlwe_zero, hom_nand/src/trlwe.rs:127-137): the rows of an encrypted table (rtfhe_lut_create_encrypted).
+ * rtfhe_trlwe_phase gives b - a·s, i.e. mu plus the noise. */
+int rtfhe_trlwe_encrypt_torus(const rtfhe_params *p, const int32_t *key1, const uint32_t *mu /* [count][N] */,
+                              uint32_t *out /* [count][2][N] */, size_t count);
+int rtfhe_trlwe_phase(const rtfhe_params *p, const int32_t *key1, const uint32_t *ct /* [count][2][N] */,
+                      uint32_t *phase /* [count][N] */, size_t count);
 /* the reference's KeySwitchingKey shape from the compact one: entries t = 1 .. base-1 of every level copied, entry t = base =
  * TLWE(base * s_i / 2^(basebit (l+1))) freshly encrypted as KeySwitchingKey::new fills it (hom_nand/src/tlwe.rs:252-274) */
 int rtfhe_ksk_expand_ref(const rtfhe_params *p, const int32_t *key0, const int32_t *key1,
@@ -389,6 +418,8 @@ int rtfhe_tlwe_encrypt_bits_deterministic(const rtfhe_params *p, const int32_t *
                                           const uint8_t *bits, uint32_t *out /* [count][n+1] */, size_t count);
 int rtfhe_tlwe_encrypt_torus_deterministic(const rtfhe_params *p, const int32_t *key0, uint64_t seed,
                                             const uint32_t *mu, uint32_t *out /* [count][n+1] */, size_t count);
+int rtfhe_trlwe_encrypt_torus_deterministic(const rtfhe_params *p, const int32_t *key1, uint64_t seed,
+                                            const uint32_t *mu /* [count][N] */, uint32_t *out /* [count][2][N] */, size_t count);
 int rtfhe_tlwe_decrypt_bits(const rtfhe_params *p, const int32_t *key0, const uint32_t *in,
                             uint8_t *bits, size_t count);
 int rtfhe_tlwe_phase(const rtfhe_params *p, const int32_t *key0, const uint32_t *in, uint32_t *phase, size_t count);

@@ -243,13 +243,13 @@ int rtfhe_mux_batch_dev(rtfhe_ctx* ctx, const void* d_c, const void* d_in0, cons
 }
 
 // ---- programmable bootstrapping (include/rtfhe.h) ----
-int rtfhe_lut_create(rtfhe_ctx* ctx, const uint32_t* tv, int32_t n_lut, rtfhe_lut** out) {
-    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
-    if (!tv || !out || n_lut < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_create: null argument or n_lut < 1");
+// the rows of a table (plain: [n_lut][N] test polynomials; encrypted: [n_lut][2][N] TRLWEs) uploaded to every entry of the context
+static int lut_upload(rtfhe_ctx* ctx, const uint32_t* tv, int32_t n_lut, bool encrypted, rtfhe_lut** out) {
     *out = nullptr;
-    const size_t bytes = (size_t)n_lut * ctx->p.N * 4;
+    const size_t bytes = (size_t)n_lut * ctx->p.N * (encrypted ? 2 : 1) * 4;
     rtfhe_lut* lut = new rtfhe_lut();
     lut->n_lut = n_lut;
+    lut->encrypted = encrypted;
     const int entries = 1 + (int)ctx->peers.size();
     int rc = 0;
     for (int d = 0; d < entries && !rc; d++) {
@@ -276,6 +276,18 @@ int rtfhe_lut_create(rtfhe_ctx* ctx, const uint32_t* tv, int32_t n_lut, rtfhe_lu
     ctx->luts.push_back(lut);
     *out = lut;
     return 0;
+}
+
+int rtfhe_lut_create(rtfhe_ctx* ctx, const uint32_t* tv, int32_t n_lut, rtfhe_lut** out) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!tv || !out || n_lut < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_create: null argument or n_lut < 1");
+    return lut_upload(ctx, tv, n_lut, false, out);
+}
+
+int rtfhe_lut_create_encrypted(rtfhe_ctx* ctx, const uint32_t* trlwe, int32_t n_lut, rtfhe_lut** out) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!trlwe || !out || n_lut < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_create_encrypted: null argument or n_lut < 1");
+    return lut_upload(ctx, trlwe, n_lut, true, out);
 }
 
 void rtfhe_lut_destroy(rtfhe_lut* lut) {
@@ -310,7 +322,7 @@ int rtfhe_pbs_batch(rtfhe_ctx* ctx, const rtfhe_lut* lut, const int32_t* lut_idx
         for (size_t g = 0; g < count; g++)
             if ((uint32_t)lut_idx[g] >= (uint32_t)lut->n_lut)
                 return fail(ctx, RTFHE_ERR_INVALID, "lut_idx[" + std::to_string(g) + "] = " + std::to_string(lut_idx[g]) + " is outside [0, " + std::to_string(lut->n_lut) + ")");
-    return sharded_host_pbs(ctx, lut, lut_idx, tlwe, out, count);
+    return sharded_host_pbs(ctx, lut, lut_idx, tlwe, out, count, lut->encrypted ? 0 : -1);      // encrypted: the many-LUT path, one output
 }
 
 int rtfhe_pbs_batch_dev(rtfhe_ctx* ctx, const rtfhe_lut* lut, const void* d_lut_idx, const void* d_tlwe, void* d_out, size_t count, void* stream) {
@@ -320,6 +332,11 @@ int rtfhe_pbs_batch_dev(rtfhe_ctx* ctx, const rtfhe_lut* lut, const void* d_lut_
     if (!gpu_accessible(ctx, d_tlwe) || !gpu_accessible(ctx, d_out) || (d_lut_idx && !gpu_accessible(ctx, d_lut_idx)))
         return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_pbs_batch_dev needs device pointers (got memory the GPU cannot address)");
     if (count > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "count too large");
+    if (lut->encrypted) {      // the many-LUT path with one output (MODE_EXTRACT, then the batch key switch): its capture rule applies
+        if (!ctx->peers.empty())
+            return sharded_dev_batch(ctx, RTFHE_COPY, nullptr, d_tlwe, nullptr, d_out, count, (hipStream_t)stream, lut, (const int32_t*)d_lut_idx, 0);
+        return launch_pbs_many(ctx, lut_on(lut, 0, (const int32_t*)d_lut_idx, 0), d_tlwe, d_out, count, (hipStream_t)stream);
+    }
     if (!ctx->peers.empty())
         return sharded_dev_batch(ctx, RTFHE_COPY, nullptr, d_tlwe, nullptr, d_out, count, (hipStream_t)stream, lut, (const int32_t*)d_lut_idx);
     return launch_bootstrap(ctx, RTFHE_COPY, MODE_GATE, ctx->p.n, d_tlwe, nullptr, d_out, count, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, 0,

@@ -1,7 +1,7 @@
 // rtfhe_body_pair.hpp -- the body of k_bootstrap_pair and of its programmable-bootstrap twin k_pbs_pair (rtfhe_kernels_pair.hpp), included inside the braces of both
-// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany, rtfhe_kernels.hpp).
+// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany / TvEnc, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap_pair compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included three times (k_pbs_many_*: the many-LUT PBS).
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included four times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables).
     constexpr int LOGN = 10;
     typedef Geo<LOGN> G;
     constexpr int N = G::N, P = G::P, R = G::R, NT = 128 * GATES;
@@ -62,7 +62,8 @@
         for (int mm = 0; mm < 2 * R; mm++) {
             const int c = lane + 64 * mm;
             const int e = (c + bbar) & (2 * N - 1);
-            poly[c] = side ? 0u : tv_word<LOGN>(tv, e);
+            if constexpr (decltype(tvs)::ENC) poly[c] = side ? tv_word_a<LOGN>(tv, e) : tv_word<LOGN>(tv, e);   // encrypted table: side 1 from the a polynomial
+            else poly[c] = side ? 0u : tv_word<LOGN>(tv, e);
         }
     }
     wave_lds_sync();

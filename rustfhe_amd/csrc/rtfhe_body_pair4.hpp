@@ -1,7 +1,7 @@
 // rtfhe_body_pair4.hpp -- the body of k_bootstrap_pair4 and of its programmable-bootstrap twin k_pbs_pair4 (rtfhe_kernels_pair4.hpp), included inside the braces of both
-// kernels: they declare `pa` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany, rtfhe_kernels.hpp).
+// kernels: they declare `pa` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany / TvEnc, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap_pair4 compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included three times (k_pbs_many_*: the many-LUT PBS).
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included four times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables).
     constexpr int LOGN = 10, N = 1024, P = 512, R = 4;
     typedef Geo<LOGN> G;
     constexpr uint32_t M = decomp_mask(L, BGBIT);
@@ -55,7 +55,8 @@
         const int bbar = (int)abar[n];
         for (int c = lane0 + 64 * q; c < 2 * N; c += 256) {
             const int e = (c + bbar) & (2 * N - 1);
-            accbuf[c] = c < N ? tv_word<LOGN>(tv, e) : 0u;
+            if constexpr (decltype(tvs)::ENC) accbuf[c] = c < N ? tv_word<LOGN>(tv, e) : tv_word_a<LOGN>(tv, e ^ N);   // encrypted table: a coefficient c - N, (c - N + bbar) mod 2N = e ^ N
+            else accbuf[c] = c < N ? tv_word<LOGN>(tv, e) : 0u;
         }
     }
     __syncthreads();

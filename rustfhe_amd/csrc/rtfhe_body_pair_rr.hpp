@@ -1,7 +1,7 @@
 // rtfhe_body_pair_rr.hpp -- the body of k_bootstrap_pair_rr and of its programmable-bootstrap twin k_pbs_pair_rr (rtfhe_kernels_pair_rr.hpp), included inside the braces of both
-// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany, rtfhe_kernels.hpp).
+// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany / TvEnc, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap_pair_rr compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included three times (k_pbs_many_*: the many-LUT PBS).
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included four times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables).
     typedef PairRrLds S;
     constexpr int LOGN = 10, SLOTS = S::SLOTS;
     typedef Geo<LOGN> G;
@@ -58,7 +58,8 @@
         for (int c = tid; c < N; c += NT) {
             const int e = (c + bbar) & (2 * N - 1);
             acc[c] = tv_word<LOGN>(tv, e);
-            acc[N + c] = 0u;
+            if constexpr (decltype(tvs)::ENC) acc[N + c] = tv_word_a<LOGN>(tv, e);   // encrypted table: the a half from the row's a polynomial
+            else acc[N + c] = 0u;
         }
     }
     __syncthreads();

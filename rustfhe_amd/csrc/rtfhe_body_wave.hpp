@@ -1,7 +1,7 @@
 // rtfhe_body_wave.hpp -- the body of k_bootstrap and of its programmable-bootstrap twin k_pbs (rtfhe_kernels.hpp), included inside the braces of both
-// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany, rtfhe_kernels.hpp).
+// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany / TvEnc, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included three times (k_pbs_many_*: the many-LUT PBS).
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included four times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables).
     typedef Geo<LOGN> G;
     constexpr int N = G::N, R = G::R;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -45,7 +45,8 @@
             const int c = lane + 64 * mm;
             const int e = (c + bbar) & (2 * N - 1);
             accbuf[c] = tv_word<LOGN>(tv, e);
-            accbuf[N + c] = 0u;
+            if constexpr (decltype(tvs)::ENC) accbuf[N + c] = tv_word_a<LOGN>(tv, e);   // encrypted table: the a half from the row's a polynomial
+            else accbuf[N + c] = 0u;
         }
     }
     wave_lds_sync();

@@ -209,7 +209,7 @@ int rtfhe_lut_circuit_create(rtfhe_ctx* ctx, const rtfhe_lut* lut, int32_t fan_i
     if (lut_idx) std::memcpy(h_lut, lut_idx + first, (size_t)nodes * 4);
     std::memcpy(h_out, out_idx, (size_t)rows * 4);
     void *d_desc = nullptr, *d_gather = nullptr, *d_ks = nullptr, *d_tv = nullptr;
-    const size_t tv_bytes = (size_t)lut->n_lut * ctx->p.N * 4;
+    const size_t tv_bytes = (size_t)lut->n_lut * ctx->p.N * (lut->encrypted ? 2 : 1) * 4;      // an encrypted table's rows are TRLWEs: 2N words
     const std::pair<void**, size_t> bufs[] = {{&d_desc, desc_words * 4}, {&d_gather, widest * n1 * 4}, {&d_ks, widest_rows * n1 * 4}, {&d_tv, tv_bytes}};
     for (const auto& [pp, bytes] : bufs) {
         if (hipMalloc(pp, bytes) != hipSuccess) { (void)hipGetLastError(); return bail(fail(ctx, RTFHE_ERR_HIP, "rtfhe_lut_circuit_create: hipMalloc")); }
@@ -240,7 +240,7 @@ int rtfhe_lut_circuit_create(rtfhe_ctx* ctx, const rtfhe_lut* lut, int32_t fan_i
         const LutGatherArgs ga{(const uint32_t*)d_wires, (uint32_t*)d_gather, d_in + (size_t)off * fan_in, d_wt + (size_t)off * fan_in, d_cst + off, cnt,
                                (int32_t)n1, nw};
         rc = launch_lut_gather(ctx, fan_in, vec, ga, ctx->stream);
-        if (!rc) rc = launch_pbs_many(ctx, LutRef{(const uint32_t*)d_tv, lut_idx ? d_lut + off : nullptr, lut->n_lut, shift}, d_gather, d_ks, (size_t)cnt,
+        if (!rc) rc = launch_pbs_many(ctx, LutRef{(const uint32_t*)d_tv, lut_idx ? d_lut + off : nullptr, lut->n_lut, shift, lut->encrypted}, d_gather, d_ks, (size_t)cnt,
                                       ctx->stream, false);      // (d_ks is zero: cleared at creation and by every scatter, no memset node)
         const LutScatterArgs sa{(uint32_t*)d_ks, (uint32_t*)d_wires, d_out + out_base[w], cnt * th, (int32_t)n1, nw};
         if (!rc) rc = launch_lut_scatter(ctx, vec, sa, ctx->stream);

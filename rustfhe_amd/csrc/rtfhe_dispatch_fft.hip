@@ -15,14 +15,17 @@ namespace {
 
 // One launch of a kernel family: the gate kernel (k_bootstrap_*) or, for a programmable bootstrap (lut.tv set), its twin (k_pbs_*) with the
 // family's own arguments wrapped in LutArgs.  The twins share shapes, LDS and key layouts, so every choice below is made once for both.
-// A many-LUT PBS (lut.shift >= 0) takes the family's third kernel (k_pbs_many_*), in MODE_EXTRACT.
-template <typename A, typename KG, typename KP, typename KM>
-int launch_twin(rtfhe_ctx* ctx, KG kg, KP kp, KM km, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A& a, const LutRef& lut) {
+// A many-LUT PBS (lut.shift >= 0) takes the family's third kernel (k_pbs_many_*), in MODE_EXTRACT, and one with an encrypted table (lut.enc)
+// the fourth (k_pbs_enc_*), with the same arguments.
+template <typename A, typename KG, typename KP, typename KM, typename KE>
+int launch_twin(rtfhe_ctx* ctx, KG kg, KP kp, KM km, KE ke, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A& a, const LutRef& lut) {
+    if (lut.tv && lut.enc && lut.shift < 0) return fail(ctx, RTFHE_ERR_STATE, "an encrypted table runs on the many-LUT path only (launch_pbs_many)");
     if (lut.tv && lut.shift >= 0) {
-        if (int rc = allow_lds(ctx, km, lds)) return rc;
+        if (int rc = lut.enc ? allow_lds(ctx, ke, lds) : allow_lds(ctx, km, lds)) return rc;
         ManyArgs<A> p{};
         p.base = a; p.tv = lut.tv; p.tv_idx = lut.idx; p.n_tv = lut.n_tv; p.t = lut.shift;
-        hipLaunchKernelGGL(km, grid, block, lds, s, p);
+        if (lut.enc) hipLaunchKernelGGL(ke, grid, block, lds, s, p);
+        else hipLaunchKernelGGL(km, grid, block, lds, s, p);
     } else if (lut.tv) {
         if (int rc = allow_lds(ctx, kp, lds)) return rc;
         const LutArgs<A> p{a, lut.tv, lut.idx, lut.n_tv};
@@ -40,16 +43,16 @@ template <int LOGN, int W>
 int launch_bootstrap_w(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
     const size_t lds = bootstrap_lds_bytes<LOGN>(W, a.npad, bootstrap_dual_xbuf(LOGN, W));
     const int grid = (a.count + W - 1) / W;
-    return launch_twin(ctx, k_bootstrap<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs_many<LOGN, 3, 6, 8, 2, KSQ, W>, dim3(grid), dim3(64 * W), lds, s, a, lut);
+    return launch_twin(ctx, k_bootstrap<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs_many<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs_enc<LOGN, 3, 6, 8, 2, KSQ, W>, dim3(grid), dim3(64 * W), lds, s, a, lut);
 }
 
 int launch_bootstrap_wg10(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
-    return launch_twin(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_many_wg<10, 3, 6, 8, 2, KSQ>, dim3(a.count), dim3(512), WgLds<10, 3>::bytes(a.npad), s, a, lut);
+    return launch_twin(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_many_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_enc_wg<10, 3, 6, 8, 2, KSQ>, dim3(a.count), dim3(512), WgLds<10, 3>::bytes(a.npad), s, a, lut);
 }
 
 template <int GATES>
 int launch_bootstrap_pair10_g(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
-    return launch_twin(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_many_pair<3, 6, 8, 2, KSQ, GATES>, dim3((a.count + GATES - 1) / GATES), dim3(128 * GATES),
+    return launch_twin(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_many_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, GATES>, dim3((a.count + GATES - 1) / GATES), dim3(128 * GATES),
                        PairLds::bytes(GATES, a.npad), s, a, lut);
 }
 int launch_bootstrap_pair10(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) { return launch_bootstrap_pair10_g<4>(ctx, a, s, lut); }
@@ -63,13 +66,13 @@ int launch_bootstrap_pair_rr(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, con
     const int wgs = ctx->num_cus, most = (a.count + wgs - 1) / wgs;
     if (a.count < 4 * wgs || most > PairRrLds::GMAX)
         return fail(ctx, RTFHE_ERR_STATE, "k_bootstrap_pair_rr: " + std::to_string(a.count) + " gates on " + std::to_string(wgs) + " CUs is not a shape it serves");
-    return launch_twin(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_many_pair_rr<3, 6, 8, 2, KSQ>, dim3(wgs), dim3(512), PairRrLds::bytes(most, a.npad), s, a, lut);
+    return launch_twin(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_many_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_enc_pair_rr<3, 6, 8, 2, KSQ>, dim3(wgs), dim3(512), PairRrLds::bytes(most, a.npad), s, a, lut);
 }
 // four waves per gate, (polynomial, parity): up to two gates per CU (rtfhe_kernels_pair4.hpp); no fused key switch
 template <int GATES>
 int launch_bootstrap_pair4_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
     const Pair4Args a{b, ctx->d_p4bk};
-    return launch_twin(ctx, k_bootstrap_pair4<3, 6, GATES>, k_pbs_pair4<3, 6, GATES>, k_pbs_many_pair4<3, 6, GATES>, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES),
+    return launch_twin(ctx, k_bootstrap_pair4<3, 6, GATES>, k_pbs_pair4<3, 6, GATES>, k_pbs_many_pair4<3, 6, GATES>, k_pbs_enc_pair4<3, 6, GATES>, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES),
                        Pair4Lds::bytes(GATES, b.npad), s, a, lut);
 }
 
@@ -77,14 +80,14 @@ int launch_bootstrap_pair4_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, con
 template <int GATES>
 int launch_bootstrap_eo11_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
     const EoArgs a{b, ctx->d_etw, ctx->d_ebk};
-    return launch_twin(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_many_eo<3, 6, 8, 2, KSQ, GATES>, dim3((b.count + GATES - 1) / GATES), dim3(128 * GATES),
+    return launch_twin(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_many_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, GATES>, dim3((b.count + GATES - 1) / GATES), dim3(128 * GATES),
                        EoLds::bytes(GATES, b.npad), s, a, lut);
 }
 // four waves per gate, (polynomial, parity): batches of up to two gates per CU (rtfhe_kernels_eo4.hpp); no fused key switch
 template <int GATES>
 int launch_bootstrap_eo4_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
     const EoArgs a{b, ctx->d_etw, ctx->d_ebk};
-    return launch_twin(ctx, k_bootstrap_eo4<3, 6, GATES>, k_pbs_eo4<3, 6, GATES>, k_pbs_many_eo4<3, 6, GATES>, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES),
+    return launch_twin(ctx, k_bootstrap_eo4<3, 6, GATES>, k_pbs_eo4<3, 6, GATES>, k_pbs_many_eo4<3, 6, GATES>, k_pbs_enc_eo4<3, 6, GATES>, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES),
                        Eo4Lds::bytes(GATES, b.npad), s, a, lut);
 }
 template <int GATES>
@@ -302,20 +305,22 @@ int rebuild_derived_keys(rtfhe_ctx* ctx) {
     return 0;
 }
 
-// grants every bootstrap kernel of this context's parameter set, and its programmable-bootstrap and many-LUT twins, its dynamic LDS once, at context creation
-template <typename KG, typename KP, typename KM>
-static int allow_twins(rtfhe_ctx* ctx, KG kg, KP kp, KM km, size_t bytes) {
+// grants every bootstrap kernel of this context's parameter set, and its programmable-bootstrap, many-LUT and encrypted-table twins, its dynamic
+// LDS once, at context creation
+template <typename KG, typename KP, typename KM, typename KE>
+static int allow_twins(rtfhe_ctx* ctx, KG kg, KP kp, KM km, KE ke, size_t bytes) {
     if (int rc = allow_lds(ctx, kg, bytes)) return rc;
     if (int rc = allow_lds(ctx, kp, bytes)) return rc;
-    return allow_lds(ctx, km, bytes);
+    if (int rc = allow_lds(ctx, km, bytes)) return rc;
+    return allow_lds(ctx, ke, bytes);
 }
 int prime_fft_kernels(rtfhe_ctx* ctx) {
     const int npad = (ctx->p.n + 1 + 63) / 64 * 64;
     if (ctx->logn == 10) {
-        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 4>, PairLds::bytes(4, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 3>, PairLds::bytes(3, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 2>, PairLds::bytes(2, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_many_wg<10, 3, 6, 8, 2, KSQ>, WgLds<10, 3>::bytes(npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, 4>, PairLds::bytes(4, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, 3>, PairLds::bytes(3, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, 2>, PairLds::bytes(2, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_many_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_enc_wg<10, 3, 6, 8, 2, KSQ>, WgLds<10, 3>::bytes(npad))) return rc;
         // the time-sliced launch: as many gates per CU (five or six) as this mask length leaves room for in 160 KiB of LDS
         {
             int fit = 0;
@@ -323,20 +328,20 @@ int prime_fft_kernels(rtfhe_ctx* ctx) {
                 if (PairRrLds::bytes(g, npad) <= (size_t)160 * 1024) fit = g;
             if (ctx->rr > fit) ctx->rr = fit;
             if (ctx->rr >= 5)
-                if (int rc = allow_twins(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_many_pair_rr<3, 6, 8, 2, KSQ>, PairRrLds::bytes(ctx->rr, npad))) return rc;
+                if (int rc = allow_twins(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_many_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_enc_pair_rr<3, 6, 8, 2, KSQ>, PairRrLds::bytes(ctx->rr, npad))) return rc;
         }
-        if (int rc = allow_twins(ctx, k_bootstrap_pair4<3, 6, 3>, k_pbs_pair4<3, 6, 3>, k_pbs_many_pair4<3, 6, 3>, Pair4Lds::bytes(3, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_pair4<3, 6, 2>, k_pbs_pair4<3, 6, 2>, k_pbs_many_pair4<3, 6, 2>, Pair4Lds::bytes(2, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 4>, k_pbs<10, 3, 6, 8, 2, KSQ, 4>, k_pbs_many<10, 3, 6, 8, 2, KSQ, 4>, bootstrap_lds_bytes<10>(4, npad, bootstrap_dual_xbuf(10, 4)))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 8>, k_pbs<10, 3, 6, 8, 2, KSQ, 8>, k_pbs_many<10, 3, 6, 8, 2, KSQ, 8>, bootstrap_lds_bytes<10>(8, npad, bootstrap_dual_xbuf(10, 8)))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair4<3, 6, 3>, k_pbs_pair4<3, 6, 3>, k_pbs_many_pair4<3, 6, 3>, k_pbs_enc_pair4<3, 6, 3>, Pair4Lds::bytes(3, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair4<3, 6, 2>, k_pbs_pair4<3, 6, 2>, k_pbs_many_pair4<3, 6, 2>, k_pbs_enc_pair4<3, 6, 2>, Pair4Lds::bytes(2, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 4>, k_pbs<10, 3, 6, 8, 2, KSQ, 4>, k_pbs_many<10, 3, 6, 8, 2, KSQ, 4>, k_pbs_enc<10, 3, 6, 8, 2, KSQ, 4>, bootstrap_lds_bytes<10>(4, npad, bootstrap_dual_xbuf(10, 4)))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 8>, k_pbs<10, 3, 6, 8, 2, KSQ, 8>, k_pbs_many<10, 3, 6, 8, 2, KSQ, 8>, k_pbs_enc<10, 3, 6, 8, 2, KSQ, 8>, bootstrap_lds_bytes<10>(8, npad, bootstrap_dual_xbuf(10, 8)))) return rc;
     } else {
-        if (int rc = allow_twins(ctx, k_bootstrap<11, 3, 6, 8, 2, KSQ, 4>, k_pbs<11, 3, 6, 8, 2, KSQ, 4>, k_pbs_many<11, 3, 6, 8, 2, KSQ, 4>, bootstrap_lds_bytes<11>(4, npad, bootstrap_dual_xbuf(11, 4)))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 4>, EoLds::bytes(4, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 3>, EoLds::bytes(3, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 2>, EoLds::bytes(2, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 1>, EoLds::bytes(1, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo4<3, 6, 2>, k_pbs_eo4<3, 6, 2>, k_pbs_many_eo4<3, 6, 2>, Eo4Lds::bytes(2, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo4<3, 6, 1>, k_pbs_eo4<3, 6, 1>, k_pbs_many_eo4<3, 6, 1>, Eo4Lds::bytes(1, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap<11, 3, 6, 8, 2, KSQ, 4>, k_pbs<11, 3, 6, 8, 2, KSQ, 4>, k_pbs_many<11, 3, 6, 8, 2, KSQ, 4>, k_pbs_enc<11, 3, 6, 8, 2, KSQ, 4>, bootstrap_lds_bytes<11>(4, npad, bootstrap_dual_xbuf(11, 4)))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 4>, EoLds::bytes(4, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 3>, EoLds::bytes(3, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 2>, EoLds::bytes(2, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 1>, EoLds::bytes(1, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo4<3, 6, 2>, k_pbs_eo4<3, 6, 2>, k_pbs_many_eo4<3, 6, 2>, k_pbs_enc_eo4<3, 6, 2>, Eo4Lds::bytes(2, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo4<3, 6, 1>, k_pbs_eo4<3, 6, 1>, k_pbs_many_eo4<3, 6, 1>, k_pbs_enc_eo4<3, 6, 1>, Eo4Lds::bytes(1, npad))) return rc;
     }
     return 0;
 }

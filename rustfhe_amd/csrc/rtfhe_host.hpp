@@ -147,8 +147,9 @@ struct rtfhe_circuit {
 // the test polynomials of a programmable bootstrap (rtfhe_lut_create), one copy on every entry of the context
 struct rtfhe_lut {
     rtfhe_ctx* ctx = nullptr;           // the primary; null once the context has been destroyed (the handle then only remains to be freed)
-    std::vector<uint32_t*> d_tv;        // [entry] u32[n_lut][N] on entry d of the context (0: the primary, d: peers[d - 1])
+    std::vector<uint32_t*> d_tv;        // [entry] u32[n_lut][N] on entry d of the context (0: the primary, d: peers[d - 1]); encrypted: [n_lut][2][N]
     int32_t n_lut = 0;
+    bool encrypted = false;             // rtfhe_lut_create_encrypted: TRLWE rows (b, a), run by the k_pbs_enc_* kernels on the many-LUT path
 };
 
 namespace rtfhe_host {
@@ -157,11 +158,12 @@ using rtfhe::BootstrapArgs;
 
 // what a bootstrap launch reads its test polynomials from: tv null = the gates' own (k_bootstrap_*), else the k_pbs_* twins with table
 // idx[g] of tv (idx null: table 0) for gate g of the launch
-// (shift >= 0: a many-LUT PBS with 2^shift outputs per gate, the k_pbs_many_* kernels in MODE_EXTRACT, launch_pbs_many)
-struct LutRef { const uint32_t* tv = nullptr; const int32_t* idx = nullptr; int32_t n_tv = 0; int32_t shift = -1; };
+// (shift >= 0: a many-LUT PBS with 2^shift outputs per gate, the k_pbs_many_* kernels in MODE_EXTRACT, launch_pbs_many; enc: tv holds
+// encrypted rows [n_tv][2][N], the k_pbs_enc_* kernels, which need shift >= 0)
+struct LutRef { const uint32_t* tv = nullptr; const int32_t* idx = nullptr; int32_t n_tv = 0; int32_t shift = -1; bool enc = false; };
 inline LutRef lut_segment(LutRef l, size_t off) { if (l.idx) l.idx += off; return l; }     // ... for the segment starting at gate `off`
 inline LutRef lut_on(const rtfhe_lut* lut, int entry, const int32_t* d_idx, int32_t shift = -1) {
-    return lut ? LutRef{lut->d_tv[entry], d_idx, lut->n_lut, shift} : LutRef{};
+    return lut ? LutRef{lut->d_tv[entry], d_idx, lut->n_lut, shift, lut->encrypted} : LutRef{};
 }
 using rtfhe::cplx;
 

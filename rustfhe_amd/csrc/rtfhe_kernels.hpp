@@ -101,6 +101,7 @@ __device__ __forceinline__ GateIo gate_io(const BootstrapArgs& a, int g) {
 // they were before the twins existed -- and k_pbs_* with TvLut, the programmable bootstrap's caller-supplied tables (include/rtfhe.h).
 struct TvGate {
     static constexpr bool MANY = false;      // one output per gate (k_pbs_many_*: several, see TvMany)
+    static constexpr bool ENC = false;       // the a half starts at zero (k_pbs_enc_*: from an encrypted table, see TvEnc)
     struct Row { __device__ __forceinline__ bool ok() const { return true; } };
 };
 __device__ __forceinline__ TvGate::Row tv_row(const TvGate&, int, int) { return TvGate::Row{}; }
@@ -119,6 +120,7 @@ struct LutArgs {
 // reported through *fault.  The index is read once per gate before the pre-step (and once more in k_bootstrap_pair_rr's epilogue).
 struct TvLut {
     static constexpr bool MANY = false;
+    static constexpr bool ENC = false;
     const uint32_t* tv; const int32_t* idx; int32_t n_tv; int32_t* fault;
     struct Row {
         const uint32_t* p; bool good;
@@ -157,10 +159,28 @@ struct ManyArgs : LutArgs<A> {
 };
 struct TvMany : TvLut {
     static constexpr bool MANY = true;
+    static constexpr bool ENC = false;
     int32_t t;
 };
 template <typename A>
 __device__ __forceinline__ TvMany tv_many(const ManyArgs<A>& p, int32_t* fault) { return TvMany{{p.tv, p.tv_idx, p.n_tv, fault}, p.t}; }
+
+// Encrypted tables (k_pbs_enc_*, the fourth inclusion of every body): the many-LUT PBS of TvMany started from a TRLWE encryption of the
+// table instead of the trivial one, acc = X^{-bbar} * (tb, ta) (include/rtfhe.h: rtfhe_lut_create_encrypted).  The same ManyArgs, with tv
+// pointing at [n_tv][2][N] (b then a, the TRLWE layout): a row is 2N words, tv_word gives its b half and tv_word_a its a half.  The bodies
+// fill the a half under `if constexpr (ENC)` and keep their zero-filling expression for every other kernel.
+struct TvEnc : TvMany {
+    static constexpr bool ENC = true;
+};
+template <typename A>
+__device__ __forceinline__ TvEnc tv_enc(const ManyArgs<A>& p, int32_t* fault) { return TvEnc{{{p.tv, p.tv_idx, p.n_tv, fault}, p.t}}; }
+__device__ __forceinline__ TvLut::Row tv_row(const TvEnc& t, int g, int N) { return tv_row(static_cast<const TvLut&>(t), g, 2 * N); }
+template <int LOGN>
+__device__ __forceinline__ uint32_t tv_word_a(const TvLut::Row& r, int e) { return tv_word<LOGN>(TvLut::Row{r.p + (1 << LOGN), r.good}, e); }
+// (the trivial a half of the gates' test vector: named by the discarded branches of the gate kernels, whose row type does not depend on a
+// template parameter, never called)
+template <int LOGN>
+__device__ __forceinline__ uint32_t tv_word_a(const TvGate::Row&, int) { return 0u; }
 
 // The mod switch (tfhe.rs:97, 107-108) of one pre-stepped word at SH + k, scaled back by 2^k: b floor, a_i rounded, both to multiples of 2^k
 // in [0, 2N).  k = tv_shift(tvs): t for many-LUT, 0 otherwise.  The bodies call it under `if constexpr (MANY)` and keep their own k = 0
@@ -392,6 +412,12 @@ template <int LOGN, int L, int BGBIT, int KS_T, int KS_BB, int KSQ, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_pbs_many(const ManyArgs<BootstrapArgs> p) {
     const BootstrapArgs& a = p.base;
     const TvMany tvs = tv_many(p, a.fault);
+#include "rtfhe_body_wave.hpp"
+}
+template <int LOGN, int L, int BGBIT, int KS_T, int KS_BB, int KSQ, int WAVES>
+__global__ __launch_bounds__(64 * WAVES, 1) void k_pbs_enc(const ManyArgs<BootstrapArgs> p) {
+    const BootstrapArgs& a = p.base;
+    const TvEnc tvs = tv_enc(p, a.fault);
 #include "rtfhe_body_wave.hpp"
 }
 

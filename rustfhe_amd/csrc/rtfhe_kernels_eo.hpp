@@ -134,5 +134,11 @@ __global__ __launch_bounds__(128 * GATES, 1) void k_pbs_many_eo(const ManyArgs<E
     const TvMany tvs = tv_many(p, ea.b.fault);
 #include "rtfhe_body_eo.hpp"
 }
+template <int L, int BGBIT, int KS_T, int KS_BB, int KSQ, int GATES>
+__global__ __launch_bounds__(128 * GATES, 1) void k_pbs_enc_eo(const ManyArgs<EoArgs> p) {
+    const EoArgs& ea = p.base;
+    const TvEnc tvs = tv_enc(p, ea.b.fault);
+#include "rtfhe_body_eo.hpp"
+}
 
 }  // namespace rtfhe

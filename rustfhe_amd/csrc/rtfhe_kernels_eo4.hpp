@@ -61,5 +61,11 @@ __global__ __launch_bounds__(256 * GATES, 1) void k_pbs_many_eo4(const ManyArgs<
     const TvMany tvs = tv_many(p, ea.b.fault);
 #include "rtfhe_body_eo4.hpp"
 }
+template <int L, int BGBIT, int GATES>
+__global__ __launch_bounds__(256 * GATES, 1) void k_pbs_enc_eo4(const ManyArgs<EoArgs> p) {
+    const EoArgs& ea = p.base;
+    const TvEnc tvs = tv_enc(p, ea.b.fault);
+#include "rtfhe_body_eo4.hpp"
+}
 
 }  // namespace rtfhe

@@ -161,5 +161,11 @@ __global__ __launch_bounds__(128 * GATES, 1) void k_pbs_many_pair(const ManyArgs
     const TvMany tvs = tv_many(p, a.fault);
 #include "rtfhe_body_pair.hpp"
 }
+template <int L, int BGBIT, int KS_T, int KS_BB, int KSQ, int GATES>
+__global__ __launch_bounds__(128 * GATES, 1) void k_pbs_enc_pair(const ManyArgs<BootstrapArgs> p) {
+    const BootstrapArgs& a = p.base;
+    const TvEnc tvs = tv_enc(p, a.fault);
+#include "rtfhe_body_pair.hpp"
+}
 
 }  // namespace rtfhe

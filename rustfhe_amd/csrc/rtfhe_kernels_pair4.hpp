@@ -75,5 +75,11 @@ __global__ __launch_bounds__(256 * GATES, 1) void k_pbs_many_pair4(const ManyArg
     const TvMany tvs = tv_many(p, pa.b.fault);
 #include "rtfhe_body_pair4.hpp"
 }
+template <int L, int BGBIT, int GATES>
+__global__ __launch_bounds__(256 * GATES, 1) void k_pbs_enc_pair4(const ManyArgs<Pair4Args> p) {
+    const Pair4Args& pa = p.base;
+    const TvEnc tvs = tv_enc(p, pa.b.fault);
+#include "rtfhe_body_pair4.hpp"
+}
 
 }  // namespace rtfhe

@@ -49,5 +49,11 @@ __global__ __launch_bounds__(512, 1) void k_pbs_many_pair_rr(const ManyArgs<Boot
     const TvMany tvs = tv_many(p, a.fault);
 #include "rtfhe_body_pair_rr.hpp"
 }
+template <int L, int BGBIT, int KS_T, int KS_BB, int KSQ>
+__global__ __launch_bounds__(512, 1) void k_pbs_enc_pair_rr(const ManyArgs<BootstrapArgs> p) {
+    const BootstrapArgs& a = p.base;
+    const TvEnc tvs = tv_enc(p, a.fault);
+#include "rtfhe_body_pair_rr.hpp"
+}
 
 }  // namespace rtfhe

@@ -69,5 +69,11 @@ __global__ __launch_bounds__(512, 1) void k_pbs_many_wg(const ManyArgs<Bootstrap
     const TvMany tvs = tv_many(p, a.fault);
 #include "rtfhe_body_wg.hpp"
 }
+template <int LOGN, int L, int BGBIT, int KS_T, int KS_BB, int KSQ>
+__global__ __launch_bounds__(512, 1) void k_pbs_enc_wg(const ManyArgs<BootstrapArgs> p) {
+    const BootstrapArgs& a = p.base;
+    const TvEnc tvs = tv_enc(p, a.fault);
+#include "rtfhe_body_wg.hpp"
+}
 
 }  // namespace rtfhe

@@ -2,7 +2,7 @@
 // Off the timed path (the reference's TFHE::new is setup too, hom_nand/src/tfhe.rs:21-25), kept on the
 // host like the reference's.  Follows:
 //   TLWE encrypt/decrypt       hom_nand/src/tlwe.rs:181-241
-//   TRLWE zero encryption      hom_nand/src/trlwe.rs:127-137
+//   TRLWE zero encryption      hom_nand/src/trlwe.rs:127-137 (also of encrypted tables: rtfhe_trlwe_encrypt_torus)
 //   TRGSW encryption of a bit  hom_nand/src/trgsw.rs:118-138,217-229
 //   BootstrappingKey::new      hom_nand/src/tfhe.rs:119-126 (torus form; the device transforms it)
 //   KeySwitchingKey::new       hom_nand/src/tlwe.rs:247-277
@@ -241,6 +241,20 @@ int encrypt_torus(const rtfhe_params* p, Rng& r, const int32_t* key0, const uint
     return 0;
 }
 
+// TRLWE encryptions of the polynomials mu[count][N] under key1 (encrypted tables, rtfhe_lut_create_encrypted): trlwe_zero's
+// b = a * s + e with alpha = 2^-25, as the bootstrapping key's rows, then b += mu.  Layout [count][2][N]: b then a.
+int encrypt_trlwe(const rtfhe_params* p, Rng& r, const int32_t* key1, const uint32_t* mu, uint32_t* out, size_t count) {
+    const int N = p->N;
+    for (int i = 0; i < N; i++) if (key1[i] != 0 && key1[i] != 1) return RTFHE_ERR_INVALID;
+    const float alpha = 1.0f / 33554432.0f;      // 2^-25, trlwe.rs:77
+    for (size_t g = 0; g < count; g++) {
+        uint32_t* b = out + g * 2 * (size_t)N;
+        trlwe_zero(r, N, key1, alpha, b, b + N);
+        for (int k = 0; k < N; k++) b[k] += mu[g * (size_t)N + k];
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -281,6 +295,14 @@ int rtfhe_tlwe_encrypt_torus(const rtfhe_params* p, const int32_t* key0, const u
     return encrypt_torus(p, r, key0, mu, out, count);
 }
 
+int rtfhe_trlwe_encrypt_torus(const rtfhe_params* p, const int32_t* key1, const uint32_t* mu, uint32_t* out, size_t count) {
+    if (!valid(p) || !key1 || !mu || !out) return RTFHE_ERR_INVALID;
+    Source src;
+    if (!Source::from_os(src)) return RTFHE_ERR_STATE;
+    ChaCha r(src.key, 0);          // a fresh OS key per call
+    return encrypt_trlwe(p, r, key1, mu, out, count);
+}
+
 int rtfhe_ksk_expand_ref(const rtfhe_params* p, const int32_t* key0, const int32_t* key1, const uint32_t* ksk, uint32_t* ksk_ref) {
     if (!valid(p) || !key0 || !key1 || !ksk || !ksk_ref) return RTFHE_ERR_INVALID;
     Source src;
@@ -317,6 +339,31 @@ int rtfhe_tlwe_encrypt_torus_deterministic(const rtfhe_params* p, const int32_t*
     if (!valid(p) || !key0 || !mu || !out) return RTFHE_ERR_INVALID;
     Xoshiro r(seed);
     return encrypt_torus(p, r, key0, mu, out, count);
+}
+
+int rtfhe_trlwe_encrypt_torus_deterministic(const rtfhe_params* p, const int32_t* key1, uint64_t seed, const uint32_t* mu, uint32_t* out, size_t count) {
+    if (!valid(p) || !key1 || !mu || !out) return RTFHE_ERR_INVALID;
+    Xoshiro r(seed);
+    return encrypt_trlwe(p, r, key1, mu, out, count);
+}
+
+// phase = b - a * s (exact negacyclic product with the binary key), per TRLWE of ct[count][2][N]
+int rtfhe_trlwe_phase(const rtfhe_params* p, const int32_t* key1, const uint32_t* ct, uint32_t* phase, size_t count) {
+    if (!valid(p) || !key1 || !ct || !phase) return RTFHE_ERR_INVALID;
+    const int N = p->N;
+    for (int i = 0; i < N; i++) if (key1[i] != 0 && key1[i] != 1) return RTFHE_ERR_INVALID;
+    for (size_t g = 0; g < count; g++) {
+        const uint32_t* b = ct + g * 2 * (size_t)N;
+        const uint32_t* a = b + N;
+        uint32_t* ph = phase + g * (size_t)N;
+        std::memcpy(ph, b, (size_t)N * 4);
+        for (int j = 0; j < N; j++) {
+            if (!key1[j]) continue;
+            for (int k = 0; k < N - j; k++) ph[k + j] -= a[k];
+            for (int k = N - j; k < N; k++) ph[k + j - N] += a[k];
+        }
+    }
+    return 0;
 }
 
 int rtfhe_tlwe_phase(const rtfhe_params* p, const int32_t* key0, const uint32_t* in, uint32_t* phase, size_t count) {

@@ -254,6 +254,11 @@ class Engine:
         rustfhe_amd.lut_polynomial builds one for a function of a small integer."""
         return Lut(self, tv)
 
+    def lut_encrypted(self, trlwe):
+        """Uploads an encrypted table (include/rtfhe.h: rtfhe_lut_create_encrypted): u32[n_lut][2][N] (or one u32[2][N]) TRLWE rows under the
+        lvl1 key, e.g. from rustfhe_amd.encrypt_lut.  Returns a Lut (lut.encrypted is True) usable wherever a Lut is."""
+        return Lut(self, trlwe, encrypted=True)
+
     def pbs_batch(self, lut, tlwe, lut_idx=None):
         """One programmable bootstrap per ciphertext: gate g evaluates table lut_idx[g] (None: table 0).  Indices are checked here:
         one outside [0, n_lut) raises RtfheError before anything runs."""
@@ -344,16 +349,18 @@ class Engine:
 
 
 class Lut:
-    """Test polynomials of a programmable bootstrap on an Engine's devices (rtfhe_lut).  Closing it frees the device copies; a Lut whose Engine was
-    closed first only frees its handle."""
+    """Test polynomials of a programmable bootstrap on an Engine's devices (rtfhe_lut), plain or encrypted (TRLWE rows, Engine.lut_encrypted).
+    Closing it frees the device copies; a Lut whose Engine was closed first only frees its handle."""
 
-    def __init__(self, engine, tv):
+    def __init__(self, engine, tv, encrypted=False):
         tv = _np(tv, np.uint32)
-        tv = tv.reshape(-1, engine.p.N)
+        tv = tv.reshape(-1, 2 * engine.p.N if encrypted else engine.p.N)
         self.engine = engine
+        self.encrypted = bool(encrypted)
         self.n_lut = tv.shape[0]
         h = C.c_void_p()
-        engine._ck(engine.L.rtfhe_lut_create(engine.h, _ptr(tv), self.n_lut, C.byref(h)))
+        create = engine.L.rtfhe_lut_create_encrypted if encrypted else engine.L.rtfhe_lut_create
+        engine._ck(create(engine.h, _ptr(tv), self.n_lut, C.byref(h)))
         self.h = h
 
     def close(self):
@@ -510,6 +517,35 @@ def encrypt_torus(params, key0, mu, seed=None):
     if rc != 0:
         raise RtfheError(rc, "rtfhe_tlwe_encrypt_torus failed")
     return out
+
+
+def encrypt_lut(params, key1, tv, seed=None):
+    """TRLWE encryptions under the lvl1 key key1 of test polynomials tv (u32[n_lut][N] or one u32[N]): u32[n_lut][2][N] (b then a), the rows of
+    an encrypted table (Engine.lut_encrypted).  Noise alpha = 2^-25 as the bootstrapping key's rows.  seed None (production): OS CSPRNG; an
+    integer seed = TEST-ONLY deterministic encryption."""
+    L = _ffi.load()
+    tv = _np(tv, np.uint32).reshape(-1, params.N)
+    key1 = _np(key1, np.int32)
+    out = np.empty((tv.shape[0], 2, params.N), np.uint32)
+    if seed is None:
+        rc = L.rtfhe_trlwe_encrypt_torus(C.byref(params), _ptr(key1), _ptr(tv), _ptr(out), tv.shape[0])
+    else:
+        rc = L.rtfhe_trlwe_encrypt_torus_deterministic(C.byref(params), _ptr(key1), seed, _ptr(tv), _ptr(out), tv.shape[0])
+    if rc != 0:
+        raise RtfheError(rc, "rtfhe_trlwe_encrypt_torus failed")
+    return out
+
+
+def trlwe_phase(params, key1, ct):
+    """b - a * s of TRLWE ciphertexts u32[count][2][N] under key1: u32[count][N] (the plaintext plus the noise)."""
+    L = _ffi.load()
+    ct = _np(ct, np.uint32).reshape(-1, 2, params.N)
+    key1 = _np(key1, np.int32)
+    ph = np.empty((ct.shape[0], params.N), np.uint32)
+    rc = L.rtfhe_trlwe_phase(C.byref(params), _ptr(key1), _ptr(ct), _ptr(ph), ct.shape[0])
+    if rc != 0:
+        raise RtfheError(rc, "rtfhe_trlwe_phase failed")
+    return ph
 
 
 def decrypt_bits(params, key0, cts):

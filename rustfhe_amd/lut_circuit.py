@@ -141,11 +141,13 @@ class LutNetlist:
 
 class LutCircuitRunner:
     """Runs `replicas` independent instances of a LutNetlist on one Engine as ONE recorded circuit.  Wire table: int32[replicas * num_wires][n+1]
-    in HBM; the inputs of replica r are rows r * num_wires + 0 .. num_inputs - 1."""
+    in HBM; the inputs of replica r are rows r * num_wires + 0 .. num_inputs - 1.  Given the lvl1 key key1, the tables are encrypted under it
+    (rustfhe_amd.encrypt_lut; seed: TEST-ONLY deterministic encryption) and the circuit holds them only as ciphertexts (Engine.lut_encrypted)."""
 
-    def __init__(self, engine, net, replicas=1):
+    def __init__(self, engine, net, replicas=1, key1=None, seed=None):
         import torch
         self.e, self.net, self.R = engine, net, replicas
+        self.key1, self.seed = key1, seed
         self.n1 = engine.p.n + 1
         self.wires = torch.zeros((replicas * net.num_wires, self.n1), dtype=torch.int32, device="cuda")
         self.desc = net.arrays(replicas)
@@ -163,7 +165,13 @@ class LutCircuitRunner:
         circuit keeps its own copy)."""
         if self._circuit is None and self.net.nodes:
             d = self.desc
-            with self.e.lut(self.net.polynomials(self.e.p.N)) as lut:
+            tv = self.net.polynomials(self.e.p.N)
+            if self.key1 is not None:
+                from .engine import encrypt_lut
+                lut = self.e.lut_encrypted(encrypt_lut(self.e.p, self.key1, tv, self.seed))
+            else:
+                lut = self.e.lut(tv)
+            with lut:
                 self._circuit = self.e.lut_circuit_create(lut, d["fan_in"], d["in_idx"], d["weights"], d["cst"], d["lut_idx"], d["wave_offsets"],
                                                           d["wave_n_out"], d["out_idx"], self.wires, d["num_wires"])
         if self._circuit is not None:
