@@ -77,6 +77,9 @@ int launch_bootstrap_pair4_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, con
 }
 
 // N = 2048: two waves per transform, split by the parity of the point index (rtfhe_kernels_eo.hpp)
+// gates per workgroup (= per CU) of its whole rounds: four, or three at the mask lengths where four gates' carve passes the CU's LDS
+// (npad = 768, n >= 704: 163,904 bytes)
+constexpr int eo_round_gates(int npad) { return EoLds::bytes(4, npad) <= LDS_LIMIT ? 4 : 3; }
 template <int GATES>
 int launch_bootstrap_eo11_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
     const EoArgs a{b, ctx->d_etw, ctx->d_ebk};
@@ -152,19 +155,34 @@ int launch_bootstrap_t(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const Lut
         // (a gate's two waves then share their SIMDs with fewer other waves: a single gate takes 0.67 x a full round)
         if (split_ok(ctx, a, s)) return launch_split(ctx, a, s, rotate);
         const size_t out_words = mode_out_words(a, 1 << LOGN);
-        const size_t cus = (size_t)ctx->num_cus, round = 4 * cus, count = (size_t)a.count;
+        // (three gates per CU in the whole rounds where four gates' LDS does not fit: eo_round_gates)
+        const size_t cus = (size_t)ctx->num_cus, round = (size_t)ctx->eo_round * cus, count = (size_t)a.count;
         const size_t full = count / round * round, rem = count - full;
         if (full)
-            if (int rc = launch_bootstrap_n2048_g<4>(ctx, seg(0, full, out_words), s, lut)) return rc;
+            if (int rc = ctx->eo_round == 4 ? launch_bootstrap_n2048_g<4>(ctx, seg(0, full, out_words), s, lut) : launch_bootstrap_n2048_g<3>(ctx, seg(0, full, out_words), s, lut)) return rc;
         if (!rem) return 0;
         const BootstrapArgs tail = seg(full, rem, out_words);
         const LutRef tl = lut_segment(lut, full);
         if (rem <= cus) return launch_bootstrap_n2048_g<1>(ctx, tail, s, tl);
         if (rem <= 2 * cus) return launch_bootstrap_n2048_g<2>(ctx, tail, s, tl);
-        if (rem <= 3 * cus) return launch_bootstrap_n2048_g<3>(ctx, tail, s, tl);
+        if (rem <= 3 * cus) return launch_bootstrap_n2048_g<3>(ctx, tail, s, tl);      // (always, when eo_round is 3)
         return launch_bootstrap_n2048_g<4>(ctx, tail, s, tl);
     }
 }
+
+// Every (kernel family, gates per workgroup) the dispatch above can launch fits the CU's LDS at the longest mask the context accepts
+// (NPAD_MAX); where a family takes fewer gates at long masks, the function that prime_fft_kernels decides with is the one checked here.
+static_assert(PairLds::bytes(4, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_pair, 4 gates");
+static_assert(WgLds<10, 3>::bytes(NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_wg");
+static_assert(Pair4Lds::bytes(3, NPAD_MAX) <= LDS_LIMIT && Pair4Lds::bytes(2, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_pair4, 2 and 3 gates");
+static_assert(bootstrap_lds_bytes<10>(4, NPAD_MAX, bootstrap_dual_xbuf(10, 4)) <= LDS_LIMIT, "k_bootstrap<10>, 4 waves");
+static_assert(bootstrap_lds_bytes<10>(8, NPAD_MAX, bootstrap_dual_xbuf(10, 8)) <= LDS_LIMIT, "k_bootstrap<10>, 8 waves");
+static_assert(rr_fit<PairRrLds>(640) == 6 && rr_fit<PairRrLds>(704) == 5 && rr_fit<PairRrLds>(NPAD_MAX) == 5, "k_bootstrap_pair_rr: six gates per CU up to n = 639, five beyond");
+static_assert(PairRrLds::bytes(rr_fit<PairRrLds>(NPAD_MAX), NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_pair_rr at the longest mask");
+static_assert(bootstrap_lds_bytes<11>(4, NPAD_MAX, bootstrap_dual_xbuf(11, 4)) <= LDS_LIMIT, "k_bootstrap<11>, 4 waves");
+static_assert(eo_round_gates(704) == 4 && eo_round_gates(NPAD_MAX) == 3, "k_bootstrap_eo: four gates per CU up to n = 703, three beyond");
+static_assert(EoLds::bytes(eo_round_gates(NPAD_MAX), NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_eo at the longest mask");
+static_assert(Eo4Lds::bytes(2, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_eo4, 2 gates");
 
 // which second key layout the dispatch above reads for a batch of `count` gates in `mode` (0 = none)
 enum { LAYOUT_NONE = 0, LAYOUT_P4 = 1, LAYOUT_EO = 2 };
@@ -323,9 +341,7 @@ int prime_fft_kernels(rtfhe_ctx* ctx) {
         if (int rc = allow_twins(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_many_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_enc_wg<10, 3, 6, 8, 2, KSQ>, WgLds<10, 3>::bytes(npad))) return rc;
         // the time-sliced launch: as many gates per CU (five or six) as this mask length leaves room for in 160 KiB of LDS
         {
-            int fit = 0;
-            for (int g = 5; g <= PairRrLds::GMAX; g++)
-                if (PairRrLds::bytes(g, npad) <= (size_t)160 * 1024) fit = g;
+            const int fit = rr_fit<PairRrLds>(npad);
             if (ctx->rr > fit) ctx->rr = fit;
             if (ctx->rr >= 5)
                 if (int rc = allow_twins(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_many_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_enc_pair_rr<3, 6, 8, 2, KSQ>, PairRrLds::bytes(ctx->rr, npad))) return rc;
@@ -336,7 +352,10 @@ int prime_fft_kernels(rtfhe_ctx* ctx) {
         if (int rc = allow_twins(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 8>, k_pbs<10, 3, 6, 8, 2, KSQ, 8>, k_pbs_many<10, 3, 6, 8, 2, KSQ, 8>, k_pbs_enc<10, 3, 6, 8, 2, KSQ, 8>, bootstrap_lds_bytes<10>(8, npad, bootstrap_dual_xbuf(10, 8)))) return rc;
     } else {
         if (int rc = allow_twins(ctx, k_bootstrap<11, 3, 6, 8, 2, KSQ, 4>, k_pbs<11, 3, 6, 8, 2, KSQ, 4>, k_pbs_many<11, 3, 6, 8, 2, KSQ, 4>, k_pbs_enc<11, 3, 6, 8, 2, KSQ, 4>, bootstrap_lds_bytes<11>(4, npad, bootstrap_dual_xbuf(11, 4)))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 4>, EoLds::bytes(4, npad))) return rc;
+        // whole rounds of four gates per CU where their LDS fits, of three at the longest masks (the four-gate kernel is then never launched)
+        ctx->eo_round = eo_round_gates(npad);
+        if (ctx->eo_round == 4)
+            if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 4>, EoLds::bytes(4, npad))) return rc;
         if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 3>, EoLds::bytes(3, npad))) return rc;
         if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 2>, EoLds::bytes(2, npad))) return rc;
         if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 1>, EoLds::bytes(1, npad))) return rc;

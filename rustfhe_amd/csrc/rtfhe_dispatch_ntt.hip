@@ -161,6 +161,12 @@ int launch_bootstrap_ntt_halves(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) 
     return launch_bootstrap_ntt_halves_g<4>(ctx, tail, s);
 }
 
+// Every (kernel family, gates per workgroup) the dispatch above can launch fits the CU's LDS at the longest mask the context accepts
+static_assert(NttPairLds::bytes(4, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_ntt_pair, 4 gates");
+static_assert(ntt_lds_bytes(4, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_ntt, 4 waves");
+static_assert(NttWgLds::bytes(NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_ntt_wg");
+static_assert(NttHalvesLds::bytes(NTT_HALVES_ROUND, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_ntt_halves, a whole round's gates");
+
 }  // namespace
 
 namespace rtfhe_host {

@@ -167,6 +167,11 @@ int launch_xpair(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
     return launch_xpair_g<4>(ctx, tail, s);
 }
 
+// Every (kernel family, gates per workgroup) the dispatch above can launch fits the CU's LDS at the longest mask the context accepts
+static_assert(XPairLds::bytes(4, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_xpair, 4 gates");
+static_assert(XQuadLds::bytes(2, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_xquad, 2 gates");
+static_assert(rr_fit<XPairRrLds>(NPAD_MAX) == 0 || XPairRrLds::bytes(rr_fit<XPairRrLds>(NPAD_MAX), NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_xpair_rr at the longest mask");
+
 }  // namespace
 
 namespace rtfhe_host {
@@ -231,9 +236,7 @@ int prime_xfft_kernels(rtfhe_ctx* ctx) {
     }
     if (int rc = allow_lds(ctx, k_bootstrap_xpair<3, 6, 8, 2, KSQ, 4>, XPairLds::bytes(4, npad))) return rc;
     {   // the time-sliced launch: five or six gates per CU, as many as this mask length leaves room for in 160 KiB of LDS
-        int fit = 0;
-        for (int g = 5; g <= XPairRrLds::GMAX; g++)
-            if (XPairRrLds::bytes(g, npad) <= (size_t)160 * 1024) fit = g;
+        const int fit = rr_fit<XPairRrLds>(npad);
         ctx->xrr = ctx->rr < fit ? ctx->rr : fit;
         if (ctx->xrr >= 5)
             if (int rc = allow_lds(ctx, k_bootstrap_xpair_rr<3, 6, 8, 2, KSQ>, XPairRrLds::bytes(ctx->xrr, npad))) return rc;

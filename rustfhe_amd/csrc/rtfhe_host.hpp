@@ -67,6 +67,7 @@ struct rtfhe_ctx {
                                       // (k_bootstrap_pair_rr; RTFHE_PAIR_RR: 0 = never, 5, 6 = default)
     int xrr = 0;                      // ... the same on the split-FFT exact backend (k_bootstrap_xpair_rr): min(rr, what fits), set when that backend's kernels are primed
     int eo4 = 1;                      // N = 2048, up to two gates per CU: 1 = four waves per gate (k_bootstrap_eo4), 0 = two (RTFHE_N2048_EO4)
+    int eo_round = 4;                 // N = 2048: gates per CU in a whole round of k_bootstrap_eo: 4, or 3 where four gates' LDS passes 160 KiB (n >= 704), set when the kernels are primed
     int backend = RTFHE_BACKEND_FFT64_MIRROR;
     uint32_t* d_bk_torus = nullptr;   // kept when the key came in torus form: source for the NTT-domain key
     double* d_ntt_bk = nullptr;
@@ -168,6 +169,16 @@ inline LutRef lut_on(const rtfhe_lut* lut, int entry, const int32_t* d_idx, int3
 using rtfhe::cplx;
 
 constexpr int KSQ = 3;        // uint4 loads per lane per key-switch row: rows up to 768 words
+constexpr int NPAD_MAX = 256 * KSQ;                 // n + 1 <= 768 (rtfhe_ctx_create): the largest npad = (n + 1) rounded up to 64 a kernel is sized for
+constexpr size_t LDS_LIMIT = (size_t)160 * 1024;    // LDS of a gfx950 CU = the most dynamic LDS one workgroup can be granted
+// the time-sliced launches (k_bootstrap_pair_rr, k_bootstrap_xpair_rr): as many gates per CU, five .. GMAX, as a mask length leaves room for; 0 = none
+template <typename Lds>
+constexpr int rr_fit(int npad) {
+    int fit = 0;
+    for (int g = 5; g <= Lds::GMAX; g++)
+        if (Lds::bytes(g, npad) <= LDS_LIMIT) fit = g;
+    return fit;
+}
 constexpr int KSMM_MT = 4;    // gate tiles (of 16) per wave of k_key_switch_mm
 
 // ---- errors (rtfhe_context.hip) ----
