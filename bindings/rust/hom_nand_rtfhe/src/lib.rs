@@ -125,6 +125,50 @@ impl<const TLWE_N: usize, const TRLWE_N: usize> TFHE<TLWE_N, TRLWE_N> {
         self.gate(sys::RTFHE_NAND, a, Some(b))
     }
     pub fn params(&self) -> &sys::rtfhe_params { &self.params }
+
+    /// TRGSW encryptions of `bits` under the lvl1 key (`Crypto<i32> for TRGSW`, trgsw.rs:217-229), flat `u32[bits.len()][2][2l][N]`:
+    /// the encrypted address bits of `cmux_tree`.  Client side; masks and noise from the OS CSPRNG.
+    pub fn encrypt_selectors(&self, s_key_tlwelv1: &[Binary; TRLWE_N], bits: &[u8]) -> Vec<u32> {
+        let k1: Vec<i32> = s_key_tlwelv1.iter().map(|&b| b as i32).collect();
+        let mut out = vec![0u32; bits.len() * 2 * 2 * self.params.l as usize * TRLWE_N];
+        Self::check(std::ptr::null(), unsafe { sys::rtfhe_trgsw_encrypt_bits(&self.params, k1.as_ptr(), bits.as_ptr(), out.as_mut_ptr(), bits.len()) });
+        out
+    }
+    /// `TRGSWRepF::cmux` (trgsw.rs:319-321) as a tree: lookup g selects row `sum_k bit_k 2^k` of the `2^depth` TRLWE rows `rows`
+    /// (flat `u32[2^depth][2][N]`, b then a) with the selectors `g * depth + k` of `selectors` (flat, from `encrypt_selectors`).
+    /// Returns the selected rows, flat `u32[count][2][N]`.
+    pub fn cmux_tree(&self, selectors: &[u32], depth: usize, rows: &[u32], count: usize) -> Vec<u32> {
+        let mut out = vec![0u32; count * 2 * TRLWE_N];
+        self.tree(selectors, depth, rows, count, |ctx, sel, lut| unsafe {
+            sys::rtfhe_cmux_tree_batch(ctx, sel, std::ptr::null(), depth as i32, lut, std::ptr::null(), out.as_mut_ptr(), count)
+        });
+        out
+    }
+    /// ... followed by `identity_key_switch(sample_extract_index(row, coef[g]))`: coefficient `coef[g]` of the selected row as a TLWE.
+    pub fn cmux_tree_extract(&self, selectors: &[u32], depth: usize, rows: &[u32], coef: &[i32]) -> Vec<TLWERep<TLWE_N>> {
+        let (count, w) = (coef.len(), TLWE_N + 1);
+        let mut out = vec![0u32; count * w];
+        self.tree(selectors, depth, rows, count, |ctx, sel, lut| unsafe {
+            sys::rtfhe_cmux_tree_extract_batch(ctx, sel, std::ptr::null(), depth as i32, lut, std::ptr::null(), coef.as_ptr(), out.as_mut_ptr(), count)
+        });
+        out.chunks(w).map(TLWERep::from_flat).collect()
+    }
+    fn tree<F: FnOnce(*mut sys::rtfhe_ctx, *const sys::rtfhe_trgsw, *const sys::rtfhe_lut) -> c_int>(&self, selectors: &[u32], depth: usize, rows: &[u32],
+                                                                                                    count: usize, call: F) {
+        let trgsw = 2 * 2 * self.params.l as usize * TRLWE_N;
+        assert_eq!(selectors.len(), count * depth * trgsw);
+        assert_eq!(rows.len(), (1usize << depth) * 2 * TRLWE_N);
+        let mut sel: *mut sys::rtfhe_trgsw = std::ptr::null_mut();
+        let mut lut: *mut sys::rtfhe_lut = std::ptr::null_mut();
+        unsafe {
+            Self::check(self.ctx, sys::rtfhe_trgsw_create(self.ctx, selectors.as_ptr(), (count * depth) as i32, &mut sel));
+            let rc = sys::rtfhe_lut_create_encrypted(self.ctx, rows.as_ptr(), 1i32 << depth, &mut lut);
+            let rc = if rc == 0 { call(self.ctx, sel, lut) } else { rc };
+            sys::rtfhe_lut_destroy(lut);
+            sys::rtfhe_trgsw_destroy(sel);
+            Self::check(self.ctx, rc);
+        }
+    }
 }
 
 impl<const TLWE_N: usize, const TRLWE_N: usize> Drop for TFHE<TLWE_N, TRLWE_N> {

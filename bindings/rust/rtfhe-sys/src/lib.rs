@@ -32,6 +32,7 @@ pub struct rtfhe_peer_info {
 pub enum rtfhe_ctx {}
 pub enum rtfhe_circuit {}
 pub enum rtfhe_lut {}
+pub enum rtfhe_trgsw {}
 pub enum rtfhe_fft_plan {}
 
 pub const RTFHE_NAND: c_int = 0;
@@ -117,6 +118,18 @@ extern "C" {
                                     d_wires: *mut c_void, num_wires: usize, out: *mut *mut rtfhe_circuit) -> c_int;
     // encrypted tables: rows TRLWE [n_lut][2][N] under key1, accepted by the PBS entries and rtfhe_lut_circuit_create (freed by rtfhe_lut_destroy)
     pub fn rtfhe_lut_create_encrypted(ctx: *mut rtfhe_ctx, trlwe: *const u32, n_lut: i32, out: *mut *mut rtfhe_lut) -> c_int;
+    // CMUX-tree table lookup: selector sets (TRGSW samples [n_sel][2][2l][N] under key1), then one row out of 2^depth per lookup;
+    // sel_idx [count][depth] (null: g * depth + k), row0 [count] (null: 0), coef [count] (null: 0); out [count][2][N] / extract form [count][n+1]
+    pub fn rtfhe_trgsw_create(ctx: *mut rtfhe_ctx, trgsw: *const u32, n_sel: i32, out: *mut *mut rtfhe_trgsw) -> c_int;
+    pub fn rtfhe_trgsw_destroy(sel: *mut rtfhe_trgsw);
+    pub fn rtfhe_cmux_tree_batch(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, sel_idx: *const i32, depth: i32, lut: *const rtfhe_lut, row0: *const i32,
+                                 out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_cmux_tree_batch_dev(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, d_sel_idx: *const c_void, depth: i32, lut: *const rtfhe_lut,
+                                     d_row0: *const c_void, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
+    pub fn rtfhe_cmux_tree_extract_batch(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, sel_idx: *const i32, depth: i32, lut: *const rtfhe_lut,
+                                         row0: *const i32, coef: *const i32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_cmux_tree_extract_batch_dev(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, d_sel_idx: *const c_void, depth: i32, lut: *const rtfhe_lut,
+                                             d_row0: *const c_void, d_coef: *const c_void, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
     pub fn rtfhe_sync(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_begin(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_end(ctx: *mut rtfhe_ctx, stream: *mut c_void, ms: *mut f64, launches: *mut i64) -> c_int;
@@ -149,6 +162,7 @@ extern "C" {
     pub fn rtfhe_tlwe_encrypt_bits(p: *const rtfhe_params, key0: *const i32, bits: *const u8, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_tlwe_encrypt_torus(p: *const rtfhe_params, key0: *const i32, mu: *const u32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_trlwe_encrypt_torus(p: *const rtfhe_params, key1: *const i32, mu: *const u32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trgsw_encrypt_bits(p: *const rtfhe_params, key1: *const i32, bits: *const u8, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_trlwe_phase(p: *const rtfhe_params, key1: *const i32, ct: *const u32, phase: *mut u32, count: usize) -> c_int;
     // TEST ONLY (seeded xoshiro256**, not secure)
     pub fn rtfhe_ksk_expand_ref(p: *const rtfhe_params, key0: *const i32, key1: *const i32, ksk: *const u32, ksk_ref: *mut u32) -> c_int;
@@ -158,6 +172,7 @@ extern "C" {
     pub fn rtfhe_tlwe_encrypt_bits_deterministic(p: *const rtfhe_params, key0: *const i32, seed: u64, bits: *const u8, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_tlwe_encrypt_torus_deterministic(p: *const rtfhe_params, key0: *const i32, seed: u64, mu: *const u32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_trlwe_encrypt_torus_deterministic(p: *const rtfhe_params, key1: *const i32, seed: u64, mu: *const u32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trgsw_encrypt_bits_deterministic(p: *const rtfhe_params, key1: *const i32, seed: u64, bits: *const u8, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_tlwe_decrypt_bits(p: *const rtfhe_params, key0: *const i32, input: *const u32, bits: *mut u8, count: usize) -> c_int;
     pub fn rtfhe_keys_write(path: *const c_char, p: *const rtfhe_params, key0: *const i32, key1: *const i32, bk: *const u32, ksk: *const u32) -> c_int;
     pub fn rtfhe_keys_read_header(path: *const c_char, p: *mut rtfhe_params, flags: *mut u32) -> c_int;

@@ -30,6 +30,10 @@
  *                                       replayed through rtfhe_circuit_launch
  *   rtfhe_lut_create_encrypted       (no reference counterpart) tables the server holds only as TRLWE ciphertexts: the blind rotation
  *                                       starts from TRLWERep encryptions (hom_nand/src/trlwe.rs) instead of the trivial (tv, 0)
+ *   rtfhe_trgsw_create / rtfhe_cmux_tree_batch[_dev] / rtfhe_cmux_tree_extract_batch[_dev]
+ *                                    <- TRGSWRepF::from and TRGSWRepF::cmux (hom_nand/src/trgsw.rs:68-76, 319-321) on caller-supplied TRGSW samples:
+ *                                       one row out of 2^d rows of a table selected by d encrypted address bits (the reference has the CMUX,
+ *                                       not the tree)
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch           <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -335,6 +339,61 @@ int rtfhe_lut_circuit_create(rtfhe_ctx *ctx, const rtfhe_lut *lut, int32_t fan_i
                              const int32_t *wave_offsets /* [num_waves + 1] node offsets */, const int32_t *wave_n_out /* [num_waves] */,
                              int32_t num_waves, const int32_t *out_idx /* [Σ over nodes of its wave's n_out] */, void *d_wires,
                              size_t num_wires, rtfhe_circuit **out);
+/* ---- CMUX-tree table lookup: one row out of 2^d, selected by TRGSW-encrypted address bits (TFHE's leveled mode) ----
+ * A selector set holds n_sel TRGSW samples under the lvl1 key key1, each in the torus layout of ONE bootstrapping-key entry, u32[2][2l][N]
+ * (comp 0 = TRGSWRep.cipher rows, comp 1 = TRGSWRep.p_key rows), e.g. from rtfhe_trgsw_encrypt_bits.  rtfhe_trgsw_create converts them as
+ * rtfhe_load_bk_torus converts the key -- TRGSWRepF::from (hom_nand/src/trgsw.rs:68-76): the forward transform of the words viewed as signed
+ * i32 -- and keeps the spectra on the primary device in the canonical device layout [2l][2][R][64].  The set owns its device copy and is
+ * independent of the context's bootstrapping key: a context with no keys loaded runs rtfhe_cmux_tree_batch.  It is normally destroyed before
+ * its context; if the context goes first, the spectra are released with it, a later tree call fails with RTFHE_ERR_STATE and
+ * rtfhe_trgsw_destroy only frees the handle.
+ *
+ * Lookup g of a batch has the depth d = `depth` (1 .. 16, the same for the whole batch), selector indices sel_idx[g][0 .. d) -- entry k is
+ * address bit k, least significant first -- and the first table row row0[g] of an rtfhe_lut with n_lut rows (plain or encrypted).  It computes
+ *
+ *     level 0 nodes   r_j = row (row0[g] + j),  j = 0 .. 2^d - 1;  a plain row tv is the trivial TRLWE (b = tv, a = 0), an encrypted row is (tb, ta)
+ *     level k = 0 .. d-1:   r'_j = cmux(S_k, r_{2j+1}, r_{2j}) = cross(S_k, r_{2j+1} - r_{2j}) + r_{2j},   S_k = selector sel_idx[g][k]
+ *     result          the single node left after level d - 1: a TRLWE of row row0[g] + sum_k bit_k 2^k
+ *
+ * The subtraction and the addition wrap on every word of both polynomials; cross is Cross for TRGSWRepF (trgsw.rs:264-306: gadget
+ * decomposition of both polynomials, 2l forward transforms, multiply-accumulate against the selector's spectra in the order h = b then a,
+ * digit 0 .. l-1, two inverse transforms with truncation), i.e. exactly what rtfhe_external_product_batch computes for a key entry.
+ * sel_idx NULL: lookup g uses selectors g * depth + k.  row0 NULL: 0 for every lookup.
+ *   rtfhe_cmux_tree_batch[_dev]          out[g] = the result, u32[2][N] (b then a): the row format rtfhe_lut_create_encrypted takes, so high address
+ *                                        bits by CMUX tree and low bits by PBS compose into full vertical packing
+ *   rtfhe_cmux_tree_extract_batch[_dev]  out[g] = identity_key_switch(sample_extract_index(result, coef[g])), u32[n+1]: coefficient coef[g] of the
+ *                                        selected row as a lvl0 ciphertext (plaintext low address bits for free: N values per row).  coef NULL:
+ *                                        index 0.  Needs the key-switching key (RTFHE_ERR_STATE otherwise), not the bootstrapping key.  The samples
+ *                                        go through the batch key switch of rtfhe_pbs_many_batch (the stream's lvl1 sample buffer, then the key
+ *                                        switch as one i8 contraction, or one wave per sample under RTFHE_KS_MM_MIN=0).
+ * Checks: the handles, depth, count (count * 2^(depth-1) < 2^31), every host-side index -- sel_idx in [0, n_sel), row0 >= 0 and
+ * row0 + 2^depth <= n_lut, coef in [0, N), and with sel_idx NULL count * depth <= n_sel -- are checked before anything is allocated or launched:
+ * RTFHE_ERR_INVALID with a message naming the lookup.  The _dev forms take sel_idx / row0 / coef as device arrays and check them in the kernel:
+ * a lookup with a bad index is skipped (its output is not a valid ciphertext) and the next rtfhe_sync returns RTFHE_ERR_INVALID, as for
+ * rtfhe_pbs_batch_dev.  The FP64 mirror backend only: on either exact backend every tree call fails with RTFHE_ERR_INVALID (the context stays
+ * usable).  A multi-device context runs the tree on its primary device.
+ * Scratch: level k writes count * 2^(d-1-k) nodes; the levels alternate between two buffers that belong to the stream, each of
+ *     4 * count * 2^(depth-1) * 2N  bytes      (none for depth 1)
+ * grown outside stream captures only and kept until the context is destroyed; rtfhe_ctx_memory_bytes does not count them (as for LUT circuits).
+ * Growing them synchronises the whole device (hipDeviceSynchronize: earlier trees of the stream may still read the old pair), so a call that
+ * needs a larger pair than the stream has -- the first call on a stream, or a larger count * 2^(depth-1) -- stalls every stream of the process
+ * once, also in the otherwise asynchronous _dev forms; run the largest shape once up front to keep later calls asynchronous.
+ * Inside a caller's stream capture the rule of rtfhe_pbs_many_batch_dev applies: an eager call of the same entry point with at least this
+ * count * 2^(depth-1) (and, for the extract form, at least this count) must have run on that stream first, else RTFHE_ERR_STATE. */
+typedef struct rtfhe_trgsw rtfhe_trgsw;
+int rtfhe_trgsw_create(rtfhe_ctx *ctx, const uint32_t *trgsw /* [n_sel][2][2l][N] */, int32_t n_sel, rtfhe_trgsw **out);
+void rtfhe_trgsw_destroy(rtfhe_trgsw *sel);
+int rtfhe_cmux_tree_batch(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const int32_t *sel_idx /* [count][depth] or NULL */, int32_t depth,
+                          const rtfhe_lut *lut, const int32_t *row0 /* [count] or NULL */, uint32_t *out /* [count][2][N] */, size_t count);
+int rtfhe_cmux_tree_batch_dev(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const void *d_sel_idx /* int32[count][depth] or NULL */, int32_t depth,
+                              const rtfhe_lut *lut, const void *d_row0 /* int32[count] or NULL */, void *d_out /* [count][2][N] */, size_t count,
+                              void *stream);
+int rtfhe_cmux_tree_extract_batch(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const int32_t *sel_idx /* [count][depth] or NULL */, int32_t depth,
+                                  const rtfhe_lut *lut, const int32_t *row0 /* [count] or NULL */, const int32_t *coef /* [count] or NULL */,
+                                  uint32_t *out /* [count][n+1] */, size_t count);
+int rtfhe_cmux_tree_extract_batch_dev(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const void *d_sel_idx /* int32[count][depth] or NULL */, int32_t depth,
+                                      const rtfhe_lut *lut, const void *d_row0 /* int32[count] or NULL */, const void *d_coef /* int32[count] or NULL */,
+                                      void *d_out /* [count][n+1] */, size_t count, void *stream);
 /* waits for `stream`; also reports (once) a netlist gate skipped since the previous call */
 int rtfhe_sync(rtfhe_ctx *ctx, void *stream);
 /* device-side timing of the launches enqueued by the *_dev calls between begin and end (HIP events on
@@ -402,6 +461,11 @@ int rtfhe_trlwe_encrypt_torus(const rtfhe_params *p, const int32_t *key1, const 
                               uint32_t *out /* [count][2][N] */, size_t count);
 int rtfhe_trlwe_phase(const rtfhe_params *p, const int32_t *key1, const uint32_t *ct /* [count][2][N] */,
                       uint32_t *phase /* [count][N] */, size_t count);
+/* TRGSW encryptions under key1 [N] of the bits[count] (OS CSPRNG): what rtfhe_keygen does for every bit of key0 to make the bootstrapping key
+ * (Crypto<i32> for TRGSW, hom_nand/src/trgsw.rs:118-138, 217-229; noise alpha = 2^-25), each in the layout of one key entry, u32[2][2l][N]: the
+ * encrypted address bits of a CMUX tree (rtfhe_trgsw_create). */
+int rtfhe_trgsw_encrypt_bits(const rtfhe_params *p, const int32_t *key1, const uint8_t *bits /* [count] */,
+                             uint32_t *out /* [count][2][2l][N] */, size_t count);
 /* the reference's KeySwitchingKey shape from the compact one: entries t = 1 .. base-1 of every level copied, entry t = base =
  * TLWE(base * s_i / 2^(basebit (l+1))) freshly encrypted as KeySwitchingKey::new fills it (hom_nand/src/tlwe.rs:252-274) */
 int rtfhe_ksk_expand_ref(const rtfhe_params *p, const int32_t *key0, const int32_t *key1,
@@ -420,6 +484,8 @@ int rtfhe_tlwe_encrypt_torus_deterministic(const rtfhe_params *p, const int32_t 
                                             const uint32_t *mu, uint32_t *out /* [count][n+1] */, size_t count);
 int rtfhe_trlwe_encrypt_torus_deterministic(const rtfhe_params *p, const int32_t *key1, uint64_t seed,
                                             const uint32_t *mu /* [count][N] */, uint32_t *out /* [count][2][N] */, size_t count);
+int rtfhe_trgsw_encrypt_bits_deterministic(const rtfhe_params *p, const int32_t *key1, uint64_t seed, const uint8_t *bits /* [count] */,
+                                           uint32_t *out /* [count][2][2l][N] */, size_t count);
 int rtfhe_tlwe_decrypt_bits(const rtfhe_params *p, const int32_t *key0, const uint32_t *in,
                             uint8_t *bits, size_t count);
 int rtfhe_tlwe_phase(const rtfhe_params *p, const int32_t *key0, const uint32_t *in, uint32_t *phase, size_t count);

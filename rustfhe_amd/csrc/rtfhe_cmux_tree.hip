@@ -1,0 +1,243 @@
+// rtfhe_cmux_tree.hip -- CMUX-tree table lookup with caller-supplied TRGSW selectors (include/rtfhe.h: rtfhe_trgsw_create,
+// rtfhe_cmux_tree_batch[_dev], rtfhe_cmux_tree_extract_batch[_dev]): selector sets, the argument checks, the stream's ping-pong buffers
+// and the rules around stream captures, one launch of k_cmux_tree per level, and for the extract form the batch key switch many-LUT uses.
+#include "rtfhe_host.hpp"
+
+#include <cstdlib>
+
+#include "rtfhe_kernels_cmux_tree.hpp"
+
+using namespace rtfhe;
+using namespace rtfhe_host;
+
+namespace {
+
+template <int LOGN, int W>
+int launch_level_t(rtfhe_ctx* ctx, const CmuxTreeArgs& a, size_t nodes, hipStream_t s) {
+    auto k = k_cmux_tree<LOGN, 3, 6, W>;
+    constexpr size_t lds = cmux_tree_lds_bytes<LOGN, W>();
+    if (int rc = allow_lds(ctx, k, lds)) return rc;
+    hipLaunchKernelGGL(k, dim3((unsigned)((nodes + W - 1) / W)), dim3(64 * W), lds, s, a);
+    HIPCHECK(ctx, hipGetLastError());
+    ctx->launches++;
+    return 0;
+}
+
+int launch_level(rtfhe_ctx* ctx, const CmuxTreeArgs& a, size_t nodes, hipStream_t s) {
+    // four waves (= nodes) per workgroup at both N, the shape of k_external_product
+    return ctx->logn == 11 ? launch_level_t<11, 4>(ctx, a, nodes, s) : launch_level_t<10, 4>(ctx, a, nodes, s);
+}
+
+bool capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+// what every tree entry checks before anything is allocated or launched; host_* are the host-side index arrays (null in the _dev forms, whose
+// arrays are checked by the kernel), out the caller's result buffer
+int tree_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const rtfhe_lut* lut, int32_t depth, size_t count, bool has_sel_idx, bool has_row0,
+               const int32_t* host_sel_idx, const int32_t* host_row0, const int32_t* host_coef, const void* out, bool extract) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!sel) return fail(ctx, RTFHE_ERR_INVALID, "null selector set (rtfhe_trgsw)");
+    if (!lut) return fail(ctx, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
+    if (!out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (!sel->ctx || !lut->ctx) return fail(ctx, RTFHE_ERR_STATE, "the context of the selector set or of the table has been destroyed");
+    if (sel->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the selector set belongs to another context");
+    if (lut->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the table belongs to another context");
+    if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
+        return fail(ctx, RTFHE_ERR_INVALID, "the CMUX tree runs on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR); select it with rtfhe_set_backend");
+    if (depth < 1 || depth > CMUX_TREE_MAX_DEPTH) return fail(ctx, RTFHE_ERR_INVALID, "depth = " + std::to_string(depth) + " is outside [1, 16]");
+    if (count > ((size_t)0x7fffffff >> (depth - 1))) return fail(ctx, RTFHE_ERR_INVALID, "count * 2^(depth-1) too large");
+    if (extract && !ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "key-switching key not loaded");
+    const long long rows = 1ll << depth, n_lut = lut->n_lut, n_sel = sel->n_sel;
+    if (!has_row0 && rows > n_lut)
+        return fail(ctx, RTFHE_ERR_INVALID, "a depth-" + std::to_string(depth) + " tree reads " + std::to_string(rows) + " rows, the table has " + std::to_string(n_lut));
+    if (!has_sel_idx && (long long)count * depth > n_sel)
+        return fail(ctx, RTFHE_ERR_INVALID, "sel_idx NULL: lookup " + std::to_string(count - 1) + " needs selectors up to " + std::to_string((long long)count * depth - 1) +
+                                            ", the set has " + std::to_string(n_sel));
+    for (size_t g = 0; g < count; g++) {
+        if (host_row0 && (host_row0[g] < 0 || (long long)host_row0[g] + rows > n_lut))
+            return fail(ctx, RTFHE_ERR_INVALID, "lookup " + std::to_string(g) + ": row0 = " + std::to_string(host_row0[g]) + " with " + std::to_string(rows) +
+                                                " rows is outside the table's [0, " + std::to_string(n_lut) + ")");
+        if (host_sel_idx)
+            for (int k = 0; k < depth; k++)
+                if ((uint32_t)host_sel_idx[g * depth + k] >= (uint32_t)sel->n_sel)
+                    return fail(ctx, RTFHE_ERR_INVALID, "lookup " + std::to_string(g) + ": sel_idx[" + std::to_string(k) + "] = " + std::to_string(host_sel_idx[g * depth + k]) +
+                                                        " is outside [0, " + std::to_string(n_sel) + ")");
+        if (host_coef && (uint32_t)host_coef[g] >= (uint32_t)ctx->p.N)
+            return fail(ctx, RTFHE_ERR_INVALID, "lookup " + std::to_string(g) + ": coef = " + std::to_string(host_coef[g]) + " is outside [0, " + std::to_string(ctx->p.N) + ")");
+    }
+    return 0;
+}
+
+// The tree of `count` lookups on device buffers, primary device, stream s.  d_out: [count][2][N], or in the extract form [count][n+1].
+int launch_tree(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* d_sel_idx, int32_t depth, const rtfhe_lut* lut, const int32_t* d_row0,
+                const int32_t* d_coef, void* d_out, size_t count, bool extract, hipStream_t s) {
+    if (count == 0) return 0;
+    const size_t N = (size_t)ctx->p.N, need = depth > 1 ? (count << (depth - 1)) * 2 * N : 0;      // words of each ping-pong buffer
+    const bool cap = capturing(s);
+    auto it = ctx->tree.find(s);
+    rtfhe_ctx::Tlwe1* samples = nullptr;
+    if (cap) {
+        // nothing may be allocated inside a capture: this stream's buffers must already hold the call, and the graph then owns their addresses
+        if (need && (it == ctx->tree.end() || it->second.cap < need))
+            return fail(ctx, RTFHE_ERR_STATE, "a CMUX tree inside a stream capture needs this stream's ping-pong buffers to exist already: run one eager "
+                                              "rtfhe_cmux_tree_batch_dev of at least this count and depth on the stream before capturing");
+        if (extract) {
+            samples = tlwe1_of(ctx, s);
+            if (!samples || samples->cap < count)
+                return fail(ctx, RTFHE_ERR_STATE, "a CMUX tree with extraction inside a stream capture needs this stream's sample buffer to exist already: run one "
+                                                  "eager rtfhe_cmux_tree_extract_batch_dev of at least this count on the stream before capturing");
+            samples->captured = true;
+        }
+        if (need) it->second.captured = true;
+    } else {
+        if (need && (it == ctx->tree.end() || it->second.cap < need)) {
+            rtfhe_ctx::TreeBuf& tb = ctx->tree[s];
+            HIPCHECK(ctx, hipDeviceSynchronize());            // earlier trees of this stream may still read the old buffers
+            for (uint32_t*& d : tb.d) {
+                if (d && tb.captured) ctx->mux_retired.push_back(d);      // a graph holds its address: kept until the context goes
+                else if (d) HIPCHECK(ctx, hipFree(d));
+                d = nullptr;
+            }
+            tb.cap = 0; tb.captured = false;
+            for (uint32_t*& d : tb.d) HIPCHECK(ctx, hipMalloc((void**)&d, need * 4));
+            tb.cap = need;
+            it = ctx->tree.find(s);
+        }
+        if (extract) {
+            if (int rc = ensure_tlwe1(ctx, ctx->tlwe1[s], count)) return rc;
+            samples = &ctx->tlwe1[s];
+        }
+    }
+    CmuxTreeArgs a{};
+    a.tw = ctx->d_tw; a.sel = sel->d_spec; a.sel_idx = d_sel_idx; a.row0 = d_row0; a.coef = extract ? d_coef : nullptr;
+    a.table = lut->d_tv[0]; a.fault = ctx->d_fault;
+    a.count = (int32_t)count; a.depth = depth; a.n_sel = sel->n_sel; a.n_lut = lut->n_lut; a.enc = lut->encrypted ? 1 : 0;
+    for (int level = 0; level < depth; level++) {
+        const bool last = level == depth - 1;
+        a.level = level;
+        a.src = level ? it->second.d[(level - 1) & 1] : nullptr;
+        a.dst = last ? (extract ? nullptr : (uint32_t*)d_out) : it->second.d[level & 1];
+        a.ext = last && extract ? samples->d : nullptr;
+        if (int rc = launch_level(ctx, a, count << (depth - 1 - level), s)) return rc;
+    }
+    if (!extract) return 0;
+    // identity_key_switch of the count samples, as a many-LUT PBS does it (launch_pbs_many, rtfhe_batch.hip)
+    if (!ctx->d_ksmat) return launch_key_switch_ext(ctx, samples->d, (uint32_t*)d_out, count, s);
+    HIPCHECK(ctx, hipMemsetAsync(d_out, 0, count * ((size_t)ctx->p.n + 1) * 4, s));      // the K-slices add into it
+    BootstrapArgs k{};
+    k.out = (uint32_t*)d_out; k.count = (int32_t)count; k.n = ctx->p.n;
+    return launch_key_switch_mm(ctx, k, samples->d, s);
+}
+
+int tree_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int32_t depth, const rtfhe_lut* lut, const void* d_row0, const void* d_coef,
+             void* d_out, size_t count, bool extract, void* stream, const char* name) {
+    if (int rc = tree_ready(ctx, sel, lut, depth, count, d_sel_idx != nullptr, d_row0 != nullptr, nullptr, nullptr, nullptr, d_out, extract)) return rc;
+    if (int rc = use(ctx)) return rc;
+    if (!gpu_accessible(ctx, d_out) || (d_sel_idx && !gpu_accessible(ctx, d_sel_idx)) || (d_row0 && !gpu_accessible(ctx, d_row0)) ||
+        (d_coef && !gpu_accessible(ctx, d_coef)))
+        return fail(ctx, RTFHE_ERR_INVALID, std::string(name) + " needs device pointers (got memory the GPU cannot address)");
+    return launch_tree(ctx, sel, (const int32_t*)d_sel_idx, depth, lut, (const int32_t*)d_row0, (const int32_t*)d_coef, d_out, count, extract, (hipStream_t)stream);
+}
+
+// host buffers: the index arrays ride in the staging buffers (sel_idx in d_a; row0 then coef in d_b), the result comes back through d_c
+int tree_host(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, int32_t depth, const rtfhe_lut* lut, const int32_t* row0, const int32_t* coef,
+              uint32_t* out, size_t count, bool extract) {
+    if (int rc = tree_ready(ctx, sel, lut, depth, count, sel_idx != nullptr, row0 != nullptr, sel_idx, row0, coef, out, extract)) return rc;
+    if (int rc = use(ctx)) return rc;
+    if (count == 0) return 0;
+    const size_t out_bytes = count * (extract ? (size_t)ctx->p.n + 1 : (size_t)2 * ctx->p.N) * 4;
+    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
+    const int32_t *d_sel_idx = nullptr, *d_row0 = nullptr, *d_coef = nullptr;
+    if (sel_idx) {
+        if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, count * depth * 4)) return rc;
+        if (int rc = copy_in(ctx, ctx->d_a, sel_idx, count * depth * 4, 0)) return rc;
+        d_sel_idx = (const int32_t*)ctx->d_a;
+    }
+    if (row0 || coef) {
+        if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, 2 * count * 4)) return rc;
+        if (row0) { HIPCHECK(ctx, hipMemcpyAsync(ctx->d_b, row0, count * 4, hipMemcpyHostToDevice, ctx->stream)); d_row0 = (const int32_t*)ctx->d_b; }
+        if (coef) {
+            HIPCHECK(ctx, hipMemcpyAsync((int32_t*)ctx->d_b + count, coef, count * 4, hipMemcpyHostToDevice, ctx->stream));
+            d_coef = (const int32_t*)ctx->d_b + count;
+        }
+    }
+    if (int rc = launch_tree(ctx, sel, d_sel_idx, depth, lut, d_row0, d_coef, ctx->d_c, count, extract, ctx->stream)) return rc;
+    return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+}
+
+}  // namespace
+
+namespace rtfhe_host {
+
+void trgsw_release(rtfhe_trgsw* t) {
+    (void)hipSetDevice(t->ctx->device);
+    if (t->d_spec) (void)hipFree(t->d_spec);
+    t->d_spec = nullptr;
+}
+
+}  // namespace rtfhe_host
+
+extern "C" {
+
+// TRGSWRepF::from (trgsw.rs:68-76) of every sample, as rtfhe_load_bk_torus converts the bootstrapping key: the forward transform of the words
+// viewed as signed i32, written in the canonical device layout [2l][2][R][64]
+int rtfhe_trgsw_create(rtfhe_ctx* ctx, const uint32_t* trgsw, int32_t n_sel, rtfhe_trgsw** out) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!trgsw || !out || n_sel < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_create: null argument or n_sel < 1");
+    *out = nullptr;
+    if (int rc = use(ctx)) return rc;
+    const size_t polys = (size_t)n_sel * 2 * 2 * ctx->p.l, words = polys * ctx->p.N;
+    if (polys > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_create: n_sel too large");
+    rtfhe_trgsw* t = new rtfhe_trgsw();
+    t->n_sel = n_sel;
+    t->ctx = ctx;
+    int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, words * 4);
+    if (!rc && hipMalloc((void**)&t->d_spec, words / 2 * sizeof(cplx)) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_trgsw_create: hipMalloc");
+    if (!rc && hipMemcpy(ctx->d_a, trgsw, words * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_trgsw_create: hipMemcpy");
+    if (!rc) rc = launch_fft(ctx, true, FftArgs{ctx->d_tw, ctx->d_a, t->d_spec, (int32_t)polys, 1, 2 * ctx->p.l, 0}, ctx->stream);
+    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_trgsw_create: hipStreamSynchronize");
+    if (rc) {
+        (void)hipGetLastError();
+        trgsw_release(t);
+        delete t;
+        return rc;
+    }
+    ctx->trgsws.push_back(t);
+    *out = t;
+    return 0;
+}
+
+void rtfhe_trgsw_destroy(rtfhe_trgsw* t) {
+    if (!t) return;
+    if (rtfhe_ctx* ctx = t->ctx) {     // still attached (a context destroyed first has already freed the spectra and detached us)
+        auto& v = ctx->trgsws;
+        for (size_t i = 0; i < v.size(); i++) if (v[i] == t) { v.erase(v.begin() + i); break; }
+        trgsw_release(t);
+    }
+    delete t;
+}
+
+int rtfhe_cmux_tree_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, int32_t depth, const rtfhe_lut* lut, const int32_t* row0,
+                          uint32_t* out, size_t count) {
+    return tree_host(ctx, sel, sel_idx, depth, lut, row0, nullptr, out, count, false);
+}
+
+int rtfhe_cmux_tree_batch_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int32_t depth, const rtfhe_lut* lut, const void* d_row0,
+                              void* d_out, size_t count, void* stream) {
+    return tree_dev(ctx, sel, d_sel_idx, depth, lut, d_row0, nullptr, d_out, count, false, stream, "rtfhe_cmux_tree_batch_dev");
+}
+
+int rtfhe_cmux_tree_extract_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, int32_t depth, const rtfhe_lut* lut, const int32_t* row0,
+                                  const int32_t* coef, uint32_t* out, size_t count) {
+    return tree_host(ctx, sel, sel_idx, depth, lut, row0, coef, out, count, true);
+}
+
+int rtfhe_cmux_tree_extract_batch_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int32_t depth, const rtfhe_lut* lut, const void* d_row0,
+                                      const void* d_coef, void* d_out, size_t count, void* stream) {
+    return tree_dev(ctx, sel, d_sel_idx, depth, lut, d_row0, d_coef, d_out, count, true, stream, "rtfhe_cmux_tree_extract_batch_dev");
+}
+
+}  // extern "C"

@@ -336,6 +336,8 @@ void rtfhe_ctx_destroy(rtfhe_ctx* ctx) {
     // for rtfhe_lut_destroy (which then only frees them) and the PBS calls (which then fail with RTFHE_ERR_STATE)
     for (rtfhe_lut* l : ctx->luts) { lut_release(l); l->ctx = nullptr; }
     ctx->luts.clear();
+    for (rtfhe_trgsw* t : ctx->trgsws) { trgsw_release(t); t->ctx = nullptr; }      // selector sets: the same rule
+    ctx->trgsws.clear();
     for (rtfhe_ctx* peer : ctx->peers) rtfhe_ctx_destroy(peer);
     ctx->peers.clear();
     (void)hipSetDevice(ctx->device);
@@ -363,6 +365,7 @@ void rtfhe_ctx_destroy(rtfhe_ctx* ctx) {
     if (ctx->d_c) (void)hipFree(ctx->d_c);
     for (void* h : ctx->h_pin) if (h) (void)hipHostFree(h);
     for (auto& kv : ctx->mux) for (void* m : kv.second.m) if (m) (void)hipFree(m);
+    for (auto& kv : ctx->tree) for (uint32_t* d : kv.second.d) if (d) (void)hipFree(d);
     for (void* m : ctx->mux_retired) (void)hipFree(m);
     for (hipEvent_t e : ctx->ks_events) (void)hipEventDestroy(e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);

@@ -8,6 +8,7 @@
 //   rtfhe_batch.hip          batches of gates: the backend switch, split path, host-pointer and device-pointer batches, MUX, timers
 //   rtfhe_circuit.hip        levelised netlists: one wave per call, or all waves recorded into a HIP graph
 //   rtfhe_multi.hip          one context over several GPUs: key replication, sharding of host batches and of device-resident batches
+//   rtfhe_cmux_tree.hip      CMUX-tree table lookup: selector sets (caller-supplied TRGSW samples), one launch per tree level
 // Every kernel is instantiated in exactly one of them.  No CPU fallback anywhere: an entry point runs HIP kernels or fails.
 #pragma once
 
@@ -49,6 +50,7 @@ struct HostTw {
 
 struct rtfhe_circuit;
 struct rtfhe_lut;
+struct rtfhe_trgsw;
 struct rtfhe_ctx {
     rtfhe_params p{};
     int device = 0;
@@ -124,6 +126,11 @@ struct rtfhe_ctx {
     struct MuxBuf { void* m[2] = {nullptr, nullptr}; size_t cap = 0; bool captured = false; };
     std::unordered_map<hipStream_t, MuxBuf> mux;
     std::vector<void*> mux_retired;        // (and sample buffers of the split path that a caller's capture holds: Tlwe1::captured)
+    // the two ping-pong buffers of a CMUX tree's levels (rtfhe_cmux_tree.hip), one pair per stream a tree was ever launched on, under the same
+    // rules as the MUX pairs above; cap in words of EACH buffer; not counted by rtfhe_ctx_memory_bytes
+    struct TreeBuf { uint32_t* d[2] = {nullptr, nullptr}; size_t cap = 0; bool captured = false; };
+    std::unordered_map<hipStream_t, TreeBuf> tree;
+    std::vector<rtfhe_trgsw*> trgsws;      // live selector sets of this context: their spectra go with it, the handles stay
     int num_cus = 256;
     int force_waves = 0;   // RTFHE_FORCE_WAVES=1|2|4|8: one kernel shape for every batch (the parity tests' second opinions)
     int wg_max = 512;      // RTFHE_WG_MAX_GATES: largest batch routed to the workgroup-per-gate kernel
@@ -151,6 +158,13 @@ struct rtfhe_lut {
     std::vector<uint32_t*> d_tv;        // [entry] u32[n_lut][N] on entry d of the context (0: the primary, d: peers[d - 1]); encrypted: [n_lut][2][N]
     int32_t n_lut = 0;
     bool encrypted = false;             // rtfhe_lut_create_encrypted: TRLWE rows (b, a), run by the k_pbs_enc_* kernels on the many-LUT path
+};
+
+// a selector set of a CMUX tree (rtfhe_trgsw_create): caller-supplied TRGSW samples as spectra on the primary device
+struct rtfhe_trgsw {
+    rtfhe_ctx* ctx = nullptr;           // null once the context has been destroyed (the handle then only remains to be freed)
+    rtfhe::cplx* d_spec = nullptr;      // [n_sel][2l][2][R][64], the layout of one bootstrapping-key entry each
+    int32_t n_sel = 0;
 };
 
 namespace rtfhe_host {
@@ -207,6 +221,7 @@ int copy_in(rtfhe_ctx* ctx, void* dst, const void* src, size_t bytes, int slot);
 int copy_out(rtfhe_ctx* ctx, void* dst, const void* src, size_t bytes, int slot);     // device -> host on ctx->stream, synchronous on return
 void circuit_release(rtfhe_circuit* c);                                   // rtfhe_circuit.hip
 void lut_release(rtfhe_lut* lut);                                         // frees a table's device copies (rtfhe_context.hip)
+void trgsw_release(rtfhe_trgsw* t);                                       // frees a selector set's spectra (rtfhe_cmux_tree.hip)
 
 // ---- twiddles (rtfhe_twiddles.hip) ----
 bool unit_twiddles_ok(const HostTw& tw);

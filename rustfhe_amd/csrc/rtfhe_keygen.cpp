@@ -141,6 +141,23 @@ void trlwe_zero(Rng& r, int N, const int32_t* key, float alpha, uint32_t* b, uin
     }
 }
 
+// TRGSW encryption of the bit mu under key1 (trgsw.rs:118-138, 217-229): 2l TRLWE encryptions of zero (alpha = 2^-25, trlwe.rs:77) plus mu
+// times the gadget, mu / Bg^(k+1) on the constant coefficient of row k's b polynomial and of row l + k's a polynomial.  ct: [2][2l][N], comp 0 =
+// the b polynomials (TRGSWRep.cipher), comp 1 = the a polynomials (p_key).  An entry of the bootstrapping key and a caller's selector alike.
+void trgsw_encrypt(Rng& r, const rtfhe_params* p, const int32_t* key1, int32_t mu, uint32_t* ct) {
+    const int N = p->N, l = p->l, rows = 2 * l;
+    const float alpha_bk = 1.0f / 33554432.0f;   // 2^-25, trlwe.rs:77
+    for (int j = 0; j < rows; j++) trlwe_zero(r, N, key1, alpha_bk, ct + (size_t)j * N, ct + ((size_t)rows + j) * N);
+    const float bg_inv = 1.0f / (float)(1 << p->bgbit);
+    for (int k = 0; k < l; k++) {
+        float pw = 1.0f;
+        for (int e = 0; e < 1 + k; e++) pw *= bg_inv;
+        const uint32_t t2 = torus_from_f32((float)mu * pw);
+        ct[(size_t)k * N] += t2;
+        ct[((size_t)rows + k + l) * N] += t2;
+    }
+}
+
 bool valid(const rtfhe_params* p) {
     return p && p->n > 0 && p->N >= 16 && (p->N & (p->N - 1)) == 0 && p->l > 0 && p->bgbit > 0 && p->l * p->bgbit <= 32 &&
            p->ks_t > 0 && p->ks_basebit > 0 && p->ks_t * p->ks_basebit <= 32;
@@ -151,7 +168,6 @@ int keygen_material(const rtfhe_params* p, const Source& src, const int32_t* key
     const int n = p->n, N = p->N, l = p->l, rows = 2 * l;
     for (int i = 0; i < n; i++) if (key0[i] != 0 && key0[i] != 1) return RTFHE_ERR_INVALID;
     for (int i = 0; i < N; i++) if (key1[i] != 0 && key1[i] != 1) return RTFHE_ERR_INVALID;
-    const float alpha_bk = 1.0f / 33554432.0f;   // 2^-25, trlwe.rs:77
     const float alpha_ks = 1.0f / 32768.0f;      // 2^-15, tlwe.rs:176
     const unsigned hw = std::thread::hardware_concurrency();
     const int nthreads = (int)(hw ? (hw > 16 ? 16 : hw) : 1);
@@ -166,18 +182,7 @@ int keygen_material(const rtfhe_params* p, const Source& src, const int32_t* key
         const size_t trgsw = (size_t)2 * rows * N;
         auto work = [&](int t) {
             for (int i = t; i < n; i += nthreads)
-                row_rng(1, i, [&](Rng& r) {
-                    uint32_t* ct = bk + (size_t)i * trgsw;
-                    for (int j = 0; j < rows; j++) trlwe_zero(r, N, key1, alpha_bk, ct + (size_t)j * N, ct + ((size_t)rows + j) * N);
-                    const float bg_inv = 1.0f / (float)(1 << p->bgbit);
-                    for (int k = 0; k < l; k++) {
-                        float pw = 1.0f;
-                        for (int e = 0; e < 1 + k; e++) pw *= bg_inv;
-                        const uint32_t t2 = torus_from_f32((float)key0[i] * pw);
-                        ct[(size_t)k * N] += t2;
-                        ct[((size_t)rows + k + l) * N] += t2;
-                    }
-                });
+                row_rng(1, i, [&](Rng& r) { trgsw_encrypt(r, p, key1, key0[i], bk + (size_t)i * trgsw); });
         };
         std::vector<std::thread> th;
         for (int t = 0; t < nthreads; t++) th.emplace_back(work, t);
@@ -255,6 +260,14 @@ int encrypt_trlwe(const rtfhe_params* p, Rng& r, const int32_t* key1, const uint
     return 0;
 }
 
+// TRGSW encryptions of bits[count] under key1 (the selectors of a CMUX tree, rtfhe_trgsw_create): what keygen_material does per key bit
+int encrypt_trgsw_bits(const rtfhe_params* p, Rng& r, const int32_t* key1, const uint8_t* bits, uint32_t* out, size_t count) {
+    for (int i = 0; i < p->N; i++) if (key1[i] != 0 && key1[i] != 1) return RTFHE_ERR_INVALID;
+    const size_t trgsw = (size_t)2 * 2 * p->l * p->N;
+    for (size_t g = 0; g < count; g++) trgsw_encrypt(r, p, key1, bits[g] ? 1 : 0, out + g * trgsw);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -303,6 +316,14 @@ int rtfhe_trlwe_encrypt_torus(const rtfhe_params* p, const int32_t* key1, const 
     return encrypt_trlwe(p, r, key1, mu, out, count);
 }
 
+int rtfhe_trgsw_encrypt_bits(const rtfhe_params* p, const int32_t* key1, const uint8_t* bits, uint32_t* out, size_t count) {
+    if (!valid(p) || !key1 || !bits || !out) return RTFHE_ERR_INVALID;
+    Source src;
+    if (!Source::from_os(src)) return RTFHE_ERR_STATE;
+    ChaCha r(src.key, 0);          // a fresh OS key per call
+    return encrypt_trgsw_bits(p, r, key1, bits, out, count);
+}
+
 int rtfhe_ksk_expand_ref(const rtfhe_params* p, const int32_t* key0, const int32_t* key1, const uint32_t* ksk, uint32_t* ksk_ref) {
     if (!valid(p) || !key0 || !key1 || !ksk || !ksk_ref) return RTFHE_ERR_INVALID;
     Source src;
@@ -345,6 +366,12 @@ int rtfhe_trlwe_encrypt_torus_deterministic(const rtfhe_params* p, const int32_t
     if (!valid(p) || !key1 || !mu || !out) return RTFHE_ERR_INVALID;
     Xoshiro r(seed);
     return encrypt_trlwe(p, r, key1, mu, out, count);
+}
+
+int rtfhe_trgsw_encrypt_bits_deterministic(const rtfhe_params* p, const int32_t* key1, uint64_t seed, const uint8_t* bits, uint32_t* out, size_t count) {
+    if (!valid(p) || !key1 || !bits || !out) return RTFHE_ERR_INVALID;
+    Xoshiro r(seed);
+    return encrypt_trgsw_bits(p, r, key1, bits, out, count);
 }
 
 // phase = b - a * s (exact negacyclic product with the binary key), per TRLWE of ct[count][2][N]

@@ -291,6 +291,45 @@ class Engine:
         self._ck(self.L.rtfhe_pbs_many_batch_dev(self.h, lut.h, int(n_out), self._dev(d_lut_idx), self._dev(d_tlwe), self._dev(d_out), count,
                                                  C.c_void_p(stream) if stream else None))
 
+    # ---- CMUX-tree table lookup (include/rtfhe.h: rtfhe_trgsw_create, rtfhe_cmux_tree_batch[_dev], rtfhe_cmux_tree_extract_batch[_dev]) ------
+    def selectors(self, trgsw):
+        """Uploads TRGSW samples u32[n_sel][2][2l][N] (or one u32[2][2l][N]) under the lvl1 key, e.g. from rustfhe_amd.encrypt_selectors, and
+        converts them to spectra on the primary device; a Selectors handle, closed by close() or a with block."""
+        return Selectors(self, trgsw)
+
+    def _tree_args(self, sel_idx, depth, row0, coef, count):
+        i32 = lambda a, shape: None if a is None else _np(a, np.int32).reshape(shape)      # noqa: E731
+        return i32(sel_idx, (count, depth)), i32(row0, (count,)), i32(coef, (count,))
+
+    def cmux_tree_batch(self, sel, lut, depth, count, sel_idx=None, row0=None):
+        """`count` lookups of depth `depth`: lookup g selects row row0[g] + (address bits sel_idx[g][0 .. depth), least significant first) of
+        `lut` (plain or encrypted) with 2^depth - 1 CMUXes; u32[count][2][N] TRLWE rows (b then a).  sel_idx None: lookup g uses selectors
+        g * depth + k; row0 None: 0.  Indices are checked here: a bad one raises RtfheError before anything runs."""
+        idx, r0, _ = self._tree_args(sel_idx, depth, row0, None, count)
+        out = np.empty((count, 2, self.p.N), np.uint32)
+        self._ck(self.L.rtfhe_cmux_tree_batch(self.h, sel.h, _ptr(idx), int(depth), lut.h, _ptr(r0), _ptr(out), count))
+        return out
+
+    def cmux_tree_batch_dev(self, sel, lut, depth, d_out, count, d_sel_idx=None, d_row0=None, stream=None):
+        """... on device buffers (d_sel_idx: int32[count][depth], d_row0: int32[count], d_out: [count][2][N] words), asynchronous on `stream`;
+        bad indices are reported by the next sync().  Inside a stream capture an eager call of at least this count and depth must have run
+        on the stream first."""
+        self._ck(self.L.rtfhe_cmux_tree_batch_dev(self.h, sel.h, self._dev(d_sel_idx), int(depth), lut.h, self._dev(d_row0), self._dev(d_out), count,
+                                                  C.c_void_p(stream) if stream else None))
+
+    def cmux_tree_extract_batch(self, sel, lut, depth, count, sel_idx=None, row0=None, coef=None):
+        """The same tree followed by sample extract at coefficient coef[g] (None: 0) and the key switch: u32[count][n+1] lvl0 ciphertexts of
+        that coefficient of the selected row.  Needs the key-switching key, not the bootstrapping key."""
+        idx, r0, cf = self._tree_args(sel_idx, depth, row0, coef, count)
+        out = np.empty((count, self.p.n + 1), np.uint32)
+        self._ck(self.L.rtfhe_cmux_tree_extract_batch(self.h, sel.h, _ptr(idx), int(depth), lut.h, _ptr(r0), _ptr(cf), _ptr(out), count))
+        return out
+
+    def cmux_tree_extract_batch_dev(self, sel, lut, depth, d_out, count, d_sel_idx=None, d_row0=None, d_coef=None, stream=None):
+        """... on device buffers (d_out: [count][n+1] words), under cmux_tree_batch_dev's rules."""
+        self._ck(self.L.rtfhe_cmux_tree_extract_batch_dev(self.h, sel.h, self._dev(d_sel_idx), int(depth), lut.h, self._dev(d_row0), self._dev(d_coef),
+                                                          self._dev(d_out), count, C.c_void_p(stream) if stream else None))
+
     # ---- stage level ------------------------------------------------------------------------
     def blind_rotate_batch(self, tlwe, steps=None):
         tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)
@@ -366,6 +405,37 @@ class Lut:
     def close(self):
         if getattr(self, "h", None):
             self.engine.L.rtfhe_lut_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Selectors:
+    """The TRGSW selectors of CMUX trees on an Engine's primary device (rtfhe_trgsw), kept as spectra.  Closing it frees the device copy; one
+    whose Engine was closed first only frees its handle."""
+
+    def __init__(self, engine, trgsw):
+        p = engine.p
+        trgsw = _np(trgsw, np.uint32).reshape(-1, 2 * 2 * p.l * p.N)
+        self.engine = engine
+        self.n_sel = trgsw.shape[0]
+        h = C.c_void_p()
+        engine._ck(engine.L.rtfhe_trgsw_create(engine.h, _ptr(trgsw), self.n_sel, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.engine.L.rtfhe_trgsw_destroy(self.h)
             self.h = None
 
     def __enter__(self):
@@ -533,6 +603,23 @@ def encrypt_lut(params, key1, tv, seed=None):
         rc = L.rtfhe_trlwe_encrypt_torus_deterministic(C.byref(params), _ptr(key1), seed, _ptr(tv), _ptr(out), tv.shape[0])
     if rc != 0:
         raise RtfheError(rc, "rtfhe_trlwe_encrypt_torus failed")
+    return out
+
+
+def encrypt_selectors(params, key1, bits, seed=None):
+    """TRGSW encryptions under the lvl1 key key1 of the bits (u8[count]): u32[count][2][2l][N], each in the layout of one bootstrapping-key
+    entry -- the encrypted address bits of a CMUX tree (Engine.selectors).  Noise alpha = 2^-25 as the bootstrapping key's.  seed None
+    (production): OS CSPRNG; an integer seed = TEST-ONLY deterministic encryption."""
+    L = _ffi.load()
+    bits = _np(bits, np.uint8).reshape(-1)
+    key1 = _np(key1, np.int32)
+    out = np.empty((bits.size, 2, 2 * params.l, params.N), np.uint32)
+    if seed is None:
+        rc = L.rtfhe_trgsw_encrypt_bits(C.byref(params), _ptr(key1), _ptr(bits), _ptr(out), bits.size)
+    else:
+        rc = L.rtfhe_trgsw_encrypt_bits_deterministic(C.byref(params), _ptr(key1), seed, _ptr(bits), _ptr(out), bits.size)
+    if rc != 0:
+        raise RtfheError(rc, "rtfhe_trgsw_encrypt_bits failed")
     return out
 
 
