@@ -153,6 +153,23 @@ impl<const TLWE_N: usize, const TRLWE_N: usize> TFHE<TLWE_N, TRLWE_N> {
         });
         out.chunks(w).map(TLWERep::from_flat).collect()
     }
+    /// Horizontal packing: `rows` (flat `u32[count][2][N]`, e.g. from `cmux_tree`) rotated by the `depth` address bits in the selectors
+    /// `g * depth + k` of `selectors` -- `depth` steps of `TFHE::blind_rotate` (tfhe.rs:103-110) with X^{-2^k} --, then
+    /// `identity_key_switch(sample_extract_index(., 0))`: coefficient `addr` of every row as a TLWE.  Needs no bootstrapping key.
+    pub fn trgsw_rotate_extract(&self, selectors: &[u32], depth: usize, rows: &[u32], count: usize) -> Vec<TLWERep<TLWE_N>> {
+        let (trgsw, w) = (2 * 2 * self.params.l as usize * TRLWE_N, TLWE_N + 1);
+        assert_eq!(selectors.len(), count * depth * trgsw);
+        assert_eq!(rows.len(), count * 2 * TRLWE_N);
+        let mut out = vec![0u32; count * w];
+        let mut sel: *mut sys::rtfhe_trgsw = std::ptr::null_mut();
+        unsafe {
+            Self::check(self.ctx, sys::rtfhe_trgsw_create(self.ctx, selectors.as_ptr(), (count * depth) as i32, &mut sel));
+            let rc = sys::rtfhe_trgsw_rotate_extract_batch(self.ctx, sel, std::ptr::null(), depth as i32, std::ptr::null(), rows.as_ptr(), out.as_mut_ptr(), count);
+            sys::rtfhe_trgsw_destroy(sel);
+            Self::check(self.ctx, rc);
+        }
+        out.chunks(w).map(TLWERep::from_flat).collect()
+    }
     fn tree<F: FnOnce(*mut sys::rtfhe_ctx, *const sys::rtfhe_trgsw, *const sys::rtfhe_lut) -> c_int>(&self, selectors: &[u32], depth: usize, rows: &[u32],
                                                                                                     count: usize, call: F) {
         let trgsw = 2 * 2 * self.params.l as usize * TRLWE_N;

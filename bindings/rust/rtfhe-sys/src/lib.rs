@@ -130,6 +130,16 @@ extern "C" {
                                          row0: *const i32, coef: *const i32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_cmux_tree_extract_batch_dev(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, d_sel_idx: *const c_void, depth: i32, lut: *const rtfhe_lut,
                                              d_row0: *const c_void, d_coef: *const c_void, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
+    // TRGSW blind rotation: depth steps acc <- cmux(S_k, X^rot[k] * acc, acc) on each TRLWE [2][N]; sel_idx [count][depth] (null: g * depth + k),
+    // rot a HOST array [depth] in every form (null: 2N - 2^k, depth <= log2 N + 1); out [count][2][N] (d_out may be d_trlwe) / extract form [count][n+1]
+    pub fn rtfhe_trgsw_rotate_batch(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, sel_idx: *const i32, depth: i32, rot: *const i32, trlwe: *const u32,
+                                    out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trgsw_rotate_batch_dev(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, d_sel_idx: *const c_void, depth: i32, rot: *const i32,
+                                        d_trlwe: *const c_void, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
+    pub fn rtfhe_trgsw_rotate_extract_batch(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, sel_idx: *const i32, depth: i32, rot: *const i32,
+                                            trlwe: *const u32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trgsw_rotate_extract_batch_dev(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, d_sel_idx: *const c_void, depth: i32, rot: *const i32,
+                                                d_trlwe: *const c_void, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
     pub fn rtfhe_sync(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_begin(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_end(ctx: *mut rtfhe_ctx, stream: *mut c_void, ms: *mut f64, launches: *mut i64) -> c_int;

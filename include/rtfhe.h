@@ -34,6 +34,8 @@
  *                                    <- TRGSWRepF::from and TRGSWRepF::cmux (hom_nand/src/trgsw.rs:68-76, 319-321) on caller-supplied TRGSW samples:
  *                                       one row out of 2^d rows of a table selected by d encrypted address bits (the reference has the CMUX,
  *                                       not the tree)
+ *   rtfhe_trgsw_rotate_batch[_dev] / rtfhe_trgsw_rotate_extract_batch[_dev]
+ *                                    <- one step of TFHE::blind_rotate (hom_nand/src/tfhe.rs:103-110) per caller-supplied TRGSW sample and exponent
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch           <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -394,6 +396,49 @@ int rtfhe_cmux_tree_extract_batch(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const 
 int rtfhe_cmux_tree_extract_batch_dev(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const void *d_sel_idx /* int32[count][depth] or NULL */, int32_t depth,
                                       const rtfhe_lut *lut, const void *d_row0 /* int32[count] or NULL */, const void *d_coef /* int32[count] or NULL */,
                                       void *d_out /* [count][n+1] */, size_t count, void *stream);
+/* ---- TRGSW blind rotation: a TRLWE rotated by encrypted address bits (horizontal packing, the other half of TFHE's leveled table lookup) ----
+ * Lookup g of a batch takes a TRLWE trlwe[g], u32[2][N] (b then a) -- an rtfhe_cmux_tree_batch result, a row of an encrypted table, or a
+ * trivial (tv, 0) --, a depth d = `depth` (1 .. 16, the same for the whole batch), selector indices sel_idx[g][0 .. d) into an rtfhe_trgsw
+ * set (NULL: lookup g uses selectors g * depth + k, as in the tree) and exponents rot[0 .. d), ONE host array shared by the whole batch, each in
+ * [0, 2N).  It computes
+ *
+ *     acc_0     = trlwe[g]
+ *     acc_{k+1} = cmux(S_k, X^{rot[k]} * acc_k, acc_k) = cross(S_k, X^{rot[k]} * acc_k - acc_k) + acc_k,   S_k = selector sel_idx[g][k]
+ *     result    = acc_d
+ *
+ * X^r * p is the negacyclic rotation of the bootstrap (utils/src/math.rs:85-132) applied to both polynomials; every step is one step of
+ * TFHE::blind_rotate (hom_nand/src/tfhe.rs:103-110) with the key entry replaced by S_k and abar_i by rot[k]; cross is what
+ * rtfhe_external_product_batch computes.  rot NULL: rot[k] = 2N - 2^k, i.e. X^{-2^k}, which requires depth <= log2 N + 1: with address bit k
+ * in S_k the result is X^{-addr} * trlwe[g], whose coefficient 0 is coefficient addr of the row.  A CMUX tree of depth d and this rotation
+ * look up a table of 2^d * N entries under a fully encrypted address in (2^d - 1) + log2 N CMUXes, without a bootstrapping key.
+ *   rtfhe_trgsw_rotate_batch[_dev]          out[g] = the result, u32[2][N].  rot is a host array in both forms: it is copied into the
+ *                                           kernel's arguments when the call is enqueued (a stream capture bakes it in).  d_out may be exactly
+ *                                           d_trlwe (every lookup reads its whole row before it stores); no other overlap is allowed.  The
+ *                                           _dev form allocates nothing: it may sit in a caller's stream capture without a prior eager call.
+ *   rtfhe_trgsw_rotate_extract_batch[_dev]  out[g] = identity_key_switch(sample_extract_index(result, 0)), u32[n+1], through the route of
+ *                                           rtfhe_cmux_tree_extract_batch (the stream's lvl1 sample buffer, then the key switch as one i8
+ *                                           contraction, or one wave per sample under RTFHE_KS_MM_MIN=0).  Needs the key-switching key
+ *                                           (RTFHE_ERR_STATE otherwise), not the bootstrapping key.  Inside a caller's stream capture an eager
+ *                                           call of this entry point with at least this count must have run on the stream first, else
+ *                                           RTFHE_ERR_STATE.
+ * Checks before anything is launched: the handles, depth, count (count * depth < 2^31), every rot[k] in [0, 2N), the depth limit of rot NULL,
+ * null in / out pointers, host sel_idx in [0, n_sel), and with sel_idx NULL count * depth <= n_sel: RTFHE_ERR_INVALID with a message naming the
+ * lookup or the step.  The _dev forms check d_sel_idx in the kernel, all d indices of a lookup before its row is touched: a lookup with a bad
+ * index is skipped whole, its output row keeps the bytes it had, and the next rtfhe_sync returns RTFHE_ERR_INVALID once, as for
+ * rtfhe_cmux_tree_batch_dev.  The FP64 mirror backend only: on either exact backend every call fails with RTFHE_ERR_INVALID (the context
+ * stays usable).  A multi-device context runs the rotation on its primary device. */
+int rtfhe_trgsw_rotate_batch(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const int32_t *sel_idx /* [count][depth] or NULL */, int32_t depth,
+                             const int32_t *rot /* [depth] or NULL */, const uint32_t *trlwe /* [count][2][N] */, uint32_t *out /* [count][2][N] */,
+                             size_t count);
+int rtfhe_trgsw_rotate_batch_dev(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const void *d_sel_idx /* int32[count][depth] or NULL */, int32_t depth,
+                                 const int32_t *rot /* HOST [depth] or NULL */, const void *d_trlwe /* [count][2][N] */,
+                                 void *d_out /* [count][2][N], may be d_trlwe */, size_t count, void *stream);
+int rtfhe_trgsw_rotate_extract_batch(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const int32_t *sel_idx /* [count][depth] or NULL */, int32_t depth,
+                                     const int32_t *rot /* [depth] or NULL */, const uint32_t *trlwe /* [count][2][N] */,
+                                     uint32_t *out /* [count][n+1] */, size_t count);
+int rtfhe_trgsw_rotate_extract_batch_dev(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const void *d_sel_idx /* int32[count][depth] or NULL */,
+                                         int32_t depth, const int32_t *rot /* HOST [depth] or NULL */, const void *d_trlwe /* [count][2][N] */,
+                                         void *d_out /* [count][n+1] */, size_t count, void *stream);
 /* waits for `stream`; also reports (once) a netlist gate skipped since the previous call */
 int rtfhe_sync(rtfhe_ctx *ctx, void *stream);
 /* device-side timing of the launches enqueued by the *_dev calls between begin and end (HIP events on

@@ -1,11 +1,14 @@
 // rtfhe_cmux_tree.hip -- CMUX-tree table lookup with caller-supplied TRGSW selectors (include/rtfhe.h: rtfhe_trgsw_create,
 // rtfhe_cmux_tree_batch[_dev], rtfhe_cmux_tree_extract_batch[_dev]): selector sets, the argument checks, the stream's ping-pong buffers
 // and the rules around stream captures, one launch of k_cmux_tree per level, and for the extract form the batch key switch many-LUT uses.
+// Beside it the TRGSW blind rotation (rtfhe_trgsw_rotate_batch[_dev], rtfhe_trgsw_rotate_extract_batch[_dev]): the same selector sets, one
+// launch of k_trgsw_rotate for all steps of all lookups, the same key switch behind the extract form.
 #include "rtfhe_host.hpp"
 
 #include <cstdlib>
 
 #include "rtfhe_kernels_cmux_tree.hpp"
+#include "rtfhe_kernels_trgsw_rotate.hpp"
 
 using namespace rtfhe;
 using namespace rtfhe_host;
@@ -168,6 +171,142 @@ int tree_host(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, in
     return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
 }
 
+// ---- TRGSW blind rotation ----
+template <int LOGN, int W>
+int launch_rotate_t(rtfhe_ctx* ctx, const TrgswRotateArgs& a, hipStream_t s) {
+    auto k = k_trgsw_rotate<LOGN, 3, 6, W>;
+    constexpr size_t lds = cmux_tree_lds_bytes<LOGN, W>();
+    if (int rc = allow_lds(ctx, k, lds)) return rc;
+    hipLaunchKernelGGL(k, dim3((unsigned)(((size_t)a.count + W - 1) / W)), dim3(64 * W), lds, s, a);
+    HIPCHECK(ctx, hipGetLastError());
+    ctx->launches++;
+    return 0;
+}
+
+template <int LOGN, int W>
+int launch_rotate_restore_t(rtfhe_ctx* ctx, const TrgswRotateArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL((k_trgsw_rotate_restore<LOGN, W>), dim3((unsigned)(((size_t)a.count + W - 1) / W)), dim3(64 * W), 0, s, a);
+    HIPCHECK(ctx, hipGetLastError());
+    ctx->launches++;
+    return 0;
+}
+
+// grants k_trgsw_rotate its dynamic LDS when a selector set is created, so that the first rotation of a context may already sit in a stream capture
+int prime_rotate(rtfhe_ctx* ctx) {
+    return ctx->logn == 11 ? allow_lds(ctx, k_trgsw_rotate<11, 3, 6, 4>, cmux_tree_lds_bytes<11, 4>()) : allow_lds(ctx, k_trgsw_rotate<10, 3, 6, 4>, cmux_tree_lds_bytes<10, 4>());
+}
+
+// what every rotation entry checks before anything is allocated or launched; host_sel_idx is null in the _dev forms, whose array the kernel checks
+int rotate_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, int32_t depth, const int32_t* rot, size_t count, bool has_sel_idx, const int32_t* host_sel_idx,
+                 const void* in, const void* out, bool extract) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!sel) return fail(ctx, RTFHE_ERR_INVALID, "null selector set (rtfhe_trgsw)");
+    if (!in || !out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (!sel->ctx) return fail(ctx, RTFHE_ERR_STATE, "the context of the selector set has been destroyed");
+    if (sel->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the selector set belongs to another context");
+    if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
+        return fail(ctx, RTFHE_ERR_INVALID, "the TRGSW rotation runs on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR); select it with rtfhe_set_backend");
+    if (depth < 1 || depth > TRGSW_ROTATE_MAX_DEPTH) return fail(ctx, RTFHE_ERR_INVALID, "depth = " + std::to_string(depth) + " is outside [1, 16]");
+    if (count > (size_t)0x7fffffff / (size_t)depth) return fail(ctx, RTFHE_ERR_INVALID, "count * depth too large");
+    const int N = ctx->p.N;
+    if (rot) {
+        for (int k = 0; k < depth; k++)
+            if (rot[k] < 0 || rot[k] >= 2 * N)
+                return fail(ctx, RTFHE_ERR_INVALID, "step " + std::to_string(k) + ": rot = " + std::to_string(rot[k]) + " is outside [0, " + std::to_string(2 * N) + ")");
+    } else if (depth > ctx->logn + 1) {
+        return fail(ctx, RTFHE_ERR_INVALID, "rot NULL: step " + std::to_string(ctx->logn + 1) + " would rotate by X^-2^" + std::to_string(ctx->logn + 1) +
+                                            " = 1; depth = " + std::to_string(depth) + " is above log2 N + 1 = " + std::to_string(ctx->logn + 1));
+    }
+    if (extract && !ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "key-switching key not loaded");
+    const long long n_sel = sel->n_sel;
+    if (!has_sel_idx && (long long)count * depth > n_sel)
+        return fail(ctx, RTFHE_ERR_INVALID, "sel_idx NULL: lookup " + std::to_string(count - 1) + " needs selectors up to " + std::to_string((long long)count * depth - 1) +
+                                            ", the set has " + std::to_string(n_sel));
+    if (host_sel_idx)
+        for (size_t g = 0; g < count; g++)
+            for (int k = 0; k < depth; k++)
+                if ((uint32_t)host_sel_idx[g * depth + k] >= (uint32_t)sel->n_sel)
+                    return fail(ctx, RTFHE_ERR_INVALID, "lookup " + std::to_string(g) + ": sel_idx[" + std::to_string(k) + "] = " + std::to_string(host_sel_idx[g * depth + k]) +
+                                                        " is outside [0, " + std::to_string(n_sel) + ")");
+    return 0;
+}
+
+// The rotation of `count` TRLWEs on device buffers, primary device, stream s.  d_out: [count][2][N] (may be d_in), or in the extract form [count][n+1].
+// The plain form allocates nothing; the extract form needs the stream's lvl1 sample buffer, under the tree's rule inside a capture.
+int launch_rotate(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* d_sel_idx, int32_t depth, const int32_t* rot, const void* d_in, void* d_out, size_t count,
+                  bool extract, hipStream_t s) {
+    if (count == 0) return 0;
+    rtfhe_ctx::Tlwe1* samples = nullptr;
+    if (extract) {
+        if (capturing(s)) {
+            samples = tlwe1_of(ctx, s);
+            if (!samples || samples->cap < count)
+                return fail(ctx, RTFHE_ERR_STATE, "a TRGSW rotation with extraction inside a stream capture needs this stream's sample buffer to exist already: run one "
+                                                  "eager rtfhe_trgsw_rotate_extract_batch_dev of at least this count on the stream before capturing");
+            samples->captured = true;
+        } else {
+            if (int rc = ensure_tlwe1(ctx, ctx->tlwe1[s], count)) return rc;
+            samples = &ctx->tlwe1[s];
+        }
+    }
+    TrgswRotateArgs a{};
+    a.tw = ctx->d_tw; a.sel = sel->d_spec; a.sel_idx = d_sel_idx; a.in = (const uint32_t*)d_in; a.fault = ctx->d_fault;
+    a.out = extract ? nullptr : (uint32_t*)d_out;
+    a.ext = extract ? samples->d : nullptr;
+    a.ks_out = extract ? (uint32_t*)d_out : nullptr;
+    a.count = (int32_t)count; a.depth = depth; a.n_sel = sel->n_sel; a.n = ctx->p.n;
+    for (int k = 0; k < depth; k++) a.rot[k] = rot ? rot[k] : 2 * ctx->p.N - (1 << k);      // NULL: X^{-2^k}
+    if (int rc = ctx->logn == 11 ? launch_rotate_t<11, 4>(ctx, a, s) : launch_rotate_t<10, 4>(ctx, a, s)) return rc;
+    if (!extract) return 0;
+    // identity_key_switch of the count samples, as the tree's extract form does it; then the rows of skipped lookups as they were
+    if (!ctx->d_ksmat) {
+        if (int rc = launch_key_switch_ext(ctx, samples->d, (uint32_t*)d_out, count, s)) return rc;
+    } else {
+        HIPCHECK(ctx, hipMemsetAsync(d_out, 0, count * ((size_t)ctx->p.n + 1) * 4, s));      // the K-slices add into it
+        BootstrapArgs k{};
+        k.out = (uint32_t*)d_out; k.count = (int32_t)count; k.n = ctx->p.n;
+        if (int rc = launch_key_switch_mm(ctx, k, samples->d, s)) return rc;
+    }
+    return ctx->logn == 11 ? launch_rotate_restore_t<11, 4>(ctx, a, s) : launch_rotate_restore_t<10, 4>(ctx, a, s);
+}
+
+int rotate_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int32_t depth, const int32_t* rot, const void* d_trlwe, void* d_out, size_t count,
+               bool extract, void* stream, const char* name) {
+    if (int rc = rotate_ready(ctx, sel, depth, rot, count, d_sel_idx != nullptr, nullptr, d_trlwe, d_out, extract)) return rc;
+    if (int rc = use(ctx)) return rc;
+    if (!gpu_accessible(ctx, d_out) || !gpu_accessible(ctx, d_trlwe) || (d_sel_idx && !gpu_accessible(ctx, d_sel_idx)))
+        return fail(ctx, RTFHE_ERR_INVALID, std::string(name) + " needs device pointers (got memory the GPU cannot address)");
+    if (d_out != d_trlwe) {
+        const char *i0 = (const char*)d_trlwe, *o0 = (const char*)d_out;
+        const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = extract ? count * ((size_t)ctx->p.n + 1) * 4 : in_bytes;
+        if (i0 < o0 + out_bytes && o0 < i0 + in_bytes)
+            return fail(ctx, RTFHE_ERR_INVALID, std::string(name) + ": d_out overlaps d_trlwe (it may only be exactly d_trlwe, in the form without extraction)");
+    } else if (extract) {
+        return fail(ctx, RTFHE_ERR_INVALID, std::string(name) + ": d_out overlaps d_trlwe (it may only be exactly d_trlwe, in the form without extraction)");
+    }
+    return launch_rotate(ctx, sel, (const int32_t*)d_sel_idx, depth, rot, d_trlwe, d_out, count, extract, (hipStream_t)stream);
+}
+
+// host buffers: sel_idx rides in d_a, the rows in d_b, the result comes back through d_c
+int rotate_host(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, int32_t depth, const int32_t* rot, const uint32_t* trlwe, uint32_t* out, size_t count,
+                bool extract) {
+    if (int rc = rotate_ready(ctx, sel, depth, rot, count, sel_idx != nullptr, sel_idx, trlwe, out, extract)) return rc;
+    if (int rc = use(ctx)) return rc;
+    if (count == 0) return 0;
+    const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = extract ? count * ((size_t)ctx->p.n + 1) * 4 : in_bytes;
+    if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, in_bytes)) return rc;
+    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
+    const int32_t* d_sel_idx = nullptr;
+    if (sel_idx) {
+        if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, count * depth * 4)) return rc;
+        if (int rc = copy_in(ctx, ctx->d_a, sel_idx, count * depth * 4, 0)) return rc;
+        d_sel_idx = (const int32_t*)ctx->d_a;
+    }
+    if (int rc = copy_in(ctx, ctx->d_b, trlwe, in_bytes, 1)) return rc;
+    if (int rc = launch_rotate(ctx, sel, d_sel_idx, depth, rot, ctx->d_b, ctx->d_c, count, extract, ctx->stream)) return rc;
+    return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+}
+
 }  // namespace
 
 namespace rtfhe_host {
@@ -189,6 +328,7 @@ int rtfhe_trgsw_create(rtfhe_ctx* ctx, const uint32_t* trgsw, int32_t n_sel, rtf
     if (!trgsw || !out || n_sel < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_create: null argument or n_sel < 1");
     *out = nullptr;
     if (int rc = use(ctx)) return rc;
+    if (int rc = prime_rotate(ctx)) return rc;
     const size_t polys = (size_t)n_sel * 2 * 2 * ctx->p.l, words = polys * ctx->p.N;
     if (polys > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_create: n_sel too large");
     rtfhe_trgsw* t = new rtfhe_trgsw();
@@ -238,6 +378,26 @@ int rtfhe_cmux_tree_extract_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const 
 int rtfhe_cmux_tree_extract_batch_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int32_t depth, const rtfhe_lut* lut, const void* d_row0,
                                       const void* d_coef, void* d_out, size_t count, void* stream) {
     return tree_dev(ctx, sel, d_sel_idx, depth, lut, d_row0, d_coef, d_out, count, true, stream, "rtfhe_cmux_tree_extract_batch_dev");
+}
+
+int rtfhe_trgsw_rotate_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, int32_t depth, const int32_t* rot, const uint32_t* trlwe,
+                             uint32_t* out, size_t count) {
+    return rotate_host(ctx, sel, sel_idx, depth, rot, trlwe, out, count, false);
+}
+
+int rtfhe_trgsw_rotate_batch_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int32_t depth, const int32_t* rot, const void* d_trlwe,
+                                 void* d_out, size_t count, void* stream) {
+    return rotate_dev(ctx, sel, d_sel_idx, depth, rot, d_trlwe, d_out, count, false, stream, "rtfhe_trgsw_rotate_batch_dev");
+}
+
+int rtfhe_trgsw_rotate_extract_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, int32_t depth, const int32_t* rot, const uint32_t* trlwe,
+                                     uint32_t* out, size_t count) {
+    return rotate_host(ctx, sel, sel_idx, depth, rot, trlwe, out, count, true);
+}
+
+int rtfhe_trgsw_rotate_extract_batch_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int32_t depth, const int32_t* rot, const void* d_trlwe,
+                                         void* d_out, size_t count, void* stream) {
+    return rotate_dev(ctx, sel, d_sel_idx, depth, rot, d_trlwe, d_out, count, true, stream, "rtfhe_trgsw_rotate_extract_batch_dev");
 }
 
 }  // extern "C"

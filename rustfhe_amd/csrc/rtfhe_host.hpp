@@ -8,7 +8,7 @@
 //   rtfhe_batch.hip          batches of gates: the backend switch, split path, host-pointer and device-pointer batches, MUX, timers
 //   rtfhe_circuit.hip        levelised netlists: one wave per call, or all waves recorded into a HIP graph
 //   rtfhe_multi.hip          one context over several GPUs: key replication, sharding of host batches and of device-resident batches
-//   rtfhe_cmux_tree.hip      CMUX-tree table lookup: selector sets (caller-supplied TRGSW samples), one launch per tree level
+//   rtfhe_cmux_tree.hip      CMUX-tree table lookup: selector sets (caller-supplied TRGSW samples), one launch per tree level; TRGSW blind rotation
 // Every kernel is instantiated in exactly one of them.  No CPU fallback anywhere: an entry point runs HIP kernels or fails.
 #pragma once
 

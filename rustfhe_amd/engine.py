@@ -330,6 +330,52 @@ class Engine:
         self._ck(self.L.rtfhe_cmux_tree_extract_batch_dev(self.h, sel.h, self._dev(d_sel_idx), int(depth), lut.h, self._dev(d_row0), self._dev(d_coef),
                                                           self._dev(d_out), count, C.c_void_p(stream) if stream else None))
 
+    # ---- TRGSW blind rotation (include/rtfhe.h: rtfhe_trgsw_rotate_batch[_dev], rtfhe_trgsw_rotate_extract_batch[_dev]) ------------------------
+    def _rot_arg(self, rot, depth):
+        if rot is None:
+            return None
+        rot = _np(rot, np.int32).reshape(-1)
+        assert rot.size == int(depth), "one exponent per step"
+        return rot
+
+    def trgsw_rotate_batch(self, sel, trlwe, depth, sel_idx=None, rot=None):
+        """One rotation per TRLWE of u32[count][2][N]: depth steps acc <- cmux(S_k, X^rot[k] * acc, acc) with S_k = selector sel_idx[g][k] (None:
+        g * depth + k) and the exponents rot[0 .. depth) in [0, 2N) shared by the batch (None: 2N - 2^k, so that address bits in S_k give
+        X^-addr * trlwe[g]); u32[count][2][N].  Indices and exponents are checked here: a bad one raises RtfheError before anything runs."""
+        trlwe = _np(trlwe, np.uint32).reshape(-1, 2, self.p.N)
+        count = trlwe.shape[0]
+        idx = None if sel_idx is None else _np(sel_idx, np.int32).reshape(count, depth)
+        r = self._rot_arg(rot, depth)
+        out = np.empty_like(trlwe)
+        self._ck(self.L.rtfhe_trgsw_rotate_batch(self.h, sel.h, _ptr(idx), int(depth), _ptr(r), _ptr(trlwe), _ptr(out), count))
+        return out
+
+    def trgsw_rotate_batch_dev(self, sel, d_trlwe, depth, d_out, count, d_sel_idx=None, rot=None, stream=None):
+        """... on device buffers (d_trlwe, d_out: [count][2][N] words, d_out may be d_trlwe; d_sel_idx: int32[count][depth]; rot stays a host
+        array, copied at enqueue time), asynchronous on `stream`; a lookup with a bad index is skipped, its output row untouched, and the next
+        sync() raises.  Allocates nothing: it may be captured without a prior eager call."""
+        r = self._rot_arg(rot, depth)
+        self._ck(self.L.rtfhe_trgsw_rotate_batch_dev(self.h, sel.h, self._dev(d_sel_idx), int(depth), _ptr(r), self._dev(d_trlwe), self._dev(d_out), count,
+                                                     C.c_void_p(stream) if stream else None))
+
+    def trgsw_rotate_extract_batch(self, sel, trlwe, depth, sel_idx=None, rot=None):
+        """The same rotation followed by sample extract at coefficient 0 and the key switch: u32[count][n+1] lvl0 ciphertexts.  With rot None
+        and address bits in the selectors that is coefficient addr of each row.  Needs the key-switching key, not the bootstrapping key."""
+        trlwe = _np(trlwe, np.uint32).reshape(-1, 2, self.p.N)
+        count = trlwe.shape[0]
+        idx = None if sel_idx is None else _np(sel_idx, np.int32).reshape(count, depth)
+        r = self._rot_arg(rot, depth)
+        out = np.empty((count, self.p.n + 1), np.uint32)
+        self._ck(self.L.rtfhe_trgsw_rotate_extract_batch(self.h, sel.h, _ptr(idx), int(depth), _ptr(r), _ptr(trlwe), _ptr(out), count))
+        return out
+
+    def trgsw_rotate_extract_batch_dev(self, sel, d_trlwe, depth, d_out, count, d_sel_idx=None, rot=None, stream=None):
+        """... on device buffers (d_out: [count][n+1] words).  Inside a stream capture an eager call of at least this count must have run on the
+        stream first."""
+        r = self._rot_arg(rot, depth)
+        self._ck(self.L.rtfhe_trgsw_rotate_extract_batch_dev(self.h, sel.h, self._dev(d_sel_idx), int(depth), _ptr(r), self._dev(d_trlwe), self._dev(d_out),
+                                                             count, C.c_void_p(stream) if stream else None))
+
     # ---- stage level ------------------------------------------------------------------------
     def blind_rotate_batch(self, tlwe, steps=None):
         tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)
