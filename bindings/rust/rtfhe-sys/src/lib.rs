@@ -140,6 +140,13 @@ extern "C" {
                                             trlwe: *const u32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_trgsw_rotate_extract_batch_dev(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, d_sel_idx: *const c_void, depth: i32, rot: *const i32,
                                                 d_trlwe: *const c_void, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
+    // CMUX netlists: node i = cmux(S_var[i], X^rot[i] * hi[i], lo[i]) over TRLWEs; a reference r >= 0 is node r < i, r < 0 table row row0[g] + (-1 - r);
+    // out_coef null: d_out [count][n_out][2][N], else [count][n_out][n+1]; recorded into one graph (replay / free with rtfhe_circuit_launch / _destroy)
+    pub fn rtfhe_cmux_circuit_create(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, lut: *const rtfhe_lut, var: *const i32, hi: *const i32, lo: *const i32,
+                                     rot: *const i32, n_nodes: i32, n_vars: i32, out_ref: *const i32, out_coef: *const i32, n_out: i32,
+                                     d_sel_idx: *const c_void, d_row0: *const c_void, d_out: *mut c_void, count: usize, out: *mut *mut rtfhe_circuit) -> c_int;
+    // rewrites selectors [first, first + n) of a live set (synchronous): the inputs of the circuits recorded on it
+    pub fn rtfhe_trgsw_update(sel: *mut rtfhe_trgsw, trgsw: *const u32, first: i32, n: i32) -> c_int;
     pub fn rtfhe_sync(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_begin(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_end(ctx: *mut rtfhe_ctx, stream: *mut c_void, ms: *mut f64, launches: *mut i64) -> c_int;

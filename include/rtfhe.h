@@ -36,6 +36,9 @@
  *                                       not the tree)
  *   rtfhe_trgsw_rotate_batch[_dev] / rtfhe_trgsw_rotate_extract_batch[_dev]
  *                                    <- one step of TFHE::blind_rotate (hom_nand/src/tfhe.rs:103-110) per caller-supplied TRGSW sample and exponent
+ *   rtfhe_cmux_circuit_create / rtfhe_trgsw_update
+ *                                    (no reference counterpart) netlists of such CMUXes -- decision diagrams over TRGSW-encrypted inputs --
+ *                                       recorded once and replayed through rtfhe_circuit_launch
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch           <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -439,6 +442,55 @@ int rtfhe_trgsw_rotate_extract_batch(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, con
 int rtfhe_trgsw_rotate_extract_batch_dev(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const void *d_sel_idx /* int32[count][depth] or NULL */,
                                          int32_t depth, const int32_t *rot /* HOST [depth] or NULL */, const void *d_trlwe /* [count][2][N] */,
                                          void *d_out /* [count][n+1] */, size_t count, void *stream);
+/* ---- CMUX netlists: decision diagrams over TRGSW-encrypted inputs, recorded once and replayed as one submission ----
+ * The tree and the rotation above are the two degenerate shapes of one node,
+ *   node = cmux(S_var, X^rot * hi, lo),
+ * the fully expanded one and the single chain.  A CMUX netlist is any shape between: an arbitrary function of TRGSW-encrypted bits through
+ * its reduced decision diagram, equal sub-diagrams computed once, several outputs from one diagram.
+ *
+ * A netlist has n_vars input variables and n_nodes nodes in topological order; every node value is a TRLWE u32[2][N] (b then a).  Node i
+ * carries var[i] in [0, n_vars), the references hi[i] and lo[i], and rot[i] in [0, 2N) (rot NULL: all zero).  A reference r >= 0 is node r
+ * and must satisfy r < i; a reference r < 0 is table row row0[g] + (-1 - r) of `lut`, plain or encrypted (a plain row tv is the trivial TRLWE
+ * (tv, 0)).  For replica g of a batch of `count`:
+ *   S        = selector d_sel_idx[g][var[i]]          (d_sel_idx NULL: g * n_vars + var[i])
+ *   value_i  = cmux(S, X^rot[i] * value(hi[i]), value(lo[i])) = cross(S, X^rot[i] * hi - lo) + lo     (wrapping on every word)
+ * with X^r the bootstrap's negacyclic rotation (rotated_coef, utils/src/math.rs:85-132), cmux TRGSWRepF::cmux (hom_nand/src/trgsw.rs:319-321)
+ * and cross what rtfhe_external_product_batch computes.  With rot = 0 and a full binary shape this is rtfhe_cmux_tree_batch; with hi = lo =
+ * the previous node it is one step of rtfhe_trgsw_rotate_batch.
+ *
+ * out_ref[0 .. n_out) names nodes only (a table row is refused).  Two forms, chosen at creation: out_coef NULL gives the TRLWE form,
+ * d_out[count][n_out][2][N]; with out_coef given, d_out[count][n_out][n+1] = identity_key_switch(sample_extract_index(node, out_coef[o]))
+ * through the tree's extract route (the batch key switch many-LUT uses, or under RTFHE_KS_MM_MIN=0 the wave-per-sample one); that form needs
+ * the key-switching key only.
+ *
+ * rtfhe_cmux_circuit_create checks, before anything is allocated: the handles; n_nodes, n_vars, n_out, count >= 1; every var, every reference
+ * (the topological order; the row range against the table when d_row0 is NULL), every rot and every out_coef (< N); with d_sel_idx NULL
+ * count * n_vars <= n_sel; that the node buffer's byte count fits size_t.  A failure is RTFHE_ERR_INVALID and the message names the node or
+ * output.  It then levelises the netlist -- level(i) = 1 + the largest level of its node children, 0 for a node with only leaf children --,
+ * uploads the description, allocates what the circuit owns (the node buffer [count][n_nodes][2][N]: no slot is reused, it is
+ * count * n_nodes * 8N bytes; its own copy of the table rows, so `lut` may be destroyed afterwards; one flag per replica; in the extract
+ * form the sample buffer) and records ONE linear HIP graph: the check kernel, one launch per level, the output kernel, and in the extract form
+ * the key switch.  The handle is an ordinary rtfhe_circuit: rtfhe_circuit_launch replays it on any stream (asynchronous, nothing is
+ * allocated), rtfhe_circuit_destroy frees it, and a context destroyed first is rtfhe_circuit_create's case.  Two replays of one circuit must
+ * not overlap (they share the node buffer).
+ *
+ * d_sel_idx, d_row0 and d_out belong to the caller, stay in place while the circuit exists and are read or written at replay.  The circuit
+ * reads the selector set's spectra in place -- they are its inputs: rtfhe_trgsw_update rewrites selectors [first, first + n) of a live set
+ * with rtfhe_trgsw_create's conversion (synchronous; it waits for the device first), and the next replay computes on the new ciphertexts.
+ * Destroying the set marks the circuits recorded on it: their rtfhe_circuit_launch then fails with RTFHE_ERR_STATE.
+ *
+ * The device-resident indices are checked at every replay by the first kernel, all n_vars selector indices of a replica and its row0 against
+ * the smallest and largest leaf the netlist names.  A bad replica is skipped whole: nothing is read or written through its indices, its node
+ * slots are not written, its TRLWE output rows keep their bytes, its extract-form rows are all zero (no valid ciphertexts), and the next
+ * rtfhe_sync returns RTFHE_ERR_INVALID once, as for rtfhe_cmux_tree_batch_dev.  The FP64 mirror backend only; a multi-device context runs
+ * the circuit on its primary device. */
+int rtfhe_cmux_circuit_create(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const rtfhe_lut *lut, const int32_t *var /* [n_nodes] */,
+                              const int32_t *hi /* [n_nodes] */, const int32_t *lo /* [n_nodes] */, const int32_t *rot /* [n_nodes] or NULL */,
+                              int32_t n_nodes, int32_t n_vars, const int32_t *out_ref /* [n_out] */,
+                              const int32_t *out_coef /* [n_out], or NULL: TRLWE form */, int32_t n_out,
+                              const void *d_sel_idx /* int32[count][n_vars] or NULL */, const void *d_row0 /* int32[count] or NULL */,
+                              void *d_out, size_t count, rtfhe_circuit **out);
+int rtfhe_trgsw_update(rtfhe_trgsw *sel, const uint32_t *trgsw /* [n][2][2l][N] */, int32_t first, int32_t n);
 /* waits for `stream`; also reports (once) a netlist gate skipped since the previous call */
 int rtfhe_sync(rtfhe_ctx *ctx, void *stream);
 /* device-side timing of the launches enqueued by the *_dev calls between begin and end (HIP events on

@@ -8,7 +8,9 @@ from .engine import (Engine, FftPlan, Lut, RtfheError, Selectors, decrypt_bits, 
                      load_tlwe, phases, pinned_empty, save_keys, save_tlwe, shard_range, trlwe_phase)
 from .pbs import decode_msgs, encode_msgs, lut_polynomial, many_lut_polynomial  # noqa: F401
 from .lut_circuit import LutCircuitRunner, LutNetlist, lut_ripple_adder  # noqa: F401
+from .cmux_net import CmuxCircuit, CmuxNetlist, bdd_netlist, cmux_tree_netlist, trgsw_rotate_netlist  # noqa: F401
 
 __all__ = ["Engine", "FftPlan", "Params", "RtfheError", "keygen", "ksk_expand_ref", "encrypt_bits", "decrypt_bits", "phases", "save_keys", "load_keys", "save_tlwe", "load_tlwe", "pinned_empty", "shard_range", "device_link",
            "Lut", "Selectors", "encrypt_torus", "encrypt_lut", "encrypt_selectors", "trlwe_phase", "encode_msgs", "decode_msgs", "lut_polynomial", "many_lut_polynomial", "LutNetlist", "LutCircuitRunner", "lut_ripple_adder",
+           "CmuxNetlist", "CmuxCircuit", "bdd_netlist", "cmux_tree_netlist", "trgsw_rotate_netlist",
            "NAND", "AND", "OR", "XOR", "NOT", "COPY", "ANDNY", "load"]

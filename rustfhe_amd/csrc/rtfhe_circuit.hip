@@ -265,6 +265,8 @@ int rtfhe_circuit_launch(rtfhe_circuit* c, void* stream) {
     if (int rc = use(ctx)) return rc;
     if (c->stale) return fail(ctx, RTFHE_ERR_STATE, "the circuit was recorded on an exact backend and the bootstrapping key has since been replaced by one without a "
                                                   "torus form (rtfhe_load_bk_fft): its key form could not follow; record the circuit again");
+    if (c->sel_gone) return fail(ctx, RTFHE_ERR_STATE, "the selector set (rtfhe_trgsw) this CMUX netlist was recorded on has been destroyed: its graph reads the "
+                                                     "set's spectra in place; record the circuit again on a live set");
     HIPCHECK(ctx, hipGraphLaunch(c->exec, (hipStream_t)stream));
     ctx->launches += c->launches;
     return 0;

@@ -355,6 +355,7 @@ void rtfhe_trgsw_destroy(rtfhe_trgsw* t) {
     if (rtfhe_ctx* ctx = t->ctx) {     // still attached (a context destroyed first has already freed the spectra and detached us)
         auto& v = ctx->trgsws;
         for (size_t i = 0; i < v.size(); i++) if (v[i] == t) { v.erase(v.begin() + i); break; }
+        for (rtfhe_circuit* c : ctx->circuits) if (c->sel == t) { c->sel = nullptr; c->sel_gone = true; }      // CMUX netlists recorded on this set
         trgsw_release(t);
     }
     delete t;

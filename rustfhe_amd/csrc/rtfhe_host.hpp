@@ -9,6 +9,7 @@
 //   rtfhe_circuit.hip        levelised netlists: one wave per call, or all waves recorded into a HIP graph
 //   rtfhe_multi.hip          one context over several GPUs: key replication, sharding of host batches and of device-resident batches
 //   rtfhe_cmux_tree.hip      CMUX-tree table lookup: selector sets (caller-supplied TRGSW samples), one launch per tree level; TRGSW blind rotation
+//   rtfhe_cmux_net.hip       CMUX netlists: decision diagrams over a selector set, levelised (rtfhe_cmux_net_plan.cpp, host only) and recorded into a HIP graph
 // Every kernel is instantiated in exactly one of them.  No CPU fallback anywhere: an entry point runs HIP kernels or fails.
 #pragma once
 
@@ -150,6 +151,8 @@ struct rtfhe_circuit {
     int64_t launches = 0;      // kernel launches one replay stands for
     int backend = RTFHE_BACKEND_FFT64_MIRROR;   // the backend it was recorded on
     bool stale = false;        // recorded on an exact backend whose key form could not follow a key change (rebuild_derived_keys)
+    const rtfhe_trgsw* sel = nullptr;   // a CMUX netlist (rtfhe_cmux_circuit_create): the selector set whose spectra its graph reads in place
+    bool sel_gone = false;     // ... and that set has been destroyed (rtfhe_trgsw_destroy): the graph holds freed addresses
 };
 
 // the test polynomials of a programmable bootstrap (rtfhe_lut_create), one copy on every entry of the context

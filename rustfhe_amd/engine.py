@@ -376,6 +376,15 @@ class Engine:
         self._ck(self.L.rtfhe_trgsw_rotate_extract_batch_dev(self.h, sel.h, self._dev(d_sel_idx), int(depth), _ptr(r), self._dev(d_trlwe), self._dev(d_out),
                                                              count, C.c_void_p(stream) if stream else None))
 
+    # ---- CMUX netlists (include/rtfhe.h: rtfhe_cmux_circuit_create; rustfhe_amd.cmux_net) -----------------------------------------------------
+    def cmux_circuit(self, netlist, sel, lut, d_out, count, d_sel_idx=None, d_row0=None):
+        """Records `count` replicas of a CmuxNetlist over the selector set `sel` and the table `lut` into one graph.  d_out: device buffer
+        [count][n_out][2][N] words, or [count][n_out][n+1] when the netlist's outputs carry coefficients; d_sel_idx: int32[count][n_vars] on
+        the device (None: replica g uses selectors g * n_vars + v); d_row0: int32[count] (None: 0).  The description is checked here: a bad
+        node or output raises RtfheError before anything is allocated.  Returns a CmuxCircuit: launch(stream), close()."""
+        from .cmux_net import CmuxCircuit
+        return CmuxCircuit(self, netlist, sel, lut, d_out, count, d_sel_idx, d_row0)
+
     # ---- stage level ------------------------------------------------------------------------
     def blind_rotate_batch(self, tlwe, steps=None):
         tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)
@@ -478,6 +487,13 @@ class Selectors:
         h = C.c_void_p()
         engine._ck(engine.L.rtfhe_trgsw_create(engine.h, _ptr(trgsw), self.n_sel, C.byref(h)))
         self.h = h
+
+    def update(self, words, first=0):
+        """Rewrites selectors [first, first + n) with new TRGSW samples u32[n][2][2l][N] (rtfhe_trgsw_update; synchronous): the circuits
+        recorded on this set (Engine.cmux_circuit) then run on the new ciphertexts."""
+        p = self.engine.p
+        words = _np(words, np.uint32).reshape(-1, 2 * 2 * p.l * p.N)
+        self.engine._ck(self.engine.L.rtfhe_trgsw_update(self.h, _ptr(words), int(first), words.shape[0]))
 
     def close(self):
         if getattr(self, "h", None):
