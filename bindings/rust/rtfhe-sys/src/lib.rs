@@ -33,6 +33,7 @@ pub enum rtfhe_ctx {}
 pub enum rtfhe_circuit {}
 pub enum rtfhe_lut {}
 pub enum rtfhe_trgsw {}
+pub enum rtfhe_packing_key {}
 pub enum rtfhe_fft_plan {}
 
 pub const RTFHE_NAND: c_int = 0;
@@ -147,6 +148,16 @@ extern "C" {
                                      d_sel_idx: *const c_void, d_row0: *const c_void, d_out: *mut c_void, count: usize, out: *mut *mut rtfhe_circuit) -> c_int;
     // rewrites selectors [first, first + n) of a live set (synchronous): the inputs of the circuits recorded on it
     pub fn rtfhe_trgsw_update(sel: *mut rtfhe_trgsw, trgsw: *const u32, first: i32, n: i32) -> c_int;
+    // packing key switch: lvl0 samples [count][P][n+1] into TRLWE rows [count][2][N]; pk [n][t][base-1][2][N] under key1; pos HOST [P] (null: p * rep);
+    // rtfhe_lut_update_dev rewrites rows of an encrypted table in place from device memory (stream-ordered)
+    pub fn rtfhe_packing_keygen(p: *const rtfhe_params, key0: *const i32, key1: *const i32, pk: *mut u32) -> c_int;
+    pub fn rtfhe_packing_keygen_deterministic(p: *const rtfhe_params, seed: u64, key0: *const i32, key1: *const i32, pk: *mut u32) -> c_int;
+    pub fn rtfhe_packing_key_create(ctx: *mut rtfhe_ctx, pk: *const u32, out: *mut *mut rtfhe_packing_key) -> c_int;
+    pub fn rtfhe_packing_key_destroy(pk: *mut rtfhe_packing_key);
+    pub fn rtfhe_pack_batch(ctx: *mut rtfhe_ctx, pk: *const rtfhe_packing_key, tlwe: *const u32, P: i32, pos: *const i32, rep: i32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_pack_batch_dev(ctx: *mut rtfhe_ctx, pk: *const rtfhe_packing_key, d_tlwe: *const c_void, P: i32, pos: *const i32, rep: i32, d_out: *mut c_void,
+                                count: usize, stream: *mut c_void) -> c_int;
+    pub fn rtfhe_lut_update_dev(lut: *mut rtfhe_lut, d_trlwe: *const c_void, first: i32, n: i32, stream: *mut c_void) -> c_int;
     pub fn rtfhe_sync(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_begin(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_end(ctx: *mut rtfhe_ctx, stream: *mut c_void, ms: *mut f64, launches: *mut i64) -> c_int;

@@ -39,6 +39,9 @@
  *   rtfhe_cmux_circuit_create / rtfhe_trgsw_update
  *                                    (no reference counterpart) netlists of such CMUXes -- decision diagrams over TRGSW-encrypted inputs --
  *                                       recorded once and replayed through rtfhe_circuit_launch
+ *   rtfhe_packing_key_create / rtfhe_pack_batch[_dev] / rtfhe_lut_update_dev
+ *                                    (no reference counterpart) TFHE's public packing key switch: lvl0 samples into TRLWE rows, with the digits of
+ *                                       identity_key_switch (hom_nand/src/tlwe.rs:43-73) and TRLWE key rows (hom_nand/src/trlwe.rs) in the place of TLWE ones
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch           <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -65,6 +68,7 @@
  *   BK fft      f64[n][2][2l][N]   same order; each poly an FrrSeries: Re[0..N/2) then Im[0..N/2),
  *                                  in the transform's native order (utils/src/spqlios.rs:147,205-208)
  *   KSK         u32[N][t][base-1][n+1]   rows d = 1 .. base-1 of level l of coefficient i   (rtfhe_load_ksk, rtfhe_keygen*)
+ *   PK          u32[n][t][base-1][2][N]  packing key: row d = 1 .. base-1 of level j of coefficient i, a TRLWE (rtfhe_packing_keygen*)
  *   KSK (ref)   u32[N][t][base][n+1]     the reference's [[TLWERep; IKS_T]; IKS_L]: one more row (t = base) per level, never read
  *                                        (rtfhe_load_ksk_ref drops it)
  */
@@ -491,6 +495,74 @@ int rtfhe_cmux_circuit_create(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const rtfh
                               const void *d_sel_idx /* int32[count][n_vars] or NULL */, const void *d_row0 /* int32[count] or NULL */,
                               void *d_out, size_t count, rtfhe_circuit **out);
 int rtfhe_trgsw_update(rtfhe_trgsw *sel, const uint32_t *trgsw /* [n][2][2l][N] */, int32_t first, int32_t n);
+/* ---- packing key switch: lvl0 ciphertexts into TRLWE rows (bootstrapped mode -> leveled mode) ----
+ * Packing key.  pk is u32[n][t][base-1][2][N], with t = ks_t and base = 2^ks_basebit.  Row (i, j, d) is a TRLWE in the project's layout (b(X),
+ * then a(X)) under key1.  It encrypts the constant polynomial (d+1) · key0[i] · 2^(-ks_basebit·(j+1)) with alpha = 2^-25.  The message word is
+ * formed exactly as the key-switching key's: torus_from_f32((float)key0[i] * pw * (float)(d+1)).  rtfhe_packing_keygen draws it from the OS
+ * CSPRNG, rtfhe_packing_keygen_deterministic (TEST ONLY) from a seed; both reject non-binary keys.
+ * The rows' noise MUST BE ZERO-MEAN: about 3/4 · n · t · P · rep row coefficients (4 · 10^6 at n = 635, P · rep = 1024) add into every packed
+ * coefficient, so a common mean grows linearly where the noise itself grows with the square root.  The f32 sampler of the other keys
+ * (Normal f32 through torus_from_f32, as the reference's) has a mean of about +10 · 2^-32 at alpha = 2^-25: rows drawn with it give a packed
+ * error of 9 · 10^-3 of the torus where zero-mean rows give 4 · 10^-4.  The two generators here draw the noise in double precision, rounded to
+ * the nearest torus word; a key made elsewhere must do the same.
+ *
+ * Key switch of one sample.  Take a lvl0 sample c = (a_0 … a_{n-1}, b).
+ *   - Let ROUND = 2^(32 - t·ks_basebit - 1).
+ *   - Let d_{i,j} = ((a_i + ROUND) >> (32 - (j+1)·ks_basebit)) & (base - 1).  These are the digits of identity_key_switch.
+ *   - S(c) is the TRLWE with
+ *       S.b[k] = [k = 0]·b - Σ_{i,j : d_{i,j} ≠ 0} pk[i][j][d_{i,j}-1].b[k]
+ *       S.a[k] =           - Σ_{i,j : d_{i,j} ≠ 0} pk[i][j][d_{i,j}-1].a[k]
+ *   - Every word wraps mod 2^32.
+ *
+ * Packing.  Output g of a batch is out[g] = Σ_{p<P} X^{pos[p]} · (1 + X + … + X^{rep-1}) · S(c[g][p]) mod X^N + 1, on both halves.  Word for word:
+ *   - out[g][h][c] = Σ_p Σ_{k<rep} ± S_p[h][u mod N], where u = (c - pos[p] - k) mod 2N.
+ *   - The sign is + if u < N and - otherwise.
+ *   - u32 addition is associative and commutative.  Any summation order gives the same words.
+ *
+ * Parameters.
+ *   - pos is a host array int32[P], shared by the batch (copied into the launch's arguments when the call is enqueued: a stream capture bakes
+ *     it in).  pos NULL means pos[p] = p·rep.
+ *   - The calls check 1 ≤ P ≤ N, 1 ≤ rep ≤ N and pos[p] ∈ [0, 2N) (also for the positions pos NULL stands for).  A failed check returns
+ *     RTFHE_ERR_INVALID before anything is launched.
+ *   - Overlapping runs are allowed; they add.
+ *   - The key type needs ks_t = 8 and ks_basebit = 2, the one instantiation the batch key switch has.  Anything else returns RTFHE_ERR_INVALID
+ *     at key generation and at key creation.
+ *
+ * Backends and devices.  Nothing here multiplies polynomials.  The calls work on every rtfhe_backend and never read the bootstrapping key or
+ * the key-switching key.  On an rtfhe_ctx_create_multi context they run on the primary device only.
+ *
+ * Table layout.  With rep = B = N / 2^p and pos[e] = (e·B - B/2) mod 2N, packing the 2^p ciphertexts of enc_out(f(e)) yields an encryption of
+ * the test polynomial of f on p-bit messages (rustfhe_amd.pbs.lut_polynomial; rustfhe_amd.pbs.lut_pack_layout gives pos and rep).  Box e covers
+ * [eB - B/2, eB + B/2), and entry 0's lower half-box lands on the top coefficients with the sign flipped.
+ *
+ * Key handle.  rtfhe_packing_key_create uploads the rows to the primary device, turns them into signed byte limbs in the operand order of the
+ * i8 matrix pipe and frees the upload.  Device footprint of a handle: N · n16 · 256 bytes, n16 = n rounded up to a multiple of 16 (168 MB at
+ * n = 635, N = 1024; creation also holds the 2N · 4 · n · t · (base-1) bytes of the upload, 125 MB, until it returns).  It is not counted by
+ * rtfhe_ctx_memory_bytes, as for selector sets.  Lifetime as rtfhe_trgsw: normally destroyed before its context; if the context goes first,
+ * the matrix is released with it, a later pack call with the handle fails with RTFHE_ERR_STATE and rtfhe_packing_key_destroy only frees the
+ * handle.
+ *
+ * rtfhe_pack_batch takes host buffers and is synchronous.  rtfhe_pack_batch_dev is asynchronous and stream-ordered.  The key-switched samples
+ * S[count·P][2N] live in a buffer of the context that belongs to `stream` (8N bytes per sample; not counted by rtfhe_ctx_memory_bytes), grown
+ * outside stream captures only -- growing an existing one synchronises the device -- and kept until the context is destroyed.  Inside a
+ * stream capture the call allocates nothing: an eager rtfhe_pack_batch_dev of at least count·P samples must have run on that stream first,
+ * else RTFHE_ERR_STATE.  This is the rule of rtfhe_pbs_many_batch_dev.
+ *
+ * rtfhe_lut_update_dev rewrites rows first … first+n-1 of an ENCRYPTED table in place from device memory, a stream-ordered copy: a packed row
+ * becomes a table row without a host round trip.  It returns RTFHE_ERR_INVALID for a plain table, for a range outside the table and on a
+ * multi-device context, and RTFHE_ERR_STATE after the context is gone.  PBS calls enqueued later on the same stream read the new rows.  LUT
+ * circuits and CMUX netlists own a copy of their rows and are not affected. */
+typedef struct rtfhe_packing_key rtfhe_packing_key;
+int rtfhe_packing_keygen(const rtfhe_params *p, const int32_t *key0, const int32_t *key1, uint32_t *pk /* [n][t][base-1][2][N] */);
+/* TEST ONLY -- NOT SECURE (see rtfhe_keygen_deterministic) */
+int rtfhe_packing_keygen_deterministic(const rtfhe_params *p, uint64_t seed, const int32_t *key0, const int32_t *key1, uint32_t *pk);
+int rtfhe_packing_key_create(rtfhe_ctx *ctx, const uint32_t *pk /* [n][t][base-1][2][N] */, rtfhe_packing_key **out);
+void rtfhe_packing_key_destroy(rtfhe_packing_key *pk);
+int rtfhe_pack_batch(rtfhe_ctx *ctx, const rtfhe_packing_key *pk, const uint32_t *tlwe /* [count][P][n+1] */, int32_t P,
+                     const int32_t *pos /* [P] or NULL */, int32_t rep, uint32_t *out /* [count][2][N] */, size_t count);
+int rtfhe_pack_batch_dev(rtfhe_ctx *ctx, const rtfhe_packing_key *pk, const void *d_tlwe /* [count][P][n+1] */, int32_t P,
+                         const int32_t *pos /* HOST [P] or NULL */, int32_t rep, void *d_out /* [count][2][N] */, size_t count, void *stream);
+int rtfhe_lut_update_dev(rtfhe_lut *lut, const void *d_trlwe /* [n][2][N] */, int32_t first, int32_t n, void *stream);
 /* waits for `stream`; also reports (once) a netlist gate skipped since the previous call */
 int rtfhe_sync(rtfhe_ctx *ctx, void *stream);
 /* device-side timing of the launches enqueued by the *_dev calls between begin and end (HIP events on

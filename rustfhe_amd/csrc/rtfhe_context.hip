@@ -338,6 +338,8 @@ void rtfhe_ctx_destroy(rtfhe_ctx* ctx) {
     ctx->luts.clear();
     for (rtfhe_trgsw* t : ctx->trgsws) { trgsw_release(t); t->ctx = nullptr; }      // selector sets: the same rule
     ctx->trgsws.clear();
+    for (rtfhe_packing_key* k : ctx->pack_keys) { packing_key_release(k); k->ctx = nullptr; }      // packing keys: the same rule
+    ctx->pack_keys.clear();
     for (rtfhe_ctx* peer : ctx->peers) rtfhe_ctx_destroy(peer);
     ctx->peers.clear();
     (void)hipSetDevice(ctx->device);
@@ -366,6 +368,7 @@ void rtfhe_ctx_destroy(rtfhe_ctx* ctx) {
     for (void* h : ctx->h_pin) if (h) (void)hipHostFree(h);
     for (auto& kv : ctx->mux) for (void* m : kv.second.m) if (m) (void)hipFree(m);
     for (auto& kv : ctx->tree) for (uint32_t* d : kv.second.d) if (d) (void)hipFree(d);
+    for (auto& kv : ctx->pack) if (kv.second.d) (void)hipFree(kv.second.d);
     for (void* m : ctx->mux_retired) (void)hipFree(m);
     for (hipEvent_t e : ctx->ks_events) (void)hipEventDestroy(e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);

@@ -10,6 +10,7 @@
 //   rtfhe_multi.hip          one context over several GPUs: key replication, sharding of host batches and of device-resident batches
 //   rtfhe_cmux_tree.hip      CMUX-tree table lookup: selector sets (caller-supplied TRGSW samples), one launch per tree level; TRGSW blind rotation
 //   rtfhe_cmux_net.hip       CMUX netlists: decision diagrams over a selector set, levelised (rtfhe_cmux_net_plan.cpp, host only) and recorded into a HIP graph
+//   rtfhe_pack.hip           packing key switch: packing keys (signed byte limbs in operand order), lvl0 samples into TRLWE rows, in-place table updates
 // Every kernel is instantiated in exactly one of them.  No CPU fallback anywhere: an entry point runs HIP kernels or fails.
 #pragma once
 
@@ -52,6 +53,7 @@ struct HostTw {
 struct rtfhe_circuit;
 struct rtfhe_lut;
 struct rtfhe_trgsw;
+struct rtfhe_packing_key;
 struct rtfhe_ctx {
     rtfhe_params p{};
     int device = 0;
@@ -132,6 +134,11 @@ struct rtfhe_ctx {
     struct TreeBuf { uint32_t* d[2] = {nullptr, nullptr}; size_t cap = 0; bool captured = false; };
     std::unordered_map<hipStream_t, TreeBuf> tree;
     std::vector<rtfhe_trgsw*> trgsws;      // live selector sets of this context: their spectra go with it, the handles stay
+    // the key-switched samples S[count * P][2N] between the two launches of a packing key switch (rtfhe_pack.hip), one buffer per stream a pack
+    // was ever launched on, under the rules of the tree's buffers above; cap in samples; not counted by rtfhe_ctx_memory_bytes
+    struct PackBuf { uint32_t* d = nullptr; size_t cap = 0; bool captured = false; };
+    std::unordered_map<hipStream_t, PackBuf> pack;
+    std::vector<rtfhe_packing_key*> pack_keys;      // live packing keys of this context: their matrices go with it, the handles stay
     int num_cus = 256;
     int force_waves = 0;   // RTFHE_FORCE_WAVES=1|2|4|8: one kernel shape for every batch (the parity tests' second opinions)
     int wg_max = 512;      // RTFHE_WG_MAX_GATES: largest batch routed to the workgroup-per-gate kernel
@@ -168,6 +175,13 @@ struct rtfhe_trgsw {
     rtfhe_ctx* ctx = nullptr;           // null once the context has been destroyed (the handle then only remains to be freed)
     rtfhe::cplx* d_spec = nullptr;      // [n_sel][2l][2][R][64], the layout of one bootstrapping-key entry each
     int32_t n_sel = 0;
+};
+
+// a packing key (rtfhe_packing_key_create): the key rows as signed byte limbs in i8-MFMA operand order on the primary device
+struct rtfhe_packing_key {
+    rtfhe_ctx* ctx = nullptr;           // null once the context has been destroyed (the handle then only remains to be freed)
+    uint4* d_kmat = nullptr;            // [2N / 16 column groups][n16 / 2 K-steps][4 limbs][64 lanes] x 16 B (rtfhe_kernels_pack.hpp)
+    int32_t n16 = 0, colgroups = 0;
 };
 
 namespace rtfhe_host {
@@ -225,6 +239,7 @@ int copy_out(rtfhe_ctx* ctx, void* dst, const void* src, size_t bytes, int slot)
 void circuit_release(rtfhe_circuit* c);                                   // rtfhe_circuit.hip
 void lut_release(rtfhe_lut* lut);                                         // frees a table's device copies (rtfhe_context.hip)
 void trgsw_release(rtfhe_trgsw* t);                                       // frees a selector set's spectra (rtfhe_cmux_tree.hip)
+void packing_key_release(rtfhe_packing_key* k);                           // frees a packing key's matrix (rtfhe_pack.hip)
 
 // ---- twiddles (rtfhe_twiddles.hip) ----
 bool unit_twiddles_ok(const HostTw& tw);

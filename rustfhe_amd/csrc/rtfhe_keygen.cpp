@@ -122,6 +122,17 @@ uint32_t gaussian_torus(Rng& r, float alpha) {
     return torus_from_f32((float)z * alpha);
 }
 
+// The same distribution without the f32 round trip: z alpha 2^32 rounded to the nearest integer in double precision.  torus_from_f32 above
+// truncates towards zero on the positive side and rounds 1 + v to f32's 2^-24 grid on the negative side, which leaves the samples of
+// alpha = 2^-25 with a mean of about +10 LSB (2^-28.7).  One row does not notice; the packing key switch adds n t P rep ~ 4 * 10^6 such
+// samples into every coefficient, where a common mean grows linearly, so the packing key's rows are drawn with this one.
+uint32_t gaussian_torus_centred(Rng& r, double alpha) {
+    double u1 = r.unit53(), u2 = r.unit53();
+    if (u1 < 1e-300) u1 = 1e-300;
+    const double z = std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586 * u2);
+    return (uint32_t)(int64_t)std::llround(z * alpha * 4294967296.0);
+}
+
 void tlwe_encrypt(Rng& r, int n, const int32_t* key, uint32_t msg, float alpha, uint32_t* ct) {
     uint32_t b = 0;
     for (int i = 0; i < n; i++) ct[i] = uniform_torus(r);
@@ -131,9 +142,10 @@ void tlwe_encrypt(Rng& r, int n, const int32_t* key, uint32_t msg, float alpha, 
 }
 
 // b = a * s + e  (exact negacyclic product with the binary key; the reference uses its FFT here)
-void trlwe_zero(Rng& r, int N, const int32_t* key, float alpha, uint32_t* b, uint32_t* a) {
+// (centred: the noise from gaussian_torus_centred, for the packing key)
+void trlwe_zero(Rng& r, int N, const int32_t* key, float alpha, uint32_t* b, uint32_t* a, bool centred = false) {
     for (int k = 0; k < N; k++) a[k] = uniform_torus(r);
-    for (int k = 0; k < N; k++) b[k] = gaussian_torus(r, alpha);
+    for (int k = 0; k < N; k++) b[k] = centred ? gaussian_torus_centred(r, (double)alpha) : gaussian_torus(r, alpha);
     for (int j = 0; j < N; j++) {
         if (!key[j]) continue;
         for (int k = 0; k < N - j; k++) b[k + j] += a[k];
@@ -206,6 +218,42 @@ int keygen_material(const rtfhe_params* p, const Source& src, const int32_t* key
         for (int k = 0; k < nthreads; k++) th.emplace_back(work, k);
         for (auto& x : th) x.join();
     }
+    return 0;
+}
+
+// The packing key (rtfhe_packing_keygen; include/rtfhe.h): row (i, j, d) is a TRLWE under key1 of the constant polynomial
+// (d + 1) key0[i] / 2^(basebit (j + 1)) with alpha = 2^-25 (zero-mean: gaussian_torus_centred), the message word formed as the key-switching
+// key's above.  One generator per
+// coefficient i, striped over the threads as keygen_material does; secure: ChaCha streams of domain 4, deterministic: seeds of its own.
+int packing_keygen(const rtfhe_params* p, const Source& src, const int32_t* key0, const int32_t* key1, uint32_t* pk) {
+    const int n = p->n, N = p->N, t = p->ks_t, bb = p->ks_basebit, base1 = (1 << bb) - 1;
+    if (t != 8 || bb != 2) return RTFHE_ERR_INVALID;      // the one instantiation the packing key switch has
+    for (int i = 0; i < n; i++) if (key0[i] != 0 && key0[i] != 1) return RTFHE_ERR_INVALID;
+    for (int i = 0; i < N; i++) if (key1[i] != 0 && key1[i] != 1) return RTFHE_ERR_INVALID;
+    const float alpha = 1.0f / 33554432.0f;      // 2^-25, trlwe.rs:77
+    const unsigned hw = std::thread::hardware_concurrency();
+    const int nthreads = (int)(hw ? (hw > 16 ? 16 : hw) : 1);
+    uint64_t s_pk = 0;
+    if (!src.secure) { Xoshiro root(src.seed); root.next(); root.next(); s_pk = root.next(); }      // (the first two are keygen_material's)
+    auto body = [&](Rng& r, int i) {
+        for (int lv = 0; lv < t; lv++)
+            for (int d = 0; d < base1; d++) {
+                float pw = 1.0f;
+                for (int e = 0; e < bb * (lv + 1); e++) pw *= 0.5f;
+                uint32_t* b = pk + (((size_t)i * t + lv) * base1 + d) * 2 * (size_t)N;
+                trlwe_zero(r, N, key1, alpha, b, b + N, true);
+                b[0] += torus_from_f32((float)key0[i] * pw * (float)(d + 1));
+            }
+    };
+    auto work = [&](int tid) {
+        for (int i = tid; i < n; i += nthreads) {
+            if (src.secure) { ChaCha r(src.key, ((uint64_t)4 << 32) | (uint32_t)i); body(r, i); }
+            else { Xoshiro r(s_pk + 0xd6e8feb86659fd93ull * (uint64_t)(i + 1)); body(r, i); }
+        }
+    };
+    std::vector<std::thread> th;
+    for (int k = 0; k < nthreads; k++) th.emplace_back(work, k);
+    for (auto& x : th) x.join();
     return 0;
 }
 
@@ -331,7 +379,19 @@ int rtfhe_ksk_expand_ref(const rtfhe_params* p, const int32_t* key0, const int32
     return ksk_expand_ref(p, src, key0, key1, ksk, ksk_ref);
 }
 
+int rtfhe_packing_keygen(const rtfhe_params* p, const int32_t* key0, const int32_t* key1, uint32_t* pk) {
+    if (!valid(p) || !key0 || !key1 || !pk) return RTFHE_ERR_INVALID;
+    Source src;
+    if (!Source::from_os(src)) return RTFHE_ERR_STATE;
+    return packing_keygen(p, src, key0, key1, pk);
+}
+
 // ---- TEST ONLY: reproducible from a 64-bit seed (xoshiro256**, not a CSPRNG) ----
+int rtfhe_packing_keygen_deterministic(const rtfhe_params* p, uint64_t seed, const int32_t* key0, const int32_t* key1, uint32_t* pk) {
+    if (!valid(p) || !key0 || !key1 || !pk) return RTFHE_ERR_INVALID;
+    return packing_keygen(p, Source::from_seed(seed), key0, key1, pk);
+}
+
 int rtfhe_ksk_expand_ref_deterministic(const rtfhe_params* p, uint64_t seed, const int32_t* key0, const int32_t* key1, const uint32_t* ksk, uint32_t* ksk_ref) {
     if (!valid(p) || !key0 || !key1 || !ksk || !ksk_ref) return RTFHE_ERR_INVALID;
     return ksk_expand_ref(p, Source::from_seed(seed), key0, key1, ksk, ksk_ref);

@@ -1,0 +1,199 @@
+// rtfhe_pack.hip -- the packing key switch (include/rtfhe.h: rtfhe_packing_key_create, rtfhe_pack_batch[_dev], rtfhe_lut_update_dev): packing
+// keys as signed byte limbs in operand order (k_pkmat_build), the argument checks, the stream's buffer of key-switched samples and the rules
+// around stream captures, k_pack_ks_mm then k_pack_combine per call, and the stream-ordered rewrite of an encrypted table's rows.
+// Nothing here multiplies polynomials: the calls work on every backend and never read the bootstrapping key.
+#include "rtfhe_host.hpp"
+
+#include "rtfhe_kernels_pack.hpp"
+
+using namespace rtfhe;
+using namespace rtfhe_host;
+
+namespace {
+
+bool capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+// what both pack entries check before anything is allocated or launched; fills shift[P] with the positions (pos NULL: p * rep)
+int pack_ready(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const void* in, int32_t P, const int32_t* pos, int32_t rep, const void* out, size_t count,
+               std::vector<int32_t>& shift) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!pk) return fail(ctx, RTFHE_ERR_INVALID, "null packing key (rtfhe_packing_key)");
+    if (!in || !out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (!pk->ctx) return fail(ctx, RTFHE_ERR_STATE, "the context of the packing key has been destroyed");
+    if (pk->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the packing key belongs to another context");
+    const int N = ctx->p.N;
+    if (P < 1 || P > N) return fail(ctx, RTFHE_ERR_INVALID, "P = " + std::to_string(P) + " is outside [1, " + std::to_string(N) + "]");
+    if (rep < 1 || rep > N) return fail(ctx, RTFHE_ERR_INVALID, "rep = " + std::to_string(rep) + " is outside [1, " + std::to_string(N) + "]");
+    if (count > (size_t)0x7fffffff / (size_t)P) return fail(ctx, RTFHE_ERR_INVALID, "count * P too large");
+    shift.resize((size_t)P);
+    for (int p = 0; p < P; p++) {
+        const long long v = pos ? (long long)pos[p] : (long long)p * rep;
+        if (v < 0 || v >= 2 * N)
+            return fail(ctx, RTFHE_ERR_INVALID, "sample " + std::to_string(p) + ": pos = " + std::to_string(v) + " is outside [0, " + std::to_string(2 * N) + ")" +
+                                                (pos ? "" : " (pos NULL: p * rep)"));
+        shift[(size_t)p] = (int32_t)v;
+    }
+    return 0;
+}
+
+template <int LOGN>
+void launch_combine_t(const PackCombineArgs& a, size_t count, hipStream_t s) {
+    hipLaunchKernelGGL((k_pack_combine<LOGN>), dim3((unsigned)(2 * count)), dim3(PACK_CT), 0, s, a);
+}
+
+// `count` outputs of P samples each on device buffers, primary device, stream s.  d_tlwe: [count * P][n+1], d_out: [count][2][N].
+int launch_pack(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const void* d_tlwe, int32_t P, const std::vector<int32_t>& shift, int32_t rep, void* d_out,
+                size_t count, hipStream_t s) {
+    if (count == 0) return 0;
+    const size_t N = (size_t)ctx->p.N, M = count * (size_t)P;
+    auto it = ctx->pack.find(s);
+    if (capturing(s)) {
+        // nothing may be allocated inside a capture: this stream's buffer must already hold the call, and the graph then owns its address
+        if (it == ctx->pack.end() || it->second.cap < M)
+            return fail(ctx, RTFHE_ERR_STATE, "a packing key switch inside a stream capture needs this stream's sample buffer to exist already: run one eager "
+                                              "rtfhe_pack_batch_dev of at least count * P = " + std::to_string(M) + " samples on the stream before capturing");
+        it->second.captured = true;
+    } else if (it == ctx->pack.end() || it->second.cap < M) {
+        rtfhe_ctx::PackBuf& pb = ctx->pack[s];
+        if (pb.d) {
+            HIPCHECK(ctx, hipDeviceSynchronize());            // earlier packs of this stream may still read the old buffer
+            uint32_t* old = pb.d;
+            const bool keep = pb.captured;
+            pb.d = nullptr; pb.cap = 0; pb.captured = false;      // (before the free: a failure below must not leave the old address behind)
+            if (keep) ctx->mux_retired.push_back(old);        // a graph holds its address: kept until the context goes
+            else HIPCHECK(ctx, hipFree(old));
+        }
+        HIPCHECK(ctx, hipMalloc((void**)&pb.d, M * 2 * N * 4));
+        pb.cap = M;
+        it = ctx->pack.find(s);
+    }
+    uint32_t* d_s = it->second.d;
+    PackMmArgs m{};
+    m.tlwe = (const uint32_t*)d_tlwe; m.kmat = pk->d_kmat; m.s = d_s;
+    m.M = (int32_t)M; m.n = ctx->p.n; m.n16 = pk->n16; m.colgroups = pk->colgroups;
+    m.mgroups = (int32_t)((M + 64 * PACK_WAVES - 1) / (64 * PACK_WAVES));
+    hipLaunchKernelGGL((k_pack_ks_mm<8, 2>), dim3((unsigned)(m.colgroups * m.mgroups)), dim3(64 * PACK_WAVES), 0, s, m);
+    HIPCHECK(ctx, hipGetLastError());
+    ctx->launches++;
+    PackCombineArgs c{};
+    c.s = d_s; c.tlwe = (const uint32_t*)d_tlwe; c.out = (uint32_t*)d_out;
+    c.P = P; c.n = ctx->p.n; c.rep = rep;
+    for (int32_t p0 = 0; p0 < P; p0 += PACK_POS_MAX) {
+        c.p0 = p0; c.np = P - p0 < PACK_POS_MAX ? P - p0 : PACK_POS_MAX; c.accumulate = p0 ? 1 : 0;
+        std::memcpy(c.pos, shift.data() + p0, (size_t)c.np * 4);
+        if (ctx->logn == 11) launch_combine_t<11>(c, count, s); else launch_combine_t<10>(c, count, s);
+        HIPCHECK(ctx, hipGetLastError());
+        ctx->launches++;
+    }
+    return 0;
+}
+
+}  // namespace
+
+namespace rtfhe_host {
+
+void packing_key_release(rtfhe_packing_key* k) {
+    (void)hipSetDevice(k->ctx->device);
+    if (k->d_kmat) (void)hipFree(k->d_kmat);
+    k->d_kmat = nullptr;
+}
+
+}  // namespace rtfhe_host
+
+extern "C" {
+
+int rtfhe_packing_key_create(rtfhe_ctx* ctx, const uint32_t* pk, rtfhe_packing_key** out) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!pk || !out) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_packing_key_create: null argument");
+    *out = nullptr;
+    if (ctx->p.ks_t != 8 || ctx->p.ks_basebit != 2)
+        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_packing_key_create: the packing key switch needs ks_t = 8 and ks_basebit = 2");
+    if (int rc = use(ctx)) return rc;
+    const size_t n = (size_t)ctx->p.n, N = (size_t)ctx->p.N, rows = n * 8 * 3, raw_bytes = rows * 2 * N * 4;
+    rtfhe_packing_key* k = new rtfhe_packing_key();
+    k->ctx = ctx;
+    k->n16 = (int32_t)((n + 15) / 16 * 16);
+    k->colgroups = (int32_t)(2 * N / 16);
+    const size_t kmat_v4 = (size_t)k->colgroups * (k->n16 / 2) * 4 * 64;
+    uint32_t* d_raw = nullptr;
+    int rc = 0;
+    if (hipMalloc((void**)&d_raw, raw_bytes) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_packing_key_create: hipMalloc (raw rows)");
+    if (!rc && hipMalloc((void**)&k->d_kmat, kmat_v4 * sizeof(uint4)) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_packing_key_create: hipMalloc (key matrix)");
+    if (!rc && hipMemcpy(d_raw, pk, raw_bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_packing_key_create: hipMemcpy");
+    if (!rc) {
+        PkMatArgs a{d_raw, k->d_kmat, ctx->p.n, k->n16, k->colgroups};
+        hipLaunchKernelGGL((k_pkmat_build<8, 2>), dim3(4096), dim3(256), 0, ctx->stream, a);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_packing_key_create: k_pkmat_build");
+        else ctx->launches++;
+    }
+    if (d_raw) (void)hipFree(d_raw);      // the operand form is all the calls read
+    if (rc) {
+        (void)hipGetLastError();
+        packing_key_release(k);
+        delete k;
+        return rc;
+    }
+    ctx->pack_keys.push_back(k);
+    *out = k;
+    return 0;
+}
+
+void rtfhe_packing_key_destroy(rtfhe_packing_key* k) {
+    if (!k) return;
+    if (rtfhe_ctx* ctx = k->ctx) {     // still attached (a context destroyed first has already freed the matrix and detached us)
+        auto& v = ctx->pack_keys;
+        for (size_t i = 0; i < v.size(); i++) if (v[i] == k) { v.erase(v.begin() + i); break; }
+        (void)hipSetDevice(ctx->device);
+        (void)hipDeviceSynchronize();      // a pack in flight may still read the matrix
+        packing_key_release(k);
+    }
+    delete k;
+}
+
+int rtfhe_pack_batch_dev(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const void* d_tlwe, int32_t P, const int32_t* pos, int32_t rep, void* d_out, size_t count,
+                         void* stream) {
+    std::vector<int32_t> shift;
+    if (int rc = pack_ready(ctx, pk, d_tlwe, P, pos, rep, d_out, count, shift)) return rc;
+    if (int rc = use(ctx)) return rc;
+    if (!gpu_accessible(ctx, d_out) || !gpu_accessible(ctx, d_tlwe))
+        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_pack_batch_dev needs device pointers (got memory the GPU cannot address)");
+    return launch_pack(ctx, pk, d_tlwe, P, shift, rep, d_out, count, (hipStream_t)stream);
+}
+
+// host buffers: the samples ride in d_a, the result comes back through d_c
+int rtfhe_pack_batch(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const uint32_t* tlwe, int32_t P, const int32_t* pos, int32_t rep, uint32_t* out, size_t count) {
+    std::vector<int32_t> shift;
+    if (int rc = pack_ready(ctx, pk, tlwe, P, pos, rep, out, count, shift)) return rc;
+    if (int rc = use(ctx)) return rc;
+    if (count == 0) return 0;
+    const size_t in_bytes = count * (size_t)P * ((size_t)ctx->p.n + 1) * 4, out_bytes = count * 2 * (size_t)ctx->p.N * 4;
+    if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, in_bytes)) return rc;
+    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
+    if (int rc = copy_in(ctx, ctx->d_a, tlwe, in_bytes, 0)) return rc;
+    if (int rc = launch_pack(ctx, pk, ctx->d_a, P, shift, rep, ctx->d_c, count, ctx->stream)) return rc;
+    return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+}
+
+int rtfhe_lut_update_dev(rtfhe_lut* lut, const void* d_trlwe, int32_t first, int32_t n, void* stream) {
+    if (!lut) return fail(nullptr, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
+    rtfhe_ctx* ctx = lut->ctx;
+    if (!ctx) return fail(nullptr, RTFHE_ERR_STATE, "the context of the table has been destroyed");
+    if (!d_trlwe) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (!lut->encrypted) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_update_dev rewrites the rows of an encrypted table (rtfhe_lut_create_encrypted); this one is plain");
+    if (!ctx->peers.empty()) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_update_dev: a multi-device context holds one copy of the table per device; not supported");
+    if (first < 0 || n < 0 || (long long)first + n > lut->n_lut)
+        return fail(ctx, RTFHE_ERR_INVALID, "rows [" + std::to_string(first) + ", " + std::to_string((long long)first + n) + ") are outside the table's [0, " +
+                                            std::to_string(lut->n_lut) + ")");
+    if (int rc = use(ctx)) return rc;
+    if (!gpu_accessible(ctx, d_trlwe)) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_update_dev needs a device pointer (got memory the GPU cannot address)");
+    if (n == 0) return 0;
+    const size_t row = 2 * (size_t)ctx->p.N;
+    HIPCHECK(ctx, hipMemcpyAsync(lut->d_tv[0] + (size_t)first * row, d_trlwe, (size_t)n * row * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+}  // extern "C"

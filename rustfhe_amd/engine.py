@@ -385,6 +385,38 @@ class Engine:
         from .cmux_net import CmuxCircuit
         return CmuxCircuit(self, netlist, sel, lut, d_out, count, d_sel_idx, d_row0)
 
+    # ---- packing key switch (include/rtfhe.h: rtfhe_packing_key_create, rtfhe_pack_batch[_dev], rtfhe_lut_update_dev) --------------------------
+    def packing_key(self, pk):
+        """Uploads a packing key u32[n][t][base-1][2][N] (rustfhe_amd.packing_keygen) to the primary device in the operand order of the matrix
+        pipe; a PackingKey handle, closed by close() or a with block."""
+        return PackingKey(self, pk)
+
+    def _pos_arg(self, pos, P):
+        if pos is None:
+            return None
+        pos = _np(pos, np.int32).reshape(-1)
+        assert pos.size == int(P), "one position per sample"
+        return pos
+
+    def pack_batch(self, pk, tlwe, P, rep=1, pos=None):
+        """Packs lvl0 ciphertexts u32[count][P][n+1] into TRLWE rows u32[count][2][N] (b then a): output g is the sum over p of
+        X^pos[p] * (1 + X + .. + X^(rep-1)) * key_switch(tlwe[g][p]), i.e. the phase of tlwe[g][p] on coefficients pos[p] .. pos[p] + rep - 1
+        (negacyclic).  pos None: p * rep.  rustfhe_amd.lut_pack_layout gives the (pos, rep) of a PBS table.  Arguments are checked here: a bad
+        one raises RtfheError before anything runs."""
+        tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)
+        P = int(P)
+        count = tlwe.shape[0] // P if P > 0 else tlwe.shape[0]
+        assert P <= 0 or tlwe.shape[0] == count * P, "P ciphertexts per output"
+        out = np.empty((count, 2, self.p.N), np.uint32)
+        self._ck(self.L.rtfhe_pack_batch(self.h, pk.h, _ptr(tlwe), P, _ptr(self._pos_arg(pos, P)), int(rep), _ptr(out), count))
+        return out
+
+    def pack_batch_dev(self, pk, d_tlwe, P, d_out, count, rep=1, pos=None, stream=None):
+        """... on device buffers (d_tlwe: [count][P][n+1] words, d_out: [count][2][N] words; pos stays a host array, copied at enqueue time),
+        asynchronous on `stream`.  Inside a stream capture an eager call of at least count * P samples must have run on the stream first."""
+        self._ck(self.L.rtfhe_pack_batch_dev(self.h, pk.h, self._dev(d_tlwe), int(P), _ptr(self._pos_arg(pos, P)), int(rep), self._dev(d_out), count,
+                                             C.c_void_p(stream) if stream else None))
+
     # ---- stage level ------------------------------------------------------------------------
     def blind_rotate_batch(self, tlwe, steps=None):
         tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)
@@ -457,6 +489,14 @@ class Lut:
         engine._ck(create(engine.h, _ptr(tv), self.n_lut, C.byref(h)))
         self.h = h
 
+    def update_dev(self, d_trlwe, first=0, n=1, stream=None):
+        """Rewrites rows [first, first + n) of an encrypted table in place from device memory u32[n][2][N] (rtfhe_lut_update_dev), e.g. the
+        output of Engine.pack_batch_dev; a copy ordered on `stream`.  Refused for a plain table, a bad range and a multi-device Engine."""
+        e = self.engine
+        rc = e.L.rtfhe_lut_update_dev(self.h, e._dev(d_trlwe), int(first), int(n), C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise RtfheError(rc, (e.L.rtfhe_last_error(e.h if e.h else None) or b"").decode())
+
     def close(self):
         if getattr(self, "h", None):
             self.engine.L.rtfhe_lut_destroy(self.h)
@@ -498,6 +538,37 @@ class Selectors:
     def close(self):
         if getattr(self, "h", None):
             self.engine.L.rtfhe_trgsw_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PackingKey:
+    """A packing key on an Engine's primary device (rtfhe_packing_key), kept as signed byte limbs in the matrix pipe's operand order.  Closing
+    it frees the device copy; one whose Engine was closed first only frees its handle."""
+
+    def __init__(self, engine, pk):
+        p = engine.p
+        pk = _np(pk, np.uint32).reshape(-1)
+        assert pk.size == packing_key_words(p), "pk must be u32[n][t][base-1][2][N]"
+        self.engine = engine
+        h = C.c_void_p()
+        engine._ck(engine.L.rtfhe_packing_key_create(engine.h, _ptr(pk), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.engine.L.rtfhe_packing_key_destroy(self.h)
             self.h = None
 
     def __enter__(self):
@@ -618,6 +689,28 @@ def keygen(params, seed=None, want_bk=True, want_ksk=True):
     if rc != 0:
         raise RtfheError(rc, "rtfhe_keygen failed")
     return key0, key1, bk, ksk
+
+
+def packing_key_words(params):
+    return params.n * params.ks_t * ((1 << params.ks_basebit) - 1) * 2 * params.N
+
+
+def packing_keygen(params, key0, key1, seed=None):
+    """The packing key of the lvl0 key key0 under the lvl1 key key1 (include/rtfhe.h: rtfhe_packing_keygen): u32[n][t][base-1][2][N], row
+    (i, j, d) a TRLWE of the constant (d+1) key0[i] / 2^(basebit (j+1)) with alpha = 2^-25 (125 MB at the default parameters).  seed None
+    (production): OS CSPRNG; an integer seed = TEST-ONLY deterministic generation.  Non-binary keys and ks parameters other than (8, 2) are
+    refused."""
+    L = _ffi.load()
+    key0, key1 = _np(key0, np.int32).reshape(-1), _np(key1, np.int32).reshape(-1)
+    assert key0.size == params.n and key1.size == params.N
+    pk = np.empty((params.n, params.ks_t, (1 << params.ks_basebit) - 1, 2, params.N), np.uint32)
+    if seed is None:
+        rc = L.rtfhe_packing_keygen(C.byref(params), _ptr(key0), _ptr(key1), _ptr(pk))
+    else:
+        rc = L.rtfhe_packing_keygen_deterministic(C.byref(params), seed, _ptr(key0), _ptr(key1), _ptr(pk))
+    if rc != 0:
+        raise RtfheError(rc, "rtfhe_packing_keygen failed (non-binary key, or ks parameters other than t = 8, basebit = 2)")
+    return pk
 
 
 def encrypt_bits(params, key0, bits, seed=None):

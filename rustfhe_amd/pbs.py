@@ -66,6 +66,18 @@ def lut_polynomial(f, N, msg_bits, out_bits=None, raw=False):
     return tv.astype(np.uint32)
 
 
+def lut_pack_layout(N, msg_bits):
+    """(pos, rep) with which Engine.pack_batch turns the 2^msg_bits ciphertexts of enc_out(f(e)), e = 0 .. 2^msg_bits - 1, into an encryption
+    of lut_polynomial(f, N, msg_bits): rep = B = N / 2^msg_bits and pos[e] = (e B - B/2) mod 2N, int32.  Box e of the module docstring is
+    [e B - B/2, e B + B/2); entry 0's lower half-box starts at 2N - B/2 = X^N * X^(N - B/2), i.e. on the top half-box with the sign flipped."""
+    p = msg_bits
+    if p < 1 or (1 << p) > N // 2:
+        raise ValueError("a box must hold at least two coefficients: 1 <= msg_bits <= log2(N) - 1")
+    B = N >> p
+    pos = (np.arange(1 << p, dtype=np.int64) * B - B // 2) % (2 * N)
+    return pos.astype(np.int32), B
+
+
 def many_lut_polynomial(fs, N, msg_bits, out_bits=None, raw=False):
     """The test polynomial (u32[N]) of a many-LUT PBS (Engine.pbs_many_batch with n_out = len(fs)): theta = len(fs) functions of the same
     message, interleaved.  Each f in fs is what lut_polynomial takes (a callable or 2^msg_bits values); out_bits and raw apply to all of them.
