@@ -47,6 +47,8 @@ pub const RTFHE_ANDNY: c_int = 6;
 pub const RTFHE_BACKEND_FFT64_MIRROR: c_int = 0;
 pub const RTFHE_BACKEND_NTT_EXACT: c_int = 1;
 pub const RTFHE_BACKEND_FFT_SPLIT_EXACT: c_int = 2;
+pub const RTFHE_DECOMP_REFERENCE: c_int = 0;
+pub const RTFHE_DECOMP_ROUNDED: c_int = 1;
 
 pub const RTFHE_OK: c_int = 0;
 pub const RTFHE_ERR_INVALID: c_int = -1;
@@ -72,6 +74,8 @@ extern "C" {
     pub fn rtfhe_device_count() -> c_int;
     pub fn rtfhe_set_backend(ctx: *mut rtfhe_ctx, backend: c_int) -> c_int;
     pub fn rtfhe_get_backend(ctx: *const rtfhe_ctx) -> c_int;
+    pub fn rtfhe_set_decomposition(ctx: *mut rtfhe_ctx, mode: c_int) -> c_int;
+    pub fn rtfhe_get_decomposition(ctx: *const rtfhe_ctx) -> c_int;
     pub fn rtfhe_get_twiddles(ctx: *const rtfhe_ctx, ifft_table: *mut f64, fft_table: *mut f64) -> c_int;
     pub fn rtfhe_set_twiddles(ctx: *mut rtfhe_ctx, ifft_table: *const f64, fft_table: *const f64) -> c_int;
     pub fn rtfhe_ctx_params(ctx: *const rtfhe_ctx, p: *mut rtfhe_params) -> c_int;

@@ -313,6 +313,39 @@ int rtfhe_pbs_many_batch_dev(rtfhe_ctx *ctx, const rtfhe_lut *lut, int32_t n_out
  * so inside a stream capture rtfhe_pbs_batch_dev with an encrypted table follows rtfhe_pbs_many_batch_dev's capture rule: an eager call of
  * at least `count` gates (and, for the many entry, at least this n_out) must have run on that stream first (else RTFHE_ERR_STATE). */
 int rtfhe_lut_create_encrypted(rtfhe_ctx *ctx, const uint32_t *trlwe /* [n_lut][2][N] */, int32_t n_lut, rtfhe_lut **out);
+/* ---- rounded gadget decomposition: 4-bit messages through one PBS at N = 1024 ----
+ * In every CMUX step each word x of the difference polynomials X^{abar_i} acc - acc becomes
+ *
+ *     u = ((x + MA) mod 2^32) ^ MX ;   digit j = the signed bgbit-wide field of u at bit 32 - bgbit (j+1),   j = 0 .. l-1
+ *
+ *   RTFHE_DECOMP_REFERENCE   MA = MX = make_decomp_mask(l, bgbit) (utils/src/math.rs:542-560), the reference's constants: 0x02084000 for
+ *                            l = 3, bgbit = 6.  With them x - Sum_j d_j 2^(32 - bgbit (j+1)) lies in [-2^-17, 2^-18] of the torus with mean
+ *                            -2^-19 at every coefficient; multiplied by the key that mean is most of a bootstrapped ciphertext's noise.
+ *   RTFHE_DECOMP_ROUNDED     MX = Sum_{j=1..l} 2^(32 - bgbit j + bgbit - 1)  and  MA = MX + 2^(32 - l bgbit - 1):  0x82080000 and 0x82082000
+ *                            for l = 3, bgbit = 6.  The digits are balanced (in [-2^(bgbit-1), 2^(bgbit-1) - 1]) and x is rounded to the
+ *                            nearest multiple of 2^(32 - l bgbit): the error lies in [-2^-19, 2^-19) with mean ~0.
+ *
+ * Nothing else changes: not the mod switch, the transforms, the accumulation order, the truncation, the extract or the key switch, and the
+ * bootstrapping key is the same.  A rounded-mode output is therefore NOT the reference's word; it decrypts to the same message with about a
+ * fifth of the noise at N = 1024 (measured: DESIGN.md 5.12), which moves the PBS family from 2-bit to 4-bit messages there.
+ *
+ * The mode is a property of the context, RTFHE_DECOMP_REFERENCE until set, and is read by these calls only:
+ *   rtfhe_pbs_batch[_dev], rtfhe_pbs_many_batch[_dev]   with plain and encrypted tables, when the call is made;
+ *   rtfhe_lut_circuit_create                            which RECORDS the mode in force at creation: the circuit replays in that mode
+ *                                                       whatever the context is set to later.
+ * Gates, MUX, rtfhe_bootstrap_batch[_dev], gate circuits, rtfhe_blind_rotate_batch, rtfhe_external_product_batch and the leveled entry points
+ * (CMUX tree, TRGSW rotation, CMUX netlists, packing) always use the reference decomposition: the gate path stays bit-identical to the
+ * reference in either mode.  On a multi-device context the setter sets every entry.  Any other mode value: RTFHE_ERR_INVALID, the mode in force
+ * stays.  The setter works on every backend; on the exact backends the PBS calls keep failing with RTFHE_ERR_INVALID as before.
+ * In rounded mode rtfhe_pbs_batch[_dev] with a plain table runs as rtfhe_pbs_many_batch[_dev] with n_out = 1, as an encrypted table already
+ * does; so inside a stream capture rtfhe_pbs_batch_dev in rounded mode follows rtfhe_pbs_many_batch_dev's capture rule: an eager call of at
+ * least `count` gates must have run on that stream first (else RTFHE_ERR_STATE). */
+typedef enum {
+    RTFHE_DECOMP_REFERENCE = 0,
+    RTFHE_DECOMP_ROUNDED = 1
+} rtfhe_decomposition;
+int rtfhe_set_decomposition(rtfhe_ctx *ctx, int mode);
+int rtfhe_get_decomposition(const rtfhe_ctx *ctx);      /* the mode in force, or RTFHE_ERR_INVALID for a NULL context */
 /* ---- LUT circuits: netlists of many-LUT bootstraps, recorded once and replayed as one submission ----
  * A LUT circuit works on the wire table d_wires, u32[num_wires][n+1] lvl0 ciphertexts in device memory, as a gate circuit does.  It is a
  * sequence of waves: wave w holds nodes wave_offsets[w] .. wave_offsets[w+1] (host array, num_waves + 1 entries, strictly increasing from

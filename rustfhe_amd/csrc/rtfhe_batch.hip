@@ -322,7 +322,7 @@ int rtfhe_pbs_batch(rtfhe_ctx* ctx, const rtfhe_lut* lut, const int32_t* lut_idx
         for (size_t g = 0; g < count; g++)
             if ((uint32_t)lut_idx[g] >= (uint32_t)lut->n_lut)
                 return fail(ctx, RTFHE_ERR_INVALID, "lut_idx[" + std::to_string(g) + "] = " + std::to_string(lut_idx[g]) + " is outside [0, " + std::to_string(lut->n_lut) + ")");
-    return sharded_host_pbs(ctx, lut, lut_idx, tlwe, out, count, lut->encrypted ? 0 : -1);      // encrypted: the many-LUT path, one output
+    return sharded_host_pbs(ctx, lut, lut_idx, tlwe, out, count, pbs_shift(ctx, lut));      // encrypted or rounded: the many-LUT path, one output
 }
 
 int rtfhe_pbs_batch_dev(rtfhe_ctx* ctx, const rtfhe_lut* lut, const void* d_lut_idx, const void* d_tlwe, void* d_out, size_t count, void* stream) {
@@ -332,7 +332,7 @@ int rtfhe_pbs_batch_dev(rtfhe_ctx* ctx, const rtfhe_lut* lut, const void* d_lut_
     if (!gpu_accessible(ctx, d_tlwe) || !gpu_accessible(ctx, d_out) || (d_lut_idx && !gpu_accessible(ctx, d_lut_idx)))
         return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_pbs_batch_dev needs device pointers (got memory the GPU cannot address)");
     if (count > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "count too large");
-    if (lut->encrypted) {      // the many-LUT path with one output (MODE_EXTRACT, then the batch key switch): its capture rule applies
+    if (pbs_shift(ctx, lut) == 0) {      // the many-LUT path with one output (MODE_EXTRACT, then the batch key switch): its capture rule applies
         if (!ctx->peers.empty())
             return sharded_dev_batch(ctx, RTFHE_COPY, nullptr, d_tlwe, nullptr, d_out, count, (hipStream_t)stream, lut, (const int32_t*)d_lut_idx, 0);
         return launch_pbs_many(ctx, lut_on(lut, 0, (const int32_t*)d_lut_idx, 0), d_tlwe, d_out, count, (hipStream_t)stream);

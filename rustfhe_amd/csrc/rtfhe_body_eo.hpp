@@ -1,10 +1,10 @@
 // rtfhe_body_eo.hpp -- the body of k_bootstrap_eo and of its programmable-bootstrap twin k_pbs_eo (rtfhe_kernels_eo.hpp), included inside the braces of both
-// kernels: they declare `ea` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany / TvEnc, rtfhe_kernels.hpp).
+// kernels: they declare `ea` (the family's arguments) and `tvs` (where the accumulator starts and how the step decomposes: TvGate / TvLut / TvMany / TvEnc / TvManyR / TvEncR, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap_eo compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included four times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables).
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included five times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables; k_pbs_round_*: both with the rounded decomposition).
     constexpr int LOGN = 11, N = 2048, R = 8, NT = 128 * GATES;
     typedef Geo<10> G;   // geometry of a parity's 512-point sub-network
-    constexpr uint32_t M = decomp_mask(L, BGBIT);
+    constexpr uint32_t MA = decomp_add(L, BGBIT, decltype(tvs)::ROUNDED), MX = decomp_xor(L, BGBIT, decltype(tvs)::ROUNDED);
     static_assert(L == 3, "three digit rows of a polynomial are transformed side by side");
     const BootstrapArgs& a = ea.b;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -211,14 +211,14 @@
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int k = 0; k < 2 * R; k++) {
-                    mo[k] = M - mo[k];
-                    asm("" : "+v"(mo[k]));      // (keeps "(M - own) - sign" from being re-associated into one more bit-field extract and an or)
+                    mo[k] = MA - mo[k];
+                    asm("" : "+v"(mo[k]));      // (keeps "(MA - own) - sign" from being re-associated into one more bit-field extract and an or)
                 }
 #pragma unroll
                 for (int k = 0; k < 2 * R; k++) {
-                    uint32_t x;                                                     // (+-v - own) + M = (v ^ sign) + ((M - own) - sign)
+                    uint32_t x;                                                     // (+-v - own) + MA = (v ^ sign) + ((MA - own) - sign)
                     asm("v_xad_u32 %0, %1, %2, %3" : "=v"(x) : "v"(v[k]), "v"(sg[k]), "v"(mo[k] - sg[k]));
-                    const uint32_t u = x ^ M;
+                    const uint32_t u = x ^ MX;
                     if (k < R) ure[k] = u; else uim[k - R] = u;
                 }
             }

@@ -1,11 +1,11 @@
 // rtfhe_body_pair.hpp -- the body of k_bootstrap_pair and of its programmable-bootstrap twin k_pbs_pair (rtfhe_kernels_pair.hpp), included inside the braces of both
-// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany / TvEnc, rtfhe_kernels.hpp).
+// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts and how the step decomposes: TvGate / TvLut / TvMany / TvEnc / TvManyR / TvEncR, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap_pair compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included four times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables).
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included five times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables; k_pbs_round_*: both with the rounded decomposition).
     constexpr int LOGN = 10;
     typedef Geo<LOGN> G;
     constexpr int N = G::N, P = G::P, R = G::R, NT = 128 * GATES;
-    constexpr uint32_t M = decomp_mask(L, BGBIT);
+    constexpr uint32_t MA = decomp_add(L, BGBIT, decltype(tvs)::ROUNDED), MX = decomp_xor(L, BGBIT, decltype(tvs)::ROUNDED);
     static_assert(L == 3, "three rows per side are held in registers");
     // The two waves of a gate meet through their own arrival flags in LDS at every workgroup size, never through the workgroup barrier (round 6).
     // Round 3 had measured the barrier and a busy-polling pair_sync equal at four gates per workgroup (6.74 vs 6.76 ms); what the split-FFT
@@ -138,7 +138,7 @@
 #pragma unroll
         for (int mm = 0; mm < 2 * R; mm++) {
             const int c = ln + 64 * mm;
-            u[mm] = ((rotated_coef<LOGN>(poly, c, r) - own[mm]) + M) ^ M;
+            u[mm] = ((rotated_coef<LOGN>(poly, c, r) - own[mm]) + MA) ^ MX;
         }
         PAIR_STAMP(0);
         double xr[L][R], xi[L][R];

@@ -1,10 +1,10 @@
 // rtfhe_body_pair4.hpp -- the body of k_bootstrap_pair4 and of its programmable-bootstrap twin k_pbs_pair4 (rtfhe_kernels_pair4.hpp), included inside the braces of both
-// kernels: they declare `pa` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany / TvEnc, rtfhe_kernels.hpp).
+// kernels: they declare `pa` (the family's arguments) and `tvs` (where the accumulator starts and how the step decomposes: TvGate / TvLut / TvMany / TvEnc / TvManyR / TvEncR, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap_pair4 compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included four times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables).
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included five times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables; k_pbs_round_*: both with the rounded decomposition).
     constexpr int LOGN = 10, N = 1024, P = 512, R = 4;
     typedef Geo<LOGN> G;
-    constexpr uint32_t M = decomp_mask(L, BGBIT);
+    constexpr uint32_t MA = decomp_add(L, BGBIT, decltype(tvs)::ROUNDED), MX = decomp_xor(L, BGBIT, decltype(tvs)::ROUNDED);
     static_assert(L == 3, "slots P / Q / R hold three digit rows each");
     const BootstrapArgs& a = pa.b;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -162,8 +162,8 @@
                 const uint32_t v1 = *reinterpret_cast<const uint32_t*>(pb + (t1 & (4 * N - 4)));
                 const uint32_t sg0 = (uint32_t)((int32_t)((uint32_t)t0 << (31 - LOGN - 2)) >> 31);     // all ones iff bit LOGN of (i - r) is set
                 const uint32_t sg1 = (uint32_t)((int32_t)((uint32_t)t1 << (31 - LOGN - 2)) >> 31);
-                ure[m] = ((((v0 ^ sg0) - sg0) - poly[c0]) + M) ^ M;
-                uim[m] = ((((v1 ^ sg1) - sg1) - poly[c1]) + M) ^ M;
+                ure[m] = ((((v0 ^ sg0) - sg0) - poly[c0]) + MA) ^ MX;
+                uim[m] = ((((v1 ^ sg1) - sg1) - poly[c1]) + MA) ^ MX;
             }
         }
         double yr[L][R], yi[L][R];

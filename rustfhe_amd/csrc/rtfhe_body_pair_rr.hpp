@@ -1,12 +1,12 @@
 // rtfhe_body_pair_rr.hpp -- the body of k_bootstrap_pair_rr and of its programmable-bootstrap twin k_pbs_pair_rr (rtfhe_kernels_pair_rr.hpp), included inside the braces of both
-// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany / TvEnc, rtfhe_kernels.hpp).
+// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts and how the step decomposes: TvGate / TvLut / TvMany / TvEnc / TvManyR / TvEncR, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap_pair_rr compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included four times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables).
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included five times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables; k_pbs_round_*: both with the rounded decomposition).
     typedef PairRrLds S;
     constexpr int LOGN = 10, SLOTS = S::SLOTS;
     typedef Geo<LOGN> G;
     constexpr int N = G::N, P = G::P, R = G::R, NT = 128 * SLOTS;
-    constexpr uint32_t M = decomp_mask(L, BGBIT);
+    constexpr uint32_t MA = decomp_add(L, BGBIT, decltype(tvs)::ROUNDED), MX = decomp_xor(L, BGBIT, decltype(tvs)::ROUNDED);
     static_assert(L == 3, "three rows per side are held in registers");
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -115,7 +115,7 @@
         for (int mm = 0; mm < 2 * R; mm++) {
             const int c = ln + 64 * mm;
             own[mm] = poly[c];
-            u[mm] = ((rotated_coef<LOGN>(poly, c, r) - own[mm]) + M) ^ M;
+            u[mm] = ((rotated_coef<LOGN>(poly, c, r) - own[mm]) + MA) ^ MX;
         }
         double xr[L][R], xi[L][R];
 #pragma unroll

@@ -1,7 +1,7 @@
 // rtfhe_body_wave.hpp -- the body of k_bootstrap and of its programmable-bootstrap twin k_pbs (rtfhe_kernels.hpp), included inside the braces of both
-// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany / TvEnc, rtfhe_kernels.hpp).
+// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts and how the step decomposes: TvGate / TvLut / TvMany / TvEnc / TvManyR / TvEncR, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included four times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables).
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included five times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables; k_pbs_round_*: both with the rounded decomposition).
     typedef Geo<LOGN> G;
     constexpr int N = G::N, R = G::R;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -55,7 +55,7 @@
 #pragma unroll 1
     for (int i = 0; i < a.steps; i++) {
         const int r = __builtin_amdgcn_readfirstlane((int)abar[i]);
-        cmux_step<LOGN, L, BGBIT, true, DUAL>(accbuf, r, a.bk + (size_t)i * trgsw_cplx, twf, twi, twi_big, xbuf, lane);
+        cmux_step<LOGN, L, BGBIT, true, DUAL, decltype(tvs)::ROUNDED>(accbuf, r, a.bk + (size_t)i * trgsw_cplx, twf, twi, twi_big, xbuf, lane);
     }
 
     if (a.mode == MODE_BLIND_ROTATE) {

@@ -1,13 +1,13 @@
 // rtfhe_body_wg.hpp -- the body of k_bootstrap_wg and of its programmable-bootstrap twin k_pbs_wg (rtfhe_kernels_wg.hpp), included inside the braces of both
-// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts: TvGate / TvLut / TvMany / TvEnc, rtfhe_kernels.hpp).
+// kernels: they declare `a` (the family's arguments) and `tvs` (where the accumulator starts and how the step decomposes: TvGate / TvLut / TvMany / TvEnc / TvManyR / TvEncR, rtfhe_kernels.hpp).
 // The body is text, not a __device__ function, so that k_bootstrap_wg compiles to exactly what it did before the twin existed
-// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included four times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables).
+// (a function taking the arguments by reference changes instruction order and scalar registers).  No include guard: included five times (k_pbs_many_*: the many-LUT PBS; k_pbs_enc_*: encrypted tables; k_pbs_round_*: both with the rounded decomposition).
     typedef Geo<LOGN> G;
     typedef WgLds<LOGN, L> S;
     constexpr int N = G::N, P = G::P, R = G::R, NW = S::NW, ROWS = 2 * L;
     static_assert(R == NW, "the MAC phase gives each of the 8 waves one of the R = 8 points a lane holds");
     static_assert(ROWS + 2 == NW, "rows 0..2l-1 start on waves 0..2l-1; the last two rows finish on waves 2l, 2l+1");
-    constexpr uint32_t M = decomp_mask(L, BGBIT);
+    constexpr uint32_t MA = decomp_add(L, BGBIT, decltype(tvs)::ROUNDED), MX = decomp_xor(L, BGBIT, decltype(tvs)::ROUNDED);
     extern __shared__ __align__(16) unsigned char smem[];
     cplx* tw = reinterpret_cast<cplx*>(smem + S::TW);
     uint32_t* accbuf = reinterpret_cast<uint32_t*>(smem + S::ACC);
@@ -90,8 +90,8 @@
                 const int c0 = lane + 64 * m, c1 = c0 + P;
                 const uint32_t d0 = rotated_coef<LOGN>(poly, c0, r) - poly[c0];
                 const uint32_t d1 = rotated_coef<LOGN>(poly, c1, r) - poly[c1];
-                re[m] = (double)decomp_digit((d0 + M) ^ M, BGBIT, jj);
-                im[m] = (double)decomp_digit((d1 + M) ^ M, BGBIT, jj);
+                re[m] = (double)decomp_digit((d0 + MA) ^ MX, BGBIT, jj);
+                im[m] = (double)decomp_digit((d1 + MA) ^ MX, BGBIT, jj);
             }
             // exchange buffer = this row's own (still unwritten) spectrum slot, one 16-byte access per complex value
             fft_forward<LOGN, 2, BOOT_TRIV>(re, im, twf, reinterpret_cast<double*>(spec + (size_t)wave * S::SROW), lane);
@@ -115,8 +115,8 @@
                     const int c0 = 2 * (lane + 64 * m) + (ODD ? 1 : 0), c1 = c0 + P;
                     const uint32_t d0 = rotated_coef<LOGN>(poly, c0, r) - poly[c0];
                     const uint32_t d1 = rotated_coef<LOGN>(poly, c1, r) - poly[c1];
-                    re[m] = (double)decomp_digit((d0 + M) ^ M, BGBIT, jj);
-                    im[m] = (double)decomp_digit((d1 + M) ^ M, BGBIT, jj);
+                    re[m] = (double)decomp_digit((d0 + MA) ^ MX, BGBIT, jj);
+                    im[m] = (double)decomp_digit((d1 + MA) ^ MX, BGBIT, jj);
                 }
                 sub256_forward<ODD, BOOT_TRIV>(re, im, qinv, xc, lane, [](int k) { if (k == 2) __builtin_amdgcn_s_setprio(1); });
 #pragma unroll

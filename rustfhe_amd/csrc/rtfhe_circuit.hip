@@ -240,7 +240,7 @@ int rtfhe_lut_circuit_create(rtfhe_ctx* ctx, const rtfhe_lut* lut, int32_t fan_i
         const LutGatherArgs ga{(const uint32_t*)d_wires, (uint32_t*)d_gather, d_in + (size_t)off * fan_in, d_wt + (size_t)off * fan_in, d_cst + off, cnt,
                                (int32_t)n1, nw};
         rc = launch_lut_gather(ctx, fan_in, vec, ga, ctx->stream);
-        if (!rc) rc = launch_pbs_many(ctx, LutRef{(const uint32_t*)d_tv, lut_idx ? d_lut + off : nullptr, lut->n_lut, shift, lut->encrypted}, d_gather, d_ks, (size_t)cnt,
+        if (!rc) rc = launch_pbs_many(ctx, LutRef{(const uint32_t*)d_tv, lut_idx ? d_lut + off : nullptr, lut->n_lut, shift, lut->encrypted, ctx->decomp == RTFHE_DECOMP_ROUNDED}, d_gather, d_ks, (size_t)cnt,
                                       ctx->stream, false);      // (d_ks is zero: cleared at creation and by every scatter, no memset node)
         const LutScatterArgs sa{(uint32_t*)d_ks, (uint32_t*)d_wires, d_out + out_base[w], cnt * th, (int32_t)n1, nw};
         if (!rc) rc = launch_lut_scatter(ctx, vec, sa, ctx->stream);

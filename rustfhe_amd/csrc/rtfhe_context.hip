@@ -390,6 +390,17 @@ int rtfhe_set_backend(rtfhe_ctx* ctx, int backend) {
 
 int rtfhe_get_backend(const rtfhe_ctx* ctx) { return ctx ? ctx->backend : RTFHE_ERR_INVALID; }
 
+// host state only: read by the PBS entry points when they choose their kernels (rtfhe_batch.hip, rtfhe_circuit.hip)
+int rtfhe_set_decomposition(rtfhe_ctx* ctx, int mode) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (mode != RTFHE_DECOMP_REFERENCE && mode != RTFHE_DECOMP_ROUNDED) return fail(ctx, RTFHE_ERR_INVALID, "unknown decomposition mode");
+    ctx->decomp = mode;
+    for (rtfhe_ctx* peer : ctx->peers) peer->decomp = mode;
+    return 0;
+}
+
+int rtfhe_get_decomposition(const rtfhe_ctx* ctx) { return ctx ? ctx->decomp : RTFHE_ERR_INVALID; }
+
 int rtfhe_ctx_params(const rtfhe_ctx* ctx, rtfhe_params* p) {
     if (!ctx || !p) return fail(nullptr, RTFHE_ERR_INVALID, "null argument");
     *p = ctx->p;

@@ -594,7 +594,23 @@ __host__ __device__ constexpr uint32_t decomp_mask(int l, int bits) {
     return u;
 }
 
-// digit j of the pre-masked word u = (x + M) ^ M, sign-extended from `bits` (utils/src/math.rs:314-322):
+// The two constants of the decomposition's pre-masking u = ((x + MA) mod 2^32) ^ MX (include/rtfhe.h: rtfhe_set_decomposition).  Reference:
+// both are make_decomp_mask above.  Rounded: MX sets the top bit of every digit field (the xor then turns the field of x + MA, an unsigned
+// digit plus half the base, into the balanced digit in two's complement) and MA adds to it half a unit of the last digit, which rounds to nearest.
+__host__ __device__ constexpr uint32_t decomp_xor(int l, int bits, bool rounded) {
+    if (!rounded) return decomp_mask(l, bits);
+    uint32_t u = 0;
+    for (int j = 1; j <= l; j++) u += 1u << (32 - bits * j + bits - 1);
+    return u;
+}
+__host__ __device__ constexpr uint32_t decomp_add(int l, int bits, bool rounded) {
+    if (!rounded) return decomp_mask(l, bits);
+    return decomp_xor(l, bits, true) + (32 - l * bits != 0 ? 1u << (32 - l * bits - 1) : 0u);
+}
+static_assert(decomp_xor(3, 6, true) == 0x82080000u && decomp_add(3, 6, true) == 0x82082000u, "rounded decomposition, l = 3, bgbit = 6");
+static_assert(decomp_xor(3, 6, false) == 0x02084000u && decomp_add(3, 6, false) == 0x02084000u, "reference decomposition, l = 3, bgbit = 6");
+
+// digit j of the pre-masked word u = (x + MA) ^ MX (reference: MA = MX = M), sign-extended from `bits` (utils/src/math.rs:314-322):
 // (v & half) * 0xfffffffe + v  ==  v - 2 (v & half)  ==  the two's-complement value of the `bits`-wide field
 __device__ __forceinline__ int32_t decomp_digit(uint32_t u, int bits, int j) {
     return __builtin_amdgcn_sbfe((int32_t)u, (uint32_t)(32 - bits * (j + 1)), (uint32_t)bits);

@@ -16,16 +16,18 @@ namespace {
 // One launch of a kernel family: the gate kernel (k_bootstrap_*) or, for a programmable bootstrap (lut.tv set), its twin (k_pbs_*) with the
 // family's own arguments wrapped in LutArgs.  The twins share shapes, LDS and key layouts, so every choice below is made once for both.
 // A many-LUT PBS (lut.shift >= 0) takes the family's third kernel (k_pbs_many_*), in MODE_EXTRACT, and one with an encrypted table (lut.enc)
-// the fourth (k_pbs_enc_*), with the same arguments.
-template <typename A, typename KG, typename KP, typename KM, typename KE>
-int launch_twin(rtfhe_ctx* ctx, KG kg, KP kp, KM km, KE ke, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A& a, const LutRef& lut) {
+// the fourth (k_pbs_enc_*), with the same arguments.  In rounded mode (lut.rounded) those two are replaced by the family's k_pbs_round_* pair
+// (kmr: plain tables, ker: encrypted), again with the same arguments.
+template <typename A, typename KG, typename KP, typename KM>
+int launch_twin(rtfhe_ctx* ctx, KG kg, KP kp, KM km, KM ke, KM kmr, KM ker, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A& a, const LutRef& lut) {
     if (lut.tv && lut.enc && lut.shift < 0) return fail(ctx, RTFHE_ERR_STATE, "an encrypted table runs on the many-LUT path only (launch_pbs_many)");
+    if (lut.tv && lut.rounded && lut.shift < 0) return fail(ctx, RTFHE_ERR_STATE, "the rounded decomposition runs on the many-LUT path only (launch_pbs_many)");
     if (lut.tv && lut.shift >= 0) {
-        if (int rc = lut.enc ? allow_lds(ctx, ke, lds) : allow_lds(ctx, km, lds)) return rc;
+        const KM k = lut.rounded ? (lut.enc ? ker : kmr) : (lut.enc ? ke : km);
+        if (int rc = allow_lds(ctx, k, lds)) return rc;
         ManyArgs<A> p{};
         p.base = a; p.tv = lut.tv; p.tv_idx = lut.idx; p.n_tv = lut.n_tv; p.t = lut.shift;
-        if (lut.enc) hipLaunchKernelGGL(ke, grid, block, lds, s, p);
-        else hipLaunchKernelGGL(km, grid, block, lds, s, p);
+        hipLaunchKernelGGL(k, grid, block, lds, s, p);
     } else if (lut.tv) {
         if (int rc = allow_lds(ctx, kp, lds)) return rc;
         const LutArgs<A> p{a, lut.tv, lut.idx, lut.n_tv};
@@ -43,16 +45,16 @@ template <int LOGN, int W>
 int launch_bootstrap_w(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
     const size_t lds = bootstrap_lds_bytes<LOGN>(W, a.npad, bootstrap_dual_xbuf(LOGN, W));
     const int grid = (a.count + W - 1) / W;
-    return launch_twin(ctx, k_bootstrap<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs_many<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs_enc<LOGN, 3, 6, 8, 2, KSQ, W>, dim3(grid), dim3(64 * W), lds, s, a, lut);
+    return launch_twin(ctx, k_bootstrap<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs_many<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs_enc<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs_round<LOGN, 3, 6, 8, 2, KSQ, W, false>, k_pbs_round<LOGN, 3, 6, 8, 2, KSQ, W, true>, dim3(grid), dim3(64 * W), lds, s, a, lut);
 }
 
 int launch_bootstrap_wg10(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
-    return launch_twin(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_many_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_enc_wg<10, 3, 6, 8, 2, KSQ>, dim3(a.count), dim3(512), WgLds<10, 3>::bytes(a.npad), s, a, lut);
+    return launch_twin(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_many_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_enc_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_round_wg<10, 3, 6, 8, 2, KSQ, false>, k_pbs_round_wg<10, 3, 6, 8, 2, KSQ, true>, dim3(a.count), dim3(512), WgLds<10, 3>::bytes(a.npad), s, a, lut);
 }
 
 template <int GATES>
 int launch_bootstrap_pair10_g(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
-    return launch_twin(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_many_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, GATES>, dim3((a.count + GATES - 1) / GATES), dim3(128 * GATES),
+    return launch_twin(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_many_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_round_pair<3, 6, 8, 2, KSQ, GATES, false>, k_pbs_round_pair<3, 6, 8, 2, KSQ, GATES, true>, dim3((a.count + GATES - 1) / GATES), dim3(128 * GATES),
                        PairLds::bytes(GATES, a.npad), s, a, lut);
 }
 int launch_bootstrap_pair10(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) { return launch_bootstrap_pair10_g<4>(ctx, a, s, lut); }
@@ -66,13 +68,13 @@ int launch_bootstrap_pair_rr(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, con
     const int wgs = ctx->num_cus, most = (a.count + wgs - 1) / wgs;
     if (a.count < 4 * wgs || most > PairRrLds::GMAX)
         return fail(ctx, RTFHE_ERR_STATE, "k_bootstrap_pair_rr: " + std::to_string(a.count) + " gates on " + std::to_string(wgs) + " CUs is not a shape it serves");
-    return launch_twin(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_many_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_enc_pair_rr<3, 6, 8, 2, KSQ>, dim3(wgs), dim3(512), PairRrLds::bytes(most, a.npad), s, a, lut);
+    return launch_twin(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_many_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_enc_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_round_pair_rr<3, 6, 8, 2, KSQ, false>, k_pbs_round_pair_rr<3, 6, 8, 2, KSQ, true>, dim3(wgs), dim3(512), PairRrLds::bytes(most, a.npad), s, a, lut);
 }
 // four waves per gate, (polynomial, parity): up to two gates per CU (rtfhe_kernels_pair4.hpp); no fused key switch
 template <int GATES>
 int launch_bootstrap_pair4_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
     const Pair4Args a{b, ctx->d_p4bk};
-    return launch_twin(ctx, k_bootstrap_pair4<3, 6, GATES>, k_pbs_pair4<3, 6, GATES>, k_pbs_many_pair4<3, 6, GATES>, k_pbs_enc_pair4<3, 6, GATES>, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES),
+    return launch_twin(ctx, k_bootstrap_pair4<3, 6, GATES>, k_pbs_pair4<3, 6, GATES>, k_pbs_many_pair4<3, 6, GATES>, k_pbs_enc_pair4<3, 6, GATES>, k_pbs_round_pair4<3, 6, GATES, false>, k_pbs_round_pair4<3, 6, GATES, true>, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES),
                        Pair4Lds::bytes(GATES, b.npad), s, a, lut);
 }
 
@@ -83,14 +85,14 @@ constexpr int eo_round_gates(int npad) { return EoLds::bytes(4, npad) <= LDS_LIM
 template <int GATES>
 int launch_bootstrap_eo11_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
     const EoArgs a{b, ctx->d_etw, ctx->d_ebk};
-    return launch_twin(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_many_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, GATES>, dim3((b.count + GATES - 1) / GATES), dim3(128 * GATES),
+    return launch_twin(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_many_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_round_eo<3, 6, 8, 2, KSQ, GATES, false>, k_pbs_round_eo<3, 6, 8, 2, KSQ, GATES, true>, dim3((b.count + GATES - 1) / GATES), dim3(128 * GATES),
                        EoLds::bytes(GATES, b.npad), s, a, lut);
 }
 // four waves per gate, (polynomial, parity): batches of up to two gates per CU (rtfhe_kernels_eo4.hpp); no fused key switch
 template <int GATES>
 int launch_bootstrap_eo4_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
     const EoArgs a{b, ctx->d_etw, ctx->d_ebk};
-    return launch_twin(ctx, k_bootstrap_eo4<3, 6, GATES>, k_pbs_eo4<3, 6, GATES>, k_pbs_many_eo4<3, 6, GATES>, k_pbs_enc_eo4<3, 6, GATES>, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES),
+    return launch_twin(ctx, k_bootstrap_eo4<3, 6, GATES>, k_pbs_eo4<3, 6, GATES>, k_pbs_many_eo4<3, 6, GATES>, k_pbs_enc_eo4<3, 6, GATES>, k_pbs_round_eo4<3, 6, GATES, false>, k_pbs_round_eo4<3, 6, GATES, true>, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES),
                        Eo4Lds::bytes(GATES, b.npad), s, a, lut);
 }
 template <int GATES>
@@ -325,42 +327,43 @@ int rebuild_derived_keys(rtfhe_ctx* ctx) {
 
 // grants every bootstrap kernel of this context's parameter set, and its programmable-bootstrap, many-LUT and encrypted-table twins, its dynamic
 // LDS once, at context creation
-template <typename KG, typename KP, typename KM, typename KE>
-static int allow_twins(rtfhe_ctx* ctx, KG kg, KP kp, KM km, KE ke, size_t bytes) {
+template <typename KG, typename KP, typename KM>
+static int allow_twins(rtfhe_ctx* ctx, KG kg, KP kp, KM km, KM ke, KM kmr, KM ker, size_t bytes) {
     if (int rc = allow_lds(ctx, kg, bytes)) return rc;
     if (int rc = allow_lds(ctx, kp, bytes)) return rc;
-    if (int rc = allow_lds(ctx, km, bytes)) return rc;
-    return allow_lds(ctx, ke, bytes);
+    for (KM k : {km, ke, kmr, ker})
+        if (int rc = allow_lds(ctx, k, bytes)) return rc;
+    return 0;
 }
 int prime_fft_kernels(rtfhe_ctx* ctx) {
     const int npad = (ctx->p.n + 1 + 63) / 64 * 64;
     if (ctx->logn == 10) {
-        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, 4>, PairLds::bytes(4, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, 3>, PairLds::bytes(3, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, 2>, PairLds::bytes(2, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_many_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_enc_wg<10, 3, 6, 8, 2, KSQ>, WgLds<10, 3>::bytes(npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_round_pair<3, 6, 8, 2, KSQ, 4, false>, k_pbs_round_pair<3, 6, 8, 2, KSQ, 4, true>, PairLds::bytes(4, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_round_pair<3, 6, 8, 2, KSQ, 3, false>, k_pbs_round_pair<3, 6, 8, 2, KSQ, 3, true>, PairLds::bytes(3, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_round_pair<3, 6, 8, 2, KSQ, 2, false>, k_pbs_round_pair<3, 6, 8, 2, KSQ, 2, true>, PairLds::bytes(2, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_many_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_enc_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_round_wg<10, 3, 6, 8, 2, KSQ, false>, k_pbs_round_wg<10, 3, 6, 8, 2, KSQ, true>, WgLds<10, 3>::bytes(npad))) return rc;
         // the time-sliced launch: as many gates per CU (five or six) as this mask length leaves room for in 160 KiB of LDS
         {
             const int fit = rr_fit<PairRrLds>(npad);
             if (ctx->rr > fit) ctx->rr = fit;
             if (ctx->rr >= 5)
-                if (int rc = allow_twins(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_many_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_enc_pair_rr<3, 6, 8, 2, KSQ>, PairRrLds::bytes(ctx->rr, npad))) return rc;
+                if (int rc = allow_twins(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_many_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_enc_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_round_pair_rr<3, 6, 8, 2, KSQ, false>, k_pbs_round_pair_rr<3, 6, 8, 2, KSQ, true>, PairRrLds::bytes(ctx->rr, npad))) return rc;
         }
-        if (int rc = allow_twins(ctx, k_bootstrap_pair4<3, 6, 3>, k_pbs_pair4<3, 6, 3>, k_pbs_many_pair4<3, 6, 3>, k_pbs_enc_pair4<3, 6, 3>, Pair4Lds::bytes(3, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_pair4<3, 6, 2>, k_pbs_pair4<3, 6, 2>, k_pbs_many_pair4<3, 6, 2>, k_pbs_enc_pair4<3, 6, 2>, Pair4Lds::bytes(2, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 4>, k_pbs<10, 3, 6, 8, 2, KSQ, 4>, k_pbs_many<10, 3, 6, 8, 2, KSQ, 4>, k_pbs_enc<10, 3, 6, 8, 2, KSQ, 4>, bootstrap_lds_bytes<10>(4, npad, bootstrap_dual_xbuf(10, 4)))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 8>, k_pbs<10, 3, 6, 8, 2, KSQ, 8>, k_pbs_many<10, 3, 6, 8, 2, KSQ, 8>, k_pbs_enc<10, 3, 6, 8, 2, KSQ, 8>, bootstrap_lds_bytes<10>(8, npad, bootstrap_dual_xbuf(10, 8)))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair4<3, 6, 3>, k_pbs_pair4<3, 6, 3>, k_pbs_many_pair4<3, 6, 3>, k_pbs_enc_pair4<3, 6, 3>, k_pbs_round_pair4<3, 6, 3, false>, k_pbs_round_pair4<3, 6, 3, true>, Pair4Lds::bytes(3, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_pair4<3, 6, 2>, k_pbs_pair4<3, 6, 2>, k_pbs_many_pair4<3, 6, 2>, k_pbs_enc_pair4<3, 6, 2>, k_pbs_round_pair4<3, 6, 2, false>, k_pbs_round_pair4<3, 6, 2, true>, Pair4Lds::bytes(2, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 4>, k_pbs<10, 3, 6, 8, 2, KSQ, 4>, k_pbs_many<10, 3, 6, 8, 2, KSQ, 4>, k_pbs_enc<10, 3, 6, 8, 2, KSQ, 4>, k_pbs_round<10, 3, 6, 8, 2, KSQ, 4, false>, k_pbs_round<10, 3, 6, 8, 2, KSQ, 4, true>, bootstrap_lds_bytes<10>(4, npad, bootstrap_dual_xbuf(10, 4)))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 8>, k_pbs<10, 3, 6, 8, 2, KSQ, 8>, k_pbs_many<10, 3, 6, 8, 2, KSQ, 8>, k_pbs_enc<10, 3, 6, 8, 2, KSQ, 8>, k_pbs_round<10, 3, 6, 8, 2, KSQ, 8, false>, k_pbs_round<10, 3, 6, 8, 2, KSQ, 8, true>, bootstrap_lds_bytes<10>(8, npad, bootstrap_dual_xbuf(10, 8)))) return rc;
     } else {
-        if (int rc = allow_twins(ctx, k_bootstrap<11, 3, 6, 8, 2, KSQ, 4>, k_pbs<11, 3, 6, 8, 2, KSQ, 4>, k_pbs_many<11, 3, 6, 8, 2, KSQ, 4>, k_pbs_enc<11, 3, 6, 8, 2, KSQ, 4>, bootstrap_lds_bytes<11>(4, npad, bootstrap_dual_xbuf(11, 4)))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap<11, 3, 6, 8, 2, KSQ, 4>, k_pbs<11, 3, 6, 8, 2, KSQ, 4>, k_pbs_many<11, 3, 6, 8, 2, KSQ, 4>, k_pbs_enc<11, 3, 6, 8, 2, KSQ, 4>, k_pbs_round<11, 3, 6, 8, 2, KSQ, 4, false>, k_pbs_round<11, 3, 6, 8, 2, KSQ, 4, true>, bootstrap_lds_bytes<11>(4, npad, bootstrap_dual_xbuf(11, 4)))) return rc;
         // whole rounds of four gates per CU where their LDS fits, of three at the longest masks (the four-gate kernel is then never launched)
         ctx->eo_round = eo_round_gates(npad);
         if (ctx->eo_round == 4)
-            if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 4>, EoLds::bytes(4, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 3>, EoLds::bytes(3, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 2>, EoLds::bytes(2, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 1>, EoLds::bytes(1, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo4<3, 6, 2>, k_pbs_eo4<3, 6, 2>, k_pbs_many_eo4<3, 6, 2>, k_pbs_enc_eo4<3, 6, 2>, Eo4Lds::bytes(2, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo4<3, 6, 1>, k_pbs_eo4<3, 6, 1>, k_pbs_many_eo4<3, 6, 1>, k_pbs_enc_eo4<3, 6, 1>, Eo4Lds::bytes(1, npad))) return rc;
+            if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 4, false>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 4, true>, EoLds::bytes(4, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 3, false>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 3, true>, EoLds::bytes(3, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 2, false>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 2, true>, EoLds::bytes(2, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 1, false>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 1, true>, EoLds::bytes(1, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo4<3, 6, 2>, k_pbs_eo4<3, 6, 2>, k_pbs_many_eo4<3, 6, 2>, k_pbs_enc_eo4<3, 6, 2>, k_pbs_round_eo4<3, 6, 2, false>, k_pbs_round_eo4<3, 6, 2, true>, Eo4Lds::bytes(2, npad))) return rc;
+        if (int rc = allow_twins(ctx, k_bootstrap_eo4<3, 6, 1>, k_pbs_eo4<3, 6, 1>, k_pbs_many_eo4<3, 6, 1>, k_pbs_enc_eo4<3, 6, 1>, k_pbs_round_eo4<3, 6, 1, false>, k_pbs_round_eo4<3, 6, 1, true>, Eo4Lds::bytes(1, npad))) return rc;
     }
     return 0;
 }

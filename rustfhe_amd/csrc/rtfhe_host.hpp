@@ -74,6 +74,7 @@ struct rtfhe_ctx {
     int eo4 = 1;                      // N = 2048, up to two gates per CU: 1 = four waves per gate (k_bootstrap_eo4), 0 = two (RTFHE_N2048_EO4)
     int eo_round = 4;                 // N = 2048: gates per CU in a whole round of k_bootstrap_eo: 4, or 3 where four gates' LDS passes 160 KiB (n >= 704), set when the kernels are primed
     int backend = RTFHE_BACKEND_FFT64_MIRROR;
+    int decomp = RTFHE_DECOMP_REFERENCE;   // the gadget decomposition of the PBS family (rtfhe_set_decomposition); gates never read it
     uint32_t* d_bk_torus = nullptr;   // kept when the key came in torus form: source for the NTT-domain key
     double* d_ntt_bk = nullptr;
     double* d_ntt_tw = nullptr;
@@ -191,12 +192,15 @@ using rtfhe::BootstrapArgs;
 // what a bootstrap launch reads its test polynomials from: tv null = the gates' own (k_bootstrap_*), else the k_pbs_* twins with table
 // idx[g] of tv (idx null: table 0) for gate g of the launch
 // (shift >= 0: a many-LUT PBS with 2^shift outputs per gate, the k_pbs_many_* kernels in MODE_EXTRACT, launch_pbs_many; enc: tv holds
-// encrypted rows [n_tv][2][N], the k_pbs_enc_* kernels, which need shift >= 0)
-struct LutRef { const uint32_t* tv = nullptr; const int32_t* idx = nullptr; int32_t n_tv = 0; int32_t shift = -1; bool enc = false; };
+// encrypted rows [n_tv][2][N], the k_pbs_enc_* kernels, which need shift >= 0; rounded: the rounded gadget decomposition, the k_pbs_round_*
+// kernels, which need shift >= 0 too -- a plain-table PBS in rounded mode is a many-LUT PBS with shift = 0)
+struct LutRef { const uint32_t* tv = nullptr; const int32_t* idx = nullptr; int32_t n_tv = 0; int32_t shift = -1; bool enc = false; bool rounded = false; };
 inline LutRef lut_segment(LutRef l, size_t off) { if (l.idx) l.idx += off; return l; }     // ... for the segment starting at gate `off`
 inline LutRef lut_on(const rtfhe_lut* lut, int entry, const int32_t* d_idx, int32_t shift = -1) {
-    return lut ? LutRef{lut->d_tv[entry], d_idx, lut->n_lut, shift, lut->encrypted} : LutRef{};
+    return lut ? LutRef{lut->d_tv[entry], d_idx, lut->n_lut, shift, lut->encrypted, lut->ctx && lut->ctx->decomp == RTFHE_DECOMP_ROUNDED} : LutRef{};
 }
+// the path of a one-output PBS with this table: the many-LUT path (shift 0) for an encrypted table and in rounded mode, else the fused kernels (-1)
+inline int32_t pbs_shift(const rtfhe_ctx* ctx, const rtfhe_lut* lut) { return (lut->encrypted || ctx->decomp == RTFHE_DECOMP_ROUNDED) ? 0 : -1; }
 using rtfhe::cplx;
 
 constexpr int KSQ = 3;        // uint4 loads per lane per key-switch row: rows up to 768 words

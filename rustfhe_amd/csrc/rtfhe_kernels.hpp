@@ -102,6 +102,7 @@ __device__ __forceinline__ GateIo gate_io(const BootstrapArgs& a, int g) {
 struct TvGate {
     static constexpr bool MANY = false;      // one output per gate (k_pbs_many_*: several, see TvMany)
     static constexpr bool ENC = false;       // the a half starts at zero (k_pbs_enc_*: from an encrypted table, see TvEnc)
+    static constexpr bool ROUNDED = false;   // the reference's gadget decomposition (k_pbs_round_*: rounded to nearest, see TvManyR)
     struct Row { __device__ __forceinline__ bool ok() const { return true; } };
 };
 __device__ __forceinline__ TvGate::Row tv_row(const TvGate&, int, int) { return TvGate::Row{}; }
@@ -121,6 +122,7 @@ struct LutArgs {
 struct TvLut {
     static constexpr bool MANY = false;
     static constexpr bool ENC = false;
+    static constexpr bool ROUNDED = false;
     const uint32_t* tv; const int32_t* idx; int32_t n_tv; int32_t* fault;
     struct Row {
         const uint32_t* p; bool good;
@@ -182,6 +184,21 @@ __device__ __forceinline__ uint32_t tv_word_a(const TvLut::Row& r, int e) { retu
 template <int LOGN>
 __device__ __forceinline__ uint32_t tv_word_a(const TvGate::Row&, int) { return 0u; }
 
+// Rounded gadget decomposition (k_pbs_round_*, the fifth inclusion of every body, ENC = false / true): the many-LUT PBS of TvMany and the
+// encrypted-table PBS of TvEnc with the decomposition's two constants replaced (decomp_add / decomp_xor, rtfhe_device.hpp); nothing else
+// differs.  The same ManyArgs; a plain-table PBS in rounded mode is the many-LUT twin with t = 0 (include/rtfhe.h: rtfhe_set_decomposition).
+struct TvManyR : TvMany {
+    static constexpr bool ROUNDED = true;
+};
+struct TvEncR : TvEnc {
+    static constexpr bool ROUNDED = true;
+};
+template <bool E, typename A>
+__device__ __forceinline__ auto tv_round(const ManyArgs<A>& p, int32_t* fault) {
+    if constexpr (E) return TvEncR{tv_enc(p, fault)};
+    else return TvManyR{tv_many(p, fault)};
+}
+
 // The mod switch (tfhe.rs:97, 107-108) of one pre-stepped word at SH + k, scaled back by 2^k: b floor, a_i rounded, both to multiples of 2^k
 // in [0, 2N).  k = tv_shift(tvs): t for many-LUT, 0 otherwise.  The bodies call it under `if constexpr (MANY)` and keep their own k = 0
 // expression for the gates' and the PBS's kernels: routed through this function (k a compile-time 0) those kernels' code changed by a few
@@ -212,13 +229,14 @@ __device__ __forceinline__ void many_extract(uint32_t* ext, int ge, int t, const
 //   CMUX = true : acc <- cross(bk_i, X^r * acc - acc) + acc      (trgsw.rs:319-321, tfhe.rs:103-110)
 //   CMUX = false: acc <- cross(bk_i, acc)                          (trgsw.rs:264-306)
 // accbuf: LDS u32 [2][N] (b then a).  bk_i: this TRGSW in device layout [2l][2][R][64] cplx.
-template <int LOGN, int L, int BGBIT, bool CMUX, bool DUAL = false>
+// ROUNDED: the decomposition rounds to nearest with balanced digits (TvManyR); every caller but the k_pbs_round kernels leaves it false.
+template <int LOGN, int L, int BGBIT, bool CMUX, bool DUAL = false, bool ROUNDED = false>
 __device__ __forceinline__ void cmux_step(uint32_t* __restrict__ accbuf, int r, const cplx* __restrict__ bk_i,
                                           const cplx* __restrict__ twf, const cplx* __restrict__ twi, const cplx* __restrict__ twi_big,
                                           double* __restrict__ xbuf, int lane) {
     typedef Geo<LOGN> G;
     constexpr int N = G::N, P = G::P, R = G::R;
-    constexpr uint32_t M = decomp_mask(L, BGBIT);
+    constexpr uint32_t MA = decomp_add(L, BGBIT, ROUNDED), MX = decomp_xor(L, BGBIT, ROUNDED);
 
     double s0re[R], s0im[R], s1re[R], s1im[R];
 #pragma unroll
@@ -233,7 +251,7 @@ __device__ __forceinline__ void cmux_step(uint32_t* __restrict__ accbuf, int r, 
             const int c = lane + 64 * mm;
             const uint32_t own = poly[c];
             const uint32_t d = CMUX ? (rotated_coef<LOGN>(poly, c, r) - own) : own;
-            u[mm] = (d + M) ^ M;
+            u[mm] = (d + MA) ^ MX;
         }
 #pragma unroll 1
         for (int jj = 0; jj < L; jj++) {
@@ -418,6 +436,12 @@ template <int LOGN, int L, int BGBIT, int KS_T, int KS_BB, int KSQ, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_pbs_enc(const ManyArgs<BootstrapArgs> p) {
     const BootstrapArgs& a = p.base;
     const TvEnc tvs = tv_enc(p, a.fault);
+#include "rtfhe_body_wave.hpp"
+}
+template <int LOGN, int L, int BGBIT, int KS_T, int KS_BB, int KSQ, int WAVES, bool E>
+__global__ __launch_bounds__(64 * WAVES, 1) void k_pbs_round(const ManyArgs<BootstrapArgs> p) {
+    const BootstrapArgs& a = p.base;
+    const auto tvs = tv_round<E>(p, a.fault);
 #include "rtfhe_body_wave.hpp"
 }
 

@@ -140,5 +140,12 @@ __global__ __launch_bounds__(128 * GATES, 1) void k_pbs_enc_eo(const ManyArgs<Eo
     const TvEnc tvs = tv_enc(p, ea.b.fault);
 #include "rtfhe_body_eo.hpp"
 }
+// the rounded-decomposition twins of k_pbs_many_eo (E = false) and k_pbs_enc_eo (E = true): TvManyR / TvEncR, rtfhe_kernels.hpp
+template <int L, int BGBIT, int KS_T, int KS_BB, int KSQ, int GATES, bool E>
+__global__ __launch_bounds__(128 * GATES, 1) void k_pbs_round_eo(const ManyArgs<EoArgs> p) {
+    const EoArgs& ea = p.base;
+    const auto tvs = tv_round<E>(p, ea.b.fault);
+#include "rtfhe_body_eo.hpp"
+}
 
 }  // namespace rtfhe

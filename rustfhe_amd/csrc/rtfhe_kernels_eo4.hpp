@@ -67,5 +67,12 @@ __global__ __launch_bounds__(256 * GATES, 1) void k_pbs_enc_eo4(const ManyArgs<E
     const TvEnc tvs = tv_enc(p, ea.b.fault);
 #include "rtfhe_body_eo4.hpp"
 }
+// the rounded-decomposition twins of k_pbs_many_eo4 (E = false) and k_pbs_enc_eo4 (E = true): TvManyR / TvEncR, rtfhe_kernels.hpp
+template <int L, int BGBIT, int GATES, bool E>
+__global__ __launch_bounds__(256 * GATES, 1) void k_pbs_round_eo4(const ManyArgs<EoArgs> p) {
+    const EoArgs& ea = p.base;
+    const auto tvs = tv_round<E>(p, ea.b.fault);
+#include "rtfhe_body_eo4.hpp"
+}
 
 }  // namespace rtfhe

@@ -167,5 +167,12 @@ __global__ __launch_bounds__(128 * GATES, 1) void k_pbs_enc_pair(const ManyArgs<
     const TvEnc tvs = tv_enc(p, a.fault);
 #include "rtfhe_body_pair.hpp"
 }
+// the rounded-decomposition twins of k_pbs_many_pair (E = false) and k_pbs_enc_pair (E = true): TvManyR / TvEncR, rtfhe_kernels.hpp
+template <int L, int BGBIT, int KS_T, int KS_BB, int KSQ, int GATES, bool E>
+__global__ __launch_bounds__(128 * GATES, 1) void k_pbs_round_pair(const ManyArgs<BootstrapArgs> p) {
+    const BootstrapArgs& a = p.base;
+    const auto tvs = tv_round<E>(p, a.fault);
+#include "rtfhe_body_pair.hpp"
+}
 
 }  // namespace rtfhe

@@ -81,5 +81,12 @@ __global__ __launch_bounds__(256 * GATES, 1) void k_pbs_enc_pair4(const ManyArgs
     const TvEnc tvs = tv_enc(p, pa.b.fault);
 #include "rtfhe_body_pair4.hpp"
 }
+// the rounded-decomposition twins of k_pbs_many_pair4 (E = false) and k_pbs_enc_pair4 (E = true): TvManyR / TvEncR, rtfhe_kernels.hpp
+template <int L, int BGBIT, int GATES, bool E>
+__global__ __launch_bounds__(256 * GATES, 1) void k_pbs_round_pair4(const ManyArgs<Pair4Args> p) {
+    const Pair4Args& pa = p.base;
+    const auto tvs = tv_round<E>(p, pa.b.fault);
+#include "rtfhe_body_pair4.hpp"
+}
 
 }  // namespace rtfhe

@@ -55,5 +55,12 @@ __global__ __launch_bounds__(512, 1) void k_pbs_enc_pair_rr(const ManyArgs<Boots
     const TvEnc tvs = tv_enc(p, a.fault);
 #include "rtfhe_body_pair_rr.hpp"
 }
+// the rounded-decomposition twins of k_pbs_many_pair_rr (E = false) and k_pbs_enc_pair_rr (E = true): TvManyR / TvEncR, rtfhe_kernels.hpp
+template <int L, int BGBIT, int KS_T, int KS_BB, int KSQ, bool E>
+__global__ __launch_bounds__(512, 1) void k_pbs_round_pair_rr(const ManyArgs<BootstrapArgs> p) {
+    const BootstrapArgs& a = p.base;
+    const auto tvs = tv_round<E>(p, a.fault);
+#include "rtfhe_body_pair_rr.hpp"
+}
 
 }  // namespace rtfhe

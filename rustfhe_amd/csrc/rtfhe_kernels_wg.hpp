@@ -75,5 +75,12 @@ __global__ __launch_bounds__(512, 1) void k_pbs_enc_wg(const ManyArgs<BootstrapA
     const TvEnc tvs = tv_enc(p, a.fault);
 #include "rtfhe_body_wg.hpp"
 }
+// the rounded-decomposition twins of k_pbs_many_wg (E = false) and k_pbs_enc_wg (E = true): TvManyR / TvEncR, rtfhe_kernels.hpp
+template <int LOGN, int L, int BGBIT, int KS_T, int KS_BB, int KSQ, bool E>
+__global__ __launch_bounds__(512, 1) void k_pbs_round_wg(const ManyArgs<BootstrapArgs> p) {
+    const BootstrapArgs& a = p.base;
+    const auto tvs = tv_round<E>(p, a.fault);
+#include "rtfhe_body_wg.hpp"
+}
 
 }  // namespace rtfhe

@@ -124,6 +124,15 @@ class Engine:
     def backend(self):
         return self.L.rtfhe_get_backend(self.h)
 
+    def set_decomposition(self, mode):
+        """The gadget decomposition of the PBS family (pbs_batch*, pbs_many_batch*, LUT circuits at creation): _ffi.DECOMP_REFERENCE (the
+        default, the reference's words) or _ffi.DECOMP_ROUNDED (round to nearest, balanced digits: about a fifth of the output noise at
+        N = 1024, 4-bit messages).  Gates and every other call always use the reference decomposition."""
+        self._ck(self.L.rtfhe_set_decomposition(self.h, mode))
+
+    def decomposition(self):
+        return self.L.rtfhe_get_decomposition(self.h)
+
     def twiddles(self):
         a = np.zeros(2 * self.p.N, np.float64)
         b = np.zeros(2 * self.p.N, np.float64)

@@ -142,12 +142,15 @@ class LutNetlist:
 class LutCircuitRunner:
     """Runs `replicas` independent instances of a LutNetlist on one Engine as ONE recorded circuit.  Wire table: int32[replicas * num_wires][n+1]
     in HBM; the inputs of replica r are rows r * num_wires + 0 .. num_inputs - 1.  Given the lvl1 key key1, the tables are encrypted under it
-    (rustfhe_amd.encrypt_lut; seed: TEST-ONLY deterministic encryption) and the circuit holds them only as ciphertexts (Engine.lut_encrypted)."""
+    (rustfhe_amd.encrypt_lut; seed: TEST-ONLY deterministic encryption) and the circuit holds them only as ciphertexts (Engine.lut_encrypted).
+    rounded=True records the circuit with the rounded gadget decomposition (Engine.set_decomposition): the engine's mode is set around the
+    recording and restored after it; the circuit replays in the mode it was recorded in."""
 
-    def __init__(self, engine, net, replicas=1, key1=None, seed=None):
+    def __init__(self, engine, net, replicas=1, key1=None, seed=None, rounded=False):
         import torch
         self.e, self.net, self.R = engine, net, replicas
         self.key1, self.seed = key1, seed
+        self.rounded = bool(rounded)
         self.n1 = engine.p.n + 1
         self.wires = torch.zeros((replicas * net.num_wires, self.n1), dtype=torch.int32, device="cuda")
         self.desc = net.arrays(replicas)
@@ -171,9 +174,15 @@ class LutCircuitRunner:
                 lut = self.e.lut_encrypted(encrypt_lut(self.e.p, self.key1, tv, self.seed))
             else:
                 lut = self.e.lut(tv)
+            from . import _ffi
+            before = self.e.decomposition()
             with lut:
-                self._circuit = self.e.lut_circuit_create(lut, d["fan_in"], d["in_idx"], d["weights"], d["cst"], d["lut_idx"], d["wave_offsets"],
-                                                          d["wave_n_out"], d["out_idx"], self.wires, d["num_wires"])
+                self.e.set_decomposition(_ffi.DECOMP_ROUNDED if self.rounded else _ffi.DECOMP_REFERENCE)
+                try:
+                    self._circuit = self.e.lut_circuit_create(lut, d["fan_in"], d["in_idx"], d["weights"], d["cst"], d["lut_idx"], d["wave_offsets"],
+                                                              d["wave_n_out"], d["out_idx"], self.wires, d["num_wires"])
+                finally:
+                    self.e.set_decomposition(before)
         if self._circuit is not None:
             self.e.circuit_launch(self._circuit, stream)
 
