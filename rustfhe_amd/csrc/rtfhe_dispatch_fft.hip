@@ -1,6 +1,8 @@
 // rtfhe_dispatch_fft.hip -- the FP64 mirror backend's bootstrap kernels and the choice of kernel shape per batch.
 #include "rtfhe_host.hpp"
 
+#include <algorithm>
+
 #include "rtfhe_kernels_wg.hpp"
 #include "rtfhe_kernels_pair.hpp"
 #include "rtfhe_kernels_pair4.hpp"
@@ -13,190 +15,136 @@ using namespace rtfhe_host;
 
 namespace {
 
-// One launch of a kernel family: the gate kernel (k_bootstrap_*) or, for a programmable bootstrap (lut.tv set), its twin (k_pbs_*) with the
-// family's own arguments wrapped in LutArgs.  The twins share shapes, LDS and key layouts, so every choice below is made once for both.
-// A many-LUT PBS (lut.shift >= 0) takes the family's third kernel (k_pbs_many_*), in MODE_EXTRACT, and one with an encrypted table (lut.enc)
-// the fourth (k_pbs_enc_*), with the same arguments.  In rounded mode (lut.rounded) those two are replaced by the family's k_pbs_round_* pair
-// (kmr: plain tables, ker: encrypted), again with the same arguments.
-template <typename A, typename KG, typename KP, typename KM>
-int launch_twin(rtfhe_ctx* ctx, KG kg, KP kp, KM km, KM ke, KM kmr, KM ker, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A& a, const LutRef& lut) {
-    if (lut.tv && lut.enc && lut.shift < 0) return fail(ctx, RTFHE_ERR_STATE, "an encrypted table runs on the many-LUT path only (launch_pbs_many)");
-    if (lut.tv && lut.rounded && lut.shift < 0) return fail(ctx, RTFHE_ERR_STATE, "the rounded decomposition runs on the many-LUT path only (launch_pbs_many)");
-    if (lut.tv && lut.shift >= 0) {
-        const KM k = lut.rounded ? (lut.enc ? ker : kmr) : (lut.enc ? ke : km);
-        if (int rc = allow_lds(ctx, k, lds)) return rc;
-        ManyArgs<A> p{};
-        p.base = a; p.tv = lut.tv; p.tv_idx = lut.idx; p.n_tv = lut.n_tv; p.t = lut.shift;
-        hipLaunchKernelGGL(k, grid, block, lds, s, p);
-    } else if (lut.tv) {
-        if (int rc = allow_lds(ctx, kp, lds)) return rc;
-        const LutArgs<A> p{a, lut.tv, lut.idx, lut.n_tv};
-        hipLaunchKernelGGL(kp, grid, block, lds, s, p);
-    } else {
-        if (int rc = allow_lds(ctx, kg, lds)) return rc;
-        hipLaunchKernelGGL(kg, grid, block, lds, s, a);
-    }
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
-}
-
+// ---- the kernel shapes of this backend (Shape / Family: rtfhe_host.hpp) ----
 template <int LOGN, int W>
-int launch_bootstrap_w(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
-    const size_t lds = bootstrap_lds_bytes<LOGN>(W, a.npad, bootstrap_dual_xbuf(LOGN, W));
-    const int grid = (a.count + W - 1) / W;
-    return launch_twin(ctx, k_bootstrap<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs_many<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs_enc<LOGN, 3, 6, 8, 2, KSQ, W>, k_pbs_round<LOGN, 3, 6, 8, 2, KSQ, W, false>, k_pbs_round<LOGN, 3, 6, 8, 2, KSQ, W, true>, dim3(grid), dim3(64 * W), lds, s, a, lut);
-}
-
-int launch_bootstrap_wg10(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
-    return launch_twin(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_many_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_enc_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_round_wg<10, 3, 6, 8, 2, KSQ, false>, k_pbs_round_wg<10, 3, 6, 8, 2, KSQ, true>, dim3(a.count), dim3(512), WgLds<10, 3>::bytes(a.npad), s, a, lut);
-}
-
+struct WaveShape : GatesPerWorkgroup<W, 64> {          // one wave per gate, W gates per workgroup (rtfhe_kernels.hpp)
+    static TwinKernels<BootstrapArgs> kernels() { return RTFHE_TWINS(, LOGN, 3, 6, 8, 2, KSQ, W); }
+    static constexpr size_t lds(int npad) { return bootstrap_lds_bytes<LOGN>(W, npad, bootstrap_dual_xbuf(LOGN, W)); }
+    static BootstrapArgs args(const rtfhe_ctx*, const BootstrapArgs& b) { return b; }
+};
+template <int W> using Wave10Shape = WaveShape<10, W>;
+template <int W> using Wave11Shape = WaveShape<11, W>;
 template <int GATES>
-int launch_bootstrap_pair10_g(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
-    return launch_twin(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_many_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, GATES>, k_pbs_round_pair<3, 6, 8, 2, KSQ, GATES, false>, k_pbs_round_pair<3, 6, 8, 2, KSQ, GATES, true>, dim3((a.count + GATES - 1) / GATES), dim3(128 * GATES),
-                       PairLds::bytes(GATES, a.npad), s, a, lut);
-}
-int launch_bootstrap_pair10(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) { return launch_bootstrap_pair10_g<4>(ctx, a, s, lut); }
+struct WgShape : GatesPerWorkgroup<GATES, 512> {       // one gate per 8-wave workgroup (rtfhe_kernels_wg.hpp)
+    static TwinKernels<BootstrapArgs> kernels() { return RTFHE_TWINS(_wg, 10, 3, 6, 8, 2, KSQ); }
+    static constexpr size_t lds(int npad) { return WgLds<10, 3>::bytes(npad); }
+    static BootstrapArgs args(const rtfhe_ctx*, const BootstrapArgs& b) { return b; }
+};
+template <int GATES>
+struct PairShape : GatesPerWorkgroup<GATES, 128> {     // two waves per gate (rtfhe_kernels_pair.hpp)
+    static TwinKernels<BootstrapArgs> kernels() { return RTFHE_TWINS(_pair, 3, 6, 8, 2, KSQ, GATES); }
+    static constexpr size_t lds(int npad) { return PairLds::bytes(GATES, npad); }
+    static BootstrapArgs args(const rtfhe_ctx*, const BootstrapArgs& b) { return b; }
+};
+template <int GATES>
+struct PairRrShape : WorkgroupPerCu {                  // GATES = 5 or 6 gates on the four wave pairs of every CU, time-sliced (rtfhe_kernels_pair_rr.hpp)
+    static TwinKernels<BootstrapArgs> kernels() { return RTFHE_TWINS(_pair_rr, 3, 6, 8, 2, KSQ); }
+    static constexpr size_t lds(int npad) { return PairRrLds::bytes(GATES, npad); }
+    static BootstrapArgs args(const rtfhe_ctx*, const BootstrapArgs& b) { return b; }
+};
+template <int GATES>
+struct Pair4Shape : GatesPerWorkgroup<GATES, 256> {    // four waves per gate, (polynomial, parity) (rtfhe_kernels_pair4.hpp); no fused key switch
+    static TwinKernels<Pair4Args> kernels() { return RTFHE_TWINS(_pair4, 3, 6, GATES); }
+    static constexpr size_t lds(int npad) { return Pair4Lds::bytes(GATES, npad); }
+    static Pair4Args args(const rtfhe_ctx* ctx, const BootstrapArgs& b) { return {b, ctx->d_p4bk}; }
+};
+template <int GATES>
+struct EoShape : GatesPerWorkgroup<GATES, 128> {       // N = 2048: two waves per transform, split by the parity of the point index (rtfhe_kernels_eo.hpp)
+    static TwinKernels<EoArgs> kernels() { return RTFHE_TWINS(_eo, 3, 6, 8, 2, KSQ, GATES); }
+    static constexpr size_t lds(int npad) { return EoLds::bytes(GATES, npad); }
+    static EoArgs args(const rtfhe_ctx* ctx, const BootstrapArgs& b) { return {b, ctx->d_etw, ctx->d_ebk}; }
+};
+template <int GATES>
+struct Eo4Shape : GatesPerWorkgroup<GATES, 256> {      // N = 2048: four waves per gate, (polynomial, parity) (rtfhe_kernels_eo4.hpp); no fused key switch
+    static TwinKernels<EoArgs> kernels() { return RTFHE_TWINS(_eo4, 3, 6, GATES); }
+    static constexpr size_t lds(int npad) { return Eo4Lds::bytes(GATES, npad); }
+    static EoArgs args(const rtfhe_ctx* ctx, const BootstrapArgs& b) { return {b, ctx->d_etw, ctx->d_ebk}; }
+};
+typedef Family<Wave10Shape, 4, 8> Wave10;
+typedef Family<WgShape, 1> Wg;
+typedef Family<PairShape, 2, 3, 4> Pair;              // (there is no pair<1>: a tail of up to one gate per CU beyond wg_max runs two per workgroup)
+typedef Family<PairRrShape, 5, 6> PairRr;
+typedef Family<Pair4Shape, 2, 3> Pair4;
+typedef Family<Wave11Shape, 4> Wave11;
+typedef Family<EoShape, 1, 2, 3, 4> Eo;
+typedef Family<Eo4Shape, 1, 2> Eo4;
+
 // 4 x CUs < count <= rr x CUs gates on the four wave pairs of every CU, time-sliced (rtfhe_kernels_pair_rr.hpp)
 bool rr_applies(const rtfhe_ctx* ctx, size_t count) {
     const size_t cus = (size_t)ctx->num_cus, round = 4 * cus, rem = count % round;
     const int rr = ctx->rr > PairRrLds::GMAX ? PairRrLds::GMAX : ctx->rr;
     return rr > 4 && !ctx->force_waves && count > round && rem != 0 && round + rem <= (size_t)rr * cus;
 }
-int launch_bootstrap_pair_rr(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
-    const int wgs = ctx->num_cus, most = (a.count + wgs - 1) / wgs;
-    if (a.count < 4 * wgs || most > PairRrLds::GMAX)
-        return fail(ctx, RTFHE_ERR_STATE, "k_bootstrap_pair_rr: " + std::to_string(a.count) + " gates on " + std::to_string(wgs) + " CUs is not a shape it serves");
-    return launch_twin(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_many_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_enc_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_round_pair_rr<3, 6, 8, 2, KSQ, false>, k_pbs_round_pair_rr<3, 6, 8, 2, KSQ, true>, dim3(wgs), dim3(512), PairRrLds::bytes(most, a.npad), s, a, lut);
+// Gates per workgroup (2 or 3) of an N = 1024 tail of `rem` gates that wants four waves per gate (k_bootstrap_pair4), else 0.  k_bootstrap_pair
+// would leave SIMDs a lone wave on tails of more than wg_max gates and up to two / three gates per CU (7 % on 257-512-gate and 1-4 % on
+// 513-768-gate batches; at four gates per CU pair4 loses 12 %, profiles/r04/pair4_ab.log).  The dispatch and layout_needed both ask here.
+int pair4_tail_gates(const rtfhe_ctx* ctx, size_t rem) {
+    const size_t cus = (size_t)ctx->num_cus;
+    if (rem <= (size_t)ctx->wg_max) return 0;
+    const int gates = rem <= 2 * cus ? 2 : rem <= 3 * cus ? 3 : 0;
+    return gates && ctx->pair4 >= gates ? gates : 0;
 }
-// four waves per gate, (polynomial, parity): up to two gates per CU (rtfhe_kernels_pair4.hpp); no fused key switch
-template <int GATES>
-int launch_bootstrap_pair4_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
-    const Pair4Args a{b, ctx->d_p4bk};
-    return launch_twin(ctx, k_bootstrap_pair4<3, 6, GATES>, k_pbs_pair4<3, 6, GATES>, k_pbs_many_pair4<3, 6, GATES>, k_pbs_enc_pair4<3, 6, GATES>, k_pbs_round_pair4<3, 6, GATES, false>, k_pbs_round_pair4<3, 6, GATES, true>, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES),
-                       Pair4Lds::bytes(GATES, b.npad), s, a, lut);
-}
-
-// N = 2048: two waves per transform, split by the parity of the point index (rtfhe_kernels_eo.hpp)
-// gates per workgroup (= per CU) of its whole rounds: four, or three at the mask lengths where four gates' carve passes the CU's LDS
+// gates per workgroup (= per CU) of the N = 2048 whole rounds: four, or three at the mask lengths where four gates' carve passes the CU's LDS
 // (npad = 768, n >= 704: 163,904 bytes)
 constexpr int eo_round_gates(int npad) { return EoLds::bytes(4, npad) <= LDS_LIMIT ? 4 : 3; }
-template <int GATES>
-int launch_bootstrap_eo11_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
-    const EoArgs a{b, ctx->d_etw, ctx->d_ebk};
-    return launch_twin(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_many_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, GATES>, k_pbs_round_eo<3, 6, 8, 2, KSQ, GATES, false>, k_pbs_round_eo<3, 6, 8, 2, KSQ, GATES, true>, dim3((b.count + GATES - 1) / GATES), dim3(128 * GATES),
-                       EoLds::bytes(GATES, b.npad), s, a, lut);
-}
-// four waves per gate, (polynomial, parity): batches of up to two gates per CU (rtfhe_kernels_eo4.hpp); no fused key switch
-template <int GATES>
-int launch_bootstrap_eo4_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
-    const EoArgs a{b, ctx->d_etw, ctx->d_ebk};
-    return launch_twin(ctx, k_bootstrap_eo4<3, 6, GATES>, k_pbs_eo4<3, 6, GATES>, k_pbs_many_eo4<3, 6, GATES>, k_pbs_enc_eo4<3, 6, GATES>, k_pbs_round_eo4<3, 6, GATES, false>, k_pbs_round_eo4<3, 6, GATES, true>, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES),
-                       Eo4Lds::bytes(GATES, b.npad), s, a, lut);
-}
-template <int GATES>
-int launch_bootstrap_n2048_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s, const LutRef& lut) {
-    // up to two gates per CU: four waves per gate, so that no SIMD is left with a lone wave (single gate 9.78 -> 5.84 ms, 512 gates 9.91 -> 7.8 ms,
-    // profiles/r04/n2048_four_waves_per_gate_ab.log); the fused key switch and a forced split stay on the two-wave kernels
-    if constexpr (GATES <= 2) {
-        if (ctx->eo4 && (b.mode == MODE_EXTRACT || b.mode == MODE_BLIND_ROTATE)) return launch_bootstrap_eo4_g<GATES>(ctx, b, s, lut);
-    }
-    return launch_bootstrap_eo11_g<GATES>(ctx, b, s, lut);
-}
 
 // Kernel shape by batch size (N = 1024), measured in profiles/r01_pair/shape_sweep.log:
 //   whole rounds of 4 gates per CU : two waves per gate, 8-wave workgroups (k_bootstrap_pair) -- best throughput at every size
 //   a remainder <= 1 gate per CU   : one gate per 8-wave workgroup (k_bootstrap_wg): ~2.4x lower latency
 //   a remainder <= 2 / 3 gates per CU : the two-waves-per-gate kernel with 2 / 3 gates per workgroup, one workgroup per CU -- every
 //                                    gate still has its two waves, which then share their SIMDs with fewer (or no) other waves
+//                                    (or four waves per gate: pair4_tail_gates)
 //   a larger remainder             : one more (partly filled) round of 4 gates per CU
-// The segments are queued back to back on the caller's stream.  RTFHE_FORCE_WAVES=1|2|4|8 forces one shape for the
-// whole batch (4, 8: one gate per wave in 4- / 8-wave workgroups).  A programmable bootstrap takes the same shapes on the k_pbs_* twins;
-// its table indices travel with the ciphertexts of each segment.
-template <int LOGN>
-int launch_bootstrap_t(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
-    auto seg = [&](size_t off, size_t cnt, size_t out_words) { return batch_segment(ctx, a, off, cnt, out_words); };
-    auto rotate = [&lut](rtfhe_ctx* c, BootstrapArgs b, hipStream_t st) { return launch_bootstrap_t<LOGN>(c, b, st, lut); };
-    if constexpr (LOGN == 10) {
-        const int force = ctx->force_waves;
-        if (force == 1) return launch_bootstrap_wg10(ctx, a, s, lut);
-        if (force == 2) return launch_bootstrap_pair10(ctx, a, s, lut);
-        if (force == 8) return launch_bootstrap_w<10, 8>(ctx, a, s, lut);
-        if (force == 4) return launch_bootstrap_w<10, 4>(ctx, a, s, lut);
-        if (split_ok(ctx, a, s)) return launch_split(ctx, a, s, rotate);     // comes back here in MODE_EXTRACT
-        const size_t out_words = mode_out_words(a, 1 << LOGN);
-        const size_t round = (size_t)4 * ctx->num_cus, count = (size_t)a.count;
-        const size_t full = count / round * round, rem = count - full;
-        // four waves per gate (k_bootstrap_pair4) where k_bootstrap_pair would leave SIMDs a lone wave: tails of more than wg_max gates and up to
-        // two / three gates per CU (7 % on 257-512-gate and 1-4 % on 513-768-gate batches; at four gates per CU it loses 12 %, profiles/r04/pair4_ab.log)
-        const bool p4 = ctx->p4bk_valid && (a.mode == MODE_EXTRACT || a.mode == MODE_BLIND_ROTATE);
-        if (rr_applies(ctx, count)) {
-            // the last whole round and the remainder as ONE launch of five or six gates per CU: (4 + rem / CUs) / 4 rounds instead of 2
-            // (1,280 gates 9.3 -> 8.2 ms; profiles/r06/pair_rr_sweep.log)
-            if (full > round)
-                if (int rc = launch_bootstrap_pair10(ctx, seg(0, full - round, out_words), s, lut)) return rc;
-            return launch_bootstrap_pair_rr(ctx, seg(full - round, round + rem, out_words), s, lut_segment(lut, full - round));
-        }
-        if (full)
-            if (int rc = launch_bootstrap_pair10(ctx, seg(0, full, out_words), s, lut)) return rc;
-        if (rem) {
-            const BootstrapArgs tail = seg(full, rem, out_words);
-            const LutRef tl = lut_segment(lut, full);
-            if (rem <= (size_t)ctx->wg_max) return launch_bootstrap_wg10(ctx, tail, s, tl);
-            if (rem <= (size_t)2 * ctx->num_cus) return (p4 && ctx->pair4 >= 2) ? launch_bootstrap_pair4_g<2>(ctx, tail, s, tl) : launch_bootstrap_pair10_g<2>(ctx, tail, s, tl);
-            if (rem <= (size_t)3 * ctx->num_cus) return (p4 && ctx->pair4 >= 3) ? launch_bootstrap_pair4_g<3>(ctx, tail, s, tl) : launch_bootstrap_pair10_g<3>(ctx, tail, s, tl);
-            return launch_bootstrap_pair10(ctx, tail, s, tl);
-        }
-        return 0;
-    } else {
-        // two waves per transform (two waves per SIMD, no AGPR traffic); RTFHE_FORCE_WAVES=4 selects one wave per gate
-        // (inverse pass-1/untwist twiddles in global memory: 4 gates per CU fit)
-        if (!(ctx->d_etw && ctx->ebk_valid) || ctx->force_waves == 4) return launch_bootstrap_w<11, 4>(ctx, a, s, lut);
-        // whole rounds of 4 gates per CU in one launch; a remainder with 1 / 2 / 3 gates per workgroup, one workgroup per CU
-        // (a gate's two waves then share their SIMDs with fewer other waves: a single gate takes 0.67 x a full round)
-        if (split_ok(ctx, a, s)) return launch_split(ctx, a, s, rotate);
-        const size_t out_words = mode_out_words(a, 1 << LOGN);
-        // (three gates per CU in the whole rounds where four gates' LDS does not fit: eo_round_gates)
-        const size_t cus = (size_t)ctx->num_cus, round = (size_t)ctx->eo_round * cus, count = (size_t)a.count;
-        const size_t full = count / round * round, rem = count - full;
-        if (full)
-            if (int rc = ctx->eo_round == 4 ? launch_bootstrap_n2048_g<4>(ctx, seg(0, full, out_words), s, lut) : launch_bootstrap_n2048_g<3>(ctx, seg(0, full, out_words), s, lut)) return rc;
-        if (!rem) return 0;
-        const BootstrapArgs tail = seg(full, rem, out_words);
-        const LutRef tl = lut_segment(lut, full);
-        if (rem <= cus) return launch_bootstrap_n2048_g<1>(ctx, tail, s, tl);
-        if (rem <= 2 * cus) return launch_bootstrap_n2048_g<2>(ctx, tail, s, tl);
-        if (rem <= 3 * cus) return launch_bootstrap_n2048_g<3>(ctx, tail, s, tl);      // (always, when eo_round is 3)
-        return launch_bootstrap_n2048_g<4>(ctx, tail, s, tl);
-    }
+//   a last whole round and a remainder of up to rr gates per CU together (rr_applies): ONE launch of five or six gates per CU, (4 + rem / CUs) / 4
+//                                    rounds instead of 2 (1,280 gates 9.3 -> 8.2 ms; profiles/r06/pair_rr_sweep.log)
+// RTFHE_FORCE_WAVES=1|2|4|8 forces one shape for the whole batch (4, 8: one gate per wave in 4- / 8-wave workgroups).  A programmable
+// bootstrap takes the same shapes on the k_pbs_* twins.
+int launch_bootstrap_n1024(rtfhe_ctx* ctx, const BootstrapArgs& a, hipStream_t s, const LutRef& lut) {
+    const int force = ctx->force_waves;
+    if (force == 1) return Wg::launch(ctx, 1, a, s, lut);
+    if (force == 2) return Pair::launch(ctx, 4, a, s, lut);
+    if (force == 4 || force == 8) return Wave10::launch(ctx, force, a, s, lut);
+    return walk_ladder(ctx, a, s, lut, 4, rr_applies(ctx, (size_t)a.count), [&](const BootstrapArgs& b, const LutRef& l, int gates, bool tail) {
+        if (!tail) return Pair::launch(ctx, 4, b, s, l);
+        if (gates > 4) return PairRr::launch(ctx, gates, b, s, l);
+        if ((size_t)b.count <= (size_t)ctx->wg_max) return Wg::launch(ctx, 1, b, s, l);
+        const bool p4 = ctx->p4bk_valid && (b.mode == MODE_EXTRACT || b.mode == MODE_BLIND_ROTATE);      // (a split MODE_GATE batch comes here in MODE_EXTRACT)
+        if (const int g4 = p4 ? pair4_tail_gates(ctx, (size_t)b.count) : 0) return Pair4::launch(ctx, g4, b, s, l);
+        return Pair::launch(ctx, gates < 2 ? 2 : gates, b, s, l);
+    });
+}
+
+// N = 2048: two waves per transform (two waves per SIMD, no AGPR traffic) in whole rounds of eo_round gates per CU and a tail.  Up to two gates per
+// CU: four waves per gate, so that no SIMD is left with a lone wave (single gate 9.78 -> 5.84 ms, 512 gates 9.91 -> 7.8 ms,
+// profiles/r04/n2048_four_waves_per_gate_ab.log); the fused key switch stays on the two-wave kernels.  Without the tables or the key layout of
+// those kernels, and under RTFHE_FORCE_WAVES=4: one wave per gate (inverse pass-1/untwist twiddles in global memory: 4 gates per CU fit).
+int launch_bootstrap_n2048(rtfhe_ctx* ctx, const BootstrapArgs& a, hipStream_t s, const LutRef& lut) {
+    if (!(ctx->d_etw && ctx->ebk_valid) || ctx->force_waves == 4) return Wave11::launch(ctx, 4, a, s, lut);
+    return walk_ladder(ctx, a, s, lut, ctx->eo_round, false, [&](const BootstrapArgs& b, const LutRef& l, int gates, bool) {
+        const bool four = gates <= 2 && ctx->eo4 && (b.mode == MODE_EXTRACT || b.mode == MODE_BLIND_ROTATE);
+        return four ? Eo4::launch(ctx, gates, b, s, l) : Eo::launch(ctx, gates, b, s, l);
+    });
 }
 
 // Every (kernel family, gates per workgroup) the dispatch above can launch fits the CU's LDS at the longest mask the context accepts
 // (NPAD_MAX); where a family takes fewer gates at long masks, the function that prime_fft_kernels decides with is the one checked here.
-static_assert(PairLds::bytes(4, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_pair, 4 gates");
-static_assert(WgLds<10, 3>::bytes(NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_wg");
-static_assert(Pair4Lds::bytes(3, NPAD_MAX) <= LDS_LIMIT && Pair4Lds::bytes(2, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_pair4, 2 and 3 gates");
-static_assert(bootstrap_lds_bytes<10>(4, NPAD_MAX, bootstrap_dual_xbuf(10, 4)) <= LDS_LIMIT, "k_bootstrap<10>, 4 waves");
-static_assert(bootstrap_lds_bytes<10>(8, NPAD_MAX, bootstrap_dual_xbuf(10, 8)) <= LDS_LIMIT, "k_bootstrap<10>, 8 waves");
+static_assert(Pair::fits(NPAD_MAX) && Wg::fits(NPAD_MAX) && Pair4::fits(NPAD_MAX) && Wave10::fits(NPAD_MAX) && Wave11::fits(NPAD_MAX) && Eo4::fits(NPAD_MAX), "every shape at every mask length");
 static_assert(rr_fit<PairRrLds>(640) == 6 && rr_fit<PairRrLds>(704) == 5 && rr_fit<PairRrLds>(NPAD_MAX) == 5, "k_bootstrap_pair_rr: six gates per CU up to n = 639, five beyond");
-static_assert(PairRrLds::bytes(rr_fit<PairRrLds>(NPAD_MAX), NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_pair_rr at the longest mask");
-static_assert(bootstrap_lds_bytes<11>(4, NPAD_MAX, bootstrap_dual_xbuf(11, 4)) <= LDS_LIMIT, "k_bootstrap<11>, 4 waves");
+static_assert(PairRr::fits(NPAD_MAX, rr_fit<PairRrLds>(NPAD_MAX)), "k_bootstrap_pair_rr at the longest mask");
 static_assert(eo_round_gates(704) == 4 && eo_round_gates(NPAD_MAX) == 3, "k_bootstrap_eo: four gates per CU up to n = 703, three beyond");
-static_assert(EoLds::bytes(eo_round_gates(NPAD_MAX), NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_eo at the longest mask");
-static_assert(Eo4Lds::bytes(2, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_eo4, 2 gates");
+static_assert(Eo::fits(NPAD_MAX, eo_round_gates(NPAD_MAX)), "k_bootstrap_eo at the longest mask");
 
 // which second key layout the dispatch above reads for a batch of `count` gates in `mode` (0 = none)
 enum { LAYOUT_NONE = 0, LAYOUT_P4 = 1, LAYOUT_EO = 2 };
 int layout_needed(const rtfhe_ctx* ctx, size_t count, int mode) {
     if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR) return LAYOUT_NONE;
     if (ctx->logn == 11) return ctx->force_waves == 4 ? LAYOUT_NONE : LAYOUT_EO;
-    if (ctx->force_waves || ctx->pair4 < 2) return LAYOUT_NONE;
-    const size_t cus = (size_t)ctx->num_cus, rem = count % (4 * cus);
+    if (ctx->force_waves) return LAYOUT_NONE;
     if (rr_applies(ctx, count)) return LAYOUT_NONE;      // the remainder rides with the last whole round (k_bootstrap_pair_rr reads d_bk)
-    // (a MODE_GATE batch reaches the four-wave kernel through the split path only, as MODE_EXTRACT: without the matrix form of the key it stays on the fused kernels)
+    // (a MODE_GATE batch reaches the four-wave kernel through the split path only, as MODE_EXTRACT: without the matrix form of the key it stays on the fused
+    // kernels.  This runs before the stream's scratch exists, so it cannot ask split_ok: it restates the part of it that is known by now.)
     if (mode == MODE_GATE && !(ctx->d_ksmat && ctx->ks_mm_min > 0 && count >= (size_t)ctx->ks_mm_min)) return LAYOUT_NONE;
-    return (rem > (size_t)ctx->wg_max && rem <= (size_t)(ctx->pair4 < 3 ? 2 : 3) * cus) ? LAYOUT_P4 : LAYOUT_NONE;
+    return pair4_tail_gates(ctx, count % ((size_t)4 * ctx->num_cus)) ? LAYOUT_P4 : LAYOUT_NONE;
 }
 
 }  // namespace
@@ -278,7 +226,7 @@ std::vector<cplx> HostTw::q4_table() const {
 namespace rtfhe_host {
 
 int launch_bootstrap_fft(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, const LutRef& lut) {
-    return ctx->logn == 10 ? launch_bootstrap_t<10>(ctx, a, s, lut) : launch_bootstrap_t<11>(ctx, a, s, lut);
+    return ctx->logn == 10 ? launch_bootstrap_n1024(ctx, a, s, lut) : launch_bootstrap_n2048(ctx, a, s, lut);
 }
 
 // The key spectra once more in the layout a kernel family reads (derived from d_bk on this context's device), built by the first batch whose
@@ -325,47 +273,24 @@ int rebuild_derived_keys(rtfhe_ctx* ctx) {
     return 0;
 }
 
-// grants every bootstrap kernel of this context's parameter set, and its programmable-bootstrap, many-LUT and encrypted-table twins, its dynamic
-// LDS once, at context creation
-template <typename KG, typename KP, typename KM>
-static int allow_twins(rtfhe_ctx* ctx, KG kg, KP kp, KM km, KM ke, KM kmr, KM ker, size_t bytes) {
-    if (int rc = allow_lds(ctx, kg, bytes)) return rc;
-    if (int rc = allow_lds(ctx, kp, bytes)) return rc;
-    for (KM k : {km, ke, kmr, ker})
-        if (int rc = allow_lds(ctx, k, bytes)) return rc;
-    return 0;
-}
+// grants every bootstrap kernel of this context's parameter set, and its twins, its dynamic LDS once, at context creation: the families the
+// dispatch above launches from, each at the gate counts its Family lists
 int prime_fft_kernels(rtfhe_ctx* ctx) {
     const int npad = (ctx->p.n + 1 + 63) / 64 * 64;
     if (ctx->logn == 10) {
-        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, 4>, k_pbs_round_pair<3, 6, 8, 2, KSQ, 4, false>, k_pbs_round_pair<3, 6, 8, 2, KSQ, 4, true>, PairLds::bytes(4, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, 3>, k_pbs_round_pair<3, 6, 8, 2, KSQ, 3, false>, k_pbs_round_pair<3, 6, 8, 2, KSQ, 3, true>, PairLds::bytes(3, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_many_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_enc_pair<3, 6, 8, 2, KSQ, 2>, k_pbs_round_pair<3, 6, 8, 2, KSQ, 2, false>, k_pbs_round_pair<3, 6, 8, 2, KSQ, 2, true>, PairLds::bytes(2, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_many_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_enc_wg<10, 3, 6, 8, 2, KSQ>, k_pbs_round_wg<10, 3, 6, 8, 2, KSQ, false>, k_pbs_round_wg<10, 3, 6, 8, 2, KSQ, true>, WgLds<10, 3>::bytes(npad))) return rc;
+        if (int rc = Pair::prime(ctx, npad)) return rc;
+        if (int rc = Wg::prime(ctx, npad)) return rc;
         // the time-sliced launch: as many gates per CU (five or six) as this mask length leaves room for in 160 KiB of LDS
-        {
-            const int fit = rr_fit<PairRrLds>(npad);
-            if (ctx->rr > fit) ctx->rr = fit;
-            if (ctx->rr >= 5)
-                if (int rc = allow_twins(ctx, k_bootstrap_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_many_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_enc_pair_rr<3, 6, 8, 2, KSQ>, k_pbs_round_pair_rr<3, 6, 8, 2, KSQ, false>, k_pbs_round_pair_rr<3, 6, 8, 2, KSQ, true>, PairRrLds::bytes(ctx->rr, npad))) return rc;
-        }
-        if (int rc = allow_twins(ctx, k_bootstrap_pair4<3, 6, 3>, k_pbs_pair4<3, 6, 3>, k_pbs_many_pair4<3, 6, 3>, k_pbs_enc_pair4<3, 6, 3>, k_pbs_round_pair4<3, 6, 3, false>, k_pbs_round_pair4<3, 6, 3, true>, Pair4Lds::bytes(3, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_pair4<3, 6, 2>, k_pbs_pair4<3, 6, 2>, k_pbs_many_pair4<3, 6, 2>, k_pbs_enc_pair4<3, 6, 2>, k_pbs_round_pair4<3, 6, 2, false>, k_pbs_round_pair4<3, 6, 2, true>, Pair4Lds::bytes(2, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 4>, k_pbs<10, 3, 6, 8, 2, KSQ, 4>, k_pbs_many<10, 3, 6, 8, 2, KSQ, 4>, k_pbs_enc<10, 3, 6, 8, 2, KSQ, 4>, k_pbs_round<10, 3, 6, 8, 2, KSQ, 4, false>, k_pbs_round<10, 3, 6, 8, 2, KSQ, 4, true>, bootstrap_lds_bytes<10>(4, npad, bootstrap_dual_xbuf(10, 4)))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap<10, 3, 6, 8, 2, KSQ, 8>, k_pbs<10, 3, 6, 8, 2, KSQ, 8>, k_pbs_many<10, 3, 6, 8, 2, KSQ, 8>, k_pbs_enc<10, 3, 6, 8, 2, KSQ, 8>, k_pbs_round<10, 3, 6, 8, 2, KSQ, 8, false>, k_pbs_round<10, 3, 6, 8, 2, KSQ, 8, true>, bootstrap_lds_bytes<10>(8, npad, bootstrap_dual_xbuf(10, 8)))) return rc;
-    } else {
-        if (int rc = allow_twins(ctx, k_bootstrap<11, 3, 6, 8, 2, KSQ, 4>, k_pbs<11, 3, 6, 8, 2, KSQ, 4>, k_pbs_many<11, 3, 6, 8, 2, KSQ, 4>, k_pbs_enc<11, 3, 6, 8, 2, KSQ, 4>, k_pbs_round<11, 3, 6, 8, 2, KSQ, 4, false>, k_pbs_round<11, 3, 6, 8, 2, KSQ, 4, true>, bootstrap_lds_bytes<11>(4, npad, bootstrap_dual_xbuf(11, 4)))) return rc;
-        // whole rounds of four gates per CU where their LDS fits, of three at the longest masks (the four-gate kernel is then never launched)
-        ctx->eo_round = eo_round_gates(npad);
-        if (ctx->eo_round == 4)
-            if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 4>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 4, false>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 4, true>, EoLds::bytes(4, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 3>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 3, false>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 3, true>, EoLds::bytes(3, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 2>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 2, false>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 2, true>, EoLds::bytes(2, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_many_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_enc_eo<3, 6, 8, 2, KSQ, 1>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 1, false>, k_pbs_round_eo<3, 6, 8, 2, KSQ, 1, true>, EoLds::bytes(1, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo4<3, 6, 2>, k_pbs_eo4<3, 6, 2>, k_pbs_many_eo4<3, 6, 2>, k_pbs_enc_eo4<3, 6, 2>, k_pbs_round_eo4<3, 6, 2, false>, k_pbs_round_eo4<3, 6, 2, true>, Eo4Lds::bytes(2, npad))) return rc;
-        if (int rc = allow_twins(ctx, k_bootstrap_eo4<3, 6, 1>, k_pbs_eo4<3, 6, 1>, k_pbs_many_eo4<3, 6, 1>, k_pbs_enc_eo4<3, 6, 1>, k_pbs_round_eo4<3, 6, 1, false>, k_pbs_round_eo4<3, 6, 1, true>, Eo4Lds::bytes(1, npad))) return rc;
+        ctx->rr = std::min(ctx->rr, rr_fit<PairRrLds>(npad));
+        if (int rc = PairRr::prime(ctx, npad, ctx->rr)) return rc;
+        if (int rc = Pair4::prime(ctx, npad)) return rc;
+        return Wave10::prime(ctx, npad);
     }
-    return 0;
+    if (int rc = Wave11::prime(ctx, npad)) return rc;
+    // whole rounds of four gates per CU where their LDS fits, of three at the longest masks (the four-gate kernel is then never launched)
+    ctx->eo_round = eo_round_gates(npad);
+    if (int rc = Eo::prime(ctx, npad, ctx->eo_round)) return rc;
+    return Eo4::prime(ctx, npad);
 }
 
 }  // namespace rtfhe_host

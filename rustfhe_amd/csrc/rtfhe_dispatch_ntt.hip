@@ -78,94 +78,38 @@ std::vector<double> ntt_halves_device_table() {
     return t;
 }
 
+// ---- the kernel shapes of this backend (Shape / Family: rtfhe_host.hpp) ----
 template <int W>
-int launch_bootstrap_ntt_w(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s) {
-    auto k = k_bootstrap_ntt<3, 6, 8, 2, KSQ, W>;
-    const size_t lds = ntt_lds_bytes(W, b.npad);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    NttBootstrapArgs a{b, ctx->d_ntt_tw, ctx->d_ntt_bk};
-    hipLaunchKernelGGL(k, dim3((b.count + W - 1) / W), dim3(64 * W), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
-}
-
+struct NttWaveShape : GatesPerWorkgroup<W, 64> {        // one wave per gate, W gates per workgroup (rtfhe_kernels_ntt.hpp)
+    static GateKernel<NttBootstrapArgs> kernels() { return {k_bootstrap_ntt<3, 6, 8, 2, KSQ, W>}; }
+    static constexpr size_t lds(int npad) { return ntt_lds_bytes(W, npad); }
+    static NttBootstrapArgs args(const rtfhe_ctx* ctx, const BootstrapArgs& b) { return {b, ctx->d_ntt_tw, ctx->d_ntt_bk}; }
+};
 template <int GATES>
-int launch_bootstrap_ntt_pair_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s) {
-    auto k = k_bootstrap_ntt_pair<3, 6, 8, 2, KSQ, GATES>;
-    const size_t lds = NttPairLds::bytes(GATES, b.npad);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    NttBootstrapArgs a{b, ctx->d_ntt_tw, ctx->d_ntt_bk};
-    hipLaunchKernelGGL(k, dim3((b.count + GATES - 1) / GATES), dim3(128 * GATES), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
-}
-
-// NTT backend, one gate per 8-wave workgroup (the latency shape)
-int launch_bootstrap_ntt_wg(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s) {
-    auto k = k_bootstrap_ntt_wg<3, 6, 8, 2, KSQ>;
-    const size_t lds = NttWgLds::bytes(b.npad);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    NttBootstrapArgs a{b, ctx->d_ntt_tw, ctx->d_ntt_bk};
-    hipLaunchKernelGGL(k, dim3(b.count), dim3(512), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
-}
-
-// NTT backend, two waves per gate.  Whole rounds of 4 gates per CU in one launch; a remainder runs with 1 / 2 / 3 gates per
-// workgroup (one workgroup per CU): with fewer gates per CU a gate's two waves share their SIMDs with fewer other waves -- a
-// circuit wave of 1-3 gates takes 0.67 x the time of a full round instead of all of it.
-int launch_bootstrap_ntt_pair(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
-    if (split_ok(ctx, a, s)) return launch_split(ctx, a, s, launch_bootstrap_ntt_pair);
-    const size_t out_words = mode_out_words(a, ntt::N);
-    const size_t cus = (size_t)ctx->num_cus, round = 4 * cus, count = (size_t)a.count;
-    const size_t full = count / round * round, rem = count - full;
-    if (full)
-        if (int rc = launch_bootstrap_ntt_pair_g<4>(ctx, batch_segment(ctx, a, 0, full, out_words), s)) return rc;
-    if (!rem) return 0;
-    const BootstrapArgs tail = batch_segment(ctx, a, full, rem, out_words);
-    if (rem <= cus) return ctx->force_waves == 2 ? launch_bootstrap_ntt_pair_g<1>(ctx, tail, s) : launch_bootstrap_ntt_wg(ctx, tail, s);
-    if (rem <= 2 * cus) return launch_bootstrap_ntt_pair_g<2>(ctx, tail, s);
-    if (rem <= 3 * cus) return launch_bootstrap_ntt_pair_g<3>(ctx, tail, s);
-    return launch_bootstrap_ntt_pair_g<4>(ctx, tail, s);
-}
-
+struct NttPairShape : GatesPerWorkgroup<GATES, 128> {   // two waves per gate
+    static GateKernel<NttBootstrapArgs> kernels() { return {k_bootstrap_ntt_pair<3, 6, 8, 2, KSQ, GATES>}; }
+    static constexpr size_t lds(int npad) { return NttPairLds::bytes(GATES, npad); }
+    static NttBootstrapArgs args(const rtfhe_ctx* ctx, const BootstrapArgs& b) { return {b, ctx->d_ntt_tw, ctx->d_ntt_bk}; }
+};
 template <int GATES>
-int launch_bootstrap_ntt_halves_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s) {
-    auto k = k_bootstrap_ntt_halves<3, 6, 8, 2, KSQ, GATES>;
-    const size_t lds = NttHalvesLds::bytes(GATES, b.npad);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    NttHalvesArgs a{b, ctx->d_ntt_tw, ctx->d_ntt_bk};
-    hipLaunchKernelGGL(k, dim3((b.count + GATES - 1) / GATES), dim3(128 * GATES), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
-}
+struct NttWgShape : GatesPerWorkgroup<GATES, 512> {     // one gate per 8-wave workgroup, the latency shape (rtfhe_kernels_ntt_wg.hpp)
+    static GateKernel<NttBootstrapArgs> kernels() { return {k_bootstrap_ntt_wg<3, 6, 8, 2, KSQ>}; }
+    static constexpr size_t lds(int npad) { return NttWgLds::bytes(npad); }
+    static NttBootstrapArgs args(const rtfhe_ctx* ctx, const BootstrapArgs& b) { return {b, ctx->d_ntt_tw, ctx->d_ntt_bk}; }
+};
+template <int GATES>
+struct NttHalvesShape : GatesPerWorkgroup<GATES, 128> { // N = 2048: two waves per gate, one per half of the transform (rtfhe_kernels_ntt_halves.hpp)
+    static GateKernel<NttHalvesArgs> kernels() { return {k_bootstrap_ntt_halves<3, 6, 8, 2, KSQ, GATES>}; }
+    static constexpr size_t lds(int npad) { return NttHalvesLds::bytes(GATES, npad); }
+    static NttHalvesArgs args(const rtfhe_ctx* ctx, const BootstrapArgs& b) { return {b, ctx->d_ntt_tw, ctx->d_ntt_bk}; }
+};
+typedef Family<NttWaveShape, 4> NttWave;
+typedef Family<NttPairShape, 1, 2, 3, 4> NttPair;
+typedef Family<NttWgShape, 1> NttWg;
+typedef Family<NttHalvesShape, 1, 2, 3, 4> NttHalves;
 
-// NTT backend at N = 2048: the same ladder (NTT_HALVES_ROUND gates per CU in whole rounds, fewer per workgroup for a remainder)
-constexpr int NTT_HALVES_ROUND = 4;
-int launch_bootstrap_ntt_halves(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
-    if (split_ok(ctx, a, s)) return launch_split(ctx, a, s, launch_bootstrap_ntt_halves);
-    const size_t out_words = mode_out_words(a, 2048);
-    const size_t cus = (size_t)ctx->num_cus, round = NTT_HALVES_ROUND * cus, count = (size_t)a.count;
-    const size_t full = count / round * round, rem = count - full;
-    if (full)
-        if (int rc = launch_bootstrap_ntt_halves_g<NTT_HALVES_ROUND>(ctx, batch_segment(ctx, a, 0, full, out_words), s)) return rc;
-    if (!rem) return 0;
-    const BootstrapArgs tail = batch_segment(ctx, a, full, rem, out_words);
-    if (rem <= cus || NTT_HALVES_ROUND == 1) return launch_bootstrap_ntt_halves_g<1>(ctx, tail, s);
-    if (rem <= 2 * cus || NTT_HALVES_ROUND == 2) return launch_bootstrap_ntt_halves_g<2>(ctx, tail, s);
-    if (rem <= 3 * cus || NTT_HALVES_ROUND == 3) return launch_bootstrap_ntt_halves_g<3>(ctx, tail, s);
-    return launch_bootstrap_ntt_halves_g<4>(ctx, tail, s);
-}
-
-// Every (kernel family, gates per workgroup) the dispatch above can launch fits the CU's LDS at the longest mask the context accepts
-static_assert(NttPairLds::bytes(4, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_ntt_pair, 4 gates");
-static_assert(ntt_lds_bytes(4, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_ntt, 4 waves");
-static_assert(NttWgLds::bytes(NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_ntt_wg");
-static_assert(NttHalvesLds::bytes(NTT_HALVES_ROUND, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_ntt_halves, a whole round's gates");
+// Every (kernel family, gates per workgroup) the dispatch can launch fits the CU's LDS at the longest mask the context accepts
+static_assert(NttPair::fits(NPAD_MAX) && NttWave::fits(NPAD_MAX) && NttWg::fits(NPAD_MAX) && NttHalves::fits(NPAD_MAX), "every shape at every mask length");
 
 }  // namespace
 
@@ -203,48 +147,33 @@ int ntt_prepare(rtfhe_ctx* ctx) {
     return 0;
 }
 
+// Two waves per gate: 11.5 ms per 1024 gates vs 13.3 ms one wave per gate in 4-wave workgroups (RTFHE_FORCE_WAVES=4, N = 1024 only); 6-wave
+// workgroups of the latter measured slower still (64 k vs 76 k gates/s): LDS-bound.  Both rings walk the ladder in rounds of 4 gates per CU; at
+// N = 1024 a tail of at most one gate per CU takes the latency shape (RTFHE_FORCE_WAVES=2: stays on two waves per gate).
 int launch_bootstrap_ntt(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
-    // two waves per gate: 11.5 ms per 1024 gates vs 13.3 ms one wave per gate in 4-wave workgroups (RTFHE_FORCE_WAVES=4);
-    // 6-wave workgroups of the latter measured slower still (64 k vs 76 k gates/s): LDS-bound
-    if (ctx->logn == 11) return launch_bootstrap_ntt_halves(ctx, a, s);
-    if (ctx->force_waves == 4) return launch_bootstrap_ntt_w<4>(ctx, a, s);
-    return launch_bootstrap_ntt_pair(ctx, a, s);
+    if (ctx->logn == 10 && ctx->force_waves == 4) return NttWave::launch(ctx, 4, a, s);
+    return walk_ladder(ctx, a, s, LutRef{}, 4, false, [&](const BootstrapArgs& b, const LutRef&, int gates, bool tail) {
+        if (ctx->logn == 11) return NttHalves::launch(ctx, gates, b, s);
+        return tail && gates == 1 && ctx->force_waves != 2 ? NttWg::launch(ctx, 1, b, s) : NttPair::launch(ctx, gates, b, s);
+    });
 }
 
 // external product of `count` TRLWE samples with bk[idx[g]] on the NTT backend (stage-level entry point)
 int launch_extprod_ntt(rtfhe_ctx* ctx, const int32_t* d_idx, const uint32_t* d_in, uint32_t* d_out, int32_t count, hipStream_t s) {
     if (ctx->logn == 11) {
-        NttHalvesExtProdArgs a{ctx->d_ntt_tw, ctx->d_ntt_bk, d_idx, d_in, d_out, count};
         const size_t lds = NttHalvesLds::TW + (size_t)2 * 2048 * 4 + 2 * NttHalvesLds::XB;
-        if (int rc = allow_lds(ctx, k_external_product_ntt_halves<3, 6>, lds)) return rc;
-        hipLaunchKernelGGL((k_external_product_ntt_halves<3, 6>), dim3(a.count), dim3(128), lds, s, a);
-    } else {
-        constexpr int W = 4;
-        NttExtProdArgs a{ctx->d_ntt_tw, ctx->d_ntt_bk, d_idx, d_in, d_out, count};
-        const size_t lds = ntt_lds_bytes(W, 0);
-        if (int rc = allow_lds(ctx, k_external_product_ntt<3, 6, W>, lds)) return rc;
-        hipLaunchKernelGGL((k_external_product_ntt<3, 6, W>), dim3((a.count + W - 1) / W), dim3(64 * W), lds, s, a);
+        return launch_kernel(ctx, k_external_product_ntt_halves<3, 6>, dim3(count), dim3(128), lds, s, NttHalvesExtProdArgs{ctx->d_ntt_tw, ctx->d_ntt_bk, d_idx, d_in, d_out, count}, false);
     }
-    HIPCHECK(ctx, hipGetLastError());
-    return 0;
+    constexpr int W = 4;
+    return launch_kernel(ctx, k_external_product_ntt<3, 6, W>, dim3((count + W - 1) / W), dim3(64 * W), ntt_lds_bytes(W, 0), s, NttExtProdArgs{ctx->d_ntt_tw, ctx->d_ntt_bk, d_idx, d_in, d_out, count}, false);
 }
 
 int prime_ntt_kernels(rtfhe_ctx* ctx) {
     const int npad = (ctx->p.n + 1 + 63) / 64 * 64;
-    if (ctx->logn == 10) {
-        if (int rc = allow_lds(ctx, k_bootstrap_ntt_pair<3, 6, 8, 2, KSQ, 4>, NttPairLds::bytes(4, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_ntt_pair<3, 6, 8, 2, KSQ, 3>, NttPairLds::bytes(3, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_ntt_pair<3, 6, 8, 2, KSQ, 2>, NttPairLds::bytes(2, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_ntt_pair<3, 6, 8, 2, KSQ, 1>, NttPairLds::bytes(1, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_ntt<3, 6, 8, 2, KSQ, 4>, ntt_lds_bytes(4, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_ntt_wg<3, 6, 8, 2, KSQ>, NttWgLds::bytes(npad))) return rc;
-    } else {
-        if (int rc = allow_lds(ctx, k_bootstrap_ntt_halves<3, 6, 8, 2, KSQ, 4>, NttHalvesLds::bytes(4, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_ntt_halves<3, 6, 8, 2, KSQ, 3>, NttHalvesLds::bytes(3, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_ntt_halves<3, 6, 8, 2, KSQ, 2>, NttHalvesLds::bytes(2, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_ntt_halves<3, 6, 8, 2, KSQ, 1>, NttHalvesLds::bytes(1, npad))) return rc;
-    }
-    return 0;
+    if (ctx->logn == 11) return NttHalves::prime(ctx, npad);
+    if (int rc = NttPair::prime(ctx, npad)) return rc;
+    if (int rc = NttWave::prime(ctx, npad)) return rc;
+    return NttWg::prime(ctx, npad);
 }
 
 }  // namespace rtfhe_host

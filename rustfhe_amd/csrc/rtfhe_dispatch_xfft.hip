@@ -2,6 +2,7 @@
 // tables, the split key spectra, kernel shapes per batch.
 #include "rtfhe_host.hpp"
 
+#include <algorithm>
 #include <cmath>
 
 #include "rtfhe_kernels_xfft.hpp"
@@ -91,86 +92,34 @@ std::vector<cplx> xfft2_device_table() {
     return tb;
 }
 
+// ---- the kernel shapes of this backend (Shape / Family: rtfhe_host.hpp) ----
 template <int GATES>
-int launch_xpair_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s) {
-    auto k = k_bootstrap_xpair<3, 6, 8, 2, KSQ, GATES>;
-    const size_t lds = XPairLds::bytes(GATES, b.npad);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    XBootstrapArgs a{b, ctx->d_xtw, ctx->d_xbk};
-    hipLaunchKernelGGL(k, dim3((b.count + GATES - 1) / GATES), dim3(128 * GATES), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
-}
-
+struct XPairShape : GatesPerWorkgroup<GATES, 128> {     // N = 1024: two waves per gate (rtfhe_kernels_xfft.hpp)
+    static GateKernel<XBootstrapArgs> kernels() { return {k_bootstrap_xpair<3, 6, 8, 2, KSQ, GATES>}; }
+    static constexpr size_t lds(int npad) { return XPairLds::bytes(GATES, npad); }
+    static XBootstrapArgs args(const rtfhe_ctx* ctx, const BootstrapArgs& b) { return {b, ctx->d_xtw, ctx->d_xbk}; }
+};
+// GATES = 5 or 6 gates on the four wave pairs of every CU, time-sliced (rtfhe_kernels_xfft_rr.hpp; the mirror backend's k_bootstrap_pair_rr on this
+// backend's arithmetic)
 template <int GATES>
-int launch_xquad_g(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s) {
-    auto k = k_bootstrap_xquad<3, 6, 8, 2, KSQ, GATES>;
-    const size_t lds = XQuadLds::bytes(GATES, b.npad);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    XBootstrapArgs a{b, ctx->d_xtw, ctx->d_xbk};
-    hipLaunchKernelGGL(k, dim3((b.count + GATES - 1) / GATES), dim3(256 * GATES), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
-}
+struct XPairRrShape : WorkgroupPerCu {
+    static GateKernel<XBootstrapArgs> kernels() { return {k_bootstrap_xpair_rr<3, 6, 8, 2, KSQ>}; }
+    static constexpr size_t lds(int npad) { return XPairRrLds::bytes(GATES, npad); }
+    static XBootstrapArgs args(const rtfhe_ctx* ctx, const BootstrapArgs& b) { return {b, ctx->d_xtw, ctx->d_xbk}; }
+};
+template <int GATES>
+struct XQuadShape : GatesPerWorkgroup<GATES, 256> {     // N = 2048: four waves per gate, two waves per SIMD (rtfhe_kernels_xfft2.hpp)
+    static GateKernel<XBootstrapArgs> kernels() { return {k_bootstrap_xquad<3, 6, 8, 2, KSQ, GATES>}; }
+    static constexpr size_t lds(int npad) { return XQuadLds::bytes(GATES, npad); }
+    static XBootstrapArgs args(const rtfhe_ctx* ctx, const BootstrapArgs& b) { return {b, ctx->d_xtw, ctx->d_xbk}; }
+};
+typedef Family<XPairShape, 1, 2, 3, 4> XPair;
+typedef Family<XPairRrShape, 5, 6> XPairRr;
+typedef Family<XQuadShape, 1, 2> XQuad;
 
-// N = 2048: whole rounds of 2 gates per CU (four waves per gate: two waves per SIMD); a remainder of at most one gate per CU runs one gate per workgroup
-int launch_xquad(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
-    if (split_ok(ctx, a, s)) return launch_split(ctx, a, s, launch_xquad);
-    const size_t out_words = mode_out_words(a, 2048);
-    const size_t cus = (size_t)ctx->num_cus, round = 2 * cus, count = (size_t)a.count;
-    const size_t full = count / round * round, rem = count - full;
-    if (full)
-        if (int rc = launch_xquad_g<2>(ctx, batch_segment(ctx, a, 0, full, out_words), s)) return rc;
-    if (!rem) return 0;
-    const BootstrapArgs tail = batch_segment(ctx, a, full, rem, out_words);
-    return rem <= cus ? launch_xquad_g<1>(ctx, tail, s) : launch_xquad_g<2>(ctx, tail, s);
-}
-
-// 4 x CUs < count <= 6 x CUs gates on the four wave pairs of every CU, time-sliced (rtfhe_kernels_xfft_rr.hpp; the mirror backend's
-// k_bootstrap_pair_rr on this backend's arithmetic)
-int launch_xpair_rr(rtfhe_ctx* ctx, BootstrapArgs b, hipStream_t s) {
-    auto k = k_bootstrap_xpair_rr<3, 6, 8, 2, KSQ>;
-    const int wgs = ctx->num_cus, most = (b.count + wgs - 1) / wgs;
-    if (b.count < 4 * wgs || most > XPairRrLds::GMAX)
-        return fail(ctx, RTFHE_ERR_STATE, "k_bootstrap_xpair_rr: " + std::to_string(b.count) + " gates on " + std::to_string(wgs) + " CUs is not a shape it serves");
-    const size_t lds = XPairRrLds::bytes(most, b.npad);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    XBootstrapArgs a{b, ctx->d_xtw, ctx->d_xbk};
-    hipLaunchKernelGGL(k, dim3(wgs), dim3(512), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
-}
-
-// whole rounds of 4 gates per CU in one launch; a remainder with 1 / 2 / 3 gates per workgroup, one workgroup per CU (as the other two-waves-per-gate
-// kernels); behind at least one whole round, a remainder of up to 2 gates per CU rides with the last whole round in one time-sliced launch
-int launch_xpair(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
-    if (split_ok(ctx, a, s)) return launch_split(ctx, a, s, launch_xpair);
-    const size_t out_words = mode_out_words(a, 1024);
-    const size_t cus = (size_t)ctx->num_cus, round = 4 * cus, count = (size_t)a.count;
-    const size_t full = count / round * round, rem = count - full;
-    const int rr = ctx->xrr > XPairRrLds::GMAX ? XPairRrLds::GMAX : ctx->xrr;
-    if (rr > 4 && full && rem && round + rem <= (size_t)rr * cus) {
-        if (full > round)
-            if (int rc = launch_xpair_g<4>(ctx, batch_segment(ctx, a, 0, full - round, out_words), s)) return rc;
-        return launch_xpair_rr(ctx, batch_segment(ctx, a, full - round, round + rem, out_words), s);
-    }
-    if (full)
-        if (int rc = launch_xpair_g<4>(ctx, batch_segment(ctx, a, 0, full, out_words), s)) return rc;
-    if (!rem) return 0;
-    const BootstrapArgs tail = batch_segment(ctx, a, full, rem, out_words);
-    if (rem <= cus) return launch_xpair_g<1>(ctx, tail, s);
-    if (rem <= 2 * cus) return launch_xpair_g<2>(ctx, tail, s);
-    if (rem <= 3 * cus) return launch_xpair_g<3>(ctx, tail, s);
-    return launch_xpair_g<4>(ctx, tail, s);
-}
-
-// Every (kernel family, gates per workgroup) the dispatch above can launch fits the CU's LDS at the longest mask the context accepts
-static_assert(XPairLds::bytes(4, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_xpair, 4 gates");
-static_assert(XQuadLds::bytes(2, NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_xquad, 2 gates");
-static_assert(rr_fit<XPairRrLds>(NPAD_MAX) == 0 || XPairRrLds::bytes(rr_fit<XPairRrLds>(NPAD_MAX), NPAD_MAX) <= LDS_LIMIT, "k_bootstrap_xpair_rr at the longest mask");
+// Every (kernel family, gates per workgroup) the dispatch can launch fits the CU's LDS at the longest mask the context accepts
+static_assert(XPair::fits(NPAD_MAX) && XQuad::fits(NPAD_MAX), "every shape at every mask length");
+static_assert(XPairRr::fits(NPAD_MAX, rr_fit<XPairRrLds>(NPAD_MAX)), "k_bootstrap_xpair_rr at the longest mask");
 
 }  // namespace
 
@@ -206,45 +155,38 @@ int xfft_prepare(rtfhe_ctx* ctx) {
     return 0;
 }
 
-int launch_bootstrap_xfft(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) { return ctx->logn == 11 ? launch_xquad(ctx, a, s) : launch_xpair(ctx, a, s); }
+// N = 1024: rounds of 4 gates per CU; behind at least one whole round, a remainder of up to xrr - 4 gates per CU rides with the last whole round in
+// one time-sliced launch.  N = 2048: rounds of 2 gates per CU (four waves per gate: two waves per SIMD).
+int launch_bootstrap_xfft(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s) {
+    if (ctx->logn == 11)
+        return walk_ladder(ctx, a, s, LutRef{}, 2, false, [&](const BootstrapArgs& b, const LutRef&, int gates, bool) { return XQuad::launch(ctx, gates, b, s); });
+    const LadderSplit sp = ladder_split((size_t)a.count, (size_t)ctx->num_cus, 4);
+    const int rr = ctx->xrr > XPairRrLds::GMAX ? XPairRrLds::GMAX : ctx->xrr;
+    const bool time_sliced = rr > 4 && sp.full && sp.rem && (size_t)4 * ctx->num_cus + sp.rem <= (size_t)rr * ctx->num_cus;
+    return walk_ladder(ctx, a, s, LutRef{}, 4, time_sliced, [&](const BootstrapArgs& b, const LutRef&, int gates, bool) {
+        return gates > 4 ? XPairRr::launch(ctx, gates, b, s) : XPair::launch(ctx, gates, b, s);
+    });
+}
 
 // external product of `count` TRLWE samples with bk[idx[g]] on this backend (stage-level entry point)
 int launch_extprod_xfft(rtfhe_ctx* ctx, const int32_t* d_idx, const uint32_t* d_in, uint32_t* d_out, int32_t count, hipStream_t s) {
+    const XExtProdArgs a{ctx->d_xtw, ctx->d_xbk, d_idx, d_in, d_out, count};
     if (ctx->logn == 11) {      // one workgroup of two waves per sample
-        XExtProdArgs a{ctx->d_xtw, ctx->d_xbk, d_idx, d_in, d_out, count};
         const size_t lds = (size_t)xfft::XTw2::TOTAL * sizeof(cplx) + (size_t)2 * 2 * Geo<10>::XSLOTS * sizeof(double) + (size_t)2 * 2 * 4 * 64 * sizeof(cplx);
-        if (int rc = allow_lds(ctx, k_external_product_xfft2<3, 6>, lds)) return rc;
-        hipLaunchKernelGGL((k_external_product_xfft2<3, 6>), dim3(count), dim3(128), lds, s, a);
-        HIPCHECK(ctx, hipGetLastError());
-        return 0;
+        return launch_kernel(ctx, k_external_product_xfft2<3, 6>, dim3(count), dim3(128), lds, s, a, false);
     }
     constexpr int W = 2;
-    XExtProdArgs a{ctx->d_xtw, ctx->d_xbk, d_idx, d_in, d_out, count};
     const size_t lds = (size_t)XTw::TOTAL * sizeof(cplx) + (size_t)W * 2 * Geo<10>::XSLOTS * sizeof(double);
-    if (int rc = allow_lds(ctx, k_external_product_xfft<3, 6, W>, lds)) return rc;
-    hipLaunchKernelGGL((k_external_product_xfft<3, 6, W>), dim3((count + W - 1) / W), dim3(64 * W), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    return 0;
+    return launch_kernel(ctx, k_external_product_xfft<3, 6, W>, dim3((count + W - 1) / W), dim3(64 * W), lds, s, a, false);
 }
 
 int prime_xfft_kernels(rtfhe_ctx* ctx) {
     const int npad = (ctx->p.n + 1 + 63) / 64 * 64;
-    if (ctx->logn == 11) {
-        if (int rc = allow_lds(ctx, k_bootstrap_xquad<3, 6, 8, 2, KSQ, 2>, XQuadLds::bytes(2, npad))) return rc;
-        if (int rc = allow_lds(ctx, k_bootstrap_xquad<3, 6, 8, 2, KSQ, 1>, XQuadLds::bytes(1, npad))) return rc;
-        return 0;
-    }
-    if (int rc = allow_lds(ctx, k_bootstrap_xpair<3, 6, 8, 2, KSQ, 4>, XPairLds::bytes(4, npad))) return rc;
-    {   // the time-sliced launch: five or six gates per CU, as many as this mask length leaves room for in 160 KiB of LDS
-        const int fit = rr_fit<XPairRrLds>(npad);
-        ctx->xrr = ctx->rr < fit ? ctx->rr : fit;
-        if (ctx->xrr >= 5)
-            if (int rc = allow_lds(ctx, k_bootstrap_xpair_rr<3, 6, 8, 2, KSQ>, XPairRrLds::bytes(ctx->xrr, npad))) return rc;
-    }
-    if (int rc = allow_lds(ctx, k_bootstrap_xpair<3, 6, 8, 2, KSQ, 3>, XPairLds::bytes(3, npad))) return rc;
-    if (int rc = allow_lds(ctx, k_bootstrap_xpair<3, 6, 8, 2, KSQ, 2>, XPairLds::bytes(2, npad))) return rc;
-    if (int rc = allow_lds(ctx, k_bootstrap_xpair<3, 6, 8, 2, KSQ, 1>, XPairLds::bytes(1, npad))) return rc;
-    return 0;
+    if (ctx->logn == 11) return XQuad::prime(ctx, npad);
+    // the time-sliced launch: five or six gates per CU, as many as this mask length leaves room for in 160 KiB of LDS
+    ctx->xrr = std::min(ctx->rr, rr_fit<XPairRrLds>(npad));
+    if (int rc = XPairRr::prime(ctx, npad, ctx->xrr)) return rc;
+    return XPair::prime(ctx, npad);
 }
 
 }  // namespace rtfhe_host

@@ -18,6 +18,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -345,6 +346,128 @@ int launch_split(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, F blind_rotate)
     a.mode = rtfhe::MODE_EXTRACT; a.ext = samples;
     if (int rc = blind_rotate(ctx, a, s)) return rc;
     return launch_key_switch_mm(ctx, a, samples, s);
+}
+
+// ---- kernel shapes and their launches (the three rtfhe_dispatch_*.hip units) ----
+// One launch: grants the kernel its dynamic LDS (once per device, allow_lds_raw), launches and checks.  counted: a bootstrap launch, which
+// rtfhe_timer_end reports; the stage-level external products are not.
+template <typename K, typename A>
+int launch_kernel(rtfhe_ctx* ctx, K k, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A& a, bool counted = true) {
+    if (int rc = allow_lds(ctx, k, lds)) return rc;
+    hipLaunchKernelGGL(k, grid, block, lds, s, a);
+    HIPCHECK(ctx, hipGetLastError());
+    if (counted) ctx->launches++;
+    return 0;
+}
+
+// The kernels of one shape, all with the same block size, LDS and key layout.  The exact backends have the gate kernel alone; a family of the FP64
+// mirror has its twins beside it: the programmable bootstrap (k_pbs_*), the many-LUT PBS (k_pbs_many_*), the encrypted table (k_pbs_enc_*) and
+// the last two under the rounded decomposition (k_pbs_round_*<.., false / true>).
+template <typename A>
+struct GateKernel { void (*gate)(A); };
+template <typename A>
+struct TwinKernels { void (*gate)(A); void (*pbs)(rtfhe::LutArgs<A>); void (*many)(rtfhe::ManyArgs<A>), (*enc)(rtfhe::ManyArgs<A>), (*many_round)(rtfhe::ManyArgs<A>), (*enc_round)(rtfhe::ManyArgs<A>); };
+// ... of family k_bootstrap`suffix`, the template arguments stated once for all six
+#define RTFHE_TWINS(suffix, ...)                                                                                                         \
+    { k_bootstrap##suffix<__VA_ARGS__>, k_pbs##suffix<__VA_ARGS__>, k_pbs_many##suffix<__VA_ARGS__>, k_pbs_enc##suffix<__VA_ARGS__>,    \
+      k_pbs_round##suffix<__VA_ARGS__, false>, k_pbs_round##suffix<__VA_ARGS__, true> }
+
+// One launch of a kernel family: the gate kernel (k_bootstrap_*) or, for a programmable bootstrap (lut.tv set), its twin (k_pbs_*) with the
+// family's own arguments wrapped in LutArgs.  The twins share shapes, LDS and key layouts, so every choice of the dispatch is made once for all.
+// A many-LUT PBS (lut.shift >= 0) takes k.many, in MODE_EXTRACT, and one with an encrypted table (lut.enc) k.enc, with the same arguments
+// (ManyArgs); in rounded mode (lut.rounded) those two are replaced by k.many_round / k.enc_round.
+template <typename A>
+int launch_twin(rtfhe_ctx* ctx, const TwinKernels<A>& k, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A& a, const LutRef& lut) {
+    if (lut.tv && lut.enc && lut.shift < 0) return fail(ctx, RTFHE_ERR_STATE, "an encrypted table runs on the many-LUT path only (launch_pbs_many)");
+    if (lut.tv && lut.rounded && lut.shift < 0) return fail(ctx, RTFHE_ERR_STATE, "the rounded decomposition runs on the many-LUT path only (launch_pbs_many)");
+    if (lut.tv && lut.shift >= 0) {
+        rtfhe::ManyArgs<A> p{};
+        p.base = a; p.tv = lut.tv; p.tv_idx = lut.idx; p.n_tv = lut.n_tv; p.t = lut.shift;
+        return launch_kernel(ctx, lut.rounded ? (lut.enc ? k.enc_round : k.many_round) : (lut.enc ? k.enc : k.many), grid, block, lds, s, p);
+    }
+    if (lut.tv) return launch_kernel(ctx, k.pbs, grid, block, lds, s, rtfhe::LutArgs<A>{a, lut.tv, lut.idx, lut.n_tv});
+    return launch_kernel(ctx, k.gate, grid, block, lds, s, a);
+}
+// (an exact backend's family: launch_bootstrap has refused a table before it gets here)
+template <typename A>
+int launch_twin(rtfhe_ctx* ctx, const GateKernel<A>& k, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A& a, const LutRef&) {
+    return launch_kernel(ctx, k.gate, grid, block, lds, s, a);
+}
+template <typename A>
+int prime_kernels(rtfhe_ctx* ctx, const TwinKernels<A>& k, size_t lds) {
+    if (int rc = allow_lds(ctx, k.gate, lds)) return rc;
+    if (int rc = allow_lds(ctx, k.pbs, lds)) return rc;
+    for (auto m : {k.many, k.enc, k.many_round, k.enc_round})
+        if (int rc = allow_lds(ctx, m, lds)) return rc;
+    return 0;
+}
+template <typename A>
+int prime_kernels(rtfhe_ctx* ctx, const GateKernel<A>& k, size_t lds) { return allow_lds(ctx, k.gate, lds); }
+
+// A shape -- a kernel family at one number of gates per workgroup -- is described once, by a struct Shape<GATES> with
+//   kernels()          its GateKernel / TwinKernels
+//   grid(count, cus)   workgroups for `count` gates on `cus` CUs, block(): threads of one
+//   lds(npad)          dynamic LDS bytes at this mask length
+//   args(ctx, b)       BootstrapArgs wrapped into the family's own argument struct
+// and a Family lists the GATES a shape exists for.  The dispatch launches through Family::launch and prime_*_kernels grants LDS through
+// Family::prime, so what can be launched and what is primed are one list; a gate count outside it is an error, not a new instantiation.
+template <int GATES, int THREADS_PER_GATE>
+struct GatesPerWorkgroup {      // GATES gates per workgroup, the last workgroup partly filled
+    static dim3 grid(int count, int) { return dim3((count + GATES - 1) / GATES); }
+    static dim3 block() { return dim3(THREADS_PER_GATE * GATES); }
+};
+struct WorkgroupPerCu {         // the time-sliced kernels: the gates shared evenly by one 8-wave workgroup per CU
+    static dim3 grid(int, int cus) { return dim3(cus); }
+    static dim3 block() { return dim3(512); }
+};
+template <template <int> class Shape, int... GATES>
+struct Family {
+    static int launch(rtfhe_ctx* ctx, int gates, const BootstrapArgs& b, hipStream_t s, const LutRef& lut = LutRef{}) {
+        int rc = 0;
+        if (((gates == GATES && ((rc = launch_twin(ctx, Shape<GATES>::kernels(), Shape<GATES>::grid(b.count, ctx->num_cus), Shape<GATES>::block(), Shape<GATES>::lds(b.npad), s,
+                                                   Shape<GATES>::args(ctx, b), lut)), true)) || ...)) return rc;
+        return fail(ctx, RTFHE_ERR_STATE, "no kernel shape of this family takes " + std::to_string(gates) + " gates per workgroup (" + std::to_string(b.count) + " gates on " +
+                                              std::to_string(ctx->num_cus) + " CUs)");
+    }
+    // (most: the shapes of up to `most` gates only, where a long mask leaves room for fewer)
+    static int prime(rtfhe_ctx* ctx, int npad, int most = INT_MAX) {
+        int rc = 0;
+        ((rc = rc || GATES > most ? rc : prime_kernels(ctx, Shape<GATES>::kernels(), Shape<GATES>::lds(npad))), ...);
+        return rc;
+    }
+    static constexpr bool fits(int npad, int most = INT_MAX) { return ((GATES > most || Shape<GATES>::lds(npad) <= LDS_LIMIT) && ...); }
+};
+
+// ---- the ladder every backend's dispatch walks ----
+// Whole rounds of round_gates gates per CU, then the remainder with ceil(rem / CUs) gates per workgroup, one workgroup per CU (a gate's waves then
+// share their SIMDs with fewer other waves: a tail of 1-3 gates per CU takes 0.67 x the time of a full round instead of all of it).
+struct LadderSplit { size_t full, rem; int tail_gates; };
+constexpr LadderSplit ladder_split(size_t count, size_t cus, int round_gates) {
+    const size_t round = (size_t)round_gates * cus, full = count / round * round, rem = count - full;
+    return {full, rem, (int)((rem + cus - 1) / cus)};
+}
+constexpr bool ladder_is(size_t count, size_t cus, int round_gates, size_t full, size_t rem, int tail_gates) {
+    const LadderSplit sp = ladder_split(count, cus, round_gates);
+    return sp.full == full && sp.rem == rem && sp.tail_gates == tail_gates;
+}
+static_assert(ladder_is(0, 256, 4, 0, 0, 0) && ladder_is(1, 256, 4, 0, 1, 1) && ladder_is(256, 256, 4, 0, 256, 1) && ladder_is(257, 256, 4, 0, 257, 2), "tails of one and two gates per CU");
+static_assert(ladder_is(1023, 256, 4, 0, 1023, 4) && ladder_is(1024, 256, 4, 1024, 0, 0) && ladder_is(1025, 256, 4, 1024, 1, 1), "around one whole round");
+static_assert(ladder_is(767, 256, 3, 0, 767, 3) && ladder_is(768, 256, 3, 768, 0, 0) && ladder_is(1025, 256, 3, 768, 257, 2), "rounds of three gates per CU");
+
+// The segments are queued back to back on stream s: launch(segment, its tables, gates per workgroup, tail) once for the whole rounds (tail =
+// false) and once for the remainder.  A plain batch that may take the split path (split_ok) walks the ladder in MODE_EXTRACT and ends in the
+// batch key switch.  merge_last: the backend's own condition for its time-sliced kernel -- the last whole round rides with the remainder in one
+// tail of round_gates + 1 .. + 2 gates per CU.  A programmable bootstrap's table indices travel with the ciphertexts of each segment.
+template <typename F>
+int walk_ladder(rtfhe_ctx* ctx, const BootstrapArgs& a, hipStream_t s, const LutRef& lut, int round_gates, bool merge_last, F launch) {
+    if (split_ok(ctx, a, s))
+        return launch_split(ctx, a, s, [&](rtfhe_ctx* c, const BootstrapArgs& b, hipStream_t st) { return walk_ladder(c, b, st, lut, round_gates, merge_last, launch); });
+    const size_t cus = (size_t)ctx->num_cus, out_words = mode_out_words(a, ctx->p.N);
+    LadderSplit sp = ladder_split((size_t)a.count, cus, round_gates);
+    if (merge_last) sp = {sp.full - round_gates * cus, sp.rem + round_gates * cus, sp.tail_gates + round_gates};
+    if (sp.full)
+        if (int rc = launch(batch_segment(ctx, a, 0, sp.full, out_words), lut, round_gates, false)) return rc;
+    return sp.rem ? launch(batch_segment(ctx, a, sp.full, sp.rem, out_words), lut_segment(lut, sp.full), sp.tail_gates, true) : 0;
 }
 
 }  // namespace rtfhe_host
