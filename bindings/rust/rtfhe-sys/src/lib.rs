@@ -76,6 +76,8 @@ extern "C" {
     pub fn rtfhe_get_backend(ctx: *const rtfhe_ctx) -> c_int;
     pub fn rtfhe_set_decomposition(ctx: *mut rtfhe_ctx, mode: c_int) -> c_int;
     pub fn rtfhe_get_decomposition(ctx: *const rtfhe_ctx) -> c_int;
+    pub fn rtfhe_set_leveled_decomposition(ctx: *mut rtfhe_ctx, mode: c_int) -> c_int;
+    pub fn rtfhe_get_leveled_decomposition(ctx: *const rtfhe_ctx) -> c_int;
     pub fn rtfhe_get_twiddles(ctx: *const rtfhe_ctx, ifft_table: *mut f64, fft_table: *mut f64) -> c_int;
     pub fn rtfhe_set_twiddles(ctx: *mut rtfhe_ctx, ifft_table: *const f64, fft_table: *const f64) -> c_int;
     pub fn rtfhe_ctx_params(ctx: *const rtfhe_ctx, p: *mut rtfhe_params) -> c_int;

@@ -334,8 +334,8 @@ int rtfhe_lut_create_encrypted(rtfhe_ctx *ctx, const uint32_t *trlwe /* [n_lut][
  *   rtfhe_lut_circuit_create                            which RECORDS the mode in force at creation: the circuit replays in that mode
  *                                                       whatever the context is set to later.
  * Gates, MUX, rtfhe_bootstrap_batch[_dev], gate circuits, rtfhe_blind_rotate_batch, rtfhe_external_product_batch and the leveled entry points
- * (CMUX tree, TRGSW rotation, CMUX netlists, packing) always use the reference decomposition: the gate path stays bit-identical to the
- * reference in either mode.  On a multi-device context the setter sets every entry.  Any other mode value: RTFHE_ERR_INVALID, the mode in force
+ * (CMUX tree, TRGSW rotation, CMUX netlists, packing) always use the reference decomposition unless rtfhe_set_leveled_decomposition (below)
+ * says otherwise for some of them: the gate path stays bit-identical to the reference in either mode.  On a multi-device context the setter sets every entry.  Any other mode value: RTFHE_ERR_INVALID, the mode in force
  * stays.  The setter works on every backend; on the exact backends the PBS calls keep failing with RTFHE_ERR_INVALID as before.
  * In rounded mode rtfhe_pbs_batch[_dev] with a plain table runs as rtfhe_pbs_many_batch[_dev] with n_out = 1, as an encrypted table already
  * does; so inside a stream capture rtfhe_pbs_batch_dev in rounded mode follows rtfhe_pbs_many_batch_dev's capture rule: an eager call of at
@@ -346,6 +346,25 @@ typedef enum {
 } rtfhe_decomposition;
 int rtfhe_set_decomposition(rtfhe_ctx *ctx, int mode);
 int rtfhe_get_decomposition(const rtfhe_ctx *ctx);      /* the mode in force, or RTFHE_ERR_INVALID for a NULL context */
+/* ---- the same choice for the leveled entry points: 6-bit table rows through a depth-8 tree and a 10-step rotation ----
+ * A second, independent mode with the same two values and the same rules (host state only, RTFHE_DECOMP_REFERENCE until set, every entry
+ * of a multi-device context set, NULL context or unknown mode: RTFHE_ERR_INVALID and the mode in force stays, accepted on every backend).
+ * Neither setter touches the other's state; rtfhe_set_decomposition keeps meaning the PBS family only.  In a CMUX the decomposition error
+ * is multiplied by the encrypted selector bit, so the reference constants' mean error shows only at levels whose bit is 1 (about 1e-3 of
+ * the torus per such level at N = 1024); in rounded mode the selectors' own noise is what remains (measured: DESIGN.md 5.13).
+ * The mode is read by these calls only:
+ *   rtfhe_cmux_tree_batch[_dev], rtfhe_cmux_tree_extract_batch[_dev],
+ *   rtfhe_trgsw_rotate_batch[_dev], rtfhe_trgsw_rotate_extract_batch[_dev]   when the call is made (inside a stream capture: when it is
+ *                                                       captured; the capture rules of these calls hold in either mode);
+ *   rtfhe_external_product_batch                        on the mirror backend, when the call is made.  On RTFHE_BACKEND_NTT_EXACT and
+ *                                                       RTFHE_BACKEND_FFT_SPLIT_EXACT with the rounded leveled mode in force it returns
+ *                                                       RTFHE_ERR_INVALID before anything is launched; in reference mode it runs there as before;
+ *   rtfhe_cmux_circuit_create                           which RECORDS the mode in force at creation: the circuit replays in that mode
+ *                                                       whatever the context is set to later.
+ * Gates, MUX, rtfhe_bootstrap_batch[_dev], rtfhe_blind_rotate_batch, the PBS family, packing and the key switch behind the extract forms
+ * never read it.  A rounded-mode output is NOT the reference's word; it decrypts to the same message. */
+int rtfhe_set_leveled_decomposition(rtfhe_ctx *ctx, int mode);
+int rtfhe_get_leveled_decomposition(const rtfhe_ctx *ctx);      /* the mode in force, or RTFHE_ERR_INVALID for a NULL context */
 /* ---- LUT circuits: netlists of many-LUT bootstraps, recorded once and replayed as one submission ----
  * A LUT circuit works on the wire table d_wires, u32[num_wires][n+1] lvl0 ciphertexts in device memory, as a gate circuit does.  It is a
  * sequence of waves: wave w holds nodes wave_offsets[w] .. wave_offsets[w+1] (host array, num_waves + 1 entries, strictly increasing from

@@ -47,7 +47,7 @@ class PeerInfo(C.Structure):
 
 NAND, AND, OR, XOR, NOT, COPY, ANDNY = range(7)
 BACKEND_FFT64_MIRROR, BACKEND_NTT_EXACT, BACKEND_FFT_SPLIT_EXACT = 0, 1, 2
-DECOMP_REFERENCE, DECOMP_ROUNDED = 0, 1      # rtfhe_set_decomposition: the gadget decomposition of the PBS family
+DECOMP_REFERENCE, DECOMP_ROUNDED = 0, 1      # rtfhe_set_decomposition / rtfhe_set_leveled_decomposition: the gadget decomposition of the PBS family / of the leveled entry points
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, -1, -2, -3, -4, -5
 
 _SIGNATURES = {
@@ -69,6 +69,8 @@ _SIGNATURES = {
     "rtfhe_get_backend": (C.c_int, [C.c_void_p]),
     "rtfhe_set_decomposition": (C.c_int, [C.c_void_p, C.c_int]),
     "rtfhe_get_decomposition": (C.c_int, [C.c_void_p]),
+    "rtfhe_set_leveled_decomposition": (C.c_int, [C.c_void_p, C.c_int]),
+    "rtfhe_get_leveled_decomposition": (C.c_int, [C.c_void_p]),
     "rtfhe_get_twiddles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtfhe_set_twiddles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtfhe_ctx_params": (C.c_int, [C.c_void_p, "PP"]),

@@ -10,6 +10,8 @@ import ctypes as C
 
 import numpy as np
 
+from . import _ffi
+
 
 class CmuxNetlist:
     """References are integers: r >= 0 is node r (in the order the nodes were added), r < 0 is table row -1 - r (CmuxNetlist.row)."""
@@ -194,18 +196,27 @@ def bdd_netlist(n_vars, fn_or_truth_tables, order=None, true_row=0, false_row=1)
 
 class CmuxCircuit:
     """A recorded CMUX netlist on an Engine (Engine.cmux_circuit): launch(stream) replays it, close() frees it.  It keeps the device arrays it
-    was recorded on alive."""
+    was recorded on alive.  rounded: None records the engine's leveled decomposition in force (Engine.set_leveled_decomposition); True / False
+    set it around the recording and restore it after.  The circuit replays in the mode it was recorded in."""
 
-    def __init__(self, engine, netlist, sel, lut, d_out, count, d_sel_idx=None, d_row0=None):
+    def __init__(self, engine, netlist, sel, lut, d_out, count, d_sel_idx=None, d_row0=None, rounded=None):
         a = netlist.arrays(engine.p.N)
         self.engine, self.netlist, self.count = engine, netlist, int(count)
         self._keep = (sel, d_out, d_sel_idx, d_row0)
         ptr =lambda v: None if v is None else C.c_void_p(v.ctypes.data)  # noqa: E731
         h = C.c_void_p()
         self.h = None
-        engine._ck(engine.L.rtfhe_cmux_circuit_create(engine.h, sel.h, lut.h, ptr(a["var"]), ptr(a["hi"]), ptr(a["lo"]), ptr(a["rot"]), a["n_nodes"], a["n_vars"],
-                                                      ptr(a["out_ref"]), ptr(a["out_coef"]), a["n_out"], engine._dev(d_sel_idx), engine._dev(d_row0),
-                                                      engine._dev(d_out), self.count, C.byref(h)))
+        before = engine.leveled_decomposition()
+        if rounded is not None:
+            engine.set_leveled_decomposition(_ffi.DECOMP_ROUNDED if rounded else _ffi.DECOMP_REFERENCE)
+        try:
+            engine._ck(engine.L.rtfhe_cmux_circuit_create(engine.h, sel.h, lut.h, ptr(a["var"]), ptr(a["hi"]), ptr(a["lo"]), ptr(a["rot"]), a["n_nodes"],
+                                                          a["n_vars"], ptr(a["out_ref"]), ptr(a["out_coef"]), a["n_out"], engine._dev(d_sel_idx),
+                                                          engine._dev(d_row0), engine._dev(d_out), self.count, C.byref(h)))
+        finally:
+            if rounded is not None:
+                engine.set_leveled_decomposition(before)
+        self.rounded = before == _ffi.DECOMP_ROUNDED if rounded is None else bool(rounded)
         self.h = h
         self.levels = len(netlist.levels())      # kernel launches of one replay: levels + 2, and the key switch in the extract form
 

@@ -1,7 +1,7 @@
 // rtfhe_cmux_net.hip -- CMUX netlists (include/rtfhe.h: rtfhe_cmux_circuit_create, rtfhe_trgsw_update): a decision diagram over
 // TRGSW-encrypted inputs, checked and levelised on the host (rtfhe_cmux_net_plan.cpp), recorded once into one linear HIP graph -- the check
-// kernel, one launch of k_cmux_net per level, the output kernel, and in the extract form the batch key switch -- and replayed through
-// rtfhe_circuit_launch.
+// kernel, one launch of k_cmux_net per level (its ROUNDED twin when the leveled mode in force at creation is the rounded one), the output
+// kernel, and in the extract form the batch key switch -- and replayed through rtfhe_circuit_launch.
 #include "rtfhe_host.hpp"
 
 #include <utility>
@@ -17,7 +17,10 @@ namespace {
 constexpr int NET_WAVES = 4;      // four waves (= nodes) per workgroup at both N, the tree's shape
 
 template <int LOGN>
-int prime_net_t(rtfhe_ctx* ctx) { return allow_lds(ctx, k_cmux_net<LOGN, 3, 6, NET_WAVES>, cmux_tree_lds_bytes<LOGN, NET_WAVES>()); }
+int prime_net_t(rtfhe_ctx* ctx) {
+    if (int rc = allow_lds(ctx, k_cmux_net<LOGN, 3, 6, NET_WAVES, false>, cmux_tree_lds_bytes<LOGN, NET_WAVES>())) return rc;
+    return allow_lds(ctx, k_cmux_net<LOGN, 3, 6, NET_WAVES, true>, cmux_tree_lds_bytes<LOGN, NET_WAVES>());
+}
 
 unsigned blocks_of(size_t waves) { return (unsigned)((waves + NET_WAVES - 1) / NET_WAVES); }
 
@@ -26,15 +29,17 @@ int launch_net_t(rtfhe_ctx* ctx, const CmuxNetArgs& a, int what, hipStream_t s) 
     const dim3 block(64 * NET_WAVES);
     constexpr size_t lds = cmux_tree_lds_bytes<LOGN, NET_WAVES>();
     if (what == 0) hipLaunchKernelGGL((k_cmux_net_check<NET_WAVES>), dim3(blocks_of((size_t)a.count)), block, 0, s, a);
+    else if (what == 1 && leveled_rounded(ctx))
+        hipLaunchKernelGGL((k_cmux_net<LOGN, 3, 6, NET_WAVES, true>), dim3(blocks_of((size_t)a.count * a.n_level)), block, lds, s, a);
     else if (what == 1)
-        hipLaunchKernelGGL((k_cmux_net<LOGN, 3, 6, NET_WAVES>), dim3(blocks_of((size_t)a.count * a.n_level)), block, lds, s, a);
+        hipLaunchKernelGGL((k_cmux_net<LOGN, 3, 6, NET_WAVES, false>), dim3(blocks_of((size_t)a.count * a.n_level)), block, lds, s, a);
     else hipLaunchKernelGGL((k_cmux_net_out<LOGN, NET_WAVES>), dim3(blocks_of((size_t)a.count * a.n_out)), block, 0, s, a);
     HIPCHECK(ctx, hipGetLastError());
     ctx->launches++;
     return 0;
 }
 
-// what: 0 = k_cmux_net_check, 1 = k_cmux_net (one level), 2 = k_cmux_net_out
+// what: 0 = k_cmux_net_check, 1 = k_cmux_net (one level; the twin of the leveled mode in force: the graph keeps it), 2 = k_cmux_net_out
 int launch_net(rtfhe_ctx* ctx, const CmuxNetArgs& a, int what, hipStream_t s) {
     return ctx->logn == 11 ? launch_net_t<11>(ctx, a, what, s) : launch_net_t<10>(ctx, a, what, s);
 }

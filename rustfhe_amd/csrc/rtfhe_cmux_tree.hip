@@ -1,6 +1,7 @@
 // rtfhe_cmux_tree.hip -- CMUX-tree table lookup with caller-supplied TRGSW selectors (include/rtfhe.h: rtfhe_trgsw_create,
 // rtfhe_cmux_tree_batch[_dev], rtfhe_cmux_tree_extract_batch[_dev]): selector sets, the argument checks, the stream's ping-pong buffers
-// and the rules around stream captures, one launch of k_cmux_tree per level, and for the extract form the batch key switch many-LUT uses.
+// and the rules around stream captures, one launch of k_cmux_tree per level (its ROUNDED twin in the rounded leveled mode,
+// rtfhe_set_leveled_decomposition), and for the extract form the batch key switch many-LUT uses.
 // Beside it the TRGSW blind rotation (rtfhe_trgsw_rotate_batch[_dev], rtfhe_trgsw_rotate_extract_batch[_dev]): the same selector sets, one
 // launch of k_trgsw_rotate for all steps of all lookups, the same key switch behind the extract form.
 #include "rtfhe_host.hpp"
@@ -15,10 +16,12 @@ using namespace rtfhe_host;
 
 namespace {
 
-template <int LOGN, int W>
+template <int LOGN, int W, bool ROUNDED>
 int launch_level_t(rtfhe_ctx* ctx, const CmuxTreeArgs& a, size_t nodes, hipStream_t s) {
-    auto k = k_cmux_tree<LOGN, 3, 6, W>;
+    auto k = k_cmux_tree<LOGN, 3, 6, W, ROUNDED>;
     constexpr size_t lds = cmux_tree_lds_bytes<LOGN, W>();
+    // both twins: the eager call the capture rule asks for may have run in the other mode
+    if (int rc = allow_lds(ctx, k_cmux_tree<LOGN, 3, 6, W, !ROUNDED>, lds)) return rc;
     if (int rc = allow_lds(ctx, k, lds)) return rc;
     hipLaunchKernelGGL(k, dim3((unsigned)((nodes + W - 1) / W)), dim3(64 * W), lds, s, a);
     HIPCHECK(ctx, hipGetLastError());
@@ -27,8 +30,9 @@ int launch_level_t(rtfhe_ctx* ctx, const CmuxTreeArgs& a, size_t nodes, hipStrea
 }
 
 int launch_level(rtfhe_ctx* ctx, const CmuxTreeArgs& a, size_t nodes, hipStream_t s) {
-    // four waves (= nodes) per workgroup at both N, the shape of k_external_product
-    return ctx->logn == 11 ? launch_level_t<11, 4>(ctx, a, nodes, s) : launch_level_t<10, 4>(ctx, a, nodes, s);
+    // four waves (= nodes) per workgroup at both N, the shape of k_external_product; the mode is read here, when the call is made
+    if (leveled_rounded(ctx)) return ctx->logn == 11 ? launch_level_t<11, 4, true>(ctx, a, nodes, s) : launch_level_t<10, 4, true>(ctx, a, nodes, s);
+    return ctx->logn == 11 ? launch_level_t<11, 4, false>(ctx, a, nodes, s) : launch_level_t<10, 4, false>(ctx, a, nodes, s);
 }
 
 bool capturing(hipStream_t s) {
@@ -172,10 +176,11 @@ int tree_host(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, in
 }
 
 // ---- TRGSW blind rotation ----
-template <int LOGN, int W>
+template <int LOGN, int W, bool ROUNDED>
 int launch_rotate_t(rtfhe_ctx* ctx, const TrgswRotateArgs& a, hipStream_t s) {
-    auto k = k_trgsw_rotate<LOGN, 3, 6, W>;
+    auto k = k_trgsw_rotate<LOGN, 3, 6, W, ROUNDED>;
     constexpr size_t lds = cmux_tree_lds_bytes<LOGN, W>();
+    if (int rc = allow_lds(ctx, k_trgsw_rotate<LOGN, 3, 6, W, !ROUNDED>, lds)) return rc;      // (prime_rotate has granted both already)
     if (int rc = allow_lds(ctx, k, lds)) return rc;
     hipLaunchKernelGGL(k, dim3((unsigned)(((size_t)a.count + W - 1) / W)), dim3(64 * W), lds, s, a);
     HIPCHECK(ctx, hipGetLastError());
@@ -191,10 +196,14 @@ int launch_rotate_restore_t(rtfhe_ctx* ctx, const TrgswRotateArgs& a, hipStream_
     return 0;
 }
 
-// grants k_trgsw_rotate its dynamic LDS when a selector set is created, so that the first rotation of a context may already sit in a stream capture
-int prime_rotate(rtfhe_ctx* ctx) {
-    return ctx->logn == 11 ? allow_lds(ctx, k_trgsw_rotate<11, 3, 6, 4>, cmux_tree_lds_bytes<11, 4>()) : allow_lds(ctx, k_trgsw_rotate<10, 3, 6, 4>, cmux_tree_lds_bytes<10, 4>());
+// grants k_trgsw_rotate its dynamic LDS when a selector set is created, so that the first rotation of a context may already sit in a stream
+// capture: both twins, since the mode may be switched between the set's creation and the capture
+template <int LOGN>
+int prime_rotate_t(rtfhe_ctx* ctx) {
+    if (int rc = allow_lds(ctx, k_trgsw_rotate<LOGN, 3, 6, 4, false>, cmux_tree_lds_bytes<LOGN, 4>())) return rc;
+    return allow_lds(ctx, k_trgsw_rotate<LOGN, 3, 6, 4, true>, cmux_tree_lds_bytes<LOGN, 4>());
 }
+int prime_rotate(rtfhe_ctx* ctx) { return ctx->logn == 11 ? prime_rotate_t<11>(ctx) : prime_rotate_t<10>(ctx); }
 
 // what every rotation entry checks before anything is allocated or launched; host_sel_idx is null in the _dev forms, whose array the kernel checks
 int rotate_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, int32_t depth, const int32_t* rot, size_t count, bool has_sel_idx, const int32_t* host_sel_idx,
@@ -256,7 +265,9 @@ int launch_rotate(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* d_sel_i
     a.ks_out = extract ? (uint32_t*)d_out : nullptr;
     a.count = (int32_t)count; a.depth = depth; a.n_sel = sel->n_sel; a.n = ctx->p.n;
     for (int k = 0; k < depth; k++) a.rot[k] = rot ? rot[k] : 2 * ctx->p.N - (1 << k);      // NULL: X^{-2^k}
-    if (int rc = ctx->logn == 11 ? launch_rotate_t<11, 4>(ctx, a, s) : launch_rotate_t<10, 4>(ctx, a, s)) return rc;
+    if (int rc = leveled_rounded(ctx) ? (ctx->logn == 11 ? launch_rotate_t<11, 4, true>(ctx, a, s) : launch_rotate_t<10, 4, true>(ctx, a, s))
+                                      : (ctx->logn == 11 ? launch_rotate_t<11, 4, false>(ctx, a, s) : launch_rotate_t<10, 4, false>(ctx, a, s)))
+        return rc;
     if (!extract) return 0;
     // identity_key_switch of the count samples, as the tree's extract form does it; then the rows of skipped lookups as they were
     if (!ctx->d_ksmat) {

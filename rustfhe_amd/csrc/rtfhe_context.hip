@@ -401,6 +401,18 @@ int rtfhe_set_decomposition(rtfhe_ctx* ctx, int mode) {
 
 int rtfhe_get_decomposition(const rtfhe_ctx* ctx) { return ctx ? ctx->decomp : RTFHE_ERR_INVALID; }
 
+// host state only, and a second mode beside the one above: read by the leveled entry points when they choose their kernels
+// (rtfhe_cmux_tree.hip, rtfhe_cmux_net.hip, rtfhe_external_product_batch in rtfhe_stages.hip)
+int rtfhe_set_leveled_decomposition(rtfhe_ctx* ctx, int mode) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (mode != RTFHE_DECOMP_REFERENCE && mode != RTFHE_DECOMP_ROUNDED) return fail(ctx, RTFHE_ERR_INVALID, "unknown decomposition mode");
+    ctx->leveled_decomp = mode;
+    for (rtfhe_ctx* peer : ctx->peers) peer->leveled_decomp = mode;
+    return 0;
+}
+
+int rtfhe_get_leveled_decomposition(const rtfhe_ctx* ctx) { return ctx ? ctx->leveled_decomp : RTFHE_ERR_INVALID; }
+
 int rtfhe_ctx_params(const rtfhe_ctx* ctx, rtfhe_params* p) {
     if (!ctx || !p) return fail(nullptr, RTFHE_ERR_INVALID, "null argument");
     *p = ctx->p;

@@ -76,6 +76,8 @@ struct rtfhe_ctx {
     int eo_round = 4;                 // N = 2048: gates per CU in a whole round of k_bootstrap_eo: 4, or 3 where four gates' LDS passes 160 KiB (n >= 704), set when the kernels are primed
     int backend = RTFHE_BACKEND_FFT64_MIRROR;
     int decomp = RTFHE_DECOMP_REFERENCE;   // the gadget decomposition of the PBS family (rtfhe_set_decomposition); gates never read it
+    int leveled_decomp = RTFHE_DECOMP_REFERENCE;   // ... of the leveled entry points (rtfhe_set_leveled_decomposition): tree, rotation, CMUX netlists
+                                           // at creation, the mirror backend's external product; independent of `decomp`
     uint32_t* d_bk_torus = nullptr;   // kept when the key came in torus form: source for the NTT-domain key
     double* d_ntt_bk = nullptr;
     double* d_ntt_tw = nullptr;
@@ -201,6 +203,8 @@ inline LutRef lut_on(const rtfhe_lut* lut, int entry, const int32_t* d_idx, int3
     return lut ? LutRef{lut->d_tv[entry], d_idx, lut->n_lut, shift, lut->encrypted, lut->ctx && lut->ctx->decomp == RTFHE_DECOMP_ROUNDED} : LutRef{};
 }
 // the path of a one-output PBS with this table: the many-LUT path (shift 0) for an encrypted table and in rounded mode, else the fused kernels (-1)
+// does a leveled entry point of this context launch the ROUNDED = true twin of its kernel?
+inline bool leveled_rounded(const rtfhe_ctx* ctx) { return ctx->leveled_decomp == RTFHE_DECOMP_ROUNDED; }
 inline int32_t pbs_shift(const rtfhe_ctx* ctx, const rtfhe_lut* lut) { return (lut->encrypted || ctx->decomp == RTFHE_DECOMP_ROUNDED) ? 0 : -1; }
 using rtfhe::cplx;
 

@@ -229,7 +229,8 @@ __device__ __forceinline__ void many_extract(uint32_t* ext, int ge, int t, const
 //   CMUX = true : acc <- cross(bk_i, X^r * acc - acc) + acc      (trgsw.rs:319-321, tfhe.rs:103-110)
 //   CMUX = false: acc <- cross(bk_i, acc)                          (trgsw.rs:264-306)
 // accbuf: LDS u32 [2][N] (b then a).  bk_i: this TRGSW in device layout [2l][2][R][64] cplx.
-// ROUNDED: the decomposition rounds to nearest with balanced digits (TvManyR); every caller but the k_pbs_round kernels leaves it false.
+// ROUNDED: the decomposition rounds to nearest with balanced digits (TvManyR): the k_pbs_round kernels, and the ROUNDED = true twins of the
+// leveled kernels (k_cmux_tree, k_trgsw_rotate, k_cmux_net, k_external_product); every other caller leaves it false.
 template <int LOGN, int L, int BGBIT, bool CMUX, bool DUAL = false, bool ROUNDED = false>
 __device__ __forceinline__ void cmux_step(uint32_t* __restrict__ accbuf, int r, const cplx* __restrict__ bk_i,
                                           const cplx* __restrict__ twf, const cplx* __restrict__ twi, const cplx* __restrict__ twi_big,
@@ -606,7 +607,7 @@ struct ExtProdArgs {
     int32_t count;
 };
 
-template <int LOGN, int L, int BGBIT, int WAVES>
+template <int LOGN, int L, int BGBIT, int WAVES, bool ROUNDED>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_external_product(const ExtProdArgs a) {
     typedef Geo<LOGN> G;
     constexpr int N = G::N, R = G::R;
@@ -623,7 +624,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_external_product(const ExtPro
     for (int c = lane; c < 2 * N; c += 64) accbuf[c] = a.trlwe[(size_t)g * 2 * N + c];
     wave_lds_sync();
     const size_t trgsw_cplx = (size_t)2 * L * 2 * R * 64;
-    cmux_step<LOGN, L, BGBIT, false>(accbuf, 0, a.bk + (size_t)a.bk_index[g] * trgsw_cplx, TwStage<LOGN>::fwd(tw), TwStage<LOGN>::inv_small(tw), TwStage<LOGN>::inv_big(tw, a.tw), xbuf, lane);
+    cmux_step<LOGN, L, BGBIT, false, false, ROUNDED>(accbuf, 0, a.bk + (size_t)a.bk_index[g] * trgsw_cplx, TwStage<LOGN>::fwd(tw), TwStage<LOGN>::inv_small(tw), TwStage<LOGN>::inv_big(tw, a.tw), xbuf, lane);
     for (int c = lane; c < 2 * N; c += 64) a.out[(size_t)g * 2 * N + c] = accbuf[c];
 }
 

@@ -5,7 +5,8 @@
 //   value_i = cmux(S, X^rot * value(hi), value(lo)) = cross(S, X^rot * hi - lo) + lo          (TRGSWRepF::cmux, hom_nand/src/trgsw.rs:319-321;
 //                                                                                              X^rot: rotated_coef, utils/src/math.rs:85-132)
 // hi and lo are slots of lower levels or table rows (a plain row tv is the trivial TRLWE (tv, 0)).  The product is
-// cmux_step<.., CMUX = false> itself (rtfhe_kernels.hpp), called, not restated, on the tree's launch shape and LDS carve.
+// cmux_step<.., CMUX = false> itself (rtfhe_kernels.hpp), called, not restated, on the tree's launch shape and LDS carve; ROUNDED is
+// cmux_step's, as in k_cmux_tree.
 // k_cmux_net_check runs first (a wave per replica: its device-resident indices), k_cmux_net_out last (a wave per (replica, output): the
 // node copied to d_out, or its sample extract in the batch key switch's operand order).  Instantiated in rtfhe_cmux_net.hip.
 #pragma once
@@ -40,7 +41,7 @@ struct CmuxNetArgs {
 
 // acc <- cmux(S, X^r * hi, lo) on the wave-private accumulator, beside cmux_select (rtfhe_kernels_cmux_tree.hpp): the rotated read of hi
 // comes from global memory, and either child may be a plain table row, whose a-half (null) reads as zero.
-template <int LOGN, int L, int BGBIT, bool DUAL>
+template <int LOGN, int L, int BGBIT, bool DUAL, bool ROUNDED>
 __device__ __forceinline__ void cmux_select_rotated(uint32_t* __restrict__ accbuf, const cplx* __restrict__ S, int r, const uint32_t* __restrict__ b1,
                                                     const uint32_t* __restrict__ a1, const uint32_t* __restrict__ b0, const uint32_t* __restrict__ a0,
                                                     const cplx* __restrict__ twf, const cplx* __restrict__ twi, const cplx* __restrict__ twi_big,
@@ -51,7 +52,7 @@ __device__ __forceinline__ void cmux_select_rotated(uint32_t* __restrict__ accbu
         accbuf[N + c] = (a1 ? rotated_coef<LOGN>(a1, c, r) : 0u) - (a0 ? a0[c] : 0u);
     }
     wave_lds_sync();
-    cmux_step<LOGN, L, BGBIT, false, DUAL>(accbuf, 0, S, twf, twi, twi_big, xbuf, lane);
+    cmux_step<LOGN, L, BGBIT, false, DUAL, ROUNDED>(accbuf, 0, S, twf, twi, twi_big, xbuf, lane);
     for (int c = lane; c < N; c += 64) {
         accbuf[c] += b0[c];
         if (a0) accbuf[N + c] += a0[c];
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_cmux_net_check(const CmuxNetArgs
     }
 }
 
-template <int LOGN, int L, int BGBIT, int WAVES>
+template <int LOGN, int L, int BGBIT, int WAVES, bool ROUNDED>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_cmux_net(const CmuxNetArgs a) {
     typedef Geo<LOGN> G;
     constexpr int N = G::N, R = G::R;
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_cmux_net(const CmuxNetArgs a)
         }
     }
     const size_t trgsw_cplx = (size_t)2 * L * 2 * R * 64;
-    cmux_select_rotated<LOGN, L, BGBIT, DUAL>(accbuf, a.sel + (size_t)s * trgsw_cplx, r, bb[1], aa[1], bb[0], aa[0], TwStage<LOGN>::fwd(tw),
+    cmux_select_rotated<LOGN, L, BGBIT, DUAL, ROUNDED>(accbuf, a.sel + (size_t)s * trgsw_cplx, r, bb[1], aa[1], bb[0], aa[0], TwStage<LOGN>::fwd(tw),
                                               TwStage<LOGN>::inv_small(tw), TwStage<LOGN>::inv_big(tw, a.tw), xbuf, lane);
     uint32_t* o = slots + (size_t)i * 2 * N;
     for (int c = lane; c < 2 * N; c += 64) o[c] = accbuf[c];

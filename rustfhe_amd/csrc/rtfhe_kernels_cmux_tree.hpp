@@ -5,7 +5,8 @@
 // Level 0 reads its two children from the table (a plain row tv is the trivial TRLWE (tv, 0)), every other level from the previous level's
 // buffer; the last level writes the lookup's result -- or, in the extract form, sample extract index coef[g] of it (trlwe.rs:110-121) in the
 // batch key switch's operand order (ext_slot).  The product is cmux_step<.., CMUX = false> itself (rtfhe_kernels.hpp), called, not restated:
-// the kernels that existed before compile to what they did.  Instantiated in rtfhe_cmux_tree.hip.
+// the kernels that existed before compile to what they did.  ROUNDED is cmux_step's: the rounded gadget decomposition of the leveled mode
+// (include/rtfhe.h: rtfhe_set_leveled_decomposition), two other constants and nothing else.  Instantiated in rtfhe_cmux_tree.hip.
 #pragma once
 
 #include "rtfhe_kernels.hpp"
@@ -37,7 +38,7 @@ __host__ __device__ constexpr size_t cmux_tree_lds_bytes() { return bootstrap_ld
 // acc <- cmux(S, r1, r0) on the wave-private accumulator: the difference into LDS, the external product in place, r0 added back from where it
 // came (a second read of 2N words that the L2 still holds costs less than 2N / 64 registers live across the product).  A null a-half (plain
 // table rows) reads as zero.
-template <int LOGN, int L, int BGBIT, bool DUAL>
+template <int LOGN, int L, int BGBIT, bool DUAL, bool ROUNDED>
 __device__ __forceinline__ void cmux_select(uint32_t* __restrict__ accbuf, const cplx* __restrict__ S, const uint32_t* __restrict__ b1,
                                             const uint32_t* __restrict__ a1, const uint32_t* __restrict__ b0, const uint32_t* __restrict__ a0,
                                             const cplx* __restrict__ twf, const cplx* __restrict__ twi, const cplx* __restrict__ twi_big,
@@ -48,7 +49,7 @@ __device__ __forceinline__ void cmux_select(uint32_t* __restrict__ accbuf, const
         accbuf[N + c] = a1 ? a1[c] - a0[c] : 0u;
     }
     wave_lds_sync();
-    cmux_step<LOGN, L, BGBIT, false, DUAL>(accbuf, 0, S, twf, twi, twi_big, xbuf, lane);
+    cmux_step<LOGN, L, BGBIT, false, DUAL, ROUNDED>(accbuf, 0, S, twf, twi, twi_big, xbuf, lane);
     for (int c = lane; c < N; c += 64) {
         accbuf[c] += b0[c];
         if (a0) accbuf[N + c] += a0[c];
@@ -56,7 +57,7 @@ __device__ __forceinline__ void cmux_select(uint32_t* __restrict__ accbuf, const
     wave_lds_sync();
 }
 
-template <int LOGN, int L, int BGBIT, int WAVES>
+template <int LOGN, int L, int BGBIT, int WAVES, bool ROUNDED>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_cmux_tree(const CmuxTreeArgs a) {
     typedef Geo<LOGN> G;
     constexpr int N = G::N, R = G::R;
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_cmux_tree(const CmuxTreeArgs 
         b0 = p0; a0 = p0 + N; b1 = p0 + 2 * N; a1 = p0 + 3 * N;
     }
     const size_t trgsw_cplx = (size_t)2 * L * 2 * R * 64;
-    cmux_select<LOGN, L, BGBIT, DUAL>(accbuf, a.sel + (size_t)s * trgsw_cplx, b1, a1, b0, a0, TwStage<LOGN>::fwd(tw), TwStage<LOGN>::inv_small(tw),
+    cmux_select<LOGN, L, BGBIT, DUAL, ROUNDED>(accbuf, a.sel + (size_t)s * trgsw_cplx, b1, a1, b0, a0, TwStage<LOGN>::fwd(tw), TwStage<LOGN>::inv_small(tw),
                                       TwStage<LOGN>::inv_big(tw, a.tw), xbuf, lane);
 
     if (a.ext && lvl_bits == 0) {

@@ -5,7 +5,7 @@
 //                                                                                              the key entry replaced by selector S_k, abar_i by rot[k])
 // then stores the 2N words -- or, in the extract form, sample extract index 0 (trlwe.rs:110-121) in the batch key switch's operand order
 // (ext_slot).  The step is cmux_step<.., CMUX = true> itself (rtfhe_kernels.hpp), called, not restated: the kernels that existed before
-// compile to what they did.  Instantiated in rtfhe_cmux_tree.hip.
+// compile to what they did.  ROUNDED is cmux_step's, as in k_cmux_tree.  Instantiated in rtfhe_cmux_tree.hip.
 //
 // A lookup with a selector index outside the set is skipped whole and its output row stays as it was.  In the extract form the batch key
 // switch that follows writes every row: the skipped lookup's wave parks the row's n + 1 <= N words in its own (otherwise unused) sample slots,
@@ -42,7 +42,7 @@ __device__ __forceinline__ bool trgsw_rotate_ok(const TrgswRotateArgs& a, long l
     return ok;
 }
 
-template <int LOGN, int L, int BGBIT, int WAVES>
+template <int LOGN, int L, int BGBIT, int WAVES, bool ROUNDED>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_trgsw_rotate(const TrgswRotateArgs a) {
     typedef Geo<LOGN> G;
     constexpr int N = G::N, R = G::R;
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_trgsw_rotate(const TrgswRotat
     for (int k = 0; k < a.depth; k++) {
         const int sk = __builtin_amdgcn_readfirstlane(a.sel_idx ? a.sel_idx[(size_t)g * a.depth + k] : (int)g * a.depth + k);
         const int r = a.rot[k];
-        cmux_step<LOGN, L, BGBIT, true, DUAL>(accbuf, r, a.sel + (size_t)sk * trgsw_cplx, TwStage<LOGN>::fwd(tw), TwStage<LOGN>::inv_small(tw),
+        cmux_step<LOGN, L, BGBIT, true, DUAL, ROUNDED>(accbuf, r, a.sel + (size_t)sk * trgsw_cplx, TwStage<LOGN>::fwd(tw), TwStage<LOGN>::inv_small(tw),
                                               TwStage<LOGN>::inv_big(tw, a.tw), xbuf, lane);
     }
 

@@ -31,11 +31,12 @@ int launch_fft_t(rtfhe_ctx* ctx, bool forward, FftArgs a, hipStream_t s) {
     HIPCHECK(ctx, hipGetLastError());
     return 0;
 }
-template <int LOGN>
+template <int LOGN, bool ROUNDED>
 int launch_extprod_t(rtfhe_ctx* ctx, ExtProdArgs a, hipStream_t s) {
     constexpr int W = 4;
-    auto k = k_external_product<LOGN, 3, 6, W>;
+    auto k = k_external_product<LOGN, 3, 6, W, ROUNDED>;
     const size_t lds = bootstrap_lds_bytes<LOGN>(W, 0);
+    if (int rc = allow_lds(ctx, k_external_product<LOGN, 3, 6, W, !ROUNDED>, lds)) return rc;      // both twins, as the leveled launches do
     if (int rc = allow_lds(ctx, k, lds)) return rc;
     hipLaunchKernelGGL(k, dim3((a.count + W - 1) / W), dim3(64 * W), lds, s, a);
     HIPCHECK(ctx, hipGetLastError());
@@ -167,6 +168,9 @@ int rtfhe_external_product_batch(rtfhe_ctx* ctx, const int32_t* bk_index, const 
     if (int rc = use(ctx)) return rc;
     if (!bk_index || !trlwe || !out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
     if (!ctx->has_bk) return fail(ctx, RTFHE_ERR_STATE, "bootstrapping key not loaded");
+    if (leveled_rounded(ctx) && ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
+        return fail(ctx, RTFHE_ERR_INVALID, "the rounded leveled decomposition (rtfhe_set_leveled_decomposition) runs on the FP64 mirror backend only "
+                                            "(RTFHE_BACKEND_FFT64_MIRROR); select it with rtfhe_set_backend or switch the leveled mode back");
     if (count == 0) return 0;
     if (count > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "count too large");
     for (size_t g = 0; g < count; g++)
@@ -186,7 +190,8 @@ int rtfhe_external_product_batch(rtfhe_ctx* ctx, const int32_t* bk_index, const 
         if ((rc = launch_extprod_xfft(ctx, (const int32_t*)ctx->d_b, (const uint32_t*)ctx->d_a, (uint32_t*)ctx->d_c, (int32_t)count, ctx->stream))) return rc;
     } else {
         ExtProdArgs a{ctx->d_tw, ctx->d_bk, (const int32_t*)ctx->d_b, (const uint32_t*)ctx->d_a, (uint32_t*)ctx->d_c, (int32_t)count};
-        rc = ctx->logn == 10 ? launch_extprod_t<10>(ctx, a, ctx->stream) : launch_extprod_t<11>(ctx, a, ctx->stream);
+        if (leveled_rounded(ctx)) rc = ctx->logn == 10 ? launch_extprod_t<10, true>(ctx, a, ctx->stream) : launch_extprod_t<11, true>(ctx, a, ctx->stream);
+        else rc = ctx->logn == 10 ? launch_extprod_t<10, false>(ctx, a, ctx->stream) : launch_extprod_t<11, false>(ctx, a, ctx->stream);
         if (rc) return rc;
     }
     HIPCHECK(ctx, hipMemcpyAsync(out, ctx->d_c, bytes, hipMemcpyDeviceToHost, ctx->stream));

@@ -133,6 +133,16 @@ class Engine:
     def decomposition(self):
         return self.L.rtfhe_get_decomposition(self.h)
 
+    def set_leveled_decomposition(self, mode):
+        """The gadget decomposition of the leveled calls (cmux_tree_*, trgsw_rotate_*, external_product_batch on the mirror backend, CMUX
+        netlists at creation): _ffi.DECOMP_REFERENCE (the default, the reference's words) or _ffi.DECOMP_ROUNDED (round to nearest, balanced
+        digits: no systematic error under selector bits that are 1, 6-bit rows through a depth-8 tree and a 10-step rotation).  A second mode,
+        independent of set_decomposition's; gates, the PBS family and packing never read it."""
+        self._ck(self.L.rtfhe_set_leveled_decomposition(self.h, mode))
+
+    def leveled_decomposition(self):
+        return self.L.rtfhe_get_leveled_decomposition(self.h)
+
     def twiddles(self):
         a = np.zeros(2 * self.p.N, np.float64)
         b = np.zeros(2 * self.p.N, np.float64)
@@ -386,13 +396,15 @@ class Engine:
                                                              count, C.c_void_p(stream) if stream else None))
 
     # ---- CMUX netlists (include/rtfhe.h: rtfhe_cmux_circuit_create; rustfhe_amd.cmux_net) -----------------------------------------------------
-    def cmux_circuit(self, netlist, sel, lut, d_out, count, d_sel_idx=None, d_row0=None):
+    def cmux_circuit(self, netlist, sel, lut, d_out, count, d_sel_idx=None, d_row0=None, rounded=None):
         """Records `count` replicas of a CmuxNetlist over the selector set `sel` and the table `lut` into one graph.  d_out: device buffer
         [count][n_out][2][N] words, or [count][n_out][n+1] when the netlist's outputs carry coefficients; d_sel_idx: int32[count][n_vars] on
         the device (None: replica g uses selectors g * n_vars + v); d_row0: int32[count] (None: 0).  The description is checked here: a bad
-        node or output raises RtfheError before anything is allocated.  Returns a CmuxCircuit: launch(stream), close()."""
+        node or output raises RtfheError before anything is allocated.  rounded: None records the leveled decomposition in force
+        (set_leveled_decomposition), True / False set it around the recording and restore it; the circuit replays in the mode it was recorded
+        in.  Returns a CmuxCircuit: launch(stream), close()."""
         from .cmux_net import CmuxCircuit
-        return CmuxCircuit(self, netlist, sel, lut, d_out, count, d_sel_idx, d_row0)
+        return CmuxCircuit(self, netlist, sel, lut, d_out, count, d_sel_idx, d_row0, rounded)
 
     # ---- packing key switch (include/rtfhe.h: rtfhe_packing_key_create, rtfhe_pack_batch[_dev], rtfhe_lut_update_dev) --------------------------
     def packing_key(self, pk):
