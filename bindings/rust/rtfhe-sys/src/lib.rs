@@ -164,6 +164,14 @@ extern "C" {
     pub fn rtfhe_pack_batch_dev(ctx: *mut rtfhe_ctx, pk: *const rtfhe_packing_key, d_tlwe: *const c_void, P: i32, pos: *const i32, rep: i32, d_out: *mut c_void,
                                 count: usize, stream: *mut c_void) -> c_int;
     pub fn rtfhe_lut_update_dev(lut: *mut rtfhe_lut, d_trlwe: *const c_void, first: i32, n: i32, stream: *mut c_void) -> c_int;
+    // CMUX demultiplexer tree (the CMUX tree run backwards): x [count][2][N] into out [count][2^depth][2][N], leaf `addr` a TRLWE of x's message and
+    // every other leaf of 0; level t splits on selector depth - 1 - t.  rtfhe_lut_accumulate_dev adds [count][n][2][N] into rows
+    // [first, first + n) of an encrypted table, wrapping (stream-ordered); rtfhe_lut_read_dev copies such rows out to device memory
+    pub fn rtfhe_demux_tree_batch(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, sel_idx: *const i32, depth: i32, x: *const u32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_demux_tree_batch_dev(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, d_sel_idx: *const c_void, depth: i32, d_x: *const c_void, d_out: *mut c_void,
+                                      count: usize, stream: *mut c_void) -> c_int;
+    pub fn rtfhe_lut_accumulate_dev(lut: *mut rtfhe_lut, d_trlwe: *const c_void, first: i32, n: i32, count: usize, stream: *mut c_void) -> c_int;
+    pub fn rtfhe_lut_read_dev(lut: *const rtfhe_lut, d_out: *mut c_void, first: i32, n: i32, stream: *mut c_void) -> c_int;
     pub fn rtfhe_sync(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_begin(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_end(ctx: *mut rtfhe_ctx, stream: *mut c_void, ms: *mut f64, launches: *mut i64) -> c_int;

@@ -42,6 +42,10 @@
  *   rtfhe_packing_key_create / rtfhe_pack_batch[_dev] / rtfhe_lut_update_dev
  *                                    (no reference counterpart) TFHE's public packing key switch: lvl0 samples into TRLWE rows, with the digits of
  *                                       identity_key_switch (hom_nand/src/tlwe.rs:43-73) and TRLWE key rows (hom_nand/src/trlwe.rs) in the place of TLWE ones
+ *   rtfhe_demux_tree_batch[_dev] / rtfhe_lut_accumulate_dev / rtfhe_lut_read_dev
+ *                                    <- TRGSWRepF::cross (hom_nand/src/trgsw.rs:264-306) on caller-supplied TRGSW samples: the tree run backwards, one
+ *                                       TRLWE into leaf `addr` of 2^d and zero into the others, and the leaves added into an encrypted table's rows
+ *                                       (the reference has the product, not the demultiplexer)
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch           <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -615,6 +619,54 @@ int rtfhe_pack_batch(rtfhe_ctx *ctx, const rtfhe_packing_key *pk, const uint32_t
 int rtfhe_pack_batch_dev(rtfhe_ctx *ctx, const rtfhe_packing_key *pk, const void *d_tlwe /* [count][P][n+1] */, int32_t P,
                          const int32_t *pos /* HOST [P] or NULL */, int32_t rep, void *d_out /* [count][2][N] */, size_t count, void *stream);
 int rtfhe_lut_update_dev(rtfhe_lut *lut, const void *d_trlwe /* [n][2][N] */, int32_t first, int32_t n, void *stream);
+/* ---- CMUX demultiplexer tree: a TRLWE written to leaf `addr` of 2^d, addr given as TRGSW-encrypted bits (the tree above run backwards) ----
+ * Lookup g of a batch takes a TRLWE x[g], u32[2][N] (b then a) -- a plain polynomial tv is passed as the trivial (tv, 0) --, a depth
+ * d = `depth` (1 .. 16, the same for the whole batch) and selector indices sel_idx[g][0 .. d) into an rtfhe_trgsw set: entry k is address bit k,
+ * least significant first; NULL: lookup g uses selectors g * depth + k.  These are the tree's conventions.  It computes
+ *
+ *     level 0 node    x[g]
+ *     level t = 0 .. d-1, 2^t nodes, selector k = demux_level_selector(d, t) = d - 1 - t, S_k = selector sel_idx[g][k]:
+ *         child[2j+1] = cross(S_k, node_j)
+ *         child[2j]   = node_j - child[2j+1]
+ *     result          the 2^d children of level d - 1: leaf i is out[g][i]
+ *
+ * The subtraction wraps on every word of both polynomials; cross is Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306), i.e. exactly what
+ * rtfhe_external_product_batch computes for a key entry, and cross(S, x) = cmux(S, x, 0).  Leaf sum_k bit_k 2^k is a TRLWE of x[g]'s message
+ * and every other leaf a TRLWE of 0, each having passed d external products: 2^d - 1 products per lookup.  Level t splits on the selector
+ * the tree's level d - 1 - t joins on (the tree's level k uses selector k), so the demultiplexer is the tree's inverse: rtfhe_cmux_tree_batch
+ * over the 2^d leaves (as an encrypted table) with the same selectors returns a TRLWE of x[g]'s message, and with any address bit flipped a
+ * TRLWE of 0.
+ *   rtfhe_demux_tree_batch[_dev]   out[g][i] = leaf i, u32[count][2^d][2][N]: rows in the format of rtfhe_lut_create_encrypted and of
+ *                                  rtfhe_lut_accumulate_dev
+ * Checks before anything is allocated or launched: the handles, depth, count (count * 2^(depth-1) < 2^31), null x / out, host sel_idx in
+ * [0, n_sel), with sel_idx NULL count * depth <= n_sel, and in the _dev form d_out overlapping d_x: RTFHE_ERR_INVALID with a message naming
+ * the lookup.  The _dev form checks d_sel_idx in the kernel, all d indices of a lookup at every level: a lookup with a bad index is skipped
+ * whole, its 2^d output rows keep the bytes they had, and the next rtfhe_sync returns RTFHE_ERR_INVALID once, as for
+ * rtfhe_cmux_tree_batch_dev.  Only the selector set is needed, no key of the context.  The FP64 mirror backend only: on either exact backend
+ * every call fails with RTFHE_ERR_INVALID (the context stays usable).  A multi-device context runs it on its primary device.  The call reads
+ * rtfhe_set_leveled_decomposition when it is made, as the tree does.
+ * Scratch: level t < d - 1 writes count * 2^(t+1) nodes; the levels alternate between the two buffers of the stream that the CMUX tree uses,
+ * each of 4 * count * 2^(depth-1) * 2N bytes (none for depth 1), under the tree's rules: grown outside stream captures only (growing
+ * synchronises the device), kept until the context is destroyed, and inside a caller's stream capture an eager call with at least this
+ * count * 2^(depth-1) must have run on that stream first, else RTFHE_ERR_STATE (depth 1 needs none).
+ *
+ * rtfhe_lut_accumulate_dev adds TRLWEs into rows first .. first+n-1 of an ENCRYPTED table in place, stream-ordered:
+ *     row[first + r] += sum_{g < count} d_trlwe[g][r]      for r in [0, n), wrapping on every word of both polynomials
+ * Wrapping addition is exact in any order, so the result is deterministic.  With d_trlwe the leaves of `count` demultiplexed writes
+ * (n = 2^d) this is an oblivious scatter-add: the server adds x[g] into the row each encrypted address names without learning it.  It follows
+ * rtfhe_lut_update_dev's rules: RTFHE_ERR_INVALID for a plain table, for first < 0 or first + n > n_lut, for count < 1 and on a multi-device
+ * context, RTFHE_ERR_STATE after the context is gone; calls enqueued later on the same stream read the new rows; LUT circuits and CMUX netlists
+ * own a copy of their rows and are not affected.  d_trlwe must not overlap the table.
+ *
+ * rtfhe_lut_read_dev is rtfhe_lut_update_dev the other way: a stream-ordered copy of rows first .. first+n-1 of an ENCRYPTED table into
+ * device memory u32[n][2][N], under the same rules and refusals.  A table the server has written is state only the server holds; this is
+ * how its rows leave for whoever holds the key (the histogram's counts), and how the accumulation is checked word for word. */
+int rtfhe_demux_tree_batch(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const int32_t *sel_idx /* [count][depth] or NULL */, int32_t depth,
+                           const uint32_t *x /* [count][2][N] */, uint32_t *out /* [count][2^depth][2][N] */, size_t count);
+int rtfhe_demux_tree_batch_dev(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const void *d_sel_idx /* int32[count][depth] or NULL */, int32_t depth,
+                               const void *d_x /* [count][2][N] */, void *d_out /* [count][2^depth][2][N] */, size_t count, void *stream);
+int rtfhe_lut_accumulate_dev(rtfhe_lut *lut, const void *d_trlwe /* [count][n][2][N] */, int32_t first, int32_t n, size_t count, void *stream);
+int rtfhe_lut_read_dev(const rtfhe_lut *lut, void *d_out /* [n][2][N] */, int32_t first, int32_t n, void *stream);
 /* waits for `stream`; also reports (once) a netlist gate skipped since the previous call */
 int rtfhe_sync(rtfhe_ctx *ctx, void *stream);
 /* device-side timing of the launches enqueued by the *_dev calls between begin and end (HIP events on

@@ -4,11 +4,14 @@
 // rtfhe_set_leveled_decomposition), and for the extract form the batch key switch many-LUT uses.
 // Beside it the TRGSW blind rotation (rtfhe_trgsw_rotate_batch[_dev], rtfhe_trgsw_rotate_extract_batch[_dev]): the same selector sets, one
 // launch of k_trgsw_rotate for all steps of all lookups, the same key switch behind the extract form.
+// And the tree run backwards, the CMUX demultiplexer (rtfhe_demux_tree_batch[_dev]): one launch of k_demux_tree per level through the same
+// ping-pong buffers, with rtfhe_lut_accumulate_dev (k_trlwe_accumulate) adding the leaves into an encrypted table's rows.
 #include "rtfhe_host.hpp"
 
 #include <cstdlib>
 
 #include "rtfhe_kernels_cmux_tree.hpp"
+#include "rtfhe_kernels_demux_tree.hpp"
 #include "rtfhe_kernels_trgsw_rotate.hpp"
 
 using namespace rtfhe;
@@ -173,6 +176,94 @@ int tree_host(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, in
     }
     if (int rc = launch_tree(ctx, sel, d_sel_idx, depth, lut, d_row0, d_coef, ctx->d_c, count, extract, ctx->stream)) return rc;
     return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+}
+
+// ---- CMUX demultiplexer tree ----
+template <int LOGN, int W, bool ROUNDED>
+int launch_demux_level_t(rtfhe_ctx* ctx, const DemuxTreeArgs& a, size_t nodes, hipStream_t s) {
+    auto k = k_demux_tree<LOGN, 3, 6, W, ROUNDED>;
+    constexpr size_t lds = cmux_tree_lds_bytes<LOGN, W>();
+    if (int rc = allow_lds(ctx, k_demux_tree<LOGN, 3, 6, W, !ROUNDED>, lds)) return rc;      // (prime_demux has granted both already)
+    if (int rc = allow_lds(ctx, k, lds)) return rc;
+    hipLaunchKernelGGL(k, dim3((unsigned)((nodes + W - 1) / W)), dim3(64 * W), lds, s, a);
+    HIPCHECK(ctx, hipGetLastError());
+    ctx->launches++;
+    return 0;
+}
+
+int launch_demux_level(rtfhe_ctx* ctx, const DemuxTreeArgs& a, size_t nodes, hipStream_t s) {
+    // k_cmux_tree's shape: four waves (= input nodes) per workgroup at both N; the mode is read here, when the call is made
+    if (leveled_rounded(ctx)) return ctx->logn == 11 ? launch_demux_level_t<11, 4, true>(ctx, a, nodes, s) : launch_demux_level_t<10, 4, true>(ctx, a, nodes, s);
+    return ctx->logn == 11 ? launch_demux_level_t<11, 4, false>(ctx, a, nodes, s) : launch_demux_level_t<10, 4, false>(ctx, a, nodes, s);
+}
+
+// grants k_demux_tree its dynamic LDS when a selector set is created, beside the rotation's: both twins
+template <int LOGN>
+int prime_demux_t(rtfhe_ctx* ctx) {
+    if (int rc = allow_lds(ctx, k_demux_tree<LOGN, 3, 6, 4, false>, cmux_tree_lds_bytes<LOGN, 4>())) return rc;
+    return allow_lds(ctx, k_demux_tree<LOGN, 3, 6, 4, true>, cmux_tree_lds_bytes<LOGN, 4>());
+}
+int prime_demux(rtfhe_ctx* ctx) { return ctx->logn == 11 ? prime_demux_t<11>(ctx) : prime_demux_t<10>(ctx); }
+
+// what both demultiplexer entries check before anything is allocated or launched; host_sel_idx is null in the _dev form, whose array the kernel checks
+int demux_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, int32_t depth, size_t count, bool has_sel_idx, const int32_t* host_sel_idx, const void* x, const void* out) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!sel) return fail(ctx, RTFHE_ERR_INVALID, "null selector set (rtfhe_trgsw)");
+    if (!x || !out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (!sel->ctx) return fail(ctx, RTFHE_ERR_STATE, "the context of the selector set has been destroyed");
+    if (sel->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the selector set belongs to another context");
+    if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
+        return fail(ctx, RTFHE_ERR_INVALID, "the CMUX demultiplexer runs on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR); select it with rtfhe_set_backend");
+    if (depth < 1 || depth > DEMUX_TREE_MAX_DEPTH) return fail(ctx, RTFHE_ERR_INVALID, "depth = " + std::to_string(depth) + " is outside [1, 16]");
+    if (count > ((size_t)0x7fffffff >> (depth - 1))) return fail(ctx, RTFHE_ERR_INVALID, "count * 2^(depth-1) too large");
+    const long long n_sel = sel->n_sel;
+    if (!has_sel_idx && (long long)count * depth > n_sel)
+        return fail(ctx, RTFHE_ERR_INVALID, "sel_idx NULL: lookup " + std::to_string(count - 1) + " needs selectors up to " + std::to_string((long long)count * depth - 1) +
+                                            ", the set has " + std::to_string(n_sel));
+    if (host_sel_idx)
+        for (size_t g = 0; g < count; g++)
+            for (int k = 0; k < depth; k++)
+                if ((uint32_t)host_sel_idx[g * depth + k] >= (uint32_t)sel->n_sel)
+                    return fail(ctx, RTFHE_ERR_INVALID, "lookup " + std::to_string(g) + ": sel_idx[" + std::to_string(k) + "] = " + std::to_string(host_sel_idx[g * depth + k]) +
+                                                        " is outside [0, " + std::to_string(n_sel) + ")");
+    return 0;
+}
+
+// The demultiplexer of `count` TRLWEs on device buffers, primary device, stream s.  d_x: [count][2][N], d_out: [count][2^depth][2][N].  Level t
+// reads count << t nodes and writes twice as many; levels 0 .. depth-2 alternate between the stream's ping-pong buffers (the tree's, under the
+// tree's rules), the last level writes d_out.
+int launch_demux(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* d_sel_idx, int32_t depth, const void* d_x, void* d_out, size_t count, hipStream_t s) {
+    if (count == 0) return 0;
+    const size_t N = (size_t)ctx->p.N, need = depth > 1 ? (count << (depth - 1)) * 2 * N : 0;      // words of each ping-pong buffer
+    auto it = ctx->tree.find(s);
+    if (capturing(s)) {
+        if (need && (it == ctx->tree.end() || it->second.cap < need))
+            return fail(ctx, RTFHE_ERR_STATE, "a CMUX demultiplexer inside a stream capture needs this stream's ping-pong buffers to exist already: run one eager "
+                                              "rtfhe_demux_tree_batch_dev of at least this count and depth on the stream before capturing");
+        if (need) it->second.captured = true;
+    } else if (need && (it == ctx->tree.end() || it->second.cap < need)) {
+        rtfhe_ctx::TreeBuf& tb = ctx->tree[s];
+        HIPCHECK(ctx, hipDeviceSynchronize());            // earlier trees of this stream may still read the old buffers
+        for (uint32_t*& d : tb.d) {
+            if (d && tb.captured) ctx->mux_retired.push_back(d);      // a graph holds its address: kept until the context goes
+            else if (d) HIPCHECK(ctx, hipFree(d));
+            d = nullptr;
+        }
+        tb.cap = 0; tb.captured = false;
+        for (uint32_t*& d : tb.d) HIPCHECK(ctx, hipMalloc((void**)&d, need * 4));
+        tb.cap = need;
+        it = ctx->tree.find(s);
+    }
+    DemuxTreeArgs a{};
+    a.tw = ctx->d_tw; a.sel = sel->d_spec; a.sel_idx = d_sel_idx; a.fault = ctx->d_fault;
+    a.count = (int32_t)count; a.depth = depth; a.n_sel = sel->n_sel;
+    for (int level = 0; level < depth; level++) {
+        a.level = level;
+        a.src = level ? it->second.d[(level - 1) & 1] : (const uint32_t*)d_x;
+        a.dst = level == depth - 1 ? (uint32_t*)d_out : it->second.d[level & 1];
+        if (int rc = launch_demux_level(ctx, a, count << level, s)) return rc;
+    }
+    return 0;
 }
 
 // ---- TRGSW blind rotation ----
@@ -340,6 +431,7 @@ int rtfhe_trgsw_create(rtfhe_ctx* ctx, const uint32_t* trgsw, int32_t n_sel, rtf
     *out = nullptr;
     if (int rc = use(ctx)) return rc;
     if (int rc = prime_rotate(ctx)) return rc;
+    if (int rc = prime_demux(ctx)) return rc;
     const size_t polys = (size_t)n_sel * 2 * 2 * ctx->p.l, words = polys * ctx->p.N;
     if (polys > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_create: n_sel too large");
     rtfhe_trgsw* t = new rtfhe_trgsw();
@@ -390,6 +482,78 @@ int rtfhe_cmux_tree_extract_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const 
 int rtfhe_cmux_tree_extract_batch_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int32_t depth, const rtfhe_lut* lut, const void* d_row0,
                                       const void* d_coef, void* d_out, size_t count, void* stream) {
     return tree_dev(ctx, sel, d_sel_idx, depth, lut, d_row0, d_coef, d_out, count, true, stream, "rtfhe_cmux_tree_extract_batch_dev");
+}
+
+int rtfhe_demux_tree_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, int32_t depth, const uint32_t* x, uint32_t* out, size_t count) {
+    if (int rc = demux_ready(ctx, sel, depth, count, sel_idx != nullptr, sel_idx, x, out)) return rc;
+    if (int rc = use(ctx)) return rc;
+    if (count == 0) return 0;
+    // host buffers: sel_idx rides in d_a, the inputs in d_b, the leaves come back through d_c
+    const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = in_bytes << depth;
+    if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, in_bytes)) return rc;
+    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
+    const int32_t* d_sel_idx = nullptr;
+    if (sel_idx) {
+        if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, count * depth * 4)) return rc;
+        if (int rc = copy_in(ctx, ctx->d_a, sel_idx, count * depth * 4, 0)) return rc;
+        d_sel_idx = (const int32_t*)ctx->d_a;
+    }
+    if (int rc = copy_in(ctx, ctx->d_b, x, in_bytes, 1)) return rc;
+    if (int rc = launch_demux(ctx, sel, d_sel_idx, depth, ctx->d_b, ctx->d_c, count, ctx->stream)) return rc;
+    return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+}
+
+int rtfhe_demux_tree_batch_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int32_t depth, const void* d_x, void* d_out, size_t count,
+                               void* stream) {
+    if (int rc = demux_ready(ctx, sel, depth, count, d_sel_idx != nullptr, nullptr, d_x, d_out)) return rc;
+    if (int rc = use(ctx)) return rc;
+    if (!gpu_accessible(ctx, d_out) || !gpu_accessible(ctx, d_x) || (d_sel_idx && !gpu_accessible(ctx, d_sel_idx)))
+        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_demux_tree_batch_dev needs device pointers (got memory the GPU cannot address)");
+    const char *i0 = (const char*)d_x, *o0 = (const char*)d_out;
+    const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = in_bytes << depth;
+    if (i0 < o0 + out_bytes && o0 < i0 + in_bytes)      // the last level stores leaves while other waves still read their nodes (depth 1: x itself)
+        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_demux_tree_batch_dev: d_out overlaps d_x");
+    return launch_demux(ctx, sel, (const int32_t*)d_sel_idx, depth, d_x, d_out, count, (hipStream_t)stream);
+}
+
+int rtfhe_lut_accumulate_dev(rtfhe_lut* lut, const void* d_trlwe, int32_t first, int32_t n, size_t count, void* stream) {
+    if (!lut) return fail(nullptr, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
+    rtfhe_ctx* ctx = lut->ctx;
+    if (!ctx) return fail(nullptr, RTFHE_ERR_STATE, "the context of the table has been destroyed");
+    if (!d_trlwe) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (!lut->encrypted) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_accumulate_dev adds into the rows of an encrypted table (rtfhe_lut_create_encrypted); this one is plain");
+    if (!ctx->peers.empty()) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_accumulate_dev: a multi-device context holds one copy of the table per device; not supported");
+    if (first < 0 || n < 0 || (long long)first + n > lut->n_lut)
+        return fail(ctx, RTFHE_ERR_INVALID, "rows [" + std::to_string(first) + ", " + std::to_string((long long)first + n) + ") are outside the table's [0, " +
+                                            std::to_string(lut->n_lut) + ")");
+    if (count < 1 || count > (size_t)0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "count = " + std::to_string(count) + " is outside [1, 2^31)");
+    if (int rc = use(ctx)) return rc;
+    if (!gpu_accessible(ctx, d_trlwe)) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_accumulate_dev needs a device pointer (got memory the GPU cannot address)");
+    if (n == 0) return 0;
+    const size_t row = 2 * (size_t)ctx->p.N;
+    TrlweAccumulateArgs a{lut->d_tv[0] + (size_t)first * row, (const uint32_t*)d_trlwe, (size_t)n * row, (int32_t)count};
+    hipLaunchKernelGGL(k_trlwe_accumulate, dim3((unsigned)((a.words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    HIPCHECK(ctx, hipGetLastError());
+    ctx->launches++;
+    return 0;
+}
+
+int rtfhe_lut_read_dev(const rtfhe_lut* lut, void* d_out, int32_t first, int32_t n, void* stream) {
+    if (!lut) return fail(nullptr, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
+    rtfhe_ctx* ctx = lut->ctx;
+    if (!ctx) return fail(nullptr, RTFHE_ERR_STATE, "the context of the table has been destroyed");
+    if (!d_out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (!lut->encrypted) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_read_dev copies the rows of an encrypted table (rtfhe_lut_create_encrypted); this one is plain");
+    if (!ctx->peers.empty()) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_read_dev: a multi-device context holds one copy of the table per device; not supported");
+    if (first < 0 || n < 0 || (long long)first + n > lut->n_lut)
+        return fail(ctx, RTFHE_ERR_INVALID, "rows [" + std::to_string(first) + ", " + std::to_string((long long)first + n) + ") are outside the table's [0, " +
+                                            std::to_string(lut->n_lut) + ")");
+    if (int rc = use(ctx)) return rc;
+    if (!gpu_accessible(ctx, d_out)) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_read_dev needs a device pointer (got memory the GPU cannot address)");
+    if (n == 0) return 0;
+    const size_t row = 2 * (size_t)ctx->p.N;
+    HIPCHECK(ctx, hipMemcpyAsync(d_out, lut->d_tv[0] + (size_t)first * row, (size_t)n * row * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
 }
 
 int rtfhe_trgsw_rotate_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, int32_t depth, const int32_t* rot, const uint32_t* trlwe,

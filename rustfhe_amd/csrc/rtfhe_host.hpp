@@ -9,6 +9,7 @@
 //   rtfhe_circuit.hip        levelised netlists: one wave per call, or all waves recorded into a HIP graph
 //   rtfhe_multi.hip          one context over several GPUs: key replication, sharding of host batches and of device-resident batches
 //   rtfhe_cmux_tree.hip      CMUX-tree table lookup: selector sets (caller-supplied TRGSW samples), one launch per tree level; TRGSW blind rotation
+//                            and the CMUX demultiplexer tree with the accumulation of its leaves into an encrypted table's rows
 //   rtfhe_cmux_net.hip       CMUX netlists: decision diagrams over a selector set, levelised (rtfhe_cmux_net_plan.cpp, host only) and recorded into a HIP graph
 //   rtfhe_pack.hip           packing key switch: packing keys (signed byte limbs in operand order), lvl0 samples into TRLWE rows, in-place table updates
 // Every kernel is instantiated in exactly one of them.  No CPU fallback anywhere: an entry point runs HIP kernels or fails.

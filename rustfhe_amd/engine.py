@@ -395,6 +395,28 @@ class Engine:
         self._ck(self.L.rtfhe_trgsw_rotate_extract_batch_dev(self.h, sel.h, self._dev(d_sel_idx), int(depth), _ptr(r), self._dev(d_trlwe), self._dev(d_out),
                                                              count, C.c_void_p(stream) if stream else None))
 
+    # ---- CMUX demultiplexer tree (include/rtfhe.h: rtfhe_demux_tree_batch[_dev], rtfhe_lut_accumulate_dev) --------------------------------------
+    def demux_tree_batch(self, sel, x, depth, sel_idx=None):
+        """One demultiplexer per TRLWE of u32[count][2][N] (a plain polynomial tv goes in as the trivial (tv, 0)): leaf (address bits
+        sel_idx[g][0 .. depth), least significant first; None: selectors g * depth + k) of the 2^depth leaves is a TRLWE of x[g]'s message,
+        every other leaf a TRLWE of 0; u32[count][2^depth][2][N].  Level t splits on selector demux_level_selector(depth, t) = depth - 1 - t,
+        the one cmux_tree_batch's level depth - 1 - t joins on: cmux_tree_batch over the leaves with the same selectors gives x[g] back.
+        Indices are checked here: a bad one raises RtfheError before anything runs."""
+        x = _np(x, np.uint32).reshape(-1, 2, self.p.N)
+        count = x.shape[0]
+        idx = None if sel_idx is None else _np(sel_idx, np.int32).reshape(count, depth)
+        out = np.empty((count, 1 << int(depth) if 1 <= int(depth) <= 16 else 1, 2, self.p.N), np.uint32)      # (a bad depth is refused by the library)
+        self._ck(self.L.rtfhe_demux_tree_batch(self.h, sel.h, _ptr(idx), int(depth), _ptr(x), _ptr(out), count))
+        return out
+
+    def demux_tree_batch_dev(self, sel, d_x, depth, d_out, count, d_sel_idx=None, stream=None):
+        """... on device buffers (d_x: [count][2][N] words, d_out: [count][2^depth][2][N] words, not overlapping; d_sel_idx:
+        int32[count][depth]), asynchronous on `stream`; a lookup with a bad index is skipped, its 2^depth output rows untouched, and the next
+        sync() raises.  Inside a stream capture an eager call of at least this count and depth must have run on the stream first (depth 1
+        needs none)."""
+        self._ck(self.L.rtfhe_demux_tree_batch_dev(self.h, sel.h, self._dev(d_sel_idx), int(depth), self._dev(d_x), self._dev(d_out), count,
+                                                   C.c_void_p(stream) if stream else None))
+
     # ---- CMUX netlists (include/rtfhe.h: rtfhe_cmux_circuit_create; rustfhe_amd.cmux_net) -----------------------------------------------------
     def cmux_circuit(self, netlist, sel, lut, d_out, count, d_sel_idx=None, d_row0=None, rounded=None):
         """Records `count` replicas of a CmuxNetlist over the selector set `sel` and the table `lut` into one graph.  d_out: device buffer
@@ -515,6 +537,24 @@ class Lut:
         output of Engine.pack_batch_dev; a copy ordered on `stream`.  Refused for a plain table, a bad range and a multi-device Engine."""
         e = self.engine
         rc = e.L.rtfhe_lut_update_dev(self.h, e._dev(d_trlwe), int(first), int(n), C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise RtfheError(rc, (e.L.rtfhe_last_error(e.h if e.h else None) or b"").decode())
+
+    def accumulate_dev(self, d_trlwe, first=0, n=1, count=1, stream=None):
+        """Adds device TRLWEs u32[count][n][2][N] into rows [first, first + n) of an encrypted table in place (rtfhe_lut_accumulate_dev):
+        row[first + r] += sum over g of d_trlwe[g][r], wrapping on every word, ordered on `stream` -- e.g. the leaves of
+        Engine.demux_tree_batch_dev (n = 2^depth): an oblivious scatter-add.  Refused for a plain table, a bad range, count < 1 and a
+        multi-device Engine."""
+        e = self.engine
+        rc = e.L.rtfhe_lut_accumulate_dev(self.h, e._dev(d_trlwe), int(first), int(n), int(count), C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise RtfheError(rc, (e.L.rtfhe_last_error(e.h if e.h else None) or b"").decode())
+
+    def read_dev(self, d_out, first=0, n=1, stream=None):
+        """Copies rows [first, first + n) of an encrypted table into device memory u32[n][2][N] (rtfhe_lut_read_dev), ordered on `stream`:
+        update_dev the other way, under the same refusals."""
+        e = self.engine
+        rc = e.L.rtfhe_lut_read_dev(self.h, e._dev(d_out), int(first), int(n), C.c_void_p(stream) if stream else None)
         if rc != 0:
             raise RtfheError(rc, (e.L.rtfhe_last_error(e.h if e.h else None) or b"").decode())
 
@@ -710,6 +750,13 @@ def keygen(params, seed=None, want_bk=True, want_ksk=True):
     if rc != 0:
         raise RtfheError(rc, "rtfhe_keygen failed")
     return key0, key1, bk, ksk
+
+
+def demux_level_selector(depth, level):
+    """The selector (address bit) that level `level` of a depth-`depth` demultiplexer (Engine.demux_tree_batch) splits on: depth - 1 - level,
+    the most significant bit first.  Level k of cmux_tree_batch joins on selector k, so demux level t undoes tree level
+    demux_level_selector(depth, t): the demultiplexer is the tree's inverse."""
+    return int(depth) - 1 - int(level)
 
 
 def packing_key_words(params):
