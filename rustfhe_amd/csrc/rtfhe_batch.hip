@@ -13,17 +13,43 @@ int backend_prepare(rtfhe_ctx* ctx) {
     return 0;
 }
 
-// lvl1 sample buffer of the split path for stream s: sized outside launches (hipMalloc is not allowed inside a stream capture)
-int ensure_tlwe1(rtfhe_ctx* ctx, rtfhe_ctx::Tlwe1& b, size_t gates) {
-    if (b.cap >= gates) return 0;
-    HIPCHECK(ctx, hipDeviceSynchronize());            // earlier launches may still read the old buffer
-    if (b.d && b.captured) ctx->mux_retired.push_back(b.d);      // a caller's graph holds its address: kept until the context goes
-    else if (b.d) HIPCHECK(ctx, hipFree(b.d));
-    b.d = nullptr; b.cap = 0; b.captured = false;
-    const size_t cap = ((gates < 1024 ? 1024 : gates) + 15) / 16 * 16;      // whole tiles of 16 gates (rtfhe::ext_slot): 16 N + 16 words each
-    HIPCHECK(ctx, hipMalloc((void**)&b.d, cap * ((size_t)ctx->p.N + 1) * 4));
+// Scratch is sized outside launches (hipMalloc is not allowed inside a stream capture).  Every step leaves b consistent: it is cleared before
+// anything is freed, so a failure cannot leave a freed address behind, and a pair whose second hipMalloc fails gives the first back.
+int grow_scratch(rtfhe_ctx* ctx, StreamScratch& b, const ScratchShape& shape, size_t need) {
+    if (b.cap >= need) return 0;
+    HIPCHECK(ctx, hipDeviceSynchronize());            // earlier launches may still read the old buffers
+    const StreamScratch old = b;
+    b = StreamScratch{};
+    hipError_t e = hipSuccess;
+    for (uint32_t* d : old.d) {
+        if (!d) continue;
+        if (old.captured) ctx->mux_retired.push_back(d);      // a caller's graph holds its address: kept until the context goes
+        else if (hipError_t f = hipFree(d); e == hipSuccess) e = f;
+    }
+    const size_t cap = ((need < shape.min_cap ? shape.min_cap : need) + shape.tile - 1) / shape.tile * shape.tile;
+    for (int i = 0; i < shape.bufs && e == hipSuccess; i++) e = hipMalloc((void**)&b.d[i], cap * shape.unit_bytes);
+    if (e != hipSuccess) {
+        for (uint32_t*& d : b.d) { if (d) (void)hipFree(d); d = nullptr; }
+        return fail(ctx, RTFHE_ERR_HIP, std::string("per-stream scratch (hipFree / hipMalloc): ") + hipGetErrorString(e));
+    }
     b.cap = cap;
     return 0;
+}
+
+int stream_scratch(rtfhe_ctx* ctx, ScratchMap& map, hipStream_t s, bool in_capture, const ScratchShape& shape, size_t need, const char* refusal,
+                   StreamScratch*& out, StreamScratch* own) {
+    out = own;
+    if (!out) {
+        auto it = map.find(s);
+        if (it != map.end()) out = &it->second;
+    }
+    if (in_capture) {
+        if (!out || out->cap < need) return fail(ctx, RTFHE_ERR_STATE, refusal);
+        out->captured = true;
+        return 0;
+    }
+    if (!out) out = &map[s];
+    return grow_scratch(ctx, *out, shape, need);
 }
 
 int launch_bootstrap(rtfhe_ctx* ctx, int op, int mode, int steps, const void* d_in0, const void* d_in1, void* d_out,
@@ -47,17 +73,12 @@ int launch_bootstrap(rtfhe_ctx* ctx, int op, int mode, int steps, const void* d_
     // second key layout the dispatch of this batch reads is built on first use.  Inside a capture that is not rtfhe_circuit_create's own
     // (which prepared both before it began) the batch stays on the fused kernel and on the kernels that read the canonical key layout.
     if (!ctx->tlwe1_capture) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-        if (cs != hipStreamCaptureStatusNone) {
+        if (capturing(s)) {
             ctx->foreign_capture = true;
         } else {
             if (int rc = ensure_bk_layouts(ctx, count, mode)) return rc;
-            if (mode == MODE_GATE && ctx->ks_mm_min > 0 && ctx->d_ksmat) {
-                const rtfhe_ctx::Tlwe1* have = tlwe1_of(ctx, s);
-                if (!have || count > have->cap)
-                    if (int rc = ensure_tlwe1(ctx, ctx->tlwe1[s], count)) return rc;
-            }
+            if (mode == MODE_GATE && ctx->ks_mm_min > 0 && ctx->d_ksmat)
+                if (int rc = ensure_tlwe1(ctx, ctx->tlwe1[s], count)) return rc;
         }
     }
     if (lut.tv && ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
@@ -119,7 +140,7 @@ int run_host_pbs_one(rtfhe_ctx* ctx, const LutRef& lut, const int32_t* lut_idx, 
 // sample.  Outside a stream capture the sample buffer grows and the second key layout is built here; inside one nothing may be allocated: the
 // sample buffer is rtfhe_lut_circuit_create's own (handed over through tlwe1_capture), or else this stream's, which must already hold
 // count << shift samples -- an eager many-PBS of at least `count` gates and at least this many outputs on the stream first -- and is then kept
-// for as long as the context lives (Tlwe1::captured).
+// for as long as the context lives (StreamScratch::captured).
 int launch_pbs_many(rtfhe_ctx* ctx, const LutRef& lut, const void* d_in, void* d_out, size_t count, hipStream_t s, bool zero_out) {
     if (!ctx->has_bk) return fail(ctx, RTFHE_ERR_STATE, "bootstrapping key not loaded");
     if (!ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "key-switching key not loaded");
@@ -128,32 +149,23 @@ int launch_pbs_many(rtfhe_ctx* ctx, const LutRef& lut, const void* d_in, void* d
     if (count == 0) return 0;
     const size_t rows = count << lut.shift;
     if (rows > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "count << log2(n_out) too large");
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-    rtfhe_ctx::Tlwe1* buf = tlwe1_of(ctx, s);
-    if (cs != hipStreamCaptureStatusNone) {
-        if (!buf || buf->cap < rows)
-            return fail(ctx, RTFHE_ERR_STATE, "a many-LUT PBS inside a stream capture needs this stream's sample buffer to exist already: run one eager "
-                                              "rtfhe_pbs_many_batch_dev of at least this many gates and outputs on the stream before capturing");
-        buf->captured = true;
-    } else {
+    const bool cap = capturing(s);
+    if (!cap)
         if (int rc = ensure_bk_layouts(ctx, count, MODE_EXTRACT)) return rc;
-        if (int rc = ensure_tlwe1(ctx, ctx->tlwe1[s], rows)) return rc;
-        buf = &ctx->tlwe1[s];
-    }
+    StreamScratch* buf = nullptr;
+    if (int rc = stream_scratch(ctx, ctx->tlwe1, s, cap, tlwe1_shape(ctx), rows,
+                                "a many-LUT PBS inside a stream capture needs this stream's sample buffer to exist already: run one eager "
+                                "rtfhe_pbs_many_batch_dev of at least this many gates and outputs on the stream before capturing", buf, ctx->tlwe1_capture))
+        return rc;
     BootstrapArgs a{};
     a.tw = ctx->d_tw; a.bk = ctx->d_bk; a.ksk = ctx->d_ksk;
     a.in0 = (const uint32_t*)d_in; a.in1 = a.in0; a.out = (uint32_t*)d_out;
     a.count = (int)count; a.op = RTFHE_COPY; a.n = ctx->p.n; a.steps = ctx->p.n; a.mode = MODE_EXTRACT; a.ksw = ctx->ksw;
     a.npad = (ctx->p.n + 1 + 63) / 64 * 64;
     a.fault = ctx->d_fault; a.dbg = ctx->d_dbg;
-    a.ext = buf->d; a.ext_first = 0;
+    a.ext = buf->d[0]; a.ext_first = 0;
     if (int rc = launch_bootstrap_fft(ctx, a, s, lut)) return rc;
-    if (!ctx->d_ksmat) return launch_key_switch_ext(ctx, buf->d, (uint32_t*)d_out, rows, s);
-    if (zero_out) HIPCHECK(ctx, hipMemsetAsync(d_out, 0, rows * ((size_t)ctx->p.n + 1) * 4, s));      // the K-slices add into it
-    BootstrapArgs k = a;
-    k.count = (int32_t)rows;
-    return launch_key_switch_mm(ctx, k, buf->d, s);
+    return launch_key_switch_rows(ctx, buf->d[0], (uint32_t*)d_out, rows, s, zero_out);
 }
 
 // hom_mux (tfhe.rs:27-40): i1 = AND(c, in1); i0 = AND(-c, in0); bootstrap(i1 + i0 + 1/8) -- the last line is hom_or(i1, i0).
@@ -165,30 +177,13 @@ int mux_dev_one(rtfhe_ctx* ctx, const void* d_c, const void* d_in0, const void* 
     if (int rc = use(ctx)) return rc;
     if (count == 0) return 0;
     const size_t bytes = count * ((size_t)ctx->p.n + 1) * 4;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-    const bool capturing = cs != hipStreamCaptureStatusNone;
-    auto it = ctx->mux.find(s);
-    if (capturing) {
-        if (it == ctx->mux.end() || it->second.cap < bytes)
-            return fail(ctx, RTFHE_ERR_STATE, "a MUX batch inside a stream capture needs this stream's intermediate buffers to exist already: run one eager MUX batch of "
-                                              "at least this many gates on the stream before capturing");
-        it->second.captured = true;
-    } else if (it == ctx->mux.end() || it->second.cap < bytes) {
-        rtfhe_ctx::MuxBuf& mb = ctx->mux[s];
-        HIPCHECK(ctx, hipDeviceSynchronize());            // earlier MUX batches of this stream may still read the old intermediates
-        for (void*& m : mb.m) {
-            if (m && mb.captured) ctx->mux_retired.push_back(m);      // a graph holds its address: kept until the context goes
-            else if (m) HIPCHECK(ctx, hipFree(m));
-            m = nullptr;
-        }
-        mb.cap = 0; mb.captured = false;
-        for (void*& m : mb.m) HIPCHECK(ctx, hipMalloc(&m, bytes));
-        mb.cap = bytes;
-        it = ctx->mux.find(s);
-    }
-    void* const i1 = it->second.m[0];
-    void* const i0 = it->second.m[1];
+    StreamScratch* mb = nullptr;
+    if (int rc = stream_scratch(ctx, ctx->mux, s, capturing(s), ScratchShape{2, 1}, bytes,
+                                "a MUX batch inside a stream capture needs this stream's intermediate buffers to exist already: run one eager MUX batch of "
+                                "at least this many gates on the stream before capturing", mb))
+        return rc;
+    void* const i1 = mb->d[0];
+    void* const i0 = mb->d[1];
     const int n = ctx->p.n;
     if (int rc = launch_bootstrap(ctx, RTFHE_AND, MODE_GATE, n, d_c, d_in1, i1, count, s)) return rc;
     if (int rc = launch_bootstrap(ctx, RTFHE_ANDNY, MODE_GATE, n, d_c, d_in0, i0, count, s)) return rc;

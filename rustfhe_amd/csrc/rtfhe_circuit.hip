@@ -93,22 +93,22 @@ int rtfhe_circuit_create(rtfhe_ctx* ctx, const void* d_ops, const void* d_idx0, 
     if (int rc = backend_prepare(ctx)) return rc;          // nothing but kernel launches may happen inside the capture
     for (int32_t w = 0; w < num_waves; w++)                // ... so the key layouts the waves' dispatches read are built now
         if (int rc = ensure_bk_layouts(ctx, (size_t)(wave_offsets[w + 1] - wave_offsets[w]), MODE_GATE)) return rc;
-    rtfhe_ctx::Tlwe1 cbuf;                                 // ... so the circuit's own sample buffer (split path) is allocated now
+    StreamScratch cbuf;                                 // ... so the circuit's own sample buffer (split path) is allocated now
     if (ctx->ks_mm_min > 0 && ctx->d_ksmat) {
         size_t widest = 0;
         for (int32_t w = 0; w < num_waves; w++) widest = std::max(widest, (size_t)(wave_offsets[w + 1] - wave_offsets[w]));
         if (int rc = ensure_tlwe1(ctx, cbuf, widest)) return rc;
     }
     rtfhe_circuit* c = new (std::nothrow) rtfhe_circuit();
-    if (!c) { if (cbuf.d) (void)hipFree(cbuf.d); return fail(ctx, RTFHE_ERR_NOMEM, "out of host memory"); }
-    c->ctx = ctx; c->device = ctx->device; c->waves = num_waves; c->d_samples = cbuf.d; c->backend = ctx->backend;
+    if (!c) { if (cbuf.d[0]) (void)hipFree(cbuf.d[0]); return fail(ctx, RTFHE_ERR_NOMEM, "out of host memory"); }
+    c->ctx = ctx; c->device = ctx->device; c->waves = num_waves; c->d_samples = cbuf.d[0]; c->backend = ctx->backend;
     const int64_t before = ctx->launches;
     hipError_t e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { circuit_release(c); delete c; return fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e)); }
     e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
     if (e != hipSuccess) { circuit_release(c); delete c; return fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e)); }
     int rc = 0;
-    ctx->tlwe1_capture = cbuf.d ? &cbuf : nullptr;
+    ctx->tlwe1_capture = cbuf.d[0] ? &cbuf : nullptr;
     for (int32_t w = 0; w < num_waves && !rc; w++) {
         const size_t off = (size_t)wave_offsets[w], cnt = (size_t)(wave_offsets[w + 1] - wave_offsets[w]);
         rc = launch_bootstrap(ctx, RTFHE_COPY, MODE_GATE, ctx->p.n, d_wires, d_wires, d_wires, cnt, ctx->stream,
@@ -192,9 +192,9 @@ int rtfhe_lut_circuit_create(rtfhe_ctx* ctx, const rtfhe_lut* lut, int32_t fan_i
     if (!c) return fail(ctx, RTFHE_ERR_NOMEM, "out of host memory");
     c->ctx = ctx; c->device = ctx->device; c->waves = num_waves; c->backend = ctx->backend;
     auto bail = [&](int rc) { circuit_release(c); delete c; return rc; };
-    rtfhe_ctx::Tlwe1 cbuf;
+    StreamScratch cbuf;
     if (int rc = ensure_tlwe1(ctx, cbuf, widest_rows)) return bail(rc);
-    c->d_samples = cbuf.d;
+    c->d_samples = cbuf.d[0];
     // description: in_idx, weights [nodes][fan_in] | cst, lut_idx [nodes] | out_idx [rows]
     const size_t desc_words = (size_t)nodes * (2 * fan_in + 2) + rows;
     std::vector<int32_t> desc(desc_words, 0);

@@ -14,34 +14,12 @@ using namespace rtfhe_host;
 
 namespace {
 
-constexpr int NET_WAVES = 4;      // four waves (= nodes) per workgroup at both N, the tree's shape
+RTFHE_LEVELED_FAMILY(net_twins, CmuxNetArgs, k_cmux_net, cmux_tree_lds_bytes<LOGN, LEVELED_WAVES>())      // the tree's shape and LDS carve
 
-template <int LOGN>
-int prime_net_t(rtfhe_ctx* ctx) {
-    if (int rc = allow_lds(ctx, k_cmux_net<LOGN, 3, 6, NET_WAVES, false>, cmux_tree_lds_bytes<LOGN, NET_WAVES>())) return rc;
-    return allow_lds(ctx, k_cmux_net<LOGN, 3, 6, NET_WAVES, true>, cmux_tree_lds_bytes<LOGN, NET_WAVES>());
-}
-
-unsigned blocks_of(size_t waves) { return (unsigned)((waves + NET_WAVES - 1) / NET_WAVES); }
-
-template <int LOGN>
-int launch_net_t(rtfhe_ctx* ctx, const CmuxNetArgs& a, int what, hipStream_t s) {
-    const dim3 block(64 * NET_WAVES);
-    constexpr size_t lds = cmux_tree_lds_bytes<LOGN, NET_WAVES>();
-    if (what == 0) hipLaunchKernelGGL((k_cmux_net_check<NET_WAVES>), dim3(blocks_of((size_t)a.count)), block, 0, s, a);
-    else if (what == 1 && leveled_rounded(ctx))
-        hipLaunchKernelGGL((k_cmux_net<LOGN, 3, 6, NET_WAVES, true>), dim3(blocks_of((size_t)a.count * a.n_level)), block, lds, s, a);
-    else if (what == 1)
-        hipLaunchKernelGGL((k_cmux_net<LOGN, 3, 6, NET_WAVES, false>), dim3(blocks_of((size_t)a.count * a.n_level)), block, lds, s, a);
-    else hipLaunchKernelGGL((k_cmux_net_out<LOGN, NET_WAVES>), dim3(blocks_of((size_t)a.count * a.n_out)), block, 0, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
-}
-
-// what: 0 = k_cmux_net_check, 1 = k_cmux_net (one level; the twin of the leveled mode in force: the graph keeps it), 2 = k_cmux_net_out
-int launch_net(rtfhe_ctx* ctx, const CmuxNetArgs& a, int what, hipStream_t s) {
-    return ctx->logn == 11 ? launch_net_t<11>(ctx, a, what, s) : launch_net_t<10>(ctx, a, what, s);
+// k_cmux_net_check and k_cmux_net_out: no twin, no dynamic LDS, a wave per replica / per (replica, output) on the same workgroups of four waves
+template <typename K>
+int launch_net_plain(rtfhe_ctx* ctx, K k, size_t waves, const CmuxNetArgs& a, hipStream_t s) {
+    return launch_kernel(ctx, k, dim3((unsigned)((waves + LEVELED_WAVES - 1) / LEVELED_WAVES)), dim3(64 * LEVELED_WAVES), 0, s, a);
 }
 
 }  // namespace
@@ -54,14 +32,7 @@ int rtfhe_cmux_circuit_create(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const rtfh
     if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
     if (!out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (!sel) return fail(ctx, RTFHE_ERR_INVALID, "null selector set (rtfhe_trgsw)");
-    if (!lut) return fail(ctx, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
-    if (!var || !hi || !lo || !out_ref || !d_out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    if (!sel->ctx || !lut->ctx) return fail(ctx, RTFHE_ERR_STATE, "the context of the selector set or of the table has been destroyed");
-    if (sel->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the selector set belongs to another context");
-    if (lut->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the table belongs to another context");
-    if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
-        return fail(ctx, RTFHE_ERR_INVALID, "CMUX netlists run on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR); select it with rtfhe_set_backend");
+    if (int rc = selector_set_ready(ctx, sel, true, lut, var && hi && lo && out_ref && d_out, "CMUX netlists run")) return rc;
     if (n_nodes < 1 || n_vars < 1 || n_out < 1 || count < 1)
         return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_cmux_circuit_create: n_nodes, n_vars, n_out and count must be at least 1");
     // the whole description is checked and levelised before anything is allocated, captured or launched
@@ -79,16 +50,17 @@ int rtfhe_cmux_circuit_create(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const rtfh
     if (!gpu_accessible(ctx, d_out) || (d_sel_idx && !gpu_accessible(ctx, d_sel_idx)) || (d_row0 && !gpu_accessible(ctx, d_row0)))
         return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_cmux_circuit_create needs device pointers (got memory the GPU cannot address)");
     // everything that allocates or synchronises happens now, outside the capture
-    if (int rc = ctx->logn == 11 ? prime_net_t<11>(ctx) : prime_net_t<10>(ctx)) return rc;
+    const LeveledTwins<CmuxNetArgs> net = net_twins(ctx);
+    if (int rc = prime_leveled(ctx, net)) return rc;
     rtfhe_circuit* c = new (std::nothrow) rtfhe_circuit();
     if (!c) return fail(ctx, RTFHE_ERR_NOMEM, "out of host memory");
     c->ctx = ctx; c->device = ctx->device; c->waves = n_levels; c->backend = ctx->backend; c->sel = sel;
     auto bail = [&](int rc) { circuit_release(c); delete c; return rc; };
-    const size_t samples = count * (size_t)n_out, n1 = (size_t)ctx->p.n + 1;
-    rtfhe_ctx::Tlwe1 cbuf;
+    const size_t samples = count * (size_t)n_out;
+    StreamScratch cbuf;
     if (extract) {
         if (int rc = ensure_tlwe1(ctx, cbuf, samples)) return bail(rc);
-        c->d_samples = cbuf.d;
+        c->d_samples = cbuf.d[0];
     }
     // description: var, hi, lo, rot, order [n_nodes] each | out_ref, out_coef [n_out] each
     const size_t desc_words = (size_t)n_nodes * 5 + (size_t)n_out * 2;
@@ -118,7 +90,7 @@ int rtfhe_cmux_circuit_create(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const rtfh
     a.nodes = (uint32_t*)d_nodes; a.ok = (int32_t*)d_ok;
     a.var = dd; a.hi = dd + n_nodes; a.lo = dd + (size_t)n_nodes * 2; a.rot = rot ? dd + (size_t)n_nodes * 3 : nullptr;
     a.out_ref = dd + (size_t)n_nodes * 5; a.out_coef = extract ? dd + (size_t)n_nodes * 5 + n_out : nullptr;
-    a.out = extract ? nullptr : (uint32_t*)d_out; a.ext = extract ? cbuf.d : nullptr; a.fault = ctx->d_fault;
+    a.out = extract ? nullptr : (uint32_t*)d_out; a.ext = extract ? cbuf.d[0] : nullptr; a.fault = ctx->d_fault;
     a.count = (int32_t)count; a.n_nodes = n_nodes; a.n_vars = n_vars; a.n_out = n_out; a.n_sel = sel->n_sel; a.n_lut = lut->n_lut;
     a.leaf_min = leaf_span[0]; a.leaf_max = leaf_span[1]; a.enc = lut->encrypted ? 1 : 0;
     const int64_t before = ctx->launches;
@@ -127,24 +99,17 @@ int rtfhe_cmux_circuit_create(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const rtfh
     e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
     if (e != hipSuccess) return bail(fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e)));
     ctx->tlwe1_capture = &cbuf;      // (the key switch brackets nothing with timer events inside a circuit's capture)
-    int rc = launch_net(ctx, a, 0, ctx->stream);
+    // (every failure from here on still reaches hipStreamEndCapture: return codes, no early return)
+    int rc = launch_net_plain(ctx, k_cmux_net_check<LEVELED_WAVES>, count, a, ctx->stream);
     for (int32_t k = 0; k < n_levels && !rc; k++) {
         a.level = dd + (size_t)n_nodes * 4 + level_off[(size_t)k];
         a.n_level = level_off[(size_t)k + 1] - level_off[(size_t)k];
-        rc = launch_net(ctx, a, 1, ctx->stream);
+        rc = launch_leveled(ctx, net, count * (size_t)a.n_level, ctx->stream, a);      // the twin of the leveled mode in force: the graph keeps it
     }
-    if (!rc) rc = launch_net(ctx, a, 2, ctx->stream);
-    if (!rc && extract) {
-        // identity_key_switch of the count * n_out samples, as the tree's extract form does it
-        if (!ctx->d_ksmat) {
-            rc = launch_key_switch_ext(ctx, cbuf.d, (uint32_t*)d_out, samples, ctx->stream);
-        } else {
-            if (hipMemsetAsync(d_out, 0, samples * n1 * 4, ctx->stream) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_cmux_circuit_create: hipMemsetAsync");
-            BootstrapArgs k{};
-            k.out = (uint32_t*)d_out; k.count = (int32_t)samples; k.n = ctx->p.n;
-            if (!rc) rc = launch_key_switch_mm(ctx, k, cbuf.d, ctx->stream);
-        }
-    }
+    if (!rc) rc = ctx->logn == 11 ? launch_net_plain(ctx, k_cmux_net_out<11, LEVELED_WAVES>, samples, a, ctx->stream)
+                                  : launch_net_plain(ctx, k_cmux_net_out<10, LEVELED_WAVES>, samples, a, ctx->stream);
+    // identity_key_switch of the count * n_out samples, as the tree's extract form does it
+    if (!rc && extract) rc = launch_key_switch_rows(ctx, cbuf.d[0], (uint32_t*)d_out, samples, ctx->stream);
     ctx->tlwe1_capture = nullptr;
     e = hipStreamEndCapture(ctx->stream, &c->graph);
     c->launches = ctx->launches - before;

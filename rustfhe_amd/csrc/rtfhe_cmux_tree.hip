@@ -19,62 +19,71 @@ using namespace rtfhe_host;
 
 namespace {
 
-template <int LOGN, int W, bool ROUNDED>
-int launch_level_t(rtfhe_ctx* ctx, const CmuxTreeArgs& a, size_t nodes, hipStream_t s) {
-    auto k = k_cmux_tree<LOGN, 3, 6, W, ROUNDED>;
-    constexpr size_t lds = cmux_tree_lds_bytes<LOGN, W>();
-    // both twins: the eager call the capture rule asks for may have run in the other mode
-    if (int rc = allow_lds(ctx, k_cmux_tree<LOGN, 3, 6, W, !ROUNDED>, lds)) return rc;
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    hipLaunchKernelGGL(k, dim3((unsigned)((nodes + W - 1) / W)), dim3(64 * W), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
+// the three families' twins, four waves (= nodes) per workgroup at both N, on k_cmux_tree's LDS carve
+RTFHE_LEVELED_FAMILY(tree_twins, CmuxTreeArgs, k_cmux_tree, cmux_tree_lds_bytes<LOGN, LEVELED_WAVES>())
+RTFHE_LEVELED_FAMILY(demux_twins, DemuxTreeArgs, k_demux_tree, cmux_tree_lds_bytes<LOGN, LEVELED_WAVES>())
+RTFHE_LEVELED_FAMILY(rotate_twins, TrgswRotateArgs, k_trgsw_rotate, cmux_tree_lds_bytes<LOGN, LEVELED_WAVES>())
+
+// ---- the argument checks every entry over a selector set shares, after selector_set_ready and in this order ----
+// depth, and count against the 2^31 nodes (doubling: a tree's levels) or steps (a rotation's) one launch can number
+int depth_ready(rtfhe_ctx* ctx, int32_t depth, size_t count, bool doubling) {
+    if (depth < 1 || depth > CMUX_TREE_MAX_DEPTH) return fail(ctx, RTFHE_ERR_INVALID, "depth = " + std::to_string(depth) + " is outside [1, 16]");
+    if (doubling && count > ((size_t)0x7fffffff >> (depth - 1))) return fail(ctx, RTFHE_ERR_INVALID, "count * 2^(depth-1) too large");
+    if (!doubling && count > (size_t)0x7fffffff / (size_t)depth) return fail(ctx, RTFHE_ERR_INVALID, "count * depth too large");
     return 0;
 }
-
-int launch_level(rtfhe_ctx* ctx, const CmuxTreeArgs& a, size_t nodes, hipStream_t s) {
-    // four waves (= nodes) per workgroup at both N, the shape of k_external_product; the mode is read here, when the call is made
-    if (leveled_rounded(ctx)) return ctx->logn == 11 ? launch_level_t<11, 4, true>(ctx, a, nodes, s) : launch_level_t<10, 4, true>(ctx, a, nodes, s);
-    return ctx->logn == 11 ? launch_level_t<11, 4, false>(ctx, a, nodes, s) : launch_level_t<10, 4, false>(ctx, a, nodes, s);
-}
-
-bool capturing(hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-    return cs != hipStreamCaptureStatusNone;
-}
-
-// what every tree entry checks before anything is allocated or launched; host_* are the host-side index arrays (null in the _dev forms, whose
-// arrays are checked by the kernel), out the caller's result buffer
-int tree_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const rtfhe_lut* lut, int32_t depth, size_t count, bool has_sel_idx, bool has_row0,
-               const int32_t* host_sel_idx, const int32_t* host_row0, const int32_t* host_coef, const void* out, bool extract) {
-    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
-    if (!sel) return fail(ctx, RTFHE_ERR_INVALID, "null selector set (rtfhe_trgsw)");
-    if (!lut) return fail(ctx, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
-    if (!out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    if (!sel->ctx || !lut->ctx) return fail(ctx, RTFHE_ERR_STATE, "the context of the selector set or of the table has been destroyed");
-    if (sel->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the selector set belongs to another context");
-    if (lut->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the table belongs to another context");
-    if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
-        return fail(ctx, RTFHE_ERR_INVALID, "the CMUX tree runs on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR); select it with rtfhe_set_backend");
-    if (depth < 1 || depth > CMUX_TREE_MAX_DEPTH) return fail(ctx, RTFHE_ERR_INVALID, "depth = " + std::to_string(depth) + " is outside [1, 16]");
-    if (count > ((size_t)0x7fffffff >> (depth - 1))) return fail(ctx, RTFHE_ERR_INVALID, "count * 2^(depth-1) too large");
-    if (extract && !ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "key-switching key not loaded");
-    const long long rows = 1ll << depth, n_lut = lut->n_lut, n_sel = sel->n_sel;
-    if (!has_row0 && rows > n_lut)
-        return fail(ctx, RTFHE_ERR_INVALID, "a depth-" + std::to_string(depth) + " tree reads " + std::to_string(rows) + " rows, the table has " + std::to_string(n_lut));
+// the selector indices: host_sel_idx is the host-side array (null in the _dev forms, whose array the kernel checks)
+int sel_idx_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, int32_t depth, size_t count, bool has_sel_idx, const int32_t* host_sel_idx) {
+    const long long n_sel = sel->n_sel;
     if (!has_sel_idx && (long long)count * depth > n_sel)
         return fail(ctx, RTFHE_ERR_INVALID, "sel_idx NULL: lookup " + std::to_string(count - 1) + " needs selectors up to " + std::to_string((long long)count * depth - 1) +
                                             ", the set has " + std::to_string(n_sel));
-    for (size_t g = 0; g < count; g++) {
-        if (host_row0 && (host_row0[g] < 0 || (long long)host_row0[g] + rows > n_lut))
-            return fail(ctx, RTFHE_ERR_INVALID, "lookup " + std::to_string(g) + ": row0 = " + std::to_string(host_row0[g]) + " with " + std::to_string(rows) +
-                                                " rows is outside the table's [0, " + std::to_string(n_lut) + ")");
-        if (host_sel_idx)
+    if (host_sel_idx)
+        for (size_t g = 0; g < count; g++)
             for (int k = 0; k < depth; k++)
                 if ((uint32_t)host_sel_idx[g * depth + k] >= (uint32_t)sel->n_sel)
                     return fail(ctx, RTFHE_ERR_INVALID, "lookup " + std::to_string(g) + ": sel_idx[" + std::to_string(k) + "] = " + std::to_string(host_sel_idx[g * depth + k]) +
                                                         " is outside [0, " + std::to_string(n_sel) + ")");
+    return 0;
+}
+
+// host-pointer forms: sel_idx [count][depth] rides in the staging buffer d_a (null stays null: the kernels then number the selectors themselves)
+int stage_sel_idx(rtfhe_ctx* ctx, const int32_t* sel_idx, size_t count, int32_t depth, const int32_t*& d_sel_idx) {
+    d_sel_idx = nullptr;
+    if (!sel_idx) return 0;
+    if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, count * depth * 4)) return rc;
+    if (int rc = copy_in(ctx, ctx->d_a, sel_idx, count * depth * 4, 0)) return rc;
+    d_sel_idx = (const int32_t*)ctx->d_a;
+    return 0;
+}
+
+bool overlaps(const void* in, size_t in_bytes, const void* out, size_t out_bytes) {
+    const char *i0 = (const char*)in, *o0 = (const char*)out;
+    return i0 < o0 + out_bytes && o0 < i0 + in_bytes;
+}
+
+// the ping-pong buffers of a tree's or a demultiplexer's levels on stream s, `need` words each (0: a single level, no buffer, nothing to refuse)
+int level_buffers(rtfhe_ctx* ctx, hipStream_t s, bool in_capture, size_t need, const char* refusal, StreamScratch*& out) {
+    out = nullptr;
+    return need ? stream_scratch(ctx, ctx->tree, s, in_capture, ScratchShape{2, 4}, need, refusal, out) : 0;
+}
+
+// ---- CMUX tree ----
+// what every tree entry checks before anything is allocated or launched; host_* are the host-side index arrays (null in the _dev forms, whose
+// arrays are checked by the kernel), out the caller's result buffer
+int tree_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const rtfhe_lut* lut, int32_t depth, size_t count, bool has_sel_idx, bool has_row0,
+               const int32_t* host_sel_idx, const int32_t* host_row0, const int32_t* host_coef, const void* out, bool extract) {
+    if (int rc = selector_set_ready(ctx, sel, true, lut, out != nullptr, "the CMUX tree runs")) return rc;
+    if (int rc = depth_ready(ctx, depth, count, true)) return rc;
+    if (extract && !ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "key-switching key not loaded");
+    const long long rows = 1ll << depth, n_lut = lut->n_lut;
+    if (!has_row0 && rows > n_lut)
+        return fail(ctx, RTFHE_ERR_INVALID, "a depth-" + std::to_string(depth) + " tree reads " + std::to_string(rows) + " rows, the table has " + std::to_string(n_lut));
+    if (int rc = sel_idx_ready(ctx, sel, depth, count, has_sel_idx, host_sel_idx)) return rc;
+    for (size_t g = 0; g < count; g++) {
+        if (host_row0 && (host_row0[g] < 0 || (long long)host_row0[g] + rows > n_lut))
+            return fail(ctx, RTFHE_ERR_INVALID, "lookup " + std::to_string(g) + ": row0 = " + std::to_string(host_row0[g]) + " with " + std::to_string(rows) +
+                                                " rows is outside the table's [0, " + std::to_string(n_lut) + ")");
         if (host_coef && (uint32_t)host_coef[g] >= (uint32_t)ctx->p.N)
             return fail(ctx, RTFHE_ERR_INVALID, "lookup " + std::to_string(g) + ": coef = " + std::to_string(host_coef[g]) + " is outside [0, " + std::to_string(ctx->p.N) + ")");
     }
@@ -87,59 +96,30 @@ int launch_tree(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* d_sel_idx
     if (count == 0) return 0;
     const size_t N = (size_t)ctx->p.N, need = depth > 1 ? (count << (depth - 1)) * 2 * N : 0;      // words of each ping-pong buffer
     const bool cap = capturing(s);
-    auto it = ctx->tree.find(s);
-    rtfhe_ctx::Tlwe1* samples = nullptr;
-    if (cap) {
-        // nothing may be allocated inside a capture: this stream's buffers must already hold the call, and the graph then owns their addresses
-        if (need && (it == ctx->tree.end() || it->second.cap < need))
-            return fail(ctx, RTFHE_ERR_STATE, "a CMUX tree inside a stream capture needs this stream's ping-pong buffers to exist already: run one eager "
-                                              "rtfhe_cmux_tree_batch_dev of at least this count and depth on the stream before capturing");
-        if (extract) {
-            samples = tlwe1_of(ctx, s);
-            if (!samples || samples->cap < count)
-                return fail(ctx, RTFHE_ERR_STATE, "a CMUX tree with extraction inside a stream capture needs this stream's sample buffer to exist already: run one "
-                                                  "eager rtfhe_cmux_tree_extract_batch_dev of at least this count on the stream before capturing");
-            samples->captured = true;
-        }
-        if (need) it->second.captured = true;
-    } else {
-        if (need && (it == ctx->tree.end() || it->second.cap < need)) {
-            rtfhe_ctx::TreeBuf& tb = ctx->tree[s];
-            HIPCHECK(ctx, hipDeviceSynchronize());            // earlier trees of this stream may still read the old buffers
-            for (uint32_t*& d : tb.d) {
-                if (d && tb.captured) ctx->mux_retired.push_back(d);      // a graph holds its address: kept until the context goes
-                else if (d) HIPCHECK(ctx, hipFree(d));
-                d = nullptr;
-            }
-            tb.cap = 0; tb.captured = false;
-            for (uint32_t*& d : tb.d) HIPCHECK(ctx, hipMalloc((void**)&d, need * 4));
-            tb.cap = need;
-            it = ctx->tree.find(s);
-        }
-        if (extract) {
-            if (int rc = ensure_tlwe1(ctx, ctx->tlwe1[s], count)) return rc;
-            samples = &ctx->tlwe1[s];
-        }
-    }
+    StreamScratch *pp = nullptr, *samples = nullptr;
+    if (int rc = level_buffers(ctx, s, cap, need, "a CMUX tree inside a stream capture needs this stream's ping-pong buffers to exist already: run one eager "
+                                                  "rtfhe_cmux_tree_batch_dev of at least this count and depth on the stream before capturing", pp))
+        return rc;
+    if (extract)
+        if (int rc = stream_scratch(ctx, ctx->tlwe1, s, cap, tlwe1_shape(ctx), count,
+                                    "a CMUX tree with extraction inside a stream capture needs this stream's sample buffer to exist already: run one "
+                                    "eager rtfhe_cmux_tree_extract_batch_dev of at least this count on the stream before capturing", samples, ctx->tlwe1_capture))
+            return rc;
     CmuxTreeArgs a{};
     a.tw = ctx->d_tw; a.sel = sel->d_spec; a.sel_idx = d_sel_idx; a.row0 = d_row0; a.coef = extract ? d_coef : nullptr;
     a.table = lut->d_tv[0]; a.fault = ctx->d_fault;
     a.count = (int32_t)count; a.depth = depth; a.n_sel = sel->n_sel; a.n_lut = lut->n_lut; a.enc = lut->encrypted ? 1 : 0;
+    const LeveledTwins<CmuxTreeArgs> k = tree_twins(ctx);
     for (int level = 0; level < depth; level++) {
         const bool last = level == depth - 1;
         a.level = level;
-        a.src = level ? it->second.d[(level - 1) & 1] : nullptr;
-        a.dst = last ? (extract ? nullptr : (uint32_t*)d_out) : it->second.d[level & 1];
-        a.ext = last && extract ? samples->d : nullptr;
-        if (int rc = launch_level(ctx, a, count << (depth - 1 - level), s)) return rc;
+        a.src = level ? pp->d[(level - 1) & 1] : nullptr;
+        a.dst = last ? (extract ? nullptr : (uint32_t*)d_out) : pp->d[level & 1];
+        a.ext = last && extract ? samples->d[0] : nullptr;
+        if (int rc = launch_leveled(ctx, k, count << (depth - 1 - level), s, a)) return rc;
     }
-    if (!extract) return 0;
     // identity_key_switch of the count samples, as a many-LUT PBS does it (launch_pbs_many, rtfhe_batch.hip)
-    if (!ctx->d_ksmat) return launch_key_switch_ext(ctx, samples->d, (uint32_t*)d_out, count, s);
-    HIPCHECK(ctx, hipMemsetAsync(d_out, 0, count * ((size_t)ctx->p.n + 1) * 4, s));      // the K-slices add into it
-    BootstrapArgs k{};
-    k.out = (uint32_t*)d_out; k.count = (int32_t)count; k.n = ctx->p.n;
-    return launch_key_switch_mm(ctx, k, samples->d, s);
+    return extract ? launch_key_switch_rows(ctx, samples->d[0], (uint32_t*)d_out, count, s) : 0;
 }
 
 int tree_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int32_t depth, const rtfhe_lut* lut, const void* d_row0, const void* d_coef,
@@ -161,11 +141,7 @@ int tree_host(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, in
     const size_t out_bytes = count * (extract ? (size_t)ctx->p.n + 1 : (size_t)2 * ctx->p.N) * 4;
     if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
     const int32_t *d_sel_idx = nullptr, *d_row0 = nullptr, *d_coef = nullptr;
-    if (sel_idx) {
-        if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, count * depth * 4)) return rc;
-        if (int rc = copy_in(ctx, ctx->d_a, sel_idx, count * depth * 4, 0)) return rc;
-        d_sel_idx = (const int32_t*)ctx->d_a;
-    }
+    if (int rc = stage_sel_idx(ctx, sel_idx, count, depth, d_sel_idx)) return rc;
     if (row0 || coef) {
         if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, 2 * count * 4)) return rc;
         if (row0) { HIPCHECK(ctx, hipMemcpyAsync(ctx->d_b, row0, count * 4, hipMemcpyHostToDevice, ctx->stream)); d_row0 = (const int32_t*)ctx->d_b; }
@@ -179,54 +155,11 @@ int tree_host(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, in
 }
 
 // ---- CMUX demultiplexer tree ----
-template <int LOGN, int W, bool ROUNDED>
-int launch_demux_level_t(rtfhe_ctx* ctx, const DemuxTreeArgs& a, size_t nodes, hipStream_t s) {
-    auto k = k_demux_tree<LOGN, 3, 6, W, ROUNDED>;
-    constexpr size_t lds = cmux_tree_lds_bytes<LOGN, W>();
-    if (int rc = allow_lds(ctx, k_demux_tree<LOGN, 3, 6, W, !ROUNDED>, lds)) return rc;      // (prime_demux has granted both already)
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    hipLaunchKernelGGL(k, dim3((unsigned)((nodes + W - 1) / W)), dim3(64 * W), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
-}
-
-int launch_demux_level(rtfhe_ctx* ctx, const DemuxTreeArgs& a, size_t nodes, hipStream_t s) {
-    // k_cmux_tree's shape: four waves (= input nodes) per workgroup at both N; the mode is read here, when the call is made
-    if (leveled_rounded(ctx)) return ctx->logn == 11 ? launch_demux_level_t<11, 4, true>(ctx, a, nodes, s) : launch_demux_level_t<10, 4, true>(ctx, a, nodes, s);
-    return ctx->logn == 11 ? launch_demux_level_t<11, 4, false>(ctx, a, nodes, s) : launch_demux_level_t<10, 4, false>(ctx, a, nodes, s);
-}
-
-// grants k_demux_tree its dynamic LDS when a selector set is created, beside the rotation's: both twins
-template <int LOGN>
-int prime_demux_t(rtfhe_ctx* ctx) {
-    if (int rc = allow_lds(ctx, k_demux_tree<LOGN, 3, 6, 4, false>, cmux_tree_lds_bytes<LOGN, 4>())) return rc;
-    return allow_lds(ctx, k_demux_tree<LOGN, 3, 6, 4, true>, cmux_tree_lds_bytes<LOGN, 4>());
-}
-int prime_demux(rtfhe_ctx* ctx) { return ctx->logn == 11 ? prime_demux_t<11>(ctx) : prime_demux_t<10>(ctx); }
-
 // what both demultiplexer entries check before anything is allocated or launched; host_sel_idx is null in the _dev form, whose array the kernel checks
 int demux_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, int32_t depth, size_t count, bool has_sel_idx, const int32_t* host_sel_idx, const void* x, const void* out) {
-    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
-    if (!sel) return fail(ctx, RTFHE_ERR_INVALID, "null selector set (rtfhe_trgsw)");
-    if (!x || !out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    if (!sel->ctx) return fail(ctx, RTFHE_ERR_STATE, "the context of the selector set has been destroyed");
-    if (sel->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the selector set belongs to another context");
-    if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
-        return fail(ctx, RTFHE_ERR_INVALID, "the CMUX demultiplexer runs on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR); select it with rtfhe_set_backend");
-    if (depth < 1 || depth > DEMUX_TREE_MAX_DEPTH) return fail(ctx, RTFHE_ERR_INVALID, "depth = " + std::to_string(depth) + " is outside [1, 16]");
-    if (count > ((size_t)0x7fffffff >> (depth - 1))) return fail(ctx, RTFHE_ERR_INVALID, "count * 2^(depth-1) too large");
-    const long long n_sel = sel->n_sel;
-    if (!has_sel_idx && (long long)count * depth > n_sel)
-        return fail(ctx, RTFHE_ERR_INVALID, "sel_idx NULL: lookup " + std::to_string(count - 1) + " needs selectors up to " + std::to_string((long long)count * depth - 1) +
-                                            ", the set has " + std::to_string(n_sel));
-    if (host_sel_idx)
-        for (size_t g = 0; g < count; g++)
-            for (int k = 0; k < depth; k++)
-                if ((uint32_t)host_sel_idx[g * depth + k] >= (uint32_t)sel->n_sel)
-                    return fail(ctx, RTFHE_ERR_INVALID, "lookup " + std::to_string(g) + ": sel_idx[" + std::to_string(k) + "] = " + std::to_string(host_sel_idx[g * depth + k]) +
-                                                        " is outside [0, " + std::to_string(n_sel) + ")");
-    return 0;
+    if (int rc = selector_set_ready(ctx, sel, false, nullptr, x && out, "the CMUX demultiplexer runs")) return rc;
+    if (int rc = depth_ready(ctx, depth, count, true)) return rc;
+    return sel_idx_ready(ctx, sel, depth, count, has_sel_idx, host_sel_idx);
 }
 
 // The demultiplexer of `count` TRLWEs on device buffers, primary device, stream s.  d_x: [count][2][N], d_out: [count][2^depth][2][N].  Level t
@@ -235,79 +168,29 @@ int demux_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, int32_t depth, size_t co
 int launch_demux(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* d_sel_idx, int32_t depth, const void* d_x, void* d_out, size_t count, hipStream_t s) {
     if (count == 0) return 0;
     const size_t N = (size_t)ctx->p.N, need = depth > 1 ? (count << (depth - 1)) * 2 * N : 0;      // words of each ping-pong buffer
-    auto it = ctx->tree.find(s);
-    if (capturing(s)) {
-        if (need && (it == ctx->tree.end() || it->second.cap < need))
-            return fail(ctx, RTFHE_ERR_STATE, "a CMUX demultiplexer inside a stream capture needs this stream's ping-pong buffers to exist already: run one eager "
-                                              "rtfhe_demux_tree_batch_dev of at least this count and depth on the stream before capturing");
-        if (need) it->second.captured = true;
-    } else if (need && (it == ctx->tree.end() || it->second.cap < need)) {
-        rtfhe_ctx::TreeBuf& tb = ctx->tree[s];
-        HIPCHECK(ctx, hipDeviceSynchronize());            // earlier trees of this stream may still read the old buffers
-        for (uint32_t*& d : tb.d) {
-            if (d && tb.captured) ctx->mux_retired.push_back(d);      // a graph holds its address: kept until the context goes
-            else if (d) HIPCHECK(ctx, hipFree(d));
-            d = nullptr;
-        }
-        tb.cap = 0; tb.captured = false;
-        for (uint32_t*& d : tb.d) HIPCHECK(ctx, hipMalloc((void**)&d, need * 4));
-        tb.cap = need;
-        it = ctx->tree.find(s);
-    }
+    StreamScratch* pp = nullptr;
+    if (int rc = level_buffers(ctx, s, capturing(s), need, "a CMUX demultiplexer inside a stream capture needs this stream's ping-pong buffers to exist already: run one eager "
+                                                           "rtfhe_demux_tree_batch_dev of at least this count and depth on the stream before capturing", pp))
+        return rc;
     DemuxTreeArgs a{};
     a.tw = ctx->d_tw; a.sel = sel->d_spec; a.sel_idx = d_sel_idx; a.fault = ctx->d_fault;
     a.count = (int32_t)count; a.depth = depth; a.n_sel = sel->n_sel;
+    const LeveledTwins<DemuxTreeArgs> k = demux_twins(ctx);
     for (int level = 0; level < depth; level++) {
         a.level = level;
-        a.src = level ? it->second.d[(level - 1) & 1] : (const uint32_t*)d_x;
-        a.dst = level == depth - 1 ? (uint32_t*)d_out : it->second.d[level & 1];
-        if (int rc = launch_demux_level(ctx, a, count << level, s)) return rc;
+        a.src = level ? pp->d[(level - 1) & 1] : (const uint32_t*)d_x;
+        a.dst = level == depth - 1 ? (uint32_t*)d_out : pp->d[level & 1];
+        if (int rc = launch_leveled(ctx, k, count << level, s, a)) return rc;
     }
     return 0;
 }
 
 // ---- TRGSW blind rotation ----
-template <int LOGN, int W, bool ROUNDED>
-int launch_rotate_t(rtfhe_ctx* ctx, const TrgswRotateArgs& a, hipStream_t s) {
-    auto k = k_trgsw_rotate<LOGN, 3, 6, W, ROUNDED>;
-    constexpr size_t lds = cmux_tree_lds_bytes<LOGN, W>();
-    if (int rc = allow_lds(ctx, k_trgsw_rotate<LOGN, 3, 6, W, !ROUNDED>, lds)) return rc;      // (prime_rotate has granted both already)
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    hipLaunchKernelGGL(k, dim3((unsigned)(((size_t)a.count + W - 1) / W)), dim3(64 * W), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
-}
-
-template <int LOGN, int W>
-int launch_rotate_restore_t(rtfhe_ctx* ctx, const TrgswRotateArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL((k_trgsw_rotate_restore<LOGN, W>), dim3((unsigned)(((size_t)a.count + W - 1) / W)), dim3(64 * W), 0, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
-}
-
-// grants k_trgsw_rotate its dynamic LDS when a selector set is created, so that the first rotation of a context may already sit in a stream
-// capture: both twins, since the mode may be switched between the set's creation and the capture
-template <int LOGN>
-int prime_rotate_t(rtfhe_ctx* ctx) {
-    if (int rc = allow_lds(ctx, k_trgsw_rotate<LOGN, 3, 6, 4, false>, cmux_tree_lds_bytes<LOGN, 4>())) return rc;
-    return allow_lds(ctx, k_trgsw_rotate<LOGN, 3, 6, 4, true>, cmux_tree_lds_bytes<LOGN, 4>());
-}
-int prime_rotate(rtfhe_ctx* ctx) { return ctx->logn == 11 ? prime_rotate_t<11>(ctx) : prime_rotate_t<10>(ctx); }
-
 // what every rotation entry checks before anything is allocated or launched; host_sel_idx is null in the _dev forms, whose array the kernel checks
 int rotate_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, int32_t depth, const int32_t* rot, size_t count, bool has_sel_idx, const int32_t* host_sel_idx,
                  const void* in, const void* out, bool extract) {
-    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
-    if (!sel) return fail(ctx, RTFHE_ERR_INVALID, "null selector set (rtfhe_trgsw)");
-    if (!in || !out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    if (!sel->ctx) return fail(ctx, RTFHE_ERR_STATE, "the context of the selector set has been destroyed");
-    if (sel->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the selector set belongs to another context");
-    if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
-        return fail(ctx, RTFHE_ERR_INVALID, "the TRGSW rotation runs on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR); select it with rtfhe_set_backend");
-    if (depth < 1 || depth > TRGSW_ROTATE_MAX_DEPTH) return fail(ctx, RTFHE_ERR_INVALID, "depth = " + std::to_string(depth) + " is outside [1, 16]");
-    if (count > (size_t)0x7fffffff / (size_t)depth) return fail(ctx, RTFHE_ERR_INVALID, "count * depth too large");
+    if (int rc = selector_set_ready(ctx, sel, false, nullptr, in && out, "the TRGSW rotation runs")) return rc;
+    if (int rc = depth_ready(ctx, depth, count, false)) return rc;
     const int N = ctx->p.N;
     if (rot) {
         for (int k = 0; k < depth; k++)
@@ -318,17 +201,7 @@ int rotate_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, int32_t depth, const in
                                             " = 1; depth = " + std::to_string(depth) + " is above log2 N + 1 = " + std::to_string(ctx->logn + 1));
     }
     if (extract && !ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "key-switching key not loaded");
-    const long long n_sel = sel->n_sel;
-    if (!has_sel_idx && (long long)count * depth > n_sel)
-        return fail(ctx, RTFHE_ERR_INVALID, "sel_idx NULL: lookup " + std::to_string(count - 1) + " needs selectors up to " + std::to_string((long long)count * depth - 1) +
-                                            ", the set has " + std::to_string(n_sel));
-    if (host_sel_idx)
-        for (size_t g = 0; g < count; g++)
-            for (int k = 0; k < depth; k++)
-                if ((uint32_t)host_sel_idx[g * depth + k] >= (uint32_t)sel->n_sel)
-                    return fail(ctx, RTFHE_ERR_INVALID, "lookup " + std::to_string(g) + ": sel_idx[" + std::to_string(k) + "] = " + std::to_string(host_sel_idx[g * depth + k]) +
-                                                        " is outside [0, " + std::to_string(n_sel) + ")");
-    return 0;
+    return sel_idx_ready(ctx, sel, depth, count, has_sel_idx, host_sel_idx);
 }
 
 // The rotation of `count` TRLWEs on device buffers, primary device, stream s.  d_out: [count][2][N] (may be d_in), or in the extract form [count][n+1].
@@ -336,40 +209,26 @@ int rotate_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, int32_t depth, const in
 int launch_rotate(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* d_sel_idx, int32_t depth, const int32_t* rot, const void* d_in, void* d_out, size_t count,
                   bool extract, hipStream_t s) {
     if (count == 0) return 0;
-    rtfhe_ctx::Tlwe1* samples = nullptr;
-    if (extract) {
-        if (capturing(s)) {
-            samples = tlwe1_of(ctx, s);
-            if (!samples || samples->cap < count)
-                return fail(ctx, RTFHE_ERR_STATE, "a TRGSW rotation with extraction inside a stream capture needs this stream's sample buffer to exist already: run one "
-                                                  "eager rtfhe_trgsw_rotate_extract_batch_dev of at least this count on the stream before capturing");
-            samples->captured = true;
-        } else {
-            if (int rc = ensure_tlwe1(ctx, ctx->tlwe1[s], count)) return rc;
-            samples = &ctx->tlwe1[s];
-        }
-    }
+    StreamScratch* samples = nullptr;
+    if (extract)
+        if (int rc = stream_scratch(ctx, ctx->tlwe1, s, capturing(s), tlwe1_shape(ctx), count,
+                                    "a TRGSW rotation with extraction inside a stream capture needs this stream's sample buffer to exist already: run one "
+                                    "eager rtfhe_trgsw_rotate_extract_batch_dev of at least this count on the stream before capturing", samples, ctx->tlwe1_capture))
+            return rc;
     TrgswRotateArgs a{};
     a.tw = ctx->d_tw; a.sel = sel->d_spec; a.sel_idx = d_sel_idx; a.in = (const uint32_t*)d_in; a.fault = ctx->d_fault;
     a.out = extract ? nullptr : (uint32_t*)d_out;
-    a.ext = extract ? samples->d : nullptr;
+    a.ext = extract ? samples->d[0] : nullptr;
     a.ks_out = extract ? (uint32_t*)d_out : nullptr;
     a.count = (int32_t)count; a.depth = depth; a.n_sel = sel->n_sel; a.n = ctx->p.n;
     for (int k = 0; k < depth; k++) a.rot[k] = rot ? rot[k] : 2 * ctx->p.N - (1 << k);      // NULL: X^{-2^k}
-    if (int rc = leveled_rounded(ctx) ? (ctx->logn == 11 ? launch_rotate_t<11, 4, true>(ctx, a, s) : launch_rotate_t<10, 4, true>(ctx, a, s))
-                                      : (ctx->logn == 11 ? launch_rotate_t<11, 4, false>(ctx, a, s) : launch_rotate_t<10, 4, false>(ctx, a, s)))
-        return rc;
+    if (int rc = launch_leveled(ctx, rotate_twins(ctx), count, s, a)) return rc;
     if (!extract) return 0;
     // identity_key_switch of the count samples, as the tree's extract form does it; then the rows of skipped lookups as they were
-    if (!ctx->d_ksmat) {
-        if (int rc = launch_key_switch_ext(ctx, samples->d, (uint32_t*)d_out, count, s)) return rc;
-    } else {
-        HIPCHECK(ctx, hipMemsetAsync(d_out, 0, count * ((size_t)ctx->p.n + 1) * 4, s));      // the K-slices add into it
-        BootstrapArgs k{};
-        k.out = (uint32_t*)d_out; k.count = (int32_t)count; k.n = ctx->p.n;
-        if (int rc = launch_key_switch_mm(ctx, k, samples->d, s)) return rc;
-    }
-    return ctx->logn == 11 ? launch_rotate_restore_t<11, 4>(ctx, a, s) : launch_rotate_restore_t<10, 4>(ctx, a, s);
+    if (int rc = launch_key_switch_rows(ctx, samples->d[0], (uint32_t*)d_out, count, s)) return rc;
+    const dim3 grid((unsigned)((count + LEVELED_WAVES - 1) / LEVELED_WAVES)), block(64 * LEVELED_WAVES);
+    return ctx->logn == 11 ? launch_kernel(ctx, k_trgsw_rotate_restore<11, LEVELED_WAVES>, grid, block, 0, s, a)
+                           : launch_kernel(ctx, k_trgsw_rotate_restore<10, LEVELED_WAVES>, grid, block, 0, s, a);
 }
 
 int rotate_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int32_t depth, const int32_t* rot, const void* d_trlwe, void* d_out, size_t count,
@@ -378,14 +237,9 @@ int rotate_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, in
     if (int rc = use(ctx)) return rc;
     if (!gpu_accessible(ctx, d_out) || !gpu_accessible(ctx, d_trlwe) || (d_sel_idx && !gpu_accessible(ctx, d_sel_idx)))
         return fail(ctx, RTFHE_ERR_INVALID, std::string(name) + " needs device pointers (got memory the GPU cannot address)");
-    if (d_out != d_trlwe) {
-        const char *i0 = (const char*)d_trlwe, *o0 = (const char*)d_out;
-        const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = extract ? count * ((size_t)ctx->p.n + 1) * 4 : in_bytes;
-        if (i0 < o0 + out_bytes && o0 < i0 + in_bytes)
-            return fail(ctx, RTFHE_ERR_INVALID, std::string(name) + ": d_out overlaps d_trlwe (it may only be exactly d_trlwe, in the form without extraction)");
-    } else if (extract) {
+    const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = extract ? count * ((size_t)ctx->p.n + 1) * 4 : in_bytes;
+    if (d_out != d_trlwe ? overlaps(d_trlwe, in_bytes, d_out, out_bytes) : extract)
         return fail(ctx, RTFHE_ERR_INVALID, std::string(name) + ": d_out overlaps d_trlwe (it may only be exactly d_trlwe, in the form without extraction)");
-    }
     return launch_rotate(ctx, sel, (const int32_t*)d_sel_idx, depth, rot, d_trlwe, d_out, count, extract, (hipStream_t)stream);
 }
 
@@ -399,11 +253,7 @@ int rotate_host(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, 
     if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, in_bytes)) return rc;
     if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
     const int32_t* d_sel_idx = nullptr;
-    if (sel_idx) {
-        if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, count * depth * 4)) return rc;
-        if (int rc = copy_in(ctx, ctx->d_a, sel_idx, count * depth * 4, 0)) return rc;
-        d_sel_idx = (const int32_t*)ctx->d_a;
-    }
+    if (int rc = stage_sel_idx(ctx, sel_idx, count, depth, d_sel_idx)) return rc;
     if (int rc = copy_in(ctx, ctx->d_b, trlwe, in_bytes, 1)) return rc;
     if (int rc = launch_rotate(ctx, sel, d_sel_idx, depth, rot, ctx->d_b, ctx->d_c, count, extract, ctx->stream)) return rc;
     return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
@@ -412,6 +262,20 @@ int rotate_host(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, 
 }  // namespace
 
 namespace rtfhe_host {
+
+int selector_set_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, bool with_table, const rtfhe_lut* lut, bool args_ok, const char* who) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!sel) return fail(ctx, RTFHE_ERR_INVALID, "null selector set (rtfhe_trgsw)");
+    if (with_table && !lut) return fail(ctx, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
+    if (!args_ok) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (!sel->ctx || (with_table && !lut->ctx))
+        return fail(ctx, RTFHE_ERR_STATE, with_table ? "the context of the selector set or of the table has been destroyed" : "the context of the selector set has been destroyed");
+    if (sel->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the selector set belongs to another context");
+    if (with_table && lut->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the table belongs to another context");
+    if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
+        return fail(ctx, RTFHE_ERR_INVALID, std::string(who) + " on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR); select it with rtfhe_set_backend");
+    return 0;
+}
 
 void trgsw_release(rtfhe_trgsw* t) {
     (void)hipSetDevice(t->ctx->device);
@@ -430,8 +294,9 @@ int rtfhe_trgsw_create(rtfhe_ctx* ctx, const uint32_t* trgsw, int32_t n_sel, rtf
     if (!trgsw || !out || n_sel < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_create: null argument or n_sel < 1");
     *out = nullptr;
     if (int rc = use(ctx)) return rc;
-    if (int rc = prime_rotate(ctx)) return rc;
-    if (int rc = prime_demux(ctx)) return rc;
+    // the rotation and the demultiplexer are granted their dynamic LDS now, so that the first of a context may already sit in a stream capture
+    if (int rc = prime_leveled(ctx, rotate_twins(ctx))) return rc;
+    if (int rc = prime_leveled(ctx, demux_twins(ctx))) return rc;
     const size_t polys = (size_t)n_sel * 2 * 2 * ctx->p.l, words = polys * ctx->p.N;
     if (polys > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_create: n_sel too large");
     rtfhe_trgsw* t = new rtfhe_trgsw();
@@ -493,11 +358,7 @@ int rtfhe_demux_tree_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t
     if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, in_bytes)) return rc;
     if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
     const int32_t* d_sel_idx = nullptr;
-    if (sel_idx) {
-        if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, count * depth * 4)) return rc;
-        if (int rc = copy_in(ctx, ctx->d_a, sel_idx, count * depth * 4, 0)) return rc;
-        d_sel_idx = (const int32_t*)ctx->d_a;
-    }
+    if (int rc = stage_sel_idx(ctx, sel_idx, count, depth, d_sel_idx)) return rc;
     if (int rc = copy_in(ctx, ctx->d_b, x, in_bytes, 1)) return rc;
     if (int rc = launch_demux(ctx, sel, d_sel_idx, depth, ctx->d_b, ctx->d_c, count, ctx->stream)) return rc;
     return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
@@ -509,9 +370,8 @@ int rtfhe_demux_tree_batch_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const voi
     if (int rc = use(ctx)) return rc;
     if (!gpu_accessible(ctx, d_out) || !gpu_accessible(ctx, d_x) || (d_sel_idx && !gpu_accessible(ctx, d_sel_idx)))
         return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_demux_tree_batch_dev needs device pointers (got memory the GPU cannot address)");
-    const char *i0 = (const char*)d_x, *o0 = (const char*)d_out;
     const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = in_bytes << depth;
-    if (i0 < o0 + out_bytes && o0 < i0 + in_bytes)      // the last level stores leaves while other waves still read their nodes (depth 1: x itself)
+    if (overlaps(d_x, in_bytes, d_out, out_bytes))      // the last level stores leaves while other waves still read their nodes (depth 1: x itself)
         return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_demux_tree_batch_dev: d_out overlaps d_x");
     return launch_demux(ctx, sel, (const int32_t*)d_sel_idx, depth, d_x, d_out, count, (hipStream_t)stream);
 }
@@ -532,10 +392,7 @@ int rtfhe_lut_accumulate_dev(rtfhe_lut* lut, const void* d_trlwe, int32_t first,
     if (n == 0) return 0;
     const size_t row = 2 * (size_t)ctx->p.N;
     TrlweAccumulateArgs a{lut->d_tv[0] + (size_t)first * row, (const uint32_t*)d_trlwe, (size_t)n * row, (int32_t)count};
-    hipLaunchKernelGGL(k_trlwe_accumulate, dim3((unsigned)((a.words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
+    return launch_kernel(ctx, k_trlwe_accumulate, dim3((unsigned)((a.words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
 }
 
 int rtfhe_lut_read_dev(const rtfhe_lut* lut, void* d_out, int32_t first, int32_t n, void* stream) {

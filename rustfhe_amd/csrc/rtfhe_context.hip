@@ -361,14 +361,12 @@ void rtfhe_ctx_destroy(rtfhe_ctx* ctx) {
     if (ctx->d_xtw) (void)hipFree(ctx->d_xtw);
     if (ctx->d_ksk) (void)hipFree(ctx->d_ksk);
     if (ctx->d_ksmat) (void)hipFree(ctx->d_ksmat);
-    for (auto& kv : ctx->tlwe1) if (kv.second.d) (void)hipFree(kv.second.d);
     if (ctx->d_a) (void)hipFree(ctx->d_a);
     if (ctx->d_b) (void)hipFree(ctx->d_b);
     if (ctx->d_c) (void)hipFree(ctx->d_c);
     for (void* h : ctx->h_pin) if (h) (void)hipHostFree(h);
-    for (auto& kv : ctx->mux) for (void* m : kv.second.m) if (m) (void)hipFree(m);
-    for (auto& kv : ctx->tree) for (uint32_t* d : kv.second.d) if (d) (void)hipFree(d);
-    for (auto& kv : ctx->pack) if (kv.second.d) (void)hipFree(kv.second.d);
+    for (ScratchMap* map : {&ctx->tlwe1, &ctx->mux, &ctx->tree, &ctx->pack})      // every stream's scratch, then what graphs held
+        for (auto& kv : *map) for (uint32_t* d : kv.second.d) if (d) (void)hipFree(d);
     for (void* m : ctx->mux_retired) (void)hipFree(m);
     for (hipEvent_t e : ctx->ks_events) (void)hipEventDestroy(e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);

@@ -52,6 +52,13 @@ struct HostTw {
     std::vector<rtfhe::cplx> q4_table() const;                 // Q4Tw: the parity sub-networks of k_bootstrap_wg / _pair4 (N = 1024)
 };
 
+// Device scratch between the launches of one call, ONE buffer (or pair) per stream the call was ever launched on: launches of one stream are
+// ordered, launches on different streams of one context may overlap and must not share it.  cap: what each buffer holds, in its owner's units.
+// captured: a call inside a caller's stream capture baked d into a graph -- never freed while the context lives (a larger eager call retires it
+// to rtfhe_ctx::mux_retired and gets a new one).  rtfhe_host::stream_scratch is the one place that applies these rules.
+struct StreamScratch { uint32_t* d[2] = {nullptr, nullptr}; size_t cap = 0; bool captured = false; };
+typedef std::unordered_map<hipStream_t, StreamScratch> ScratchMap;
+
 struct rtfhe_circuit;
 struct rtfhe_lut;
 struct rtfhe_trgsw;
@@ -90,13 +97,9 @@ struct rtfhe_ctx {
     int ksw = 0;
     uint4* d_ksmat = nullptr;         // the key-switching key as signed byte limbs in i8-MFMA operand order (rtfhe_kernels_ksmm.hpp)
     size_t ksk_bytes = 0, ksmat_bytes = 0;
-    // lvl1 samples between the two launches of the split path: ONE buffer per stream a batch was ever launched on (launches of one stream are
-    // ordered, launches on different streams of one context may overlap and must not share it), plus a circuit's own during its capture
-    // cap in gates (samples); captured: a many-LUT PBS inside a caller's stream capture baked d into a graph -- never freed while the context
-    // lives (a larger eager batch retires it to mux_retired and gets a new one)
-    struct Tlwe1 { uint32_t* d = nullptr; size_t cap = 0; bool captured = false; };
-    std::unordered_map<hipStream_t, Tlwe1> tlwe1;
-    Tlwe1* tlwe1_capture = nullptr;   // set by rtfhe_circuit_create around its capture: the circuit's buffer
+    // lvl1 samples between the two launches of the split path (d[0]; cap in samples), plus a circuit's own during its capture
+    ScratchMap tlwe1;
+    StreamScratch* tlwe1_capture = nullptr;   // set by rtfhe_circuit_create around its capture: the circuit's buffer
     bool foreign_capture = false;     // set by launch_bootstrap for the duration of a call made inside a stream capture that is NOT
                                       // rtfhe_circuit_create's: such a batch stays on the fused kernel (see split_ok)
     int ks_mm_min = 1;                // batches of at least this many gates take the split path (0 = never: fused kernel); RTFHE_KS_MM_MIN
@@ -128,21 +131,15 @@ struct rtfhe_ctx {
     std::vector<rtfhe_ctx*> peers;
     std::vector<rtfhe_circuit*> circuits;   // live HIP-graph circuits of this context: orphaned (not freed) by rtfhe_ctx_destroy
     std::vector<rtfhe_lut*> luts;           // live PBS tables of this context (primary only): their device copies go with it, the handles stay
-    // device intermediates (i1, i0) of a MUX batch: one pair per stream a MUX batch was ever launched on, as the lvl1 samples above (two MUX
-    // batches on different streams of one context may overlap).  A pair whose addresses went into a caller's capture is never freed or replaced
-    // while the context lives (`captured`): a later, larger eager batch on that stream gets a new pair and the old one moves to mux_retired.
-    struct MuxBuf { void* m[2] = {nullptr, nullptr}; size_t cap = 0; bool captured = false; };
-    std::unordered_map<hipStream_t, MuxBuf> mux;
-    std::vector<void*> mux_retired;        // (and sample buffers of the split path that a caller's capture holds: Tlwe1::captured)
-    // the two ping-pong buffers of a CMUX tree's levels (rtfhe_cmux_tree.hip), one pair per stream a tree was ever launched on, under the same
-    // rules as the MUX pairs above; cap in words of EACH buffer; not counted by rtfhe_ctx_memory_bytes
-    struct TreeBuf { uint32_t* d[2] = {nullptr, nullptr}; size_t cap = 0; bool captured = false; };
-    std::unordered_map<hipStream_t, TreeBuf> tree;
+    ScratchMap mux;                        // device intermediates (i1, i0) of a MUX batch: a pair, cap in bytes of EACH
+    std::vector<void*> mux_retired;        // scratch of any kind below or above that a caller's graph holds and a larger eager call replaced: freed with the context
+    // the two ping-pong buffers of a CMUX tree's or demultiplexer's levels (rtfhe_cmux_tree.hip): a pair, cap in words of EACH; not counted by
+    // rtfhe_ctx_memory_bytes
+    ScratchMap tree;
     std::vector<rtfhe_trgsw*> trgsws;      // live selector sets of this context: their spectra go with it, the handles stay
-    // the key-switched samples S[count * P][2N] between the two launches of a packing key switch (rtfhe_pack.hip), one buffer per stream a pack
-    // was ever launched on, under the rules of the tree's buffers above; cap in samples; not counted by rtfhe_ctx_memory_bytes
-    struct PackBuf { uint32_t* d = nullptr; size_t cap = 0; bool captured = false; };
-    std::unordered_map<hipStream_t, PackBuf> pack;
+    // the key-switched samples S[count * P][2N] between the two launches of a packing key switch (rtfhe_pack.hip): d[0], cap in samples; not
+    // counted by rtfhe_ctx_memory_bytes
+    ScratchMap pack;
     std::vector<rtfhe_packing_key*> pack_keys;      // live packing keys of this context: their matrices go with it, the handles stay
     int num_cus = 256;
     int force_waves = 0;   // RTFHE_FORCE_WAVES=1|2|4|8: one kernel shape for every batch (the parity tests' second opinions)
@@ -250,6 +247,9 @@ void circuit_release(rtfhe_circuit* c);                                   // rtf
 void lut_release(rtfhe_lut* lut);                                         // frees a table's device copies (rtfhe_context.hip)
 void trgsw_release(rtfhe_trgsw* t);                                       // frees a selector set's spectra (rtfhe_cmux_tree.hip)
 void packing_key_release(rtfhe_packing_key* k);                           // frees a packing key's matrix (rtfhe_pack.hip)
+// what every entry point over a selector set checks first (rtfhe_cmux_tree.hip): the handles (lut only with_table), the caller's other pointers
+// (args_ok), live and own contexts, the mirror backend -- who: "the CMUX tree runs", for the message
+int selector_set_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, bool with_table, const rtfhe_lut* lut, bool args_ok, const char* who);
 
 // ---- twiddles (rtfhe_twiddles.hip) ----
 bool unit_twiddles_ok(const HostTw& tw);
@@ -285,12 +285,35 @@ int launch_ksmat_build(rtfhe_ctx* ctx, const uint32_t* d_raw, int colgroups, hip
 int launch_key_switch_mm(rtfhe_ctx* ctx, const BootstrapArgs& a, const uint32_t* samples, hipStream_t s);
 // the same key switch one wave per sample from the gathered key rows (k_key_switch_ext): contexts without the matrix form (RTFHE_KS_MM_MIN=0)
 int launch_key_switch_ext(rtfhe_ctx* ctx, uint32_t* samples, uint32_t* d_out, size_t count, hipStream_t s);
+// the extract tail of every entry point that leaves lvl1 samples behind (many-LUT PBS, tree, rotation, CMUX netlist): the identity key switch of
+// `rows` samples into d_out [rows][n+1] -- without the matrix key _ext, else d_out zeroed (the K-slices add into it) and _mm
+// (zero_out = false: d_out is zero already -- a LUT circuit's key-switched buffer, which k_lut_scatter clears)
+int launch_key_switch_rows(rtfhe_ctx* ctx, uint32_t* samples, uint32_t* d_out, size_t rows, hipStream_t s, bool zero_out = true);
 
 // ---- batches (rtfhe_batch.hip) ----
 int launch_bootstrap(rtfhe_ctx* ctx, int op, int mode, int steps, const void* d_in0, const void* d_in1, void* d_out,
                      size_t count, hipStream_t s, const int32_t* d_ops = nullptr, const int32_t* d_idx0 = nullptr,
                      const int32_t* d_idx1 = nullptr, const int32_t* d_idx_out = nullptr, int32_t num_wires = 0, const LutRef& lut = LutRef{});
-int ensure_tlwe1(rtfhe_ctx* ctx, rtfhe_ctx::Tlwe1& b, size_t gates);
+// ---- per-stream scratch (rtfhe_batch.hip) ----
+inline bool capturing(hipStream_t s) {      // is a stream capture under way on s?  (a failed query counts as one: nothing is allocated then)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
+    return cs != hipStreamCaptureStatusNone;
+}
+// how a kind of scratch is allocated: `bufs` buffers (1 or 2) of unit_bytes per unit of cap each, at least min_cap units, whole tiles of `tile`
+struct ScratchShape { int bufs; size_t unit_bytes, min_cap = 0, tile = 1; };
+// the lvl1 sample buffer: at least 1024 samples, whole tiles of 16 (rtfhe::ext_slot), N + 1 words each
+inline ScratchShape tlwe1_shape(const rtfhe_ctx* ctx) { return {1, ((size_t)ctx->p.N + 1) * 4, 1024, 16}; }
+// The rule of every per-stream scratch buffer, applied to the one of stream s in `map` (own: a buffer that lives in no map and takes precedence
+// -- a circuit's, tlwe1_capture).  Outside a capture (in_capture = capturing(s), asked once per call) a buffer that holds fewer than `need` units
+// is replaced (grow_scratch); inside one nothing may be allocated: the buffer must hold the call already, else RTFHE_ERR_STATE with the caller's
+// `refusal`, and the graph then owns its address (captured).  out: the buffer.
+int stream_scratch(rtfhe_ctx* ctx, ScratchMap& map, hipStream_t s, bool in_capture, const ScratchShape& shape, size_t need, const char* refusal,
+                   StreamScratch*& out, StreamScratch* own = nullptr);
+// ... its eager half, also for a buffer that lives in no map: no-op when b holds `need` units, else device-sync (earlier launches may still read
+// it), b cleared, the old buffers freed -- or retired to mux_retired when a graph holds them --, new ones allocated
+int grow_scratch(rtfhe_ctx* ctx, StreamScratch& b, const ScratchShape& shape, size_t need);
+inline int ensure_tlwe1(rtfhe_ctx* ctx, StreamScratch& b, size_t gates) { return grow_scratch(ctx, b, tlwe1_shape(ctx), gates); }
 int run_host_bootstrap_one(rtfhe_ctx* ctx, int op, int mode, int steps, const uint32_t* in0, const uint32_t* in1, uint32_t* out, size_t count, size_t out_words);
 int mux_host_one(rtfhe_ctx* ctx, const uint32_t* c, const uint32_t* in0, const uint32_t* in1, uint32_t* out, size_t count);
 // a programmable bootstrap of host buffers on one device (lut_idx already checked; null = table 0)
@@ -329,7 +352,7 @@ inline BootstrapArgs batch_segment(const rtfhe_ctx* ctx, BootstrapArgs a, size_t
 // (the bootstrap kernel in MODE_EXTRACT, launched by `blind_rotate`), then the key switch of the whole batch as one exact i8
 // contraction on the matrix pipe (k_key_switch_mm) -- two launches back to back on the caller's stream, the lvl1 samples in between
 // stay in HBM (4 MB per 1024 gates at N = 1024).
-inline rtfhe_ctx::Tlwe1* tlwe1_of(rtfhe_ctx* ctx, hipStream_t s) {
+inline StreamScratch* tlwe1_of(rtfhe_ctx* ctx, hipStream_t s) {
     if (ctx->tlwe1_capture) return ctx->tlwe1_capture;
     auto it = ctx->tlwe1.find(s);
     return it == ctx->tlwe1.end() ? nullptr : &it->second;
@@ -340,14 +363,14 @@ inline bool split_ok(rtfhe_ctx* ctx, const BootstrapArgs& a, hipStream_t s) {
     // on the stream frees and reallocates that buffer (ensure_tlwe1) and a replay then writes freed memory; a replay on another stream
     // would share the scratch with eager work on this one.  Only rtfhe_circuit_create's captures (which own their sample buffer) split.
     if (ctx->foreign_capture) return false;
-    const rtfhe_ctx::Tlwe1* b = tlwe1_of(ctx, s);
+    const StreamScratch* b = tlwe1_of(ctx, s);
     return b && (size_t)a.count <= b->cap;      // (the sample buffer is sized by ensure_tlwe1 before any launch or capture)
 }
 // blind_rotate(ctx, a', s) launches the bootstrap kernel(s) of the whole batch with a'.mode = MODE_EXTRACT: every gate's lvl1 sample goes to
 // a'.ext in the key switch's operand order (rtfhe::ext_slot; segments of a batch advance ext_first, not the pointer) and its output row is zeroed for the key switch's atomics
 template <typename F>
 int launch_split(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, F blind_rotate) {
-    uint32_t* samples = tlwe1_of(ctx, s)->d;
+    uint32_t* samples = tlwe1_of(ctx, s)->d[0];
     a.mode = rtfhe::MODE_EXTRACT; a.ext = samples;
     if (int rc = blind_rotate(ctx, a, s)) return rc;
     return launch_key_switch_mm(ctx, a, samples, s);
@@ -363,6 +386,33 @@ int launch_kernel(rtfhe_ctx* ctx, K k, dim3 grid, dim3 block, size_t lds, hipStr
     HIPCHECK(ctx, hipGetLastError());
     if (counted) ctx->launches++;
     return 0;
+}
+
+// ---- the leveled kernels (tree, demultiplexer, rotation, CMUX netlist, the mirror's external product) ----
+// A kernel and its ROUNDED twin (rtfhe_set_leveled_decomposition) with their dynamic LDS; a wave per node, LEVELED_WAVES waves per workgroup at both N.
+constexpr int LEVELED_WAVES = 4;
+template <typename A>
+struct LeveledTwins { void (*reference)(A); void (*rounded)(A); size_t lds; };
+// defines name(ctx): the twins of family `kernel` at the context's ring, the template arguments stated once; the last argument is the LDS at LOGN
+#define RTFHE_LEVELED_FAMILY(name, Args, kernel, ...)                                                                                                    \
+    template <int LOGN>                                                                                                                                 \
+    rtfhe_host::LeveledTwins<Args> name##_t() {                                                                                                          \
+        return {kernel<LOGN, 3, 6, rtfhe_host::LEVELED_WAVES, false>, kernel<LOGN, 3, 6, rtfhe_host::LEVELED_WAVES, true>, __VA_ARGS__};                  \
+    }                                                                                                                                                   \
+    rtfhe_host::LeveledTwins<Args> name(const rtfhe_ctx* ctx) { return ctx->logn == 11 ? name##_t<11>() : name##_t<10>(); }
+// grants both twins their LDS (where the first launch of a context may already sit in a stream capture)
+template <typename A>
+int prime_leveled(rtfhe_ctx* ctx, const LeveledTwins<A>& k) {
+    if (int rc = allow_lds(ctx, k.reference, k.lds)) return rc;
+    return allow_lds(ctx, k.rounded, k.lds);
+}
+// One launch over `waves` nodes: the twin of the leveled mode in force now, when the call is made.  The other twin is granted its LDS too: the
+// eager call a capture rule asks for may have run in the other mode.
+template <typename A>
+int launch_leveled(rtfhe_ctx* ctx, const LeveledTwins<A>& k, size_t waves, hipStream_t s, const A& a, bool counted = true) {
+    const bool r = leveled_rounded(ctx);
+    if (int rc = allow_lds(ctx, r ? k.reference : k.rounded, k.lds)) return rc;
+    return launch_kernel(ctx, r ? k.rounded : k.reference, dim3((unsigned)((waves + LEVELED_WAVES - 1) / LEVELED_WAVES)), dim3(64 * LEVELED_WAVES), k.lds, s, a, counted);
 }
 
 // The kernels of one shape, all with the same block size, LDS and key layout.  The exact backends have the gate kernel alone; a family of the FP64

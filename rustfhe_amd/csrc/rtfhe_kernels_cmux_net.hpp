@@ -88,10 +88,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_cmux_net(const CmuxNetArgs a)
     static_assert(cmux_tree_lds_bytes<LOGN, WAVES>() <= (size_t)160 * 1024, "k_cmux_net: the LDS carve of this (N, waves) shape passes the 160 KiB of a CU");
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    cplx* tw = reinterpret_cast<cplx*>(smem);
-    TwStage<LOGN>::stage(tw, a.tw, tid, 64 * WAVES);
-    __syncthreads();
-    // from here on waves never synchronise with each other
+    cplx* tw = leveled_stage_twiddles<LOGN, WAVES>(smem, a.tw, tid);
 
     const long long q = (long long)blockIdx.x * WAVES + wave;      // replica g, node j of the level
     if (q >= (long long)a.count * a.n_level) return;
@@ -102,9 +99,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_cmux_net(const CmuxNetArgs a)
     const int r = a.rot ? a.rot[i] : 0;
     const long long r0 = a.row0 ? a.row0[g] : 0;
 
-    unsigned char* wbase = smem + (size_t)TwStage<LOGN>::LDS_CPLX * sizeof(cplx) + (size_t)wave * bootstrap_wave_lds_bytes<LOGN>(0, DUAL);
-    double* xbuf = reinterpret_cast<double*>(wbase);
-    uint32_t* accbuf = reinterpret_cast<uint32_t*>(wbase + (size_t)G::XSLOTS * sizeof(double) * (DUAL ? 2 : 1));
+    const WaveLds w = leveled_wave_lds<LOGN, WAVES>(smem, wave);
+    double* xbuf = w.xbuf;
+    uint32_t* accbuf = w.accbuf;
 
     uint32_t* slots = a.nodes + (size_t)g * a.n_nodes * 2 * N;
     const size_t roww = a.enc ? (size_t)2 * N : (size_t)N;

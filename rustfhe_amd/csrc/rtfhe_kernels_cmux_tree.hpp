@@ -35,6 +35,25 @@ struct CmuxTreeArgs {
 template <int LOGN, int WAVES>
 __host__ __device__ constexpr size_t cmux_tree_lds_bytes() { return bootstrap_lds_bytes<LOGN>(WAVES, 0, bootstrap_dual_xbuf(LOGN, WAVES)); }
 
+// ---- the frame the four leveled kernels (k_cmux_tree, k_demux_tree, k_trgsw_rotate, k_cmux_net) open with ----
+// In two halves, because the kernels leave early in between.  First the twiddles of the workgroup into the head of
+// its LDS and the one barrier; from there on waves never synchronise with each other.
+template <int LOGN, int WAVES>
+__device__ __forceinline__ cplx* leveled_stage_twiddles(unsigned char* smem, const cplx* tw_global, int tid) {
+    cplx* tw = reinterpret_cast<cplx*>(smem);
+    TwStage<LOGN>::stage(tw, tw_global, tid, 64 * WAVES);
+    __syncthreads();
+    return tw;
+}
+// ... then the wave's own carve behind them: the exchange buffer(s) of the transforms, then the accumulator (b then a)
+struct WaveLds { double* xbuf; uint32_t* accbuf; };
+template <int LOGN, int WAVES>
+__device__ __forceinline__ WaveLds leveled_wave_lds(unsigned char* smem, int wave) {
+    constexpr bool DUAL = bootstrap_dual_xbuf(LOGN, WAVES);
+    unsigned char* wbase = smem + (size_t)TwStage<LOGN>::LDS_CPLX * sizeof(cplx) + (size_t)wave * bootstrap_wave_lds_bytes<LOGN>(0, DUAL);
+    return {reinterpret_cast<double*>(wbase), reinterpret_cast<uint32_t*>(wbase + (size_t)Geo<LOGN>::XSLOTS * sizeof(double) * (DUAL ? 2 : 1))};
+}
+
 // acc <- cmux(S, r1, r0) on the wave-private accumulator: the difference into LDS, the external product in place, r0 added back from where it
 // came (a second read of 2N words that the L2 still holds costs less than 2N / 64 registers live across the product).  A null a-half (plain
 // table rows) reads as zero.
@@ -65,10 +84,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_cmux_tree(const CmuxTreeArgs 
     static_assert(cmux_tree_lds_bytes<LOGN, WAVES>() <= (size_t)160 * 1024, "k_cmux_tree: the LDS carve of this (N, waves) shape passes the 160 KiB of a CU");
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    cplx* tw = reinterpret_cast<cplx*>(smem);
-    TwStage<LOGN>::stage(tw, a.tw, tid, 64 * WAVES);
-    __syncthreads();
-    // from here on waves never synchronise with each other
+    cplx* tw = leveled_stage_twiddles<LOGN, WAVES>(smem, a.tw, tid);
 
     const int lvl_bits = a.depth - 1 - a.level;            // log2 of this level's nodes per lookup
     const long long q = (long long)blockIdx.x * WAVES + wave;      // node number within the level: lookup g, node j
@@ -87,9 +103,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_cmux_tree(const CmuxTreeArgs 
     }
     if (!ok) { if (a.fault) *a.fault = 1; return; }
 
-    unsigned char* wbase = smem + (size_t)TwStage<LOGN>::LDS_CPLX * sizeof(cplx) + (size_t)wave * bootstrap_wave_lds_bytes<LOGN>(0, DUAL);
-    double* xbuf = reinterpret_cast<double*>(wbase);
-    uint32_t* accbuf = reinterpret_cast<uint32_t*>(wbase + (size_t)G::XSLOTS * sizeof(double) * (DUAL ? 2 : 1));
+    const WaveLds w = leveled_wave_lds<LOGN, WAVES>(smem, wave);
+    double* xbuf = w.xbuf;
+    uint32_t* accbuf = w.accbuf;
 
     const uint32_t *b0, *a0, *b1, *a1;
     if (a.level == 0) {

@@ -40,10 +40,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_demux_tree(const DemuxTreeArg
     static_assert(cmux_tree_lds_bytes<LOGN, WAVES>() <= (size_t)160 * 1024, "k_demux_tree: the LDS carve of this (N, waves) shape passes the 160 KiB of a CU");
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    cplx* tw = reinterpret_cast<cplx*>(smem);
-    TwStage<LOGN>::stage(tw, a.tw, tid, 64 * WAVES);
-    __syncthreads();
-    // from here on waves never synchronise with each other
+    cplx* tw = leveled_stage_twiddles<LOGN, WAVES>(smem, a.tw, tid);
 
     const long long q = (long long)blockIdx.x * WAVES + wave;      // input node number within the level: lookup g, node j = q - (g << level)
     if (q >= ((long long)a.count << a.level)) return;
@@ -60,9 +57,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_demux_tree(const DemuxTreeArg
     }
     if (!ok) { if (a.fault) *a.fault = 1; return; }
 
-    unsigned char* wbase = smem + (size_t)TwStage<LOGN>::LDS_CPLX * sizeof(cplx) + (size_t)wave * bootstrap_wave_lds_bytes<LOGN>(0, DUAL);
-    double* xbuf = reinterpret_cast<double*>(wbase);
-    uint32_t* accbuf = reinterpret_cast<uint32_t*>(wbase + (size_t)G::XSLOTS * sizeof(double) * (DUAL ? 2 : 1));
+    const WaveLds w = leveled_wave_lds<LOGN, WAVES>(smem, wave);
+    double* xbuf = w.xbuf;
+    uint32_t* accbuf = w.accbuf;
 
     const uint32_t* node = a.src + (size_t)q * 2 * N;
     for (int c = lane; c < 2 * N; c += 64) accbuf[c] = node[c];

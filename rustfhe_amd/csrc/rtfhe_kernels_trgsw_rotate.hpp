@@ -50,10 +50,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_trgsw_rotate(const TrgswRotat
     static_assert(cmux_tree_lds_bytes<LOGN, WAVES>() <= (size_t)160 * 1024, "k_trgsw_rotate: the LDS carve of this (N, waves) shape passes the 160 KiB of a CU");
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    cplx* tw = reinterpret_cast<cplx*>(smem);
-    TwStage<LOGN>::stage(tw, a.tw, tid, 64 * WAVES);
-    __syncthreads();
-    // from here on waves never synchronise with each other
+    cplx* tw = leveled_stage_twiddles<LOGN, WAVES>(smem, a.tw, tid);
 
     const long long g = (long long)blockIdx.x * WAVES + wave;
     if (g >= a.count) return;
@@ -68,6 +65,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_trgsw_rotate(const TrgswRotat
         return;
     }
 
+    // leveled_wave_lds restated: through the helper the N = 2048 kernel comes out with other spill code (scripts/isa/snapshot.py)
     unsigned char* wbase = smem + (size_t)TwStage<LOGN>::LDS_CPLX * sizeof(cplx) + (size_t)wave * bootstrap_wave_lds_bytes<LOGN>(0, DUAL);
     double* xbuf = reinterpret_cast<double*>(wbase);
     uint32_t* accbuf = reinterpret_cast<uint32_t*>(wbase + (size_t)G::XSLOTS * sizeof(double) * (DUAL ? 2 : 1));

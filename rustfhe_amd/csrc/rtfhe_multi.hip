@@ -113,9 +113,7 @@ int sharded_dev_batch(rtfhe_ctx* ctx, int op, const void* d_c, const void* d_in0
     const bool ship_idx = lut && d_lut_idx;
     if (count == 0) return 0;
     if (count > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "count too large");
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-    if (cs != hipStreamCaptureStatusNone) return run(ctx, 0, d_c, d_in0, d_in1, d_out, count, s, d_lut_idx);
+    if (capturing(s)) return run(ctx, 0, d_c, d_in0, d_in1, d_out, count, s, d_lut_idx);
     const int n_dev = 1 + (int)ctx->peers.size();
     const size_t w = (size_t)ctx->p.n + 1, ow = many ? w << shift : w;      // words per gate in, out
     auto at = [&](const void* p, size_t gate) { return p ? (const void*)((const uint32_t*)p + gate * w) : nullptr; };

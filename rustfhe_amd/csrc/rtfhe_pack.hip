@@ -11,12 +11,6 @@ using namespace rtfhe_host;
 
 namespace {
 
-bool capturing(hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-    return cs != hipStreamCaptureStatusNone;
-}
-
 // what both pack entries check before anything is allocated or launched; fills shift[P] with the positions (pos NULL: p * rep)
 int pack_ready(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const void* in, int32_t P, const int32_t* pos, int32_t rep, const void* out, size_t count,
                std::vector<int32_t>& shift) {
@@ -50,28 +44,13 @@ int launch_pack(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const void* d_tlwe,
                 size_t count, hipStream_t s) {
     if (count == 0) return 0;
     const size_t N = (size_t)ctx->p.N, M = count * (size_t)P;
-    auto it = ctx->pack.find(s);
-    if (capturing(s)) {
-        // nothing may be allocated inside a capture: this stream's buffer must already hold the call, and the graph then owns its address
-        if (it == ctx->pack.end() || it->second.cap < M)
-            return fail(ctx, RTFHE_ERR_STATE, "a packing key switch inside a stream capture needs this stream's sample buffer to exist already: run one eager "
-                                              "rtfhe_pack_batch_dev of at least count * P = " + std::to_string(M) + " samples on the stream before capturing");
-        it->second.captured = true;
-    } else if (it == ctx->pack.end() || it->second.cap < M) {
-        rtfhe_ctx::PackBuf& pb = ctx->pack[s];
-        if (pb.d) {
-            HIPCHECK(ctx, hipDeviceSynchronize());            // earlier packs of this stream may still read the old buffer
-            uint32_t* old = pb.d;
-            const bool keep = pb.captured;
-            pb.d = nullptr; pb.cap = 0; pb.captured = false;      // (before the free: a failure below must not leave the old address behind)
-            if (keep) ctx->mux_retired.push_back(old);        // a graph holds its address: kept until the context goes
-            else HIPCHECK(ctx, hipFree(old));
-        }
-        HIPCHECK(ctx, hipMalloc((void**)&pb.d, M * 2 * N * 4));
-        pb.cap = M;
-        it = ctx->pack.find(s);
-    }
-    uint32_t* d_s = it->second.d;
+    const bool cap = capturing(s);
+    const std::string refusal = !cap ? std::string()
+                                     : "a packing key switch inside a stream capture needs this stream's sample buffer to exist already: run one eager "
+                                       "rtfhe_pack_batch_dev of at least count * P = " + std::to_string(M) + " samples on the stream before capturing";
+    StreamScratch* pb = nullptr;
+    if (int rc = stream_scratch(ctx, ctx->pack, s, cap, ScratchShape{1, 2 * N * 4}, M, refusal.c_str(), pb)) return rc;
+    uint32_t* d_s = pb->d[0];
     PackMmArgs m{};
     m.tlwe = (const uint32_t*)d_tlwe; m.kmat = pk->d_kmat; m.s = d_s;
     m.M = (int32_t)M; m.n = ctx->p.n; m.n16 = pk->n16; m.colgroups = pk->colgroups;

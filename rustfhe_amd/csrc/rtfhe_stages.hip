@@ -31,17 +31,7 @@ int launch_fft_t(rtfhe_ctx* ctx, bool forward, FftArgs a, hipStream_t s) {
     HIPCHECK(ctx, hipGetLastError());
     return 0;
 }
-template <int LOGN, bool ROUNDED>
-int launch_extprod_t(rtfhe_ctx* ctx, ExtProdArgs a, hipStream_t s) {
-    constexpr int W = 4;
-    auto k = k_external_product<LOGN, 3, 6, W, ROUNDED>;
-    const size_t lds = bootstrap_lds_bytes<LOGN>(W, 0);
-    if (int rc = allow_lds(ctx, k_external_product<LOGN, 3, 6, W, !ROUNDED>, lds)) return rc;      // both twins, as the leveled launches do
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
-    hipLaunchKernelGGL(k, dim3((a.count + W - 1) / W), dim3(64 * W), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    return 0;
-}
+RTFHE_LEVELED_FAMILY(extprod_twins, ExtProdArgs, k_external_product, bootstrap_lds_bytes<LOGN>(LEVELED_WAVES, 0))      // (its own LDS: no accumulator)
 
 template <int LOGN>
 int launch_keyswitch_t(rtfhe_ctx* ctx, KeySwitchArgs a, hipStream_t s) {
@@ -160,6 +150,14 @@ int launch_key_switch_ext(rtfhe_ctx* ctx, uint32_t* samples, uint32_t* d_out, si
     return ctx->logn == 10 ? launch_keyswitch_ext_t<10>(ctx, a, s) : launch_keyswitch_ext_t<11>(ctx, a, s);
 }
 
+int launch_key_switch_rows(rtfhe_ctx* ctx, uint32_t* samples, uint32_t* d_out, size_t rows, hipStream_t s, bool zero_out) {
+    if (!ctx->d_ksmat) return launch_key_switch_ext(ctx, samples, d_out, rows, s);
+    if (zero_out) HIPCHECK(ctx, hipMemsetAsync(d_out, 0, rows * ((size_t)ctx->p.n + 1) * 4, s));      // the K-slices add into it
+    BootstrapArgs k{};
+    k.out = d_out; k.count = (int32_t)rows; k.n = ctx->p.n;
+    return launch_key_switch_mm(ctx, k, samples, s);
+}
+
 }  // namespace rtfhe_host
 
 extern "C" {
@@ -190,9 +188,7 @@ int rtfhe_external_product_batch(rtfhe_ctx* ctx, const int32_t* bk_index, const 
         if ((rc = launch_extprod_xfft(ctx, (const int32_t*)ctx->d_b, (const uint32_t*)ctx->d_a, (uint32_t*)ctx->d_c, (int32_t)count, ctx->stream))) return rc;
     } else {
         ExtProdArgs a{ctx->d_tw, ctx->d_bk, (const int32_t*)ctx->d_b, (const uint32_t*)ctx->d_a, (uint32_t*)ctx->d_c, (int32_t)count};
-        if (leveled_rounded(ctx)) rc = ctx->logn == 10 ? launch_extprod_t<10, true>(ctx, a, ctx->stream) : launch_extprod_t<11, true>(ctx, a, ctx->stream);
-        else rc = ctx->logn == 10 ? launch_extprod_t<10, false>(ctx, a, ctx->stream) : launch_extprod_t<11, false>(ctx, a, ctx->stream);
-        if (rc) return rc;
+        if ((rc = launch_leveled(ctx, extprod_twins(ctx), count, ctx->stream, a, false))) return rc;      // a stage-level call: not counted
     }
     HIPCHECK(ctx, hipMemcpyAsync(out, ctx->d_c, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));

@@ -337,6 +337,38 @@ def test_graph_capture_replays_eager_words(world):
         w.eng.sync(s.cuda_stream)
 
 
+def test_larger_eager_call_retires_the_buffers_a_graph_holds(orc, world):
+    """A fresh stream: an eager depth-2 tree of 5 lookups, the same call captured, then an eager depth-3 tree of 37 lookups on that stream, which
+    replaces the stream's ping-pong buffers.  The graph holds the old pair's addresses: it is kept, not freed, so the replays still give the
+    small call's eager words (the oracle's), and the large call gives the oracle's."""
+    import torch
+    w = world
+    lut = w.lut["encrypted"]
+    idx2, row2, _, _ = _lookups(2, 5)[0]
+    idx3, row3, _, _ = _lookups(3, 37)[0]
+    d_idx2, d_row2, d_idx3, d_row3 = _cuda(idx2), _cuda(row2), _cuda(idx3), _cuda(row3)
+    s = torch.cuda.Stream()
+    out = torch.zeros((5, 2, w.N), dtype=torch.int32, device="cuda")
+    big = torch.zeros((37, 2, w.N), dtype=torch.int32, device="cuda")
+    with torch.cuda.stream(s):
+        w.eng.cmux_tree_batch_dev(w.sel, lut, 2, out, 5, d_idx2, d_row2, s.cuda_stream)
+        w.eng.sync(s.cuda_stream)
+        eager = out.clone()
+        assert np.array_equal(eager.cpu().numpy().view(np.uint32), _oracle(orc, w, "encrypted", 2, idx2, row2))
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            w.eng.cmux_tree_batch_dev(w.sel, lut, 2, out, 5, d_idx2, d_row2, s.cuda_stream)
+        w.eng.cmux_tree_batch_dev(w.sel, lut, 3, big, 37, d_idx3, d_row3, s.cuda_stream)
+        w.eng.sync(s.cuda_stream)
+        assert np.array_equal(big.cpu().numpy().view(np.uint32), _oracle(orc, w, "encrypted", 3, idx3, row3))
+        for _ in range(2):
+            out.zero_()
+            g.replay()
+            torch.cuda.synchronize()
+            assert torch.equal(out, eager)
+        w.eng.sync(s.cuda_stream)
+
+
 def test_wide_lut_example(engine, keys):
     """examples/wide_lut.py at the full parameter set: 24 six-bit lookups, four address bits by CMUX tree and two by PBS."""
     import importlib.util

@@ -290,6 +290,40 @@ def test_capture_replay_and_two_streams(worlds):
     assert np.array_equal(out.cpu().numpy().view(np.uint32), want_a) and np.array_equal(out2.cpu().numpy().view(np.uint32), want_b)
 
 
+def test_larger_eager_pack_retires_the_buffer_a_graph_holds(worlds):
+    """A fresh stream: an eager pack of 3 x 4 samples, the same call captured, then an eager pack of 9 x 4 samples on that stream, which replaces
+    the stream's buffer of key-switched samples.  The graph holds the old buffer's address: it is kept, not freed, so the replays still give
+    the small call's words, and the large call gives the oracle's."""
+    import torch
+    w = worlds(N1, 33)
+    R, e = w.R, w.eng
+    P, rep = 4, 256
+    pos, _ = R.lut_pack_layout(N1, 2)
+    a, b = _shape_inputs(w, 3, P, 501), _shape_inputs(w, 9, P, 503)
+    want_a, want_b = O.pack(w.rp, w.pk, a, P, pos, rep), O.pack(w.rp, w.pk, b, P, pos, rep)
+    s = torch.cuda.Stream()
+    d_a, d_b = _cuda(a, np.uint32), _cuda(b, np.uint32)
+    out = torch.zeros((3, 2, N1), dtype=torch.int32, device="cuda")
+    big = torch.zeros((9, 2, N1), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        e.pack_batch_dev(w.key, d_a, P, out, 3, rep, pos, s.cuda_stream)
+        e.sync(s.cuda_stream)
+        assert np.array_equal(out.cpu().numpy().view(np.uint32), want_a)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            e.pack_batch_dev(w.key, d_a, P, out, 3, rep, pos, s.cuda_stream)
+        e.pack_batch_dev(w.key, d_b, P, big, 9, rep, pos, s.cuda_stream)
+        e.sync(s.cuda_stream)
+        assert np.array_equal(big.cpu().numpy().view(np.uint32), want_b)
+        for _ in range(2):
+            out.zero_()
+            g.replay()
+            torch.cuda.synchronize()
+            assert np.array_equal(out.cpu().numpy().view(np.uint32), want_a)
+    e.sync(s.cuda_stream)
+
+
 def test_exact_backends_give_the_same_words(worlds):
     w = worlds(N1, 33)
     R, e = w.R, w.eng
