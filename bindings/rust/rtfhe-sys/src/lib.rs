@@ -172,6 +172,14 @@ extern "C" {
                                       count: usize, stream: *mut c_void) -> c_int;
     pub fn rtfhe_lut_accumulate_dev(lut: *mut rtfhe_lut, d_trlwe: *const c_void, first: i32, n: i32, count: usize, stream: *mut c_void) -> c_int;
     pub fn rtfhe_lut_read_dev(lut: *const rtfhe_lut, d_out: *mut c_void, first: i32, n: i32, stream: *mut c_void) -> c_int;
+    // TRLWE sample extraction (the packing key switch's inverse): coefficients coef[0 .. P) (HOST, null: p * stride) of trlwe [count][2][N] as lvl0
+    // ciphertexts out [count][P][n+1] (needs the key-switching key) or, the lvl1 forms, as lvl1 samples out [count][P][N+1] (no key at all)
+    pub fn rtfhe_trlwe_extract_batch(ctx: *mut rtfhe_ctx, trlwe: *const u32, P: i32, coef: *const i32, stride: i32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trlwe_extract_batch_dev(ctx: *mut rtfhe_ctx, d_trlwe: *const c_void, P: i32, coef: *const i32, stride: i32, d_out: *mut c_void, count: usize,
+                                         stream: *mut c_void) -> c_int;
+    pub fn rtfhe_trlwe_extract_lvl1_batch(ctx: *mut rtfhe_ctx, trlwe: *const u32, P: i32, coef: *const i32, stride: i32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trlwe_extract_lvl1_batch_dev(ctx: *mut rtfhe_ctx, d_trlwe: *const c_void, P: i32, coef: *const i32, stride: i32, d_out: *mut c_void, count: usize,
+                                              stream: *mut c_void) -> c_int;
     pub fn rtfhe_sync(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_begin(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_end(ctx: *mut rtfhe_ctx, stream: *mut c_void, ms: *mut f64, launches: *mut i64) -> c_int;

@@ -46,6 +46,9 @@
  *                                    <- TRGSWRepF::cross (hom_nand/src/trgsw.rs:264-306) on caller-supplied TRGSW samples: the tree run backwards, one
  *                                       TRLWE into leaf `addr` of 2^d and zero into the others, and the leaves added into an encrypted table's rows
  *                                       (the reference has the product, not the demultiplexer)
+ *   rtfhe_trlwe_extract_batch[_dev] / rtfhe_trlwe_extract_lvl1_batch[_dev]
+ *                                    <- TRLWERep::sample_extract_index (hom_nand/src/trlwe.rs:110-121) at caller-chosen coefficients of TRLWEs that already
+ *                                       exist, then TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73): leveled mode -> bootstrapped mode
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch           <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -667,6 +670,48 @@ int rtfhe_demux_tree_batch_dev(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const voi
                                const void *d_x /* [count][2][N] */, void *d_out /* [count][2^depth][2][N] */, size_t count, void *stream);
 int rtfhe_lut_accumulate_dev(rtfhe_lut *lut, const void *d_trlwe /* [count][n][2][N] */, int32_t first, int32_t n, size_t count, void *stream);
 int rtfhe_lut_read_dev(const rtfhe_lut *lut, void *d_out /* [n][2][N] */, int32_t first, int32_t n, void *stream);
+/* ---- TRLWE sample extraction: coefficients of TRLWE rows as lvl0 ciphertexts (leveled mode -> bootstrapped mode) ----
+ * The inverse of the packing key switch.  It takes TRLWEs that already exist -- a row read with rtfhe_lut_read_dev, a packed row, a
+ * demultiplexer leaf, a row a client sent -- and returns ciphertexts of chosen coefficients, which the bootstrapped entry points (gates,
+ * PBS, LUT circuits) take as they are.
+ *
+ * Sample (g, p).  For the TRLWE x[g], u32[2][N] (b then a), and the coefficient list coef[0 .. P), sample (g, p) is
+ * e = sample_extract_index(x[g], coef[p]), the reference's TRLWERep::sample_extract_index (hom_nand/src/trlwe.rs:110-121).  Word for word,
+ * with j = coef[p]:
+ *   - e.a[c] = x.a[j - c]            for c <= j;
+ *   - e.a[c] = 0 - x.a[N + j - c]    for c > j, wrapping mod 2^32;
+ *   - e.b    = x.b[j].
+ * Its layout is that of rtfhe_key_switch_batch's input, the lvl1 TLWE: a'[0 .. N), then b'.
+ *   rtfhe_trlwe_extract_lvl1_batch[_dev]   out[g][p] = e, u32[N+1].  Needs no key at all: a context with nothing loaded runs it.
+ *   rtfhe_trlwe_extract_batch[_dev]        out[g][p] = identity_key_switch(e), u32[n+1], by the route every extract form takes (the stream's
+ *                                          lvl1 sample buffer, then the key switch as one i8 contraction, or one wave per sample under
+ *                                          RTFHE_KS_MM_MIN=0).  Needs the key-switching key (RTFHE_ERR_STATE otherwise), not the bootstrapping key.
+ *
+ * Parameters.
+ *   - coef is a host array int32[P], shared by the whole batch like rtfhe_pack_batch's pos (copied into the launches' arguments when the call is
+ *     enqueued: a stream capture bakes it in).  Duplicates are allowed.
+ *   - coef NULL means coef[p] = p * stride: rtfhe_trlwe_extract_batch(P, NULL, rep) reads back what rtfhe_pack_batch(P, NULL, rep) wrote.
+ *     stride is ignored when coef is given.
+ *   - Checked before anything is allocated or launched, RTFHE_ERR_INVALID with a message naming the sample: 1 <= P <= N; coef[p] in [0, N);
+ *     with coef NULL stride >= 1 and (P - 1) * stride < N; count * P < 2^31; no null buffer; out does not overlap trlwe.
+ *   - count == 0 returns 0.
+ *
+ * Backends and devices.  No polynomial is multiplied: both forms run on every rtfhe_backend, as packing does, and on an
+ * rtfhe_ctx_create_multi context on the primary device.
+ *
+ * Scratch and captures.  The lvl1 form allocates nothing and may sit in a caller's stream capture without a prior eager call.  The samples of
+ * the lvl0 form go through the stream's lvl1 sample buffer, 4 (N + 1) bytes per sample, under rtfhe_pbs_many_batch_dev's rule: grown outside
+ * stream captures only (growing an existing one synchronises the device) and kept until the context is destroyed; inside a caller's capture
+ * an eager rtfhe_trlwe_extract_batch_dev of at least count * P samples must have run on that stream first, else RTFHE_ERR_STATE.
+ * A call is ceil(P / 512) launches of the extract kernel plus, in the lvl0 form, the key switch. */
+int rtfhe_trlwe_extract_batch(rtfhe_ctx *ctx, const uint32_t *trlwe /* [count][2][N] */, int32_t P, const int32_t *coef /* [P] or NULL */,
+                              int32_t stride, uint32_t *out /* [count][P][n+1] */, size_t count);
+int rtfhe_trlwe_extract_batch_dev(rtfhe_ctx *ctx, const void *d_trlwe /* [count][2][N] */, int32_t P, const int32_t *coef /* HOST [P] or NULL */,
+                                  int32_t stride, void *d_out /* [count][P][n+1] */, size_t count, void *stream);
+int rtfhe_trlwe_extract_lvl1_batch(rtfhe_ctx *ctx, const uint32_t *trlwe /* [count][2][N] */, int32_t P, const int32_t *coef /* [P] or NULL */,
+                                   int32_t stride, uint32_t *out /* [count][P][N+1] */, size_t count);
+int rtfhe_trlwe_extract_lvl1_batch_dev(rtfhe_ctx *ctx, const void *d_trlwe /* [count][2][N] */, int32_t P, const int32_t *coef /* HOST [P] or NULL */,
+                                       int32_t stride, void *d_out /* [count][P][N+1] */, size_t count, void *stream);
 /* waits for `stream`; also reports (once) a netlist gate skipped since the previous call */
 int rtfhe_sync(rtfhe_ctx *ctx, void *stream);
 /* device-side timing of the launches enqueued by the *_dev calls between begin and end (HIP events on

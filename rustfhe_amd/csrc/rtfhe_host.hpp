@@ -12,6 +12,8 @@
 //                            and the CMUX demultiplexer tree with the accumulation of its leaves into an encrypted table's rows
 //   rtfhe_cmux_net.hip       CMUX netlists: decision diagrams over a selector set, levelised (rtfhe_cmux_net_plan.cpp, host only) and recorded into a HIP graph
 //   rtfhe_pack.hip           packing key switch: packing keys (signed byte limbs in operand order), lvl0 samples into TRLWE rows, in-place table updates
+//   rtfhe_extract.hip        TRLWE sample extraction: chosen coefficients of existing TRLWEs as lvl1 samples or, through the extract tail, lvl0 ciphertexts
+//                            (its argument checks: rtfhe_extract_plan.cpp, host only)
 // Every kernel is instantiated in exactly one of them.  No CPU fallback anywhere: an entry point runs HIP kernels or fails.
 #pragma once
 

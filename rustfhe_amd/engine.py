@@ -460,6 +460,45 @@ class Engine:
         self._ck(self.L.rtfhe_pack_batch_dev(self.h, pk.h, self._dev(d_tlwe), int(P), _ptr(self._pos_arg(pos, P)), int(rep), self._dev(d_out), count,
                                              C.c_void_p(stream) if stream else None))
 
+    # ---- TRLWE sample extraction (include/rtfhe.h: rtfhe_trlwe_extract_batch[_dev], rtfhe_trlwe_extract_lvl1_batch[_dev]) ----------------------
+    def _coef_arg(self, coef, P):
+        if coef is None:
+            return None
+        coef = _np(coef, np.int32).reshape(-1)
+        assert coef.size == int(P), "one coefficient per sample"
+        return coef
+
+    def trlwe_extract_batch(self, trlwe, P, coef=None, stride=1):
+        """Coefficients coef[0 .. P) (None: p * stride) of every TRLWE of u32[count][2][N] (b then a) as lvl0 ciphertexts u32[count][P][n+1]:
+        sample extract at coef[p], then the key switch -- pack_batch the other way.  Needs the key-switching key, not the bootstrapping key.
+        Arguments are checked here: a bad one raises RtfheError before anything runs."""
+        trlwe = _np(trlwe, np.uint32).reshape(-1, 2, self.p.N)
+        P = int(P)
+        out = np.empty((trlwe.shape[0], max(P, 0), self.p.n + 1), np.uint32)
+        self._ck(self.L.rtfhe_trlwe_extract_batch(self.h, _ptr(trlwe), P, _ptr(self._coef_arg(coef, P)), int(stride), _ptr(out), trlwe.shape[0]))
+        return out
+
+    def trlwe_extract_batch_dev(self, d_trlwe, P, d_out, count, coef=None, stride=1, stream=None):
+        """... on device buffers (d_trlwe: [count][2][N] words, d_out: [count][P][n+1] words, not overlapping; coef stays a host array, copied at
+        enqueue time), asynchronous on `stream`.  Inside a stream capture an eager call of at least count * P samples must have run on the
+        stream first."""
+        self._ck(self.L.rtfhe_trlwe_extract_batch_dev(self.h, self._dev(d_trlwe), int(P), _ptr(self._coef_arg(coef, P)), int(stride), self._dev(d_out), count,
+                                                      C.c_void_p(stream) if stream else None))
+
+    def trlwe_extract_lvl1_batch(self, trlwe, P, coef=None, stride=1):
+        """The same samples before the key switch: lvl1 samples u32[count][P][N+1] (a'[0..N), b'), the input layout of key_switch_batch.  Needs
+        no key at all."""
+        trlwe = _np(trlwe, np.uint32).reshape(-1, 2, self.p.N)
+        P = int(P)
+        out = np.empty((trlwe.shape[0], max(P, 0), self.p.N + 1), np.uint32)
+        self._ck(self.L.rtfhe_trlwe_extract_lvl1_batch(self.h, _ptr(trlwe), P, _ptr(self._coef_arg(coef, P)), int(stride), _ptr(out), trlwe.shape[0]))
+        return out
+
+    def trlwe_extract_lvl1_batch_dev(self, d_trlwe, P, d_out, count, coef=None, stride=1, stream=None):
+        """... on device buffers (d_out: [count][P][N+1] words).  Allocates nothing: it may be captured without a prior eager call."""
+        self._ck(self.L.rtfhe_trlwe_extract_lvl1_batch_dev(self.h, self._dev(d_trlwe), int(P), _ptr(self._coef_arg(coef, P)), int(stride), self._dev(d_out),
+                                                           count, C.c_void_p(stream) if stream else None))
+
     # ---- stage level ------------------------------------------------------------------------
     def blind_rotate_batch(self, tlwe, steps=None):
         tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)

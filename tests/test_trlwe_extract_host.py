@@ -1,0 +1,109 @@
+"""CPU: TRLWE sample extraction (include/rtfhe.h: rtfhe_trlwe_extract_batch) without a device -- the numpy restatement of
+sample_extract_index that the GPU tests' inputs are planned with against the oracle, the planted edge words' sides, the parameter arithmetic of
+examples/histogram_threshold.py, and the seeds of the GPU suite's meaning test: on the oracle's own words every entry decodes, so the GPU test,
+which asserts those words, cannot fail on noise."""
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+import extract_helpers as X
+import pack_oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize("N", [16, 1024, 2048])
+def test_formula_equals_the_oracle_sample_extract(orc, N):
+    rng = np.random.default_rng(N)
+    x = rng.integers(0, 1 << 32, (2, N), dtype=np.uint64).astype(np.uint32)
+    x[1, [0, 1, N // 2, N - 1]] = [0, 0x80000000, 0xFFFFFFFF, 1]
+    P = orc.Params(n=8, N=N)
+    for j in (0, 1, N // 2, N - 1):
+        want = orc.sample_extract(P, x.reshape(-1), j)
+        got = X.extract_formula(x, N, j)
+        assert np.array_equal(got, want), (N, j, np.flatnonzero(got != want)[:5])
+        # word for word as include/rtfhe.h states it
+        assert got[N] == x[0, j] and got[0] == x[1, j]
+        if j < N - 1:
+            assert got[j + 1] == (0 - int(x[1, N - 1])) & 0xFFFFFFFF
+
+
+def test_planted_edges_land_on_both_sides():
+    """the lists of the GPU suite's shapes that leave room: every edge value once where index <= j (plain) and once where index > j (negated)"""
+    for N in (1024, 2048):
+        for coefs in ([0, 1, N // 2, N - 2, N - 1], [5, 5], [1, N // 2, N - 1], list(range(17)), list(range(0, N, N // 16))):
+            plain, neg = X.edge_slots(N, coefs)
+            assert not set(plain) & set(neg)
+            x = X.trlwe_inputs(7, N, 3, coefs)
+            for g in range(3):
+                a = x[g, 1]
+                for v in X.EDGES:
+                    at = np.flatnonzero(a == v)
+                    if max(coefs) >= len(X.EDGES) - 1:
+                        assert any(i <= max(coefs) for i in at), (N, coefs, hex(int(v)))
+                    assert any(i > min(coefs) for i in at), (N, coefs, hex(int(v)))
+        # the single-coefficient shapes complement each other: j = 0 has one plain index, j = N - 1 no negated one
+        assert X.edge_slots(N, [0])[0] == [0] and len(X.edge_slots(N, [0])[1]) == len(X.EDGES)
+        assert X.edge_slots(N, [N - 1])[1] == [] and len(X.edge_slots(N, [N - 1])[0]) == len(X.EDGES)
+
+
+def _example():
+    spec = importlib.util.spec_from_file_location("histogram_threshold", os.path.join(ROOT, "examples", "histogram_threshold.py"))
+    ex = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ex)
+    return ex
+
+
+def test_example_parameter_arithmetic():
+    import rustfhe_amd as R
+    ex = _example()
+    p = R.Params()
+    # the counting unit is encode_msgs(1, 3) = 2^-4; 7 of them keep the padding bit clear; one slot per row, at N/2
+    assert int(R.encode_msgs([1], ex.MSG_BITS)[0]) == 1 << (32 - ex.UNIT_BITS) == 1 << 28
+    assert 7 * (1 << 28) < 1 << 31 and ex.MAX_VOTERS == 15
+    from private_histogram import counting_units, slots_for
+    for voters in (1, 12, 15):
+        assert slots_for(voters, ex.UNIT_BITS) == 1 and ex.slot_coefficients(p, voters, ex.UNIT_BITS).tolist() == [p.N // 2]
+        x = counting_units(p, voters, ex.UNIT_BITS)
+        assert (x[:, 0, p.N // 2] == 1 << 28).all() and np.count_nonzero(x) == voters
+    assert slots_for(16, ex.UNIT_BITS) == 2
+    # the budget the docstring states: 3.4e-3 and 8.6 deviations at 15 writes; 3 bits stand, 4 bits would not
+    sigma, margin = ex.noise_budget(p.n, p.N, 15)
+    assert abs(sigma - 3.4e-3) < 1e-4 and abs(margin - 8.6) < 0.1 and margin >= ex.DEVIATIONS
+    assert (2.0 ** -6 - ex.KEY_SWITCH_MEAN) / sigma < ex.DEVIATIONS
+    rng = np.random.default_rng(3)
+    for voters in (1, 12, 15):
+        votes = ex.draw_votes(rng, voters)
+        assert votes.size == voters and np.bincount(votes).max() <= 7 and votes.max() < 16
+    tv = R.lut_polynomial(lambda m: int(m >= 2), p.N, ex.MSG_BITS, out_bits=1)
+    B = p.N >> ex.MSG_BITS
+    assert [int(tv[m * B]) for m in range(8)] == [0, 0] + [1 << 30] * 6
+
+
+@pytest.mark.parametrize("N", [1024, 2048])
+def test_meaning_case_a_seeds_decode_on_the_oracle(orc, N):
+    import rustfhe_amd as R
+    rp, key0, key1, ksk = X.meaning_keys(R, N)
+    msgs, row, coef = X.meaning_case_a(R, N, rp, key1)
+    assert np.array_equal(R.decode_msgs(R.trlwe_phase(rp, key1, row)[0], X.MEANING_BITS), msgs)
+    _, lvl0 = X.oracle_words(orc, orc.Params(n=rp.n, N=N), ksk, row, coef)
+    ph = R.phases(rp, key0, lvl0[0])
+    assert np.array_equal(R.decode_msgs(ph, X.MEANING_BITS), msgs[coef]), (N, R.decode_msgs(ph, X.MEANING_BITS), msgs[coef])
+    # not on the edge of a box either: within a quarter of a box of the entry
+    err = (ph.astype(np.int64) - R.encode_msgs(msgs[coef], X.MEANING_BITS).astype(np.int64) + 2 ** 31) % 2 ** 32 - 2 ** 31
+    assert np.abs(err).max() < 1 << (32 - X.MEANING_BITS - 3), np.abs(err).max() / 2.0 ** 32
+
+
+def test_meaning_case_b_seeds_decode_on_the_oracle(orc):
+    import rustfhe_amd as R
+    N = 1024
+    rp, key0, key1, ksk = X.meaning_keys(R, N)
+    msgs, ct, pk = X.meaning_case_b(R, N, rp, key0, key1)
+    packed = O.pack(rp, pk, ct, X.MEANING_PACK_P, None, 1)
+    _, lvl0 = X.oracle_words(orc, orc.Params(n=rp.n, N=N), ksk, packed, X.coefficients(N, X.MEANING_PACK_P, None, 1))
+    ph = R.phases(rp, key0, lvl0[0])
+    assert np.array_equal(R.decode_msgs(ph, X.MEANING_BITS), msgs)
+    err = (ph.astype(np.int64) - R.encode_msgs(msgs, X.MEANING_BITS).astype(np.int64) + 2 ** 31) % 2 ** 32 - 2 ** 31
+    assert np.abs(err).max() < 1 << (32 - X.MEANING_BITS - 3), np.abs(err).max() / 2.0 ** 32
