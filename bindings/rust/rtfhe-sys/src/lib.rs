@@ -34,6 +34,7 @@ pub enum rtfhe_circuit {}
 pub enum rtfhe_lut {}
 pub enum rtfhe_trgsw {}
 pub enum rtfhe_packing_key {}
+pub enum rtfhe_plain {}
 pub enum rtfhe_fft_plan {}
 
 pub const RTFHE_NAND: c_int = 0;
@@ -180,6 +181,14 @@ extern "C" {
     pub fn rtfhe_trlwe_extract_lvl1_batch(ctx: *mut rtfhe_ctx, trlwe: *const u32, P: i32, coef: *const i32, stride: i32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_trlwe_extract_lvl1_batch_dev(ctx: *mut rtfhe_ctx, d_trlwe: *const c_void, P: i32, coef: *const i32, stride: i32, d_out: *mut c_void, count: usize,
                                               stream: *mut c_void) -> c_int;
+    // exact TRLWE x plain-polynomial products: out[g] = (accumulate ? out[g] : 0) + sum_k w[w_idx[g][k]] * x[x_idx[g][k]] mod 2^32, K in 1 ..= 8,
+    // K * wmax <= 192 N; w_idx / x_idx [count][K] (null: entry k / row g * K + k); needs no key, every backend
+    pub fn rtfhe_plain_create(ctx: *mut rtfhe_ctx, w: *const i32, n_w: i32, out: *mut *mut rtfhe_plain) -> c_int;
+    pub fn rtfhe_plain_destroy(w: *mut rtfhe_plain);
+    pub fn rtfhe_trlwe_mul_plain_batch(ctx: *mut rtfhe_ctx, w: *const rtfhe_plain, w_idx: *const i32, x: *const u32, n_x: i32, x_idx: *const i32, K: i32,
+                                       accumulate: i32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trlwe_mul_plain_batch_dev(ctx: *mut rtfhe_ctx, w: *const rtfhe_plain, d_w_idx: *const c_void, d_x: *const c_void, n_x: i32,
+                                           d_x_idx: *const c_void, K: i32, accumulate: i32, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
     pub fn rtfhe_sync(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_begin(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_end(ctx: *mut rtfhe_ctx, stream: *mut c_void, ms: *mut f64, launches: *mut i64) -> c_int;

@@ -49,6 +49,10 @@
  *   rtfhe_trlwe_extract_batch[_dev] / rtfhe_trlwe_extract_lvl1_batch[_dev]
  *                                    <- TRLWERep::sample_extract_index (hom_nand/src/trlwe.rs:110-121) at caller-chosen coefficients of TRLWEs that already
  *                                       exist, then TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73): leveled mode -> bootstrapped mode
+ *   rtfhe_plain_create / rtfhe_trlwe_mul_plain_batch[_dev]
+ *                                    <- Polynomial::cross (utils/src/math.rs:238-257) of both polynomials of a TRLWE row with a plain integer polynomial:
+ *                                       the exact ciphertext x plaintext product, sums of up to eight per sample (the reference has the polynomial
+ *                                       product, not the TRLWE operation)
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch           <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -712,6 +716,45 @@ int rtfhe_trlwe_extract_lvl1_batch(rtfhe_ctx *ctx, const uint32_t *trlwe /* [cou
                                    int32_t stride, uint32_t *out /* [count][P][N+1] */, size_t count);
 int rtfhe_trlwe_extract_lvl1_batch_dev(rtfhe_ctx *ctx, const void *d_trlwe /* [count][2][N] */, int32_t P, const int32_t *coef /* HOST [P] or NULL */,
                                        int32_t stride, void *d_out /* [count][P][N+1] */, size_t count, void *stream);
+/* ---- exact TRLWE x plain-polynomial products: ciphertext x plaintext, the linear layer of the leveled mode ----
+ * A plain set holds n_w integer polynomials w[e], int32[N], transformed once at creation.  A call computes, for g in [0, count):
+ *
+ *   out[g] = (accumulate ? out[g] : 0) + sum_{k < K} w[w_idx[g][k]] * x[x_idx[g][k]]        in Z_{2^32}[X]/(X^N + 1)
+ *
+ * on both polynomials of the TRLWE row (u32[2][N], b then a), every word wrapping mod 2^32.  The result is EXACT: no rounding anywhere, so it
+ * does not depend on the backend and adds no noise of its own.  The output noise is the input's scaled by the weights: variance
+ * sum_k ||w_k||_2^2 sigma_x^2, mean ||w||_1 times the input's mean.
+ *
+ * Parameters.
+ *   - x is an array of n_x rows.  w_idx NULL means entry k for every g (it needs n_w >= K: the same weights for every sample); x_idx NULL means
+ *     row g * K + k (it needs n_x >= count * K).  Duplicates are allowed.
+ *   - accumulate = 1 adds into out: a bias (the caller initialises out with the trivial TRLWE: bias in b, 0 in a), more than K terms, residual
+ *     adds.  accumulate = 0 overwrites out.
+ *   - Exactness domain.  Creation records wmax = max_e ||w[e]||_1.  A call is accepted iff K * wmax <= 192 * N, 1 <= K <= 8: the total l1 norm
+ *     6 * 32 * N of the small operand at which the split-FFT exact backend's products are proven exact (worst-case transform error 2^-8.25 at
+ *     N = 1024, 2^-6.62 at N = 2048, against the 1/2 of the rounding), here with the roles reversed: the weights are transformed once, the
+ *     ciphertext is split into signed 16-bit halves when it is read.
+ *   - Checked on the host before anything is allocated or launched, RTFHE_ERR_INVALID with a message naming the sample: handles and buffers
+ *     non-null; K; K * wmax; n_w, n_x >= 1; count * K < 2^31; every host index in range and the NULL-index rules above; out overlaps no part of x
+ *     (in-place products are not supported).  count == 0 returns 0.
+ *   - The _dev form takes the index arrays on the device and checks them in the kernel: a sample with a bad index is skipped, its output row
+ *     untouched, and the next rtfhe_sync returns RTFHE_ERR_INVALID once, as for rtfhe_cmux_tree_batch_dev.
+ *
+ * Keys, backends and devices.  It needs no key at all and runs on every rtfhe_backend; on an rtfhe_ctx_create_multi context on the primary
+ * device.  Lifetime is rtfhe_trgsw's: the spectra (8 N bytes per polynomial) live on the primary device and go with the context if it is
+ * destroyed first; a call then returns RTFHE_ERR_STATE and rtfhe_plain_destroy only frees the handle.
+ *
+ * Scratch and captures.  The _dev form allocates nothing and is ONE launch: it may sit in a caller's stream capture first thing on a fresh
+ * stream (rtfhe_plain_create is synchronous and builds what the kernel needs). */
+typedef struct rtfhe_plain rtfhe_plain;
+int rtfhe_plain_create(rtfhe_ctx *ctx, const int32_t *w /* [n_w][N] */, int32_t n_w, rtfhe_plain **out);
+void rtfhe_plain_destroy(rtfhe_plain *w);
+int rtfhe_trlwe_mul_plain_batch(rtfhe_ctx *ctx, const rtfhe_plain *w, const int32_t *w_idx /* [count][K] or NULL */, const uint32_t *x /* [n_x][2][N] */,
+                                int32_t n_x, const int32_t *x_idx /* [count][K] or NULL */, int32_t K, int32_t accumulate,
+                                uint32_t *out /* [count][2][N] */, size_t count);
+int rtfhe_trlwe_mul_plain_batch_dev(rtfhe_ctx *ctx, const rtfhe_plain *w, const void *d_w_idx /* [count][K] or NULL */, const void *d_x /* [n_x][2][N] */,
+                                    int32_t n_x, const void *d_x_idx /* [count][K] or NULL */, int32_t K, int32_t accumulate,
+                                    void *d_out /* [count][2][N] */, size_t count, void *stream);
 /* waits for `stream`; also reports (once) a netlist gate skipped since the previous call */
 int rtfhe_sync(rtfhe_ctx *ctx, void *stream);
 /* device-side timing of the launches enqueued by the *_dev calls between begin and end (HIP events on

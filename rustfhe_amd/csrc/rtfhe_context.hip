@@ -340,6 +340,8 @@ void rtfhe_ctx_destroy(rtfhe_ctx* ctx) {
     ctx->trgsws.clear();
     for (rtfhe_packing_key* k : ctx->pack_keys) { packing_key_release(k); k->ctx = nullptr; }      // packing keys: the same rule
     ctx->pack_keys.clear();
+    for (rtfhe_plain* w : ctx->plains) { plain_release(w); w->ctx = nullptr; }      // plain sets: the same rule
+    ctx->plains.clear();
     for (rtfhe_ctx* peer : ctx->peers) rtfhe_ctx_destroy(peer);
     ctx->peers.clear();
     (void)hipSetDevice(ctx->device);

@@ -125,15 +125,19 @@ static_assert(XPairRr::fits(NPAD_MAX, rr_fit<XPairRrLds>(NPAD_MAX)), "k_bootstra
 
 namespace rtfhe_host {
 
+int xfft_table_ensure(rtfhe_ctx* ctx) {
+    if (ctx->d_xtw) return 0;
+    const std::vector<cplx> t = ctx->logn == 11 ? xfft2_device_table() : xfft_device_table();
+    HIPCHECK(ctx, hipMalloc((void**)&ctx->d_xtw, t.size() * sizeof(cplx)));
+    HIPCHECK(ctx, hipMemcpy(ctx->d_xtw, t.data(), t.size() * sizeof(cplx), hipMemcpyHostToDevice));
+    return 0;
+}
+
 int xfft_prepare(rtfhe_ctx* ctx) {
     if (ctx->xfft_ready) return 0;
     if (!ctx->d_bk_torus) return fail(ctx, RTFHE_ERR_STATE, "the split-FFT exact backend needs the bootstrapping key in torus form (rtfhe_load_bk_torus)");
     const bool big = ctx->logn == 11;
-    if (!ctx->d_xtw) {
-        const std::vector<cplx> t = big ? xfft2_device_table() : xfft_device_table();
-        HIPCHECK(ctx, hipMalloc((void**)&ctx->d_xtw, t.size() * sizeof(cplx)));
-        HIPCHECK(ctx, hipMemcpy(ctx->d_xtw, t.data(), t.size() * sizeof(cplx), hipMemcpyHostToDevice));
-    }
+    if (int rc = xfft_table_ensure(ctx)) return rc;
     const size_t polys = bk_word_count(ctx->p) / ctx->p.N;
     if (!ctx->d_xbk) HIPCHECK(ctx, hipMalloc((void**)&ctx->d_xbk, 2 * bk_cplx_count(ctx->p) * sizeof(cplx)));
     constexpr int W = 4;

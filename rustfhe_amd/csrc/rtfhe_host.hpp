@@ -14,6 +14,8 @@
 //   rtfhe_pack.hip           packing key switch: packing keys (signed byte limbs in operand order), lvl0 samples into TRLWE rows, in-place table updates
 //   rtfhe_extract.hip        TRLWE sample extraction: chosen coefficients of existing TRLWEs as lvl1 samples or, through the extract tail, lvl0 ciphertexts
 //                            (its argument checks: rtfhe_extract_plan.cpp, host only)
+//   rtfhe_plain.hip          exact TRLWE x plain-polynomial products: plain sets (integer polynomials as spectra), sums of up to eight products per sample
+//                            on the split-FFT exact backend's arithmetic, on every backend (its argument checks: rtfhe_plain_plan.cpp, host only)
 // Every kernel is instantiated in exactly one of them.  No CPU fallback anywhere: an entry point runs HIP kernels or fails.
 #pragma once
 
@@ -65,6 +67,7 @@ struct rtfhe_circuit;
 struct rtfhe_lut;
 struct rtfhe_trgsw;
 struct rtfhe_packing_key;
+struct rtfhe_plain;
 struct rtfhe_ctx {
     rtfhe_params p{};
     int device = 0;
@@ -143,6 +146,7 @@ struct rtfhe_ctx {
     // counted by rtfhe_ctx_memory_bytes
     ScratchMap pack;
     std::vector<rtfhe_packing_key*> pack_keys;      // live packing keys of this context: their matrices go with it, the handles stay
+    std::vector<rtfhe_plain*> plains;      // live plain sets of this context: their spectra go with it, the handles stay
     int num_cus = 256;
     int force_waves = 0;   // RTFHE_FORCE_WAVES=1|2|4|8: one kernel shape for every batch (the parity tests' second opinions)
     int wg_max = 512;      // RTFHE_WG_MAX_GATES: largest batch routed to the workgroup-per-gate kernel
@@ -186,6 +190,14 @@ struct rtfhe_packing_key {
     rtfhe_ctx* ctx = nullptr;           // null once the context has been destroyed (the handle then only remains to be freed)
     uint4* d_kmat = nullptr;            // [2N / 16 column groups][n16 / 2 K-steps][4 limbs][64 lanes] x 16 B (rtfhe_kernels_pack.hpp)
     int32_t n16 = 0, colgroups = 0;
+};
+
+// a plain set (rtfhe_plain_create): integer polynomials as spectra on the primary device, the small operand of rtfhe_trlwe_mul_plain_batch
+struct rtfhe_plain {
+    rtfhe_ctx* ctx = nullptr;           // null once the context has been destroyed (the handle then only remains to be freed)
+    rtfhe::cplx* d_spec = nullptr;      // N = 1024: [n_w][512]; N = 2048: [n_w][2 halves][512] (rtfhe_kernels_plain.hpp)
+    int32_t n_w = 0;
+    int64_t wmax = 0;                   // max over the set of a polynomial's l1 norm: a call is accepted iff K * wmax <= 192 N
 };
 
 namespace rtfhe_host {
@@ -249,6 +261,7 @@ void circuit_release(rtfhe_circuit* c);                                   // rtf
 void lut_release(rtfhe_lut* lut);                                         // frees a table's device copies (rtfhe_context.hip)
 void trgsw_release(rtfhe_trgsw* t);                                       // frees a selector set's spectra (rtfhe_cmux_tree.hip)
 void packing_key_release(rtfhe_packing_key* k);                           // frees a packing key's matrix (rtfhe_pack.hip)
+void plain_release(rtfhe_plain* w);                                       // frees a plain set's spectra (rtfhe_plain.hip)
 // what every entry point over a selector set checks first (rtfhe_cmux_tree.hip): the handles (lut only with_table), the caller's other pointers
 // (args_ok), live and own contexts, the mirror backend -- who: "the CMUX tree runs", for the message
 int selector_set_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, bool with_table, const rtfhe_lut* lut, bool args_ok, const char* who);
@@ -273,6 +286,7 @@ int launch_extprod_ntt(rtfhe_ctx* ctx, const int32_t* d_idx, const uint32_t* d_i
 // ---- split-FFT exact backend (rtfhe_dispatch_xfft.hip) ----
 int prime_xfft_kernels(rtfhe_ctx* ctx);
 int xfft_prepare(rtfhe_ctx* ctx);                                         // table + split key spectra on first use
+int xfft_table_ensure(rtfhe_ctx* ctx);                                    // the table alone (d_xtw), built if absent: what a plain set needs of this backend
 int launch_bootstrap_xfft(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s);
 int launch_extprod_xfft(rtfhe_ctx* ctx, const int32_t* d_idx, const uint32_t* d_in, uint32_t* d_out, int32_t count, hipStream_t s);
 // tables / derived keys of whichever exact backend is selected (no-op on the mirror): allocates and synchronises, so outside stream captures only

@@ -499,6 +499,43 @@ class Engine:
         self._ck(self.L.rtfhe_trlwe_extract_lvl1_batch_dev(self.h, self._dev(d_trlwe), int(P), _ptr(self._coef_arg(coef, P)), int(stride), self._dev(d_out),
                                                            count, C.c_void_p(stream) if stream else None))
 
+    # ---- exact TRLWE x plain-polynomial products (include/rtfhe.h: rtfhe_plain_create, rtfhe_trlwe_mul_plain_batch[_dev]) --------------------------
+    def plain_polys(self, w):
+        """Transforms integer polynomials int32[n_w][N] once and keeps them as spectra on the primary device; a PlainPolys handle (.n polynomials,
+        .wmax = the largest l1 norm among them), closed by close() or a with block.  Needs no key."""
+        return PlainPolys(self, w)
+
+    def _term_idx(self, idx, count, K):
+        return None if idx is None else _np(idx, np.int32).reshape(count, K)
+
+    def trlwe_mul_plain_batch(self, pp, x, K=1, w_idx=None, x_idx=None, acc=None):
+        """out[g] = (acc[g] if acc is given else 0) + sum_{k < K} pp[w_idx[g][k]] * x[x_idx[g][k]] in Z_2^32[X]/(X^N + 1), on both polynomials of
+        every TRLWE row: u32[count][2][N], exact word for word.  x: u32[n_x][2][N].  w_idx None: polynomial k for every g; x_idx None: row
+        g * K + k.  count comes from an index array or acc when one is given, else it is n_x // K.  A call is accepted iff
+        K * pp.wmax <= 192 N and 1 <= K <= 8.  Arguments are checked here: a bad one raises RtfheError before anything runs."""
+        x = _np(x, np.uint32).reshape(-1, 2, self.p.N)
+        K = int(K)
+        Kd = K if K > 0 else 1
+        if w_idx is not None:
+            count = np.asarray(w_idx).size // Kd
+        elif x_idx is not None:
+            count = np.asarray(x_idx).size // Kd
+        elif acc is not None:
+            count = np.asarray(acc).size // (2 * self.p.N)
+        else:
+            count = x.shape[0] // Kd
+        wi, xi = self._term_idx(w_idx, count, Kd), self._term_idx(x_idx, count, Kd)
+        out = np.array(_np(acc, np.uint32).reshape(count, 2, self.p.N)) if acc is not None else np.empty((count, 2, self.p.N), np.uint32)
+        self._ck(self.L.rtfhe_trlwe_mul_plain_batch(self.h, pp.h, _ptr(wi), _ptr(x), x.shape[0], _ptr(xi), K, 1 if acc is not None else 0, _ptr(out), count))
+        return out
+
+    def trlwe_mul_plain_batch_dev(self, pp, d_x, n_x, d_out, count, K=1, d_w_idx=None, d_x_idx=None, accumulate=False, stream=None):
+        """... on device buffers (d_x: [n_x][2][N] words, d_out: [count][2][N] words, not overlapping; d_w_idx / d_x_idx: int32[count][K] on the
+        device), asynchronous on `stream`; accumulate adds into d_out.  A sample with a bad index is skipped, its output row untouched, and the
+        next sync() raises.  One launch, nothing allocated: it may be captured first thing on a fresh stream."""
+        self._ck(self.L.rtfhe_trlwe_mul_plain_batch_dev(self.h, pp.h, self._dev(d_w_idx), self._dev(d_x), int(n_x), self._dev(d_x_idx), int(K),
+                                                        1 if accumulate else 0, self._dev(d_out), count, C.c_void_p(stream) if stream else None))
+
     # ---- stage level ------------------------------------------------------------------------
     def blind_rotate_batch(self, tlwe, steps=None):
         tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)
@@ -669,6 +706,37 @@ class PackingKey:
     def close(self):
         if getattr(self, "h", None):
             self.engine.L.rtfhe_packing_key_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PlainPolys:
+    """Integer polynomials on an Engine's primary device (rtfhe_plain), kept as spectra: the plain operand of Engine.trlwe_mul_plain_batch[_dev].
+    Closing it frees the device copy; one whose Engine was closed first only frees its handle."""
+
+    def __init__(self, engine, w):
+        w = _np(w, np.int32).reshape(-1, engine.p.N)
+        self.engine = engine
+        self.n = w.shape[0]
+        self.wmax = int(np.abs(w.astype(np.int64)).sum(axis=1).max()) if self.n else 0
+        h = C.c_void_p()
+        engine._ck(engine.L.rtfhe_plain_create(engine.h, _ptr(w), self.n, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.engine.L.rtfhe_plain_destroy(self.h)
             self.h = None
 
     def __enter__(self):
