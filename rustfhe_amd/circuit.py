@@ -10,6 +10,7 @@ instances of the circuit at once ("replicas") so that waves are wide enough to f
 import numpy as np
 
 from ._ffi import AND, ANDNY, COPY, NAND, NOT, OR, XOR
+from .engine import _Handle
 
 _NAMES = {NAND: "nand", AND: "and", OR: "or", XOR: "xor", NOT: "not", COPY: "copy", ANDNY: "andny"}
 
@@ -278,13 +279,15 @@ def prefix_adder(nbits=8, nand_only=False):
 
 # ---- execution on the engine ------------------------------------------------------------------------
 
-class CircuitRunner:
+class CircuitRunner(_Handle):
     """Runs `replicas` independent instances of a netlist on one Engine; every dependency wave is one launch of
     replicas * wave_size gates.  Wire table: int32[replicas * num_wires][n + 1] resident in HBM."""
+    _slot = "_circuit"      # the recorded graph, once run(graph=True) has made it
 
     def __init__(self, engine, net, replicas=1):
         import torch
         self.e, self.net, self.R = engine, net, replicas
+        self._destroy = engine.circuit_destroy
         self.n1 = engine.p.n + 1
         W = net.num_wires
         base = 2 + net.num_inputs
@@ -334,17 +337,6 @@ class CircuitRunner:
                 self.e.circuit_wave_dev(ops, i0, i1, io, self.wires, self.R * self.net.num_wires, cnt, st)
         self.e.sync(st)
         return self
-
-    def close(self):
-        if getattr(self, "_circuit", None) is not None:
-            self.e.circuit_destroy(self._circuit)
-            self._circuit = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def outputs(self):
         """uint32[replicas][num_outputs][n+1]."""

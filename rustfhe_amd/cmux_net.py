@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
+from .engine import _Handle
 
 
 class CmuxNetlist:
@@ -194,7 +195,7 @@ def bdd_netlist(n_vars, fn_or_truth_tables, order=None, true_row=0, false_row=1)
     return net
 
 
-class CmuxCircuit:
+class CmuxCircuit(_Handle):
     """A recorded CMUX netlist on an Engine (Engine.cmux_circuit): launch(stream) replays it, close() frees it.  It keeps the device arrays it
     was recorded on alive.  rounded: None records the engine's leveled decomposition in force (Engine.set_leveled_decomposition); True / False
     set it around the recording and restore it after.  The circuit replays in the mode it was recorded in."""
@@ -202,6 +203,7 @@ class CmuxCircuit:
     def __init__(self, engine, netlist, sel, lut, d_out, count, d_sel_idx=None, d_row0=None, rounded=None):
         a = netlist.arrays(engine.p.N)
         self.engine, self.netlist, self.count = engine, netlist, int(count)
+        self._destroy = engine.circuit_destroy
         self._keep = (sel, d_out, d_sel_idx, d_row0)
         ptr =lambda v: None if v is None else C.c_void_p(v.ctypes.data)  # noqa: E731
         h = C.c_void_p()
@@ -223,20 +225,3 @@ class CmuxCircuit:
     def launch(self, stream=None):
         """One replay, asynchronous on `stream`; a replica with a bad device-resident index is skipped and the next Engine.sync raises."""
         self.engine.circuit_launch(self.h, stream)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.engine.circuit_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -1,5 +1,5 @@
 // rtfhe_batch.hip -- batches of gates on one device: the backend switch, the allocation rules around stream captures, device-pointer and
-// host-pointer batches, MUX, synchronisation and the timers bench.py reads.
+// host-pointer batches, MUX, the programmable-bootstrap entry points (their tables: rtfhe_lut.hip), synchronisation and the timers bench.py reads.
 #include "rtfhe_host.hpp"
 
 using namespace rtfhe;
@@ -215,8 +215,7 @@ int rtfhe_gate_batch_dev(rtfhe_ctx* ctx, int op, const void* d_in0, const void* 
     if (int rc = use(ctx)) return rc;
     if (op < RTFHE_NAND || op > RTFHE_ANDNY) return fail(ctx, RTFHE_ERR_INVALID, "unknown gate");
     if (!d_in0 || !d_out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    if (!gpu_accessible(ctx, d_in0) || (d_in1 && !gpu_accessible(ctx, d_in1)) || !gpu_accessible(ctx, d_out))
-        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_gate_batch_dev needs device pointers (got memory the GPU cannot address)");
+    if (int rc = device_pointers(ctx, "rtfhe_gate_batch_dev", {d_in0, d_out}, {d_in1})) return rc;
     if (!ctx->peers.empty()) return sharded_dev_batch(ctx, op, nullptr, d_in0, d_in1, d_out, count, (hipStream_t)stream);
     return launch_bootstrap(ctx, op, MODE_GATE, ctx->p.n, d_in0, d_in1, d_out, count, (hipStream_t)stream);
 }
@@ -228,8 +227,7 @@ int rtfhe_bootstrap_batch_dev(rtfhe_ctx* ctx, const void* d_tlwe, void* d_out, s
 int rtfhe_mux_batch_dev(rtfhe_ctx* ctx, const void* d_c, const void* d_in0, const void* d_in1, void* d_out, size_t count, void* stream) {
     if (int rc = use(ctx)) return rc;
     if (!d_c || !d_in0 || !d_in1 || !d_out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    if (!gpu_accessible(ctx, d_c) || !gpu_accessible(ctx, d_in0) || !gpu_accessible(ctx, d_in1) || !gpu_accessible(ctx, d_out))
-        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_mux_batch_dev needs device pointers (got memory the GPU cannot address)");
+    if (int rc = device_pointers(ctx, "rtfhe_mux_batch_dev", {d_c, d_in0, d_in1, d_out})) return rc;
     if (!ctx->has_bk) return fail(ctx, RTFHE_ERR_STATE, "bootstrapping key not loaded");
     if (!ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "key-switching key not loaded");
     if (count > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "count too large");
@@ -237,70 +235,11 @@ int rtfhe_mux_batch_dev(rtfhe_ctx* ctx, const void* d_c, const void* d_in0, cons
     return mux_dev_one(ctx, d_c, d_in0, d_in1, d_out, count, (hipStream_t)stream);
 }
 
-// ---- programmable bootstrapping (include/rtfhe.h) ----
-// the rows of a table (plain: [n_lut][N] test polynomials; encrypted: [n_lut][2][N] TRLWEs) uploaded to every entry of the context
-static int lut_upload(rtfhe_ctx* ctx, const uint32_t* tv, int32_t n_lut, bool encrypted, rtfhe_lut** out) {
-    *out = nullptr;
-    const size_t bytes = (size_t)n_lut * ctx->p.N * (encrypted ? 2 : 1) * 4;
-    rtfhe_lut* lut = new rtfhe_lut();
-    lut->n_lut = n_lut;
-    lut->encrypted = encrypted;
-    const int entries = 1 + (int)ctx->peers.size();
-    int rc = 0;
-    for (int d = 0; d < entries && !rc; d++) {
-        rtfhe_ctx* c = d ? ctx->peers[d - 1] : ctx;
-        void* p = nullptr;
-        rc = use(c);
-        if (!rc && hipMalloc(&p, bytes) != hipSuccess) rc = fail(c, RTFHE_ERR_HIP, "rtfhe_lut_create: hipMalloc");
-        if (p) lut->d_tv.push_back((uint32_t*)p);
-        if (!rc && hipMemcpy(p, tv, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, RTFHE_ERR_HIP, "rtfhe_lut_create: hipMemcpy");
-        if (rc && c != ctx) rc = fail(ctx, rc, "device " + std::to_string(c->device) + ": " + c->err);
-    }
-    (void)hipSetDevice(ctx->device);
-    if (rc) {
-        (void)hipGetLastError();
-        for (size_t d = 0; d < lut->d_tv.size(); d++) {
-            (void)hipSetDevice(d ? ctx->peers[d - 1]->device : ctx->device);
-            (void)hipFree(lut->d_tv[d]);
-        }
-        (void)hipSetDevice(ctx->device);
-        delete lut;
-        return rc;
-    }
-    lut->ctx = ctx;
-    ctx->luts.push_back(lut);
-    *out = lut;
-    return 0;
-}
-
-int rtfhe_lut_create(rtfhe_ctx* ctx, const uint32_t* tv, int32_t n_lut, rtfhe_lut** out) {
-    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
-    if (!tv || !out || n_lut < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_create: null argument or n_lut < 1");
-    return lut_upload(ctx, tv, n_lut, false, out);
-}
-
-int rtfhe_lut_create_encrypted(rtfhe_ctx* ctx, const uint32_t* trlwe, int32_t n_lut, rtfhe_lut** out) {
-    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
-    if (!trlwe || !out || n_lut < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_create_encrypted: null argument or n_lut < 1");
-    return lut_upload(ctx, trlwe, n_lut, true, out);
-}
-
-void rtfhe_lut_destroy(rtfhe_lut* lut) {
-    if (!lut) return;
-    if (rtfhe_ctx* ctx = lut->ctx) {     // still attached (a context destroyed first has already freed the tables and detached us)
-        auto& v = ctx->luts;
-        for (size_t i = 0; i < v.size(); i++) if (v[i] == lut) { v.erase(v.begin() + i); break; }
-        rtfhe_host::lut_release(lut);
-    }
-    delete lut;
-}
-
+// ---- programmable bootstrapping (include/rtfhe.h; the tables themselves: rtfhe_lut.hip) ----
 // what both PBS entries check before anything is launched
 static int pbs_ready(rtfhe_ctx* ctx, const rtfhe_lut* lut) {
     if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
-    if (!lut) return fail(ctx, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
-    if (!lut->ctx) return fail(ctx, RTFHE_ERR_STATE, "the table's context has been destroyed");
-    if (lut->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the table belongs to another context");
+    if (int rc = handles_ready(ctx, {ref(lut)})) return rc;
     if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
         return fail(ctx, RTFHE_ERR_INVALID, "programmable bootstrapping runs on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR); "
                                             "select it with rtfhe_set_backend");
@@ -324,8 +263,7 @@ int rtfhe_pbs_batch_dev(rtfhe_ctx* ctx, const rtfhe_lut* lut, const void* d_lut_
     if (int rc = pbs_ready(ctx, lut)) return rc;
     if (int rc = use(ctx)) return rc;
     if (!d_tlwe || !d_out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    if (!gpu_accessible(ctx, d_tlwe) || !gpu_accessible(ctx, d_out) || (d_lut_idx && !gpu_accessible(ctx, d_lut_idx)))
-        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_pbs_batch_dev needs device pointers (got memory the GPU cannot address)");
+    if (int rc = device_pointers(ctx, "rtfhe_pbs_batch_dev", {d_tlwe, d_out}, {d_lut_idx})) return rc;
     if (count > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "count too large");
     if (pbs_shift(ctx, lut) == 0) {      // the many-LUT path with one output (MODE_EXTRACT, then the batch key switch): its capture rule applies
         if (!ctx->peers.empty())
@@ -365,8 +303,7 @@ int rtfhe_pbs_many_batch_dev(rtfhe_ctx* ctx, const rtfhe_lut* lut, int32_t n_out
     int32_t shift = 0;
     if (int rc = many_shift(ctx, n_out, &shift)) return rc;
     if (!d_tlwe || !d_out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    if (!gpu_accessible(ctx, d_tlwe) || !gpu_accessible(ctx, d_out) || (d_lut_idx && !gpu_accessible(ctx, d_lut_idx)))
-        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_pbs_many_batch_dev needs device pointers (got memory the GPU cannot address)");
+    if (int rc = device_pointers(ctx, "rtfhe_pbs_many_batch_dev", {d_tlwe, d_out}, {d_lut_idx})) return rc;
     if (count > ((size_t)0x7fffffff >> shift)) return fail(ctx, RTFHE_ERR_INVALID, "count too large");
     if (!ctx->peers.empty())
         return sharded_dev_batch(ctx, RTFHE_COPY, nullptr, d_tlwe, nullptr, d_out, count, (hipStream_t)stream, lut, (const int32_t*)d_lut_idx, shift);

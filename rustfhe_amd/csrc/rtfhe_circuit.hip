@@ -70,8 +70,7 @@ int rtfhe_circuit_wave_dev(rtfhe_ctx* ctx, const void* d_ops, const void* d_idx0
     if (int rc = use(ctx)) return rc;
     if (!d_ops || !d_idx0 || !d_idx1 || !d_idx_out || !d_wires) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
     if (num_wires == 0 || num_wires > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "num_wires out of range");
-    if (!gpu_accessible(ctx, d_ops) || !gpu_accessible(ctx, d_idx0) || !gpu_accessible(ctx, d_idx1) || !gpu_accessible(ctx, d_idx_out) || !gpu_accessible(ctx, d_wires))
-        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_circuit_wave_dev needs device pointers (got memory the GPU cannot address)");
+    if (int rc = device_pointers(ctx, "rtfhe_circuit_wave_dev", {d_ops, d_idx0, d_idx1, d_idx_out, d_wires})) return rc;
     return launch_bootstrap(ctx, RTFHE_COPY, MODE_GATE, ctx->p.n, d_wires, d_wires, d_wires, count, (hipStream_t)stream,
                             (const int32_t*)d_ops, (const int32_t*)d_idx0, (const int32_t*)d_idx1, (const int32_t*)d_idx_out,
                             (int32_t)num_wires);
@@ -88,8 +87,7 @@ int rtfhe_circuit_create(rtfhe_ctx* ctx, const void* d_ops, const void* d_idx0, 
     for (int32_t w = 0; w < num_waves; w++)
         if (wave_offsets[w] < 0 || wave_offsets[w + 1] <= wave_offsets[w]) return fail(ctx, RTFHE_ERR_INVALID, "wave_offsets must be strictly increasing from >= 0");
     if (!ctx->has_bk || !ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "keys not loaded");
-    if (!gpu_accessible(ctx, d_ops) || !gpu_accessible(ctx, d_idx0) || !gpu_accessible(ctx, d_idx1) || !gpu_accessible(ctx, d_idx_out) || !gpu_accessible(ctx, d_wires))
-        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_circuit_create needs device pointers (got memory the GPU cannot address)");
+    if (int rc = device_pointers(ctx, "rtfhe_circuit_create", {d_ops, d_idx0, d_idx1, d_idx_out, d_wires})) return rc;
     if (int rc = backend_prepare(ctx)) return rc;          // nothing but kernel launches may happen inside the capture
     for (int32_t w = 0; w < num_waves; w++)                // ... so the key layouts the waves' dispatches read are built now
         if (int rc = ensure_bk_layouts(ctx, (size_t)(wave_offsets[w + 1] - wave_offsets[w]), MODE_GATE)) return rc;
@@ -135,9 +133,7 @@ int rtfhe_lut_circuit_create(rtfhe_ctx* ctx, const rtfhe_lut* lut, int32_t fan_i
     if (int rc = use(ctx)) return rc;
     if (!out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (!lut) return fail(ctx, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
-    if (!lut->ctx) return fail(ctx, RTFHE_ERR_STATE, "the table's context has been destroyed");
-    if (lut->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the table belongs to another context");
+    if (int rc = handles_ready(ctx, {ref(lut)})) return rc;
     if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
         return fail(ctx, RTFHE_ERR_INVALID, "LUT circuits (programmable bootstrapping) run on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR); "
                                             "select it with rtfhe_set_backend");
@@ -181,7 +177,7 @@ int rtfhe_lut_circuit_create(rtfhe_ctx* ctx, const rtfhe_lut* lut, int32_t fan_i
         }
     }
     if (!ctx->has_bk || !ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "keys not loaded");
-    if (!gpu_accessible(ctx, d_wires)) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_circuit_create needs a device pointer for the wire table");
+    if (int rc = device_pointers(ctx, "rtfhe_lut_circuit_create", {d_wires})) return rc;
     // everything that allocates or synchronises happens now, outside the capture: the key layouts the waves' dispatches read, the sample buffer,
     // the circuit's own copies of the description and the table rows, the gathered inputs and the key-switched outputs
     for (int32_t w = 0; w < num_waves; w++)
@@ -274,9 +270,8 @@ int rtfhe_circuit_launch(rtfhe_circuit* c, void* stream) {
 
 void rtfhe_circuit_destroy(rtfhe_circuit* c) {
     if (!c) return;
-    if (c->ctx) {      // still attached: unregister (a context destroyed first has already released the graph and detached us)
-        auto& v = c->ctx->circuits;
-        for (size_t i = 0; i < v.size(); i++) if (v[i] == c) { v.erase(v.begin() + i); break; }
+    if (c->ctx) {      // still attached
+        detach(c->ctx->circuits, c);
         circuit_release(c);
     }
     delete c;

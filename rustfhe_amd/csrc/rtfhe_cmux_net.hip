@@ -47,8 +47,7 @@ int rtfhe_cmux_circuit_create(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const rtfh
     const bool extract = out_coef != nullptr;
     if (extract && !ctx->has_ksk) return fail(ctx, RTFHE_ERR_STATE, "key-switching key not loaded");
     if (int rc = use(ctx)) return rc;
-    if (!gpu_accessible(ctx, d_out) || (d_sel_idx && !gpu_accessible(ctx, d_sel_idx)) || (d_row0 && !gpu_accessible(ctx, d_row0)))
-        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_cmux_circuit_create needs device pointers (got memory the GPU cannot address)");
+    if (int rc = device_pointers(ctx, "rtfhe_cmux_circuit_create", {d_out}, {d_sel_idx, d_row0})) return rc;
     // everything that allocates or synchronises happens now, outside the capture
     const LeveledTwins<CmuxNetArgs> net = net_twins(ctx);
     if (int rc = prime_leveled(ctx, net)) return rc;
@@ -125,9 +124,8 @@ int rtfhe_cmux_circuit_create(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const rtfh
 
 // rtfhe_trgsw_create's conversion of selectors [first, first + n) of a live set, in place and synchronous
 int rtfhe_trgsw_update(rtfhe_trgsw* sel, const uint32_t* trgsw, int32_t first, int32_t n) {
-    if (!sel) return fail(nullptr, RTFHE_ERR_INVALID, "null selector set (rtfhe_trgsw)");
-    rtfhe_ctx* ctx = sel->ctx;
-    if (!ctx) return fail(nullptr, RTFHE_ERR_STATE, "the context of the selector set has been destroyed");
+    rtfhe_ctx* ctx = sel ? sel->ctx : nullptr;
+    if (int rc = handles_ready(ctx, {ref(sel)})) return rc;
     if (!trgsw) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
     if (first < 0 || n < 1 || (long long)first + n > sel->n_sel)
         return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_update: selectors [" + std::to_string(first) + ", " + std::to_string((long long)first + n) +

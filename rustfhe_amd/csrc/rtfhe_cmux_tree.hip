@@ -5,7 +5,7 @@
 // Beside it the TRGSW blind rotation (rtfhe_trgsw_rotate_batch[_dev], rtfhe_trgsw_rotate_extract_batch[_dev]): the same selector sets, one
 // launch of k_trgsw_rotate for all steps of all lookups, the same key switch behind the extract form.
 // And the tree run backwards, the CMUX demultiplexer (rtfhe_demux_tree_batch[_dev]): one launch of k_demux_tree per level through the same
-// ping-pong buffers, with rtfhe_lut_accumulate_dev (k_trlwe_accumulate) adding the leaves into an encrypted table's rows.
+// ping-pong buffers.  (Its leaves go into an encrypted table's rows through rtfhe_lut_accumulate_dev, rtfhe_lut.hip.)
 #include "rtfhe_host.hpp"
 
 #include <cstdlib>
@@ -44,16 +44,6 @@ int sel_idx_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, int32_t depth, size_t 
                 if ((uint32_t)host_sel_idx[g * depth + k] >= (uint32_t)sel->n_sel)
                     return fail(ctx, RTFHE_ERR_INVALID, "lookup " + std::to_string(g) + ": sel_idx[" + std::to_string(k) + "] = " + std::to_string(host_sel_idx[g * depth + k]) +
                                                         " is outside [0, " + std::to_string(n_sel) + ")");
-    return 0;
-}
-
-// host-pointer forms: sel_idx [count][depth] rides in the staging buffer d_a (null stays null: the kernels then number the selectors themselves)
-int stage_sel_idx(rtfhe_ctx* ctx, const int32_t* sel_idx, size_t count, int32_t depth, const int32_t*& d_sel_idx) {
-    d_sel_idx = nullptr;
-    if (!sel_idx) return 0;
-    if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, count * depth * 4)) return rc;
-    if (int rc = copy_in(ctx, ctx->d_a, sel_idx, count * depth * 4, 0)) return rc;
-    d_sel_idx = (const int32_t*)ctx->d_a;
     return 0;
 }
 
@@ -126,9 +116,7 @@ int tree_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int3
              void* d_out, size_t count, bool extract, void* stream, const char* name) {
     if (int rc = tree_ready(ctx, sel, lut, depth, count, d_sel_idx != nullptr, d_row0 != nullptr, nullptr, nullptr, nullptr, d_out, extract)) return rc;
     if (int rc = use(ctx)) return rc;
-    if (!gpu_accessible(ctx, d_out) || (d_sel_idx && !gpu_accessible(ctx, d_sel_idx)) || (d_row0 && !gpu_accessible(ctx, d_row0)) ||
-        (d_coef && !gpu_accessible(ctx, d_coef)))
-        return fail(ctx, RTFHE_ERR_INVALID, std::string(name) + " needs device pointers (got memory the GPU cannot address)");
+    if (int rc = device_pointers(ctx, name, {d_out}, {d_sel_idx, d_row0, d_coef})) return rc;
     return launch_tree(ctx, sel, (const int32_t*)d_sel_idx, depth, lut, (const int32_t*)d_row0, (const int32_t*)d_coef, d_out, count, extract, (hipStream_t)stream);
 }
 
@@ -140,17 +128,10 @@ int tree_host(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, in
     if (count == 0) return 0;
     const size_t out_bytes = count * (extract ? (size_t)ctx->p.n + 1 : (size_t)2 * ctx->p.N) * 4;
     if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
-    const int32_t *d_sel_idx = nullptr, *d_row0 = nullptr, *d_coef = nullptr;
-    if (int rc = stage_sel_idx(ctx, sel_idx, count, depth, d_sel_idx)) return rc;
-    if (row0 || coef) {
-        if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, 2 * count * 4)) return rc;
-        if (row0) { HIPCHECK(ctx, hipMemcpyAsync(ctx->d_b, row0, count * 4, hipMemcpyHostToDevice, ctx->stream)); d_row0 = (const int32_t*)ctx->d_b; }
-        if (coef) {
-            HIPCHECK(ctx, hipMemcpyAsync((int32_t*)ctx->d_b + count, coef, count * 4, hipMemcpyHostToDevice, ctx->stream));
-            d_coef = (const int32_t*)ctx->d_b + count;
-        }
-    }
-    if (int rc = launch_tree(ctx, sel, d_sel_idx, depth, lut, d_row0, d_coef, ctx->d_c, count, extract, ctx->stream)) return rc;
+    StagedIdx d_sel, d_rows;
+    if (int rc = stage_idx(ctx, &ctx->d_a, &ctx->cap_a, count * depth, sel_idx, nullptr, d_sel)) return rc;
+    if (int rc = stage_idx(ctx, &ctx->d_b, &ctx->cap_b, count, row0, coef, d_rows)) return rc;
+    if (int rc = launch_tree(ctx, sel, d_sel.first, depth, lut, d_rows.first, d_rows.second, ctx->d_c, count, extract, ctx->stream)) return rc;
     return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
 }
 
@@ -235,8 +216,7 @@ int rotate_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, in
                bool extract, void* stream, const char* name) {
     if (int rc = rotate_ready(ctx, sel, depth, rot, count, d_sel_idx != nullptr, nullptr, d_trlwe, d_out, extract)) return rc;
     if (int rc = use(ctx)) return rc;
-    if (!gpu_accessible(ctx, d_out) || !gpu_accessible(ctx, d_trlwe) || (d_sel_idx && !gpu_accessible(ctx, d_sel_idx)))
-        return fail(ctx, RTFHE_ERR_INVALID, std::string(name) + " needs device pointers (got memory the GPU cannot address)");
+    if (int rc = device_pointers(ctx, name, {d_out, d_trlwe}, {d_sel_idx})) return rc;
     const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = extract ? count * ((size_t)ctx->p.n + 1) * 4 : in_bytes;
     if (d_out != d_trlwe ? overlaps(d_trlwe, in_bytes, d_out, out_bytes) : extract)
         return fail(ctx, RTFHE_ERR_INVALID, std::string(name) + ": d_out overlaps d_trlwe (it may only be exactly d_trlwe, in the form without extraction)");
@@ -252,10 +232,10 @@ int rotate_host(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, 
     const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = extract ? count * ((size_t)ctx->p.n + 1) * 4 : in_bytes;
     if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, in_bytes)) return rc;
     if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
-    const int32_t* d_sel_idx = nullptr;
-    if (int rc = stage_sel_idx(ctx, sel_idx, count, depth, d_sel_idx)) return rc;
+    StagedIdx d_sel;
+    if (int rc = stage_idx(ctx, &ctx->d_a, &ctx->cap_a, count * depth, sel_idx, nullptr, d_sel)) return rc;
     if (int rc = copy_in(ctx, ctx->d_b, trlwe, in_bytes, 1)) return rc;
-    if (int rc = launch_rotate(ctx, sel, d_sel_idx, depth, rot, ctx->d_b, ctx->d_c, count, extract, ctx->stream)) return rc;
+    if (int rc = launch_rotate(ctx, sel, d_sel.first, depth, rot, ctx->d_b, ctx->d_c, count, extract, ctx->stream)) return rc;
     return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
 }
 
@@ -265,13 +245,8 @@ namespace rtfhe_host {
 
 int selector_set_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, bool with_table, const rtfhe_lut* lut, bool args_ok, const char* who) {
     if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
-    if (!sel) return fail(ctx, RTFHE_ERR_INVALID, "null selector set (rtfhe_trgsw)");
-    if (with_table && !lut) return fail(ctx, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
+    if (int rc = with_table ? handles_ready(ctx, {ref(sel), ref(lut)}) : handles_ready(ctx, {ref(sel)})) return rc;
     if (!args_ok) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    if (!sel->ctx || (with_table && !lut->ctx))
-        return fail(ctx, RTFHE_ERR_STATE, with_table ? "the context of the selector set or of the table has been destroyed" : "the context of the selector set has been destroyed");
-    if (sel->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the selector set belongs to another context");
-    if (with_table && lut->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the table belongs to another context");
     if (ctx->backend != RTFHE_BACKEND_FFT64_MIRROR)
         return fail(ctx, RTFHE_ERR_INVALID, std::string(who) + " on the FP64 mirror backend only (RTFHE_BACKEND_FFT64_MIRROR); select it with rtfhe_set_backend");
     return 0;
@@ -304,7 +279,7 @@ int rtfhe_trgsw_create(rtfhe_ctx* ctx, const uint32_t* trgsw, int32_t n_sel, rtf
     t->ctx = ctx;
     int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, words * 4);
     if (!rc && hipMalloc((void**)&t->d_spec, words / 2 * sizeof(cplx)) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_trgsw_create: hipMalloc");
-    if (!rc && hipMemcpy(ctx->d_a, trgsw, words * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_trgsw_create: hipMemcpy");
+    if (!rc) rc = copy_in(ctx, ctx->d_a, trgsw, words * 4, 0);      // on the stream of the transform below, which is waited for
     if (!rc) rc = launch_fft(ctx, true, FftArgs{ctx->d_tw, ctx->d_a, t->d_spec, (int32_t)polys, 1, 2 * ctx->p.l, 0}, ctx->stream);
     if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_trgsw_create: hipStreamSynchronize");
     if (rc) {
@@ -320,9 +295,8 @@ int rtfhe_trgsw_create(rtfhe_ctx* ctx, const uint32_t* trgsw, int32_t n_sel, rtf
 
 void rtfhe_trgsw_destroy(rtfhe_trgsw* t) {
     if (!t) return;
-    if (rtfhe_ctx* ctx = t->ctx) {     // still attached (a context destroyed first has already freed the spectra and detached us)
-        auto& v = ctx->trgsws;
-        for (size_t i = 0; i < v.size(); i++) if (v[i] == t) { v.erase(v.begin() + i); break; }
+    if (rtfhe_ctx* ctx = t->ctx) {     // still attached
+        detach(ctx->trgsws, t);
         for (rtfhe_circuit* c : ctx->circuits) if (c->sel == t) { c->sel = nullptr; c->sel_gone = true; }      // CMUX netlists recorded on this set
         trgsw_release(t);
     }
@@ -357,10 +331,10 @@ int rtfhe_demux_tree_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t
     const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = in_bytes << depth;
     if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, in_bytes)) return rc;
     if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
-    const int32_t* d_sel_idx = nullptr;
-    if (int rc = stage_sel_idx(ctx, sel_idx, count, depth, d_sel_idx)) return rc;
+    StagedIdx d_sel;
+    if (int rc = stage_idx(ctx, &ctx->d_a, &ctx->cap_a, count * depth, sel_idx, nullptr, d_sel)) return rc;
     if (int rc = copy_in(ctx, ctx->d_b, x, in_bytes, 1)) return rc;
-    if (int rc = launch_demux(ctx, sel, d_sel_idx, depth, ctx->d_b, ctx->d_c, count, ctx->stream)) return rc;
+    if (int rc = launch_demux(ctx, sel, d_sel.first, depth, ctx->d_b, ctx->d_c, count, ctx->stream)) return rc;
     return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
 }
 
@@ -368,49 +342,11 @@ int rtfhe_demux_tree_batch_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const voi
                                void* stream) {
     if (int rc = demux_ready(ctx, sel, depth, count, d_sel_idx != nullptr, nullptr, d_x, d_out)) return rc;
     if (int rc = use(ctx)) return rc;
-    if (!gpu_accessible(ctx, d_out) || !gpu_accessible(ctx, d_x) || (d_sel_idx && !gpu_accessible(ctx, d_sel_idx)))
-        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_demux_tree_batch_dev needs device pointers (got memory the GPU cannot address)");
+    if (int rc = device_pointers(ctx, "rtfhe_demux_tree_batch_dev", {d_out, d_x}, {d_sel_idx})) return rc;
     const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = in_bytes << depth;
     if (overlaps(d_x, in_bytes, d_out, out_bytes))      // the last level stores leaves while other waves still read their nodes (depth 1: x itself)
         return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_demux_tree_batch_dev: d_out overlaps d_x");
     return launch_demux(ctx, sel, (const int32_t*)d_sel_idx, depth, d_x, d_out, count, (hipStream_t)stream);
-}
-
-int rtfhe_lut_accumulate_dev(rtfhe_lut* lut, const void* d_trlwe, int32_t first, int32_t n, size_t count, void* stream) {
-    if (!lut) return fail(nullptr, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
-    rtfhe_ctx* ctx = lut->ctx;
-    if (!ctx) return fail(nullptr, RTFHE_ERR_STATE, "the context of the table has been destroyed");
-    if (!d_trlwe) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    if (!lut->encrypted) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_accumulate_dev adds into the rows of an encrypted table (rtfhe_lut_create_encrypted); this one is plain");
-    if (!ctx->peers.empty()) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_accumulate_dev: a multi-device context holds one copy of the table per device; not supported");
-    if (first < 0 || n < 0 || (long long)first + n > lut->n_lut)
-        return fail(ctx, RTFHE_ERR_INVALID, "rows [" + std::to_string(first) + ", " + std::to_string((long long)first + n) + ") are outside the table's [0, " +
-                                            std::to_string(lut->n_lut) + ")");
-    if (count < 1 || count > (size_t)0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "count = " + std::to_string(count) + " is outside [1, 2^31)");
-    if (int rc = use(ctx)) return rc;
-    if (!gpu_accessible(ctx, d_trlwe)) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_accumulate_dev needs a device pointer (got memory the GPU cannot address)");
-    if (n == 0) return 0;
-    const size_t row = 2 * (size_t)ctx->p.N;
-    TrlweAccumulateArgs a{lut->d_tv[0] + (size_t)first * row, (const uint32_t*)d_trlwe, (size_t)n * row, (int32_t)count};
-    return launch_kernel(ctx, k_trlwe_accumulate, dim3((unsigned)((a.words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-}
-
-int rtfhe_lut_read_dev(const rtfhe_lut* lut, void* d_out, int32_t first, int32_t n, void* stream) {
-    if (!lut) return fail(nullptr, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
-    rtfhe_ctx* ctx = lut->ctx;
-    if (!ctx) return fail(nullptr, RTFHE_ERR_STATE, "the context of the table has been destroyed");
-    if (!d_out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    if (!lut->encrypted) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_read_dev copies the rows of an encrypted table (rtfhe_lut_create_encrypted); this one is plain");
-    if (!ctx->peers.empty()) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_read_dev: a multi-device context holds one copy of the table per device; not supported");
-    if (first < 0 || n < 0 || (long long)first + n > lut->n_lut)
-        return fail(ctx, RTFHE_ERR_INVALID, "rows [" + std::to_string(first) + ", " + std::to_string((long long)first + n) + ") are outside the table's [0, " +
-                                            std::to_string(lut->n_lut) + ")");
-    if (int rc = use(ctx)) return rc;
-    if (!gpu_accessible(ctx, d_out)) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_read_dev needs a device pointer (got memory the GPU cannot address)");
-    if (n == 0) return 0;
-    const size_t row = 2 * (size_t)ctx->p.N;
-    HIPCHECK(ctx, hipMemcpyAsync(d_out, lut->d_tv[0] + (size_t)first * row, (size_t)n * row * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return 0;
 }
 
 int rtfhe_trgsw_rotate_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, int32_t depth, const int32_t* rot, const uint32_t* trlwe,

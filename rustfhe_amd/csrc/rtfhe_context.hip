@@ -1,5 +1,6 @@
-// rtfhe_context.hip -- contexts: creation and teardown, error plumbing, device buffers and copies, twiddle-table calls, keys (loading, the
-// second layouts built on demand, the device footprint).
+// rtfhe_context.hip -- contexts: creation and teardown, error plumbing, the checks every entry point shares (handle ownership, device
+// pointers), device buffers, copies and staged index arrays, twiddle-table calls, keys (loading, the second layouts built on demand, the device
+// footprint).
 #include "rtfhe_host.hpp"
 
 #include <cmath>
@@ -66,14 +67,14 @@ int ensure(rtfhe_ctx* ctx, void** ptr, size_t* cap, size_t bytes) {
     return 0;
 }
 
-void lut_release(rtfhe_lut* lut) {
-    rtfhe_ctx* ctx = lut->ctx;
-    for (size_t d = 0; d < lut->d_tv.size(); d++) {
-        (void)hipSetDevice(d ? ctx->peers[d - 1]->device : ctx->device);
-        (void)hipFree(lut->d_tv[d]);
-    }
-    lut->d_tv.clear();
-    (void)hipSetDevice(ctx->device);
+int handles_ready(rtfhe_ctx* ctx, std::initializer_list<HandleRef> handles) {
+    for (const HandleRef& h : handles)
+        if (!h.given) return fail(ctx, RTFHE_ERR_INVALID, std::string("null ") + h.noun + " (" + h.type + ")");
+    for (const HandleRef& h : handles)
+        if (!h.owner) return fail(ctx, RTFHE_ERR_STATE, std::string("the context of the ") + h.noun + " has been destroyed");
+    for (const HandleRef& h : handles)
+        if (h.owner != ctx) return fail(ctx, RTFHE_ERR_INVALID, std::string("the ") + h.noun + " belongs to another context");
+    return 0;
 }
 
 int allow_lds_raw(rtfhe_ctx* ctx, const void* key, size_t bytes) {
@@ -105,7 +106,7 @@ int use(rtfhe_ctx* ctx) {
 // A *_dev entry point must never launch on a pointer the GPU cannot dereference (a host pointer passed by mistake would fault
 // the device): memory of the context's own device, managed and pinned-host allocations pass, memory of another GPU only with peer
 // access, anything else is refused before the launch.
-bool gpu_accessible(const rtfhe_ctx* ctx, const void* p) {
+static bool gpu_accessible(const rtfhe_ctx* ctx, const void* p) {
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
     if (a.type == hipMemoryTypeManaged || a.type == hipMemoryTypeHost) return true;
@@ -118,6 +119,13 @@ bool gpu_accessible(const rtfhe_ctx* ctx, const void* p) {
     if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) { (void)hipGetLastError(); return false; }
     (void)hipGetLastError();
     return true;
+}
+
+int device_pointers(rtfhe_ctx* ctx, const char* name, std::initializer_list<const void*> required, std::initializer_list<const void*> optional) {
+    bool ok = true;
+    for (const void* p : required) ok = ok && gpu_accessible(ctx, p);
+    for (const void* p : optional) ok = ok && (!p || gpu_accessible(ctx, p));
+    return ok ? 0 : fail(ctx, RTFHE_ERR_INVALID, std::string(name) + " needs device pointers (got memory the GPU cannot address)");
 }
 
 // true when `p` is host memory the GPU can DMA from directly (hipHostMalloc / hipHostRegister, e.g. rtfhe_host_alloc)
@@ -150,6 +158,16 @@ int copy_out(rtfhe_ctx* ctx, void* dst, const void* src, size_t bytes, int slot)
     }
     HIPCHECK(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int stage_idx(rtfhe_ctx* ctx, void** buf, size_t* cap, size_t words, const int32_t* first, const int32_t* second, StagedIdx& d) {
+    d = StagedIdx{};
+    if (!first && !second) return 0;
+    if (int rc = ensure(ctx, buf, cap, (second ? 2 : 1) * words * 4)) return rc;
+    int32_t* const base = (int32_t*)*buf;
+    if (first) { HIPCHECK(ctx, hipMemcpyAsync(base, first, words * 4, hipMemcpyHostToDevice, ctx->stream)); d.first = base; }
+    if (second) { HIPCHECK(ctx, hipMemcpyAsync(base + words, second, words * 4, hipMemcpyHostToDevice, ctx->stream)); d.second = base + words; }
     return 0;
 }
 
@@ -332,16 +350,12 @@ extern "C" int rtfhe_debug_read_wg_times(rtfhe_ctx* ctx, unsigned long long* out
 
 void rtfhe_ctx_destroy(rtfhe_ctx* ctx) {
     if (!ctx) return;
-    // tables that outlive their context: their device copies go now (while the peers' devices are still known), the handles stay valid
-    // for rtfhe_lut_destroy (which then only frees them) and the PBS calls (which then fail with RTFHE_ERR_STATE)
-    for (rtfhe_lut* l : ctx->luts) { lut_release(l); l->ctx = nullptr; }
-    ctx->luts.clear();
-    for (rtfhe_trgsw* t : ctx->trgsws) { trgsw_release(t); t->ctx = nullptr; }      // selector sets: the same rule
-    ctx->trgsws.clear();
-    for (rtfhe_packing_key* k : ctx->pack_keys) { packing_key_release(k); k->ctx = nullptr; }      // packing keys: the same rule
-    ctx->pack_keys.clear();
-    for (rtfhe_plain* w : ctx->plains) { plain_release(w); w->ctx = nullptr; }      // plain sets: the same rule
-    ctx->plains.clear();
+    // handles that outlive their context (the lifetime rule, rtfhe_host.hpp): their device memory goes now -- the tables' while the peers'
+    // devices are still known --, the handles stay valid for their destroy calls and every other call with them fails with RTFHE_ERR_STATE
+    orphan_all(ctx->luts, lut_release);
+    orphan_all(ctx->trgsws, trgsw_release);
+    orphan_all(ctx->pack_keys, packing_key_release);
+    orphan_all(ctx->plains, plain_release);
     for (rtfhe_ctx* peer : ctx->peers) rtfhe_ctx_destroy(peer);
     ctx->peers.clear();
     (void)hipSetDevice(ctx->device);

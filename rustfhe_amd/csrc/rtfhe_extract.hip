@@ -25,9 +25,10 @@ int extract_ready(rtfhe_ctx* ctx, const void* in, int32_t P, const int32_t* coef
     return 0;
 }
 
-template <int LOGN, bool TILED>
-void launch_extract_t(const TrlweExtractArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL((k_trlwe_extract<LOGN, TILED>), dim3((unsigned)(((size_t)a.M + 15) / 16)), dim3(64 * EXTRACT_WAVES), 0, s, a);
+template <int LOGN>
+int launch_extract_t(rtfhe_ctx* ctx, bool tiled, const TrlweExtractArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)(((size_t)a.M + 15) / 16)), block(64 * EXTRACT_WAVES);
+    return tiled ? launch_kernel(ctx, k_trlwe_extract<LOGN, true>, grid, block, 0, s, a) : launch_kernel(ctx, k_trlwe_extract<LOGN, false>, grid, block, 0, s, a);
 }
 
 // `count` TRLWEs of P samples each on device buffers, primary device, stream s.  d_trlwe: [count][2][N]; d_out: [count * P][N+1] (lvl1), else
@@ -49,10 +50,7 @@ int launch_extract(rtfhe_ctx* ctx, const void* d_trlwe, int32_t P, const std::ve
     for (int32_t p0 = 0; p0 < P; p0 += EXTRACT_COEF_MAX) {
         a.p0 = p0; a.np = P - p0 < EXTRACT_COEF_MAX ? P - p0 : EXTRACT_COEF_MAX;
         std::memcpy(a.coef, idx.data() + p0, (size_t)a.np * 4);
-        if (ctx->logn == 11) { if (lvl1) launch_extract_t<11, false>(a, s); else launch_extract_t<11, true>(a, s); }
-        else { if (lvl1) launch_extract_t<10, false>(a, s); else launch_extract_t<10, true>(a, s); }
-        HIPCHECK(ctx, hipGetLastError());
-        ctx->launches++;
+        if (int rc = ctx->logn == 11 ? launch_extract_t<11>(ctx, !lvl1, a, s) : launch_extract_t<10>(ctx, !lvl1, a, s)) return rc;
     }
     // identity_key_switch of the M samples, as the tree's extract form does it
     return lvl1 ? 0 : launch_key_switch_rows(ctx, samples->d[0], (uint32_t*)d_out, M, s);
@@ -64,8 +62,7 @@ int extract_dev(rtfhe_ctx* ctx, const void* d_trlwe, int32_t P, const int32_t* c
     if (int rc = extract_ready(ctx, d_trlwe, P, coef, stride, d_out, count, lvl1, idx)) return rc;
     if (int rc = use(ctx)) return rc;
     if (count == 0) return 0;
-    if (!gpu_accessible(ctx, d_out) || !gpu_accessible(ctx, d_trlwe))
-        return fail(ctx, RTFHE_ERR_INVALID, std::string(name) + " needs device pointers (got memory the GPU cannot address)");
+    if (int rc = device_pointers(ctx, name, {d_out, d_trlwe})) return rc;
     return launch_extract(ctx, d_trlwe, P, idx, d_out, count, lvl1, (hipStream_t)stream);
 }
 

@@ -1,17 +1,20 @@
 // rtfhe_host.hpp -- host-side internals shared by the translation units behind the C ABI (include/rtfhe.h):
-//   rtfhe_context.hip        contexts, keys (load / layouts on demand / footprint), twiddle-table calls, copies, error plumbing
+//   rtfhe_context.hip        contexts, keys (load / layouts on demand / footprint), twiddle-table calls, copies, error plumbing, the handle and
+//                            device-pointer checks of the entry points
 //   rtfhe_twiddles.hip       host twiddle tables (the reference's builders restated) and the per-kernel device tables
 //   rtfhe_dispatch_fft.hip   the FP64 mirror backend's bootstrap kernels: which kernel shape a batch runs on
 //   rtfhe_dispatch_ntt.hip   the exact-integer NTT backend: host tables, key transform, kernel shapes
 //   rtfhe_dispatch_xfft.hip  the split-FFT exact backend (exact products through an FMA-contracted FP64 FFT, N = 1024)
 //   rtfhe_stages.hip         stage-level kernels and entry points (transforms, external product, key switch, key permutes), FFT plans at any N
-//   rtfhe_batch.hip          batches of gates: the backend switch, split path, host-pointer and device-pointer batches, MUX, timers
+//   rtfhe_batch.hip          batches of gates: the backend switch, split path, host-pointer and device-pointer batches, MUX, PBS entry points, timers
+//   rtfhe_lut.hip            PBS tables (rtfhe_lut): creation on every entry of the context, release, and the three row calls of an encrypted
+//                            table (update, accumulate -- k_trlwe_accumulate --, read)
 //   rtfhe_circuit.hip        levelised netlists: one wave per call, or all waves recorded into a HIP graph
 //   rtfhe_multi.hip          one context over several GPUs: key replication, sharding of host batches and of device-resident batches
 //   rtfhe_cmux_tree.hip      CMUX-tree table lookup: selector sets (caller-supplied TRGSW samples), one launch per tree level; TRGSW blind rotation
-//                            and the CMUX demultiplexer tree with the accumulation of its leaves into an encrypted table's rows
+//                            and the CMUX demultiplexer tree
 //   rtfhe_cmux_net.hip       CMUX netlists: decision diagrams over a selector set, levelised (rtfhe_cmux_net_plan.cpp, host only) and recorded into a HIP graph
-//   rtfhe_pack.hip           packing key switch: packing keys (signed byte limbs in operand order), lvl0 samples into TRLWE rows, in-place table updates
+//   rtfhe_pack.hip           packing key switch: packing keys (signed byte limbs in operand order), lvl0 samples into TRLWE rows
 //   rtfhe_extract.hip        TRLWE sample extraction: chosen coefficients of existing TRLWEs as lvl1 samples or, through the extract tail, lvl0 ciphertexts
 //                            (its argument checks: rtfhe_extract_plan.cpp, host only)
 //   rtfhe_plain.hip          exact TRLWE x plain-polynomial products: plain sets (integer polynomials as spectra), sums of up to eight products per sample
@@ -26,6 +29,7 @@
 #include <climits>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -153,9 +157,14 @@ struct rtfhe_ctx {
     std::string err;
 };
 
+// The five handle types below hang on their context by one rule.  `ctx` points back at it and the context lists the live handles of each type.
+// A handle destroyed first detaches itself from that list (rtfhe_host::detach) and releases its device memory; a context destroyed first releases
+// the device memory of every listed handle and clears their `ctx` (rtfhe_host::orphan_all): the handle then only remains to be freed, and every
+// call made with it is refused by rtfhe_host::handles_ready.
+
 // a whole levelised netlist recorded into a HIP graph (rtfhe_circuit_create)
 struct rtfhe_circuit {
-    rtfhe_ctx* ctx = nullptr;  // null once the context has been destroyed (the handle then only remains to be freed)
+    rtfhe_ctx* ctx = nullptr;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     int device = 0;            // kept here: the context may be destroyed before the circuit
@@ -167,12 +176,12 @@ struct rtfhe_circuit {
     int backend = RTFHE_BACKEND_FFT64_MIRROR;   // the backend it was recorded on
     bool stale = false;        // recorded on an exact backend whose key form could not follow a key change (rebuild_derived_keys)
     const rtfhe_trgsw* sel = nullptr;   // a CMUX netlist (rtfhe_cmux_circuit_create): the selector set whose spectra its graph reads in place
-    bool sel_gone = false;     // ... and that set has been destroyed (rtfhe_trgsw_destroy): the graph holds freed addresses
+    bool sel_gone = false;     // ... and that set is gone (rtfhe_trgsw_destroy): the graph holds freed addresses
 };
 
 // the test polynomials of a programmable bootstrap (rtfhe_lut_create), one copy on every entry of the context
 struct rtfhe_lut {
-    rtfhe_ctx* ctx = nullptr;           // the primary; null once the context has been destroyed (the handle then only remains to be freed)
+    rtfhe_ctx* ctx = nullptr;           // the primary
     std::vector<uint32_t*> d_tv;        // [entry] u32[n_lut][N] on entry d of the context (0: the primary, d: peers[d - 1]); encrypted: [n_lut][2][N]
     int32_t n_lut = 0;
     bool encrypted = false;             // rtfhe_lut_create_encrypted: TRLWE rows (b, a), run by the k_pbs_enc_* kernels on the many-LUT path
@@ -180,21 +189,21 @@ struct rtfhe_lut {
 
 // a selector set of a CMUX tree (rtfhe_trgsw_create): caller-supplied TRGSW samples as spectra on the primary device
 struct rtfhe_trgsw {
-    rtfhe_ctx* ctx = nullptr;           // null once the context has been destroyed (the handle then only remains to be freed)
+    rtfhe_ctx* ctx = nullptr;
     rtfhe::cplx* d_spec = nullptr;      // [n_sel][2l][2][R][64], the layout of one bootstrapping-key entry each
     int32_t n_sel = 0;
 };
 
 // a packing key (rtfhe_packing_key_create): the key rows as signed byte limbs in i8-MFMA operand order on the primary device
 struct rtfhe_packing_key {
-    rtfhe_ctx* ctx = nullptr;           // null once the context has been destroyed (the handle then only remains to be freed)
+    rtfhe_ctx* ctx = nullptr;
     uint4* d_kmat = nullptr;            // [2N / 16 column groups][n16 / 2 K-steps][4 limbs][64 lanes] x 16 B (rtfhe_kernels_pack.hpp)
     int32_t n16 = 0, colgroups = 0;
 };
 
 // a plain set (rtfhe_plain_create): integer polynomials as spectra on the primary device, the small operand of rtfhe_trlwe_mul_plain_batch
 struct rtfhe_plain {
-    rtfhe_ctx* ctx = nullptr;           // null once the context has been destroyed (the handle then only remains to be freed)
+    rtfhe_ctx* ctx = nullptr;
     rtfhe::cplx* d_spec = nullptr;      // N = 1024: [n_w][512]; N = 2048: [n_w][2 halves][512] (rtfhe_kernels_plain.hpp)
     int32_t n_w = 0;
     int64_t wmax = 0;                   // max over the set of a polynomial's l1 norm: a call is accepted iff K * wmax <= 192 N
@@ -253,17 +262,45 @@ int ensure(rtfhe_ctx* ctx, void** ptr, size_t* cap, size_t bytes);        // gro
 int allow_lds_raw(rtfhe_ctx* ctx, const void* kernel, size_t bytes);      // raises the kernel's dynamic-LDS limit on this device once
 template <typename K>
 int allow_lds(rtfhe_ctx* ctx, K kernel, size_t bytes) { return allow_lds_raw(ctx, reinterpret_cast<const void*>(kernel), bytes); }
-bool gpu_accessible(const rtfhe_ctx* ctx, const void* p);                 // may a kernel on ctx->device dereference p?
 bool is_pinned_host(const void* p);
 int copy_in(rtfhe_ctx* ctx, void* dst, const void* src, size_t bytes, int slot);      // host -> device on ctx->stream
 int copy_out(rtfhe_ctx* ctx, void* dst, const void* src, size_t bytes, int slot);     // device -> host on ctx->stream, synchronous on return
+// what a *_dev entry point (and a circuit's creation) asks of its pointers before anything is launched: every `required` one and every non-null
+// `optional` one memory that a kernel on ctx->device may dereference, else RTFHE_ERR_INVALID "`name` needs device pointers ..."; nothing is allocated unless it refuses
+int device_pointers(rtfhe_ctx* ctx, const char* name, std::initializer_list<const void*> required, std::initializer_list<const void*> optional = {});
+// host-pointer forms: up to two optional host int32 arrays of `words` each staged back to back in the staging buffer *buf (d_a / d_b with its cap),
+// copied from the caller's memory on ctx->stream (not through the pinned slots); d: their device addresses, null where the input is null
+struct StagedIdx { const int32_t* first = nullptr; const int32_t* second = nullptr; };
+int stage_idx(rtfhe_ctx* ctx, void** buf, size_t* cap, size_t words, const int32_t* first, const int32_t* second, StagedIdx& d);
 void circuit_release(rtfhe_circuit* c);                                   // rtfhe_circuit.hip
-void lut_release(rtfhe_lut* lut);                                         // frees a table's device copies (rtfhe_context.hip)
+void lut_release(rtfhe_lut* lut);                                         // frees a table's device copies (rtfhe_lut.hip)
 void trgsw_release(rtfhe_trgsw* t);                                       // frees a selector set's spectra (rtfhe_cmux_tree.hip)
 void packing_key_release(rtfhe_packing_key* k);                           // frees a packing key's matrix (rtfhe_pack.hip)
 void plain_release(rtfhe_plain* w);                                       // frees a plain set's spectra (rtfhe_plain.hip)
+// ---- the lifetime rule of the handles (rtfhe_context.hip) ----
+// a handle as a call's check sees it: its noun and type name for the messages, whether the caller gave one, and the context it hangs on
+struct HandleRef { const char* noun; const char* type; bool given; const rtfhe_ctx* owner; };
+inline HandleRef ref(const rtfhe_lut* h) { return {"table", "rtfhe_lut", h != nullptr, h ? h->ctx : nullptr}; }
+inline HandleRef ref(const rtfhe_trgsw* h) { return {"selector set", "rtfhe_trgsw", h != nullptr, h ? h->ctx : nullptr}; }
+inline HandleRef ref(const rtfhe_packing_key* h) { return {"packing key", "rtfhe_packing_key", h != nullptr, h ? h->ctx : nullptr}; }
+inline HandleRef ref(const rtfhe_plain* h) { return {"plain set", "rtfhe_plain", h != nullptr, h ? h->ctx : nullptr}; }
+// The ownership check of the one or two handles of a call made on ctx (a call made through a handle alone passes that handle's own context,
+// null for a null handle): first every null one (RTFHE_ERR_INVALID "null NOUN (TYPE)"), then every one whose context is gone (RTFHE_ERR_STATE),
+// then every one of another context (RTFHE_ERR_INVALID).
+int handles_ready(rtfhe_ctx* ctx, std::initializer_list<HandleRef> handles);
+// a handle destroyed before its context leaves the context's list of live handles
+template <typename H>
+void detach(std::vector<H*>& live, H* h) {
+    for (size_t i = 0; i < live.size(); i++) if (live[i] == h) { live.erase(live.begin() + i); break; }
+}
+// a context destroyed before its handles: their device memory goes now, the handles stay valid for their destroy call, which then only frees them
+template <typename H>
+void orphan_all(std::vector<H*>& live, void (*release)(H*)) {
+    for (H* h : live) { release(h); h->ctx = nullptr; }
+    live.clear();
+}
 // what every entry point over a selector set checks first (rtfhe_cmux_tree.hip): the handles (lut only with_table), the caller's other pointers
-// (args_ok), live and own contexts, the mirror backend -- who: "the CMUX tree runs", for the message
+// (args_ok), the mirror backend -- who: "the CMUX tree runs", for the message
 int selector_set_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, bool with_table, const rtfhe_lut* lut, bool args_ok, const char* who);
 
 // ---- twiddles (rtfhe_twiddles.hip) ----

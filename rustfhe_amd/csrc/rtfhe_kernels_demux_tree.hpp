@@ -1,6 +1,6 @@
 // rtfhe_kernels_demux_tree.hpp -- CMUX demultiplexer tree: one TRLWE into leaf `addr` of 2^d, the address given as TRGSW-encrypted bits
-// (include/rtfhe.h: rtfhe_demux_tree_batch), and the wrapping sum of such leaves into the rows of an encrypted table
-// (rtfhe_lut_accumulate_dev).
+// (include/rtfhe.h: rtfhe_demux_tree_batch).  The wrapping sum of such leaves into the rows of an encrypted table (rtfhe_lut_accumulate_dev)
+// is the table unit's: rtfhe_kernels_lut.hpp.
 //
 // The tree of rtfhe_kernels_cmux_tree.hpp run backwards.  One launch per level over the nodes of that level of every lookup; a wave owns one
 // INPUT node and writes its two children:
@@ -77,22 +77,6 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_demux_tree(const DemuxTreeArg
         hi[c] = p;
         lo[c] = node[c] - p;
     }
-}
-
-struct TrlweAccumulateArgs {
-    uint32_t* rows;            // the table's rows [first, first + n): [n][2][N]
-    const uint32_t* src;       // [count][n][2][N]
-    size_t words;              // n * 2N
-    int32_t count;
-};
-
-// rows[w] += sum over g of src[g][w], wrapping: a thread per table word, plain vector loads and stores, no atomics (every word has one owner)
-__global__ __launch_bounds__(256) void k_trlwe_accumulate(const TrlweAccumulateArgs a) {
-    const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (w >= a.words) return;
-    uint32_t sum = a.rows[w];
-    for (int g = 0; g < a.count; g++) sum += a.src[(size_t)g * a.words + w];
-    a.rows[w] = sum;
 }
 
 }  // namespace rtfhe

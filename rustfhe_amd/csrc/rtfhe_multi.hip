@@ -94,7 +94,7 @@ int sharded_host_mux(rtfhe_ctx* ctx, const uint32_t* c, const uint32_t* in0, con
 // of a device at one workgroup per CU (__launch_bounds__(512, 1), LDS-full), and a copy KERNEL that still holds a CU when a bootstrap launch
 // starts makes one workgroup wait a whole round for it -- the send side of an RCCL send/recv pair has exactly that hazard on the root.  Without
 // peer access the runtime stages such a copy through host memory: still correct, and scatter_ms / gather_ms will show it.  Batch pointers that are
-// not device memory of the primary (pinned host, managed, another GPU's memory: all admitted by gpu_accessible) are copied with
+// not device memory of the primary (pinned host, managed, another GPU's memory: all admitted by device_pointers) are copied with
 // hipMemcpyAsync(hipMemcpyDefault) instead, which lets the runtime find out where they live.
 // Volumes are negligible next to the compute (config 3: 65,536 gates = 333 MB in, 167 MB out against 53 ms of bootstrapping per 8,192 gates).
 // Inside a stream capture on s the whole batch stays on the primary (the staging buffers of a peer are not the capture's to bake in).

@@ -1,6 +1,6 @@
-// rtfhe_pack.hip -- the packing key switch (include/rtfhe.h: rtfhe_packing_key_create, rtfhe_pack_batch[_dev], rtfhe_lut_update_dev): packing
-// keys as signed byte limbs in operand order (k_pkmat_build), the argument checks, the stream's buffer of key-switched samples and the rules
-// around stream captures, k_pack_ks_mm then k_pack_combine per call, and the stream-ordered rewrite of an encrypted table's rows.
+// rtfhe_pack.hip -- the packing key switch (include/rtfhe.h: rtfhe_packing_key_create, rtfhe_pack_batch[_dev]): packing keys as signed byte
+// limbs in operand order (k_pkmat_build), the argument checks, the stream's buffer of key-switched samples and the rules around stream
+// captures, k_pack_ks_mm then k_pack_combine per call.  (Its rows go into an encrypted table through rtfhe_lut_update_dev, rtfhe_lut.hip.)
 // Nothing here multiplies polynomials: the calls work on every backend and never read the bootstrapping key.
 #include "rtfhe_host.hpp"
 
@@ -15,10 +15,8 @@ namespace {
 int pack_ready(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const void* in, int32_t P, const int32_t* pos, int32_t rep, const void* out, size_t count,
                std::vector<int32_t>& shift) {
     if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
-    if (!pk) return fail(ctx, RTFHE_ERR_INVALID, "null packing key (rtfhe_packing_key)");
+    if (int rc = handles_ready(ctx, {ref(pk)})) return rc;
     if (!in || !out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    if (!pk->ctx) return fail(ctx, RTFHE_ERR_STATE, "the context of the packing key has been destroyed");
-    if (pk->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the packing key belongs to another context");
     const int N = ctx->p.N;
     if (P < 1 || P > N) return fail(ctx, RTFHE_ERR_INVALID, "P = " + std::to_string(P) + " is outside [1, " + std::to_string(N) + "]");
     if (rep < 1 || rep > N) return fail(ctx, RTFHE_ERR_INVALID, "rep = " + std::to_string(rep) + " is outside [1, " + std::to_string(N) + "]");
@@ -35,8 +33,8 @@ int pack_ready(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const void* in, int3
 }
 
 template <int LOGN>
-void launch_combine_t(const PackCombineArgs& a, size_t count, hipStream_t s) {
-    hipLaunchKernelGGL((k_pack_combine<LOGN>), dim3((unsigned)(2 * count)), dim3(PACK_CT), 0, s, a);
+int launch_combine_t(rtfhe_ctx* ctx, const PackCombineArgs& a, size_t count, hipStream_t s) {
+    return launch_kernel(ctx, k_pack_combine<LOGN>, dim3((unsigned)(2 * count)), dim3(PACK_CT), 0, s, a);
 }
 
 // `count` outputs of P samples each on device buffers, primary device, stream s.  d_tlwe: [count * P][n+1], d_out: [count][2][N].
@@ -55,18 +53,14 @@ int launch_pack(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const void* d_tlwe,
     m.tlwe = (const uint32_t*)d_tlwe; m.kmat = pk->d_kmat; m.s = d_s;
     m.M = (int32_t)M; m.n = ctx->p.n; m.n16 = pk->n16; m.colgroups = pk->colgroups;
     m.mgroups = (int32_t)((M + 64 * PACK_WAVES - 1) / (64 * PACK_WAVES));
-    hipLaunchKernelGGL((k_pack_ks_mm<8, 2>), dim3((unsigned)(m.colgroups * m.mgroups)), dim3(64 * PACK_WAVES), 0, s, m);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
+    if (int rc = launch_kernel(ctx, k_pack_ks_mm<8, 2>, dim3((unsigned)(m.colgroups * m.mgroups)), dim3(64 * PACK_WAVES), 0, s, m)) return rc;
     PackCombineArgs c{};
     c.s = d_s; c.tlwe = (const uint32_t*)d_tlwe; c.out = (uint32_t*)d_out;
     c.P = P; c.n = ctx->p.n; c.rep = rep;
     for (int32_t p0 = 0; p0 < P; p0 += PACK_POS_MAX) {
         c.p0 = p0; c.np = P - p0 < PACK_POS_MAX ? P - p0 : PACK_POS_MAX; c.accumulate = p0 ? 1 : 0;
         std::memcpy(c.pos, shift.data() + p0, (size_t)c.np * 4);
-        if (ctx->logn == 11) launch_combine_t<11>(c, count, s); else launch_combine_t<10>(c, count, s);
-        HIPCHECK(ctx, hipGetLastError());
-        ctx->launches++;
+        if (int rc = ctx->logn == 11 ? launch_combine_t<11>(ctx, c, count, s) : launch_combine_t<10>(ctx, c, count, s)) return rc;
     }
     return 0;
 }
@@ -105,9 +99,8 @@ int rtfhe_packing_key_create(rtfhe_ctx* ctx, const uint32_t* pk, rtfhe_packing_k
     if (!rc && hipMemcpy(d_raw, pk, raw_bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_packing_key_create: hipMemcpy");
     if (!rc) {
         PkMatArgs a{d_raw, k->d_kmat, ctx->p.n, k->n16, k->colgroups};
-        hipLaunchKernelGGL((k_pkmat_build<8, 2>), dim3(4096), dim3(256), 0, ctx->stream, a);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_packing_key_create: k_pkmat_build");
-        else ctx->launches++;
+        rc = launch_kernel(ctx, k_pkmat_build<8, 2>, dim3(4096), dim3(256), 0, ctx->stream, a);
+        if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_packing_key_create: k_pkmat_build");
     }
     if (d_raw) (void)hipFree(d_raw);      // the operand form is all the calls read
     if (rc) {
@@ -123,9 +116,8 @@ int rtfhe_packing_key_create(rtfhe_ctx* ctx, const uint32_t* pk, rtfhe_packing_k
 
 void rtfhe_packing_key_destroy(rtfhe_packing_key* k) {
     if (!k) return;
-    if (rtfhe_ctx* ctx = k->ctx) {     // still attached (a context destroyed first has already freed the matrix and detached us)
-        auto& v = ctx->pack_keys;
-        for (size_t i = 0; i < v.size(); i++) if (v[i] == k) { v.erase(v.begin() + i); break; }
+    if (rtfhe_ctx* ctx = k->ctx) {     // still attached
+        detach(ctx->pack_keys, k);
         (void)hipSetDevice(ctx->device);
         (void)hipDeviceSynchronize();      // a pack in flight may still read the matrix
         packing_key_release(k);
@@ -138,8 +130,7 @@ int rtfhe_pack_batch_dev(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const void
     std::vector<int32_t> shift;
     if (int rc = pack_ready(ctx, pk, d_tlwe, P, pos, rep, d_out, count, shift)) return rc;
     if (int rc = use(ctx)) return rc;
-    if (!gpu_accessible(ctx, d_out) || !gpu_accessible(ctx, d_tlwe))
-        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_pack_batch_dev needs device pointers (got memory the GPU cannot address)");
+    if (int rc = device_pointers(ctx, "rtfhe_pack_batch_dev", {d_out, d_tlwe})) return rc;
     return launch_pack(ctx, pk, d_tlwe, P, shift, rep, d_out, count, (hipStream_t)stream);
 }
 
@@ -155,24 +146,6 @@ int rtfhe_pack_batch(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const uint32_t
     if (int rc = copy_in(ctx, ctx->d_a, tlwe, in_bytes, 0)) return rc;
     if (int rc = launch_pack(ctx, pk, ctx->d_a, P, shift, rep, ctx->d_c, count, ctx->stream)) return rc;
     return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
-}
-
-int rtfhe_lut_update_dev(rtfhe_lut* lut, const void* d_trlwe, int32_t first, int32_t n, void* stream) {
-    if (!lut) return fail(nullptr, RTFHE_ERR_INVALID, "null table (rtfhe_lut)");
-    rtfhe_ctx* ctx = lut->ctx;
-    if (!ctx) return fail(nullptr, RTFHE_ERR_STATE, "the context of the table has been destroyed");
-    if (!d_trlwe) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    if (!lut->encrypted) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_update_dev rewrites the rows of an encrypted table (rtfhe_lut_create_encrypted); this one is plain");
-    if (!ctx->peers.empty()) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_update_dev: a multi-device context holds one copy of the table per device; not supported");
-    if (first < 0 || n < 0 || (long long)first + n > lut->n_lut)
-        return fail(ctx, RTFHE_ERR_INVALID, "rows [" + std::to_string(first) + ", " + std::to_string((long long)first + n) + ") are outside the table's [0, " +
-                                            std::to_string(lut->n_lut) + ")");
-    if (int rc = use(ctx)) return rc;
-    if (!gpu_accessible(ctx, d_trlwe)) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_update_dev needs a device pointer (got memory the GPU cannot address)");
-    if (n == 0) return 0;
-    const size_t row = 2 * (size_t)ctx->p.N;
-    HIPCHECK(ctx, hipMemcpyAsync(lut->d_tv[0] + (size_t)first * row, d_trlwe, (size_t)n * row * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return 0;
 }
 
 }  // extern "C"

@@ -36,9 +36,7 @@ int prime_plain(rtfhe_ctx* ctx) {
 int plain_ready(rtfhe_ctx* ctx, const rtfhe_plain* w, bool w_idx_given, const int32_t* host_w_idx, const void* x, int32_t n_x, bool x_idx_given,
                 const int32_t* host_x_idx, int32_t K, const void* out, size_t count) {
     if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
-    if (!w) return fail(ctx, RTFHE_ERR_INVALID, "null plain set (rtfhe_plain)");
-    if (!w->ctx) return fail(ctx, RTFHE_ERR_STATE, "the context of the plain set has been destroyed");
-    if (w->ctx != ctx) return fail(ctx, RTFHE_ERR_INVALID, "the plain set belongs to another context");
+    if (int rc = handles_ready(ctx, {ref(w)})) return rc;
     char err[256];
     if (int rc = rtfhe_plain_plan(ctx->p.N, w->n_w, w->wmax, K, w_idx_given, host_w_idx, n_x, x_idx_given, host_x_idx, count, x, out, err, sizeof err))
         return fail(ctx, rc, err);
@@ -94,7 +92,7 @@ int rtfhe_plain_create(rtfhe_ctx* ctx, const int32_t* w, int32_t n_w, rtfhe_plai
     t->n_w = n_w; t->wmax = wmax; t->ctx = ctx;
     int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, words * 4);
     if (!rc && hipMalloc((void**)&t->d_spec, words / 2 * sizeof(cplx)) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_plain_create: hipMalloc");
-    if (!rc && hipMemcpy(ctx->d_a, w, words * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_plain_create: hipMemcpy");
+    if (!rc) rc = copy_in(ctx, ctx->d_a, w, words * 4, 0);      // on the stream of the build below, which is waited for
     if (!rc) {
         const PlainBuildArgs a{ctx->d_xtw, (const int32_t*)ctx->d_a, t->d_spec, n_w};
         rc = ctx->logn == 11 ? launch_build<11>(ctx, a) : launch_build<10>(ctx, a);
@@ -113,9 +111,8 @@ int rtfhe_plain_create(rtfhe_ctx* ctx, const int32_t* w, int32_t n_w, rtfhe_plai
 
 void rtfhe_plain_destroy(rtfhe_plain* w) {
     if (!w) return;
-    if (rtfhe_ctx* ctx = w->ctx) {     // still attached (a context destroyed first has already freed the spectra and detached us)
-        auto& v = ctx->plains;
-        for (size_t i = 0; i < v.size(); i++) if (v[i] == w) { v.erase(v.begin() + i); break; }
+    if (rtfhe_ctx* ctx = w->ctx) {     // still attached
+        detach(ctx->plains, w);
         plain_release(w);
     }
     delete w;
@@ -128,22 +125,15 @@ int rtfhe_trlwe_mul_plain_batch(rtfhe_ctx* ctx, const rtfhe_plain* w, const int3
     if (int rc = plain_ready(ctx, w, w_idx != nullptr, w_idx, x, n_x, x_idx != nullptr, x_idx, K, out, count)) return rc;
     if (int rc = use(ctx)) return rc;
     if (count == 0) return 0;
-    const size_t row = 2 * (size_t)ctx->p.N * 4, in_bytes = (size_t)n_x * row, out_bytes = count * row, idx_bytes = count * (size_t)K * 4;
+    const size_t row = 2 * (size_t)ctx->p.N * 4, in_bytes = (size_t)n_x * row, out_bytes = count * row;
     if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, in_bytes)) return rc;
     if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
-    const int32_t *d_w_idx = nullptr, *d_x_idx = nullptr;
-    if (w_idx || x_idx) {
-        if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, 2 * idx_bytes)) return rc;
-        if (w_idx) { HIPCHECK(ctx, hipMemcpyAsync(ctx->d_b, w_idx, idx_bytes, hipMemcpyHostToDevice, ctx->stream)); d_w_idx = (const int32_t*)ctx->d_b; }
-        if (x_idx) {
-            HIPCHECK(ctx, hipMemcpyAsync((int32_t*)ctx->d_b + count * (size_t)K, x_idx, idx_bytes, hipMemcpyHostToDevice, ctx->stream));
-            d_x_idx = (const int32_t*)ctx->d_b + count * (size_t)K;
-        }
-    }
+    StagedIdx idx;
+    if (int rc = stage_idx(ctx, &ctx->d_b, &ctx->cap_b, count * (size_t)K, w_idx, x_idx, idx)) return rc;
     if (int rc = copy_in(ctx, ctx->d_a, x, in_bytes, 0)) return rc;
     if (accumulate)
         if (int rc = copy_in(ctx, ctx->d_c, out, out_bytes, 1)) return rc;
-    if (int rc = launch_mul_plain(ctx, w, d_w_idx, ctx->d_a, n_x, d_x_idx, K, accumulate, ctx->d_c, count, ctx->stream)) return rc;
+    if (int rc = launch_mul_plain(ctx, w, idx.first, ctx->d_a, n_x, idx.second, K, accumulate, ctx->d_c, count, ctx->stream)) return rc;
     return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
 }
 
@@ -152,8 +142,7 @@ int rtfhe_trlwe_mul_plain_batch_dev(rtfhe_ctx* ctx, const rtfhe_plain* w, const 
     if (int rc = plain_ready(ctx, w, d_w_idx != nullptr, nullptr, d_x, n_x, d_x_idx != nullptr, nullptr, K, d_out, count)) return rc;
     if (int rc = use(ctx)) return rc;
     if (count == 0) return 0;
-    if (!gpu_accessible(ctx, d_out) || !gpu_accessible(ctx, d_x) || (d_w_idx && !gpu_accessible(ctx, d_w_idx)) || (d_x_idx && !gpu_accessible(ctx, d_x_idx)))
-        return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trlwe_mul_plain_batch_dev needs device pointers (got memory the GPU cannot address)");
+    if (int rc = device_pointers(ctx, "rtfhe_trlwe_mul_plain_batch_dev", {d_out, d_x}, {d_w_idx, d_x_idx})) return rc;
     return launch_mul_plain(ctx, w, (const int32_t*)d_w_idx, d_x, n_x, (const int32_t*)d_x_idx, K, accumulate, d_out, count, (hipStream_t)stream);
 }
 

@@ -175,19 +175,20 @@ int rtfhe_external_product_batch(rtfhe_ctx* ctx, const int32_t* bk_index, const 
         if (bk_index[g] < 0 || bk_index[g] >= ctx->p.n) return fail(ctx, RTFHE_ERR_INVALID, "bk_index out of range");
     const size_t bytes = count * 2 * (size_t)ctx->p.N * 4;
     if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, bytes)) return rc;
-    if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, count * 4)) return rc;
     if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, bytes)) return rc;
     HIPCHECK(ctx, hipMemcpyAsync(ctx->d_a, trlwe, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHECK(ctx, hipMemcpyAsync(ctx->d_b, bk_index, count * 4, hipMemcpyHostToDevice, ctx->stream));
+    StagedIdx idx;
+    if (int rc = stage_idx(ctx, &ctx->d_b, &ctx->cap_b, count, bk_index, nullptr, idx)) return rc;
+    const int32_t* d_idx = idx.first;
     int rc;
     if (ctx->backend == RTFHE_BACKEND_NTT_EXACT) {
         if ((rc = ntt_prepare(ctx))) return rc;
-        if ((rc = launch_extprod_ntt(ctx, (const int32_t*)ctx->d_b, (const uint32_t*)ctx->d_a, (uint32_t*)ctx->d_c, (int32_t)count, ctx->stream))) return rc;
+        if ((rc = launch_extprod_ntt(ctx, d_idx, (const uint32_t*)ctx->d_a, (uint32_t*)ctx->d_c, (int32_t)count, ctx->stream))) return rc;
     } else if (ctx->backend == RTFHE_BACKEND_FFT_SPLIT_EXACT) {
         if ((rc = xfft_prepare(ctx))) return rc;
-        if ((rc = launch_extprod_xfft(ctx, (const int32_t*)ctx->d_b, (const uint32_t*)ctx->d_a, (uint32_t*)ctx->d_c, (int32_t)count, ctx->stream))) return rc;
+        if ((rc = launch_extprod_xfft(ctx, d_idx, (const uint32_t*)ctx->d_a, (uint32_t*)ctx->d_c, (int32_t)count, ctx->stream))) return rc;
     } else {
-        ExtProdArgs a{ctx->d_tw, ctx->d_bk, (const int32_t*)ctx->d_b, (const uint32_t*)ctx->d_a, (uint32_t*)ctx->d_c, (int32_t)count};
+        ExtProdArgs a{ctx->d_tw, ctx->d_bk, d_idx, (const uint32_t*)ctx->d_a, (uint32_t*)ctx->d_c, (int32_t)count};
         if ((rc = launch_leveled(ctx, extprod_twins(ctx), count, ctx->stream, a, false))) return rc;      // a stage-level call: not counted
     }
     HIPCHECK(ctx, hipMemcpyAsync(out, ctx->d_c, bytes, hipMemcpyDeviceToHost, ctx->stream));

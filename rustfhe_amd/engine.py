@@ -27,6 +27,34 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data) if a is not None else None
 
 
+def _stream(stream):
+    return C.c_void_p(stream) if stream else None
+
+
+class _Handle:
+    """Owns one handle of the library, kept in the attribute named by _slot, and the function that destroys it (self._destroy, set before the
+    handle is): close() frees it once, and so do a with block and garbage collection."""
+    _slot = "h"
+
+    def close(self):
+        h = getattr(self, self._slot, None)
+        if h:
+            self._destroy(h)
+            setattr(self, self._slot, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
 
 
@@ -36,7 +64,7 @@ def reference_twiddle_file(N):
     return path if os.path.exists(path) else None
 
 
-class Engine:
+class Engine(_Handle):
     def __init__(self, params=None, device=0, devices=None, reference_twiddles=True):
         """device: one GPU (rtfhe_ctx_create).  devices=[d0, d1, ...]: one context over several GPUs of the node
         (rtfhe_ctx_create_multi): keys are loaded once and replicated device-to-device, the host-buffer batch calls shard
@@ -45,6 +73,7 @@ class Engine:
         tables of the reference build (a few entries may be an ulp apart between libms) the shipped tables are installed
         instead (rtfhe_twiddles_load) and self.twiddle_entries_replaced says how many entries differed.  False: this host's libm as it is."""
         self.L = _ffi.load()
+        self._destroy = self.L.rtfhe_ctx_destroy
         self.p = params or Params()
         h = C.c_void_p()
         if devices is not None:
@@ -74,18 +103,9 @@ class Engine:
     def device_count(self):
         return self.L.rtfhe_ctx_device_count(self.h)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.rtfhe_ctx_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _ck(self, rc):
+        """Raises RtfheError with the context's message -- or, once the engine is closed (a call made through a handle that outlived it), with
+        the calling thread's last one."""
         if rc != 0:
             raise RtfheError(rc, (self.L.rtfhe_last_error(self.h) or b"").decode())
 
@@ -189,14 +209,14 @@ class Engine:
 
     def gate_batch_dev(self, op, d_in0, d_in1, d_out, count, stream=None):
         self._ck(self.L.rtfhe_gate_batch_dev(self.h, op, self._dev(d_in0), self._dev(d_in1), self._dev(d_out),
-                                             count, C.c_void_p(stream) if stream else None))
+                                             count, _stream(stream)))
 
     def mux_batch_dev(self, d_c, d_in0, d_in1, d_out, count, stream=None):
         self._ck(self.L.rtfhe_mux_batch_dev(self.h, self._dev(d_c), self._dev(d_in0), self._dev(d_in1), self._dev(d_out),
-                                            count, C.c_void_p(stream) if stream else None))
+                                            count, _stream(stream)))
 
     def bootstrap_batch_dev(self, d_tlwe, d_out, count, stream=None):
-        self._ck(self.L.rtfhe_bootstrap_batch_dev(self.h, self._dev(d_tlwe), self._dev(d_out), count, C.c_void_p(stream) if stream else None))
+        self._ck(self.L.rtfhe_bootstrap_batch_dev(self.h, self._dev(d_tlwe), self._dev(d_out), count, _stream(stream)))
 
     def memory_bytes(self, d=0):
         """Device memory entry d of the context holds right now: keys in every form built so far, staging and scratch (not the twiddle tables, not
@@ -217,7 +237,7 @@ class Engine:
         (rows of d_wires) and a violation surfaces as RtfheError at the next sync()."""
         self._ck(self.L.rtfhe_circuit_wave_dev(self.h, self._dev(d_ops), self._dev(d_idx0), self._dev(d_idx1),
                                                self._dev(d_idx_out), self._dev(d_wires), num_wires, count,
-                                               C.c_void_p(stream) if stream else None))
+                                               _stream(stream)))
 
     def circuit_create(self, d_ops, d_idx0, d_idx1, d_idx_out, wave_offsets, d_wires, num_wires):
         """Records the waves [wave_offsets[w], wave_offsets[w+1]) of a levelised netlist into one HIP graph; returns a handle
@@ -245,26 +265,26 @@ class Engine:
         return h
 
     def circuit_launch(self, circuit, stream=None):
-        self._ck(self.L.rtfhe_circuit_launch(circuit, C.c_void_p(stream) if stream else None))
+        self._ck(self.L.rtfhe_circuit_launch(circuit, _stream(stream)))
 
     def circuit_destroy(self, circuit):
         self.L.rtfhe_circuit_destroy(circuit)
 
     def sync(self, stream=None):
-        self._ck(self.L.rtfhe_sync(self.h, C.c_void_p(stream) if stream else None))
+        self._ck(self.L.rtfhe_sync(self.h, _stream(stream)))
 
     def timer_begin(self, stream=None):
-        self._ck(self.L.rtfhe_timer_begin(self.h, C.c_void_p(stream) if stream else None))
+        self._ck(self.L.rtfhe_timer_begin(self.h, _stream(stream)))
 
     def timer_end(self, stream=None):
         ms, n = C.c_double(), C.c_int64()
-        self._ck(self.L.rtfhe_timer_end(self.h, C.c_void_p(stream) if stream else None, C.byref(ms), C.byref(n)))
+        self._ck(self.L.rtfhe_timer_end(self.h, _stream(stream), C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
     def timer_end_detail(self, stream=None):
         """(total ms, ms of it inside the batch key switches of the split path, kernel launches)"""
         ms, ks, n = C.c_double(), C.c_double(), C.c_int64()
-        self._ck(self.L.rtfhe_timer_end_detail(self.h, C.c_void_p(stream) if stream else None, C.byref(ms), C.byref(ks), C.byref(n)))
+        self._ck(self.L.rtfhe_timer_end_detail(self.h, _stream(stream), C.byref(ms), C.byref(ks), C.byref(n)))
         return ms.value, ks.value, n.value
 
     # ---- programmable bootstrapping (include/rtfhe.h: rtfhe_lut_create, rtfhe_pbs_batch[_dev]) -------------------------------
@@ -292,7 +312,7 @@ class Engine:
         """... on device buffers (d_lut_idx: int32[count] on the device or None), asynchronous on `stream`.  Indices are checked on the device:
         a gate with a bad one is skipped and the next sync() raises RtfheError."""
         self._ck(self.L.rtfhe_pbs_batch_dev(self.h, lut.h, self._dev(d_lut_idx), self._dev(d_tlwe), self._dev(d_out), count,
-                                            C.c_void_p(stream) if stream else None))
+                                            _stream(stream)))
 
     def pbs_many_batch(self, lut, tlwe, n_out, lut_idx=None):
         """Many-LUT PBS (include/rtfhe.h: rtfhe_pbs_many_batch): n_out (1, 2, 4 or 8) functions of each ciphertext from ONE blind rotation,
@@ -308,7 +328,7 @@ class Engine:
         """... on device buffers (d_out: [count][n_out][n+1] words), asynchronous on `stream`; bad indices are reported by the next sync().
         Inside a stream capture an eager call of at least `count` gates and this n_out must have run on the stream first."""
         self._ck(self.L.rtfhe_pbs_many_batch_dev(self.h, lut.h, int(n_out), self._dev(d_lut_idx), self._dev(d_tlwe), self._dev(d_out), count,
-                                                 C.c_void_p(stream) if stream else None))
+                                                 _stream(stream)))
 
     # ---- CMUX-tree table lookup (include/rtfhe.h: rtfhe_trgsw_create, rtfhe_cmux_tree_batch[_dev], rtfhe_cmux_tree_extract_batch[_dev]) ------
     def selectors(self, trgsw):
@@ -334,7 +354,7 @@ class Engine:
         bad indices are reported by the next sync().  Inside a stream capture an eager call of at least this count and depth must have run
         on the stream first."""
         self._ck(self.L.rtfhe_cmux_tree_batch_dev(self.h, sel.h, self._dev(d_sel_idx), int(depth), lut.h, self._dev(d_row0), self._dev(d_out), count,
-                                                  C.c_void_p(stream) if stream else None))
+                                                  _stream(stream)))
 
     def cmux_tree_extract_batch(self, sel, lut, depth, count, sel_idx=None, row0=None, coef=None):
         """The same tree followed by sample extract at coefficient coef[g] (None: 0) and the key switch: u32[count][n+1] lvl0 ciphertexts of
@@ -347,7 +367,7 @@ class Engine:
     def cmux_tree_extract_batch_dev(self, sel, lut, depth, d_out, count, d_sel_idx=None, d_row0=None, d_coef=None, stream=None):
         """... on device buffers (d_out: [count][n+1] words), under cmux_tree_batch_dev's rules."""
         self._ck(self.L.rtfhe_cmux_tree_extract_batch_dev(self.h, sel.h, self._dev(d_sel_idx), int(depth), lut.h, self._dev(d_row0), self._dev(d_coef),
-                                                          self._dev(d_out), count, C.c_void_p(stream) if stream else None))
+                                                          self._dev(d_out), count, _stream(stream)))
 
     # ---- TRGSW blind rotation (include/rtfhe.h: rtfhe_trgsw_rotate_batch[_dev], rtfhe_trgsw_rotate_extract_batch[_dev]) ------------------------
     def _rot_arg(self, rot, depth):
@@ -375,7 +395,7 @@ class Engine:
         sync() raises.  Allocates nothing: it may be captured without a prior eager call."""
         r = self._rot_arg(rot, depth)
         self._ck(self.L.rtfhe_trgsw_rotate_batch_dev(self.h, sel.h, self._dev(d_sel_idx), int(depth), _ptr(r), self._dev(d_trlwe), self._dev(d_out), count,
-                                                     C.c_void_p(stream) if stream else None))
+                                                     _stream(stream)))
 
     def trgsw_rotate_extract_batch(self, sel, trlwe, depth, sel_idx=None, rot=None):
         """The same rotation followed by sample extract at coefficient 0 and the key switch: u32[count][n+1] lvl0 ciphertexts.  With rot None
@@ -393,7 +413,7 @@ class Engine:
         stream first."""
         r = self._rot_arg(rot, depth)
         self._ck(self.L.rtfhe_trgsw_rotate_extract_batch_dev(self.h, sel.h, self._dev(d_sel_idx), int(depth), _ptr(r), self._dev(d_trlwe), self._dev(d_out),
-                                                             count, C.c_void_p(stream) if stream else None))
+                                                             count, _stream(stream)))
 
     # ---- CMUX demultiplexer tree (include/rtfhe.h: rtfhe_demux_tree_batch[_dev], rtfhe_lut_accumulate_dev) --------------------------------------
     def demux_tree_batch(self, sel, x, depth, sel_idx=None):
@@ -415,7 +435,7 @@ class Engine:
         sync() raises.  Inside a stream capture an eager call of at least this count and depth must have run on the stream first (depth 1
         needs none)."""
         self._ck(self.L.rtfhe_demux_tree_batch_dev(self.h, sel.h, self._dev(d_sel_idx), int(depth), self._dev(d_x), self._dev(d_out), count,
-                                                   C.c_void_p(stream) if stream else None))
+                                                   _stream(stream)))
 
     # ---- CMUX netlists (include/rtfhe.h: rtfhe_cmux_circuit_create; rustfhe_amd.cmux_net) -----------------------------------------------------
     def cmux_circuit(self, netlist, sel, lut, d_out, count, d_sel_idx=None, d_row0=None, rounded=None):
@@ -458,7 +478,7 @@ class Engine:
         """... on device buffers (d_tlwe: [count][P][n+1] words, d_out: [count][2][N] words; pos stays a host array, copied at enqueue time),
         asynchronous on `stream`.  Inside a stream capture an eager call of at least count * P samples must have run on the stream first."""
         self._ck(self.L.rtfhe_pack_batch_dev(self.h, pk.h, self._dev(d_tlwe), int(P), _ptr(self._pos_arg(pos, P)), int(rep), self._dev(d_out), count,
-                                             C.c_void_p(stream) if stream else None))
+                                             _stream(stream)))
 
     # ---- TRLWE sample extraction (include/rtfhe.h: rtfhe_trlwe_extract_batch[_dev], rtfhe_trlwe_extract_lvl1_batch[_dev]) ----------------------
     def _coef_arg(self, coef, P):
@@ -483,7 +503,7 @@ class Engine:
         enqueue time), asynchronous on `stream`.  Inside a stream capture an eager call of at least count * P samples must have run on the
         stream first."""
         self._ck(self.L.rtfhe_trlwe_extract_batch_dev(self.h, self._dev(d_trlwe), int(P), _ptr(self._coef_arg(coef, P)), int(stride), self._dev(d_out), count,
-                                                      C.c_void_p(stream) if stream else None))
+                                                      _stream(stream)))
 
     def trlwe_extract_lvl1_batch(self, trlwe, P, coef=None, stride=1):
         """The same samples before the key switch: lvl1 samples u32[count][P][N+1] (a'[0..N), b'), the input layout of key_switch_batch.  Needs
@@ -497,7 +517,7 @@ class Engine:
     def trlwe_extract_lvl1_batch_dev(self, d_trlwe, P, d_out, count, coef=None, stride=1, stream=None):
         """... on device buffers (d_out: [count][P][N+1] words).  Allocates nothing: it may be captured without a prior eager call."""
         self._ck(self.L.rtfhe_trlwe_extract_lvl1_batch_dev(self.h, self._dev(d_trlwe), int(P), _ptr(self._coef_arg(coef, P)), int(stride), self._dev(d_out),
-                                                           count, C.c_void_p(stream) if stream else None))
+                                                           count, _stream(stream)))
 
     # ---- exact TRLWE x plain-polynomial products (include/rtfhe.h: rtfhe_plain_create, rtfhe_trlwe_mul_plain_batch[_dev]) --------------------------
     def plain_polys(self, w):
@@ -534,7 +554,7 @@ class Engine:
         device), asynchronous on `stream`; accumulate adds into d_out.  A sample with a bad index is skipped, its output row untouched, and the
         next sync() raises.  One launch, nothing allocated: it may be captured first thing on a fresh stream."""
         self._ck(self.L.rtfhe_trlwe_mul_plain_batch_dev(self.h, pp.h, self._dev(d_w_idx), self._dev(d_x), int(n_x), self._dev(d_x_idx), int(K),
-                                                        1 if accumulate else 0, self._dev(d_out), count, C.c_void_p(stream) if stream else None))
+                                                        1 if accumulate else 0, self._dev(d_out), count, _stream(stream)))
 
     # ---- stage level ------------------------------------------------------------------------
     def blind_rotate_batch(self, tlwe, steps=None):
@@ -593,14 +613,14 @@ class Engine:
         return res
 
 
-class Lut:
+class Lut(_Handle):
     """Test polynomials of a programmable bootstrap on an Engine's devices (rtfhe_lut), plain or encrypted (TRLWE rows, Engine.lut_encrypted).
     Closing it frees the device copies; a Lut whose Engine was closed first only frees its handle."""
 
     def __init__(self, engine, tv, encrypted=False):
         tv = _np(tv, np.uint32)
         tv = tv.reshape(-1, 2 * engine.p.N if encrypted else engine.p.N)
-        self.engine = engine
+        self.engine, self._destroy = engine, engine.L.rtfhe_lut_destroy
         self.encrypted = bool(encrypted)
         self.n_lut = tv.shape[0]
         h = C.c_void_p()
@@ -612,9 +632,7 @@ class Lut:
         """Rewrites rows [first, first + n) of an encrypted table in place from device memory u32[n][2][N] (rtfhe_lut_update_dev), e.g. the
         output of Engine.pack_batch_dev; a copy ordered on `stream`.  Refused for a plain table, a bad range and a multi-device Engine."""
         e = self.engine
-        rc = e.L.rtfhe_lut_update_dev(self.h, e._dev(d_trlwe), int(first), int(n), C.c_void_p(stream) if stream else None)
-        if rc != 0:
-            raise RtfheError(rc, (e.L.rtfhe_last_error(e.h if e.h else None) or b"").decode())
+        e._ck(e.L.rtfhe_lut_update_dev(self.h, e._dev(d_trlwe), int(first), int(n), _stream(stream)))
 
     def accumulate_dev(self, d_trlwe, first=0, n=1, count=1, stream=None):
         """Adds device TRLWEs u32[count][n][2][N] into rows [first, first + n) of an encrypted table in place (rtfhe_lut_accumulate_dev):
@@ -622,44 +640,23 @@ class Lut:
         Engine.demux_tree_batch_dev (n = 2^depth): an oblivious scatter-add.  Refused for a plain table, a bad range, count < 1 and a
         multi-device Engine."""
         e = self.engine
-        rc = e.L.rtfhe_lut_accumulate_dev(self.h, e._dev(d_trlwe), int(first), int(n), int(count), C.c_void_p(stream) if stream else None)
-        if rc != 0:
-            raise RtfheError(rc, (e.L.rtfhe_last_error(e.h if e.h else None) or b"").decode())
+        e._ck(e.L.rtfhe_lut_accumulate_dev(self.h, e._dev(d_trlwe), int(first), int(n), int(count), _stream(stream)))
 
     def read_dev(self, d_out, first=0, n=1, stream=None):
         """Copies rows [first, first + n) of an encrypted table into device memory u32[n][2][N] (rtfhe_lut_read_dev), ordered on `stream`:
         update_dev the other way, under the same refusals."""
         e = self.engine
-        rc = e.L.rtfhe_lut_read_dev(self.h, e._dev(d_out), int(first), int(n), C.c_void_p(stream) if stream else None)
-        if rc != 0:
-            raise RtfheError(rc, (e.L.rtfhe_last_error(e.h if e.h else None) or b"").decode())
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.engine.L.rtfhe_lut_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        e._ck(e.L.rtfhe_lut_read_dev(self.h, e._dev(d_out), int(first), int(n), _stream(stream)))
 
 
-class Selectors:
+class Selectors(_Handle):
     """The TRGSW selectors of CMUX trees on an Engine's primary device (rtfhe_trgsw), kept as spectra.  Closing it frees the device copy; one
     whose Engine was closed first only frees its handle."""
 
     def __init__(self, engine, trgsw):
         p = engine.p
         trgsw = _np(trgsw, np.uint32).reshape(-1, 2 * 2 * p.l * p.N)
-        self.engine = engine
+        self.engine, self._destroy = engine, engine.L.rtfhe_trgsw_destroy
         self.n_sel = trgsw.shape[0]
         h = C.c_void_p()
         engine._ck(engine.L.rtfhe_trgsw_create(engine.h, _ptr(trgsw), self.n_sel, C.byref(h)))
@@ -672,25 +669,8 @@ class Selectors:
         words = _np(words, np.uint32).reshape(-1, 2 * 2 * p.l * p.N)
         self.engine._ck(self.engine.L.rtfhe_trgsw_update(self.h, _ptr(words), int(first), words.shape[0]))
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.engine.L.rtfhe_trgsw_destroy(self.h)
-            self.h = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PackingKey:
+class PackingKey(_Handle):
     """A packing key on an Engine's primary device (rtfhe_packing_key), kept as signed byte limbs in the matrix pipe's operand order.  Closing
     it frees the device copy; one whose Engine was closed first only frees its handle."""
 
@@ -698,67 +678,34 @@ class PackingKey:
         p = engine.p
         pk = _np(pk, np.uint32).reshape(-1)
         assert pk.size == packing_key_words(p), "pk must be u32[n][t][base-1][2][N]"
-        self.engine = engine
+        self.engine, self._destroy = engine, engine.L.rtfhe_packing_key_destroy
         h = C.c_void_p()
         engine._ck(engine.L.rtfhe_packing_key_create(engine.h, _ptr(pk), C.byref(h)))
         self.h = h
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.engine.L.rtfhe_packing_key_destroy(self.h)
-            self.h = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PlainPolys:
+class PlainPolys(_Handle):
     """Integer polynomials on an Engine's primary device (rtfhe_plain), kept as spectra: the plain operand of Engine.trlwe_mul_plain_batch[_dev].
     Closing it frees the device copy; one whose Engine was closed first only frees its handle."""
 
     def __init__(self, engine, w):
         w = _np(w, np.int32).reshape(-1, engine.p.N)
-        self.engine = engine
+        self.engine, self._destroy = engine, engine.L.rtfhe_plain_destroy
         self.n = w.shape[0]
         self.wmax = int(np.abs(w.astype(np.int64)).sum(axis=1).max()) if self.n else 0
         h = C.c_void_p()
         engine._ck(engine.L.rtfhe_plain_create(engine.h, _ptr(w), self.n, C.byref(h)))
         self.h = h
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.engine.L.rtfhe_plain_destroy(self.h)
-            self.h = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class FftPlan:
+class FftPlan(_Handle):
     """rtfhe_fft_plan: the reference's two transforms (and Spqlios_poly_mul) at any power of two 16 <= N <= 2048 on the GPU
     (FFT_Processor_Spqlios(N), utils/src/spqlios/fft_processor_spqlios.cpp:7-14); numpy in / numpy out.  The gate path's N = 1024 /
     2048 have their own, fast kernels behind Engine; this serves every other size the reference's FFT FFI accepts."""
 
     def __init__(self, N, device=0):
         self.L = _ffi.load()
+        self._destroy = self.L.rtfhe_fft_plan_destroy
         self.N = int(N)
         h = C.c_void_p()
         rc = self.L.rtfhe_fft_plan_create(self.N, device, C.byref(h))
@@ -769,13 +716,6 @@ class FftPlan:
     def _ck(self, rc):
         if rc != 0:
             raise RtfheError(rc, (self.L.rtfhe_last_error(None) or b"").decode())
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.rtfhe_fft_plan_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def _run(self, fn, src, in_dtype, out_dtype, src2=None):
         src = _np(src, in_dtype).reshape(-1, self.N)

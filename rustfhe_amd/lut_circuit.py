@@ -7,6 +7,7 @@ s = sum_k w_k * m_k + const, which must stay in [0, 2^p) (the padding bit), and 
 """
 import numpy as np
 
+from .engine import _Handle
 from .pbs import many_lut_polynomial
 
 
@@ -139,16 +140,18 @@ class LutNetlist:
                 "wave_n_out": np.array(n_out, np.int32), "out_idx": np.array(out_idx, np.int32), "num_wires": replicas * W}
 
 
-class LutCircuitRunner:
+class LutCircuitRunner(_Handle):
     """Runs `replicas` independent instances of a LutNetlist on one Engine as ONE recorded circuit.  Wire table: int32[replicas * num_wires][n+1]
     in HBM; the inputs of replica r are rows r * num_wires + 0 .. num_inputs - 1.  Given the lvl1 key key1, the tables are encrypted under it
     (rustfhe_amd.encrypt_lut; seed: TEST-ONLY deterministic encryption) and the circuit holds them only as ciphertexts (Engine.lut_encrypted).
     rounded=True records the circuit with the rounded gadget decomposition (Engine.set_decomposition): the engine's mode is set around the
     recording and restored after it; the circuit replays in the mode it was recorded in."""
+    _slot = "_circuit"      # the recorded circuit, once launch() has made it
 
     def __init__(self, engine, net, replicas=1, key1=None, seed=None, rounded=False):
         import torch
         self.e, self.net, self.R = engine, net, replicas
+        self._destroy = engine.circuit_destroy
         self.key1, self.seed = key1, seed
         self.rounded = bool(rounded)
         self.n1 = engine.p.n + 1
@@ -203,17 +206,6 @@ class LutCircuitRunner:
 
     def wire(self, w):
         return self.wires.view(self.R, self.net.num_wires, self.n1)[:, w].cpu().numpy().view(np.uint32)
-
-    def close(self):
-        if getattr(self, "_circuit", None) is not None:
-            self.e.circuit_destroy(self._circuit)
-            self._circuit = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def lut_ripple_adder(bits=8):
