@@ -189,6 +189,12 @@ extern "C" {
                                        accumulate: i32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_trlwe_mul_plain_batch_dev(ctx: *mut rtfhe_ctx, w: *const rtfhe_plain, d_w_idx: *const c_void, d_x: *const c_void, n_x: i32,
                                            d_x_idx: *const c_void, K: i32, accumulate: i32, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
+    // TRLWE x TRGSW multiply-accumulate: out[g] = (accumulate ? out[g] : 0) + sum_k S[s_idx[g][k]] (.) x[x_idx[g][k]], summed in the frequency domain,
+    // K in 1 ..= 8; s_idx / x_idx [count][K] (null: entry g * K + k); FP64 mirror backend only, no key of the context
+    pub fn rtfhe_trlwe_mul_trgsw_batch(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, s_idx: *const i32, x: *const u32, n_x: i32, x_idx: *const i32, K: i32,
+                                       accumulate: c_int, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trlwe_mul_trgsw_batch_dev(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, d_s_idx: *const c_void, d_x: *const c_void, n_x: i32,
+                                           d_x_idx: *const c_void, K: i32, accumulate: c_int, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
     pub fn rtfhe_sync(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_begin(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_end(ctx: *mut rtfhe_ctx, stream: *mut c_void, ms: *mut f64, launches: *mut i64) -> c_int;
@@ -222,6 +228,7 @@ extern "C" {
     pub fn rtfhe_tlwe_encrypt_torus(p: *const rtfhe_params, key0: *const i32, mu: *const u32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_trlwe_encrypt_torus(p: *const rtfhe_params, key1: *const i32, mu: *const u32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_trgsw_encrypt_bits(p: *const rtfhe_params, key1: *const i32, bits: *const u8, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trgsw_encrypt_polys(p: *const rtfhe_params, key1: *const i32, mu: *const i32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_trlwe_phase(p: *const rtfhe_params, key1: *const i32, ct: *const u32, phase: *mut u32, count: usize) -> c_int;
     // TEST ONLY (seeded xoshiro256**, not secure)
     pub fn rtfhe_ksk_expand_ref(p: *const rtfhe_params, key0: *const i32, key1: *const i32, ksk: *const u32, ksk_ref: *mut u32) -> c_int;
@@ -232,6 +239,7 @@ extern "C" {
     pub fn rtfhe_tlwe_encrypt_torus_deterministic(p: *const rtfhe_params, key0: *const i32, seed: u64, mu: *const u32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_trlwe_encrypt_torus_deterministic(p: *const rtfhe_params, key1: *const i32, seed: u64, mu: *const u32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_trgsw_encrypt_bits_deterministic(p: *const rtfhe_params, key1: *const i32, seed: u64, bits: *const u8, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trgsw_encrypt_polys_deterministic(p: *const rtfhe_params, key1: *const i32, seed: u64, mu: *const i32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_tlwe_decrypt_bits(p: *const rtfhe_params, key0: *const i32, input: *const u32, bits: *mut u8, count: usize) -> c_int;
     pub fn rtfhe_keys_write(path: *const c_char, p: *const rtfhe_params, key0: *const i32, key1: *const i32, bk: *const u32, ksk: *const u32) -> c_int;
     pub fn rtfhe_keys_read_header(path: *const c_char, p: *mut rtfhe_params, flags: *mut u32) -> c_int;

@@ -53,8 +53,12 @@
  *                                    <- Polynomial::cross (utils/src/math.rs:238-257) of both polynomials of a TRLWE row with a plain integer polynomial:
  *                                       the exact ciphertext x plaintext product, sums of up to eight per sample (the reference has the polynomial
  *                                       product, not the TRLWE operation)
+ *   rtfhe_trlwe_mul_trgsw_batch[_dev] / rtfhe_trgsw_encrypt_polys[_deterministic]
+ *                                    <- TRGSWRepF::cross (hom_nand/src/trgsw.rs:264-306) on caller-supplied TRGSW samples of small-integer polynomials
+ *                                       (Crypto<i32> for TRGSW, trgsw.rs:118-138, with a polynomial in the bit's place), its fold-add carried over
+ *                                       up to eight products per sample (the reference has the product, not the sum)
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
- *   rtfhe_key_switch_batch           <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
+ *   rtfhe_key_switch_batch          <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
  *   rtfhe_fft_u32_batch              <- Spqlios_fft_u32 (utils/src/spqlios.rs:25, spqlios-wrapper.cpp:34-36)
  *   rtfhe_ifft_f64_batch / _fft_f64_batch / _poly_mul_batch
@@ -755,6 +759,45 @@ int rtfhe_trlwe_mul_plain_batch(rtfhe_ctx *ctx, const rtfhe_plain *w, const int3
 int rtfhe_trlwe_mul_plain_batch_dev(rtfhe_ctx *ctx, const rtfhe_plain *w, const void *d_w_idx /* [count][K] or NULL */, const void *d_x /* [n_x][2][N] */,
                                     int32_t n_x, const void *d_x_idx /* [count][K] or NULL */, int32_t K, int32_t accumulate,
                                     void *d_out /* [count][2][N] */, size_t count, void *stream);
+/* ---- TRLWE x TRGSW multiply-accumulate: ciphertext x ciphertext, the linear layer with encrypted weights ----
+ * TRGSWRepF::cross (hom_nand/src/trgsw.rs:264-306) on the samples of a selector set (rtfhe_trgsw_create; e.g. encryptions of small-integer
+ * polynomials from rtfhe_trgsw_encrypt_polys), with its fold-add carried over K terms.  For g in [0, count), on both polynomials of the row:
+ *
+ *   sum_c  = 0.0;  for k = 0 .. K-1, for h = b, a, for j = 0 .. l-1:
+ *                sum_c = sum_c + hadamard(S[s_idx[g][k]].row(c, h, j), ifft_i32(digit_j(x[x_idx[g][k]].poly_h)))          c = 0, 1
+ *   out[g].poly_c = (accumulate ? out[g].poly_c : 0) + fft_u32(sum_c)                                    wrapping u32 add
+ *
+ * i.e. out[g] = (accumulate ? out[g] : 0) + sum_k S_k (.) x_k with ONE pair of inverse transforms and one truncation for the whole sum.  The
+ * blocks are those of rtfhe_external_product_batch on the FP64 mirror backend: the digits of the leveled decomposition in force when the call
+ * is made (rtfhe_set_leveled_decomposition), the reference's forward transform, the unfused multiply-add, the inverse transform with
+ * truncation toward zero -- exact over the sum's whole range, K * 2l * N * (Bg/2) * 2^31 < 2^53.  K = 1 without accumulate gives the words of
+ * rtfhe_external_product_batch on the same TRGSW sample and row.
+ *
+ * With S_k encrypting mu_k(X) the result decrypts to sum_k mu_k * phase(x_k) plus, per term, the selector rows' noise (which does not scale
+ * with mu), the decomposition's rounding through mu_k, and x_k's own noise through mu_k.  One-hot selectors make it a K-way row select.
+ *
+ * Parameters.
+ *   - 1 <= K <= 8.  x is an array of n_x rows.  s_idx NULL means selector g * K + k (it needs n_sel >= count * K); x_idx NULL means row
+ *     g * K + k (it needs n_x >= count * K).  Duplicates are allowed.
+ *   - accumulate = 1 adds into out (a bias as the trivial TRLWE, more than K terms); accumulate = 0 overwrites out.
+ *   - Checked on the host before anything is allocated or launched, RTFHE_ERR_INVALID with a message naming the sample: handles and buffers
+ *     non-null; K; n_x >= 1; count * K < 2^31; every host index in range and the NULL-index rules above; out overlaps no part of x (in-place
+ *     products are not supported).  count == 0 returns 0.
+ *   - The _dev form takes the index arrays on the device and checks them in the kernel: a sample with a bad index is skipped, its output row
+ *     untouched, and the next rtfhe_sync returns RTFHE_ERR_INVALID once, as for rtfhe_cmux_tree_batch_dev.
+ *
+ * Keys, backends and devices.  It needs no key of the context.  FP64 mirror backend only: on an exact backend the call returns
+ * RTFHE_ERR_INVALID and the context stays usable, as for every other call over a selector set.  On an rtfhe_ctx_create_multi context it runs
+ * on the primary device.  A destroyed context gives RTFHE_ERR_STATE.
+ *
+ * Scratch and captures.  The _dev form allocates nothing and is ONE launch, counted by rtfhe_timer_end: it may sit in a caller's stream
+ * capture first thing on a fresh stream (rtfhe_trgsw_create grants the kernel what it needs). */
+int rtfhe_trlwe_mul_trgsw_batch(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const int32_t *s_idx /* [count][K] or NULL */, const uint32_t *x /* [n_x][2][N] */,
+                                int32_t n_x, const int32_t *x_idx /* [count][K] or NULL */, int32_t K, int accumulate,
+                                uint32_t *out /* [count][2][N] */, size_t count);
+int rtfhe_trlwe_mul_trgsw_batch_dev(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const void *d_s_idx /* [count][K] or NULL */, const void *d_x /* [n_x][2][N] */,
+                                    int32_t n_x, const void *d_x_idx /* [count][K] or NULL */, int32_t K, int accumulate,
+                                    void *d_out /* [count][2][N] */, size_t count, void *stream);
 /* waits for `stream`; also reports (once) a netlist gate skipped since the previous call */
 int rtfhe_sync(rtfhe_ctx *ctx, void *stream);
 /* device-side timing of the launches enqueued by the *_dev calls between begin and end (HIP events on
@@ -827,6 +870,12 @@ int rtfhe_trlwe_phase(const rtfhe_params *p, const int32_t *key1, const uint32_t
  * encrypted address bits of a CMUX tree (rtfhe_trgsw_create). */
 int rtfhe_trgsw_encrypt_bits(const rtfhe_params *p, const int32_t *key1, const uint8_t *bits /* [count] */,
                              uint32_t *out /* [count][2][2l][N] */, size_t count);
+/* TRGSW encryptions under key1 [N] of the small-integer polynomials mu[count][N] (OS CSPRNG): rtfhe_trgsw_encrypt_bits (Crypto<i32> for TRGSW,
+ * hom_nand/src/trgsw.rs:118-138; the product they feed is trgsw.rs:264-306) with mu(X) * 2^(32 - (j+1) bgbit), wrapping, added over all N
+ * coefficients of gadget position j where that adds bit * 2^(32 - (j+1) bgbit) at coefficient 0.  Same layout, same noise alpha = 2^-25, same
+ * order of the mask and noise draws: the encrypted weights of rtfhe_trlwe_mul_trgsw_batch, uploaded through rtfhe_trgsw_create. */
+int rtfhe_trgsw_encrypt_polys(const rtfhe_params *p, const int32_t *key1, const int32_t *mu /* [count][N] */,
+                              uint32_t *out /* [count][2][2l][N] */, size_t count);
 /* the reference's KeySwitchingKey shape from the compact one: entries t = 1 .. base-1 of every level copied, entry t = base =
  * TLWE(base * s_i / 2^(basebit (l+1))) freshly encrypted as KeySwitchingKey::new fills it (hom_nand/src/tlwe.rs:252-274) */
 int rtfhe_ksk_expand_ref(const rtfhe_params *p, const int32_t *key0, const int32_t *key1,
@@ -847,6 +896,9 @@ int rtfhe_trlwe_encrypt_torus_deterministic(const rtfhe_params *p, const int32_t
                                             const uint32_t *mu /* [count][N] */, uint32_t *out /* [count][2][N] */, size_t count);
 int rtfhe_trgsw_encrypt_bits_deterministic(const rtfhe_params *p, const int32_t *key1, uint64_t seed, const uint8_t *bits /* [count] */,
                                            uint32_t *out /* [count][2][2l][N] */, size_t count);
+/* (with a constant polynomial mu = bit and the same seed: the words of rtfhe_trgsw_encrypt_bits_deterministic; trgsw.rs:118-138, 264-306) */
+int rtfhe_trgsw_encrypt_polys_deterministic(const rtfhe_params *p, const int32_t *key1, uint64_t seed, const int32_t *mu /* [count][N] */,
+                                            uint32_t *out /* [count][2][2l][N] */, size_t count);
 int rtfhe_tlwe_decrypt_bits(const rtfhe_params *p, const int32_t *key0, const uint32_t *in,
                             uint8_t *bits, size_t count);
 int rtfhe_tlwe_phase(const rtfhe_params *p, const int32_t *key0, const uint32_t *in, uint32_t *phase, size_t count);

@@ -269,9 +269,11 @@ int rtfhe_trgsw_create(rtfhe_ctx* ctx, const uint32_t* trgsw, int32_t n_sel, rtf
     if (!trgsw || !out || n_sel < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_create: null argument or n_sel < 1");
     *out = nullptr;
     if (int rc = use(ctx)) return rc;
-    // the rotation and the demultiplexer are granted their dynamic LDS now, so that the first of a context may already sit in a stream capture
+    // the rotation, the demultiplexer and the TRLWE x TRGSW product are granted their dynamic LDS now, so that the first of a context may already
+    // sit in a stream capture
     if (int rc = prime_leveled(ctx, rotate_twins(ctx))) return rc;
     if (int rc = prime_leveled(ctx, demux_twins(ctx))) return rc;
+    if (int rc = prime_trgsw_mac(ctx)) return rc;
     const size_t polys = (size_t)n_sel * 2 * 2 * ctx->p.l, words = polys * ctx->p.N;
     if (polys > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_create: n_sel too large");
     rtfhe_trgsw* t = new rtfhe_trgsw();

@@ -277,6 +277,7 @@ void lut_release(rtfhe_lut* lut);                                         // fre
 void trgsw_release(rtfhe_trgsw* t);                                       // frees a selector set's spectra (rtfhe_cmux_tree.hip)
 void packing_key_release(rtfhe_packing_key* k);                           // frees a packing key's matrix (rtfhe_pack.hip)
 void plain_release(rtfhe_plain* w);                                       // frees a plain set's spectra (rtfhe_plain.hip)
+int prime_trgsw_mac(rtfhe_ctx* ctx);                                      // grants the TRLWE x TRGSW product's twins their LDS (rtfhe_trgsw_mac.hip)
 // ---- the lifetime rule of the handles (rtfhe_context.hip) ----
 // a handle as a call's check sees it: its noun and type name for the messages, whether the caller gave one, and the context it hangs on
 struct HandleRef { const char* noun; const char* type; bool given; const rtfhe_ctx* owner; };

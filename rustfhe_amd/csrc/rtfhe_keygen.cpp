@@ -170,6 +170,26 @@ void trgsw_encrypt(Rng& r, const rtfhe_params* p, const int32_t* key1, int32_t m
     }
 }
 
+// TRGSW encryption of the small-integer polynomial mu(X) under key1: trgsw_encrypt with mu(X) / Bg^(k+1) over all N coefficients where that adds
+// the bit's share to coefficient 0 (the same 2l zero encryptions, drawn in the same order, so that a constant polynomial mu = bit gives
+// trgsw_encrypt's words).  The share is the integer mu_c * 2^(32 - (k+1) bgbit), wrapping: an encrypted weight row of a linear layer
+// (rtfhe_trlwe_mul_trgsw_batch), where trgsw_encrypt's are a selector's bit.
+void trgsw_encrypt_poly(Rng& r, const rtfhe_params* p, const int32_t* key1, const int32_t* mu, uint32_t* ct) {
+    const int N = p->N, l = p->l, rows = 2 * l;
+    const float alpha_bk = 1.0f / 33554432.0f;   // 2^-25, trlwe.rs:77
+    for (int j = 0; j < rows; j++) trlwe_zero(r, N, key1, alpha_bk, ct + (size_t)j * N, ct + ((size_t)rows + j) * N);
+    for (int k = 0; k < l; k++) {
+        const int sh = 32 - (k + 1) * p->bgbit;      // >= 0: valid(p) holds l * bgbit <= 32
+        uint32_t* b = ct + (size_t)k * N;
+        uint32_t* a = ct + ((size_t)rows + k + l) * N;
+        for (int c = 0; c < N; c++) {
+            const uint32_t t2 = (uint32_t)mu[c] << sh;
+            b[c] += t2;
+            a[c] += t2;
+        }
+    }
+}
+
 bool valid(const rtfhe_params* p) {
     return p && p->n > 0 && p->N >= 16 && (p->N & (p->N - 1)) == 0 && p->l > 0 && p->bgbit > 0 && p->l * p->bgbit <= 32 &&
            p->ks_t > 0 && p->ks_basebit > 0 && p->ks_t * p->ks_basebit <= 32;
@@ -316,6 +336,14 @@ int encrypt_trgsw_bits(const rtfhe_params* p, Rng& r, const int32_t* key1, const
     return 0;
 }
 
+// ... and of the integer polynomials mu[count][N] (encrypted weights, rtfhe_trlwe_mul_trgsw_batch)
+int encrypt_trgsw_polys(const rtfhe_params* p, Rng& r, const int32_t* key1, const int32_t* mu, uint32_t* out, size_t count) {
+    for (int i = 0; i < p->N; i++) if (key1[i] != 0 && key1[i] != 1) return RTFHE_ERR_INVALID;
+    const size_t trgsw = (size_t)2 * 2 * p->l * p->N;
+    for (size_t g = 0; g < count; g++) trgsw_encrypt_poly(r, p, key1, mu + g * (size_t)p->N, out + g * trgsw);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -370,6 +398,14 @@ int rtfhe_trgsw_encrypt_bits(const rtfhe_params* p, const int32_t* key1, const u
     if (!Source::from_os(src)) return RTFHE_ERR_STATE;
     ChaCha r(src.key, 0);          // a fresh OS key per call
     return encrypt_trgsw_bits(p, r, key1, bits, out, count);
+}
+
+int rtfhe_trgsw_encrypt_polys(const rtfhe_params* p, const int32_t* key1, const int32_t* mu, uint32_t* out, size_t count) {
+    if (!valid(p) || !key1 || !mu || !out) return RTFHE_ERR_INVALID;
+    Source src;
+    if (!Source::from_os(src)) return RTFHE_ERR_STATE;
+    ChaCha r(src.key, 0);          // a fresh OS key per call
+    return encrypt_trgsw_polys(p, r, key1, mu, out, count);
 }
 
 int rtfhe_ksk_expand_ref(const rtfhe_params* p, const int32_t* key0, const int32_t* key1, const uint32_t* ksk, uint32_t* ksk_ref) {
@@ -432,6 +468,12 @@ int rtfhe_trgsw_encrypt_bits_deterministic(const rtfhe_params* p, const int32_t*
     if (!valid(p) || !key1 || !bits || !out) return RTFHE_ERR_INVALID;
     Xoshiro r(seed);
     return encrypt_trgsw_bits(p, r, key1, bits, out, count);
+}
+
+int rtfhe_trgsw_encrypt_polys_deterministic(const rtfhe_params* p, const int32_t* key1, uint64_t seed, const int32_t* mu, uint32_t* out, size_t count) {
+    if (!valid(p) || !key1 || !mu || !out) return RTFHE_ERR_INVALID;
+    Xoshiro r(seed);
+    return encrypt_trgsw_polys(p, r, key1, mu, out, count);
 }
 
 // phase = b - a * s (exact negacyclic product with the binary key), per TRLWE of ct[count][2][N]

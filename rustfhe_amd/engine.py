@@ -556,6 +556,36 @@ class Engine(_Handle):
         self._ck(self.L.rtfhe_trlwe_mul_plain_batch_dev(self.h, pp.h, self._dev(d_w_idx), self._dev(d_x), int(n_x), self._dev(d_x_idx), int(K),
                                                         1 if accumulate else 0, self._dev(d_out), count, _stream(stream)))
 
+    # ---- TRLWE x TRGSW multiply-accumulate (include/rtfhe.h: rtfhe_trlwe_mul_trgsw_batch[_dev]) -----------------------------------------------------
+    def trlwe_mul_trgsw_batch(self, sel, x, K=1, s_idx=None, x_idx=None, acc=None):
+        """out[g] = (acc[g] if acc is given else 0) + sum_{k < K} sel[s_idx[g][k]] (.) x[x_idx[g][k]], the external products summed in the
+        frequency domain (one pair of inverse transforms, one truncation): u32[count][2][N].  x: u32[n_x][2][N].  s_idx None: selector
+        g * K + k; x_idx None: row g * K + k.  count comes from an index array or acc when one is given, else it is n_x // K.  1 <= K <= 8;
+        FP64 mirror backend, in the leveled decomposition in force now; needs no key.  Arguments are checked here: a bad one raises RtfheError
+        before anything runs."""
+        x = _np(x, np.uint32).reshape(-1, 2, self.p.N)
+        K = int(K)
+        Kd = K if K > 0 else 1
+        if s_idx is not None:
+            count = np.asarray(s_idx).size // Kd
+        elif x_idx is not None:
+            count = np.asarray(x_idx).size // Kd
+        elif acc is not None:
+            count = np.asarray(acc).size // (2 * self.p.N)
+        else:
+            count = x.shape[0] // Kd
+        si, xi = self._term_idx(s_idx, count, Kd), self._term_idx(x_idx, count, Kd)
+        out = np.array(_np(acc, np.uint32).reshape(count, 2, self.p.N)) if acc is not None else np.empty((count, 2, self.p.N), np.uint32)
+        self._ck(self.L.rtfhe_trlwe_mul_trgsw_batch(self.h, sel.h, _ptr(si), _ptr(x), x.shape[0], _ptr(xi), K, 1 if acc is not None else 0, _ptr(out), count))
+        return out
+
+    def trlwe_mul_trgsw_batch_dev(self, sel, d_x, n_x, d_out, count, K=1, d_s_idx=None, d_x_idx=None, accumulate=False, stream=None):
+        """... on device buffers (d_x: [n_x][2][N] words, d_out: [count][2][N] words, not overlapping; d_s_idx / d_x_idx: int32[count][K] on the
+        device), asynchronous on `stream`; accumulate adds into d_out.  A sample with a bad index is skipped, its output row untouched, and the
+        next sync() raises.  One launch, nothing allocated: it may be captured first thing on a fresh stream."""
+        self._ck(self.L.rtfhe_trlwe_mul_trgsw_batch_dev(self.h, sel.h, self._dev(d_s_idx), self._dev(d_x), int(n_x), self._dev(d_x_idx), int(K),
+                                                        1 if accumulate else 0, self._dev(d_out), count, _stream(stream)))
+
     # ---- stage level ------------------------------------------------------------------------
     def blind_rotate_batch(self, tlwe, steps=None):
         tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)
@@ -890,6 +920,24 @@ def encrypt_selectors(params, key1, bits, seed=None):
         rc = L.rtfhe_trgsw_encrypt_bits_deterministic(C.byref(params), _ptr(key1), seed, _ptr(bits), _ptr(out), bits.size)
     if rc != 0:
         raise RtfheError(rc, "rtfhe_trgsw_encrypt_bits failed")
+    return out
+
+
+def encrypt_trgsw_polys(params, key1, mu, seed=None):
+    """TRGSW encryptions under the lvl1 key key1 of the small-integer polynomials mu (int32[count][N] or one int32[N]): u32[count][2][2l][N],
+    encrypt_selectors with mu(X) in the bit's place -- the encrypted weights of Engine.trlwe_mul_trgsw_batch (Engine.selectors uploads them).
+    A constant polynomial mu = bit gives encrypt_selectors' words under the same seed.  seed None (production): OS CSPRNG; an integer seed =
+    TEST-ONLY deterministic encryption."""
+    L = _ffi.load()
+    mu = _np(mu, np.int32).reshape(-1, params.N)
+    key1 = _np(key1, np.int32)
+    out = np.empty((mu.shape[0], 2, 2 * params.l, params.N), np.uint32)
+    if seed is None:
+        rc = L.rtfhe_trgsw_encrypt_polys(C.byref(params), _ptr(key1), _ptr(mu), _ptr(out), mu.shape[0])
+    else:
+        rc = L.rtfhe_trgsw_encrypt_polys_deterministic(C.byref(params), _ptr(key1), seed, _ptr(mu), _ptr(out), mu.shape[0])
+    if rc != 0:
+        raise RtfheError(rc, "rtfhe_trgsw_encrypt_polys failed")
     return out
 
 
