@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """CPU only: the noise of accumulated demultiplexer writes.  examples/private_histogram.py's server side restated with
-tests/test_demux_tree_host.py's oracle_demux_tree in rounded leveled mode (bit-exact with k_demux_tree), the accumulation as a numpy sum:
+tests/leveled_oracle.py's oracle_demux_tree in rounded leveled mode (bit-exact with k_demux_tree), the accumulation as a numpy sum:
 `writes` clients, 16 rows, full parameter set.  Prints the error of the accumulated rows against the clear counts -- over all coefficients, by
 bands of 128 coefficients (the part that does not average out grows with the distance from N/2) and in the example's slots -- beside
 r(4, N) sqrt(writes) and half a counting unit.
@@ -13,8 +13,8 @@ import numpy as np
 import orc, round_oracle as ro
 import rustfhe_amd as R
 import private_histogram as ex
-from test_demux_tree_host import oracle_demux_tree
-from test_pbs_host import bk_fft
+from leveled_oracle import oracle_demux_tree
+from pbs_oracle import bk_fft
 
 orc.build()
 writes = int(sys.argv[1]) if len(sys.argv) > 1 else 1024

@@ -4,7 +4,8 @@ meaning cases with the seeds both tests use -- the CPU test checks on the oracle
 oracle's words, so it cannot then fail on noise."""
 import numpy as np
 
-SMALL_N = {1024: 40, 2048: 24}      # the TLWE dimensions of the stage tests
+from kit import SMALL_N  # noqa: F401
+
 EDGE_KS = np.array([0x00007FFF, 0x00008000, 0xFFFF7FFF, 0xFFFF8000, 0xFFFFFFFF, 0], np.uint32)      # EDGE_A of tests/test_gpu_pack.py: the key switch's rounding edges
 EDGES = np.concatenate([np.array([0, 0x80000000, 0xFFFFFFFF], np.uint32), EDGE_KS[:4]])           # ... with the negation's (distinct values)
 

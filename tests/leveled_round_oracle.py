@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE: the leveled entry points with a choice of gadget decomposition (include/rtfhe.h: rtfhe_set_leveled_decomposition).
-The CMUX tree, the TRGSW rotation and the CMUX netlist restated word for word as oracle_cmux_tree (tests/test_cmux_tree_host.py),
-oracle_trgsw_rotate (tests/test_trgsw_rotate_host.py) and oracle_cmux_net (tests/test_cmux_net_host.py) state them, with
+The CMUX tree, the TRGSW rotation and the CMUX netlist restated word for word as oracle_cmux_tree, oracle_trgsw_rotate and
+oracle_cmux_net (tests/leveled_oracle.py) state them, with
 round_oracle.cmux(.., ma, mx) in the place of orc_cmux.  With the reference constants they are those three functions
 (tests/test_leveled_round_host.py); with the rounded constants they are what the ROUNDED = true twins of k_cmux_tree, k_trgsw_rotate and
 k_cmux_net compute (tests/test_gpu_leveled_round.py)."""
@@ -11,7 +11,8 @@ import numpy as np
 import orc
 import round_oracle as ro
 from round_oracle import REFERENCE, ROUNDED  # noqa: F401
-from test_trgsw_rotate_host import default_rot
+from kit import torus_err  # noqa: F401
+from leveled_oracle import as_trlwe, default_rot
 
 U32P = C.POINTER(C.c_uint32)
 
@@ -84,15 +85,8 @@ def noise_bound(depth, N, l=3):
     return float(np.sqrt(depth * (2 * l * N * 18.5 ** 2 * 2.0 ** -50 + (N / 2 + 1) * 2.0 ** -38 / 3)))
 
 
-def torus_err(a, b):
-    """signed torus distance a - b in [-1/2, 1/2)"""
-    d = (np.asarray(a, np.uint32) - np.asarray(b, np.uint32)).astype(np.uint32).view(np.int32).astype(np.float64)
-    return d / 2.0 ** 32
-
-
 def meaning_setup(R, rp, key1, n_rows, seed):
     """n_rows rows of N random 6-bit messages: (msgs [n_rows][N], their torus words, {"plain": trivial TRLWEs, "encrypted": encrypt_lut's})."""
-    from test_cmux_tree_host import as_trlwe
     msgs = np.random.default_rng(seed).integers(0, 1 << MSG_BITS, (n_rows, rp.N))
     plain = R.encode_msgs(msgs, MSG_BITS)
     return msgs, plain, {"plain": as_trlwe(plain, rp.N), "encrypted": R.encrypt_lut(rp, key1, plain, seed=seed + 1)}

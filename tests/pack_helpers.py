@@ -3,13 +3,14 @@ packed row's noise against its inputs' phases."""
 import numpy as np
 
 import pack_oracle as O
+from kit import torus_dist_lsb
 
 ALPHA = 2.0 ** -25
 
 
 def sdist(a, b):
     """distance on the torus of u32 words, in LSB"""
-    return np.abs(((np.asarray(a, np.int64) - np.asarray(b, np.int64) + 2 ** 31) % 2 ** 32) - 2 ** 31)
+    return torus_dist_lsb(a, b)
 
 
 def noise_bound(params, key0, P, rep):

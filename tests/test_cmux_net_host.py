@@ -1,5 +1,5 @@
 """CPU: CMUX netlists (include/rtfhe.h, rtfhe_cmux_circuit_create; rustfhe_amd/cmux_net.py) without a GPU -- the netlist restated with the
-oracle's own building blocks (oracle_cmux_net, which tests/test_gpu_cmux_net.py compares the device's words with), what it means with keys
+oracle's own building blocks (tests/leveled_oracle.py: oracle_cmux_net, which tests/test_gpu_cmux_net.py compares the device's words with), what it means with keys
 and selectors the product generated, the builders' structure, and the entry points' argument checks."""
 import ctypes as C
 
@@ -7,45 +7,9 @@ import numpy as np
 import pytest
 
 import orc as _orc_mod  # noqa: F401  (conftest puts tests/ on the path)
-from test_cmux_tree_host import _torus_dist, as_trlwe
-from test_pbs_host import bk_fft
-
-U32P = C.POINTER(C.c_uint32)
-
-
-def oracle_cmux_net(orc, p, plan, sel_f, sel_idx, rows, netlist, ksk=None):
-    """rtfhe.h's CMUX netlist for one replica, word for word with the reference's arithmetic, node by node in index order.  sel_f: the selectors
-    as FrrSeries (orc_trgsw_to_fft of u32[n_sel][2][2l][N]); sel_idx: this replica's n_vars selector numbers; rows: the table from its row0 on,
-    u32[n][2][N] (as_trlwe).  Node i: orc_rotate_u32 by rot[i] on both polynomials of value(hi[i]), then orc_cmux(S_var[i], rotated, value(lo[i])).
-    Returns the outputs u32[n_out][2][N], or for outputs with coefficients (and ksk) orc_key_switch(orc_sample_extract(node, coef)), u32[n_out][n+1]."""
-    L = orc.lib()
-    N = p.N
-    trgsw = 2 * 2 * p.l * N
-    a = netlist.arrays(N)
-    rows = np.ascontiguousarray(rows, np.uint32).reshape(-1, 2 * N)
-    val = []
-    value = lambda r: val[r] if r >= 0 else rows[-1 - r]  # noqa: E731
-    for var, hi, lo, rot in zip(a["var"], a["hi"], a["lo"], a["rot"]):
-        k = int(sel_idx[var])
-        S = np.ascontiguousarray(sel_f[k * trgsw:(k + 1) * trgsw])
-        h, l = np.ascontiguousarray(value(hi)), np.ascontiguousarray(value(lo))
-        rotated = np.empty(2 * N, np.uint32)
-        for half in range(2):
-            L.orc_rotate_u32(N, h[half * N:].ctypes.data_as(U32P), int(rot), rotated[half * N:].ctypes.data_as(U32P))
-        out = np.empty(2 * N, np.uint32)
-        L.orc_cmux(C.byref(p), plan.h, S.ctypes.data_as(C.POINTER(C.c_double)), None, rotated.ctypes.data_as(U32P), l.ctypes.data_as(U32P),
-                   out.ctypes.data_as(U32P))
-        val.append(out)
-    if a["out_coef"] is None:
-        return np.stack([val[r].reshape(2, N) for r in a["out_ref"]])
-    return np.stack([orc.key_switch(p, ksk, orc.sample_extract(p, val[r], int(c))) for r, c in zip(a["out_ref"], a["out_coef"])])
-
-
-def three_of_five(bits):
-    """the 3-output function of 5 variables of the meaning test: the majority of the low three bits, divisibility by three, and a mixed term"""
-    x = sum(b << v for v, b in enumerate(bits))
-    return (int(bits[0] + bits[1] + bits[2] >= 2), int(x % 3 == 0), bits[3] ^ (bits[0] & bits[4]))
-
+from kit import torus_dist
+from leveled_oracle import as_trlwe, comparator_netlist, oracle_cmux_net, three_of_five
+from pbs_oracle import bk_fft
 
 @pytest.mark.parametrize("N", [1024, 2048])
 def test_oracle_net_means_its_function(orc, N, capsys):
@@ -74,7 +38,7 @@ def test_oracle_net_means_its_function(orc, N, capsys):
                 assert np.array_equal(want[o], plain[0 if f else 1]), (x, o)
             ph = R.trlwe_phase(rp, key1, got)
             assert np.array_equal(R.decode_msgs(ph, 2), R.decode_msgs(want, 2)), (kind, x)
-            worst[kind] = max(worst.get(kind, 0.0), float(_torus_dist(ph, want).max()))
+            worst[kind] = max(worst.get(kind, 0.0), float(torus_dist(ph, want).max()))
     with capsys.disabled():
         print("\noracle CMUX net, N = %d, %d nodes on %d levels: largest torus distance from evaluate_plain %s"
               % (N, net.n_nodes, levels, {k: round(v, 5) for k, v in worst.items()}))
@@ -125,17 +89,6 @@ def test_bdd_equals_its_function_on_every_input():
         for x in range(64):
             bits = tuple((x >> v) & 1 for v in range(6))
             assert net.evaluate_plain(bits, rows)[:, 0].tolist() == list(f(bits)), (order, x)
-
-
-def comparator_netlist(bits):
-    """a < b on two `bits`-bit numbers: variables 0 .. bits-1 are a (LSB first), bits .. 2 bits-1 are b; interleaved order, MSB first"""
-    import rustfhe_amd as R
-    order = [v for i in reversed(range(bits)) for v in (i, bits + i)]
-
-    def less(b):
-        a_, b_ = sum(b[i] << i for i in range(bits)), sum(b[bits + i] << i for i in range(bits))
-        return int(a_ < b_)
-    return R.bdd_netlist(2 * bits, less, order)
 
 
 def test_comparator_under_the_interleaved_order_is_small():

@@ -1,5 +1,5 @@
 """CPU: CMUX-tree table lookup (include/rtfhe.h, rtfhe_cmux_tree_batch) without a GPU -- the tree restated with the oracle's own building
-blocks (oracle_cmux_tree, which tests/test_gpu_cmux_tree.py compares the device's words with), what it means with keys and selectors the
+blocks (tests/leveled_oracle.py: oracle_cmux_tree, which tests/test_gpu_cmux_tree.py compares the device's words with), what it means with keys and selectors the
 product generated, the host TRGSW encryption of selector bits, and the entry points' argument checks."""
 import ctypes as C
 
@@ -7,48 +7,9 @@ import numpy as np
 import pytest
 
 import orc as _orc_mod  # noqa: F401  (conftest puts tests/ on the path)
-from test_pbs_host import bk_fft
-
-U32P = C.POINTER(C.c_uint32)
-
-
-def as_trlwe(rows, N):
-    """table rows as TRLWEs u32[n][2][N]: a plain row tv is the trivial (b = tv, a = 0)"""
-    rows = np.ascontiguousarray(rows, np.uint32)
-    if rows.ndim == 3:
-        return rows
-    rows = rows.reshape(-1, N)
-    return np.stack([rows, np.zeros_like(rows)], axis=1)
-
-
-def oracle_cmux_tree(orc, p, plan, sel_f, sel_idx, rows, coef=None, ksk=None):
-    """rtfhe.h's CMUX tree, word for word with the reference's arithmetic.  sel_f: the selectors as FrrSeries (orc_trgsw_to_fft of
-    u32[n_sel][2][2l][N]); sel_idx: the depth selector numbers of this lookup, address bit 0 first; rows: its 2^depth level-0 nodes,
-    u32[2^depth][2][N] (as_trlwe).  Level k: r'_j = orc_cmux(S_k, r_{2j+1}, r_{2j}).  Returns the result u32[2][N], or with coef (and ksk) given
-    orc_key_switch(orc_sample_extract(result, coef)), u32[n+1]."""
-    L = orc.lib()
-    N = p.N
-    trgsw = 2 * 2 * p.l * N
-    nodes = [np.ascontiguousarray(r, np.uint32).reshape(2 * N) for r in rows]
-    assert len(nodes) == 1 << len(sel_idx)
-    for k in sel_idx:
-        S = np.ascontiguousarray(sel_f[int(k) * trgsw:(int(k) + 1) * trgsw])
-        nxt = []
-        for j in range(len(nodes) // 2):
-            out = np.empty(2 * N, np.uint32)
-            L.orc_cmux(C.byref(p), plan.h, S.ctypes.data_as(C.POINTER(C.c_double)), None, nodes[2 * j + 1].ctypes.data_as(U32P),
-                       nodes[2 * j].ctypes.data_as(U32P), out.ctypes.data_as(U32P))
-            nxt.append(out)
-        nodes = nxt
-    if coef is None:
-        return nodes[0].reshape(2, N)
-    return orc.key_switch(p, ksk, orc.sample_extract(p, nodes[0], int(coef)))
-
-
-def _torus_dist(a, b):
-    d = (np.asarray(a, np.uint32) - np.asarray(b, np.uint32)).astype(np.uint32).view(np.int32).astype(np.int64)
-    return np.abs(d) / 2.0 ** 32
-
+from kit import torus_dist
+from leveled_oracle import as_trlwe, oracle_cmux_tree
+from pbs_oracle import bk_fft
 
 @pytest.mark.parametrize("N", [1024, 2048])
 def test_oracle_tree_selects_the_addressed_row(orc, N, capsys):
@@ -73,7 +34,7 @@ def test_oracle_tree_selects_the_addressed_row(orc, N, capsys):
                 got = oracle_cmux_tree(orc, p, plan, bk_fft(orc, p, plan, sel.reshape(-1)), range(depth), rows)
                 ph = R.trlwe_phase(rp, key1, got[None])[0]
                 assert np.array_equal(R.decode_msgs(ph, 2), msgs[addr]), (depth, kind, addr)
-                worst[depth, kind] = max(worst.get((depth, kind), 0.0), float(_torus_dist(ph, plain[addr]).max()))
+                worst[depth, kind] = max(worst.get((depth, kind), 0.0), float(torus_dist(ph, plain[addr]).max()))
     with capsys.disabled():
         print("\noracle CMUX tree, N = %d: largest torus distance from the addressed row %s" % (N, {k: round(v, 5) for k, v in worst.items()}))
     for (depth, kind), w in worst.items():
@@ -111,7 +72,7 @@ def test_encrypted_selectors_behave_as_bk_entries_do(orc, N):
         for bit in (0, 1):
             got = oracle_cmux_tree(orc, p, plan, sel_f, [bit], reps)
             ph = R.trlwe_phase(rp, key1, got[None])[0]
-            assert _torus_dist(ph, pols[bit]).max() < 2e-3 * N / 1024, (seed, bit)
+            assert torus_dist(ph, pols[bit]).max() < 2e-3 * N / 1024, (seed, bit)
             rows = sel[bit].reshape(2, 2 * p.l, N)
             for j in range(2 * p.l):
                 ph = R.trlwe_phase(rp, key1, np.stack([rows[0, j], rows[1, j]])[None])[0].astype(np.int64)

@@ -1,5 +1,5 @@
 """CPU: the CMUX demultiplexer tree (include/rtfhe.h, rtfhe_demux_tree_batch) without a GPU -- the demultiplexer restated with the oracle's
-own building blocks (oracle_demux_tree, which tests/test_gpu_demux_tree.py compares the device's words with), what it means with keys and
+own building blocks (tests/leveled_oracle.py: oracle_demux_tree, which tests/test_gpu_demux_tree.py compares the device's words with), what it means with keys and
 selectors the product generated, that it is the inverse of the CMUX tree, and the entry points' argument checks that need no device."""
 import ctypes as C
 
@@ -8,39 +8,9 @@ import pytest
 
 import orc as _orc_mod  # noqa: F401  (conftest puts tests/ on the path)
 import round_oracle as ro
-from test_cmux_tree_host import _torus_dist, as_trlwe, oracle_cmux_tree
-from test_pbs_host import bk_fft
-
-U32P = C.POINTER(C.c_uint32)
-
-
-def oracle_demux_tree(orc, p, plan, sel_f, sel_idx, x, mode=ro.REFERENCE):
-    """rtfhe.h's demultiplexer, word for word with the reference's arithmetic.  sel_f: the selectors as FrrSeries (orc_trgsw_to_fft of
-    u32[n_sel][2][2l][N]); sel_idx: the depth selector numbers of this lookup, address bit 0 first; x: u32[2][N].  Level t = 0 .. depth-1 uses
-    selector k = depth - 1 - t: hi = orc_cmux(S_k, node, zeros) (cross(S, x) = cmux(S, x, 0)), lo = node - hi, children (lo, hi) at 2j, 2j + 1.
-    In rounded mode round_oracle.cmux(.., ma, mx) takes orc_cmux's place, as in tests/leveled_round_oracle.py.  Returns u32[2^depth][2][N]."""
-    L = orc.lib()
-    N = p.N
-    trgsw = 2 * 2 * p.l * N
-    zeros = np.zeros(2 * N, np.uint32)
-    ma, mx = ro.constants(p.l, p.bgbit, mode)
-    depth = len(sel_idx)
-    nodes = [np.ascontiguousarray(x, np.uint32).reshape(2 * N).copy()]
-    for t in range(depth):
-        k = int(sel_idx[depth - 1 - t])
-        S = np.ascontiguousarray(sel_f[k * trgsw:(k + 1) * trgsw])
-        nxt = []
-        for node in nodes:
-            if mode == ro.REFERENCE:
-                hi = np.empty(2 * N, np.uint32)
-                L.orc_cmux(C.byref(p), plan.h, S.ctypes.data_as(C.POINTER(C.c_double)), None, node.ctypes.data_as(U32P), zeros.ctypes.data_as(U32P),
-                           hi.ctypes.data_as(U32P))
-            else:
-                hi = ro.cmux(p, plan, S, node, zeros, ma, mx)
-            nxt += [node - hi, hi]
-        nodes = nxt
-    return np.stack(nodes).reshape(1 << depth, 2, N)
-
+from kit import torus_dist
+from leveled_oracle import as_trlwe, oracle_cmux_tree, oracle_demux_tree
+from pbs_oracle import bk_fft
 
 @pytest.mark.parametrize("N", [1024, 2048])
 def test_oracle_demux_writes_the_addressed_leaf(orc, N, capsys):
@@ -73,7 +43,7 @@ def test_oracle_demux_writes_the_addressed_leaf(orc, N, capsys):
                 assert np.array_equal(R.decode_msgs(ph, 2), want), (depth, kind, addr)
                 target = np.tile(zero, (1 << depth, 1))
                 target[addr] = plain
-                worst[depth, kind] = max(worst.get((depth, kind), 0.0), float(_torus_dist(ph, target).max()))
+                worst[depth, kind] = max(worst.get((depth, kind), 0.0), float(torus_dist(ph, target).max()))
                 back = oracle_cmux_tree(orc, p, plan, sel_f, range(depth), leaves)
                 assert np.array_equal(R.decode_msgs(R.trlwe_phase(rp, key1, back[None])[0], 2), msgs), (depth, kind, addr, "inverse")
     with capsys.disabled():

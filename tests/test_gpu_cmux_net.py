@@ -1,20 +1,18 @@
 """GPU: CMUX netlists (rtfhe_cmux_circuit_create, rtfhe_trgsw_update; the k_cmux_net kernels).  Every word against the oracle's netlist
-(tests/test_cmux_net_host.py: oracle_cmux_net) at both N on a mixed netlist of 11 nodes, plain and encrypted tables, counts 1, 5 and 37, both
+(tests/leveled_oracle.py: oracle_cmux_net) at both N on a mixed netlist of 11 nodes, plain and encrypted tables, counts 1, 5 and 37, both
 output forms and both key-switch routes; second opinions from the tree and the rotation entry points; replay, selector update and a destroyed
 set; skipped replicas; what a comparator means; refusals.  Small TLWE dimensions as the tree tests use: n = 40 at N = 1024, n = 24 at N = 2048."""
-import types
-
 import numpy as np
 import pytest
 
-from test_cmux_net_host import comparator_netlist, oracle_cmux_net
-from test_cmux_tree_host import as_trlwe
-from test_gpu_pbs import _engine, _random_words
-from test_pbs_host import bk_fft
+import gpu_kit as gk
+from kit import random_words
+from leveled_kit import net_run, selector_world
+from leveled_oracle import as_trlwe, comparator_netlist, oracle_cmux_net
+from pbs_oracle import bk_fft
 
 pytestmark = pytest.mark.gpu
 
-SMALL_N = {1024: 40, 2048: 24}
 N_VARS = 5
 N_SEL = 37 * N_VARS      # sel_idx = NULL at 37 replicas reads selectors 0 .. 184
 N_ROWS = 8 + 7           # the mixed netlist names rows 0 .. 7, row0 up to 7
@@ -48,19 +46,10 @@ def mixed_netlist(R, N, coefs=None):
 def world(request, orc):
     """Per N: keys from the product's keygen on an engine, N_SEL selectors of known random bits (device handle, torus words and the oracle's
     spectra of them), one plain and one really encrypted table of N_ROWS random rows."""
-    import rustfhe_amd as R
     N = request.param
-    rp = R.Params(n=SMALL_N[N], N=N)
-    key0, key1, bk, ksk = R.keygen(rp, 0x9E7 + N)
-    w = types.SimpleNamespace(R=R, N=N, rp=rp, key0=key0, key1=key1, bk=bk, ksk=ksk)
-    w.P = orc.Params(n=rp.n, N=N)
-    w.plan = orc.Plan(N)
-    rng = np.random.default_rng(N + 17)
-    w.bits = rng.integers(0, 2, N_SEL).astype(np.uint8)
-    w.sel_t = R.encrypt_selectors(rp, key1, w.bits, seed=0x5E1EC8 + N)
-    w.sel_f = bk_fft(orc, w.P, w.plan, w.sel_t.reshape(-1))
-    w.rows = {"plain": _random_words(rng, (N_ROWS, N)), "encrypted": R.encrypt_lut(rp, key1, _random_words(rng, (N_ROWS, N)), seed=0x7AC + N)}
-    w.eng = _engine(R, rp, bk, ksk)
+    w, rng = selector_world(orc, N, 0x9E7 + N, N + 17, N_SEL, 0x5E1EC8 + N, known=())
+    w.rows = {"plain": random_words(rng, (N_ROWS, N)), "encrypted": w.R.encrypt_lut(w.rp, w.key1, random_words(rng, (N_ROWS, N)), seed=0x7AC + N)}
+    w.eng = gk.engine(w.R, w.rp, w.bk, w.ksk)
     w.sel = w.eng.selectors(w.sel_t)
     w.lut = {"plain": w.eng.lut(w.rows["plain"]), "encrypted": w.eng.lut_encrypted(w.rows["encrypted"])}
     w.oracle_memo = {}
@@ -73,34 +62,12 @@ def world(request, orc):
 def _oracle(orc, w, kind, sel_idx, row0, coefs=None, sel_f=None, tag=None):
     """the oracle's mixed netlist of every replica: sel_idx [count][5], row0 [count]; computed once per world and arguments, shared by the tests
     that ask for the same replicas, and read-only"""
-    key = (kind, sel_idx.tobytes(), row0.tobytes(), coefs, tag)
-    if key not in w.oracle_memo:
+    def compute():
         net = mixed_netlist(w.R, w.N, coefs)
         rows = as_trlwe(w.rows[kind], w.N)
-        want = np.stack([oracle_cmux_net(orc, w.P, w.plan, w.sel_f if sel_f is None else sel_f, sel_idx[g], rows[row0[g]:], net, w.ksk)
+        return np.stack([oracle_cmux_net(orc, w.P, w.plan, w.sel_f if sel_f is None else sel_f, sel_idx[g], rows[row0[g]:], net, w.ksk)
                          for g in range(len(row0))])
-        want.setflags(write=False)
-        w.oracle_memo[key] = want
-    return w.oracle_memo[key]
-
-
-def _cuda(a, dtype=np.int32):
-    import torch
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype).view(np.int32)).cuda()
-
-
-def _run(w, net, lut, count, sel_idx=None, row0=None, on=None, sel=None):
-    """records the netlist on the world's engine (or `on`), replays it once and returns d_out's words"""
-    import torch
-    eng = on or w.eng
-    n_out = len(net.outputs)
-    shape = (count, n_out, 2, w.N) if net.outputs[0][1] is None else (count, n_out, w.rp.n + 1)
-    d_out = torch.zeros(shape, dtype=torch.int32, device="cuda")
-    st = torch.cuda.current_stream().cuda_stream
-    with eng.cmux_circuit(net, sel or w.sel, lut, d_out, count, _cuda(sel_idx), _cuda(row0)) as c:
-        c.launch(st)
-        eng.sync(st)
-    return d_out.cpu().numpy().view(np.uint32)
+    return gk.memo(w.oracle_memo, (kind, sel_idx, row0, coefs, tag), compute)
 
 
 def _replicas(count):
@@ -124,7 +91,7 @@ def test_every_word_equals_the_oracle_net(orc, world, count):
     for kind in ("plain", "encrypted"):
         for sel_idx, row0, exp_idx, exp_row0 in _replicas(count):
             want = _oracle(orc, w, kind, exp_idx, exp_row0)
-            got = _run(w, net, w.lut[kind], count, sel_idx, row0)
+            got = net_run(w, net, w.lut[kind], count, sel_idx, row0)
             assert got.shape == (count, 3, 2, w.N)
             assert np.array_equal(got, want), (kind, sel_idx is None, np.argwhere((got != want).any(axis=(2, 3)))[:8])
 
@@ -137,14 +104,14 @@ def test_extract_form_equals_the_oracle(orc, world, monkeypatch):
     net = mixed_netlist(w.R, w.N, coefs)
     count = 5
     (sel_idx, row0, _, _), _ = _replicas(count)
-    plain_route = _engine(w.R, w.rp, w.bk, w.ksk, monkeypatch, {"RTFHE_KS_MM_MIN": "0"})
+    plain_route = gk.engine(w.R, w.rp, w.bk, w.ksk, monkeypatch, {"RTFHE_KS_MM_MIN": "0"})
     try:
         for kind in ("plain", "encrypted"):
             want = _oracle(orc, w, kind, sel_idx, row0, coefs)
-            got = _run(w, net, w.lut[kind], count, sel_idx, row0)
+            got = net_run(w, net, w.lut[kind], count, sel_idx, row0)
             assert got.shape == (count, 3, w.rp.n + 1) and np.array_equal(got, want), kind
             with plain_route.selectors(w.sel_t[:7]) as sel, (plain_route.lut(w.rows[kind]) if kind == "plain" else plain_route.lut_encrypted(w.rows[kind])) as lut:
-                assert np.array_equal(_run(w, net, lut, count, sel_idx, row0, on=plain_route, sel=sel), want), kind
+                assert np.array_equal(net_run(w, net, lut, count, sel_idx, row0, on=plain_route, sel=sel), want), kind
     finally:
         plain_route.close()
 
@@ -159,7 +126,7 @@ def test_tree_netlist_equals_the_tree_entry(world):
     net = w.R.cmux_tree_netlist(3)
     for kind in ("plain", "encrypted"):
         want = w.eng.cmux_tree_batch(w.sel, w.lut[kind], 3, count, sel_idx, row0)
-        assert np.array_equal(_run(w, net, w.lut[kind], count, sel_idx, row0)[:, 0], want), kind
+        assert np.array_equal(net_run(w, net, w.lut[kind], count, sel_idx, row0)[:, 0], want), kind
 
 
 def test_rotation_netlist_equals_the_rotation_entry(world):
@@ -172,11 +139,11 @@ def test_rotation_netlist_equals_the_rotation_entry(world):
     rot = [2 * w.N - 1, 0, w.N, 1, int(rng.integers(0, 2 * w.N))]
     rows = as_trlwe(w.rows["encrypted"], w.N)[:count]
     want = w.eng.trgsw_rotate_batch(w.sel, rows, 5, sel_idx, rot)
-    got = _run(w, w.R.trgsw_rotate_netlist(5, rot), w.lut["encrypted"], count, sel_idx, np.arange(count, dtype=np.int32))
+    got = net_run(w, w.R.trgsw_rotate_netlist(5, rot), w.lut["encrypted"], count, sel_idx, np.arange(count, dtype=np.int32))
     assert np.array_equal(got[:, 0], want)
     # rot None is X^-2^k, the entry's default
     want = w.eng.trgsw_rotate_batch(w.sel, rows, 5, sel_idx)
-    got = _run(w, w.R.trgsw_rotate_netlist(5), w.lut["encrypted"], count, sel_idx, np.arange(count, dtype=np.int32))
+    got = net_run(w, w.R.trgsw_rotate_netlist(5), w.lut["encrypted"], count, sel_idx, np.arange(count, dtype=np.int32))
     assert np.array_equal(got[:, 0], want)
 
 
@@ -193,7 +160,7 @@ def test_replay_update_and_a_destroyed_set(orc, world):
     words = lambda: d_out.cpu().numpy().view(np.uint32)  # noqa: E731
     st = torch.cuda.current_stream().cuda_stream
     sel = w.eng.selectors(w.sel_t[:7])
-    c = w.eng.cmux_circuit(net, sel, w.lut["encrypted"], d_out, count, _cuda(sel_idx), _cuda(row0))
+    c = w.eng.cmux_circuit(net, sel, w.lut["encrypted"], d_out, count, gk.to_device(sel_idx), gk.to_device(row0))
     try:
         c.launch(st)
         w.eng.sync(st)
@@ -256,7 +223,7 @@ def test_skipped_replicas(orc, world):
             net = mixed_netlist(R, w.N, coefs)
             want = _oracle(orc, w, "encrypted", sel_idx, row0, coefs)
             guarded = torch.full((count + 2,) + want.shape[1:], int(sentinel), dtype=torch.int32, device="cuda")
-            with w.eng.cmux_circuit(net, sel, w.lut["encrypted"], guarded[1:], count, _cuda(bad_sel), _cuda(bad_row)) as c:
+            with w.eng.cmux_circuit(net, sel, w.lut["encrypted"], guarded[1:], count, gk.to_device(bad_sel), gk.to_device(bad_row)) as c:
                 c.launch(st)
                 with pytest.raises(R.RtfheError) as ei:
                     w.eng.sync(st)
@@ -290,7 +257,7 @@ def test_comparator_means_less_than(world):
     rows = np.zeros((2, w.N), np.uint32)
     rows[0, 0], rows[1, 0] = 0x20000000, 0xE0000000
     with w.eng.selectors(sel_t) as sel, w.eng.lut(rows) as lut:
-        y = _run(w, out, lut, 256, sel_idx, sel=sel)[:, 0]
+        y = net_run(w, out, lut, 256, sel_idx, sel=sel)[:, 0]
     assert np.array_equal(R.decrypt_bits(w.rp, w.key0, y).astype(bool), a < b)
     assert np.array_equal(R.decrypt_bits(w.rp, w.key0, w.eng.gate_batch(R.NAND, y, y)).astype(bool), ~(a < b))
 
@@ -339,7 +306,7 @@ def test_refusals(world):
         w.eng.cmux_circuit(net(), w.sel, lut, d_out, 0)
     assert ei.value.code == R._ffi.ERR_INVALID and "at least 1" in str(ei.value)
     assert w.eng.timer_end()[1] == 0, "the checks come before any launch"
-    ref = _run(w, net(), lut, 5)
+    ref = net_run(w, net(), lut, 5)
     try:
         for b in (R._ffi.BACKEND_NTT_EXACT, R._ffi.BACKEND_FFT_SPLIT_EXACT):
             w.eng.set_backend(b)
@@ -348,12 +315,12 @@ def test_refusals(world):
             assert ei.value.code == R._ffi.ERR_INVALID and "mirror" in str(ei.value)
     finally:
         w.eng.set_backend(R._ffi.BACKEND_FFT64_MIRROR)
-    assert np.array_equal(_run(w, net(), lut, 5), ref)
+    assert np.array_equal(net_run(w, net(), lut, 5), ref)
     # no key-switching key: the TRLWE form runs (a netlist needs no key of the context), the extract form is refused
     bare = R.Engine(R.Params(n=w.rp.n, N=N), 0)
     try:
         with bare.selectors(w.sel_t[:25]) as sel, bare.lut(w.rows["plain"]) as blut:
-            assert np.array_equal(_run(w, net(), blut, 5, on=bare, sel=sel), ref)
+            assert np.array_equal(net_run(w, net(), blut, 5, on=bare, sel=sel), ref)
             with pytest.raises(R.RtfheError) as ei:
                 bare.cmux_circuit(net(coefs=(0, 1, 2)), sel, blut, d_out, 5)
             assert ei.value.code == R._ffi.ERR_STATE and "key-switching key" in str(ei.value)

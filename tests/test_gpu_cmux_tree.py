@@ -1,42 +1,27 @@
 """GPU: CMUX-tree table lookup with caller-supplied TRGSW selectors (rtfhe_trgsw_create, rtfhe_cmux_tree_batch[_dev],
-rtfhe_cmux_tree_extract_batch[_dev]; the k_cmux_tree kernels).  Every word against the oracle's tree (tests/test_cmux_tree_host.py:
+rtfhe_cmux_tree_extract_batch[_dev]; the k_cmux_tree kernels).  Every word against the oracle's tree (tests/leveled_oracle.py:
 oracle_cmux_tree) at both N, every depth 1 .. 4 and counts 1, 5 and 37; the extract form; a second opinion built from
 rtfhe_external_product_batch alone; what the tree means; its composition with the PBS from encrypted tables; refusals and the capture rule.
 Small TLWE dimensions as the other stage tests use: n = 40 at N = 1024, n = 24 at N = 2048."""
-import types
-
 import numpy as np
 import pytest
 
-from test_cmux_tree_host import as_trlwe, oracle_cmux_tree
-from test_gpu_pbs import _engine, _random_words
-from test_pbs_host import bk_fft
+import gpu_kit as gk
+from kit import random_words
+from leveled_kit import TREE_N_ROWS, TREE_N_SEL, selector_world, tree_dev, tree_lookups, tree_oracle
+from leveled_oracle import as_trlwe
 
 pytestmark = pytest.mark.gpu
-
-SMALL_N = {1024: 40, 2048: 24}
-N_SEL = 37 * 4          # sel_idx = NULL at depth 4 and 37 lookups reads selectors 0 .. 147
-N_ROWS = 16 + 7         # row0 up to 7 at depth 4
 
 
 @pytest.fixture(scope="module", params=[1024, 2048], ids=lambda N: "N%d" % N)
 def world(request, orc):
-    """Per N: keys from the product's keygen on an engine, N_SEL selectors of known random bits (device handle, torus words and the oracle's
-    spectra of them), one plain and one really encrypted table of N_ROWS random rows."""
-    import rustfhe_amd as R
+    """Per N: keys from the product's keygen on an engine, TREE_N_SEL selectors of known random bits (device handle, torus words and the oracle's
+    spectra of them), one plain and one really encrypted table of TREE_N_ROWS random rows."""
     N = request.param
-    rp = R.Params(n=SMALL_N[N], N=N)
-    key0, key1, bk, ksk = R.keygen(rp, 0x7EE + N)
-    w = types.SimpleNamespace(R=R, N=N, rp=rp, key0=key0, key1=key1, bk=bk, ksk=ksk)
-    w.P = orc.Params(n=rp.n, N=N)
-    w.plan = orc.Plan(N)
-    rng = np.random.default_rng(N + 11)
-    w.bits = rng.integers(0, 2, N_SEL).astype(np.uint8)
-    w.bits[:2] = (0, 1)
-    w.sel_t = R.encrypt_selectors(rp, key1, w.bits, seed=0x5E1EC7 + N)
-    w.sel_f = bk_fft(orc, w.P, w.plan, w.sel_t.reshape(-1))
-    w.rows = {"plain": _random_words(rng, (N_ROWS, N)), "encrypted": R.encrypt_lut(rp, key1, _random_words(rng, (N_ROWS, N)), seed=0x7AB + N)}
-    w.eng = _engine(R, rp, bk, ksk)
+    w, rng = selector_world(orc, N, 0x7EE + N, N + 11, TREE_N_SEL, 0x5E1EC7 + N)
+    w.rows = {"plain": random_words(rng, (TREE_N_ROWS, N)), "encrypted": w.R.encrypt_lut(w.rp, w.key1, random_words(rng, (TREE_N_ROWS, N)), seed=0x7AB + N)}
+    w.eng = gk.engine(w.R, w.rp, w.bk, w.ksk)
     w.sel = w.eng.selectors(w.sel_t)
     w.lut = {"plain": w.eng.lut(w.rows["plain"]), "encrypted": w.eng.lut_encrypted(w.rows["encrypted"])}
     w.oracle_memo = {}
@@ -44,51 +29,6 @@ def world(request, orc):
     for h in (w.sel, w.lut["plain"], w.lut["encrypted"]):
         h.close()
     w.eng.close()
-
-
-def _oracle(orc, w, kind, depth, sel_idx, row0, coef=None):
-    """the oracle's tree of every lookup: sel_idx [count][depth], row0 [count], coef [count] or None; computed once per world and arguments,
-    shared by the tests that ask for the same lookups, and read-only"""
-    key = (kind, depth, sel_idx.tobytes(), row0.tobytes(), None if coef is None else coef.tobytes())
-    if key not in w.oracle_memo:
-        rows = as_trlwe(w.rows[kind], w.N)
-        want = np.stack([oracle_cmux_tree(orc, w.P, w.plan, w.sel_f, sel_idx[g], rows[row0[g]:row0[g] + (1 << depth)],
-                                          None if coef is None else coef[g], w.ksk) for g in range(len(row0))])
-        want.setflags(write=False)
-        w.oracle_memo[key] = want
-    return w.oracle_memo[key]
-
-
-def _cuda(a):
-    import torch
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
-
-
-def _tree_dev(w, kind, depth, count, sel_idx, row0, coef=None, extract=False, on=None):
-    """the _dev form on the world's engine, selectors and tables, or on=(engine, selectors, table)"""
-    import torch
-    eng, sel, lut = on or (w.eng, w.sel, w.lut[kind])
-    st = torch.cuda.current_stream().cuda_stream
-    if extract:
-        d_out = torch.zeros((count, w.rp.n + 1), dtype=torch.int32, device="cuda")
-        eng.cmux_tree_extract_batch_dev(sel, lut, depth, d_out, count, _cuda(sel_idx), _cuda(row0), _cuda(coef), st)
-    else:
-        d_out = torch.zeros((count, 2, w.N), dtype=torch.int32, device="cuda")
-        eng.cmux_tree_batch_dev(sel, lut, depth, d_out, count, _cuda(sel_idx), _cuda(row0), st)
-    eng.sync(st)
-    return d_out.cpu().numpy().view(np.uint32)
-
-
-def _lookups(depth, count):
-    """(sel_idx, row0, and what they mean to the oracle) twice: six selectors shared between the lookups with row0 non-zero and differing per
-    lookup; then sel_idx = NULL and row0 = NULL"""
-    rng = np.random.default_rng(100 * depth + count)
-    shared = rng.integers(0, 6, (count, depth)).astype(np.int32)             # six selectors serve every lookup
-    rows0 = rng.integers(1, N_ROWS - (1 << depth) + 1, count).astype(np.int32)
-    if count > 1:
-        rows0[0], rows0[1] = 1, N_ROWS - (1 << depth)                        # they differ, and one lookup ends on the table's last row
-    default_idx = np.arange(count * depth, dtype=np.int32).reshape(count, depth)
-    return (shared, rows0, shared, rows0), (None, None, default_idx, np.zeros(count, np.int32))
 
 
 @pytest.mark.parametrize("count", [1, 5, 37])
@@ -100,12 +40,12 @@ def test_every_word_equals_the_oracle_tree(orc, world, depth, count):
     two levels: no multiple of a wave count."""
     w = world
     for kind in ("plain", "encrypted"):
-        for sel_idx, row0, exp_idx, exp_row0 in _lookups(depth, count):
-            want = _oracle(orc, w, kind, depth, exp_idx, exp_row0)
+        for sel_idx, row0, exp_idx, exp_row0 in tree_lookups(depth, count):
+            want = tree_oracle(orc, w, kind, depth, exp_idx, exp_row0)
             got = w.eng.cmux_tree_batch(w.sel, w.lut[kind], depth, count, sel_idx, row0)
             assert got.shape == (count, 2, w.N)
             assert np.array_equal(got, want), (kind, sel_idx is None, np.flatnonzero((got != want).any(axis=(1, 2)))[:8])
-            assert np.array_equal(_tree_dev(w, kind, depth, count, sel_idx, row0), got), (kind, sel_idx is None)
+            assert np.array_equal(tree_dev(w, kind, depth, count, sel_idx, row0), got), (kind, sel_idx is None)
 
 
 def test_extract_form_equals_the_oracle(orc, world):
@@ -113,15 +53,15 @@ def test_extract_form_equals_the_oracle(orc, world):
     w = world
     depth, count = 3, 7
     rng = np.random.default_rng(w.N + 31)
-    sel_idx = rng.integers(0, N_SEL, (count, depth)).astype(np.int32)
-    row0 = rng.integers(0, N_ROWS - 8 + 1, count).astype(np.int32)
+    sel_idx = rng.integers(0, TREE_N_SEL, (count, depth)).astype(np.int32)
+    row0 = rng.integers(0, TREE_N_ROWS - 8 + 1, count).astype(np.int32)
     coef = np.array([0, 1, w.N - 1, w.N - 1, 1, 0, w.N // 2 + 3], np.int32)
     for kind in ("plain", "encrypted"):
         for cf, exp in ((coef, coef), (None, np.zeros(count, np.int32))):
-            want = _oracle(orc, w, kind, depth, sel_idx, row0, exp)
+            want = tree_oracle(orc, w, kind, depth, sel_idx, row0, exp)
             got = w.eng.cmux_tree_extract_batch(w.sel, w.lut[kind], depth, count, sel_idx, row0, cf)
             assert got.shape == (count, w.rp.n + 1) and np.array_equal(got, want), (kind, cf is None)
-            assert np.array_equal(_tree_dev(w, kind, depth, count, sel_idx, row0, cf, extract=True), got), (kind, cf is None)
+            assert np.array_equal(tree_dev(w, kind, depth, count, sel_idx, row0, cf, extract=True), got), (kind, cf is None)
 
 
 def test_extract_form_of_a_single_level(orc, world):
@@ -131,18 +71,18 @@ def test_extract_form_of_a_single_level(orc, world):
     w = world
     depth, count = 1, 5
     sel_idx = np.array([[0], [1], [1], [7], [0]], np.int32)
-    row0 = np.array([0, N_ROWS - 2, 3, 3, 8], np.int32)
+    row0 = np.array([0, TREE_N_ROWS - 2, 3, 3, 8], np.int32)
     coef = np.array([0, 1, w.N - 1, w.N // 2 + 3, 0], np.int32)
-    e = _engine(w.R, w.rp, w.bk, w.ksk)
+    e = gk.engine(w.R, w.rp, w.bk, w.ksk)
     try:
         with e.selectors(w.sel_t[:8]) as sel:
             for kind in ("plain", "encrypted"):
                 with (e.lut(w.rows[kind]) if kind == "plain" else e.lut_encrypted(w.rows[kind])) as lut:
                     for cf, exp in ((coef, coef), (None, np.zeros(count, np.int32))):
-                        want = _oracle(orc, w, kind, depth, sel_idx, row0, exp)
+                        want = tree_oracle(orc, w, kind, depth, sel_idx, row0, exp)
                         got = e.cmux_tree_extract_batch(sel, lut, depth, count, sel_idx, row0, cf)
                         assert got.shape == (count, w.rp.n + 1) and np.array_equal(got, want), (kind, cf is None)
-                        assert np.array_equal(_tree_dev(w, kind, depth, count, sel_idx, row0, cf, extract=True, on=(e, sel, lut)), got), (kind, cf is None)
+                        assert np.array_equal(tree_dev(w, kind, depth, count, sel_idx, row0, cf, extract=True, on=(e, sel, lut)), got), (kind, cf is None)
     finally:
         e.close()
 
@@ -150,7 +90,7 @@ def test_extract_form_of_a_single_level(orc, world):
 def test_extract_form_with_the_wave_per_sample_key_switch(orc, world, monkeypatch):
     """RTFHE_KS_MM_MIN=0: a context without the matrix form of the key-switching key runs k_key_switch_ext after the tree; the same words."""
     w = world
-    e = _engine(w.R, w.rp, w.bk, w.ksk, monkeypatch, {"RTFHE_KS_MM_MIN": "0"})
+    e = gk.engine(w.R, w.rp, w.bk, w.ksk, monkeypatch, {"RTFHE_KS_MM_MIN": "0"})
     try:
         depth, count = 2, 5
         sel_idx = np.array([[0, 1], [1, 0], [2, 3], [5, 5], [1, 1]], np.int32)
@@ -158,7 +98,7 @@ def test_extract_form_with_the_wave_per_sample_key_switch(orc, world, monkeypatc
         coef = np.array([0, 1, w.N - 1, 17, 0], np.int32)
         with e.selectors(w.sel_t[:6]) as sel, e.lut_encrypted(w.rows["encrypted"]) as lut:
             got = e.cmux_tree_extract_batch(sel, lut, depth, count, sel_idx, row0, coef)
-        assert np.array_equal(got, _oracle(orc, w, "encrypted", depth, sel_idx, row0, coef))
+        assert np.array_equal(got, tree_oracle(orc, w, "encrypted", depth, sel_idx, row0, coef))
     finally:
         e.close()
 
@@ -172,7 +112,7 @@ def test_second_opinion_from_external_products_alone(world):
     rng = np.random.default_rng(w.N + 41)
     p = R.Params(n=depth, N=w.N)
     sel_idx = rng.integers(0, depth, (count, depth)).astype(np.int32)
-    row0 = rng.integers(0, N_ROWS - 8 + 1, count).astype(np.int32)
+    row0 = rng.integers(0, TREE_N_ROWS - 8 + 1, count).astype(np.int32)
     e = R.Engine(p, 0)
     bare = R.Engine(p, 0)
     try:
@@ -250,8 +190,8 @@ def test_bad_arguments_host_and_device(world):
     ref = w.eng.cmux_tree_batch(w.sel, lut, depth, count, sel_idx, row0)
     ref_x = w.eng.cmux_tree_extract_batch(w.sel, lut, depth, count, sel_idx, row0)
     bad_sel, bad_row, bad_coef = sel_idx.copy(), row0.copy(), np.zeros(count, np.int32)
-    bad_sel[3, 1] = N_SEL
-    bad_row[3] = N_ROWS - 3
+    bad_sel[3, 1] = TREE_N_SEL
+    bad_row[3] = TREE_N_ROWS - 3
     bad_coef[3] = w.N
     w.eng.timer_begin()
     for call, names in ((lambda: w.eng.cmux_tree_batch(w.sel, lut, depth, count, bad_sel, row0), "lookup 3: sel_idx[1]"),
@@ -268,7 +208,7 @@ def test_bad_arguments_host_and_device(world):
     keep = np.ones(count, bool)
     keep[3] = False
     st = torch.cuda.current_stream().cuda_stream
-    for kw in ({"d_sel_idx": _cuda(bad_sel), "d_row0": _cuda(row0)}, {"d_sel_idx": _cuda(sel_idx), "d_row0": _cuda(bad_row)}):
+    for kw in ({"d_sel_idx": gk.to_device(bad_sel), "d_row0": gk.to_device(row0)}, {"d_sel_idx": gk.to_device(sel_idx), "d_row0": gk.to_device(bad_row)}):
         d_out = torch.zeros((count, 2, w.N), dtype=torch.int32, device="cuda")
         w.eng.cmux_tree_batch_dev(w.sel, lut, depth, d_out, count, stream=st, **kw)
         with pytest.raises(R.RtfheError) as ei:
@@ -277,12 +217,12 @@ def test_bad_arguments_host_and_device(world):
         got = d_out.cpu().numpy().view(np.uint32)
         assert np.array_equal(got[keep], ref[keep]) and not got[3].any()
     d_out = torch.zeros((count, w.rp.n + 1), dtype=torch.int32, device="cuda")
-    w.eng.cmux_tree_extract_batch_dev(w.sel, lut, depth, d_out, count, _cuda(sel_idx), _cuda(row0), _cuda(bad_coef), st)
+    w.eng.cmux_tree_extract_batch_dev(w.sel, lut, depth, d_out, count, gk.to_device(sel_idx), gk.to_device(row0), gk.to_device(bad_coef), st)
     with pytest.raises(R.RtfheError):
         w.eng.sync(st)
     assert np.array_equal(d_out.cpu().numpy().view(np.uint32)[keep], ref_x[keep])
     w.eng.sync(st)                                           # reported once
-    assert np.array_equal(_tree_dev(w, "encrypted", depth, count, sel_idx, row0), ref)
+    assert np.array_equal(tree_dev(w, "encrypted", depth, count, sel_idx, row0), ref)
 
 
 def test_exact_backends_refuse_and_mirror_recovers(world):
@@ -308,9 +248,9 @@ def test_graph_capture_replays_eager_words(world):
     w = world
     depth, count = 3, 37
     rng = np.random.default_rng(w.N + 71)
-    sel_idx = _cuda(rng.integers(0, N_SEL, (count, depth)))
-    row0 = _cuda(rng.integers(0, N_ROWS - 8 + 1, count))
-    coef = _cuda(rng.integers(0, w.N, count))
+    sel_idx = gk.to_device(rng.integers(0, TREE_N_SEL, (count, depth)))
+    row0 = gk.to_device(rng.integers(0, TREE_N_ROWS - 8 + 1, count))
+    coef = gk.to_device(rng.integers(0, w.N, count))
     lut = w.lut["encrypted"]
     s = torch.cuda.Stream()
     out = torch.zeros((count, 2, w.N), dtype=torch.int32, device="cuda")
@@ -344,9 +284,9 @@ def test_larger_eager_call_retires_the_buffers_a_graph_holds(orc, world):
     import torch
     w = world
     lut = w.lut["encrypted"]
-    idx2, row2, _, _ = _lookups(2, 5)[0]
-    idx3, row3, _, _ = _lookups(3, 37)[0]
-    d_idx2, d_row2, d_idx3, d_row3 = _cuda(idx2), _cuda(row2), _cuda(idx3), _cuda(row3)
+    idx2, row2, _, _ = tree_lookups(2, 5)[0]
+    idx3, row3, _, _ = tree_lookups(3, 37)[0]
+    d_idx2, d_row2, d_idx3, d_row3 = gk.to_device(idx2), gk.to_device(row2), gk.to_device(idx3), gk.to_device(row3)
     s = torch.cuda.Stream()
     out = torch.zeros((5, 2, w.N), dtype=torch.int32, device="cuda")
     big = torch.zeros((37, 2, w.N), dtype=torch.int32, device="cuda")
@@ -354,13 +294,13 @@ def test_larger_eager_call_retires_the_buffers_a_graph_holds(orc, world):
         w.eng.cmux_tree_batch_dev(w.sel, lut, 2, out, 5, d_idx2, d_row2, s.cuda_stream)
         w.eng.sync(s.cuda_stream)
         eager = out.clone()
-        assert np.array_equal(eager.cpu().numpy().view(np.uint32), _oracle(orc, w, "encrypted", 2, idx2, row2))
+        assert np.array_equal(eager.cpu().numpy().view(np.uint32), tree_oracle(orc, w, "encrypted", 2, idx2, row2))
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=s):
             w.eng.cmux_tree_batch_dev(w.sel, lut, 2, out, 5, d_idx2, d_row2, s.cuda_stream)
         w.eng.cmux_tree_batch_dev(w.sel, lut, 3, big, 37, d_idx3, d_row3, s.cuda_stream)
         w.eng.sync(s.cuda_stream)
-        assert np.array_equal(big.cpu().numpy().view(np.uint32), _oracle(orc, w, "encrypted", 3, idx3, row3))
+        assert np.array_equal(big.cpu().numpy().view(np.uint32), tree_oracle(orc, w, "encrypted", 3, idx3, row3))
         for _ in range(2):
             out.zero_()
             g.replay()

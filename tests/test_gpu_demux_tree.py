@@ -1,36 +1,23 @@
 """GPU: the CMUX demultiplexer tree and the table accumulation (rtfhe_demux_tree_batch[_dev], rtfhe_lut_accumulate_dev, rtfhe_lut_read_dev;
-k_demux_tree, k_trlwe_accumulate).  Every word against the oracle's demultiplexer (tests/test_demux_tree_host.py: oracle_demux_tree) at both N,
+k_demux_tree, k_trlwe_accumulate).  Every word against the oracle's demultiplexer (tests/leveled_oracle.py: oracle_demux_tree) at both N,
 depths 1 .. 3 and counts 1, 5 and 37, in both leveled decomposition modes; a second opinion built from rtfhe_external_product_batch alone; the
 inverse of the CMUX tree on the device; the accumulation word for word; skipped lookups; refusals; the capture rule; the histogram example.
 Small TLWE dimensions as the tree's tests use: n = 40 at N = 1024, n = 24 at N = 2048."""
 import contextlib
-import types
 
 import numpy as np
 import pytest
 
+import gpu_kit as gk
 import round_oracle as ro
-from test_demux_tree_host import oracle_demux_tree
-from test_gpu_pbs import _engine, _random_words
-from test_pbs_host import bk_fft
+from kit import random_words
+from leveled_kit import selector_world
+from leveled_oracle import oracle_demux_tree
 
 pytestmark = pytest.mark.gpu
 
-SMALL_N = {1024: 40, 2048: 24}
 MAX_DEPTH, MAX_COUNT = 3, 37
 N_SEL = MAX_COUNT * MAX_DEPTH          # sel_idx = NULL at depth 3 and 37 lookups reads selectors 0 .. 110
-
-
-def _cuda(a, dtype=np.int32):
-    import torch
-    if a is None:
-        return None
-    a = np.ascontiguousarray(a, dtype)
-    return torch.from_numpy(a.view(np.int32) if dtype == np.uint32 else a).cuda()
-
-
-def _host(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 @contextlib.contextmanager
@@ -49,20 +36,10 @@ def _leveled(eng, rounded=True):
 def world(request, orc):
     """Per N: keys from the product's keygen on an engine, N_SEL selectors of known random bits (device handle, torus words and the oracle's
     spectra of them), MAX_COUNT inputs x of random words."""
-    import rustfhe_amd as R
     N = request.param
-    rp = R.Params(n=SMALL_N[N], N=N)
-    key0, key1, bk, ksk = R.keygen(rp, 0xDE7 + N)
-    w = types.SimpleNamespace(R=R, N=N, rp=rp, key0=key0, key1=key1, bk=bk, ksk=ksk)
-    w.P = orc.Params(n=rp.n, N=N)
-    w.plan = orc.Plan(N)
-    rng = np.random.default_rng(N + 13)
-    w.bits = rng.integers(0, 2, N_SEL).astype(np.uint8)
-    w.bits[:2] = (0, 1)
-    w.sel_t = R.encrypt_selectors(rp, key1, w.bits, seed=0x5E1ED3 + N)
-    w.sel_f = bk_fft(orc, w.P, w.plan, w.sel_t.reshape(-1))
-    w.x = _random_words(rng, (MAX_COUNT, 2, N))
-    w.eng = _engine(R, rp, bk, ksk)
+    w, rng = selector_world(orc, N, 0xDE7 + N, N + 13, N_SEL, 0x5E1ED3 + N)
+    w.x = random_words(rng, (MAX_COUNT, 2, N))
+    w.eng = gk.engine(w.R, w.rp, w.bk, w.ksk)
     w.sel = w.eng.selectors(w.sel_t)
     w.memo = {}
     yield w
@@ -73,12 +50,8 @@ def world(request, orc):
 def _oracle(orc, w, depth, sel_idx, x, mode=ro.REFERENCE):
     """the oracle's demultiplexer of every lookup: sel_idx [count][depth], x [count][2][N]; computed once per world and arguments, shared by the
     tests that ask for the same lookups, and read-only"""
-    key = (depth, mode, sel_idx.tobytes(), x.tobytes())
-    if key not in w.memo:
-        want = np.stack([oracle_demux_tree(orc, w.P, w.plan, w.sel_f, sel_idx[g], x[g], mode) for g in range(len(x))])
-        want.setflags(write=False)
-        w.memo[key] = want
-    return w.memo[key]
+    return gk.memo(w.memo, (depth, mode, sel_idx, x),
+                   lambda: np.stack([oracle_demux_tree(orc, w.P, w.plan, w.sel_f, sel_idx[g], x[g], mode) for g in range(len(x))]))
 
 
 def _demux_dev(w, x, depth, sel_idx, on=None, stream=None):
@@ -88,9 +61,9 @@ def _demux_dev(w, x, depth, sel_idx, on=None, stream=None):
     st = stream or torch.cuda.current_stream().cuda_stream
     count = len(x)
     d_out = torch.zeros((count, 1 << depth, 2, w.N), dtype=torch.int32, device="cuda")
-    eng.demux_tree_batch_dev(sel, _cuda(x, np.uint32), depth, d_out, count, _cuda(sel_idx), st)
+    eng.demux_tree_batch_dev(sel, gk.to_device(x, np.uint32), depth, d_out, count, gk.to_device(sel_idx), st)
     eng.sync(st)
-    return _host(d_out)
+    return gk.words_of(d_out)
 
 
 def _lookups(depth, count):
@@ -202,9 +175,9 @@ def test_accumulate_adds_the_leaves_into_the_tables_rows(world):
     depth, count = 3, 5
     st = torch.cuda.current_stream().cuda_stream
     rng = np.random.default_rng(w.N + 61)
-    rows = _random_words(rng, (16, 2, w.N))
+    rows = random_words(rng, (16, 2, w.N))
     leaves = w.eng.demux_tree_batch(w.sel, w.x[:count], depth, _lookups(depth, count)[0][0])
-    d_leaves = _cuda(leaves, np.uint32)
+    d_leaves = gk.to_device(leaves, np.uint32)
     want = rows.copy()
     want[3:11] += leaves.sum(axis=0, dtype=np.uint32)
     d_back = torch.zeros((16, 2, w.N), dtype=torch.int32, device="cuda")
@@ -212,13 +185,13 @@ def test_accumulate_adds_the_leaves_into_the_tables_rows(world):
         table.accumulate_dev(d_leaves, 3, 8, count, st)
         table.read_dev(d_back, 0, 16, st)
         w.eng.sync(st)
-        assert np.array_equal(_host(d_back), want), np.flatnonzero((_host(d_back) != want).any(axis=(1, 2)))
+        assert np.array_equal(gk.words_of(d_back), want), np.flatnonzero((gk.words_of(d_back) != want).any(axis=(1, 2)))
         table.accumulate_dev(d_leaves[:2], 8, 8, 2, st)                      # the last row of the table is the range's last
         want[8:16] += leaves[:2].sum(axis=0, dtype=np.uint32)
         part = torch.zeros((9, 2, w.N), dtype=torch.int32, device="cuda")
         table.read_dev(part[:8], 8, 8, st)
         w.eng.sync(st)
-        assert np.array_equal(_host(part)[:8], want[8:]) and not _host(part)[8].any()
+        assert np.array_equal(gk.words_of(part)[:8], want[8:]) and not gk.words_of(part)[8].any()
         w.eng.timer_begin()
         for call, word in ((lambda: plain.accumulate_dev(d_leaves, 3, 8, count), "plain"), (lambda: plain.read_dev(d_back, 0, 1), "plain"),
                            (lambda: table.accumulate_dev(d_leaves, -1, 8, count), "outside"), (lambda: table.accumulate_dev(d_leaves, 9, 8, count), "outside"),
@@ -233,7 +206,7 @@ def test_accumulate_adds_the_leaves_into_the_tables_rows(world):
         table.accumulate_dev(d_leaves, 16, 0, count)                        # an empty range is no error
         table.read_dev(d_back, 0, 16, st)
         w.eng.sync(st)
-        assert np.array_equal(_host(d_back), want)
+        assert np.array_equal(gk.words_of(d_back), want)
 
 
 @pytest.mark.parametrize("depth", [1, 3])
@@ -251,8 +224,8 @@ def test_a_lookup_with_a_bad_device_index_is_skipped_whole(orc, world, depth):
     clean = _oracle(orc, w, depth, good, x)
     n_rows = count * leaves + 2 * GUARD
     sentinel = (0xA5000000 + 0x1001 * np.arange(n_rows, dtype=np.uint32)[:, None] + np.arange(2 * w.N, dtype=np.uint32)[None, :]).astype(np.uint32)
-    buf = _cuda(sentinel, np.uint32)
-    w.eng.demux_tree_batch_dev(w.sel, _cuda(x, np.uint32), depth, buf[GUARD:GUARD + count * leaves], count, _cuda(bad), st)
+    buf = gk.to_device(sentinel, np.uint32)
+    w.eng.demux_tree_batch_dev(w.sel, gk.to_device(x, np.uint32), depth, buf[GUARD:GUARD + count * leaves], count, gk.to_device(bad), st)
     with pytest.raises(R.RtfheError) as ei:
         w.eng.sync(st)
     assert ei.value.code == R._ffi.ERR_INVALID
@@ -260,7 +233,7 @@ def test_a_lookup_with_a_bad_device_index_is_skipped_whole(orc, world, depth):
     want = sentinel.copy()
     for g in (0, 1, 2, 4):
         want[GUARD + g * leaves:GUARD + (g + 1) * leaves] = clean[g].reshape(leaves, 2 * w.N)
-    got = _host(buf)
+    got = gk.words_of(buf)
     assert np.array_equal(got, want), np.flatnonzero((got != want).any(axis=1))
     assert np.array_equal(_demux_dev(w, x, depth, good), clean)
 
@@ -273,7 +246,7 @@ def test_bad_arguments_are_refused_before_anything_is_launched(world):
     sel_idx = np.tile(np.array([[0, 1]], np.int32), (count, 1))
     bad_sel = sel_idx.copy()
     bad_sel[3, 1] = N_SEL
-    d_x = _cuda(x, np.uint32)
+    d_x = gk.to_device(x, np.uint32)
     d_big = torch.zeros((count * 4 + 1, 2, w.N), dtype=torch.int32, device="cuda")
     host_out = np.zeros((count, 4, 2, w.N), np.uint32)
     w.eng.timer_begin()
@@ -295,9 +268,9 @@ def test_bad_arguments_are_refused_before_anything_is_launched(world):
         assert ei.value.code == R._ffi.ERR_INVALID and names in str(ei.value), str(ei.value)
     assert w.eng.timer_end()[1] == 0, "the checks come before any launch"
     # d_out right behind d_x does not overlap it
-    w.eng.demux_tree_batch_dev(w.sel, d_big[:1], depth, d_big[1:5], 1, _cuda(sel_idx[:1]))
+    w.eng.demux_tree_batch_dev(w.sel, d_big[:1], depth, d_big[1:5], 1, gk.to_device(sel_idx[:1]))
     w.eng.sync()
-    assert np.array_equal(_host(d_big[1:5])[None], w.eng.demux_tree_batch(w.sel, np.zeros((1, 2, w.N), np.uint32), depth, sel_idx[:1]))
+    assert np.array_equal(gk.words_of(d_big[1:5])[None], w.eng.demux_tree_batch(w.sel, np.zeros((1, 2, w.N), np.uint32), depth, sel_idx[:1]))
 
 
 def test_exact_backends_refuse_and_mirror_recovers(world):
@@ -328,8 +301,8 @@ def test_capture_rule_and_replay(orc, world):
     try:
         with e.selectors(w.sel_t) as sel:
             s = torch.cuda.Stream()
-            d_x = _cuda(x, np.uint32)
-            d_idx = {d: _cuda(i) for d, i in idx.items()}
+            d_x = gk.to_device(x, np.uint32)
+            d_idx = {d: gk.to_device(i) for d, i in idx.items()}
             out1 = torch.zeros((count, 2, 2, w.N), dtype=torch.int32, device="cuda")
             out2 = torch.zeros((count, 4, 2, w.N), dtype=torch.int32, device="cuda")
             out3 = torch.zeros((count, 8, 2, w.N), dtype=torch.int32, device="cuda")
@@ -346,10 +319,10 @@ def test_capture_rule_and_replay(orc, world):
                 assert len(refused) == 1 and refused[0].code == R._ffi.ERR_STATE and "capture" in str(refused[0])
                 g0.replay()
                 torch.cuda.synchronize()
-                assert np.array_equal(_host(out1), want1) and not _host(out2).any()
+                assert np.array_equal(gk.words_of(out1), want1) and not gk.words_of(out2).any()
                 e.demux_tree_batch_dev(sel, d_x, 3, out3, count, d_idx[3], s.cuda_stream)      # the eager call the capture rule asks for
                 e.sync(s.cuda_stream)
-                assert np.array_equal(_host(out3), want3)
+                assert np.array_equal(gk.words_of(out3), want3)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=s):
                     e.demux_tree_batch_dev(sel, d_x, 3, out3, count, d_idx[3], s.cuda_stream)
@@ -357,7 +330,7 @@ def test_capture_rule_and_replay(orc, world):
                     out3.zero_()
                     g.replay()
                     torch.cuda.synchronize()
-                    assert np.array_equal(_host(out3), want3)
+                    assert np.array_equal(gk.words_of(out3), want3)
                 e.sync(s.cuda_stream)
     finally:
         e.close()

@@ -19,8 +19,8 @@ backends with the NTT backend's forced shape at N = 1024 and with each other at 
 import numpy as np
 import pytest
 
-from test_gpu_mask_lengths import _cus
-from test_gpu_pbs import _engine, _random_words
+import gpu_kit as gk
+from kit import keys_2048, random_words
 
 pytestmark = pytest.mark.gpu
 
@@ -63,10 +63,10 @@ class World:
     """the default engine of a ring, a forced single-shape engine beside it and one block of random input words shared by every case"""
     def __init__(self, R, N, default, forced, keys):
         self.R, self.N, self.e, self.forced, self.keys = R, N, default, forced, keys
-        self.C = _cus()
+        self.C = gk.cus()
         rng = np.random.default_rng(N)
-        self.c0 = _random_words(rng, (8 * self.C + 1, default.p.n + 1))
-        self.c1 = _random_words(rng, (8 * self.C + 1, default.p.n + 1))
+        self.c0 = random_words(rng, (8 * self.C + 1, default.p.n + 1))
+        self.c1 = random_words(rng, (8 * self.C + 1, default.p.n + 1))
         self.forced_out = {}
 
     def counted(self, e, fn):
@@ -91,11 +91,11 @@ def worlds(orc, params, keys, engine):
                 K, default = keys, engine
                 p = R.Params(n=params.n, N=params.N)
             else:
-                K = orc.Keys(orc.Params(N=2048), 2048)
+                K = keys_2048(orc)[1]
                 p = R.Params(N=2048)
-                default = _engine(R, p, K.bk_t, K.ksk)
+                default = gk.engine(R, p, K.bk_t, K.ksk)
                 engines.append(default)
-            forced = _engine(R, p, K.bk_t, K.ksk, mp, {"RTFHE_FORCE_WAVES": "4"})
+            forced = gk.engine(R, p, K.bk_t, K.ksk, mp, {"RTFHE_FORCE_WAVES": "4"})
             engines.append(forced)
             made[N] = World(R, N, default, forced, K)
         return made[N]
@@ -142,7 +142,7 @@ def test_pbs_family_launch_counts_on_the_mirror_backend(worlds, N):
     rng = np.random.default_rng(N + 1)
     w.on(e, "mirror")
     rr = RR if N == 1024 else 0
-    with e.lut(_random_words(rng, (2, N))) as lut, e.lut_encrypted(_random_words(rng, (2, 2, N))) as enc:
+    with e.lut(random_words(rng, (2, N))) as lut, e.lut_encrypted(random_words(rng, (2, 2, N))) as enc:
         G = 4 * C + 1
         k, many = w.counted(e, lambda: e.pbs_many_batch(lut, w.c0[:G], 4))
         print("N = %d many-LUT: %d gates, %d launches" % (N, G, k))
@@ -160,7 +160,7 @@ def test_pbs_family_launch_counts_on_the_mirror_backend(worlds, N):
         assert k == _ladder(G, C, 4, rr) + KS, (N, "rounded", k)
         # the many-LUT words once more from the forced single-shape engine (its own table: a table belongs to one context)
         w.on(w.forced, "mirror")
-        with w.forced.lut(_random_words(np.random.default_rng(N + 1), (2, N))) as flut:
+        with w.forced.lut(random_words(np.random.default_rng(N + 1), (2, N))) as flut:
             k, want = w.counted(w.forced, lambda: w.forced.pbs_many_batch(flut, w.c0[:4 * C + 1], 4))
         assert k == 1 + KS, (N, "forced many", k)
         assert np.array_equal(many, want), N

@@ -21,11 +21,11 @@ import types
 import numpy as np
 import pytest
 
-from test_gpu_pbs import _engine, _random_words
+import gpu_kit as gk
+from kit import SMALL_N, random_words
 
 pytestmark = pytest.mark.gpu
 
-SMALL_N = {1024: 40, 2048: 24}
 COUNTS = (5, 9)
 DEPTHS = (1, 2, 3)
 N_SEL = 9 * 3            # sel_idx = NULL at depth 3 and 9 lookups reads selectors 0 .. 26
@@ -44,12 +44,12 @@ def world(request):
     rng = np.random.default_rng(N + 19)
     w = types.SimpleNamespace(R=R, N=N, rp=rp)
     sel_t = R.encrypt_selectors(rp, key1, rng.integers(0, 2, N_SEL).astype(np.uint8), seed=0x1C1 + N)
-    table = _random_words(rng, (N_ROWS, 2, N))
-    w.rows = _random_words(rng, (max(COUNTS), 2, N))
-    w.pk = _random_words(rng, (rp.n, 8, 3, 2, N))
+    table = random_words(rng, (N_ROWS, 2, N))
+    w.rows = random_words(rng, (max(COUNTS), 2, N))
+    w.pk = random_words(rng, (rp.n, 8, 3, 2, N))
     mp = pytest.MonkeyPatch()
-    w.mm = _engine(R, rp, bk, ksk)
-    w.ext = _engine(R, rp, bk, ksk, mp, {"RTFHE_KS_MM_MIN": "0"})
+    w.mm = gk.engine(R, rp, bk, ksk)
+    w.ext = gk.engine(R, rp, bk, ksk, mp, {"RTFHE_KS_MM_MIN": "0"})
     w.on = {}
     for e in (w.mm, w.ext):
         w.on[e] = (e.selectors(sel_t), e.lut_encrypted(table))
@@ -147,7 +147,7 @@ def test_netlist(world, depth, count, extract):
 @pytest.mark.parametrize("P", [1, 4, PACK_POS_MAX, PACK_POS_MAX + 1, 600])
 def test_pack(world, P, count):
     w, e = world, world.mm
-    tlwe = _random_words(np.random.default_rng(P + count), (count, P, w.rp.n + 1))
+    tlwe = random_words(np.random.default_rng(P + count), (count, P, w.rp.n + 1))
     k, out = _counted(e, lambda: e.pack_batch(w.key, tlwe, P))
     print("N = %d P %d count %d: pack %d launches" % (w.N, P, count, k))
     assert k == 1 + (P + PACK_POS_MAX - 1) // PACK_POS_MAX and out.shape == (count, 2, w.N)

@@ -2,23 +2,18 @@
 k_cmux_tree, k_trgsw_rotate, k_cmux_net and k_external_product).  Every word against the restatement of the tree, the rotation and the
 netlist with the rounded constants (tests/leveled_round_oracle.py, which tests/test_leveled_round_host.py holds to the oracle's own three in
 reference mode) at both N; second opinions between the entry points; switching the mode forth and back, and what never reads it; captures;
-refusals; and what the mode buys: 6-bit rows through a depth-8 tree and a 10-step rotation.  The world is tests/test_gpu_cmux_tree.py's:
+refusals; and what the mode buys: 6-bit rows through a depth-8 tree and a 10-step rotation.  The world is that of tests/test_gpu_cmux_tree.py:
 n = 40 at N = 1024, n = 24 at N = 2048."""
 import contextlib
-import types
 
 import numpy as np
 import pytest
 
+import gpu_kit as gk
 import leveled_round_oracle as lo
-from test_cmux_net_host import three_of_five
-from test_cmux_tree_host import as_trlwe, oracle_cmux_tree
-from test_gpu_cmux_net import _run as _net_run
-from test_gpu_cmux_tree import N_ROWS, N_SEL, SMALL_N, _lookups, _tree_dev
-from test_gpu_pbs import _engine, _random_words
-from test_gpu_trgsw_rotate import _cuda, _rotate_dev
-from test_pbs_host import bk_fft
-from test_trgsw_rotate_host import oracle_trgsw_rotate, rotate_clear
+from kit import random_words
+from leveled_kit import TREE_N_ROWS, TREE_N_SEL, net_run, rotate_dev, selector_world, tree_dev, tree_lookups
+from leveled_oracle import as_trlwe, oracle_cmux_tree, oracle_trgsw_rotate, rotate_clear, three_of_five
 
 pytestmark = pytest.mark.gpu
 
@@ -44,26 +39,17 @@ def _R():
 
 @pytest.fixture(scope="module", params=[1024, 2048], ids=lambda N: "N%d" % N)
 def world(request, orc):
-    """Per N: keys from the product's keygen on an engine (in reference mode: every test sets the mode it wants around its calls), N_SEL
-    selectors of known random bits (device handle, torus words and spectra), one plain and one really encrypted table of N_ROWS random rows,
+    """Per N: keys from the product's keygen on an engine (in reference mode: every test sets the mode it wants around its calls), TREE_N_SEL
+    selectors of known random bits (device handle, torus words and spectra), one plain and one really encrypted table of TREE_N_ROWS random rows,
     N_ROT random input rows of the rotation."""
-    R = _R()
     N = request.param
-    rp = R.Params(n=SMALL_N[N], N=N)
-    key0, key1, bk, ksk = R.keygen(rp, 0x17E + N)
-    w = types.SimpleNamespace(R=R, N=N, logn=N.bit_length() - 1, rp=rp, key0=key0, key1=key1, bk=bk, ksk=ksk)
-    w.P = orc.Params(n=rp.n, N=N)
-    w.plan = orc.Plan(N)
-    rng = np.random.default_rng(N + 17)
-    w.bits = rng.integers(0, 2, N_SEL).astype(np.uint8)
-    w.bits[:2] = (0, 1)
-    w.sel_t = R.encrypt_selectors(rp, key1, w.bits, seed=0x5E1EC9 + N)
-    w.sel_f = bk_fft(orc, w.P, w.plan, w.sel_t.reshape(-1))
-    w.rows = {"plain": _random_words(rng, (N_ROWS, N)), "encrypted": R.encrypt_lut(rp, key1, _random_words(rng, (N_ROWS, N)), seed=0x7AD + N)}
-    w.rot_rows = _random_words(rng, (N_ROT, 2, N))
+    w, rng = selector_world(orc, N, 0x17E + N, N + 17, TREE_N_SEL, 0x5E1EC9 + N)
+    R = w.R
+    w.rows = {"plain": random_words(rng, (TREE_N_ROWS, N)), "encrypted": R.encrypt_lut(w.rp, w.key1, random_words(rng, (TREE_N_ROWS, N)), seed=0x7AD + N)}
+    w.rot_rows = random_words(rng, (N_ROT, 2, N))
     base = [2 * N - 1, 0, N, 1] + [int(r) for r in rng.integers(0, 2 * N, 12)]
     w.rot = lambda depth: np.array(base[:depth], np.int32)      # noqa: E731
-    w.eng = _engine(R, rp, bk, ksk)
+    w.eng = gk.engine(R, w.rp, w.bk, w.ksk)
     assert w.eng.leveled_decomposition() == R._ffi.DECOMP_REFERENCE, "the mode is the reference's until set"
     w.sel = w.eng.selectors(w.sel_t)
     w.lut = {"plain": w.eng.lut(w.rows["plain"]), "encrypted": w.eng.lut_encrypted(w.rows["encrypted"])}
@@ -76,25 +62,17 @@ def world(request, orc):
 
 def _want_tree(w, kind, depth, sel_idx, row0, coef=None):
     """the restated tree of every lookup in rounded mode; computed once per world and arguments, shared and read-only"""
-    key = ("tree", kind, depth, sel_idx.tobytes(), row0.tobytes(), None if coef is None else coef.tobytes())
-    if key not in w.memo:
+    def compute():
         rows = as_trlwe(w.rows[kind], w.N)
-        want = np.stack([lo.cmux_tree(w.P, w.plan, w.sel_f, sel_idx[g], rows[row0[g]:row0[g] + (1 << depth)], None if coef is None else coef[g], w.ksk)
+        return np.stack([lo.cmux_tree(w.P, w.plan, w.sel_f, sel_idx[g], rows[row0[g]:row0[g] + (1 << depth)], None if coef is None else coef[g], w.ksk)
                          for g in range(len(row0))])
-        want.setflags(write=False)
-        w.memo[key] = want
-    return w.memo[key]
+    return gk.memo(w.memo, ("tree", kind, depth, sel_idx, row0, coef), compute)
 
 
 def _want_rotate(w, sel_idx, rot, rows, extract=False):
     """the restated rotation of every lookup in rounded mode; computed once per world and arguments, shared and read-only"""
-    key = ("rot", sel_idx.tobytes(), sel_idx.shape, None if rot is None else np.asarray(rot, np.int32).tobytes(), rows.tobytes(), extract)
-    if key not in w.memo:
-        want = np.stack([lo.trgsw_rotate(w.P, w.plan, w.sel_f, sel_idx[g], None if rot is None else [int(r) for r in rot], rows[g], extract, w.ksk)
-                         for g in range(len(rows))])
-        want.setflags(write=False)
-        w.memo[key] = want
-    return w.memo[key]
+    return gk.memo(w.memo, ("rot", sel_idx, None if rot is None else np.asarray(rot, np.int32), rows, extract), lambda: np.stack(
+        [lo.trgsw_rotate(w.P, w.plan, w.sel_f, sel_idx[g], None if rot is None else [int(r) for r in rot], rows[g], extract, w.ksk) for g in range(len(rows))]))
 
 
 # ---- tree ----
@@ -107,12 +85,12 @@ def test_tree_equals_the_restatement(world, depth, count):
     w = world
     with _leveled(w.eng):
         for kind in ("plain", "encrypted"):
-            for sel_idx, row0, exp_idx, exp_row0 in _lookups(depth, count):
+            for sel_idx, row0, exp_idx, exp_row0 in tree_lookups(depth, count):
                 want = _want_tree(w, kind, depth, exp_idx, exp_row0)
                 got = w.eng.cmux_tree_batch(w.sel, w.lut[kind], depth, count, sel_idx, row0)
                 assert got.shape == (count, 2, w.N)
                 assert np.array_equal(got, want), (kind, sel_idx is None, np.flatnonzero((got != want).any(axis=(1, 2)))[:8])
-                assert np.array_equal(_tree_dev(w, kind, depth, count, sel_idx, row0), got), (kind, sel_idx is None)
+                assert np.array_equal(tree_dev(w, kind, depth, count, sel_idx, row0), got), (kind, sel_idx is None)
 
 
 def test_tree_extract_form_equals_the_restatement(world):
@@ -120,8 +98,8 @@ def test_tree_extract_form_equals_the_restatement(world):
     w = world
     depth, count = 3, 7
     rng = np.random.default_rng(w.N + 31)
-    sel_idx = rng.integers(0, N_SEL, (count, depth)).astype(np.int32)
-    row0 = rng.integers(0, N_ROWS - 8 + 1, count).astype(np.int32)
+    sel_idx = rng.integers(0, TREE_N_SEL, (count, depth)).astype(np.int32)
+    row0 = rng.integers(0, TREE_N_ROWS - 8 + 1, count).astype(np.int32)
     coef = np.array([0, 1, w.N - 1, w.N - 1, 1, 0, w.N // 2 + 3], np.int32)
     with _leveled(w.eng):
         for kind in ("plain", "encrypted"):
@@ -129,7 +107,7 @@ def test_tree_extract_form_equals_the_restatement(world):
                 want = _want_tree(w, kind, depth, sel_idx, row0, exp)
                 got = w.eng.cmux_tree_extract_batch(w.sel, w.lut[kind], depth, count, sel_idx, row0, cf)
                 assert got.shape == (count, w.rp.n + 1) and np.array_equal(got, want), (kind, cf is None)
-                assert np.array_equal(_tree_dev(w, kind, depth, count, sel_idx, row0, cf, extract=True), got), (kind, cf is None)
+                assert np.array_equal(tree_dev(w, kind, depth, count, sel_idx, row0, cf, extract=True), got), (kind, cf is None)
 
 
 # ---- rotation ----
@@ -145,32 +123,32 @@ def test_rotation_equals_the_restatement(world, d, count):
     rows = w.rot_rows[:count]
     shared = rng.integers(0, 6, (count, depth)).astype(np.int32)
     default_idx = np.arange(count * depth, dtype=np.int32).reshape(count, depth)
-    cases = [(shared, w.rot(depth), shared), (None, None, default_idx) if count * depth <= N_SEL else (shared, None, shared)]
+    cases = [(shared, w.rot(depth), shared), (None, None, default_idx) if count * depth <= TREE_N_SEL else (shared, None, shared)]
     with _leveled(w.eng):
         for sel_idx, rot, exp_idx in cases:
             want = _want_rotate(w, exp_idx, rot, rows)
             got = w.eng.trgsw_rotate_batch(w.sel, rows, depth, sel_idx, rot)
             assert np.array_equal(got, want), (sel_idx is None, rot is None, np.flatnonzero((got != want).any(axis=(1, 2)))[:8])
-            assert np.array_equal(_rotate_dev(w, rows, depth, sel_idx, rot), got), (sel_idx is None, rot is None)
-            assert np.array_equal(_rotate_dev(w, rows, depth, sel_idx, rot, in_place=True), got), (sel_idx is None, rot is None, "in place")
+            assert np.array_equal(rotate_dev(w, rows, depth, sel_idx, rot), got), (sel_idx is None, rot is None)
+            assert np.array_equal(rotate_dev(w, rows, depth, sel_idx, rot, in_place=True), got), (sel_idx is None, rot is None, "in place")
 
 
 def test_rotation_extract_form_equals_the_restatement(world):
     w = world
     depth, count = 3, 7
-    sel_idx = np.random.default_rng(w.N + 32).integers(0, N_SEL, (count, depth)).astype(np.int32)
+    sel_idx = np.random.default_rng(w.N + 32).integers(0, TREE_N_SEL, (count, depth)).astype(np.int32)
     rows = w.rot_rows[5:5 + count]
     with _leveled(w.eng):
         for rot in (w.rot(depth), None):
             want = _want_rotate(w, sel_idx, rot, rows, extract=True)
             got = w.eng.trgsw_rotate_extract_batch(w.sel, rows, depth, sel_idx, rot)
             assert got.shape == (count, w.rp.n + 1) and np.array_equal(got, want), rot is None
-            assert np.array_equal(_rotate_dev(w, rows, depth, sel_idx, rot, extract=True), got), rot is None
+            assert np.array_equal(rotate_dev(w, rows, depth, sel_idx, rot, extract=True), got), rot is None
 
 
 @pytest.mark.parametrize("extract", [False, True], ids=["rows", "extract"])
 def test_rotation_skips_lookups_with_a_bad_index(world, extract):
-    """Rounded mode, device-side sel_idx with entries -1 and N_SEL in lookups 1 and 4 of 6: those output rows and the guard rows keep every
+    """Rounded mode, device-side sel_idx with entries -1 and TREE_N_SEL in lookups 1 and 4 of 6: those output rows and the guard rows keep every
     byte of a sentinel, the other rows are the clean call's, sync raises once."""
     import torch
     w, R = world, world.R
@@ -180,14 +158,14 @@ def test_rotation_skips_lookups_with_a_bad_index(world, extract):
     rows = w.rot_rows[:count]
     good = np.tile(np.arange(depth, dtype=np.int32), (count, 1))
     bad = good.copy()
-    bad[1, 0], bad[4, depth - 1] = -1, N_SEL
+    bad[1, 0], bad[4, depth - 1] = -1, TREE_N_SEL
     with _leveled(w.eng):
-        clean = _rotate_dev(w, rows, depth, good, w.rot(depth), extract=extract)
+        clean = rotate_dev(w, rows, depth, good, w.rot(depth), extract=extract)
         assert np.array_equal(clean[0], _want_rotate(w, good[:1], w.rot(depth), rows[:1], extract)[0])
         sentinel = (0xA5000000 + 0x1001 * np.arange(count + 8, dtype=np.uint32)[:, None] + np.arange(width, dtype=np.uint32)[None, :]).astype(np.uint32)
-        buf = _cuda(sentinel, np.uint32)
+        buf = gk.to_device(sentinel, np.uint32)
         call = w.eng.trgsw_rotate_extract_batch_dev if extract else w.eng.trgsw_rotate_batch_dev
-        call(w.sel, _cuda(rows, np.uint32), depth, buf[4:4 + count], count, _cuda(bad), w.rot(depth), st)
+        call(w.sel, gk.to_device(rows, np.uint32), depth, buf[4:4 + count], count, gk.to_device(bad), w.rot(depth), st)
         with pytest.raises(R.RtfheError) as ei:
             w.eng.sync(st)
         assert ei.value.code == R._ffi.ERR_INVALID
@@ -207,15 +185,15 @@ def test_reduced_diagram_equals_the_restated_net(world):
     net = R.bdd_netlist(5, three_of_five)
     count = 5
     rng = np.random.default_rng(w.N + 41)
-    sel_idx = rng.integers(0, N_SEL, (count, 5)).astype(np.int32)
-    row0 = rng.integers(0, N_ROWS - 2 + 1, count).astype(np.int32)
+    sel_idx = rng.integers(0, TREE_N_SEL, (count, 5)).astype(np.int32)
+    row0 = rng.integers(0, TREE_N_ROWS - 2 + 1, count).astype(np.int32)
     import torch
     st = torch.cuda.current_stream().cuda_stream
     for kind in ("plain", "encrypted"):
         rows = as_trlwe(w.rows[kind], w.N)
         want = np.stack([lo.cmux_net(w.P, w.plan, w.sel_f, sel_idx[g], rows[row0[g]:], net) for g in range(count)])
         d_out = torch.zeros((count, 3, 2, w.N), dtype=torch.int32, device="cuda")
-        with w.eng.cmux_circuit(net, w.sel, w.lut[kind], d_out, count, _cuda(sel_idx), _cuda(row0), rounded=True) as c:
+        with w.eng.cmux_circuit(net, w.sel, w.lut[kind], d_out, count, gk.to_device(sel_idx), gk.to_device(row0), rounded=True) as c:
             assert c.rounded and w.eng.leveled_decomposition() == R._ffi.DECOMP_REFERENCE
             c.launch(st)
             w.eng.sync(st)
@@ -228,9 +206,9 @@ def test_tree_and_rotation_netlists_equal_their_entry_points_in_rounded_mode(wor
     w = world
     count = 6
     rng = np.random.default_rng(w.N + 43)
-    sel3 = rng.integers(0, N_SEL, (count, 3)).astype(np.int32)
-    sel5 = rng.integers(0, N_SEL, (count, 5)).astype(np.int32)
-    row0 = rng.integers(0, N_ROWS - 8 + 1, count).astype(np.int32)
+    sel3 = rng.integers(0, TREE_N_SEL, (count, 3)).astype(np.int32)
+    sel5 = rng.integers(0, TREE_N_SEL, (count, 5)).astype(np.int32)
+    row0 = rng.integers(0, TREE_N_ROWS - 8 + 1, count).astype(np.int32)
     rot = [2 * w.N - 1, 0, w.N, 1, int(rng.integers(0, 2 * w.N))]
     rows = as_trlwe(w.rows["encrypted"], w.N)[:count]
     ref_tree = w.eng.cmux_tree_batch(w.sel, w.lut["encrypted"], 3, count, sel3, row0)
@@ -238,10 +216,10 @@ def test_tree_and_rotation_netlists_equal_their_entry_points_in_rounded_mode(wor
     with _leveled(w.eng):
         for kind in ("plain", "encrypted"):
             want = w.eng.cmux_tree_batch(w.sel, w.lut[kind], 3, count, sel3, row0)
-            assert np.array_equal(_net_run(w, w.R.cmux_tree_netlist(3), w.lut[kind], count, sel3, row0)[:, 0], want), kind
+            assert np.array_equal(net_run(w, w.R.cmux_tree_netlist(3), w.lut[kind], count, sel3, row0)[:, 0], want), kind
         assert not np.array_equal(want, ref_tree)
         want = w.eng.trgsw_rotate_batch(w.sel, rows, 5, sel5, rot)
-        got = _net_run(w, w.R.trgsw_rotate_netlist(5, rot), w.lut["encrypted"], count, sel5, np.arange(count, dtype=np.int32))
+        got = net_run(w, w.R.trgsw_rotate_netlist(5, rot), w.lut["encrypted"], count, sel5, np.arange(count, dtype=np.int32))
         assert np.array_equal(got[:, 0], want) and not np.array_equal(want, ref_rot)
 
 
@@ -251,7 +229,7 @@ def test_a_cmux_circuit_keeps_the_mode_it_was_recorded_in(world):
     import torch
     w = world
     count = 5
-    sel_idx = np.random.default_rng(w.N + 45).integers(0, N_SEL, (count, 2)).astype(np.int32)
+    sel_idx = np.random.default_rng(w.N + 45).integers(0, TREE_N_SEL, (count, 2)).astype(np.int32)
     lut = w.lut["encrypted"]
     net = w.R.cmux_tree_netlist(2)
     st = torch.cuda.current_stream().cuda_stream
@@ -261,7 +239,7 @@ def test_a_cmux_circuit_keeps_the_mode_it_was_recorded_in(world):
             with _leveled(w.eng, rounded):
                 want[rounded] = w.eng.cmux_tree_batch(w.sel, lut, 2, count, sel_idx)
                 outs[rounded] = torch.zeros((count, 1, 2, w.N), dtype=torch.int32, device="cuda")
-                circ[rounded] = w.eng.cmux_circuit(net, w.sel, lut, outs[rounded], count, _cuda(sel_idx))
+                circ[rounded] = w.eng.cmux_circuit(net, w.sel, lut, outs[rounded], count, gk.to_device(sel_idx))
                 assert circ[rounded].rounded == rounded
         assert not np.array_equal(want[False], want[True])
         for at_replay in (False, True, False):
@@ -285,7 +263,7 @@ def test_second_opinion_from_external_products_alone(world):
     depth, count = 3, 5
     rng = np.random.default_rng(w.N + 47)
     sel_idx = rng.integers(0, depth, (count, depth)).astype(np.int32)
-    row0 = rng.integers(0, N_ROWS - 8 + 1, count).astype(np.int32)
+    row0 = rng.integers(0, TREE_N_ROWS - 8 + 1, count).astype(np.int32)
     e = R.Engine(R.Params(n=depth, N=w.N), 0)
     try:
         e.load_bk_torus(w.sel_t[:depth].reshape(-1))
@@ -315,8 +293,8 @@ def test_second_opinion_from_external_products_alone(world):
 def _leveled_calls(w):
     rng = np.random.default_rng(w.N + 51)
     count = 5
-    sel3 = rng.integers(0, N_SEL, (count, 3)).astype(np.int32)
-    row0 = rng.integers(0, N_ROWS - 8 + 1, count).astype(np.int32)
+    sel3 = rng.integers(0, TREE_N_SEL, (count, 3)).astype(np.int32)
+    row0 = rng.integers(0, TREE_N_ROWS - 8 + 1, count).astype(np.int32)
     rows = w.rot_rows[:count]
     idx = rng.integers(0, w.rp.n, count).astype(np.int32)
     net = w.R.cmux_tree_netlist(3)
@@ -324,7 +302,7 @@ def _leveled_calls(w):
     def run():
         return [w.eng.cmux_tree_batch(w.sel, w.lut["encrypted"], 3, count, sel3, row0), w.eng.cmux_tree_extract_batch(w.sel, w.lut["plain"], 3, count, sel3, row0),
                 w.eng.trgsw_rotate_batch(w.sel, rows, 3, sel3, w.rot(3)), w.eng.trgsw_rotate_extract_batch(w.sel, rows, 3, sel3),
-                _net_run(w, net, w.lut["encrypted"], count, sel3, row0), w.eng.external_product_batch(idx, rows)]
+                net_run(w, net, w.lut["encrypted"], count, sel3, row0), w.eng.external_product_batch(idx, rows)]
     return run, (sel3, row0, rows)
 
 
@@ -363,8 +341,8 @@ def test_the_leveled_mode_alone_leaves_pbs_gates_mux_bootstrap_blind_rotation_an
     w, R = world, world.R
     rng = np.random.default_rng(w.N + 53)
     n1 = w.rp.n + 1
-    a, b, c = (_random_words(rng, (37, n1)) for _ in range(3))
-    tv, trl = _random_words(rng, (2, w.N)), _random_words(rng, (2, 2, w.N))
+    a, b, c = (random_words(rng, (37, n1)) for _ in range(3))
+    tv, trl = random_words(rng, (2, w.N)), random_words(rng, (2, 2, w.N))
     idx = rng.integers(0, 2, 37).astype(np.int32)
     pk = R.packing_keygen(w.rp, w.key0, w.key1, 0xBACC + w.N)
     with w.eng.lut(tv) as plain, w.eng.lut_encrypted(trl) as enc, w.eng.packing_key(pk) as key:
@@ -392,16 +370,16 @@ def test_captured_tree_replays_the_eager_words_in_rounded_mode(world):
     w = world
     depth, count = 3, 37
     rng = np.random.default_rng(w.N + 61)
-    sel_idx, row0, coef = (rng.integers(0, hi, shape).astype(np.int32) for hi, shape in ((N_SEL, (count, depth)), (N_ROWS - 8 + 1, count), (w.N, count)))
+    sel_idx, row0, coef = (rng.integers(0, hi, shape).astype(np.int32) for hi, shape in ((TREE_N_SEL, (count, depth)), (TREE_N_ROWS - 8 + 1, count), (w.N, count)))
     lut = w.lut["encrypted"]
     with _leveled(w.eng):
         want = w.eng.cmux_tree_batch(w.sel, lut, depth, count, sel_idx, row0)
         want_x = w.eng.cmux_tree_extract_batch(w.sel, lut, depth, count, sel_idx, row0, coef)
-    e = _engine(w.R, w.rp, w.bk, w.ksk)
+    e = gk.engine(w.R, w.rp, w.bk, w.ksk)
     try:
         with e.selectors(w.sel_t) as sel, e.lut_encrypted(w.rows["encrypted"]) as elut:
             s = torch.cuda.Stream()
-            d_idx, d_row0, d_coef = _cuda(sel_idx), _cuda(row0), _cuda(coef)
+            d_idx, d_row0, d_coef = gk.to_device(sel_idx), gk.to_device(row0), gk.to_device(coef)
             out = torch.zeros((count, 2, w.N), dtype=torch.int32, device="cuda")
             out_x = torch.zeros((count, w.rp.n + 1), dtype=torch.int32, device="cuda")
 
@@ -434,14 +412,14 @@ def test_captured_rotation_without_a_prior_eager_call_in_rounded_mode(world):
     import torch
     w = world
     depth, count = 5, 37
-    sel_idx = np.random.default_rng(w.N + 63).integers(0, N_SEL, (count, depth)).astype(np.int32)
+    sel_idx = np.random.default_rng(w.N + 63).integers(0, TREE_N_SEL, (count, depth)).astype(np.int32)
     with _leveled(w.eng):
         want = w.eng.trgsw_rotate_batch(w.sel, w.rot_rows, depth, sel_idx, w.rot(depth))
-    e = _engine(w.R, w.rp, w.bk, w.ksk)
+    e = gk.engine(w.R, w.rp, w.bk, w.ksk)
     try:
         with e.selectors(w.sel_t) as sel:
             s = torch.cuda.Stream()
-            d_idx, d_in = _cuda(sel_idx), _cuda(w.rot_rows, np.uint32)
+            d_idx, d_in = gk.to_device(sel_idx), gk.to_device(w.rot_rows, np.uint32)
             out = torch.zeros((count, 2, w.N), dtype=torch.int32, device="cuda")
             torch.cuda.synchronize()
             with torch.cuda.stream(s):
@@ -504,12 +482,12 @@ def test_two_entry_context_takes_the_mode(world):
     w, R = world, world.R
     rng = np.random.default_rng(w.N + 71)
     count = 5
-    sel3 = rng.integers(0, N_SEL, (count, 3)).astype(np.int32)
-    a, b = _random_words(rng, (7, w.rp.n + 1)), _random_words(rng, (7, w.rp.n + 1))
+    sel3 = rng.integers(0, TREE_N_SEL, (count, 3)).astype(np.int32)
+    a, b = random_words(rng, (7, w.rp.n + 1)), random_words(rng, (7, w.rp.n + 1))
     gates = w.eng.gate_batch(R.NAND, a, b)
     with _leveled(w.eng):
         want = w.eng.cmux_tree_batch(w.sel, w.lut["plain"], 3, count, sel3), w.eng.trgsw_rotate_batch(w.sel, w.rot_rows[:count], 3, sel3)
-    multi = _engine(R, w.rp, w.bk, w.ksk, devices=[0, 0])
+    multi = gk.engine(R, w.rp, w.bk, w.ksk, devices=[0, 0])
     try:
         assert multi.device_count() == 2 and multi.leveled_decomposition() == R._ffi.DECOMP_REFERENCE
         multi.set_leveled_decomposition(R._ffi.DECOMP_ROUNDED)

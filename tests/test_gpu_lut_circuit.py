@@ -7,46 +7,15 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_pbs import _engine, _random_words
+import gpu_kit as gk
+from kit import keys_2048, random_words
+from lut_circuit_kit import adder_inputs, create, decode, host_compose, random_circuit, replay
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E8 = 0x20000000
 U32 = 0xFFFFFFFF
-
-
-def host_compose(e, lut, d, wires):
-    """rtfhe.h's LUT-circuit semantics on the host: per wave the weighted sums in numpy (wrapping u32), then Engine.pbs_many_batch."""
-    w = np.array(wires, np.uint32, copy=True)
-    F = d["fan_in"]
-    idx, wt = np.asarray(d["in_idx"]).reshape(-1, F), np.asarray(d["weights"]).reshape(-1, F)
-    cst = np.zeros(idx.shape[0], np.uint32) if d["cst"] is None else np.asarray(d["cst"], np.uint32)
-    offs, n_out, out_idx = d["wave_offsets"], d["wave_n_out"], np.asarray(d["out_idx"])
-    row = 0
-    for v in range(len(n_out)):
-        lo, hi, th = int(offs[v]), int(offs[v + 1]), int(n_out[v])
-        t = np.zeros((hi - lo, w.shape[1]), np.uint32)
-        for k in range(F):
-            used = idx[lo:hi, k] >= 0
-            t[used] += wt[lo:hi, k][used].astype(np.uint32)[:, None] * w[idx[lo:hi, k][used]]
-        t[:, -1] += cst[lo:hi]
-        li = None if d["lut_idx"] is None else np.asarray(d["lut_idx"])[lo:hi]
-        out = e.pbs_many_batch(lut, t, th, li).reshape(-1, w.shape[1])
-        w[out_idx[row:row + out.shape[0]]] = out
-        row += out.shape[0]
-    return w
-
-
-def create(e, lut, d, wires):
-    return e.lut_circuit_create(lut, d["fan_in"], d["in_idx"], d["weights"], d["cst"], d["lut_idx"], d["wave_offsets"], d["wave_n_out"],
-                                d["out_idx"], wires, d["num_wires"])
-
-
-def replay(e, c, wires):
-    e.circuit_launch(c)
-    e.sync()
-    return wires.cpu().numpy().view(np.uint32).copy()
 
 
 # ---- gate netlists as LUT circuits -------------------------------------------------------------------------------------------------------
@@ -98,54 +67,15 @@ def test_gate_netlists_as_lut_circuits_word_for_word(engine, keys, params, which
 
 
 # ---- random circuits against the host composition ----------------------------------------------------------------------------------------
-def _random_circuit(rng, fan_in, replicas, n_tables=3):
-    """Per replica: 6 input wires, then waves (level 1: n_out 1, then 4; level 2: 2, then 8; level 3: a pair of n_out = 1 nodes that swap two
-    wires in place) with one node per replica each, except the swap.  Random weights, constants, table indices and used slots."""
-    inputs = 6
-    plan = [(1, 1), (4, 1), (2, 1), (8, 1), (1, 2)]        # (n_out, nodes per replica)
-    W = inputs + sum(th * k for th, k in plan[:-1])
-    in_idx, wts, cst, lut_idx, out_idx, offs, n_out = [], [], [], [], [], [0], []
-    avail = list(range(inputs))
-    nxt = inputs
-    level_new = []
-    for v, (th, k) in enumerate(plan):
-        if v in (2, 4):                                      # a new level: what the previous one wrote becomes readable
-            avail += level_new
-            level_new = []
-        swap = v == len(plan) - 1
-        outs = [[nxt + j * th + i for i in range(th)] for j in range(k)] if not swap else [[avail[-1]], [avail[-2]]]
-        srcs = [None] * k if not swap else [[avail[-2]], [avail[-1]]]
-        for r in range(replicas):
-            for j in range(k):
-                used = rng.integers(1, fan_in + 1)
-                ws = list(rng.choice(avail, used)) if srcs[j] is None else srcs[j] * used
-                in_idx.append([r * W + x for x in ws] + [-1] * (fan_in - used))
-                wts.append(list(rng.integers(-(1 << 31), 1 << 31, used)) + list(rng.integers(-5, 5, fan_in - used)))
-                cst.append(int(rng.integers(0, 1 << 32)))
-                lut_idx.append(int(rng.integers(0, n_tables)))
-                out_idx.extend(r * W + o for o in outs[j])
-        if not swap:
-            level_new += [o for oo in outs for o in oo]
-            nxt += th * k
-        offs.append(offs[-1] + replicas * k)
-        n_out.append(th)
-    perm = rng.permutation(fan_in)                          # unused slots anywhere, not only at the end
-    in_idx = np.array(in_idx, np.int64)[:, perm]
-    wts = np.array(wts, np.int64)[:, perm]
-    return {"fan_in": fan_in, "in_idx": in_idx.astype(np.int32), "weights": wts.astype(np.int32), "cst": np.array(cst, np.uint32),
-            "lut_idx": np.array(lut_idx, np.int32), "wave_offsets": np.array(offs, np.int32), "wave_n_out": np.array(n_out, np.int32),
-            "out_idx": np.array(out_idx, np.int32), "num_wires": replicas * W}
-
-
 def _check_random(e, seed, fan_ins, replica_counts):
     import torch
     rng = np.random.default_rng(seed)
     n1 = e.p.n + 1
-    with e.lut(_random_words(rng, (3, e.p.N))) as lut:
+    with e.lut(random_words(rng, (3, e.p.N))) as lut:
         for fan_in in fan_ins:
             for reps in replica_counts:
-                d = _random_circuit(rng, fan_in, reps)
-                w0 = _random_words(rng, (d["num_wires"], n1))
+                d = random_circuit(rng, fan_in, reps)
+                w0 = random_words(rng, (d["num_wires"], n1))
                 wires = torch.from_numpy(w0.view(np.int32)).cuda()
                 want = host_compose(e, lut, d, w0)
                 c = create(e, lut, d, wires)
@@ -165,7 +95,7 @@ def test_random_circuits_match_host_composition_n1024(engine):
 
 def test_random_circuits_match_host_composition_ks_ext(params, keys, monkeypatch):
     import rustfhe_amd as R
-    e = _engine(R, R.Params(n=params.n, N=params.N), keys.bk_t, keys.ksk, monkeypatch, {"RTFHE_KS_MM_MIN": "0"})
+    e = gk.engine(R, R.Params(n=params.n, N=params.N), keys.bk_t, keys.ksk, monkeypatch, {"RTFHE_KS_MM_MIN": "0"})
     try:
         _check_random(e, 102, (2, 5), REPLICAS)
     finally:
@@ -174,14 +104,13 @@ def test_random_circuits_match_host_composition_ks_ext(params, keys, monkeypatch
 
 @pytest.fixture(scope="module")
 def keys2048(orc):
-    P = orc.Params(N=2048)
-    return P, orc.Keys(P, 2048)
+    return keys_2048(orc)
 
 
 def test_random_circuits_match_host_composition_n2048(keys2048):
     import rustfhe_amd as R
     P, K = keys2048
-    e = _engine(R, R.Params(N=2048), K.bk_t, K.ksk)
+    e = gk.engine(R, R.Params(N=2048), K.bk_t, K.ksk)
     try:
         _check_random(e, 103, (4, 7), REPLICAS)
     finally:
@@ -189,24 +118,12 @@ def test_random_circuits_match_host_composition_n2048(keys2048):
 
 
 # ---- the adder -----------------------------------------------------------------------------------------------------------------------
-def _adder_inputs(R, p, key0, reps, seed):
-    rng = np.random.default_rng(seed)
-    a, b = rng.integers(0, 256, reps), rng.integers(0, 256, reps)
-    bits = np.concatenate([(a[:, None] >> np.arange(8)) & 1, (b[:, None] >> np.arange(8)) & 1], axis=1)
-    return a, b, R.encrypt_torus(p, key0, R.encode_msgs(bits.reshape(-1), 2), seed=seed).reshape(reps, 16, p.n + 1)
-
-
-def _decode(R, p, key0, out):
-    bits = R.decode_msgs(R.phases(p, key0, out.reshape(-1, p.n + 1)), 2).reshape(out.shape[0], -1)
-    return (bits << np.arange(bits.shape[1])).sum(axis=1)
-
-
 def test_adder_on_encrypted_bytes(engine, keys):
     import rustfhe_amd as R
     p = engine.p
     reps = 1024
     net = R.lut_ripple_adder(8)
-    a, b, cts = _adder_inputs(R, p, keys.key0, reps, 0xB17E)
+    a, b, cts = adder_inputs(R, p, keys.key0, reps, 0xB17E)
     run = R.LutCircuitRunner(engine, net, reps)
     try:
         run.set_inputs(cts)
@@ -215,7 +132,7 @@ def test_adder_on_encrypted_bytes(engine, keys):
         with engine.lut(net.polynomials(p.N)) as lut:
             want = host_compose(engine, lut, run.desc, w0)
         assert np.array_equal(run.wires.cpu().numpy().view(np.uint32), want)
-        assert np.array_equal(_decode(R, p, keys.key0, run.outputs()), a + b)
+        assert np.array_equal(decode(R, p, keys.key0, run.outputs()), a + b)
     finally:
         run.close()
 
@@ -223,26 +140,26 @@ def test_adder_on_encrypted_bytes(engine, keys):
 def test_replays_new_inputs_and_a_key_change(params, keys):
     import rustfhe_amd as R
     p = R.Params(n=params.n, N=params.N)
-    e = _engine(R, p, keys.bk_t, keys.ksk)
+    e = gk.engine(R, p, keys.bk_t, keys.ksk)
     reps = 300
     run = R.LutCircuitRunner(e, R.lut_ripple_adder(8), reps)
     try:
-        a, b, cts = _adder_inputs(R, p, keys.key0, reps, 1)
+        a, b, cts = adder_inputs(R, p, keys.key0, reps, 1)
         run.set_inputs(cts)
         first = run.run().wires.cpu().numpy().copy()
         second = run.run().wires.cpu().numpy().copy()
         assert np.array_equal(first, second)
-        assert np.array_equal(_decode(R, p, keys.key0, run.outputs()), a + b)
-        a, b, cts = _adder_inputs(R, p, keys.key0, reps, 2)
+        assert np.array_equal(decode(R, p, keys.key0, run.outputs()), a + b)
+        a, b, cts = adder_inputs(R, p, keys.key0, reps, 2)
         run.set_inputs(cts)
-        assert np.array_equal(_decode(R, p, keys.key0, run.run().outputs()), a + b)
+        assert np.array_equal(decode(R, p, keys.key0, run.run().outputs()), a + b)
         # a different key set loaded after recording: the replay computes with it
         k0b, k1b, bkb, kskb = R.keygen(p, 535353)
         e.load_bk_torus(bkb)
         e.load_ksk(kskb)
-        a, b, cts = _adder_inputs(R, p, k0b, reps, 3)
+        a, b, cts = adder_inputs(R, p, k0b, reps, 3)
         run.set_inputs(cts)
-        assert np.array_equal(_decode(R, p, k0b, run.run().outputs()), a + b), "the replay computed with the old key"
+        assert np.array_equal(decode(R, p, k0b, run.run().outputs()), a + b), "the replay computed with the old key"
     finally:
         run.close()
         e.close()
@@ -254,10 +171,10 @@ def test_rejects_leave_the_context_usable(engine):
     import rustfhe_amd as R
     rng = np.random.default_rng(7)
     p = engine.p
-    d = _random_circuit(rng, 3, 4)
+    d = random_circuit(rng, 3, 4)
     wires = torch.zeros((d["num_wires"], p.n + 1), dtype=torch.int32, device="cuda")
-    ct = _random_words(rng, (37, p.n + 1))
-    with engine.lut(_random_words(rng, (3, p.N))) as lut:
+    ct = random_words(rng, (37, p.n + 1))
+    with engine.lut(random_words(rng, (3, p.N))) as lut:
         ref = engine.pbs_many_batch(lut, ct, 2)
 
         def bad(**kw):
@@ -298,11 +215,11 @@ def test_table_destroyed_first_and_context_destroyed_first(params, keys):
     import torch
     import rustfhe_amd as R
     p = R.Params(n=params.n, N=params.N)
-    e = _engine(R, p, keys.bk_t, keys.ksk)
+    e = gk.engine(R, p, keys.bk_t, keys.ksk)
     rng = np.random.default_rng(9)
-    d = _random_circuit(rng, 4, 37)
-    w0 = _random_words(rng, (d["num_wires"], p.n + 1))
-    tv = _random_words(rng, (3, p.N))
+    d = random_circuit(rng, 4, 37)
+    w0 = random_words(rng, (d["num_wires"], p.n + 1))
+    tv = random_words(rng, (3, p.N))
     wires = torch.from_numpy(w0.view(np.int32)).cuda()
     lut = e.lut(tv)
     keep = create(e, lut, d, wires)

@@ -12,18 +12,13 @@ Wall time, measured on an MI355X (256 CUs, 16 host threads for the oracle; profi
 the rest of the GPU suite -- 113 % where 50 % was budgeted.  103 s are the CPU oracle on the six long masks of the default-engine sweep; the
 random picks are at their floor of 8 per batch and the forced shapes at the smallest allowed subset plus 640 / 704, and the mask lengths, the
 boundary gates and the default-engine sweep are not cut."""
-import os
-import threading
-from concurrent.futures import ThreadPoolExecutor
-
 import numpy as np
 import pytest
 
-from test_gpu_lut_circuit import _adder_inputs, _decode, _random_circuit, create, host_compose, replay
-from test_gpu_pbs import _engine, _random_words
-from test_pbs_enc_host import oracle_pbs_enc
-from test_pbs_host import oracle_pbs
-from test_pbs_many_host import oracle_pbs_many
+import gpu_kit as gk
+from kit import random_words
+from lut_circuit_kit import adder_inputs, create, decode, host_compose, random_circuit, replay
+from pbs_oracle import oracle_pbs, oracle_pbs_enc, oracle_pbs_many
 
 pytestmark = pytest.mark.gpu
 
@@ -31,24 +26,7 @@ MASKS = {1024: (1, 2, 63, 64, 639, 640, 767), 2048: (1, 63, 64, 703, 704, 767)}
 ALL = [(N, n) for N in (1024, 2048) for n in MASKS[N]]
 # small first: a carve or ring defect shows at n = 63 / 64 before the degenerate step counts and the long masks run
 ORDER = sorted(ALL, key=lambda m: (m[1] in (1, 2), m[1] > 64, m[0], m[1]))
-THREADS = min(16, os.cpu_count() or 1)
 RANDOM_PICKS = 8
-_pool = ThreadPoolExecutor(THREADS)
-
-
-def _cus():
-    import torch
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def _sizes(N, C):
-    if N == 1024:
-        return [1, C + C // 6, 2 * C + C // 3, 3 * C + C // 2, 4 * C, 4 * C + 1, 5 * C, 6 * C, 9 * C + 44]
-    return [1, 37, C + 1, 2 * C + 1, 3 * C + 2, 4 * C, 4 * C + 76]
-
-
-def _forced_sizes(N, C):
-    return [1, C + C // 6, 2 * C + C // 3, 4 * C, 5 * C] if N == 1024 else [37, 2 * C + 1, 4 * C + 76]
 
 
 def _picks(count, N, C, rng):
@@ -64,21 +42,6 @@ def _picks(count, N, C, rng):
     return sorted(s)
 
 
-def _pmap(fn, items):
-    return list(_pool.map(fn, items))
-
-
-_tls = threading.local()
-
-
-def _plan(orc, N, backend=0):
-    """an oracle plan of the calling thread's own (a plan carries transform scratch: one per thread)"""
-    plans = _tls.__dict__.setdefault("plans", {})
-    if (N, backend) not in plans:
-        plans[N, backend] = orc.Plan(N, backend)
-    return plans[N, backend]
-
-
 class Mask:
     def __init__(self, orc, N, n):
         import rustfhe_amd as R
@@ -86,18 +49,18 @@ class Mask:
         self.P = orc.Params(n=n, N=N)
         self.K = orc.Keys(self.P, 7000 + N + n)
         self.p = R.Params(n=n, N=N)
-        self.C = _cus()
-        self.e = _engine(R, self.p, self.K.bk_t, self.K.ksk)
+        self.C = gk.cus()
+        self.e = gk.engine(R, self.p, self.K.bk_t, self.K.ksk)
 
     def engine(self, monkeypatch=None, env=None):
         import rustfhe_amd as R
-        return _engine(R, self.p, self.K.bk_t, self.K.ksk, monkeypatch, env)
+        return gk.engine(R, self.p, self.K.bk_t, self.K.ksk, monkeypatch, env)
 
     def gates(self, op, c0, c1, backend=None):
         orc, K = self.orc, self.K
         if backend is None:
-            return orc.gate_batch_mt(self.P, op, K.bk_f, None, K.ksk, c0, c1, nthreads=THREADS)[0]
-        return orc.gate_batch_mt(self.P, op, None, K.bk_t, K.ksk, c0, c1, nthreads=THREADS, backend=backend)[0]
+            return orc.gate_batch_mt(self.P, op, K.bk_f, None, K.ksk, c0, c1, nthreads=gk.THREADS)[0]
+        return orc.gate_batch_mt(self.P, op, None, K.bk_t, K.ksk, c0, c1, nthreads=gk.THREADS, backend=backend)[0]
 
 
 @pytest.fixture(scope="module", params=ORDER, ids=lambda m: "N%d-n%d" % m)
@@ -116,11 +79,11 @@ def test_default_engine_every_batch_shape_against_the_oracle(mask):
     import rustfhe_amd as R
     m, orc, P, K, e = mask, mask.orc, mask.P, mask.K, mask.e
     rng = np.random.default_rng(100 * m.N + m.n)
-    tv = _random_words(rng, (3, m.N))
+    tv = random_words(rng, (3, m.N))
     trl = R.encrypt_lut(m.p, K.key1, tv, seed=m.n)
     with e.lut(tv) as lut, e.lut_encrypted(trl) as enc:
-        for G in _sizes(m.N, m.C):
-            c0, c1 = _random_words(rng, (G, m.n + 1)), _random_words(rng, (G, m.n + 1))
+        for G in gk.sizes(m.N, m.C):
+            c0, c1 = random_words(rng, (G, m.n + 1)), random_words(rng, (G, m.n + 1))
             idx = rng.integers(0, 3, G).astype(np.int32)
             pick = _picks(G, m.N, m.C, rng)
             out = e.gate_batch(R.NAND, c0, c1)
@@ -128,17 +91,17 @@ def test_default_engine_every_batch_shape_against_the_oracle(mask):
             assert np.array_equal(out[sel], m.gates(orc.NAND, c0[sel], c1[sel])), ("gate_batch", G)
             assert np.array_equal(e.bootstrap_batch(c0)[pick], m.gates(orc.COPY, c0[pick], None)), ("bootstrap_batch", G)
             got = e.pbs_batch(lut, c0, idx)
-            exp = _pmap(lambda g: oracle_pbs(orc, P, _plan(orc, m.N), K.bk_f, K.ksk, tv[idx[g]], c0[g]), pick)
+            exp = gk.pmap(lambda g: oracle_pbs(orc, P, gk.oracle_plan(orc, m.N), K.bk_f, K.ksk, tv[idx[g]], c0[g]), pick)
             assert np.array_equal(got[pick], np.stack(exp)), ("pbs_batch", G)
             for n_out in (1, 2, 8):
                 got = e.pbs_many_batch(lut, c1, n_out, idx)
-                exp = _pmap(lambda g: oracle_pbs_many(orc, P, _plan(orc, m.N), K.bk_f, K.ksk, tv[idx[g]], c1[g], n_out), pick)
+                exp = gk.pmap(lambda g: oracle_pbs_many(orc, P, gk.oracle_plan(orc, m.N), K.bk_f, K.ksk, tv[idx[g]], c1[g], n_out), pick)
                 assert np.array_equal(got[pick], np.stack(exp)), ("pbs_many_batch", n_out, G)
             got = e.pbs_many_batch(enc, c0, 4, idx)
-            exp = _pmap(lambda g: oracle_pbs_enc(orc, P, _plan(orc, m.N), K.bk_f, K.ksk, trl[idx[g]], c0[g], 4), pick)
+            exp = gk.pmap(lambda g: oracle_pbs_enc(orc, P, gk.oracle_plan(orc, m.N), K.bk_f, K.ksk, trl[idx[g]], c0[g], 4), pick)
             assert np.array_equal(got[pick], np.stack(exp)), ("encrypted table, n_out 4", G)
             got = e.pbs_batch(enc, c1, idx)
-            exp = _pmap(lambda g: oracle_pbs_enc(orc, P, _plan(orc, m.N), K.bk_f, K.ksk, trl[idx[g]], c1[g], 1)[0], pick)
+            exp = gk.pmap(lambda g: oracle_pbs_enc(orc, P, gk.oracle_plan(orc, m.N), K.bk_f, K.ksk, trl[idx[g]], c1[g], 1)[0], pick)
             assert np.array_equal(got[pick], np.stack(exp)), ("encrypted table, pbs_batch", G)
             if m.n >= 63:
                 b0, b1 = rng.integers(0, 2, G), rng.integers(0, 2, G)
@@ -150,11 +113,11 @@ def test_blind_rotation_prefixes_at_the_edges_of_the_step_count(mask):
     m, orc, e = mask, mask.orc, mask.e
     rng = np.random.default_rng(200 * m.N + m.n)
     for G in (5, m.C + m.C // 6):
-        t = _random_words(rng, (G, m.n + 1))
+        t = random_words(rng, (G, m.n + 1))
         pick = _picks(G, m.N, m.C, rng)
         for steps in sorted({0, 1, m.n - 1, m.n}):
             got = e.blind_rotate_batch(t, steps).reshape(G, -1)
-            exp = _pmap(lambda g: orc.blind_rotate(m.P, _plan(orc, m.N), m.K.bk_f, None, t[g], steps), pick)
+            exp = gk.pmap(lambda g: orc.blind_rotate(m.P, gk.oracle_plan(orc, m.N), m.K.bk_f, None, t[g], steps), pick)
             assert np.array_equal(got[pick], np.stack(exp)), (G, steps)
 
 
@@ -176,12 +139,12 @@ def test_forced_shapes_equal_the_default_engine(mask, monkeypatch):
     if m.n not in FORCED_MASKS[m.N]:
         return
     rng = np.random.default_rng(300 * m.N + m.n)
-    tv = _random_words(rng, (3, m.N))
+    tv = random_words(rng, (3, m.N))
     trl = R.encrypt_lut(m.p, m.K.key1, tv, seed=m.n + 1)
     cases = []
     with e.lut(tv) as lut, e.lut_encrypted(trl) as enc:
-        for G in _forced_sizes(m.N, m.C):
-            c0, c1 = _random_words(rng, (G, m.n + 1)), _random_words(rng, (G, m.n + 1))
+        for G in gk.forced_sizes(m.N, m.C):
+            c0, c1 = random_words(rng, (G, m.n + 1)), random_words(rng, (G, m.n + 1))
             idx = rng.integers(0, 3, G).astype(np.int32)
             cases.append((c0, c1, idx, e.gate_batch(R.NAND, c0, c1), e.pbs_batch(lut, c0, idx), e.pbs_many_batch(lut, c1, 4, idx),
                           e.pbs_many_batch(enc, c0, 4, idx)))
@@ -211,7 +174,7 @@ def test_exact_backends_agree_and_match_the_exact_oracle(mask):
     backends = (R._ffi.BACKEND_NTT_EXACT, R._ffi.BACKEND_FFT_SPLIT_EXACT)
     try:
         for G in (1, C + C // 6, 4 * C, 5 * C, 6 * C):
-            c0, c1 = _random_words(rng, (G, m.n + 1)), _random_words(rng, (G, m.n + 1))
+            c0, c1 = random_words(rng, (G, m.n + 1)), random_words(rng, (G, m.n + 1))
             outs = []
             for b in backends:
                 e.set_backend(b)
@@ -228,16 +191,16 @@ def test_exact_backends_agree_and_match_the_exact_oracle(mask):
                 assert K.decrypt_bits(e.gate_batch(R.XOR, K.encrypt_bits(b0), K.encrypt_bits(b1))) == list(b0 ^ b1), G
         if m.n > 64:
             for G in (5, C + C // 6):
-                t = _random_words(rng, (G, m.n + 1))
+                t = random_words(rng, (G, m.n + 1))
                 pick = sorted({0, G - 1} | set(rng.choice(G, min(G, 4), replace=False).tolist()))
                 for steps in (1, 3):
-                    exp = np.stack(_pmap(lambda g: orc.blind_rotate(m.P, _plan(orc, m.N, orc.BACKEND_EXACT), None, K.bk_t, t[g], steps), pick))
+                    exp = np.stack(gk.pmap(lambda g: orc.blind_rotate(m.P, gk.oracle_plan(orc, m.N, orc.BACKEND_EXACT), None, K.bk_t, t[g], steps), pick))
                     for b in backends:
                         e.set_backend(b)
                         assert np.array_equal(e.blind_rotate_batch(t, steps).reshape(G, -1)[pick], exp), (b, G, steps)
-        ct = _random_words(rng, (37, m.n + 1))
+        ct = random_words(rng, (37, m.n + 1))
         e.set_backend(R._ffi.BACKEND_FFT64_MIRROR)
-        with e.lut(_random_words(rng, (1, m.N))) as lut:
+        with e.lut(random_words(rng, (1, m.N))) as lut:
             for b in backends:
                 e.set_backend(b)
                 with pytest.raises(R.RtfheError) as ei:
@@ -263,7 +226,7 @@ def test_lut_circuit_adder_vector_and_scalar_rows(mask):
     for misaligned in LUT_MASKS.get((m.N, m.n), ()):
         reps = 4 * m.C + 1
         net = R.lut_ripple_adder(8)
-        a, b, cts = _adder_inputs(R, m.p, m.K.key0, reps, 0xA000 + m.n)
+        a, b, cts = adder_inputs(R, m.p, m.K.key0, reps, 0xA000 + m.n)
         run = R.LutCircuitRunner(e, net, reps)
         try:
             if misaligned:
@@ -279,17 +242,17 @@ def test_lut_circuit_adder_vector_and_scalar_rows(mask):
                 run.run()
                 assert np.array_equal(run.wires.cpu().numpy().view(np.uint32), want), (m.n, misaligned)
             if m.n >= 640:
-                assert np.array_equal(_decode(R, m.p, m.K.key0, run.outputs()), a + b)
+                assert np.array_equal(decode(R, m.p, m.K.key0, run.outputs()), a + b)
         finally:
             run.close()
         rng = np.random.default_rng(500 * m.N + m.n + misaligned)
-        d = _random_circuit(rng, 3, reps)
+        d = random_circuit(rng, 3, reps)
         assert np.count_nonzero(d["cst"]) > 0
-        w0 = _random_words(rng, (d["num_wires"], m.n + 1))
+        w0 = random_words(rng, (d["num_wires"], m.n + 1))
         big = torch.zeros(w0.size + 8, dtype=torch.int32, device="cuda")
         wires = big[1:1 + w0.size].view(w0.shape) if misaligned else big[:w0.size].view(w0.shape)
         wires.copy_(torch.from_numpy(w0.view(np.int32)))
-        with e.lut(_random_words(rng, (3, m.N))) as lut:
+        with e.lut(random_words(rng, (3, m.N))) as lut:
             c = create(e, lut, d, wires)
             try:
                 for _ in range(2):                   # the last wave swaps two wires in place: the second replay starts from the first's table
@@ -316,7 +279,7 @@ def test_time_sliced_launch_at_five_gates_per_cu(mask, monkeypatch):
             out = eng.gate_batch(R.NAND, c0, c1)
             return eng.timer_end()[1], out
         for G, fewer in ((4 * C + 1, True), (5 * C, True), (6 * C, False)):
-            c0, c1 = _random_words(rng, (G, m.n + 1)), _random_words(rng, (G, m.n + 1))
+            c0, c1 = random_words(rng, (G, m.n + 1)), random_words(rng, (G, m.n + 1))
             (ka, a), (kb, b) = launches(e, c0, c1), launches(off, c0, c1)
             assert np.array_equal(a, b), G
             assert (ka < kb) if fewer else (ka == kb), (G, ka, kb)

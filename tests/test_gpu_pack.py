@@ -7,18 +7,14 @@ import types
 import numpy as np
 import pytest
 
-import pack_oracle as O
+import gpu_kit as gk
 import pack_helpers as H
+import pack_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 EDGE_KEY = np.array([0, 0x7F, 0x80, 0xFF, 0x7FFFFFFF, 0x80000000, 0x80808080, 0x7F7F7F7F, 0xFFFFFFFF], np.uint32)
 EDGE_A = np.array([0x00007FFF, 0x00008000, 0xFFFF7FFF, 0xFFFF8000, 0xFFFFFFFF, 0], np.uint32)
-
-
-def _cuda(a, dtype=np.int32):
-    import torch
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype).view(np.int32)).cuda()
 
 
 def _inputs(rng, rp, M):
@@ -45,30 +41,23 @@ def _plant(rp, pk, tlwe):
                 break
 
 
-_WORLDS = {}
-
-
 @pytest.fixture(scope="module")
 def worlds():
     """one engine (no bootstrapping key, no key-switching key), one key of random words and its handle per (N, n); built on first use"""
     import rustfhe_amd as R
 
-    def get(N, n):
-        if (N, n) not in _WORLDS:
-            rng = np.random.default_rng(N + n)
-            w = types.SimpleNamespace(R=R, rp=R.Params(n=n, N=N), N=N)
-            w.pk = rng.integers(0, 1 << 32, (n, 8, 3, 2, N), dtype=np.uint64).astype(np.uint32)
-            w.probe = _inputs(np.random.default_rng(1), w.rp, 4)      # rows 0 .. 3 of every shape's batch (see _shape_inputs)
-            _plant(w.rp, w.pk, w.probe)
-            w.eng = R.Engine(w.rp, 0)
-            w.key = w.eng.packing_key(w.pk)
-            _WORLDS[(N, n)] = w
-        return _WORLDS[(N, n)]
-    yield get
-    for w in _WORLDS.values():
-        w.key.close()
-        w.eng.close()
-    _WORLDS.clear()
+    def build(N, n):
+        rng = np.random.default_rng(N + n)
+        w = types.SimpleNamespace(R=R, rp=R.Params(n=n, N=N), N=N)
+        w.pk = rng.integers(0, 1 << 32, (n, 8, 3, 2, N), dtype=np.uint64).astype(np.uint32)
+        w.probe = _inputs(np.random.default_rng(1), w.rp, 4)      # rows 0 .. 3 of every shape's batch (see _shape_inputs)
+        _plant(w.rp, w.pk, w.probe)
+        w.eng = R.Engine(w.rp, 0)
+        w.key = w.eng.packing_key(w.pk)
+        return w
+    made = gk.Worlds(build, close=lambda w: (w.key.close(), w.eng.close()))
+    yield made
+    made.close()
 
 
 def _shape_inputs(w, count, P, seed):
@@ -83,7 +72,7 @@ def _pack_dev(w, tlwe, P, pos, rep, eng=None, key=None, stream=None):
     e, key = eng or w.eng, key or w.key
     count = tlwe.shape[0]
     st = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    d_in = _cuda(tlwe, np.uint32)
+    d_in = gk.to_device(tlwe, np.uint32)
     d_out = torch.full((count, 2, w.N), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
     e.pack_batch_dev(key, d_in, P, d_out, count, rep, pos, st)
     e.sync(st)
@@ -207,11 +196,11 @@ def test_tree_pbs_on_the_device(real_dev):
     st = torch.cuda.current_stream().cuda_stream
     pos, rep = R.lut_pack_layout(w.N, 2)
     with e.lut(tabs) as sub, e.lut_encrypted(np.zeros((G, 2, w.N), np.uint32)) as row:
-        d_lo4 = _cuda(np.repeat(c_lo, 4, axis=0), np.uint32)                 # input g four times: with sub-table 0 .. 3
-        d_idx4 = _cuda(np.tile(np.arange(4, dtype=np.int32), G))
+        d_lo4 = gk.to_device(np.repeat(c_lo, 4, axis=0), np.uint32)                 # input g four times: with sub-table 0 .. 3
+        d_idx4 = gk.to_device(np.tile(np.arange(4, dtype=np.int32), G))
         d_sub = torch.zeros((G * 4, n1), dtype=torch.int32, device="cuda")
         d_rows = torch.zeros((G, 2, w.N), dtype=torch.int32, device="cuda")
-        d_hi, d_g = _cuda(c_hi, np.uint32), _cuda(np.arange(G, dtype=np.int32))
+        d_hi, d_g = gk.to_device(c_hi, np.uint32), gk.to_device(np.arange(G, dtype=np.int32))
         d_out = torch.zeros((G, n1), dtype=torch.int32, device="cuda")
         e.pbs_batch_dev(sub, d_lo4, d_sub, G * 4, d_idx4, st)
         e.pack_batch_dev(w.key, d_sub, 4, d_rows, G, rep, pos, st)
@@ -249,7 +238,7 @@ def test_capture_replay_and_two_streams(worlds):
     a, b = _shape_inputs(w, count, P, 501), _shape_inputs(w, count, P, 502)
     want_a, want_b = O.pack(w.rp, w.pk, a, P, pos, rep), O.pack(w.rp, w.pk, b, P, pos, rep)
     s, s2 = torch.cuda.Stream(), torch.cuda.Stream()
-    d_in, d_in2 = _cuda(a, np.uint32), _cuda(b, np.uint32)
+    d_in, d_in2 = gk.to_device(a, np.uint32), gk.to_device(b, np.uint32)
     out = torch.zeros((count, 2, N1), dtype=torch.int32, device="cuda")
     out2 = torch.zeros((count, 2, N1), dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
@@ -274,13 +263,13 @@ def test_capture_replay_and_two_streams(worlds):
         with torch.cuda.graph(g, stream=s):
             e.pack_batch_dev(w.key, d_in, P, out, count, rep, pos, s.cuda_stream)
         for src, exp in ((a, want_a), (b, want_b)):
-            d_in.copy_(_cuda(src, np.uint32))
+            d_in.copy_(gk.to_device(src, np.uint32))
             out.zero_()
             g.replay()
             torch.cuda.synchronize()
             assert np.array_equal(out.cpu().numpy().view(np.uint32), exp)
     # two streams side by side, each with its own buffer of key-switched samples
-    d_in.copy_(_cuda(a, np.uint32))
+    d_in.copy_(gk.to_device(a, np.uint32))
     torch.cuda.synchronize()
     for _ in range(3):
         e.pack_batch_dev(w.key, d_in, P, out, count, rep, pos, s.cuda_stream)
@@ -302,7 +291,7 @@ def test_larger_eager_pack_retires_the_buffer_a_graph_holds(worlds):
     a, b = _shape_inputs(w, 3, P, 501), _shape_inputs(w, 9, P, 503)
     want_a, want_b = O.pack(w.rp, w.pk, a, P, pos, rep), O.pack(w.rp, w.pk, b, P, pos, rep)
     s = torch.cuda.Stream()
-    d_a, d_b = _cuda(a, np.uint32), _cuda(b, np.uint32)
+    d_a, d_b = gk.to_device(a, np.uint32), gk.to_device(b, np.uint32)
     out = torch.zeros((3, 2, N1), dtype=torch.int32, device="cuda")
     big = torch.zeros((9, 2, N1), dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
@@ -360,7 +349,7 @@ def test_refusals_and_lifetimes(worlds):
                        ((tlwe, 3, None, N + 1), "rep"), ((tlwe, 3, i32(0, 2 * N, 1), 1), "pos = %d" % (2 * N)), ((tlwe, 3, i32(0, 1, -1), 1), "pos = -1"),
                        ((tlwe, 3, None, N), "pos NULL")):
         refused(lambda: e._ck(call(*args)), word=word)
-    d_in, d_out = _cuda(tlwe, np.uint32), torch.zeros((1, 2, N), dtype=torch.int32, device="cuda")
+    d_in, d_out = gk.to_device(tlwe, np.uint32), torch.zeros((1, 2, N), dtype=torch.int32, device="cuda")
     refused(lambda: e.pack_batch_dev(w.key, d_in, 0, d_out, 1), word="P = 0")
     refused(lambda: e.pack_batch_dev(w.key, d_in, 3, d_out, 1, 1, [0, -1, 5]), word="pos = -1")
     refused(lambda: e._ck(e.L.rtfhe_pack_batch_dev(e.h, w.key.h, tlwe.ctypes.data, 3, None, 1, d_out.data_ptr(), 1, None)), word="device pointers")

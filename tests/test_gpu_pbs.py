@@ -1,51 +1,28 @@
 """GPU: programmable bootstrapping (rtfhe_lut_create / rtfhe_pbs_batch[_dev], the k_pbs_* twins of every FP64-mirror kernel family).
 With the constant 1/8 table a PBS is the gate path's bootstrap, word for word, in every batch shape the dispatch takes; with random tables it is
-the oracle's PBS (tests/test_pbs_host.py: oracle_pbs) word for word; with encoded functions it decrypts to them."""
-import os
-
+the oracle's PBS (tests/pbs_oracle.py: oracle_pbs) word for word; with encoded functions it decrypts to them."""
 import numpy as np
 import pytest
 
-from test_pbs_host import bk_fft, oracle_pbs
+import gpu_kit as gk
+from kit import keys_2048, phase_err, random_words
+from pbs_oracle import oracle_pbs
 
 pytestmark = pytest.mark.gpu
 
 EIGHTH = 0x20000000
 
 
-def _engine(R, p, keys_bk, keys_ksk, monkeypatch=None, env=None, **kw):
-    if env:
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-    try:
-        e = R.Engine(p, 0, **kw) if "devices" not in kw else R.Engine(p, **kw)
-    finally:
-        if env:
-            for k in env:
-                monkeypatch.delenv(k)
-    e.load_bk_torus(keys_bk)
-    e.load_ksk(keys_ksk)
-    return e
-
-
-def _random_words(rng, shape):
-    return rng.integers(0, 1 << 32, shape, dtype=np.uint64).astype(np.uint32)
-
-
-CONFIGS_1024 = [None, {"RTFHE_FORCE_WAVES": "1"}, {"RTFHE_FORCE_WAVES": "2"}, {"RTFHE_FORCE_WAVES": "4"}, {"RTFHE_FORCE_WAVES": "8"},
-                {"RTFHE_PAIR_RR": "0"}, {"RTFHE_PAIR4": "0"}, {"RTFHE_KS_MM_MIN": "0"}]
-
-
-@pytest.mark.parametrize("env", CONFIGS_1024, ids=lambda e: "default" if not e else ",".join("%s=%s" % kv for kv in e.items()))
+@pytest.mark.parametrize("env", gk.CONFIGS_1024, ids=gk.env_id)
 def test_constant_table_equals_bootstrap_every_shape_n1024(params, keys, monkeypatch, env):
     import rustfhe_amd as R
     p = R.Params(n=params.n, N=params.N)
-    e = _engine(R, p, keys.bk_t, keys.ksk, monkeypatch, env)
+    e = gk.engine(R, p, keys.bk_t, keys.ksk, monkeypatch, env)
     rng = np.random.default_rng(1024)
     try:
         with e.lut(np.full((2, p.N), EIGHTH, np.uint32)) as lut:       # two identical rows: random indices exercise the index path too
             for count in (1, 37, 300, 600, 900, 1024, 1280, 2048):
-                ct = _random_words(rng, (count, p.n + 1))
+                ct = random_words(rng, (count, p.n + 1))
                 ref = e.bootstrap_batch(ct)
                 assert np.array_equal(e.pbs_batch(lut, ct), ref), count
                 assert np.array_equal(e.pbs_batch(lut, ct, rng.integers(0, 2, count)), ref), count
@@ -55,21 +32,19 @@ def test_constant_table_equals_bootstrap_every_shape_n1024(params, keys, monkeyp
 
 @pytest.fixture(scope="module")
 def keys2048(orc):
-    P = orc.Params(N=2048)
-    return P, orc.Keys(P, 2048)
+    return keys_2048(orc)
 
 
-@pytest.mark.parametrize("env", [None, {"RTFHE_FORCE_WAVES": "4"}, {"RTFHE_N2048_EO4": "0"}],
-                         ids=lambda e: "default" if not e else ",".join("%s=%s" % kv for kv in e.items()))
+@pytest.mark.parametrize("env", gk.CONFIGS_2048, ids=gk.env_id)
 def test_constant_table_equals_bootstrap_every_shape_n2048(keys2048, monkeypatch, env):
     import rustfhe_amd as R
     P, K = keys2048
-    e = _engine(R, R.Params(N=2048), K.bk_t, K.ksk, monkeypatch, env)
+    e = gk.engine(R, R.Params(N=2048), K.bk_t, K.ksk, monkeypatch, env)
     rng = np.random.default_rng(2048)
     try:
         with e.lut(np.full(P.N, EIGHTH, np.uint32)) as lut:
             for count in (1, 37, 300, 600, 1024, 1100):
-                ct = _random_words(rng, (count, P.n + 1))
+                ct = random_words(rng, (count, P.n + 1))
                 assert np.array_equal(e.pbs_batch(lut, ct), e.bootstrap_batch(ct)), count
     finally:
         e.close()
@@ -77,9 +52,9 @@ def test_constant_table_equals_bootstrap_every_shape_n2048(keys2048, monkeypatch
 
 def _check_random_tables(orc, P, plan, bk_f, ksk, e, count, seed):
     rng = np.random.default_rng(seed)
-    tv = _random_words(rng, (3, P.N))
+    tv = random_words(rng, (3, P.N))
     idx = rng.integers(0, 3, count).astype(np.int32)
-    ct = _random_words(rng, (count, P.n + 1))
+    ct = random_words(rng, (count, P.n + 1))
     with e.lut(tv) as lut:
         out = e.pbs_batch(lut, ct, idx)
     pick = sorted(set([0, count - 1]) | set(rng.choice(count, min(count, 16), replace=False).tolist()))
@@ -96,24 +71,18 @@ def test_random_tables_against_the_oracle_n1024(orc, params, keys, engine):
 def test_random_tables_against_the_oracle_n2048(orc, keys2048):
     import rustfhe_amd as R
     P, K = keys2048
-    e = _engine(R, R.Params(N=2048), K.bk_t, K.ksk)
+    e = gk.engine(R, R.Params(N=2048), K.bk_t, K.ksk)
     try:
         _check_random_tables(orc, P, orc.Plan(P.N), K.bk_f, K.ksk, e, 600, 13)
     finally:
         e.close()
 
 
-def _phase_err(R, p, key0, cts, want, bits):
-    """signed distance (torus fraction) of each phase from the encoding of `want`"""
-    d = (R.phases(p, key0, cts).astype(np.int64) - R.encode_msgs(want, bits).astype(np.int64)) & 0xFFFFFFFF
-    return np.where(d >= 1 << 31, d - (1 << 32), d) / 2.0 ** 32
-
-
 @pytest.mark.parametrize("fname", ["identity", "square", "succ", "msb"])
 def test_encoded_functions_decrypt_through_two_pbs_2bit(engine, keys, fname):
     """p = 2: 1,024 fresh ciphertexts (every message 256 times), one PBS, then a second PBS on its outputs: every word decrypts to f, then f(f)."""
     import rustfhe_amd as R
-    from test_pbs_host import FUNCS
+    from pbs_oracle import FUNCS
     P = 2
     f = lambda m: FUNCS[fname](m, P)  # noqa: E731
     p = engine.p
@@ -135,7 +104,7 @@ def test_encoded_functions_3bit(engine, keys, fname):
     gives (never a wrong box by more than one, the typical error far inside the box), a 1-bit output of a 3-bit input (m >= 4) decrypts
     always, and the outputs of a first PBS chained into a second land in the right box in the large majority."""
     import rustfhe_amd as R
-    from test_pbs_host import FUNCS
+    from pbs_oracle import FUNCS
     P = 3
     f = lambda m: FUNCS[fname](m, P)  # noqa: E731
     p = engine.p
@@ -145,7 +114,7 @@ def test_encoded_functions_3bit(engine, keys, fname):
     with engine.lut(R.lut_polynomial(f, p.N, P)) as lut:
         once = engine.pbs_batch(lut, ct)
         twice = engine.pbs_batch(lut, once)
-    e1 = _phase_err(R, p, keys.key0, once, fm, P)
+    e1 = phase_err(R, p, keys.key0, once, fm, P)
     assert np.abs(e1).max() < 1.5 / 16 and np.median(np.abs(e1)) < 1.0 / 64, (np.abs(e1).max(), np.median(np.abs(e1)))
     assert np.mean(R.decode_msgs(R.phases(p, keys.key0, once), P) == fm) >= 0.9
     assert np.mean(R.decode_msgs(R.phases(p, keys.key0, twice), P) == [f(m) for m in fm]) >= 0.85
@@ -160,8 +129,8 @@ def test_bad_indices_host_and_device(engine, keys):
     p = engine.p
     rng = np.random.default_rng(8)
     count = 300
-    tv = _random_words(rng, (2, p.N))
-    ct = _random_words(rng, (count, p.n + 1))
+    tv = random_words(rng, (2, p.N))
+    ct = random_words(rng, (count, p.n + 1))
     idx = rng.integers(0, 2, count).astype(np.int32)
     with engine.lut(tv) as lut:
         ref = engine.pbs_batch(lut, ct, idx)
@@ -198,12 +167,12 @@ def test_multi_entry_context_matches_single(params, keys, engine):
     p = engine.p
     rng = np.random.default_rng(9)
     G = 8192
-    tv = _random_words(rng, (4, p.N))
-    ct = _random_words(rng, (G, p.n + 1))
+    tv = random_words(rng, (4, p.N))
+    ct = random_words(rng, (G, p.n + 1))
     idx = rng.integers(0, 4, G).astype(np.int32)
     with engine.lut(tv) as lut:
         ref = engine.pbs_batch(lut, ct, idx)
-    multi = _engine(R, p, keys.bk_t, keys.ksk, devices=[0, 0])
+    multi = gk.engine(R, p, keys.bk_t, keys.ksk, devices=[0, 0])
     try:
         with multi.lut(tv) as lut:
             assert np.array_equal(multi.pbs_batch(lut, ct, idx), ref)
@@ -223,8 +192,8 @@ def test_graph_capture_replays_eager_words(engine):
     p = engine.p
     rng = np.random.default_rng(10)
     count = 600
-    tv = _random_words(rng, (3, p.N))
-    ct = torch.from_numpy(_random_words(rng, (count, p.n + 1)).view(np.int32)).cuda()
+    tv = random_words(rng, (3, p.N))
+    ct = torch.from_numpy(random_words(rng, (count, p.n + 1)).view(np.int32)).cuda()
     idx = torch.from_numpy(rng.integers(0, 3, count).astype(np.int32)).cuda()
     s = torch.cuda.Stream()
     out = torch.zeros_like(ct)
@@ -248,7 +217,7 @@ def test_exact_backends_refuse_and_mirror_recovers(engine):
     import rustfhe_amd as R
     p = engine.p
     rng = np.random.default_rng(12)
-    ct = _random_words(rng, (37, p.n + 1))
+    ct = random_words(rng, (37, p.n + 1))
     with engine.lut(np.full(p.N, EIGHTH, np.uint32)) as lut:
         ref = engine.pbs_batch(lut, ct)
         try:
@@ -265,7 +234,7 @@ def test_exact_backends_refuse_and_mirror_recovers(engine):
 
 def test_lut_outliving_its_context(params, keys):
     import rustfhe_amd as R
-    e = _engine(R, R.Params(), keys.bk_t, keys.ksk)
+    e = gk.engine(R, R.Params(), keys.bk_t, keys.ksk)
     lut = e.lut(np.full(e.p.N, EIGHTH, np.uint32))
     e.close()
     lut.close()                                               # only frees the handle

@@ -1,6 +1,6 @@
 """GPU: programmable bootstrapping from encrypted tables (rtfhe_lut_create_encrypted; the k_pbs_enc_* kernels of every FP64-mirror kernel
 family).  A trivial encryption (tv, 0) gives the plain table's words through every PBS entry in every batch shape; a real encryption gives the
-oracle's words (tests/test_pbs_enc_host.py: oracle_pbs_enc); encoded functions decrypt; index checks, sharding, graph capture, LUT circuits,
+oracle's words (tests/pbs_oracle.py: oracle_pbs_enc); encoded functions decrypt; index checks, sharding, graph capture, LUT circuits,
 backend refusal and lifetimes follow the plain table's rules."""
 import importlib.util
 import os
@@ -8,20 +8,20 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_pbs import CONFIGS_1024, _engine, _random_words
-from test_pbs_enc_host import oracle_pbs_enc
+import gpu_kit as gk
+from kit import keys_2048, random_words
+from lut_circuit_kit import adder_inputs, decode
+from pbs_oracle import oracle_pbs_enc
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENV_IDS = lambda e: "default" if not e else ",".join("%s=%s" % kv for kv in e.items())  # noqa: E731
 COUNTS = (1, 37, 1024, 1280)
 
 
 @pytest.fixture(scope="module")
 def keys2048(orc):
-    P = orc.Params(N=2048)
-    return P, orc.Keys(P, 2048)
+    return keys_2048(orc)
 
 
 def _trivial(tv):
@@ -33,22 +33,22 @@ def _trivial(tv):
 def _check_trivial(e, N, n1, counts, seed):
     """A trivially encrypted table against the plain one on the same engine: pbs_batch and pbs_many_batch with every n_out."""
     rng = np.random.default_rng(seed)
-    tv = _random_words(rng, (3, N))
+    tv = random_words(rng, (3, N))
     with e.lut(tv) as plain, e.lut_encrypted(_trivial(tv)) as enc:
         assert enc.encrypted and not plain.encrypted and enc.n_lut == 3
         for count in counts:
-            ct = _random_words(rng, (count, n1))
+            ct = random_words(rng, (count, n1))
             idx = rng.integers(0, 3, count).astype(np.int32)
             assert np.array_equal(e.pbs_batch(enc, ct, idx), e.pbs_batch(plain, ct, idx)), count
             for n_out in (1, 2, 4, 8):
                 assert np.array_equal(e.pbs_many_batch(enc, ct, n_out, idx), e.pbs_many_batch(plain, ct, n_out, idx)), (count, n_out)
 
 
-@pytest.mark.parametrize("env", CONFIGS_1024, ids=ENV_IDS)
+@pytest.mark.parametrize("env", gk.CONFIGS_1024, ids=gk.env_id)
 def test_trivial_encryption_is_the_plain_table_every_shape_n1024(params, keys, engine, monkeypatch, env):
     import rustfhe_amd as R
     p = R.Params(n=params.n, N=params.N)
-    e = _engine(R, p, keys.bk_t, keys.ksk, monkeypatch, env) if env else engine
+    e = gk.engine(R, p, keys.bk_t, keys.ksk, monkeypatch, env) if env else engine
     try:
         _check_trivial(e, p.N, p.n + 1, COUNTS, 4097)
     finally:
@@ -56,11 +56,11 @@ def test_trivial_encryption_is_the_plain_table_every_shape_n1024(params, keys, e
             e.close()
 
 
-@pytest.mark.parametrize("env", [None, {"RTFHE_FORCE_WAVES": "4"}, {"RTFHE_N2048_EO4": "0"}], ids=ENV_IDS)
+@pytest.mark.parametrize("env", gk.CONFIGS_2048, ids=gk.env_id)
 def test_trivial_encryption_is_the_plain_table_every_shape_n2048(keys2048, monkeypatch, env):
     import rustfhe_amd as R
     P, K = keys2048
-    e = _engine(R, R.Params(N=2048), K.bk_t, K.ksk, monkeypatch, env)
+    e = gk.engine(R, R.Params(N=2048), K.bk_t, K.ksk, monkeypatch, env)
     try:
         _check_trivial(e, P.N, P.n + 1, COUNTS, 8193)
     finally:
@@ -71,9 +71,9 @@ def _check_oracle(orc, P, plan, bk_f, ksk, key1, e, count, seed):
     import rustfhe_amd as R
     rng = np.random.default_rng(seed)
     rp = R.Params(n=P.n, N=P.N)
-    table = R.encrypt_lut(rp, key1, _random_words(rng, (3, P.N)), seed=seed)
+    table = R.encrypt_lut(rp, key1, random_words(rng, (3, P.N)), seed=seed)
     idx = rng.integers(0, 3, count).astype(np.int32)
-    ct = _random_words(rng, (count, P.n + 1))
+    ct = random_words(rng, (count, P.n + 1))
     with e.lut_encrypted(table) as lut:
         for n_out in (1, 2, 4, 8):
             out = e.pbs_many_batch(lut, ct, n_out, idx)
@@ -90,7 +90,7 @@ def test_real_encryption_against_the_oracle_n1024(orc, params, keys, engine):
 def test_real_encryption_against_the_oracle_n2048(orc, keys2048):
     import rustfhe_amd as R
     P, K = keys2048
-    e = _engine(R, R.Params(N=2048), K.bk_t, K.ksk)
+    e = gk.engine(R, R.Params(N=2048), K.bk_t, K.ksk)
     try:
         _check_oracle(orc, P, orc.Plan(P.N), K.bk_f, K.ksk, K.key1, e, 37, 52)
     finally:
@@ -130,9 +130,9 @@ def test_bad_indices_host_and_device(engine, keys):
     p = engine.p
     rng = np.random.default_rng(18)
     count = 300
-    ct = _random_words(rng, (count, p.n + 1))
+    ct = random_words(rng, (count, p.n + 1))
     idx = rng.integers(0, 2, count).astype(np.int32)
-    with engine.lut_encrypted(R.encrypt_lut(p, keys.key1, _random_words(rng, (2, p.N)), seed=18)) as lut:
+    with engine.lut_encrypted(R.encrypt_lut(p, keys.key1, random_words(rng, (2, p.N)), seed=18)) as lut:
         ref1 = engine.pbs_batch(lut, ct, idx)
         ref2 = engine.pbs_many_batch(lut, ct, 2, idx)
         bad = idx.copy()
@@ -173,13 +173,13 @@ def test_multi_entry_context_matches_single(params, keys, engine):
     p = engine.p
     rng = np.random.default_rng(19)
     G = 4099
-    table = R.encrypt_lut(p, keys.key1, _random_words(rng, (4, p.N)), seed=19)
-    ct = _random_words(rng, (G, p.n + 1))
+    table = R.encrypt_lut(p, keys.key1, random_words(rng, (4, p.N)), seed=19)
+    ct = random_words(rng, (G, p.n + 1))
     idx = rng.integers(0, 4, G).astype(np.int32)
     with engine.lut_encrypted(table) as lut:
         ref1 = engine.pbs_batch(lut, ct, idx)
         ref4 = engine.pbs_many_batch(lut, ct, 4, idx)
-    multi = _engine(R, p, keys.bk_t, keys.ksk, devices=[0, 0])
+    multi = gk.engine(R, p, keys.bk_t, keys.ksk, devices=[0, 0])
     try:
         with multi.lut_encrypted(table) as lut:
             assert np.array_equal(multi.pbs_batch(lut, ct, idx), ref1)
@@ -204,8 +204,8 @@ def test_graph_capture_replays_eager_words(engine, keys):
     p = engine.p
     rng = np.random.default_rng(20)
     count = 600
-    table = R.encrypt_lut(p, keys.key1, _random_words(rng, (3, p.N)), seed=20)
-    ct = torch.from_numpy(_random_words(rng, (count, p.n + 1)).view(np.int32)).cuda()
+    table = R.encrypt_lut(p, keys.key1, random_words(rng, (3, p.N)), seed=20)
+    ct = torch.from_numpy(random_words(rng, (count, p.n + 1)).view(np.int32)).cuda()
     idx = torch.from_numpy(rng.integers(0, 3, count).astype(np.int32)).cuda()
     s = torch.cuda.Stream()
     out = torch.zeros((count, 4, p.n + 1), dtype=torch.int32, device="cuda")
@@ -234,11 +234,10 @@ def test_lut_circuit_adder_with_encrypted_tables(engine, keys):
     """lut_ripple_adder at 1,024 replicas: with its tables encrypted every sum decrypts right; with them trivially encrypted the wire table
     equals the plain-table circuit's word for word."""
     import rustfhe_amd as R
-    from test_gpu_lut_circuit import _adder_inputs, _decode
     p = engine.p
     reps = 1024
     net = R.lut_ripple_adder(8)
-    a, b, cts = _adder_inputs(R, p, keys.key0, reps, 0xE1C)
+    a, b, cts = adder_inputs(R, p, keys.key0, reps, 0xE1C)
     plain = R.LutCircuitRunner(engine, net, reps)
     enc = R.LutCircuitRunner(engine, net, reps, key1=keys.key1, seed=0xE1D)
     triv = R.LutCircuitRunner(engine, net, reps)
@@ -251,9 +250,9 @@ def test_lut_circuit_adder_with_encrypted_tables(engine, keys):
                                                       d["wave_n_out"], d["out_idx"], triv.wires, d["num_wires"])
         for run in (plain, enc, triv):
             run.run()
-        assert np.array_equal(_decode(R, p, keys.key0, enc.outputs()), a + b)
+        assert np.array_equal(decode(R, p, keys.key0, enc.outputs()), a + b)
         assert np.array_equal(triv.wires.cpu().numpy(), plain.wires.cpu().numpy())
-        assert np.array_equal(_decode(R, p, keys.key0, plain.outputs()), a + b)
+        assert np.array_equal(decode(R, p, keys.key0, plain.outputs()), a + b)
     finally:
         for run in (plain, enc, triv):
             run.close()
@@ -263,8 +262,8 @@ def test_exact_backends_refuse_and_mirror_recovers(engine, keys):
     import rustfhe_amd as R
     p = engine.p
     rng = np.random.default_rng(22)
-    ct = _random_words(rng, (37, p.n + 1))
-    with engine.lut_encrypted(R.encrypt_lut(p, keys.key1, _random_words(rng, (1, p.N)), seed=22)) as lut:
+    ct = random_words(rng, (37, p.n + 1))
+    with engine.lut_encrypted(R.encrypt_lut(p, keys.key1, random_words(rng, (1, p.N)), seed=22)) as lut:
         ref = engine.pbs_many_batch(lut, ct, 2)
         try:
             for b in (R._ffi.BACKEND_NTT_EXACT, R._ffi.BACKEND_FFT_SPLIT_EXACT):
@@ -283,10 +282,10 @@ def test_lifetimes(params, keys):
     import rustfhe_amd as R
     p = R.Params(n=params.n, N=params.N)
     rng = np.random.default_rng(24)
-    table = R.encrypt_lut(p, keys.key1, _random_words(rng, (2, p.N)), seed=24)
-    ct = _random_words(rng, (37, p.n + 1))
-    e = _engine(R, p, keys.bk_t, keys.ksk)
-    other = _engine(R, p, keys.bk_t, keys.ksk)
+    table = R.encrypt_lut(p, keys.key1, random_words(rng, (2, p.N)), seed=24)
+    ct = random_words(rng, (37, p.n + 1))
+    e = gk.engine(R, p, keys.bk_t, keys.ksk)
+    other = gk.engine(R, p, keys.bk_t, keys.ksk)
     try:
         first = e.lut_encrypted(table)
         ref = e.pbs_many_batch(first, ct, 2)

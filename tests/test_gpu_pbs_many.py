@@ -1,34 +1,33 @@
 """GPU: many-LUT programmable bootstrapping (rtfhe_pbs_many_batch[_dev], the k_pbs_many_* kernels of every FP64-mirror kernel family).
 With one output it is rtfhe_pbs_batch word for word in every batch shape the dispatch takes; with 2, 4 or 8 outputs it is the oracle's many-LUT PBS
-(tests/test_pbs_many_host.py: oracle_pbs_many) word for word, every shape gives the default shape's words, and encoded functions decrypt."""
+(tests/pbs_oracle.py: oracle_pbs_many) word for word, every shape gives the default shape's words, and encoded functions decrypt."""
 import importlib.util
 import os
 
 import numpy as np
 import pytest
 
-from test_gpu_pbs import CONFIGS_1024, _engine, _random_words
-from test_pbs_many_host import oracle_pbs_many
+import gpu_kit as gk
+from kit import keys_2048, random_words
+from pbs_oracle import oracle_pbs_many
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENV_IDS = lambda e: "default" if not e else ",".join("%s=%s" % kv for kv in e.items())  # noqa: E731
 
 
 @pytest.fixture(scope="module")
 def keys2048(orc):
-    P = orc.Params(N=2048)
-    return P, orc.Keys(P, 2048)
+    return keys_2048(orc)
 
 
 def _check_shape(e, ref_e, N, n1, counts, seed):
     """theta = 1 against pbs_batch on the same engine; theta = 4 against the reference (default-shape) engine."""
     rng = np.random.default_rng(seed)
-    tv = _random_words(rng, (3, N))
+    tv = random_words(rng, (3, N))
     with e.lut(tv) as lut, ref_e.lut(tv) as ref_lut:
         for count in counts:
-            ct = _random_words(rng, (count, n1))
+            ct = random_words(rng, (count, n1))
             idx = rng.integers(0, 3, count).astype(np.int32)
             one = e.pbs_many_batch(lut, ct, 1, idx)
             assert one.shape == (count, 1, n1)
@@ -37,11 +36,11 @@ def _check_shape(e, ref_e, N, n1, counts, seed):
                 assert np.array_equal(e.pbs_many_batch(lut, ct, 4, idx), ref_e.pbs_many_batch(ref_lut, ct, 4, idx)), count
 
 
-@pytest.mark.parametrize("env", CONFIGS_1024, ids=ENV_IDS)
+@pytest.mark.parametrize("env", gk.CONFIGS_1024, ids=gk.env_id)
 def test_one_output_is_pbs_every_shape_n1024(params, keys, engine, monkeypatch, env):
     import rustfhe_amd as R
     p = R.Params(n=params.n, N=params.N)
-    e = _engine(R, p, keys.bk_t, keys.ksk, monkeypatch, env) if env else engine
+    e = gk.engine(R, p, keys.bk_t, keys.ksk, monkeypatch, env) if env else engine
     try:
         _check_shape(e, engine, p.N, p.n + 1, (1, 37, 300, 600, 900, 1024, 1280, 2048), 4096)
     finally:
@@ -49,12 +48,12 @@ def test_one_output_is_pbs_every_shape_n1024(params, keys, engine, monkeypatch, 
             e.close()
 
 
-@pytest.mark.parametrize("env", [None, {"RTFHE_FORCE_WAVES": "4"}, {"RTFHE_N2048_EO4": "0"}], ids=ENV_IDS)
+@pytest.mark.parametrize("env", gk.CONFIGS_2048, ids=gk.env_id)
 def test_one_output_is_pbs_every_shape_n2048(keys2048, monkeypatch, env):
     import rustfhe_amd as R
     P, K = keys2048
-    ref = _engine(R, R.Params(N=2048), K.bk_t, K.ksk)
-    e = _engine(R, R.Params(N=2048), K.bk_t, K.ksk, monkeypatch, env) if env else ref
+    ref = gk.engine(R, R.Params(N=2048), K.bk_t, K.ksk)
+    e = gk.engine(R, R.Params(N=2048), K.bk_t, K.ksk, monkeypatch, env) if env else ref
     try:
         _check_shape(e, ref, P.N, P.n + 1, (1, 37, 300, 600, 1024, 1100), 8192)
     finally:
@@ -65,9 +64,9 @@ def test_one_output_is_pbs_every_shape_n2048(keys2048, monkeypatch, env):
 
 def _check_oracle(orc, P, plan, bk_f, ksk, e, count, n_out, seed):
     rng = np.random.default_rng(seed)
-    tv = _random_words(rng, (3, P.N))
+    tv = random_words(rng, (3, P.N))
     idx = rng.integers(0, 3, count).astype(np.int32)
-    ct = _random_words(rng, (count, P.n + 1))
+    ct = random_words(rng, (count, P.n + 1))
     with e.lut(tv) as lut:
         out = e.pbs_many_batch(lut, ct, n_out, idx)
     assert out.shape == (count, n_out, P.n + 1)
@@ -87,7 +86,7 @@ def test_random_tables_against_the_oracle_n1024(orc, params, keys, engine, n_out
 def test_random_tables_against_the_oracle_n2048(orc, keys2048, n_out):
     import rustfhe_amd as R
     P, K = keys2048
-    e = _engine(R, R.Params(N=2048), K.bk_t, K.ksk)
+    e = gk.engine(R, R.Params(N=2048), K.bk_t, K.ksk)
     try:
         _check_oracle(orc, P, orc.Plan(P.N), K.bk_f, K.ksk, e, 1024, n_out, 77 + n_out)
     finally:
@@ -158,8 +157,8 @@ def test_bad_indices_host_and_device(engine):
     p = engine.p
     rng = np.random.default_rng(18)
     count = 300
-    tv = _random_words(rng, (2, p.N))
-    ct = _random_words(rng, (count, p.n + 1))
+    tv = random_words(rng, (2, p.N))
+    ct = random_words(rng, (count, p.n + 1))
     idx = rng.integers(0, 2, count).astype(np.int32)
     with engine.lut(tv) as lut:
         ref = engine.pbs_many_batch(lut, ct, 2, idx)
@@ -196,12 +195,12 @@ def test_multi_entry_context_matches_single(params, keys, engine):
     p = engine.p
     rng = np.random.default_rng(19)
     G = 4099
-    tv = _random_words(rng, (4, p.N))
-    ct = _random_words(rng, (G, p.n + 1))
+    tv = random_words(rng, (4, p.N))
+    ct = random_words(rng, (G, p.n + 1))
     idx = rng.integers(0, 4, G).astype(np.int32)
     with engine.lut(tv) as lut:
         ref = engine.pbs_many_batch(lut, ct, 4, idx)
-    multi = _engine(R, p, keys.bk_t, keys.ksk, devices=[0, 0])
+    multi = gk.engine(R, p, keys.bk_t, keys.ksk, devices=[0, 0])
     try:
         with multi.lut(tv) as lut:
             assert np.array_equal(multi.pbs_many_batch(lut, ct, 4, idx), ref)
@@ -221,8 +220,8 @@ def test_graph_capture_replays_eager_words(engine):
     p = engine.p
     rng = np.random.default_rng(20)
     count = 600
-    tv = _random_words(rng, (3, p.N))
-    ct = torch.from_numpy(_random_words(rng, (count, p.n + 1)).view(np.int32)).cuda()
+    tv = random_words(rng, (3, p.N))
+    ct = torch.from_numpy(random_words(rng, (count, p.n + 1)).view(np.int32)).cuda()
     idx = torch.from_numpy(rng.integers(0, 3, count).astype(np.int32)).cuda()
     s = torch.cuda.Stream()
     out = torch.zeros((count, 4, p.n + 1), dtype=torch.int32, device="cuda")
@@ -235,7 +234,7 @@ def test_graph_capture_replays_eager_words(engine):
         with torch.cuda.graph(g, stream=s):
             engine.pbs_many_batch_dev(lut, ct, out, count, 4, idx, s.cuda_stream)
         # a larger eager batch on the stream afterwards grows its sample buffer: the graph's one must stay alive
-        big = torch.from_numpy(_random_words(rng, (2 * count, p.n + 1)).view(np.int32)).cuda()
+        big = torch.from_numpy(random_words(rng, (2 * count, p.n + 1)).view(np.int32)).cuda()
         big_out = torch.zeros((2 * count, 8, p.n + 1), dtype=torch.int32, device="cuda")
         engine.pbs_many_batch_dev(lut, big, big_out, 2 * count, 8, None, s.cuda_stream)
         engine.sync(s.cuda_stream)
@@ -251,8 +250,8 @@ def test_exact_backends_refuse_and_mirror_recovers(engine):
     import rustfhe_amd as R
     p = engine.p
     rng = np.random.default_rng(22)
-    ct = _random_words(rng, (37, p.n + 1))
-    with engine.lut(_random_words(rng, (1, p.N))) as lut:
+    ct = random_words(rng, (37, p.n + 1))
+    with engine.lut(random_words(rng, (1, p.N))) as lut:
         ref = engine.pbs_many_batch(lut, ct, 2)
         try:
             for b in (R._ffi.BACKEND_NTT_EXACT, R._ffi.BACKEND_FFT_SPLIT_EXACT):

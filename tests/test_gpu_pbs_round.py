@@ -5,16 +5,13 @@ and with the suite's real key set (n = 635, N = 1024) 4-bit messages go through 
 import numpy as np
 import pytest
 
+import gpu_kit as gk
 import round_oracle as ro
-import test_gpu_pbs as _tgp
-from test_gpu_lut_circuit import create, host_compose, replay
-from test_gpu_pbs import CONFIGS_1024, _engine, _random_words
+from kit import phase_err, random_words
+from lut_circuit_kit import create, host_compose, replay
 
 pytestmark = pytest.mark.gpu
 
-ENV_IDS = lambda e: "default" if not e else ",".join("%s=%s" % kv for kv in e.items())  # noqa: E731
-# the N = 2048 shapes of tests/test_gpu_pbs.py
-CONFIGS_2048 = [m for m in _tgp.test_constant_table_equals_bootstrap_every_shape_n2048.pytestmark if m.name == "parametrize"][0].args[1]
 # further counts per N = 1024 shape, the smallest existing tests use: the default dispatch takes k_*_pair4 at 600, k_*_pair at 1,024 and
 # k_*_pair_rr at 1,280 (k_*_wg serves 1, 5 and 37); without pair4 / pair_rr those counts go to k_*_pair with 3 and 4 gates per workgroup
 EXTRA_1024 = {"default": (600, 1024, 1280), "RTFHE_PAIR4=0": (600,), "RTFHE_PAIR_RR=0": (1280,)}
@@ -33,7 +30,7 @@ class World:
 
     def engine(self, monkeypatch=None, env=None, **kw):
         import rustfhe_amd as R
-        return _engine(R, R.Params(n=24, N=self.P.N), self.K.bk_t, self.K.ksk, monkeypatch, env, **kw)
+        return gk.engine(R, R.Params(n=24, N=self.P.N), self.K.bk_t, self.K.ksk, monkeypatch, env, **kw)
 
     def want(self, row, t, n_out, mode=ro.ROUNDED):
         return ro.pbs_many(self.P, self.plan, self.K.bk_f, self.K.ksk, row, t, n_out, mode)
@@ -41,13 +38,7 @@ class World:
 
 @pytest.fixture(scope="module")
 def worlds(orc):
-    made = {}
-
-    def get(N):
-        if N not in made:
-            made[N] = World(orc, N)
-        return made[N]
-    return get
+    return gk.Worlds(lambda N: World(orc, N))
 
 
 @pytest.fixture(scope="module")
@@ -59,11 +50,6 @@ def small(worlds):
     e.close()
 
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).cuda()
-
-
 def _many_dev(e, lut, ct, n_out, idx, pbs=False):
     """the _dev form of pbs_many_batch (pbs: of pbs_batch) on the current stream"""
     import torch
@@ -71,9 +57,9 @@ def _many_dev(e, lut, ct, n_out, idx, pbs=False):
     out = torch.zeros((G, n_out, n1), dtype=torch.int32, device="cuda")
     st = torch.cuda.current_stream().cuda_stream
     if pbs:
-        e.pbs_batch_dev(lut, _dev(ct), out, G, _dev(idx), st)
+        e.pbs_batch_dev(lut, gk.to_device(ct, np.uint32), out, G, gk.to_device(idx), st)
     else:
-        e.pbs_many_batch_dev(lut, _dev(ct), out, G, n_out, _dev(idx), st)
+        e.pbs_many_batch_dev(lut, gk.to_device(ct, np.uint32), out, G, n_out, gk.to_device(idx), st)
     e.sync(st)
     return out.cpu().numpy().view(np.uint32)
 
@@ -84,13 +70,13 @@ def _check_words(w, e, counts, seed):
     import rustfhe_amd as R
     N, n1 = w.P.N, w.P.n + 1
     rng = np.random.default_rng(seed)
-    tv = _random_words(rng, (3, N))
-    trl = _random_words(rng, (3, 2, N))      # any words: an encrypted table is data to the kernel
+    tv = random_words(rng, (3, N))
+    trl = random_words(rng, (3, 2, N))      # any words: an encrypted table is data to the kernel
     e.set_decomposition(R._ffi.DECOMP_ROUNDED)
     assert e.decomposition() == R._ffi.DECOMP_ROUNDED
     with e.lut(tv) as plain, e.lut_encrypted(trl) as enc:
         for count in counts:
-            ct = _random_words(rng, (count, n1))
+            ct = random_words(rng, (count, n1))
             idx = rng.integers(0, 3, count).astype(np.int32)
             pick = sorted({0, count - 1, int(rng.integers(0, count))})
             for lut, rows in ((plain, tv), (enc, trl)):
@@ -106,22 +92,22 @@ def _check_words(w, e, counts, seed):
                         assert np.array_equal(_many_dev(e, lut, ct, 1, idx, pbs=True), out), (label, "pbs_batch_dev")
 
 
-@pytest.mark.parametrize("env", CONFIGS_1024, ids=ENV_IDS)
+@pytest.mark.parametrize("env", gk.CONFIGS_1024, ids=gk.env_id)
 def test_rounded_words_every_shape_n1024(worlds, monkeypatch, env):
     w = worlds(1024)
     e = w.engine(monkeypatch, env)
     try:
-        _check_words(w, e, (1, 5, 37) + EXTRA_1024.get(ENV_IDS(env), ()), 1024 + len(ENV_IDS(env)))
+        _check_words(w, e, (1, 5, 37) + EXTRA_1024.get(gk.env_id(env), ()), 1024 + len(gk.env_id(env)))
     finally:
         e.close()
 
 
-@pytest.mark.parametrize("env", CONFIGS_2048, ids=ENV_IDS)
+@pytest.mark.parametrize("env", gk.CONFIGS_2048, ids=gk.env_id)
 def test_rounded_words_every_shape_n2048(worlds, monkeypatch, env):
     w = worlds(2048)
     e = w.engine(monkeypatch, env)
     try:
-        _check_words(w, e, (1, 5, 37) + EXTRA_2048.get(ENV_IDS(env), ()), 2048 + len(ENV_IDS(env)))
+        _check_words(w, e, (1, 5, 37) + EXTRA_2048.get(gk.env_id(env), ()), 2048 + len(gk.env_id(env)))
     finally:
         e.close()
 
@@ -131,8 +117,8 @@ def test_switching_back_gives_the_reference_words_again(small):
     w, e = small
     rng = np.random.default_rng(31)
     count = 37
-    tv, trl = _random_words(rng, (2, w.P.N)), _random_words(rng, (2, 2, w.P.N))
-    ct = _random_words(rng, (count, w.P.n + 1))
+    tv, trl = random_words(rng, (2, w.P.N)), random_words(rng, (2, 2, w.P.N))
+    ct = random_words(rng, (count, w.P.n + 1))
     idx = rng.integers(0, 2, count).astype(np.int32)
 
     def run(plain, enc):
@@ -157,7 +143,7 @@ def test_gates_bootstrap_and_blind_rotation_ignore_the_mode(small):
     import rustfhe_amd as R
     w, e = small
     rng = np.random.default_rng(32)
-    a, b, c = (_random_words(rng, (37, w.P.n + 1)) for _ in range(3))
+    a, b, c = (random_words(rng, (37, w.P.n + 1)) for _ in range(3))
 
     def run():
         return [e.gate_batch(R.NAND, a, b), e.gate_batch(R.XOR, a, b), e.mux_batch(c, a, b), e.bootstrap_batch(a), e.blind_rotate_batch(a)]
@@ -182,24 +168,24 @@ def test_a_lut_circuit_keeps_the_mode_it_was_recorded_in(small):
     rng = np.random.default_rng(33)
     nodes, n1 = 40, w.P.n + 1
     d = {"fan_in": 2, "in_idx": np.stack([np.arange(nodes), (np.arange(nodes) + 1) % nodes], axis=1).astype(np.int32),
-         "weights": np.ones((nodes, 2), np.int32), "cst": _random_words(rng, nodes), "lut_idx": rng.integers(0, 2, nodes).astype(np.int32),
+         "weights": np.ones((nodes, 2), np.int32), "cst": random_words(rng, nodes), "lut_idx": rng.integers(0, 2, nodes).astype(np.int32),
          "wave_offsets": np.array([0, nodes], np.int32), "wave_n_out": np.array([2], np.int32),
          "out_idx": (nodes + np.arange(2 * nodes)).astype(np.int32), "num_wires": 3 * nodes}
-    start = _random_words(rng, (3 * nodes, n1))
+    start = random_words(rng, (3 * nodes, n1))
     R_, F_ = R._ffi.DECOMP_ROUNDED, R._ffi.DECOMP_REFERENCE
     want, circ, wires = {}, {}, {}
-    with e.lut(_random_words(rng, (2, w.P.N))) as lut:
+    with e.lut(random_words(rng, (2, w.P.N))) as lut:
         try:
             for mode in (R_, F_):
                 e.set_decomposition(mode)
                 want[mode] = host_compose(e, lut, d, start)
-                wires[mode] = _dev(start)
+                wires[mode] = gk.to_device(start, np.uint32)
                 circ[mode] = create(e, lut, d, wires[mode])
             assert not np.array_equal(want[R_], want[F_])
             for now in (F_, R_):          # replay both under each setting of the context
                 e.set_decomposition(now)
                 for mode in (R_, F_):
-                    wires[mode].copy_(_dev(start))
+                    wires[mode].copy_(gk.to_device(start, np.uint32))
                     torch.cuda.synchronize()
                     assert np.array_equal(replay(e, circ[mode], wires[mode]), want[mode]), (now, mode)
         finally:
@@ -221,11 +207,6 @@ def test_a_lut_circuit_keeps_the_mode_it_was_recorded_in(small):
 
 # ---- meaning, with the suite's real key set (n = 635, N = 1024).  Every input below is seeded; the same seeds were run through round_oracle
 # on the CPU before this file was committed: no wrong output in any of the three tests' rounded legs. -----------------------------------------
-def _phase_err(R, p, key0, cts, want, bits):
-    d = (R.phases(p, key0, cts).astype(np.int64) - R.encode_msgs(want, bits).astype(np.int64)) & 0xFFFFFFFF
-    return np.where(d >= 1 << 31, d - (1 << 32), d) / 2.0 ** 32
-
-
 def inputs_4bit(R, p, key0):
     """1,024 fresh 4-bit ciphertexts, every message 64 times, and a random permutation of the 16 messages as the table"""
     perm = np.random.default_rng(0x4B17).permutation(16)
@@ -252,7 +233,7 @@ def test_4bit_messages_through_one_pbs_and_the_noise_against_reference_mode(engi
         finally:
             engine.set_decomposition(R._ffi.DECOMP_REFERENCE)
         ref = engine.pbs_batch(lut, ct)
-    er, ef = _phase_err(R, p, keys.key0, out, perm[msgs], 4), _phase_err(R, p, keys.key0, ref, perm[msgs], 4)
+    er, ef = phase_err(R, p, keys.key0, out, perm[msgs], 4), phase_err(R, p, keys.key0, ref, perm[msgs], 4)
     rms_r, rms_f = float(np.sqrt(np.mean(er ** 2))), float(np.sqrt(np.mean(ef ** 2)))
     print("rounded: rms %.5f max %.5f; reference: rms %.5f max %.5f, %d wrong" %
           (rms_r, np.abs(er).max(), rms_f, np.abs(ef).max(), int(np.sum(R.decode_msgs(R.phases(p, keys.key0, ref), 4) != perm[msgs]))))
@@ -302,10 +283,10 @@ def test_capture_and_replay_in_rounded_mode(small):
     w, e = small
     rng = np.random.default_rng(34)
     count, n1 = 300, w.P.n + 1
-    tv = _random_words(rng, (3, w.P.N))
-    ct_h = _random_words(rng, (count, n1))
+    tv = random_words(rng, (3, w.P.N))
+    ct_h = random_words(rng, (count, n1))
     idx_h = rng.integers(0, 3, count).astype(np.int32)
-    ct, idx = _dev(ct_h), _dev(idx_h)
+    ct, idx = gk.to_device(ct_h, np.uint32), gk.to_device(idx_h)
     out = torch.zeros((count, 4, n1), dtype=torch.int32, device="cuda")
     s = torch.cuda.Stream()
     torch.cuda.synchronize()
@@ -356,8 +337,8 @@ def test_bad_table_indices_skip_their_gates_only(small):
     w, e = small
     rng = np.random.default_rng(35)
     G, n1, guard = 300, w.P.n + 1, 8
-    tv, trl = _random_words(rng, (3, w.P.N)), _random_words(rng, (3, 2, w.P.N))
-    ct = _random_words(rng, (G, n1))
+    tv, trl = random_words(rng, (3, w.P.N)), random_words(rng, (3, 2, w.P.N))
+    ct = random_words(rng, (G, n1))
     idx = rng.integers(0, 3, G).astype(np.int32)
     bad = np.array([0, 5, 63, 64, G - 1])
     bad_idx = idx.astype(np.int64)
@@ -368,13 +349,13 @@ def test_bad_table_indices_skip_their_gates_only(small):
     st = torch.cuda.current_stream().cuda_stream
 
     def run(lut, n_out, pbs, indices):
-        fill = _random_words(rng, (G * n_out + 2 * guard, n1))
-        big = _dev(fill)
+        fill = random_words(rng, (G * n_out + 2 * guard, n1))
+        big = gk.to_device(fill, np.uint32)
         rows = big[guard:guard + G * n_out]
         if pbs:
-            e.pbs_batch_dev(lut, _dev(ct), rows, G, _dev(indices), st)
+            e.pbs_batch_dev(lut, gk.to_device(ct, np.uint32), rows, G, gk.to_device(indices), st)
         else:
-            e.pbs_many_batch_dev(lut, _dev(ct), rows, G, n_out, _dev(indices), st)
+            e.pbs_many_batch_dev(lut, gk.to_device(ct, np.uint32), rows, G, n_out, gk.to_device(indices), st)
         return big, fill
     try:
         e.set_decomposition(R._ffi.DECOMP_ROUNDED)
@@ -400,8 +381,8 @@ def test_exact_backends_still_refuse_pbs_and_accept_the_setter(small):
     import rustfhe_amd as R
     w, e = small
     rng = np.random.default_rng(36)
-    ct = _random_words(rng, (5, w.P.n + 1))
-    tv = _random_words(rng, (1, w.P.N))
+    ct = random_words(rng, (5, w.P.n + 1))
+    tv = random_words(rng, (1, w.P.N))
     with e.lut(tv) as lut:
         try:
             for b in (R._ffi.BACKEND_NTT_EXACT, R._ffi.BACKEND_FFT_SPLIT_EXACT):
@@ -440,8 +421,8 @@ def test_multi_entry_context_sets_every_entry(small):
     w, e = small
     rng = np.random.default_rng(37)
     count = 301
-    tv = _random_words(rng, (2, w.P.N))
-    ct = _random_words(rng, (count, w.P.n + 1))
+    tv = random_words(rng, (2, w.P.N))
+    ct = random_words(rng, (count, w.P.n + 1))
     idx = rng.integers(0, 2, count).astype(np.int32)
     multi = w.engine(devices=[0, 0])
     try:

@@ -6,17 +6,14 @@ a test decrypts: n = 40 at N = 1024, n = 24 at N = 2048 as the extract tests use
 import numpy as np
 import pytest
 
+import gpu_kit as gk
 import plain_mul_oracle as O
-from test_gpu_pbs import _engine
+from gpu_kit import CANARY, FILL
+from kit import SMALL_N, i32
 
 pytestmark = pytest.mark.gpu
 
-FILL = 0x5A5A5A5A
-CANARY = 64             # words behind every device output that must keep their bytes
-SMALL_N = {1024: 40, 2048: 24}
 LIMIT = O.L1_PER_N      # K * wmax <= 192 N
-
-_WORLDS = {}
 
 
 class World:
@@ -35,11 +32,7 @@ class World:
         self.memo = {}
 
     def oracle(self, K, w_idx, x_idx, acc, count):
-        key = (K, None if w_idx is None else w_idx.tobytes(), None if x_idx is None else x_idx.tobytes(), None if acc is None else acc.tobytes(), count)
-        if key not in self.memo:
-            self.memo[key] = O.mul_plain(self.w, self.x, K, w_idx, x_idx, acc, count)
-            self.memo[key].setflags(write=False)
-        return self.memo[key]
+        return gk.memo(self.memo, (K, w_idx, x_idx, acc, count), lambda: O.mul_plain(self.w, self.x, K, w_idx, x_idx, acc, count))
 
     def close(self):
         self.pp.close()
@@ -49,53 +42,20 @@ class World:
 @pytest.fixture(scope="module")
 def worlds():
     import rustfhe_amd as R
-
-    def get(N):
-        if N not in _WORLDS:
-            _WORLDS[N] = World(R, N)
-        return _WORLDS[N]
-    yield get
-    for w in _WORLDS.values():
-        w.close()
-    _WORLDS.clear()
+    made = gk.Worlds(lambda N: World(R, N))
+    yield made
+    made.close()
 
 
-def _cuda(a, dtype=np.uint32):
-    import torch
-    return torch.from_numpy(np.array(a, dtype=dtype).view(np.int32)).cuda()      # (a copy: the shared inputs are read-only)
-
-
-def _dev(eng, pp, x, count, K=1, w_idx=None, x_idx=None, acc=None, stream=None, sync=True):
+def _dev(eng, pp, x, count, K=1, w_idx=None, x_idx=None, acc=None, stream=None):
     """the _dev form into a 0x5A-filled buffer (or a copy of acc) with CANARY words behind it, which are checked here; u32[count][2][N]"""
     import torch
     N = x.shape[2]
     st = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    d_x = _cuda(x)
-    d_out = torch.full((count * 2 * N + CANARY,), FILL, dtype=torch.int32, device="cuda")
-    if acc is not None:
-        d_out[:count * 2 * N].copy_(_cuda(acc).reshape(-1))
-    d_wi = None if w_idx is None else _cuda(w_idx, np.int32)
-    d_xi = None if x_idx is None else _cuda(x_idx, np.int32)
-    eng.trlwe_mul_plain_batch_dev(pp, d_x, x.shape[0], d_out, count, K, d_wi, d_xi, acc is not None, st)
-    if sync:
-        eng.sync(st)
-    else:
-        torch.cuda.synchronize()
-    out = d_out.cpu().numpy().view(np.uint32)
-    assert (out[count * 2 * N:] == FILL).all(), "words behind d_out were written"
-    return out[:count * 2 * N].reshape(count, 2, N)
-
-
-def _acc(kind, count, N):
-    if kind is None:
-        return None
-    if kind == "fill":
-        return np.full((count, 2, N), FILL, np.uint32)
-    return np.random.default_rng(count * N).integers(0, 1 << 32, (count, 2, N), dtype=np.uint64).astype(np.uint32)
-
-
-def _i32(a):
-    return np.array(a, np.int32)
+    d_out = gk.guarded_out(count * 2 * N, init=acc)
+    eng.trlwe_mul_plain_batch_dev(pp, gk.to_device(x, np.uint32), x.shape[0], d_out, count, K, gk.to_device(w_idx), gk.to_device(x_idx), acc is not None, st)
+    eng.sync(st)
+    return gk.read_guarded(d_out, count * 2 * N).reshape(count, 2, N)
 
 
 # (count, K, w_idx, x_idx, accumulate): ragged workgroups (count 1, 2, 3, 5), K 1, 2, 3, 8, NULL and given indices with duplicates, one x row
@@ -118,8 +78,8 @@ def test_every_word_equals_the_oracle(worlds, N, shape):
     """host and _dev forms"""
     w = worlds(N)
     count, K, w_idx, x_idx, kind = SHAPES[shape]
-    w_idx, x_idx = (None if w_idx is None else _i32(w_idx)), (None if x_idx is None else _i32(x_idx))
-    acc = _acc(kind, count, N)
+    w_idx, x_idx = (None if w_idx is None else i32(w_idx)), (None if x_idx is None else i32(x_idx))
+    acc = gk.acc_rows(kind, count, N)
     want = w.oracle(K, w_idx, x_idx, acc, count)
     got = w.eng.trlwe_mul_plain_batch(w.pp, w.x, K, w_idx, x_idx, acc) if (w_idx is not None or x_idx is not None or acc is not None) else \
         w.eng.trlwe_mul_plain_batch(w.pp, w.x[:count * K], K)
@@ -146,10 +106,10 @@ def test_the_largest_sums_of_the_domain(worlds, N, K):
     with w.eng.plain_polys(ew) as pp:
         assert pp.wmax * K == LIMIT * N and pp.n == 4
         got = w.eng.trlwe_mul_plain_batch(pp, rows, K, w_idx, x_idx)
-        dev = _dev(w.eng, pp, rows, count, K, w_idx, x_idx, _acc("random", count, N))
+        dev = _dev(w.eng, pp, rows, count, K, w_idx, x_idx, gk.acc_rows("random", count, N))
     bad = np.argwhere(got != want)
     assert bad.size == 0, (len(bad), bad[:5])
-    assert np.array_equal(dev, want + _acc("random", count, N))
+    assert np.array_equal(dev, want + gk.acc_rows("random", count, N))
 
 
 @pytest.mark.parametrize("N", [1024, 2048])
@@ -160,7 +120,7 @@ def test_identities(worlds, N):
     one[0, 0], one[1, 0], one[2, 1], one[3, N // 2], one[4, N - 1] = 1, -1, 1, 1, 1
     with e.plain_polys(one) as pp:
         rows = x[:5]
-        got = e.trlwe_mul_plain_batch(pp, rows, 1, _i32([[0], [1], [2], [3], [4]]), None)
+        got = e.trlwe_mul_plain_batch(pp, rows, 1, i32([[0], [1], [2], [3], [4]]), None)
     assert np.array_equal(got[0], rows[0]), "w = 1 gives x"
     assert np.array_equal(got[1], (0 - rows[1].astype(np.int64)).astype(np.uint32)), "w = -1 gives -x"
     for g, r in ((2, 1), (3, N // 2), (4, N - 1)):      # w = X^r: the negacyclic rotation
@@ -169,19 +129,19 @@ def test_identities(worlds, N):
     # mul(w1 + w2) = mul(w1) + mul(w2)
     both = np.stack([w.w[0], w.w[1], w.w[0] + w.w[1]])
     with e.plain_polys(both) as pp:
-        got = e.trlwe_mul_plain_batch(pp, x[:1], 1, _i32([[0], [1], [2]]), _i32([[0], [0], [0]]))
+        got = e.trlwe_mul_plain_batch(pp, x[:1], 1, i32([[0], [1], [2]]), i32([[0], [0], [0]]))
     assert np.array_equal(got[2], got[0] + got[1])
     # K = 2 equals two K = 1 calls with accumulate
-    first = e.trlwe_mul_plain_batch(w.pp, x, 1, _i32([[3], [5]]), _i32([[2], [9]]))
-    second = e.trlwe_mul_plain_batch(w.pp, x, 1, _i32([[4], [5]]), _i32([[7], [9]]), acc=first)
-    assert np.array_equal(second, e.trlwe_mul_plain_batch(w.pp, x, 2, _i32([[3, 4], [5, 5]]), _i32([[2, 7], [9, 9]])))
+    first = e.trlwe_mul_plain_batch(w.pp, x, 1, i32([[3], [5]]), i32([[2], [9]]))
+    second = e.trlwe_mul_plain_batch(w.pp, x, 1, i32([[4], [5]]), i32([[7], [9]]), acc=first)
+    assert np.array_equal(second, e.trlwe_mul_plain_batch(w.pp, x, 2, i32([[3, 4], [5, 5]]), i32([[2, 7], [9, 9]])))
 
 
 @pytest.mark.parametrize("N", [1024, 2048])
 def test_every_backend_and_a_two_entry_context_give_the_same_words(worlds, N):
     w, R = worlds(N), worlds(N).R
     count, K, w_idx, x_idx, kind = SHAPES[3]
-    w_idx, x_idx = _i32(w_idx), _i32(x_idx)
+    w_idx, x_idx = i32(w_idx), i32(x_idx)
     want = w.oracle(K, w_idx, x_idx, None, count)
     for backend in (R._ffi.BACKEND_FFT64_MIRROR, R._ffi.BACKEND_NTT_EXACT, R._ffi.BACKEND_FFT_SPLIT_EXACT):
         e = R.Engine(w.rp, 0)            # nothing loaded
@@ -208,7 +168,7 @@ def test_a_plain_set_shares_the_split_fft_backends_table(worlds, N):
     the set built and must compute with it; gates decrypt, and the product gives the oracle's words before and after"""
     w, R = worlds(N), worlds(N).R
     key0, _, bk, ksk = R.keygen(w.rp, 0x5F7 + N)
-    e = _engine(R, w.rp, bk, ksk)
+    e = gk.engine(R, w.rp, bk, ksk)
     try:
         e.set_backend(R._ffi.BACKEND_FFT_SPLIT_EXACT)
         with e.plain_polys(w.w) as pp:
@@ -274,21 +234,21 @@ def test_capture_first_thing_on_a_fresh_stream_and_replay(worlds):
     w = worlds(N)
     e = w.eng
     count, K, w_idx, x_idx, _ = SHAPES[3]
-    w_idx, x_idx = _i32(w_idx), _i32(x_idx)
-    acc = _acc("random", count, N)
+    w_idx, x_idx = i32(w_idx), i32(x_idx)
+    acc = gk.acc_rows("random", count, N)
     want = w.oracle(K, w_idx, x_idx, acc, count)
     eager = _dev(e, w.pp, w.x, count, K, w_idx, x_idx, acc)
     assert np.array_equal(eager, want)
     s = torch.cuda.Stream()
-    d_x, d_wi, d_xi = _cuda(w.x), _cuda(w_idx, np.int32), _cuda(x_idx, np.int32)
-    d_out = _cuda(acc)
+    d_x, d_wi, d_xi = gk.to_device(w.x, np.uint32), gk.to_device(w_idx, np.int32), gk.to_device(x_idx, np.int32)
+    d_out = gk.to_device(acc, np.uint32)
     torch.cuda.synchronize()
     with torch.cuda.stream(s):
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=s):      # nothing has run on s: the call allocates nothing
             e.trlwe_mul_plain_batch_dev(w.pp, d_x, w.x.shape[0], d_out, count, K, d_wi, d_xi, True, s.cuda_stream)
         for _ in range(2):
-            d_out.copy_(_cuda(acc))
+            d_out.copy_(gk.to_device(acc, np.uint32))
             g.replay()
             torch.cuda.synchronize()
             assert np.array_equal(d_out.cpu().numpy().view(np.uint32), eager)
@@ -300,7 +260,7 @@ def test_one_launch_per_call(worlds, N):
     import torch
     w = worlds(N)
     st = torch.cuda.current_stream().cuda_stream
-    d_x = _cuda(w.x)
+    d_x = gk.to_device(w.x, np.uint32)
     for count, K in ((1, 1), (5, 2), (1, 8)):
         d_out = torch.zeros((count, 2, N), dtype=torch.int32, device="cuda")
         w.eng.timer_begin(st)
@@ -314,7 +274,7 @@ def test_refusals_leave_the_output_untouched(worlds):
     N = 1024
     w = worlds(N)
     R, e = w.R, w.eng
-    d_x = _cuda(w.x)
+    d_x = gk.to_device(w.x, np.uint32)
     d_out = torch.full((5, 2, N), FILL, dtype=torch.int32, device="cuda")
     d_both = torch.full((6, 2, N), FILL, dtype=torch.int32, device="cuda")      # rows and output in one allocation
     at_limit = np.full((1, N), LIMIT, np.int32)          # K * wmax = 192 N exactly for K = 1
@@ -323,7 +283,7 @@ def test_refusals_leave_the_output_untouched(worlds):
     pp_at, pp_over = e.plain_polys(at_limit), e.plain_polys(over)
     assert pp_at.wmax == LIMIT * N and pp_over.wmax == LIMIT * N + 1
     out_host = np.full((5, 2, N), FILL, np.uint32)
-    d_zero2 = _cuda([[0, 0]], np.int32)
+    d_zero2 = gk.to_device([[0, 0]], np.int32)
     e.timer_begin()
 
     def dev(pp=w.pp, wi=None, x=d_x.data_ptr(), n_x=12, xi=None, K=1, acc=0, out=d_out.data_ptr(), count=3, h=e.h):
@@ -336,8 +296,8 @@ def test_refusals_leave_the_output_untouched(worlds):
     for call, word in ((lambda: dev(K=0), "K = 0"), (lambda: dev(K=9), "K = 9"), (lambda: host(K=0), "K = 0"), (lambda: host(K=9), "K = 9"),
                        (lambda: dev(pp=pp_over), "exactness domain"), (lambda: host(pp=pp_over), "exactness domain"),
                        (lambda: dev(pp=pp_at, K=2, count=1, wi=d_zero2.data_ptr()), "K * wmax = 2 * %d" % (LIMIT * N)),
-                       (lambda: host(wi=_i32([[0], [8], [1]])), "sample 1: w_idx[0] = 8"), (lambda: host(wi=_i32([[0], [1], [-1]])), "sample 2: w_idx[0] = -1"),
-                       (lambda: host(xi=_i32([[0, 1], [2, 12]]), K=2, count=2), "sample 1: x_idx[1] = 12"),
+                       (lambda: host(wi=i32([[0], [8], [1]])), "sample 1: w_idx[0] = 8"), (lambda: host(wi=i32([[0], [1], [-1]])), "sample 2: w_idx[0] = -1"),
+                       (lambda: host(xi=i32([[0, 1], [2, 12]]), K=2, count=2), "sample 1: x_idx[1] = 12"),
                        (lambda: host(K=3, count=5), "x_idx NULL: sample 4"), (lambda: dev(K=3, count=5), "x_idx NULL: sample 4"),
                        (lambda: dev(n_x=0), "n_x = 0"), (lambda: dev(count=1 << 31), "count * K"), (lambda: dev(K=8, count=(1 << 31) // 8), "count * K"),
                        (lambda: dev(x=0), "null"), (lambda: dev(out=0), "null"), (lambda: dev(pp=None), "null plain set"),
@@ -360,10 +320,10 @@ def test_refusals_leave_the_output_untouched(worlds):
     e.sync()
     assert (d_out.cpu().numpy().view(np.uint32) == FILL).all() and (d_both.cpu().numpy().view(np.uint32) == FILL).all() and (out_host == FILL).all()
     # accepted exactly at the limit; d_out right behind the rows does not overlap them
-    want = O.mul_plain(at_limit, w.x[:3], 1, _i32([[0]] * 3))
-    assert np.array_equal(e.trlwe_mul_plain_batch(pp_at, w.x[:3], 1, _i32([[0]] * 3), None), want)
-    d_both[:3].copy_(_cuda(w.x[:3]))
-    e.trlwe_mul_plain_batch_dev(pp_at, d_both[:3], 3, d_both[3:], 3, 1, _cuda([[0]] * 3, np.int32))
+    want = O.mul_plain(at_limit, w.x[:3], 1, i32([[0]] * 3))
+    assert np.array_equal(e.trlwe_mul_plain_batch(pp_at, w.x[:3], 1, i32([[0]] * 3), None), want)
+    d_both[:3].copy_(gk.to_device(w.x[:3], np.uint32))
+    e.trlwe_mul_plain_batch_dev(pp_at, d_both[:3], 3, d_both[3:], 3, 1, gk.to_device([[0]] * 3, np.int32))
     e.sync()
     assert np.array_equal(d_both[3:].cpu().numpy().view(np.uint32), want)
     pp_at.close()
@@ -390,15 +350,15 @@ def test_refusals_leave_the_output_untouched(worlds):
 def test_a_bad_device_index_skips_its_sample_and_sync_reports_once(worlds, N):
     w, R = worlds(N), worlds(N).R
     count, K = 5, 2
-    w_idx = _i32([[0, 1], [2, 8], [3, 4], [5, 6], [7, 0]])            # sample 1: a weight index out of range
-    x_idx = _i32([[0, 1], [2, 3], [4, 5], [6, 12], [8, 9]])           # sample 3: a row index out of range
+    w_idx = i32([[0, 1], [2, 8], [3, 4], [5, 6], [7, 0]])            # sample 1: a weight index out of range
+    x_idx = i32([[0, 1], [2, 3], [4, 5], [6, 12], [8, 9]])           # sample 3: a row index out of range
     ok_w, ok_x = w_idx.copy(), x_idx.copy()
     ok_w[1, 1], ok_x[3, 1] = 0, 0
     want = w.oracle(K, ok_w, ok_x, None, count)
     import torch
     st = torch.cuda.current_stream().cuda_stream
     d_out = torch.full((count * 2 * N + CANARY,), FILL, dtype=torch.int32, device="cuda")
-    w.eng.trlwe_mul_plain_batch_dev(w.pp, _cuda(w.x), 12, d_out, count, K, _cuda(w_idx, np.int32), _cuda(x_idx, np.int32), False, st)
+    w.eng.trlwe_mul_plain_batch_dev(w.pp, gk.to_device(w.x, np.uint32), 12, d_out, count, K, gk.to_device(w_idx, np.int32), gk.to_device(x_idx, np.int32), False, st)
     with pytest.raises(R.RtfheError) as ei:
         w.eng.sync(st)
     assert ei.value.code == R._ffi.ERR_INVALID

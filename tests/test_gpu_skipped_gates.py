@@ -7,7 +7,7 @@ filled with a nonzero, row-dependent sentinel, so that "wrote nothing" and "wrot
 waves (per-gate opcodes, gathered inputs, scattered outputs) are compared word for word with the same engine's plain batches as well.
 
 One key set per ring at n = 64 (n + 1 = 65 is odd: misaligned rows; 64 steps: more than every prefetch depth), one engine per launch shape,
-and the session engine (N = 1024, n = 635) for one pass of the default shape.  Batch sizes [1, 4] + _forced_sizes(N, C), C = the device's CUs.
+and the session engine (N = 1024, n = 635) for one pass of the default shape.  Batch sizes [1, 4] + gk.forced_sizes(N, C), C = the device's CUs.
 What each (shape, batch size) launches, from rtfhe_dispatch_fft.hip / _ntt.hip / _xfft.hip (wg_max = C; a MODE_GATE batch of the default
 shapes takes the split path: the family's kernel in MODE_EXTRACT, then k_key_switch_mm):
 
@@ -43,26 +43,20 @@ import types
 import numpy as np
 import pytest
 
-from test_cmux_tree_host import as_trlwe
-from test_gpu_cmux_tree import _oracle as _tree_oracle
-from test_gpu_mask_lengths import _cus, _forced_sizes, _plan, _pmap
-from test_gpu_pbs import CONFIGS_1024, _engine, _random_words
-from test_pbs_enc_host import oracle_pbs_enc
-from test_pbs_host import bk_fft, oracle_pbs
-from test_pbs_many_host import oracle_pbs_many
+import gpu_kit as gk
+from kit import random_words
+from leveled_kit import tree_oracle
+from leveled_oracle import as_trlwe
+from pbs_oracle import bk_fft, oracle_pbs, oracle_pbs_enc, oracle_pbs_many
 
 pytestmark = pytest.mark.gpu
 
 N_MASK = 64
 IN_ROWS, GUARD = 64, 8
 OP_LAST = 6                                     # OP_ANDNY: the last opcode a netlist accepts
-SHAPES = {1024: CONFIGS_1024, 2048: [None, {"RTFHE_FORCE_WAVES": "4"}, {"RTFHE_N2048_EO4": "0"}]}
+SHAPES = {1024: gk.CONFIGS_1024, 2048: gk.CONFIGS_2048}
 MIRROR = [(N, env) for N in (1024, 2048) for env in SHAPES[N]]
 EXACT = [(N, b, env) for N in (1024, 2048) for b, env in (("ntt", None), ("ntt", {"RTFHE_FORCE_WAVES": "4"}), ("xfft", None))]
-
-
-def _env_id(env):
-    return "default" if not env else ",".join("%s=%s" % kv for kv in env.items())
 
 
 def _sentinel(rows, width, salt=0):
@@ -73,7 +67,7 @@ def _sentinel(rows, width, salt=0):
 
 
 def _sizes(N, C):
-    return sorted(set([1, 4] + _forced_sizes(N, C)))
+    return sorted(set([1, 4] + gk.forced_sizes(N, C)))
 
 
 def _bad_positions(G, N, C, rng):
@@ -102,15 +96,6 @@ def _picks(G, bad):
     return sorted(g for g in s if 0 <= g < G)
 
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
-
-
-def _words(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
 def _expect_invalid_once(e, st):
     import rustfhe_amd as R
     with pytest.raises(R.RtfheError) as ei:
@@ -129,23 +114,23 @@ class Ring:
         self.P = P or orc.Params(n=n, N=N)
         self.K = keys or orc.Keys(self.P, 6400 + N)
         self.p = R.Params(n=n, N=N)
-        self.C = _cus()
+        self.C = gk.cus()
         rng = np.random.default_rng(N + n)
-        self.inputs = _random_words(rng, (IN_ROWS, n + 1))
-        self.tv = _random_words(rng, (3, N))
+        self.inputs = random_words(rng, (IN_ROWS, n + 1))
+        self.tv = random_words(rng, (3, N))
         self.trl = R.encrypt_lut(self.p, self.K.key1, self.tv, seed=N + n)
         self.memo = {}
 
     def engine(self, monkeypatch=None, env=None):
         import rustfhe_amd as R
-        return _engine(R, self.p, self.K.bk_t, self.K.ksk, monkeypatch, env)
+        return gk.engine(R, self.p, self.K.bk_t, self.K.ksk, monkeypatch, env)
 
     def oracle_gates(self, exact, ops, i0, i1):
         """orc.gate of (op, input row, input row) triples, on the mirror or on the exact-integer backend"""
         orc, K = self.orc, self.K
         backend = orc.BACKEND_EXACT if exact else orc.BACKEND_MIRROR
         todo = sorted({(exact, int(o), int(a), int(b)) for o, a, b in zip(ops, i0, i1)} - set(self.memo))
-        rows = _pmap(lambda k: orc.gate(self.P, _plan(orc, self.N, backend), k[1], None if exact else K.bk_f, K.bk_t if exact else None, K.ksk,
+        rows = gk.pmap(lambda k: orc.gate(self.P, gk.oracle_plan(orc, self.N, backend), k[1], None if exact else K.bk_f, K.bk_t if exact else None, K.ksk,
                                         self.inputs[k[2]], self.inputs[k[3]]), todo)
         self.memo.update(zip(todo, rows))
         return np.stack([self.memo[exact, int(o), int(a), int(b)] for o, a, b in zip(ops, i0, i1)])
@@ -153,19 +138,13 @@ class Ring:
     def oracle_pbs(self, key, fn, picks):
         """fn(g) for the picks, memoised under (key, g)"""
         todo = [g for g in picks if (key, g) not in self.memo]
-        self.memo.update(zip([(key, g) for g in todo], _pmap(fn, todo)))
+        self.memo.update(zip([(key, g) for g in todo], gk.pmap(fn, todo)))
         return np.stack([self.memo[key, g] for g in picks])
 
 
 @pytest.fixture(scope="module")
 def rings(orc):
-    made = {}
-
-    def get(N):
-        if N not in made:
-            made[N] = Ring(orc, N)
-        return made[N]
-    return get
+    return gk.Worlds(lambda N: Ring(orc, N))
 
 
 # ---- 1. netlist waves ----------------------------------------------------------------------------------------------------------------------
@@ -195,7 +174,7 @@ def _launch_wave(e, c, ops, i0, i1, io):
     import torch
     wires = torch.from_numpy(c.table.view(np.int32).copy()).cuda()
     st = torch.cuda.current_stream().cuda_stream
-    e.circuit_wave_dev(_dev(ops), _dev(i0), _dev(i1), _dev(io), wires, c.W, c.G, st)
+    e.circuit_wave_dev(gk.to_device(ops), gk.to_device(i0), gk.to_device(i1), gk.to_device(io), wires, c.W, c.G, st)
     return wires, st
 
 
@@ -224,27 +203,27 @@ def _check_waves(ring, e, exact, label):
             _expect_invalid_once(e, st)
             exp = c.table.copy()
             exp[c.io[c.valid]] = ref[c.valid]
-            assert _table_diff(_words(wires), exp, c) is None, (label, G, all_bad, _table_diff(_words(wires), exp, c))
+            assert _table_diff(gk.words_of(wires), exp, c) is None, (label, G, all_bad, _table_diff(gk.words_of(wires), exp, c))
             wires, st = _launch_wave(e, c, c.ops, c.i0, c.i1, c.io)
             e.sync(st)
             exp = c.table.copy()
             exp[c.io] = ref
-            assert _table_diff(_words(wires), exp, c) is None, (label, G, all_bad, "clean wave", _table_diff(_words(wires), exp, c))
+            assert _table_diff(gk.words_of(wires), exp, c) is None, (label, G, all_bad, "clean wave", _table_diff(gk.words_of(wires), exp, c))
 
 
-@pytest.mark.parametrize("N,env", MIRROR, ids=lambda v: str(v) if isinstance(v, int) else _env_id(v))
+@pytest.mark.parametrize("N,env", MIRROR, ids=lambda v: str(v) if isinstance(v, int) else gk.env_id(v))
 def test_netlist_wave_skips_bad_gates_mirror(rings, monkeypatch, N, env):
     """Valid gates' rows equal gate_batch(op) of the same engine on the gathered inputs (and the oracle on the picks); every other row of the
     table -- inputs, the target rows of bad gates, guard rows -- is unchanged; sync raises ERR_INVALID once; a clean wave follows."""
     ring = rings(N)
     e = ring.engine(monkeypatch, env)
     try:
-        _check_waves(ring, e, False, (N, _env_id(env)))
+        _check_waves(ring, e, False, (N, gk.env_id(env)))
     finally:
         e.close()
 
 
-@pytest.mark.parametrize("N,backend,env", EXACT, ids=lambda v: str(v) if not isinstance(v, (dict, type(None))) else _env_id(v))
+@pytest.mark.parametrize("N,backend,env", EXACT, ids=lambda v: str(v) if not isinstance(v, (dict, type(None))) else gk.env_id(v))
 def test_netlist_wave_skips_bad_gates_exact_backends(rings, monkeypatch, N, backend, env):
     """The same on the NTT backend (default shape and RTFHE_FORCE_WAVES=4) and on the split-FFT backend, against the exact-integer oracle."""
     import rustfhe_amd as R
@@ -252,7 +231,7 @@ def test_netlist_wave_skips_bad_gates_exact_backends(rings, monkeypatch, N, back
     e = ring.engine(monkeypatch, env)
     try:
         e.set_backend(R._ffi.BACKEND_NTT_EXACT if backend == "ntt" else R._ffi.BACKEND_FFT_SPLIT_EXACT)
-        _check_waves(ring, e, True, (N, backend, _env_id(env)))
+        _check_waves(ring, e, True, (N, backend, gk.env_id(env)))
     finally:
         e.close()
 
@@ -277,18 +256,18 @@ def _pbs_dev(e, lut, call, n_out, ct, idx, salt):
     out = big[GUARD:GUARD + G * n_out]
     st = torch.cuda.current_stream().cuda_stream
     if call == "pbs":
-        e.pbs_batch_dev(lut, _dev(ct.view(np.int32)), out, G, _dev(idx), st)
+        e.pbs_batch_dev(lut, gk.to_device(ct.view(np.int32)), out, G, gk.to_device(idx), st)
     else:
-        e.pbs_many_batch_dev(lut, _dev(ct.view(np.int32)), out, G, n_out, _dev(idx), st)
+        e.pbs_many_batch_dev(lut, gk.to_device(ct.view(np.int32)), out, G, n_out, gk.to_device(idx), st)
     return big, fill, st
 
 
 def _guards_intact(big, fill, rows):
-    got = _words(big)
+    got = gk.words_of(big)
     return np.array_equal(got[:GUARD], fill[:GUARD]) and np.array_equal(got[GUARD + rows:], fill[GUARD + rows:])
 
 
-@pytest.mark.parametrize("N,env", MIRROR, ids=lambda v: str(v) if isinstance(v, int) else _env_id(v))
+@pytest.mark.parametrize("N,env", MIRROR, ids=lambda v: str(v) if isinstance(v, int) else gk.env_id(v))
 def test_device_indexed_tables_skip_bad_gates(rings, monkeypatch, N, env):
     """pbs_batch_dev, pbs_many_batch_dev (n_out 1 and 4) and both with an encrypted table, lut_idx = -1, 3, 2^31 - 1, -2^31 at the bad
     positions: valid gates' rows equal a clean run of the same engine (and the oracle on the picks), the guard rows around the output are
@@ -300,7 +279,7 @@ def test_device_indexed_tables_skip_bad_gates(rings, monkeypatch, N, env):
         with e.lut(ring.tv) as plain, e.lut_encrypted(ring.trl) as enc:
             for G in _sizes(N, ring.C):
                 rng = np.random.default_rng([N, G, 2])
-                ct = _random_words(rng, (G, ring.n + 1))
+                ct = random_words(rng, (G, ring.n + 1))
                 idx = rng.integers(0, 3, G).astype(np.int32)
                 bad = _bad_positions(G, N, ring.C, rng)
                 bad_idx = idx.astype(np.int64)
@@ -310,23 +289,23 @@ def test_device_indexed_tables_skip_bad_gates(rings, monkeypatch, N, env):
                 valid[bad] = False
                 pick = [g for g in _picks(G, bad)]
                 for vi, (call, encrypted, n_out) in enumerate(VARIANTS):
-                    label = (N, _env_id(env), call, "encrypted" if encrypted else "plain", n_out, G)
+                    label = (N, gk.env_id(env), call, "encrypted" if encrypted else "plain", n_out, G)
                     lut = enc if encrypted else plain
                     big, fill, st = _pbs_dev(e, lut, call, n_out, ct, idx, vi)
                     e.sync(st)
                     assert _guards_intact(big, fill, G * n_out), (label, "clean run: guard rows")
-                    clean = _words(big)[GUARD:GUARD + G * n_out].reshape(G, n_out, -1).copy()
+                    clean = gk.words_of(big)[GUARD:GUARD + G * n_out].reshape(G, n_out, -1).copy()
                     if encrypted:
-                        fn = lambda g: oracle_pbs_enc(orc, P, _plan(orc, N), K.bk_f, K.ksk, ring.trl[idx[g]], ct[g], n_out)  # noqa: E731
+                        fn = lambda g: oracle_pbs_enc(orc, P, gk.oracle_plan(orc, N), K.bk_f, K.ksk, ring.trl[idx[g]], ct[g], n_out)  # noqa: E731
                     elif call == "pbs":
-                        fn = lambda g: oracle_pbs(orc, P, _plan(orc, N), K.bk_f, K.ksk, ring.tv[idx[g]], ct[g])[None]  # noqa: E731
+                        fn = lambda g: oracle_pbs(orc, P, gk.oracle_plan(orc, N), K.bk_f, K.ksk, ring.tv[idx[g]], ct[g])[None]  # noqa: E731
                     else:
-                        fn = lambda g: oracle_pbs_many(orc, P, _plan(orc, N), K.bk_f, K.ksk, ring.tv[idx[g]], ct[g], n_out)  # noqa: E731
+                        fn = lambda g: oracle_pbs_many(orc, P, gk.oracle_plan(orc, N), K.bk_f, K.ksk, ring.tv[idx[g]], ct[g], n_out)  # noqa: E731
                     want = ring.oracle_pbs(("pbs", G, encrypted, "pbs" if call == "pbs" and not encrypted else n_out), fn, pick)
                     assert np.array_equal(clean[pick], want.reshape(len(pick), n_out, -1)), (label, "clean run against the oracle")
                     big, fill, st = _pbs_dev(e, lut, call, n_out, ct, bad_idx, vi + 8)
                     _expect_invalid_once(e, st)
-                    got = _words(big)[GUARD:GUARD + G * n_out].reshape(G, n_out, -1)
+                    got = gk.words_of(big)[GUARD:GUARD + G * n_out].reshape(G, n_out, -1)
                     assert np.array_equal(got[valid], clean[valid]), (label, np.flatnonzero((got != clean).any(axis=(1, 2)) & valid)[:12])
                     assert _guards_intact(big, fill, G * n_out), (label, "guard rows")
     finally:
@@ -339,14 +318,14 @@ N_SEL, N_ROWS = 8, 8 + 3
 
 @pytest.fixture(scope="module", params=[1024, 2048], ids=lambda N: "N%d" % N)
 def tree_world(request, rings, orc):
-    """the ring's key set with eight selectors of known bits and an 11-row plain and encrypted table, in the shape test_gpu_cmux_tree._oracle reads"""
+    """the ring's key set with eight selectors of known bits and an 11-row plain and encrypted table, in the shape leveled_kit.tree_oracle reads"""
     import rustfhe_amd as R
     ring = rings(request.param)
     w = types.SimpleNamespace(R=R, N=ring.N, rp=ring.p, P=ring.P, plan=orc.Plan(ring.N), ksk=ring.K.ksk, C=ring.C, oracle_memo={})
     rng = np.random.default_rng(ring.N + 3)
     sel_t = R.encrypt_selectors(ring.p, ring.K.key1, rng.integers(0, 2, N_SEL).astype(np.uint8), seed=0x5E1 + ring.N)
     w.sel_f = bk_fft(orc, w.P, w.plan, sel_t.reshape(-1))
-    w.rows = {"plain": _random_words(rng, (N_ROWS, ring.N)), "encrypted": R.encrypt_lut(ring.p, ring.K.key1, _random_words(rng, (N_ROWS, ring.N)), seed=0x7AB + ring.N)}
+    w.rows = {"plain": random_words(rng, (N_ROWS, ring.N)), "encrypted": R.encrypt_lut(ring.p, ring.K.key1, random_words(rng, (N_ROWS, ring.N)), seed=0x7AB + ring.N)}
     assert as_trlwe(w.rows["plain"], ring.N).shape == (N_ROWS, 2, ring.N)
     w.eng = ring.engine()
     w.sel = w.eng.selectors(sel_t)
@@ -365,9 +344,9 @@ def _tree_dev(w, kind, depth, count, sel_idx, row0, coef, extract, salt):
     out = big[GUARD:GUARD + count]
     st = torch.cuda.current_stream().cuda_stream
     if extract:
-        w.eng.cmux_tree_extract_batch_dev(w.sel, w.lut[kind], depth, out, count, _dev(sel_idx), _dev(row0), _dev(coef), st)
+        w.eng.cmux_tree_extract_batch_dev(w.sel, w.lut[kind], depth, out, count, gk.to_device(sel_idx), gk.to_device(row0), gk.to_device(coef), st)
     else:
-        w.eng.cmux_tree_batch_dev(w.sel, w.lut[kind], depth, out, count, _dev(sel_idx), _dev(row0), st)
+        w.eng.cmux_tree_batch_dev(w.sel, w.lut[kind], depth, out, count, gk.to_device(sel_idx), gk.to_device(row0), st)
     return big, fill, st
 
 
@@ -375,7 +354,7 @@ def _tree_dev(w, kind, depth, count, sel_idx, row0, coef, extract, salt):
 def test_cmux_tree_skips_bad_lookups(orc, tree_world, depth):
     """cmux_tree_batch_dev and the extract form, plain and encrypted tables, counts 1, 5, 37 and 4C + 1: bad sel_idx, row0 and coef values at
     the first and the last lookup, then at an aligned run of 4 lookups (one workgroup of the last level).  Valid lookups equal the clean run
-    (and test_gpu_cmux_tree._oracle on the picks), the guard rows are unchanged, the error is reported once."""
+    (and leveled_kit.tree_oracle on the picks), the guard rows are unchanged, the error is reported once."""
     w = tree_world
     for count in (1, 5, 37, 4 * w.C + 1):
         rng = np.random.default_rng([w.N, depth, count])
@@ -392,7 +371,7 @@ def test_cmux_tree_skips_bad_lookups(orc, tree_world, depth):
                 big, fill, st = _tree_dev(w, kind, depth, count, sel_idx, row0, coef, extract, 0)
                 w.eng.sync(st)
                 assert _guards_intact(big, fill, count), (label, "clean run: guard rows")
-                clean = _words(big)[GUARD:GUARD + count].copy()
+                clean = gk.words_of(big)[GUARD:GUARD + count].copy()
                 for pi, bad in enumerate(places):
                     b_sel, b_row, b_coef = sel_idx.copy(), row0.copy(), coef.copy()
                     for k, g in enumerate(bad.tolist()):
@@ -406,10 +385,10 @@ def test_cmux_tree_skips_bad_lookups(orc, tree_world, depth):
                     valid = np.ones(count, bool)
                     valid[bad] = False
                     pick = np.array(_picks(count, bad))
-                    want = _tree_oracle(orc, w, kind, depth, sel_idx[pick], row0[pick], coef[pick] if extract else None)
+                    want = tree_oracle(orc, w, kind, depth, sel_idx[pick], row0[pick], coef[pick] if extract else None)
                     assert np.array_equal(clean[pick], want.reshape(len(pick), -1)), (label, "clean run against the oracle")
                     big, fill, st = _tree_dev(w, kind, depth, count, b_sel, b_row, b_coef, extract, 1 + pi)
                     _expect_invalid_once(w.eng, st)
-                    got = _words(big)[GUARD:GUARD + count]
+                    got = gk.words_of(big)[GUARD:GUARD + count]
                     assert np.array_equal(got[valid], clean[valid]), (label, pi, np.flatnonzero((got != clean).any(axis=1) & valid)[:12])
                     assert _guards_intact(big, fill, count), (label, pi, "guard rows")

@@ -10,18 +10,16 @@ import os
 import numpy as np
 import pytest
 
+import gpu_kit as gk
 import round_oracle as ro
 import trgsw_mac_oracle as O
+from gpu_kit import CANARY, FILL
+from kit import SMALL_N, i32
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILL = 0x5A5A5A5A
-CANARY = 64             # words behind every device output that must keep their bytes
-SMALL_N = {1024: 40, 2048: 24}
 N_SEL, N_X = 16, 12
-
-_WORLDS = {}
 
 
 class World:
@@ -49,12 +47,9 @@ class World:
         self.memo = {}
 
     def oracle(self, mode, K, s_idx, x_idx, acc, count):
-        key = (mode, K, None if s_idx is None else s_idx.tobytes(), None if x_idx is None else x_idx.tobytes(), None if acc is None else acc.tobytes(), count)
-        if key not in self.memo:
-            nat = np.arange(count * K).reshape(count, K)
-            self.memo[key] = O.mac(self.p, self.plan, self.sel_f, nat if s_idx is None else s_idx, self.x, nat if x_idx is None else x_idx, acc, mode)
-            self.memo[key].setflags(write=False)
-        return self.memo[key]
+        nat = np.arange(count * K).reshape(count, K)
+        return gk.memo(self.memo, (mode, K, s_idx, x_idx, acc, count),
+                       lambda: O.mac(self.p, self.plan, self.sel_f, nat if s_idx is None else s_idx, self.x, nat if x_idx is None else x_idx, acc, mode))
 
     def mode(self, mode):
         self.eng.set_leveled_decomposition(self.R._ffi.DECOMP_ROUNDED if mode == O.ROUNDED else self.R._ffi.DECOMP_REFERENCE)
@@ -67,22 +62,14 @@ class World:
 @pytest.fixture(scope="module")
 def worlds(orc):
     import rustfhe_amd as R
+    made = gk.Worlds(lambda N: World(R, orc, N))
 
     def get(N):
-        if N not in _WORLDS:
-            _WORLDS[N] = World(R, orc, N)
-        w = _WORLDS[N]
+        w = made(N)
         w.mode(O.REFERENCE)
         return w
     yield get
-    for w in _WORLDS.values():
-        w.close()
-    _WORLDS.clear()
-
-
-def _cuda(a, dtype=np.uint32):
-    import torch
-    return torch.from_numpy(np.array(a, dtype=dtype).view(np.int32)).cuda()      # (a copy: the shared inputs are read-only)
+    made.close()
 
 
 def _dev(eng, sel, x, count, K=1, s_idx=None, x_idx=None, acc=None, stream=None):
@@ -90,29 +77,10 @@ def _dev(eng, sel, x, count, K=1, s_idx=None, x_idx=None, acc=None, stream=None)
     import torch
     N = x.shape[2]
     st = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    d_x = _cuda(x)
-    d_out = torch.full((count * 2 * N + CANARY,), FILL, dtype=torch.int32, device="cuda")
-    if acc is not None:
-        d_out[:count * 2 * N].copy_(_cuda(acc).reshape(-1))
-    d_si = None if s_idx is None else _cuda(s_idx, np.int32)
-    d_xi = None if x_idx is None else _cuda(x_idx, np.int32)
-    eng.trlwe_mul_trgsw_batch_dev(sel, d_x, x.shape[0], d_out, count, K, d_si, d_xi, acc is not None, st)
+    d_out = gk.guarded_out(count * 2 * N, init=acc)
+    eng.trlwe_mul_trgsw_batch_dev(sel, gk.to_device(x, np.uint32), x.shape[0], d_out, count, K, gk.to_device(s_idx), gk.to_device(x_idx), acc is not None, st)
     eng.sync(st)
-    out = d_out.cpu().numpy().view(np.uint32)
-    assert (out[count * 2 * N:] == FILL).all(), "words behind d_out were written"
-    return out[:count * 2 * N].reshape(count, 2, N)
-
-
-def _acc(kind, count, N):
-    if kind is None:
-        return None
-    if kind == "fill":
-        return np.full((count, 2, N), FILL, np.uint32)
-    return np.random.default_rng(count * N).integers(0, 1 << 32, (count, 2, N), dtype=np.uint64).astype(np.uint32)
-
-
-def _i32(a):
-    return np.array(a, np.int32)
+    return gk.read_guarded(d_out, count * 2 * N).reshape(count, 2, N)
 
 
 # (count, K, s_idx, x_idx, accumulate): ragged four-wave workgroups (count 1, 2, 3, 5), K 1, 2, 3, 8, NULL and given indices with duplicates,
@@ -137,8 +105,8 @@ def test_every_word_equals_the_restatement(worlds, N, mode, shape):
     w = worlds(N)
     w.mode(mode)
     count, K, s_idx, x_idx, kind = SHAPES[shape]
-    s_idx, x_idx = (None if s_idx is None else _i32(s_idx)), (None if x_idx is None else _i32(x_idx))
-    acc = _acc(kind, count, N)
+    s_idx, x_idx = (None if s_idx is None else i32(s_idx)), (None if x_idx is None else i32(x_idx))
+    acc = gk.acc_rows(kind, count, N)
     want = w.oracle(mode, K, s_idx, x_idx, acc, count)
     got = w.eng.trlwe_mul_trgsw_batch(w.sel, w.x, K, s_idx, x_idx, acc) if (s_idx is not None or x_idx is not None or acc is not None) else \
         w.eng.trlwe_mul_trgsw_batch(w.sel, w.x[:count * K], K)
@@ -166,7 +134,7 @@ def test_anchors(worlds, N):
         one[0, 0, j, 0] = one[0, 1, w.rp.l + j, 0] = 1 << (32 - (j + 1) * w.rp.bgbit)
     try:
         keyed.load_bk_torus(bk)
-        idx = _i32([3, 0, 15, 7, 7])
+        idx = i32([3, 0, 15, 7, 7])
         rows = w.x[[2, 5, 5, 0, 11]]
         with w.eng.selectors(one) as sel_one:
             for mode, lo, hi in ((O.REFERENCE, 1 - 2 ** 14, 2 ** 15), (O.ROUNDED, 1 - 2 ** 13, 2 ** 13)):
@@ -176,9 +144,9 @@ def test_anchors(worlds, N):
                 got = w.eng.trlwe_mul_trgsw_batch(w.sel, rows, 1, idx[:, None], None)
                 assert np.array_equal(got, stage), mode
                 assert np.array_equal(_dev(w.eng, w.sel, rows, 5, 1, idx[:, None], None), stage), mode
-                with_zero = w.eng.trlwe_mul_trgsw_batch(w.sel, rows, 2, np.stack([idx, np.full(5, N_SEL - 1, np.int32)], axis=1), _i32([[g, (g + 1) % 5] for g in range(5)]))
+                with_zero = w.eng.trlwe_mul_trgsw_batch(w.sel, rows, 2, np.stack([idx, np.full(5, N_SEL - 1, np.int32)], axis=1), i32([[g, (g + 1) % 5] for g in range(5)]))
                 assert np.array_equal(with_zero, got), mode
-                back = w.eng.trlwe_mul_trgsw_batch(sel_one, w.x[:5], 1, _i32([[0]] * 5), None)
+                back = w.eng.trlwe_mul_trgsw_batch(sel_one, w.x[:5], 1, i32([[0]] * 5), None)
                 e = (back - w.x[:5]).view(np.int32).astype(np.int64)
                 assert lo - 1 <= e.min() and e.max() <= hi + 1, (mode, e.min(), e.max())
                 assert e.min() < 0 < e.max()
@@ -198,14 +166,14 @@ def test_the_largest_sums_need_the_wide_conversion(worlds, N, mode):
     rows = O.extreme_rows(N, 2, mode)
     assert (ro.digits(rows[0, 0], w.rp.l, w.rp.bgbit, ma, mx) == -32).all()
     sel_t = np.full((2, 2, 2 * w.rp.l, N), 0x80000000, np.uint32)
-    s_idx, x_idx = _i32([[0, 1] * 4, [1] * 8, [0] * 8]), _i32([[0] * 8, [0, 1] * 4, [1] * 8])
+    s_idx, x_idx = i32([[0, 1] * 4, [1] * 8, [0] * 8]), i32([[0] * 8, [0, 1] * 4, [1] * 8])
     want = O.mac(w.p, w.plan, O.spectra(w.p, w.plan, sel_t), s_idx, rows, x_idx, None, mode)
     with w.eng.selectors(sel_t) as sel:
         got = w.eng.trlwe_mul_trgsw_batch(sel, rows, 8, s_idx, x_idx)
-        dev = _dev(w.eng, sel, rows, 3, 8, s_idx, x_idx, _acc("random", 3, N))
+        dev = _dev(w.eng, sel, rows, 3, 8, s_idx, x_idx, gk.acc_rows("random", 3, N))
     bad = np.argwhere(got != want)
     assert bad.size == 0, (len(bad), bad[:5])
-    assert np.array_equal(dev, want + _acc("random", 3, N))
+    assert np.array_equal(dev, want + gk.acc_rows("random", 3, N))
 
 
 def test_meaning_with_real_keys(worlds, orc):
@@ -250,22 +218,22 @@ def test_capture_first_thing_on_a_fresh_stream_and_replay():
     sel_t = R.encrypt_trgsw_polys(rp, key1, np.random.default_rng(3).integers(-1, 2, (4, N)).astype(np.int32), seed=0x7C2)
     x = O.rows_with_edges(0x7C3, N, 6)
     count, K = 5, 2
-    s_idx, x_idx = _i32([[0, 1], [2, 3], [3, 3], [1, 0], [2, 2]]), _i32([[0, 1], [2, 3], [4, 5], [5, 5], [0, 3]])
-    acc = _acc("random", count, N)
+    s_idx, x_idx = i32([[0, 1], [2, 3], [3, 3], [1, 0], [2, 2]]), i32([[0, 1], [2, 3], [4, 5], [5, 5], [0, 3]])
+    acc = gk.acc_rows("random", count, N)
     want = O.mac(p, plan, O.spectra(p, plan, sel_t), s_idx, x, x_idx, acc, O.REFERENCE)
     e = R.Engine(rp, 0)
     try:
         with e.selectors(sel_t) as sel:
             s = torch.cuda.Stream()
-            d_x, d_si, d_xi = _cuda(x), _cuda(s_idx, np.int32), _cuda(x_idx, np.int32)
-            d_out = _cuda(acc)
+            d_x, d_si, d_xi = gk.to_device(x, np.uint32), gk.to_device(s_idx, np.int32), gk.to_device(x_idx, np.int32)
+            d_out = gk.to_device(acc, np.uint32)
             torch.cuda.synchronize()
             with torch.cuda.stream(s):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=s):      # nothing has run on s, and no product on this context: the call allocates nothing
                     e.trlwe_mul_trgsw_batch_dev(sel, d_x, x.shape[0], d_out, count, K, d_si, d_xi, True, s.cuda_stream)
                 for _ in range(2):
-                    d_out.copy_(_cuda(acc))
+                    d_out.copy_(gk.to_device(acc, np.uint32))
                     g.replay()
                     torch.cuda.synchronize()
                     assert np.array_equal(d_out.cpu().numpy().view(np.uint32), want)
@@ -280,7 +248,7 @@ def test_one_launch_per_call(worlds, N):
     import torch
     w = worlds(N)
     st = torch.cuda.current_stream().cuda_stream
-    d_x = _cuda(w.x)
+    d_x = gk.to_device(w.x, np.uint32)
     for count, K in ((1, 1), (5, 2), (1, 8)):
         d_out = torch.zeros((count, 2, N), dtype=torch.int32, device="cuda")
         w.eng.timer_begin(st)
@@ -294,7 +262,7 @@ def test_refusals_leave_the_output_untouched(worlds):
     N = 1024
     w = worlds(N)
     R, e = w.R, w.eng
-    d_x = _cuda(w.x)
+    d_x = gk.to_device(w.x, np.uint32)
     d_out = torch.full((5, 2, N), FILL, dtype=torch.int32, device="cuda")
     d_both = torch.full((6, 2, N), FILL, dtype=torch.int32, device="cuda")      # rows and output in one allocation
     out_host = np.full((5, 2, N), FILL, np.uint32)
@@ -308,10 +276,10 @@ def test_refusals_leave_the_output_untouched(worlds):
                                                out_host.ctypes.data, count)
 
     for call, word in ((lambda: dev(K=0), "K = 0"), (lambda: dev(K=9), "K = 9"), (lambda: host(K=0), "K = 0"), (lambda: host(K=9), "K = 9"),
-                       (lambda: host(si=_i32([[0], [16], [1]])), "sample 1: s_idx[0] = 16"), (lambda: host(si=_i32([[0], [1], [-1]])), "sample 2: s_idx[0] = -1"),
-                       (lambda: host(xi=_i32([[0, 1], [2, 12]]), K=2, count=2), "sample 1: x_idx[1] = 12"),
+                       (lambda: host(si=i32([[0], [16], [1]])), "sample 1: s_idx[0] = 16"), (lambda: host(si=i32([[0], [1], [-1]])), "sample 2: s_idx[0] = -1"),
+                       (lambda: host(xi=i32([[0, 1], [2, 12]]), K=2, count=2), "sample 1: x_idx[1] = 12"),
                        (lambda: host(K=3, count=5), "x_idx NULL: sample 4"), (lambda: dev(K=3, count=5), "x_idx NULL: sample 4"),
-                       (lambda: host(K=6, count=3, xi=_i32([[0] * 6] * 3)), "s_idx NULL: sample 2"), (lambda: dev(K=8, count=3, xi=d_x.data_ptr()), "s_idx NULL: sample 2"),
+                       (lambda: host(K=6, count=3, xi=i32([[0] * 6] * 3)), "s_idx NULL: sample 2"), (lambda: dev(K=8, count=3, xi=d_x.data_ptr()), "s_idx NULL: sample 2"),
                        (lambda: dev(n_x=0), "n_x = 0"), (lambda: dev(count=1 << 31), "count * K"), (lambda: dev(K=8, count=(1 << 31) // 8), "count * K"),
                        (lambda: dev(x=0), "null"), (lambda: dev(out=0), "null"), (lambda: dev(sel=None), "null selector set"),
                        (lambda: dev(x=d_both.data_ptr(), n_x=3, out=d_both[2].data_ptr()), "overlaps"),
@@ -328,10 +296,10 @@ def test_refusals_leave_the_output_untouched(worlds):
     assert (d_out.cpu().numpy().view(np.uint32) == FILL).all() and (d_both.cpu().numpy().view(np.uint32) == FILL).all() and (out_host == FILL).all()
     # accepted exactly at each limit: K = 8 with NULL indices at n_sel = count * K = 16 and n_x = 12 >= 8; d_out right behind the rows does not
     # overlap them
-    assert np.array_equal(e.trlwe_mul_trgsw_batch(w.sel, w.x, 8, None, _i32([[0, 1, 2, 3, 4, 5, 6, 7], [4, 5, 6, 7, 8, 9, 10, 11]])),
-                          w.oracle(O.REFERENCE, 8, None, _i32([[0, 1, 2, 3, 4, 5, 6, 7], [4, 5, 6, 7, 8, 9, 10, 11]]), None, 2))
-    assert np.array_equal(e.trlwe_mul_trgsw_batch(w.sel, w.x, 4, _i32([[0, 1, 2, 3]] * 3), None), w.oracle(O.REFERENCE, 4, _i32([[0, 1, 2, 3]] * 3), None, None, 3))
-    d_both[:3].copy_(_cuda(w.x[:3]))
+    assert np.array_equal(e.trlwe_mul_trgsw_batch(w.sel, w.x, 8, None, i32([[0, 1, 2, 3, 4, 5, 6, 7], [4, 5, 6, 7, 8, 9, 10, 11]])),
+                          w.oracle(O.REFERENCE, 8, None, i32([[0, 1, 2, 3, 4, 5, 6, 7], [4, 5, 6, 7, 8, 9, 10, 11]]), None, 2))
+    assert np.array_equal(e.trlwe_mul_trgsw_batch(w.sel, w.x, 4, i32([[0, 1, 2, 3]] * 3), None), w.oracle(O.REFERENCE, 4, i32([[0, 1, 2, 3]] * 3), None, None, 3))
+    d_both[:3].copy_(gk.to_device(w.x[:3], np.uint32))
     e.trlwe_mul_trgsw_batch_dev(w.sel, d_both[:3], 3, d_both[3:], 3, 1)
     e.sync()
     assert np.array_equal(d_both[3:].cpu().numpy().view(np.uint32), w.oracle(O.REFERENCE, 1, None, None, None, 3))
@@ -360,7 +328,7 @@ def test_a_destroyed_context_gives_err_state():
     sel = e.selectors(np.zeros((1, 2, 2 * rp.l, N), np.uint32))
     x = np.zeros((1, 2, N), np.uint32)
     out = np.full((1, 2, N), FILL, np.uint32)
-    d_x = _cuda(x)
+    d_x = gk.to_device(x, np.uint32)
     d_out = torch.full((1, 2, N), FILL, dtype=torch.int32, device="cuda")
     e.close()
     live = R.Engine(rp, 0)
@@ -381,15 +349,15 @@ def test_a_destroyed_context_gives_err_state():
 def test_a_bad_device_index_skips_its_sample_and_sync_reports_once(worlds, N):
     w, R = worlds(N), worlds(N).R
     count, K = 5, 2
-    s_idx = _i32([[0, 1], [2, 16], [3, 4], [5, 6], [7, 0]])           # sample 1: a selector index out of range
-    x_idx = _i32([[0, 1], [2, 3], [4, 5], [6, 12], [8, 9]])           # sample 3: a row index out of range
+    s_idx = i32([[0, 1], [2, 16], [3, 4], [5, 6], [7, 0]])           # sample 1: a selector index out of range
+    x_idx = i32([[0, 1], [2, 3], [4, 5], [6, 12], [8, 9]])           # sample 3: a row index out of range
     ok_s, ok_x = s_idx.copy(), x_idx.copy()
     ok_s[1, 1], ok_x[3, 1] = 0, 0
     want = w.oracle(O.REFERENCE, K, ok_s, ok_x, None, count)
     import torch
     st = torch.cuda.current_stream().cuda_stream
     d_out = torch.full((count * 2 * N + CANARY,), FILL, dtype=torch.int32, device="cuda")
-    w.eng.trlwe_mul_trgsw_batch_dev(w.sel, _cuda(w.x), N_X, d_out, count, K, _cuda(s_idx, np.int32), _cuda(x_idx, np.int32), False, st)
+    w.eng.trlwe_mul_trgsw_batch_dev(w.sel, gk.to_device(w.x, np.uint32), N_X, d_out, count, K, gk.to_device(s_idx, np.int32), gk.to_device(x_idx, np.int32), False, st)
     with pytest.raises(R.RtfheError) as ei:
         w.eng.sync(st)
     assert ei.value.code == R._ffi.ERR_INVALID
@@ -405,7 +373,7 @@ def test_a_bad_device_index_skips_its_sample_and_sync_reports_once(worlds, N):
 def test_exact_backends_refuse_and_a_two_entry_context_runs(worlds, N):
     w, R = worlds(N), worlds(N).R
     count, K, s_idx, x_idx, _ = SHAPES[3]
-    s_idx, x_idx = _i32(s_idx), _i32(x_idx)
+    s_idx, x_idx = i32(s_idx), i32(x_idx)
     want = w.oracle(O.REFERENCE, K, s_idx, x_idx, None, count)
     e = R.Engine(w.rp, 0)            # nothing loaded
     try:

@@ -1,20 +1,18 @@
 """GPU: TRGSW blind rotation (rtfhe_trgsw_rotate_batch[_dev], rtfhe_trgsw_rotate_extract_batch[_dev]; the k_trgsw_rotate kernels).  Every word
-against the oracle's rotation (tests/test_trgsw_rotate_host.py: oracle_trgsw_rotate) at both N, depths 1, 2, 5 and log2 N + 1 and counts 1, 5
+against the oracle's rotation (tests/leveled_oracle.py: oracle_trgsw_rotate) at both N, depths 1, 2, 5 and log2 N + 1 and counts 1, 5
 and 37; the extract form; in place; a second opinion from the bootstrap's own blind rotation; the composition with the CMUX tree into a fully
 encrypted table lookup; skipped lookups; refusals and the capture rule.  Small TLWE dimensions as the other stage tests use: n = 40 at
 N = 1024, n = 24 at N = 2048."""
-import types
-
 import numpy as np
 import pytest
 
-from test_gpu_pbs import _engine, _random_words
-from test_pbs_host import bk_fft
-from test_trgsw_rotate_host import oracle_trgsw_rotate
+import gpu_kit as gk
+from kit import random_words
+from leveled_kit import rotate_dev, selector_world
+from leveled_oracle import oracle_trgsw_rotate
 
 pytestmark = pytest.mark.gpu
 
-SMALL_N = {1024: 40, 2048: 24}
 N_SEL = 37 * 5          # sel_idx = NULL at depth 5 and 37 lookups reads selectors 0 .. 184
 N_ROWS = 37
 
@@ -23,22 +21,12 @@ N_ROWS = 37
 def world(request, orc):
     """Per N: keys from the product's keygen on an engine, N_SEL selectors of known random bits (device handle, torus words and the oracle's
     spectra of them) and N_ROWS input rows with random words in both halves."""
-    import rustfhe_amd as R
     N = request.param
-    rp = R.Params(n=SMALL_N[N], N=N)
-    key0, key1, bk, ksk = R.keygen(rp, 0x207 + N)
-    w = types.SimpleNamespace(R=R, N=N, logn=N.bit_length() - 1, rp=rp, key0=key0, key1=key1, bk=bk, ksk=ksk)
-    w.P = orc.Params(n=rp.n, N=N)
-    w.plan = orc.Plan(N)
-    rng = np.random.default_rng(N + 12)
-    w.bits = rng.integers(0, 2, N_SEL).astype(np.uint8)
-    w.bits[:2] = (0, 1)
-    w.sel_t = R.encrypt_selectors(rp, key1, w.bits, seed=0x207A7E + N)
-    w.sel_f = bk_fft(orc, w.P, w.plan, w.sel_t.reshape(-1))
-    w.rows = _random_words(rng, (N_ROWS, 2, N))
+    w, rng = selector_world(orc, N, 0x207 + N, N + 12, N_SEL, 0x207A7E + N)
+    w.rows = random_words(rng, (N_ROWS, 2, N))
     base = [2 * N - 1, 0, N, 1] + [int(r) for r in rng.integers(0, 2 * N, 12)]
     w.rot = lambda depth: np.array(base[:depth], np.int32)      # noqa: E731
-    w.eng = _engine(R, rp, bk, ksk)
+    w.eng = gk.engine(w.R, w.rp, w.bk, w.ksk)
     w.sel = w.eng.selectors(w.sel_t)
     w.oracle_memo = {}
     yield w
@@ -49,35 +37,8 @@ def world(request, orc):
 def _oracle(orc, w, sel_idx, rot, rows, extract=False):
     """the oracle's rotation of every lookup: sel_idx [count][depth], rot [depth] or None, rows [count][2][N]; computed once per world and
     arguments, shared by the tests that ask for the same lookups, and read-only"""
-    key = (sel_idx.tobytes(), sel_idx.shape, None if rot is None else np.asarray(rot, np.int32).tobytes(), rows.tobytes(), extract)
-    if key not in w.oracle_memo:
-        want = np.stack([oracle_trgsw_rotate(orc, w.P, w.plan, w.sel_f, sel_idx[g], None if rot is None else [int(r) for r in rot], rows[g], extract, w.ksk)
-                         for g in range(len(rows))])
-        want.setflags(write=False)
-        w.oracle_memo[key] = want
-    return w.oracle_memo[key]
-
-
-def _cuda(a, dtype=np.int32):
-    import torch
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype).view(np.int32)).cuda()
-
-
-def _rotate_dev(w, rows, depth, sel_idx, rot, extract=False, on=None, in_place=False):
-    """the _dev form on the world's engine and selectors, or on=(engine, selectors)"""
-    import torch
-    eng, sel = on or (w.eng, w.sel)
-    st = torch.cuda.current_stream().cuda_stream
-    count = len(rows)
-    d_in = _cuda(rows, np.uint32)
-    if extract:
-        d_out = torch.zeros((count, w.rp.n + 1), dtype=torch.int32, device="cuda")
-        eng.trgsw_rotate_extract_batch_dev(sel, d_in, depth, d_out, count, _cuda(sel_idx), rot, st)
-    else:
-        d_out = d_in if in_place else torch.zeros((count, 2, w.N), dtype=torch.int32, device="cuda")
-        eng.trgsw_rotate_batch_dev(sel, d_in, depth, d_out, count, _cuda(sel_idx), rot, st)
-    eng.sync(st)
-    return d_out.cpu().numpy().view(np.uint32)
+    return gk.memo(w.oracle_memo, (sel_idx, None if rot is None else np.asarray(rot, np.int32), rows, extract), lambda: np.stack(
+        [oracle_trgsw_rotate(orc, w.P, w.plan, w.sel_f, sel_idx[g], None if rot is None else [int(r) for r in rot], rows[g], extract, w.ksk) for g in range(len(rows))]))
 
 
 def _depth(w, d):
@@ -104,7 +65,7 @@ def test_every_word_equals_the_oracle_rotation(orc, world, d, count):
         got = w.eng.trgsw_rotate_batch(w.sel, rows, depth, sel_idx, rot)
         assert got.shape == (count, 2, w.N)
         assert np.array_equal(got, want), (sel_idx is None, rot is None, np.flatnonzero((got != want).any(axis=(1, 2)))[:8])
-        assert np.array_equal(_rotate_dev(w, rows, depth, sel_idx, rot), got), (sel_idx is None, rot is None)
+        assert np.array_equal(rotate_dev(w, rows, depth, sel_idx, rot), got), (sel_idx is None, rot is None)
 
 
 def _extract_case(w):
@@ -121,19 +82,19 @@ def test_extract_form_equals_the_oracle(orc, world):
         want = _oracle(orc, w, sel_idx, rot, rows, extract=True)
         got = w.eng.trgsw_rotate_extract_batch(w.sel, rows, depth, sel_idx, rot)
         assert got.shape == (count, w.rp.n + 1) and np.array_equal(got, want), rot is None
-        assert np.array_equal(_rotate_dev(w, rows, depth, sel_idx, rot, extract=True), got), rot is None
+        assert np.array_equal(rotate_dev(w, rows, depth, sel_idx, rot, extract=True), got), rot is None
 
 
 def test_extract_form_with_the_wave_per_sample_key_switch(orc, world, monkeypatch):
     """RTFHE_KS_MM_MIN=0: a context without the matrix form of the key-switching key runs k_key_switch_ext after the rotation; the same words."""
     w = world
     depth, count, sel_idx, rows = _extract_case(w)
-    e = _engine(w.R, w.rp, w.bk, w.ksk, monkeypatch, {"RTFHE_KS_MM_MIN": "0"})
+    e = gk.engine(w.R, w.rp, w.bk, w.ksk, monkeypatch, {"RTFHE_KS_MM_MIN": "0"})
     try:
         with e.selectors(w.sel_t) as sel:
             got = e.trgsw_rotate_extract_batch(sel, rows, depth, sel_idx, w.rot(depth))
             assert np.array_equal(got, _oracle(orc, w, sel_idx, w.rot(depth), rows, extract=True))
-            assert np.array_equal(_rotate_dev(w, rows, depth, sel_idx, w.rot(depth), extract=True, on=(e, sel)), got)
+            assert np.array_equal(rotate_dev(w, rows, depth, sel_idx, w.rot(depth), extract=True, on=(e, sel)), got)
     finally:
         e.close()
 
@@ -142,8 +103,8 @@ def test_in_place_gives_the_words_of_the_out_of_place_call(world):
     w = world
     depth, count = 5, 37
     sel_idx = np.random.default_rng(w.N + 33).integers(0, N_SEL, (count, depth)).astype(np.int32)
-    ref = _rotate_dev(w, w.rows, depth, sel_idx, w.rot(depth))
-    assert np.array_equal(_rotate_dev(w, w.rows, depth, sel_idx, w.rot(depth), in_place=True), ref)
+    ref = rotate_dev(w, w.rows, depth, sel_idx, w.rot(depth))
+    assert np.array_equal(rotate_dev(w, w.rows, depth, sel_idx, w.rot(depth), in_place=True), ref)
     assert np.array_equal(ref, w.eng.trgsw_rotate_batch(w.sel, w.rows, depth, sel_idx, w.rot(depth)))
 
 
@@ -154,8 +115,8 @@ def test_second_opinion_from_the_bootstraps_blind_rotation(world):
     w = world
     N, n = w.N, w.rp.n
     rng = np.random.default_rng(N + 34)
-    tlwe = np.tile(_random_words(rng, (1, n + 1)), (3, 1))
-    tlwe[:, n] = _random_words(rng, 3)
+    tlwe = np.tile(random_words(rng, (1, n + 1)), (3, 1))
+    tlwe[:, n] = random_words(rng, 3)
     sh = 32 - w.logn - 1
     bbar = (tlwe[:, n] >> np.uint32(sh)).astype(np.int64)
     rot = (((tlwe[0, :16].astype(np.uint64) + (1 << (sh - 1))) & 0xFFFFFFFF) >> sh).astype(np.int32)
@@ -193,8 +154,8 @@ def test_tree_then_rotation_is_a_fully_encrypted_lookup(world):
     d_row = torch.zeros((count, 2, w.N), dtype=torch.int32, device="cuda")
     d_out = torch.zeros((count, w.rp.n + 1), dtype=torch.int32, device="cuda")
     with w.eng.lut_encrypted(R.encrypt_lut(w.rp, w.key1, R.encode_msgs(msgs, 2), seed=0xF00 + w.N)) as table:
-        w.eng.cmux_tree_batch_dev(w.sel, table, 2, d_row, count, _cuda(hi), None, st)
-        w.eng.trgsw_rotate_extract_batch_dev(w.sel, d_row, w.logn, d_out, count, _cuda(lo), None, st)
+        w.eng.cmux_tree_batch_dev(w.sel, table, 2, d_row, count, gk.to_device(hi), None, st)
+        w.eng.trgsw_rotate_extract_batch_dev(w.sel, d_row, w.logn, d_out, count, gk.to_device(lo), None, st)
         w.eng.sync(st)
     got = R.decode_msgs(R.phases(w.rp, w.key0, d_out.cpu().numpy().view(np.uint32)), 2)
     assert np.array_equal(got, msgs.reshape(-1)[addrs])
@@ -231,14 +192,14 @@ def test_skipped_lookups_leave_their_rows_untouched(world, extract):
     for count in (1, 4, 10):
         rows = w.rows[:count]
         good, patterns = _bad_patterns(count, depth)
-        clean = _rotate_dev(w, rows, depth, good, w.rot(depth), extract=extract)
+        clean = rotate_dev(w, rows, depth, good, w.rot(depth), extract=extract)
         sentinel = (0xA5000000 + 0x1001 * np.arange(count + 8, dtype=np.uint32)[:, None] + np.arange(width, dtype=np.uint32)[None, :]).astype(np.uint32)
-        d_in = _cuda(rows, np.uint32)
+        d_in = gk.to_device(rows, np.uint32)
         for name, idx, skipped in patterns:
-            buf = _cuda(sentinel, np.uint32)
+            buf = gk.to_device(sentinel, np.uint32)
             d_out = buf[4:4 + count]                        # four guard rows on each side (the output stays 16-byte aligned)
             call = w.eng.trgsw_rotate_extract_batch_dev if extract else w.eng.trgsw_rotate_batch_dev
-            call(w.sel, d_in, depth, d_out, count, _cuda(idx), w.rot(depth), st)
+            call(w.sel, d_in, depth, d_out, count, gk.to_device(idx), w.rot(depth), st)
             with pytest.raises(R.RtfheError) as ei:
                 w.eng.sync(st)
             assert ei.value.code == R._ffi.ERR_INVALID, name
@@ -248,7 +209,7 @@ def test_skipped_lookups_leave_their_rows_untouched(world, extract):
             keep = np.setdiff1d(np.arange(count), skipped)
             want[4 + keep] = clean.reshape(count, width)[keep]
             assert np.array_equal(got, want), (count, name, np.flatnonzero((got != want).any(axis=1)))
-        assert np.array_equal(_rotate_dev(w, rows, depth, good, w.rot(depth), extract=extract), clean)
+        assert np.array_equal(rotate_dev(w, rows, depth, good, w.rot(depth), extract=extract), clean)
 
 
 def test_refusals_leave_the_engine_usable(world):
@@ -309,14 +270,14 @@ def test_graph_capture_without_a_prior_eager_call(world):
     depth, count = 5, 37
     rng = np.random.default_rng(w.N + 36)
     sel_idx = rng.integers(0, N_SEL, (count, depth)).astype(np.int32)
-    rows2 = _random_words(rng, (count, 2, w.N))
+    rows2 = random_words(rng, (count, 2, w.N))
     want = [w.eng.trgsw_rotate_batch(w.sel, r, depth, sel_idx, w.rot(depth)) for r in (w.rows, rows2)]
-    e = _engine(R, w.rp, w.bk, w.ksk)
+    e = gk.engine(R, w.rp, w.bk, w.ksk)
     try:
         with e.selectors(w.sel_t) as sel:
             s = torch.cuda.Stream()
-            d_idx = _cuda(sel_idx)
-            d_in = _cuda(w.rows, np.uint32)
+            d_idx = gk.to_device(sel_idx)
+            d_in = gk.to_device(w.rows, np.uint32)
             out = torch.zeros((count, 2, w.N), dtype=torch.int32, device="cuda")
             out_x = torch.zeros((count, w.rp.n + 1), dtype=torch.int32, device="cuda")
             torch.cuda.synchronize()
@@ -331,7 +292,7 @@ def test_graph_capture_without_a_prior_eager_call(world):
                         refused.append(err)
                 assert len(refused) == 1 and refused[0].code == R._ffi.ERR_STATE and "capture" in str(refused[0])
                 for rows, exp in zip((w.rows, rows2), want):
-                    d_in.copy_(_cuda(rows, np.uint32))
+                    d_in.copy_(gk.to_device(rows, np.uint32))
                     out.zero_()
                     g.replay()
                     torch.cuda.synchronize()

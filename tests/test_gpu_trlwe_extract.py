@@ -9,14 +9,10 @@ import numpy as np
 import pytest
 
 import extract_helpers as X
-from test_gpu_pbs import _engine
+import gpu_kit as gk
+from gpu_kit import FILL
 
 pytestmark = pytest.mark.gpu
-
-FILL = 0x5A5A5A5A
-CANARY = 64             # words behind every device output that must keep their bytes
-
-_WORLDS = {}
 
 
 @pytest.fixture(scope="module")
@@ -24,34 +20,24 @@ def worlds(orc):
     """per N, built on first use: keys from the product's keygen on an engine, the oracle's parameters, a memo of oracle words"""
     import rustfhe_amd as R
 
-    def get(N):
-        if N not in _WORLDS:
-            rp = R.Params(n=X.SMALL_N[N], N=N)
-            key0, key1, bk, ksk = R.keygen(rp, 0xE7 + N)
-            w = types.SimpleNamespace(R=R, N=N, rp=rp, key0=key0, key1=key1, bk=bk, ksk=ksk, P=orc.Params(n=rp.n, N=N), memo={})
-            w.eng = _engine(R, rp, bk, ksk)
-            _WORLDS[N] = w
-        return _WORLDS[N]
-    yield get
-    for w in _WORLDS.values():
-        w.eng.close()
-    _WORLDS.clear()
+    def build(N):
+        rp = R.Params(n=X.SMALL_N[N], N=N)
+        key0, key1, bk, ksk = R.keygen(rp, 0xE7 + N)
+        w = types.SimpleNamespace(R=R, N=N, rp=rp, key0=key0, key1=key1, bk=bk, ksk=ksk, P=orc.Params(n=rp.n, N=N), memo={})
+        w.eng = gk.engine(R, rp, bk, ksk)
+        return w
+    made = gk.Worlds(build, close=lambda w: w.eng.close())
+    yield made
+    made.close()
 
 
 def _case(orc, w, count, P, coef, stride=1, seed=0):
     """(x u32[count][2][N], the coefficients, the oracle's lvl1 and lvl0 words) of a shape: computed once per world, shared, read-only"""
-    key = (count, P, None if coef is None else tuple(coef), stride, seed)
-    if key not in w.memo:
+    def compute():
         coefs = X.coefficients(w.N, P, coef, stride)
         x = X.trlwe_inputs(1000 * count + 10 * P + seed, w.N, count, coefs)
-        x.setflags(write=False)
-        w.memo[key] = (x, coefs) + X.oracle_words(orc, w.P, w.ksk, x, coefs)
-    return w.memo[key]
-
-
-def _cuda(a):
-    import torch
-    return torch.from_numpy(np.array(a, dtype=np.uint32).view(np.int32)).cuda()      # (a copy: the shared inputs are read-only)
+        return (x, coefs) + X.oracle_words(orc, w.P, w.ksk, x, coefs)
+    return gk.memo(w.memo, (count, P, coef, stride, seed), compute)
 
 
 def _dev(eng, x, P, coef, stride, lvl1, stream=None):
@@ -60,13 +46,10 @@ def _dev(eng, x, P, coef, stride, lvl1, stream=None):
     count, N = x.shape[0], x.shape[2]
     words = (N if lvl1 else eng.p.n) + 1
     st = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    d_in = _cuda(x)
-    d_out = torch.full((count * P * words + CANARY,), FILL, dtype=torch.int32, device="cuda")
-    (eng.trlwe_extract_lvl1_batch_dev if lvl1 else eng.trlwe_extract_batch_dev)(d_in, P, d_out, count, coef, stride, st)
+    d_out = gk.guarded_out(count * P * words)
+    (eng.trlwe_extract_lvl1_batch_dev if lvl1 else eng.trlwe_extract_batch_dev)(gk.to_device(x, np.uint32), P, d_out, count, coef, stride, st)
     eng.sync(st)
-    out = d_out.cpu().numpy().view(np.uint32)
-    assert (out[count * P * words:] == FILL).all(), "words behind d_out were written"
-    return out[:count * P * words].reshape(count, P, words)
+    return gk.read_guarded(d_out, count * P * words).reshape(count, P, words)
 
 
 def _shapes():
@@ -141,7 +124,7 @@ def test_other_key_switch_route_and_other_backends_give_the_same_words(orc, worl
     w, R = worlds(N), worlds(N).R
     x, _, lvl1, lvl0 = _case(orc, w, 3, 5, [0, 1, N // 2, N - 2, N - 1])
     coef = [0, 1, N // 2, N - 2, N - 1]
-    e = _engine(R, w.rp, w.bk, w.ksk, monkeypatch, {"RTFHE_KS_MM_MIN": "0"})      # no matrix key: k_key_switch_ext
+    e = gk.engine(R, w.rp, w.bk, w.ksk, monkeypatch, {"RTFHE_KS_MM_MIN": "0"})      # no matrix key: k_key_switch_ext
     try:
         assert np.array_equal(e.trlwe_extract_batch(x, 5, coef), lvl0)
         assert np.array_equal(_dev(e, x, 5, coef, 1, False), lvl0)
@@ -149,7 +132,7 @@ def test_other_key_switch_route_and_other_backends_give_the_same_words(orc, worl
     finally:
         e.close()
     for backend in (R._ffi.BACKEND_NTT_EXACT, R._ffi.BACKEND_FFT_SPLIT_EXACT):
-        e = _engine(R, w.rp, w.bk, w.ksk)
+        e = gk.engine(R, w.rp, w.bk, w.ksk)
         try:
             e.set_backend(backend)
             assert np.array_equal(e.trlwe_extract_batch(x, 5, coef), lvl0)
@@ -204,7 +187,7 @@ def test_capture_and_replay(orc, worlds):
     a, _, a1, a0 = _case(orc, w, count, P, coef)
     b, _, b1, b0 = _case(orc, w, count, P, coef, seed=1)
     s = torch.cuda.Stream()
-    d_in = _cuda(a)
+    d_in = gk.to_device(a, np.uint32)
     out0 = torch.zeros((count, P, w.rp.n + 1), dtype=torch.int32, device="cuda")
     out1 = torch.zeros((count, P, N + 1), dtype=torch.int32, device="cuda")
     host = lambda t: t.cpu().numpy().view(np.uint32)      # noqa: E731
@@ -221,14 +204,14 @@ def test_capture_and_replay(orc, worlds):
             e.trlwe_extract_lvl1_batch_dev(d_in, P, out1, count, coef, 1, s.cuda_stream)
         assert len(refused) == 1 and refused[0].code == R._ffi.ERR_STATE and "capture" in str(refused[0]), refused
         for src, exp in ((a, a1), (b, b1)):
-            d_in.copy_(_cuda(src))
+            d_in.copy_(gk.to_device(src, np.uint32))
             out1.zero_()
             g1.replay()
             torch.cuda.synchronize()
             assert np.array_equal(host(out1), exp)
         assert not host(out0).any()
         # an eager call on s, then the same call captured on s: replays on rewritten inputs give the oracle's words (coef is baked in)
-        d_in.copy_(_cuda(a))
+        d_in.copy_(gk.to_device(a, np.uint32))
         e.trlwe_extract_batch_dev(d_in, P, out0, count, coef, 1, s.cuda_stream)
         e.sync(s.cuda_stream)
         assert np.array_equal(host(out0), a0)
@@ -236,7 +219,7 @@ def test_capture_and_replay(orc, worlds):
         with torch.cuda.graph(g0, stream=s):
             e.trlwe_extract_batch_dev(d_in, P, out0, count, coef, 1, s.cuda_stream)
         for src, exp in ((b, b0), (a, a0)):
-            d_in.copy_(_cuda(src))
+            d_in.copy_(gk.to_device(src, np.uint32))
             out0.zero_()
             g0.replay()
             torch.cuda.synchronize()
@@ -250,7 +233,7 @@ def test_refusals_leave_the_output_untouched(orc, worlds):
     w = worlds(N)
     R, e = w.R, w.eng
     x, _, lvl1, lvl0 = _case(orc, w, 3, 5, [0, 1, N // 2, N - 2, N - 1])
-    d_in = _cuda(x)
+    d_in = gk.to_device(x, np.uint32)
     d_out = torch.full((3 * N * (N + 1) // 64,), FILL, dtype=torch.int32, device="cuda")      # room for every call below that could run
     d_both = torch.full((4, 2, N), FILL, dtype=torch.int32, device="cuda")                    # rows and output in one allocation
     i32 = lambda *v: np.array(v, np.int32)                                                    # noqa: E731
@@ -280,7 +263,7 @@ def test_refusals_leave_the_output_untouched(orc, worlds):
     assert (d_out.cpu().numpy().view(np.uint32) == FILL).all() and (d_both.cpu().numpy().view(np.uint32) == FILL).all()
     assert w.eng.trlwe_extract_batch(x[:0], 5, [0, 1, 2, 3, 4]).shape == (0, 5, w.rp.n + 1)
     # d_out right behind the rows does not overlap them
-    d_both[:2].copy_(_cuda(x[:2]))
+    d_both[:2].copy_(gk.to_device(x[:2], np.uint32))
     e.trlwe_extract_lvl1_batch_dev(d_both[:2], 1, d_both[2], 2, [N - 1])
     e.sync()
     assert np.array_equal(d_both[2:].cpu().numpy().view(np.uint32).reshape(-1)[:2 * (N + 1)].reshape(2, 1, N + 1),
@@ -302,7 +285,7 @@ def test_refusals_leave_the_output_untouched(orc, worlds):
     finally:
         bare.close()
     # a two-entry context: the call runs on the primary device and gives the same words
-    multi = _engine(R, w.rp, w.bk, w.ksk, devices=[0, 0])
+    multi = gk.engine(R, w.rp, w.bk, w.ksk, devices=[0, 0])
     try:
         assert multi.device_count() == 2
         assert np.array_equal(multi.trlwe_extract_batch(x, 5, [0, 1, N // 2, N - 2, N - 1]), lvl0)
@@ -323,7 +306,7 @@ def test_a_ragged_tile_writes_nothing_past_its_samples(orc, worlds, N):
     assert np.array_equal(_dev(w.eng, x, 3, coef, 1, True), lvl1) and np.array_equal(_dev(w.eng, x, 3, coef, 1, False), lvl0)
     st = torch.cuda.current_stream().cuda_stream
     d_out = torch.full((111 * (N + 1),), FILL, dtype=torch.int32, device="cuda")
-    w.eng.trlwe_extract_lvl1_batch_dev(_cuda(x), 3, d_out, 6, coef, 1, st)        # 18 samples: one whole tile and 2 slots of the next
+    w.eng.trlwe_extract_lvl1_batch_dev(gk.to_device(x, np.uint32), 3, d_out, 6, coef, 1, st)        # 18 samples: one whole tile and 2 slots of the next
     w.eng.sync(st)
     out = d_out.cpu().numpy().view(np.uint32)
     assert np.array_equal(out[:18 * (N + 1)].reshape(6, 3, N + 1), lvl1[:6]) and (out[18 * (N + 1):] == FILL).all()
@@ -335,12 +318,12 @@ def test_launch_counts(orc, worlds, monkeypatch, route):
     import torch
     N = 1024
     w = worlds(N)
-    e = w.eng if route == "matrix" else _engine(w.R, w.rp, w.bk, w.ksk, monkeypatch, {"RTFHE_KS_MM_MIN": "0"})
+    e = w.eng if route == "matrix" else gk.engine(w.R, w.rp, w.bk, w.ksk, monkeypatch, {"RTFHE_KS_MM_MIN": "0"})
     try:
         st = torch.cuda.current_stream().cuda_stream
         for count, P, coef, stride in ((1, 1, [N - 1], 1), (2, 513, None, 1)):
             x, _, lvl1, lvl0 = _case(orc, w, count, P, coef, stride)
-            d_in = _cuda(x)
+            d_in = gk.to_device(x, np.uint32)
             for lvl1_form, want in ((False, lvl0), (True, lvl1)):
                 d_out = torch.zeros(want.shape, dtype=torch.int32, device="cuda")
                 e.timer_begin(st)

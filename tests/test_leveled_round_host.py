@@ -7,14 +7,9 @@ import pytest
 
 import orc as _orc_mod  # noqa: F401  (conftest puts tests/ on the path)
 import leveled_round_oracle as lo
-from test_cmux_net_host import oracle_cmux_net, three_of_five
-from test_cmux_tree_host import as_trlwe, oracle_cmux_tree
-from test_pbs_host import bk_fft
-from test_trgsw_rotate_host import oracle_trgsw_rotate, rotate_clear
-
-
-def _words(rng, shape):
-    return rng.integers(0, 1 << 32, shape, dtype=np.uint64).astype(np.uint32)
+from kit import random_words
+from leveled_oracle import as_trlwe, oracle_cmux_net, oracle_cmux_tree, oracle_trgsw_rotate, rotate_clear, three_of_five
+from pbs_oracle import bk_fft
 
 
 @pytest.mark.parametrize("N", [1024, 2048])
@@ -27,7 +22,7 @@ def test_reference_constants_give_the_oracles_tree_rotation_and_net(orc, N):
     plan = orc.Plan(N)
     keys = orc.Keys(p, 0x17 + N, plan=plan)
     rng = np.random.default_rng(N + 17)
-    tables = {"plain": as_trlwe(_words(rng, (8, N)), N), "encrypted": _words(rng, (8, 2, N))}
+    tables = {"plain": as_trlwe(random_words(rng, (8, N)), N), "encrypted": random_words(rng, (8, 2, N))}
     for depth in (2, 3):
         sel_idx = [int(k) for k in rng.integers(0, p.n, depth)]
         rot = [int(r) for r in rng.integers(0, 2 * N, depth)]

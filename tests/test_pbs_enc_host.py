@@ -1,6 +1,6 @@
 """CPU: encrypted tables for programmable bootstrapping (include/rtfhe.h, rtfhe_lut_create_encrypted) without a GPU -- the host TRLWE
 encryption of test polynomials (rtfhe_trlwe_encrypt_torus[_deterministic], rtfhe_trlwe_phase), the PBS from an encrypted table restated
-with the oracle's own building blocks (oracle_pbs_enc, which tests/test_gpu_pbs_enc.py compares the device's words with) and the entry
+with the oracle's own building blocks (tests/pbs_oracle.py: oracle_pbs_enc, which tests/test_gpu_pbs_enc.py compares the device's words with) and the entry
 points' argument checks."""
 import ctypes as C
 
@@ -8,40 +8,8 @@ import numpy as np
 import pytest
 
 import orc as _orc_mod  # noqa: F401  (conftest puts tests/ on the path)
-from test_pbs_host import U32, bk_fft
-from test_pbs_many_host import oracle_pbs_many
-
-
-def oracle_pbs_enc(orc, p, plan, bk_f, ksk, trlwe, t, n_out):
-    """rtfhe.h's PBS from an encrypted table, word for word with the reference's arithmetic: oracle_pbs_many with the accumulator started
-    from both halves of the table row, acc = X^{-bbar} (tb, ta).  trlwe: u32[2][N] (b then a).  u32[n_out][n+1]."""
-    L = orc.lib()
-    N, n = p.N, p.n
-    lt = int(n_out).bit_length() - 1
-    assert n_out == 1 << lt
-    s = 32 - p.nbit - 1 + lt
-    t = np.ascontiguousarray(t, np.uint32)
-    trlwe = np.ascontiguousarray(trlwe, np.uint32).reshape(2, N)
-    bbar = (int(t[n]) >> s) << lt
-    acc = np.zeros(2 * N, np.uint32)
-    acc[:N] = orc.rotate(np.ascontiguousarray(trlwe[0]), -bbar)
-    acc[N:] = orc.rotate(np.ascontiguousarray(trlwe[1]), -bbar)
-    rot = np.empty(2 * N, np.uint32)
-    trgsw = 2 * 2 * p.l * N
-    for i in range(n):
-        abar = ((((int(t[i]) + (1 << (s - 1))) & U32) >> s) << lt)
-        rot[:N] = orc.rotate(acc[:N], abar)
-        rot[N:] = orc.rotate(acc[N:], abar)
-        bki = np.ascontiguousarray(bk_f[i * trgsw:(i + 1) * trgsw])
-        L.orc_cmux(C.byref(p), plan.h, bki.ctypes.data_as(C.POINTER(C.c_double)), None,
-                   rot.ctypes.data_as(C.POINTER(C.c_uint32)), acc.ctypes.data_as(C.POINTER(C.c_uint32)),
-                   acc.ctypes.data_as(C.POINTER(C.c_uint32)))
-    return np.stack([orc.key_switch(p, ksk, orc.sample_extract(p, acc, j)) for j in range(n_out)])
-
-
-def _torus_dist(a, b):
-    d = (np.asarray(a, np.uint32) - np.asarray(b, np.uint32)).astype(np.uint32).view(np.int32).astype(np.int64)
-    return np.abs(d)
+from kit import torus_dist_lsb
+from pbs_oracle import bk_fft, oracle_pbs_enc, oracle_pbs_many
 
 
 @pytest.mark.parametrize("N", [1024, 2048])
@@ -57,11 +25,11 @@ def test_encrypt_then_phase(N):
         assert ct.shape == (64, 2, N) and ct.dtype == np.uint32
         ph = R.trlwe_phase(p, key1, ct)
         assert ph.shape == (64, N)
-        assert _torus_dist(ph, mu).max() < 1 << 12, seed          # 2^-20 of the torus = 2^12 of 2^32
+        assert torus_dist_lsb(ph, mu).max() < 1 << 12, seed          # 2^-20 of the torus = 2^12 of 2^32
         assert np.any(ph != mu)                                  # there is noise
         assert not np.array_equal(ct[:, 1], np.zeros_like(ct[:, 1]))   # and a random mask
     # the mask is uniform: its words are not small
-    assert np.mean(_torus_dist(ct[:, 1], 0) > 1 << 28) > 0.8
+    assert np.mean(torus_dist_lsb(ct[:, 1], 0) > 1 << 28) > 0.8
 
 
 def test_trivial_encryption_has_the_table_as_phase():

@@ -1,60 +1,13 @@
 """CPU: programmable bootstrapping (include/rtfhe.h, rtfhe_pbs_batch) without a GPU -- the encoder of rustfhe_amd.pbs, the PBS restated with
 the oracle's own building blocks (negacyclic rotation, CMUX, sample extract, key switch), torus encryption and the entry points' argument checks.
-oracle_pbs below is also what tests/test_gpu_pbs.py compares the device's words with."""
+oracle_pbs (tests/pbs_oracle.py) is also what tests/test_gpu_pbs.py compares the device's words with."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import orc as _orc_mod  # noqa: F401  (conftest puts tests/ on the path)
-
-U32 = 0xFFFFFFFF
-
-
-def oracle_pbs(orc, p, plan, bk_f, ksk, tv, t):
-    """rtfhe.h's PBS semantics, word for word with the reference's arithmetic: acc = X^{-bbar} (tv, 0); n CMUX steps; extract; key switch."""
-    L = orc.lib()
-    N, n = p.N, p.n
-    sh = 32 - p.nbit - 1
-    t = np.ascontiguousarray(t, np.uint32)
-    bbar = int(t[n]) >> sh
-    acc = np.zeros(2 * N, np.uint32)
-    acc[:N] = orc.rotate(np.ascontiguousarray(tv, np.uint32), -bbar)
-    rot = np.empty(2 * N, np.uint32)
-    trgsw = 2 * 2 * p.l * N
-    for i in range(n):
-        abar = ((int(t[i]) + (1 << (sh - 1))) & U32) >> sh
-        rot[:N] = orc.rotate(acc[:N], abar)
-        rot[N:] = orc.rotate(acc[N:], abar)
-        bki = np.ascontiguousarray(bk_f[i * trgsw:(i + 1) * trgsw])
-        L.orc_cmux(C.byref(p), plan.h, bki.ctypes.data_as(C.POINTER(C.c_double)), None,
-                   rot.ctypes.data_as(C.POINTER(C.c_uint32)), acc.ctypes.data_as(C.POINTER(C.c_uint32)),
-                   acc.ctypes.data_as(C.POINTER(C.c_uint32)))
-    return orc.key_switch(p, ksk, orc.sample_extract(p, acc))
-
-
-def bk_fft(orc, p, plan, bk_t):
-    bk_f = np.empty(bk_t.size, np.float64)
-    orc.lib().orc_trgsw_to_fft(plan.h, np.ascontiguousarray(bk_t, np.uint32).ctypes.data_as(C.POINTER(C.c_uint32)),
-                               bk_f.ctypes.data_as(C.POINTER(C.c_double)), bk_t.size // p.N)
-    return bk_f
-
-
-FUNCS = {
-    "identity": lambda m, P: m,
-    "square": lambda m, P: (m * m) % (1 << P),
-    "succ": lambda m, P: (m + 1) % (1 << P),
-    "msb": lambda m, P: int(m >= (1 << (P - 1))),
-    "neg": lambda m, P: (-m) % (1 << P),
-}
-
-
-def coef0_after_rotation(tv, k):
-    """coefficient 0 of X^{-k} * tv, k in [0, 2N): the negacyclic extension"""
-    N = len(tv)
-    k %= 2 * N
-    return int(tv[k]) if k < N else (-int(tv[k - N])) & U32
-
+from pbs_oracle import FUNCS, U32, bk_fft, coef0_after_rotation, oracle_pbs
 
 @pytest.mark.parametrize("N", [1024, 2048])
 @pytest.mark.parametrize("P", [1, 2, 3, 4])

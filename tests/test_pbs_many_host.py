@@ -1,5 +1,5 @@
 """CPU: many-LUT programmable bootstrapping (include/rtfhe.h, rtfhe_pbs_many_batch) without a GPU -- the interleaving encoder
-rustfhe_amd.many_lut_polynomial, the many-LUT PBS restated with the oracle's own building blocks (oracle_pbs_many, which
+rustfhe_amd.many_lut_polynomial, the many-LUT PBS restated with the oracle's own building blocks (tests/pbs_oracle.py: oracle_pbs_many, which
 tests/test_gpu_pbs_many.py compares the device's words with) and the entry points' argument checks."""
 import ctypes as C
 
@@ -7,32 +7,7 @@ import numpy as np
 import pytest
 
 import orc as _orc_mod  # noqa: F401  (conftest puts tests/ on the path)
-from test_pbs_host import FUNCS, U32, bk_fft, coef0_after_rotation, oracle_pbs
-
-
-def oracle_pbs_many(orc, p, plan, bk_f, ksk, tv, t, n_out):
-    """rtfhe.h's many-LUT PBS semantics, word for word with the reference's arithmetic: the mod switch at SH + log2(n_out) scaled back by n_out,
-    acc = X^{-bbar} (tv, 0); n CMUX steps; sample extract at 0 .. n_out - 1; key switch.  u32[n_out][n+1]."""
-    L = orc.lib()
-    N, n = p.N, p.n
-    lt = int(n_out).bit_length() - 1
-    assert n_out == 1 << lt
-    s = 32 - p.nbit - 1 + lt
-    t = np.ascontiguousarray(t, np.uint32)
-    bbar = (int(t[n]) >> s) << lt
-    acc = np.zeros(2 * N, np.uint32)
-    acc[:N] = orc.rotate(np.ascontiguousarray(tv, np.uint32), -bbar)
-    rot = np.empty(2 * N, np.uint32)
-    trgsw = 2 * 2 * p.l * N
-    for i in range(n):
-        abar = ((((int(t[i]) + (1 << (s - 1))) & U32) >> s) << lt)
-        rot[:N] = orc.rotate(acc[:N], abar)
-        rot[N:] = orc.rotate(acc[N:], abar)
-        bki = np.ascontiguousarray(bk_f[i * trgsw:(i + 1) * trgsw])
-        L.orc_cmux(C.byref(p), plan.h, bki.ctypes.data_as(C.POINTER(C.c_double)), None,
-                   rot.ctypes.data_as(C.POINTER(C.c_uint32)), acc.ctypes.data_as(C.POINTER(C.c_uint32)),
-                   acc.ctypes.data_as(C.POINTER(C.c_uint32)))
-    return np.stack([orc.key_switch(p, ksk, orc.sample_extract(p, acc, j)) for j in range(n_out)])
+from pbs_oracle import FUNCS, bk_fft, coef0_after_rotation, oracle_pbs, oracle_pbs_many
 
 
 @pytest.mark.parametrize("N", [1024, 2048])

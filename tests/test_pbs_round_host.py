@@ -8,14 +8,10 @@ import pytest
 
 import orc as _orc_mod  # noqa: F401  (conftest puts tests/ on the path)
 import round_oracle as ro
-from test_pbs_host import oracle_pbs
-from test_pbs_many_host import oracle_pbs_many
+from kit import random_words
+from pbs_oracle import oracle_pbs, oracle_pbs_many
 
 U32 = 0xFFFFFFFF
-
-
-def _words(rng, shape):
-    return rng.integers(0, 1 << 32, shape, dtype=np.uint64).astype(np.uint32)
 
 
 def test_constants():
@@ -34,7 +30,7 @@ def test_reference_constants_give_the_oracles_product_and_cmux(orc, N):
     trgsw = p.trgsw_words
     for i in range(p.n):
         bki = np.ascontiguousarray(keys.bk_f[i * trgsw:(i + 1) * trgsw])
-        x, y = _words(rng, 2 * N), _words(rng, 2 * N)
+        x, y = random_words(rng, 2 * N), random_words(rng, 2 * N)
         assert np.array_equal(ro.external_product(p, plan, bki, x, ma, mx), orc.external_product(p, plan, bki, None, x))
         exp = np.empty(2 * N, np.uint32)
         orc.lib().orc_cmux(C.byref(p), plan.h, bki.ctypes.data_as(C.POINTER(C.c_double)), None, x.ctypes.data_as(C.POINTER(C.c_uint32)),
@@ -52,9 +48,9 @@ def test_reference_mode_pbs_is_oracle_pbs(orc):
     keys = orc.Keys(p, 0x51, plan=plan)
     rng = np.random.default_rng(24)
     for _ in range(2):
-        tv, t = _words(rng, p.N), _words(rng, p.n + 1)
+        tv, t = random_words(rng, p.N), random_words(rng, p.n + 1)
         assert np.array_equal(ro.pbs(p, plan, keys.bk_f, keys.ksk, tv, t, ro.REFERENCE), oracle_pbs(orc, p, plan, keys.bk_f, keys.ksk, tv, t))
-    tv, t = _words(rng, p.N), _words(rng, p.n + 1)
+    tv, t = random_words(rng, p.N), random_words(rng, p.n + 1)
     assert np.array_equal(ro.pbs_many(p, plan, keys.bk_f, keys.ksk, tv, t, 4, ro.REFERENCE), oracle_pbs_many(orc, p, plan, keys.bk_f, keys.ksk, tv, t, 4))
     assert not np.array_equal(ro.pbs(p, plan, keys.bk_f, keys.ksk, tv, t, ro.ROUNDED), ro.pbs(p, plan, keys.bk_f, keys.ksk, tv, t, ro.REFERENCE))
 
@@ -70,7 +66,7 @@ def _decomp_error(x, d):
 
 def test_rounded_digits_are_balanced_and_round_to_nearest():
     rng = np.random.default_rng(0xD161)
-    x = np.concatenate([_words(rng, 1 << 16), np.array(EDGES, np.uint32)])
+    x = np.concatenate([random_words(rng, 1 << 16), np.array(EDGES, np.uint32)])
     ma, mx = ro.constants(3, 6, ro.ROUNDED)
     d = ro.digits(x, 3, 6, ma, mx)
     assert d.min() >= -32 and d.max() <= 31

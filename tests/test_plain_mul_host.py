@@ -1,7 +1,6 @@
 """CPU: the exact TRLWE x plain-polynomial product (include/rtfhe.h: rtfhe_trlwe_mul_plain_batch) without a device -- the numpy oracle the GPU
 tests compare every word to against the definition in Python integers, the dense-layer layout against W @ x, the exactness domain against the
 split-FFT backend's error model, and the parameter arithmetic of examples/encrypted_dense_layer.py."""
-import importlib.util
 import os
 import sys
 
@@ -9,8 +8,7 @@ import numpy as np
 import pytest
 
 import plain_mul_oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kit import ROOT, load_example
 
 
 @pytest.mark.parametrize("N", [16, 1024, 2048])
@@ -94,16 +92,9 @@ def test_the_domain_is_the_split_fft_backends_bound():
     assert "#define RTFHE_PLAIN_L1_PER_N %d" % O.L1_PER_N in hdr and "#define RTFHE_PLAIN_K_MAX %d" % O.K_MAX in hdr
 
 
-def _example():
-    spec = importlib.util.spec_from_file_location("encrypted_dense_layer", os.path.join(ROOT, "examples", "encrypted_dense_layer.py"))
-    ex = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ex)
-    return ex
-
-
 def test_example_parameter_arithmetic():
     import rustfhe_amd as R
-    ex = _example()
+    ex = load_example("encrypted_dense_layer")
     p = R.Params()
     assert int(R.encode_msgs([1], ex.MSG_BITS)[0]) == ex.UNIT == 1 << 28 and p.N % ex.D == 0 and ex.M <= p.N // ex.D
     rng = np.random.default_rng(11)

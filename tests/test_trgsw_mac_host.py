@@ -4,7 +4,6 @@ integer polynomials against the bits' and against its phases, the meaning of a s
 arithmetic and the GPU meaning test's inputs), the range test's inputs against the narrow conversion, and the entry points' refusals that need
 no GPU."""
 import ctypes as C
-import importlib.util
 import os
 
 import numpy as np
@@ -12,12 +11,7 @@ import pytest
 
 import round_oracle as ro
 import trgsw_mac_oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _words(rng, shape):
-    return rng.integers(0, 1 << 32, shape, dtype=np.uint64).astype(np.uint32)
+from kit import ROOT, load_example, random_words
 
 
 @pytest.mark.parametrize("N", [1024, 2048])
@@ -45,7 +39,7 @@ def test_one_term_is_the_external_product(orc, N):
         two = O.mac(p, plan, keys.bk_f, [[2, 0]], x, [[0, 1]], None, mode)
         apart = got[0] + got[1]
         assert not np.array_equal(two[0], apart) and np.abs((two[0] - apart).view(np.int32)).max() <= 2
-        acc = _words(np.random.default_rng(N), (1, 2, N))
+        acc = random_words(np.random.default_rng(N), (1, 2, N))
         assert np.array_equal(O.mac(p, plan, keys.bk_f, [[2, 0]], x, [[0, 1]], acc, mode), two + acc)
     assert not np.array_equal(O.mac(p, plan, keys.bk_f, s_idx, x, None, None, O.REFERENCE), O.mac(p, plan, keys.bk_f, s_idx, x, None, None, O.ROUNDED))
 
@@ -114,13 +108,6 @@ def test_encrypt_trgsw_polys_phases(N):
     assert worst <= 6 * 2.0 ** -25, worst
 
 
-def _example():
-    spec = importlib.util.spec_from_file_location("private_dense_layer", os.path.join(ROOT, "examples", "private_dense_layer.py"))
-    ex = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ex)
-    return ex
-
-
 def test_meaning_of_the_sum_on_the_cpu(orc, capsys):
     """Rounded mode, through the restatement.  (a) The inputs of the GPU meaning test (trgsw_mac_oracle.meaning_world): K = 4 encrypted ternary
     polynomials times four fresh rows per sample; every coefficient of the phase is sum_k mu_k * m_k within
@@ -140,7 +127,7 @@ def test_meaning_of_the_sum_on_the_cpu(orc, capsys):
     ratios = [float(np.abs(O.torus_err(ph[g], m.want[g])).max()) / m.bound[g] for g in range(m.COUNT)]
     lines = ["meaning world: bound %.2e, max error / bound per sample %s" % (m.bound[0], ["%.2f" % r for r in ratios])]
 
-    ex = _example()
+    ex = load_example("private_dense_layer")
     rp = R.Params(n=40, N=1024)
     _, key1, _, _ = R.keygen(rp, 0x3AD0, want_bk=False, want_ksk=False)
     rng = np.random.default_rng(0x3AD1)

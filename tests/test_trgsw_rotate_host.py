@@ -1,5 +1,5 @@
 """CPU: TRGSW blind rotation (include/rtfhe.h, rtfhe_trgsw_rotate_batch) without a GPU -- the rotation restated with the oracle's own building
-blocks (oracle_trgsw_rotate, which tests/test_gpu_trgsw_rotate.py compares the device's words with), what it means with keys and selectors
+blocks (tests/leveled_oracle.py: oracle_trgsw_rotate, which tests/test_gpu_trgsw_rotate.py compares the device's words with), what it means with keys and selectors
 the product generated, and the entry points' refusal of a null context."""
 import ctypes as C
 
@@ -7,50 +7,9 @@ import numpy as np
 import pytest
 
 import orc as _orc_mod  # noqa: F401  (conftest puts tests/ on the path)
-from test_cmux_tree_host import _torus_dist, as_trlwe
-from test_pbs_host import bk_fft
-
-U32P = C.POINTER(C.c_uint32)
-
-
-def default_rot(N, depth):
-    """rot = NULL of rtfhe.h: X^{-2^k}"""
-    return [2 * N - (1 << k) for k in range(depth)]
-
-
-def oracle_trgsw_rotate(orc, p, plan, sel_f, sel_idx, rot, trlwe, extract=False, ksk=None):
-    """rtfhe.h's TRGSW rotation, word for word with the reference's arithmetic.  sel_f: the selectors as FrrSeries (orc_trgsw_to_fft of
-    u32[n_sel][2][2l][N]); sel_idx: the selector numbers of this lookup, step 0 first; rot: one exponent per step (None: default_rot); trlwe:
-    u32[2][N].  Step k: orc_rotate_u32 by rot[k] on both polynomials, then acc = orc_cmux(S_k, rotated, acc).  Returns the result u32[2][N], or
-    with extract (and ksk) orc_key_switch(orc_sample_extract(result, 0)), u32[n+1]."""
-    L = orc.lib()
-    N = p.N
-    trgsw = 2 * 2 * p.l * N
-    if rot is None:
-        rot = default_rot(N, len(sel_idx))
-    assert len(rot) == len(sel_idx)
-    acc = np.ascontiguousarray(trlwe, np.uint32).reshape(2 * N).copy()
-    for k, r in zip(sel_idx, rot):
-        S = np.ascontiguousarray(sel_f[int(k) * trgsw:(int(k) + 1) * trgsw])
-        rotated = np.empty(2 * N, np.uint32)
-        for h in range(2):
-            L.orc_rotate_u32(N, acc[h * N:].ctypes.data_as(U32P), int(r), rotated[h * N:].ctypes.data_as(U32P))
-        out = np.empty(2 * N, np.uint32)
-        L.orc_cmux(C.byref(p), plan.h, S.ctypes.data_as(C.POINTER(C.c_double)), None, rotated.ctypes.data_as(U32P), acc.ctypes.data_as(U32P),
-                   out.ctypes.data_as(U32P))
-        acc = out
-    if not extract:
-        return acc.reshape(2, N)
-    return orc.key_switch(p, ksk, orc.sample_extract(p, acc, 0))
-
-
-def rotate_clear(row, addr):
-    """X^{-addr} * row, negacyclic, on torus words: coefficient c is row[c + addr], negated once the index wraps past N"""
-    row = np.asarray(row, np.uint32)
-    N = row.size
-    e = np.arange(N) + int(addr)
-    return np.where(e >= N, (0 - row[e % N].astype(np.int64)) & 0xFFFFFFFF, row[e % N]).astype(np.uint32)
-
+from kit import torus_dist
+from leveled_oracle import as_trlwe, oracle_trgsw_rotate, rotate_clear
+from pbs_oracle import bk_fft
 
 @pytest.mark.parametrize("N", [1024, 2048])
 def test_oracle_rotation_brings_the_addressed_coefficient_to_the_front(orc, N, capsys):
@@ -81,7 +40,7 @@ def test_oracle_rotation_brings_the_addressed_coefficient_to_the_front(orc, N, c
             dec = R.decode_msgs(ph, 2)
             assert np.array_equal(dec, R.decode_msgs(want, 2)), (kind, addr)
             assert dec[0] == msgs[addr], (kind, addr)
-            worst[kind] = max(worst.get(kind, 0.0), float(_torus_dist(ph, want).max()))
+            worst[kind] = max(worst.get(kind, 0.0), float(torus_dist(ph, want).max()))
     with capsys.disabled():
         print("\noracle TRGSW rotation, N = %d, depth %d: largest torus distance from X^-addr * row %s" % (N, depth, {k: round(v, 5) for k, v in worst.items()}))
     for kind, w in worst.items():

@@ -2,16 +2,12 @@
 sample_extract_index that the GPU tests' inputs are planned with against the oracle, the planted edge words' sides, the parameter arithmetic of
 examples/histogram_threshold.py, and the seeds of the GPU suite's meaning test: on the oracle's own words every entry decodes, so the GPU test,
 which asserts those words, cannot fail on noise."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 
 import extract_helpers as X
 import pack_oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kit import load_example
 
 
 @pytest.mark.parametrize("N", [16, 1024, 2048])
@@ -49,16 +45,9 @@ def test_planted_edges_land_on_both_sides():
         assert X.edge_slots(N, [N - 1])[1] == [] and len(X.edge_slots(N, [N - 1])[0]) == len(X.EDGES)
 
 
-def _example():
-    spec = importlib.util.spec_from_file_location("histogram_threshold", os.path.join(ROOT, "examples", "histogram_threshold.py"))
-    ex = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ex)
-    return ex
-
-
 def test_example_parameter_arithmetic():
     import rustfhe_amd as R
-    ex = _example()
+    ex = load_example("histogram_threshold")
     p = R.Params()
     # the counting unit is encode_msgs(1, 3) = 2^-4; 7 of them keep the padding bit clear; one slot per row, at N/2
     assert int(R.encode_msgs([1], ex.MSG_BITS)[0]) == 1 << (32 - ex.UNIT_BITS) == 1 << 28

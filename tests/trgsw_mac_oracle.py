@@ -14,6 +14,7 @@ import numpy as np
 
 import orc
 import round_oracle as ro
+from kit import torus_err  # noqa: F401
 from round_oracle import REFERENCE, ROUNDED  # noqa: F401
 
 _f64p, _u32p, _i32p = C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
@@ -144,9 +145,3 @@ def meaning_world(R):
                        for g in range(m.COUNT)])
     m.bound = [noise_bound(N, [float((m.mu[g * m.K + k].astype(np.int64) ** 2).sum()) for k in range(m.K)]) for g in range(m.COUNT)]
     return m
-
-
-def torus_err(a, b):
-    """signed torus distance a - b in [-1/2, 1/2)"""
-    d = (np.asarray(a, np.uint32) - np.asarray(b, np.uint32)).astype(np.uint32).view(np.int32).astype(np.float64)
-    return d / 2.0 ** 32
