@@ -134,12 +134,9 @@
         // the loop and then spills them (each is one VALU op to recompute)
         int ln = lane;
         asm volatile("" : "+v"(ln));
+        // u[mm] = ((rotated_coef(poly, ln + 64 mm, r) - own[mm]) + MA) ^ MX, block and sign from a wave-uniform dispatch on r >> 6
         uint32_t u[2 * R];
-#pragma unroll
-        for (int mm = 0; mm < 2 * R; mm++) {
-            const int c = ln + 64 * mm;
-            u[mm] = ((rotated_coef<LOGN>(poly, c, r) - own[mm]) + MA) ^ MX;
-        }
+        rotated_gather(u, own, poly, ln, r, MA, MX);
         PAIR_STAMP(0);
         double xr[L][R], xi[L][R];
 #pragma unroll

@@ -112,11 +112,8 @@
         asm volatile("" : "+v"(ln));
         uint32_t own[2 * R], u[2 * R];
 #pragma unroll
-        for (int mm = 0; mm < 2 * R; mm++) {
-            const int c = ln + 64 * mm;
-            own[mm] = poly[c];
-            u[mm] = ((rotated_coef<LOGN>(poly, c, r) - own[mm]) + MA) ^ MX;
-        }
+        for (int mm = 0; mm < 2 * R; mm++) own[mm] = poly[ln + 64 * mm];
+        rotated_gather(u, own, poly, ln, r, MA, MX);      // the pair kernel's gather (rtfhe_body_pair.hpp)
         double xr[L][R], xi[L][R];
 #pragma unroll
         for (int jj = 0; jj < L; jj++) {

@@ -656,4 +656,46 @@ __device__ __forceinline__ uint32_t rotated_coef(const uint32_t* __restrict__ p,
     return (e >> LOGN) ? (0u - v) : v;      // (a branch-free (v ^ s) - s form measured 0.6 % slower in the pair kernel)
 }
 
+// The rotated gather of a whole wave at N = 1024, split into a coarse and a fine part: u[mm] = ((rotated_coef<10>(p, ln + 64 mm, r) - own[mm]) + MA) ^ MX
+// for mm = 0..15, bit for bit, without per-word index or sign arithmetic.  A lane's 16 words are 64 coefficients apart, so with r = 64 q + s and
+// d = ln - s the word of register mm comes from block (mm - q) & 15 at position d & 63 -- one block lower where d < 0 -- and is negated when
+// q >> 4 differs from (mm < (q & 15)).  Only the register with mm == (q & 15) can wrap from block 0 to block 15, which flips its sign: that one
+// word has its own address and sign (base2, sx).  Everything that depends on q alone is wave-uniform: case Q of the caller's dispatch on q & 15
+// reads block `blk` at an immediate offset and takes its sign from a scalar.
+//   s, sx : the sign as 0 / ~0 (s uniform: -(q >> 4); sx: s ^ (d < 0 ? ~0 : 0));   p1, p2: p + byte offsets base, base2 (see rotated_gather)
+template <int Q>
+__device__ __forceinline__ void rotated_gather_case(uint32_t (&u)[16], const uint32_t (&own)[16], const uint32_t* __restrict__ p1,
+                                                    const uint32_t* __restrict__ p2, uint32_t s, uint32_t sx, uint32_t ma, uint32_t mx) {
+    const uint32_t k0 = ma - s, k1 = ma - ~s;       // scalar
+#pragma unroll
+    for (int mm = 0; mm < 16; mm++) {
+        const int blk = (mm - Q) & 15;
+        if (blk == 0) {
+            u[mm] = ((p2[0] ^ sx) + ((ma - sx) - own[mm])) ^ mx;
+        } else if (mm < Q) {
+            u[mm] = ((p1[64 * blk] ^ ~s) + (k1 - own[mm])) ^ mx;
+        } else {
+            u[mm] = ((p1[64 * blk] ^ s) + (k0 - own[mm])) ^ mx;
+        }
+    }
+}
+// r: the wave-uniform rotation amount, 0 <= r < 2048; ln: the lane id
+__device__ __forceinline__ void rotated_gather(uint32_t (&u)[16], const uint32_t (&own)[16], const uint32_t* __restrict__ p, int ln, int r,
+                                               uint32_t ma, uint32_t mx) {
+    const int q = r >> 6, d = ln - (r & 63);
+    const bool neg = d < 0;
+    const int base = 4 * (d & 63) - (neg ? 256 : 0);
+    const uint32_t* p1 = reinterpret_cast<const uint32_t*>(reinterpret_cast<const unsigned char*>(p) + base);
+    const uint32_t* p2 = reinterpret_cast<const uint32_t*>(reinterpret_cast<const unsigned char*>(p) + base + (neg ? 4096 : 0));
+    const uint32_t s = 0u - (uint32_t)(q >> 4), sx = s ^ (neg ? ~0u : 0u);
+    switch (q & 15) {
+#define RTFHE_GATHER_CASE(Q) case Q: rotated_gather_case<Q>(u, own, p1, p2, s, sx, ma, mx); break;
+        RTFHE_GATHER_CASE(0) RTFHE_GATHER_CASE(1) RTFHE_GATHER_CASE(2) RTFHE_GATHER_CASE(3)
+        RTFHE_GATHER_CASE(4) RTFHE_GATHER_CASE(5) RTFHE_GATHER_CASE(6) RTFHE_GATHER_CASE(7)
+        RTFHE_GATHER_CASE(8) RTFHE_GATHER_CASE(9) RTFHE_GATHER_CASE(10) RTFHE_GATHER_CASE(11)
+        RTFHE_GATHER_CASE(12) RTFHE_GATHER_CASE(13) RTFHE_GATHER_CASE(14) RTFHE_GATHER_CASE(15)
+#undef RTFHE_GATHER_CASE
+    }
+}
+
 }  // namespace rtfhe

@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """A/B of several builds of librtfhe_hip.so in ONE process, interleaved rounds: prints per-build median/min launch time
 of a NAND batch and whether all outputs agree.  usage: ab_libs.py gates rounds lib1.so lib2.so ...  (RTFHE_FORCE_WAVES etc. apply to all;
-an argument of the form lib.so:KEY=VAL[:KEY2=VAL2] sets those environment variables around that build's context creation only)"""
+an argument of the form lib.so:KEY=VAL[:KEY2=VAL2] sets those environment variables around that build's context creation only).
+One sample is the mean of AB_LAUNCHES launches (default 3; 1: every launch is a sample); the first round is untimed, AB_WARMUP (default 1)
+rounds in all.  Each build's line also gives mean and standard deviation over its samples, of the whole launch and of the bootstrap kernel
+alone (launch minus batch key switch); with two or more builds a last line gives each build's bootstrap mean against the first one's, with
+the standard error of the difference."""
 import ctypes as C, json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,15 +45,24 @@ for spec in libs:
     for kv in envs:
         del os.environ[kv.split("=")[0]]
 times, ks_times = [[] for _ in libs], [[] for _ in libs]
-for r in range(rounds + 1):
+LAUNCHES, WARMUP = int(os.environ.get("AB_LAUNCHES", "3")), int(os.environ.get("AB_WARMUP", "1"))
+for r in range(rounds + WARMUP):
     for k, e in enumerate(engines):
         e.timer_begin(st)
-        for _ in range(3): e.gate_batch_dev(R.NAND, d0, d1, outs[k], G, st)
+        for _ in range(LAUNCHES): e.gate_batch_dev(R.NAND, d0, d1, outs[k], G, st)
         ms, ks_ms, n = e.timer_end_detail(st)
-        if r: times[k].append(ms / 3); ks_times[k].append(ks_ms / 3)
+        if r >= WARMUP: times[k].append(ms / LAUNCHES); ks_times[k].append(ks_ms / LAUNCHES)
 same = all(bool(torch.equal(outs[0], o)) for o in outs[1:])
+boot = [np.array(times[k]) - np.array(ks_times[k]) for k in range(len(libs))]
 for k, path in enumerate(libs):
     t = np.array(times[k])
     print(json.dumps({"lib": names[k], "gates": G, "median_ms": round(float(np.median(t)), 4), "min_ms": round(float(t.min()), 4),
                       "gates_per_s_median": round(G / np.median(t) * 1e3, 1), "key_switch_ms_median": round(float(np.median(ks_times[k])), 4),
+                      "samples": len(t), "launches_per_sample": LAUNCHES, "mean_ms": round(float(t.mean()), 5), "std_ms": round(float(t.std(ddof=1)), 5),
+                      "bootstrap_mean_ms": round(float(boot[k].mean()), 5), "bootstrap_std_ms": round(float(boot[k].std(ddof=1)), 5),
                       "outputs_identical": same}), flush=True)
+for k in range(1, len(libs)):
+    diff = float(boot[k].mean() - boot[0].mean())
+    se = float(np.sqrt(boot[k].var(ddof=1) / len(boot[k]) + boot[0].var(ddof=1) / len(boot[0])))
+    print(json.dumps({"lib": names[k], "against": names[0], "bootstrap_mean_diff_ms": round(diff, 5), "diff_percent": round(100 * diff / float(boot[0].mean()), 3),
+                      "standard_error_ms": round(se, 5), "diff_in_standard_errors": round(diff / se, 2) if se > 0 else None}), flush=True)
