@@ -903,6 +903,77 @@ int rtfhe_tlwe_decrypt_bits(const rtfhe_params *p, const int32_t *key0, const ui
                             uint8_t *bits, size_t count);
 int rtfhe_tlwe_phase(const rtfhe_params *p, const int32_t *key0, const uint32_t *in, uint32_t *phase, size_t count);
 
+/* ---- seeded ciphertexts: TRLWE masks regenerated from a public seed (no reference counterpart) ----
+ * Half of every TRLWE row is a uniformly random mask that carries no information.  A seeded object ships a 32-byte seed and the b polynomials
+ * only, and the receiver regenerates the a polynomials: half the bytes on the wire and over PCIe.
+ *
+ * THE MASK RULE.  A mask seed is a ChaCha20 key, u32[8].  Rows are numbered by a uint64_t.  Row R of length N has
+ *     a[16 c + i] = word i of the ChaCha20 block (RFC 8439 2.3) with key = seed, the 64-bit block counter c in state words 12-13 and R in state
+ *                   words 14-15, for c = 0 .. N/16 - 1
+ * -- the RFC's keystream with a 32-bit counter from 0 and the nonce words (0, R lo, R hi), and the generator of the production encryptors above
+ * read word by word.  The mask word is the keystream word itself, all 32 bits (the unseeded encryptors draw 24-bit masks, as the reference does).
+ *
+ * A seeded object is (seed, first_row, b): b is u32[rows][N] in the object's row order, row r masked by row first_row + r of the seed, and `group`
+ * says how rows interleave in the full layout u32[rows / group][2][group][N] (the b polynomials of a group, then its a polynomials):
+ *     TRLWE tables and rows u32[count][2][N]                      group 1
+ *     TRGSW sets and the bootstrapping key u32[count][2][2l][N]   group 2l
+ *     the packing key u32[n][t][base-1][2][N]                     group 1
+ *
+ * SECURITY RULES.  The seed is public.  The noise never comes from the seed: the production encryptors draw it from a separate OS-seeded ChaCha
+ * key, as the unseeded ones do, and the test-only forms from xoshiro256**.  A (seed, row) pair must never mask two ciphertexts under one key:
+ * that reveals the difference of their phases.  The production encryptors therefore draw a fresh seed from the OS on every call, write it to
+ * `seed` and number rows from 0; only the *_deterministic forms take a seed and a first_row (TEST ONLY -- NOT SECURE, as the ones above).
+ *
+ * Noise, message words and their placement are the unseeded encryptors'.  Where those add the message to an a polynomial (gadget rows l .. 2l-1
+ * of a TRGSW sample) the seeded row is the zero encryption under (mask - message), so that the expanded row (b, mask) is one the unseeded
+ * encryptor could have produced.  A seeded bootstrapping key needs no function of its own: it is rtfhe_trgsw_encrypt_bits_seeded with bits =
+ * key0 (count = n), loaded by rtfhe_load_bk_seeded.
+ *
+ * Every call returns RTFHE_ERR_INVALID before anything else happens for: a null pointer; N not a power of two in 16 .. 2048; group < 1; rows not a
+ * multiple of group; first_row + rows beyond 2^64; (encryptors) a non-binary key. */
+int rtfhe_mask_expand(int32_t N, const uint32_t *seed /* [8] */, uint64_t first_row, uint32_t *a /* [rows][N] */, size_t rows);
+/* the full layout on the CPU: the oracle of the device form below and the path of a server without this library's GPU side; b and out must not overlap */
+int rtfhe_seeded_expand(const rtfhe_params *p, const uint32_t *seed /* [8] */, uint64_t first_row, const uint32_t *b /* [rows][N] */, int32_t group,
+                        uint32_t *out /* [rows/group][2][group][N] */, size_t rows);
+/* the seeded forms of rtfhe_trlwe_encrypt_torus, rtfhe_trgsw_encrypt_bits, rtfhe_trgsw_encrypt_polys and rtfhe_packing_keygen (centred noise):
+ * each writes the b halves only, and the fresh seed */
+int rtfhe_trlwe_encrypt_torus_seeded(const rtfhe_params *p, const int32_t *key1, const uint32_t *mu /* [count][N] */, uint32_t *seed /* out [8] */,
+                                     uint32_t *b /* [count][N] */, size_t count);
+int rtfhe_trgsw_encrypt_bits_seeded(const rtfhe_params *p, const int32_t *key1, const uint8_t *bits /* [count] */, uint32_t *seed /* out [8] */,
+                                    uint32_t *b /* [count][2l][N] */, size_t count);
+int rtfhe_trgsw_encrypt_polys_seeded(const rtfhe_params *p, const int32_t *key1, const int32_t *mu /* [count][N] */, uint32_t *seed /* out [8] */,
+                                     uint32_t *b /* [count][2l][N] */, size_t count);
+int rtfhe_packing_keygen_seeded(const rtfhe_params *p, const int32_t *key0, const int32_t *key1, uint32_t *seed /* out [8] */,
+                                uint32_t *b /* [n][t][base-1][N] */);
+/* TEST ONLY -- NOT SECURE: the noise reproducible from noise_seed through xoshiro256**, the mask seed and its first row the caller's */
+int rtfhe_trlwe_encrypt_torus_seeded_deterministic(const rtfhe_params *p, const int32_t *key1, uint64_t noise_seed, const uint32_t *seed /* [8] */,
+                                                   uint64_t first_row, const uint32_t *mu, uint32_t *b, size_t count);
+int rtfhe_trgsw_encrypt_bits_seeded_deterministic(const rtfhe_params *p, const int32_t *key1, uint64_t noise_seed, const uint32_t *seed /* [8] */,
+                                                  uint64_t first_row, const uint8_t *bits, uint32_t *b, size_t count);
+int rtfhe_trgsw_encrypt_polys_seeded_deterministic(const rtfhe_params *p, const int32_t *key1, uint64_t noise_seed, const uint32_t *seed /* [8] */,
+                                                   uint64_t first_row, const int32_t *mu, uint32_t *b, size_t count);
+int rtfhe_packing_keygen_seeded_deterministic(const rtfhe_params *p, uint64_t noise_seed, const int32_t *key0, const int32_t *key1,
+                                              const uint32_t *seed /* [8] */, uint64_t first_row, uint32_t *b);
+/* On the device (every backend, no key, the primary device of a multi-device context): one launch of k_seeded_expand writes the whole full-layout
+ * object from d_b, which stays as it is.  Asynchronous and ordered on `stream`; nothing is allocated and the seed travels in the launch itself, so
+ * the call may be captured first thing on a fresh stream.  d_b and d_out must be 16-byte aligned and must not overlap, and rows * N / 16 stays
+ * below 2^31.  This is how compact input rows for rtfhe_trlwe_mul_plain_batch_dev, rtfhe_trlwe_mul_trgsw_batch_dev, rtfhe_demux_tree_batch_dev and
+ * rtfhe_lut_update_dev become full rows on the device. */
+int rtfhe_seeded_expand_dev(rtfhe_ctx *ctx, const uint32_t *seed /* host [8] */, uint64_t first_row, const void *d_b /* [rows][N] */, int32_t group,
+                            void *d_out /* [rows/group][2][group][N] */, size_t rows, void *stream);
+/* The upload calls' seeded forms.  Each uploads b (half the bytes of its twin), expands it on the device into the buffer the twin copies the full words
+ * into, and from there on IS the twin: same conversion, same handle, lifetime, error codes and memory accounting (the b halves pass through the
+ * context's staging). */
+int rtfhe_trgsw_create_seeded(rtfhe_ctx *ctx, const uint32_t *seed, uint64_t first_row, const uint32_t *b /* [n_sel][2l][N] */, int32_t n_sel,
+                              rtfhe_trgsw **out);
+int rtfhe_trgsw_update_seeded(rtfhe_trgsw *sel, const uint32_t *seed, uint64_t first_row, const uint32_t *b /* [n][2l][N] */, int32_t first, int32_t n);
+int rtfhe_lut_create_encrypted_seeded(rtfhe_ctx *ctx, const uint32_t *seed, uint64_t first_row, const uint32_t *b /* [n_lut][N] */, int32_t n_lut,
+                                      rtfhe_lut **out);
+/* (the derived exact-backend keys and the peers' replicas follow as in rtfhe_load_bk_torus) */
+int rtfhe_load_bk_seeded(rtfhe_ctx *ctx, const uint32_t *seed, uint64_t first_row, const uint32_t *b /* [n][2l][N] */);
+int rtfhe_packing_key_create_seeded(rtfhe_ctx *ctx, const uint32_t *seed, uint64_t first_row, const uint32_t *b /* [n][t][base-1][N] */,
+                                    rtfhe_packing_key **out);
+
 /* ---- wire format (flat little-endian files with an FNV-1a checksum; the reference has no serialization) ----
  * key file   "RTFHEKY1" | rtfhe_params | u32 flags (1 bk, 2 ksk, 4 secret keys) | u32 0 | [key0 | key1] | [bk] | [ksk] | u64 fnv
  * batch file "RTFHECT1" | i32 n | i32 0 | u64 count | u32[count][n+1] | u64 fnv */

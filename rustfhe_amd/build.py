@@ -16,8 +16,9 @@ OBJ = os.path.join(HERE, "..", "build", "obj")
 # device code lives in the .hip units (every kernel is instantiated in exactly one of them); the .cpp units are host-only
 HIP_SOURCES = ["rtfhe_dispatch_fft.hip", "rtfhe_dispatch_ntt.hip", "rtfhe_dispatch_xfft.hip", "rtfhe_stages.hip", "rtfhe_context.hip", "rtfhe_twiddles.hip",
                "rtfhe_batch.hip", "rtfhe_lut.hip", "rtfhe_circuit.hip", "rtfhe_multi.hip", "rtfhe_cmux_tree.hip", "rtfhe_cmux_net.hip", "rtfhe_pack.hip", "rtfhe_extract.hip", "rtfhe_plain.hip",
-               "rtfhe_trgsw_mac.hip"]
-CPP_SOURCES = ["rtfhe_keygen.cpp", "rtfhe_wire.cpp", "rtfhe_spqlios.cpp", "rtfhe_cmux_net_plan.cpp", "rtfhe_extract_plan.cpp", "rtfhe_plain_plan.cpp", "rtfhe_trgsw_mac_plan.cpp"]
+               "rtfhe_trgsw_mac.hip", "rtfhe_seeded.hip"]
+CPP_SOURCES = ["rtfhe_keygen.cpp", "rtfhe_wire.cpp", "rtfhe_spqlios.cpp", "rtfhe_cmux_net_plan.cpp", "rtfhe_extract_plan.cpp", "rtfhe_plain_plan.cpp", "rtfhe_trgsw_mac_plan.cpp",
+               "rtfhe_seeded.cpp"]
 SOURCES = HIP_SOURCES + CPP_SOURCES
 
 
@@ -44,7 +45,7 @@ def compile_all(out_lib, extra=(), obj_dir=OBJ, verbose=False, jobs=None, csrc=C
     os.makedirs(obj_dir, exist_ok=True)
 
     def one(src):
-        obj = os.path.join(obj_dir, os.path.splitext(src)[0] + ".o")
+        obj = os.path.join(obj_dir, src + ".o")      # (the extension stays: rtfhe_seeded.hip and rtfhe_seeded.cpp are two units)
         cmd = [hipcc] + CFLAGS + list(extra) + ["-I", os.path.join(HERE, "..", "include"), "-c", "-x", "hip", os.path.join(csrc, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)

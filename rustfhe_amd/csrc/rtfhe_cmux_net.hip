@@ -122,11 +122,15 @@ int rtfhe_cmux_circuit_create(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const rtfh
     return 0;
 }
 
+}  // extern "C"
+
 // rtfhe_trgsw_create's conversion of selectors [first, first + n) of a live set, in place and synchronous
-int rtfhe_trgsw_update(rtfhe_trgsw* sel, const uint32_t* trgsw, int32_t first, int32_t n) {
+// (args_ok: the caller's other pointers; stage(words) brings the words of the new samples into ctx->d_a: the caller's copy, or a seeded form's expansion)
+template <typename Stage>
+static int trgsw_update_staged(rtfhe_trgsw* sel, bool args_ok, int32_t first, int32_t n, Stage stage) {
     rtfhe_ctx* ctx = sel ? sel->ctx : nullptr;
     if (int rc = handles_ready(ctx, {ref(sel)})) return rc;
-    if (!trgsw) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (!args_ok) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
     if (first < 0 || n < 1 || (long long)first + n > sel->n_sel)
         return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_update: selectors [" + std::to_string(first) + ", " + std::to_string((long long)first + n) +
                                             ") are outside the set's [0, " + std::to_string(sel->n_sel) + ")");
@@ -134,10 +138,29 @@ int rtfhe_trgsw_update(rtfhe_trgsw* sel, const uint32_t* trgsw, int32_t first, i
     const size_t polys = (size_t)n * 2 * 2 * ctx->p.l, words = polys * ctx->p.N, per_sel = (size_t)2 * 2 * ctx->p.l * (ctx->p.N / 2);
     HIPCHECK(ctx, hipDeviceSynchronize());            // replays on any stream may still read the old spectra
     if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, words * 4)) return rc;
-    HIPCHECK(ctx, hipMemcpy(ctx->d_a, trgsw, words * 4, hipMemcpyHostToDevice));
+    if (int rc = stage(ctx, words)) return rc;
     if (int rc = launch_fft(ctx, true, FftArgs{ctx->d_tw, ctx->d_a, sel->d_spec + (size_t)first * per_sel, (int32_t)polys, 1, 2 * ctx->p.l, 0}, ctx->stream)) return rc;
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
+}
+
+extern "C" {
+
+int rtfhe_trgsw_update(rtfhe_trgsw* sel, const uint32_t* trgsw, int32_t first, int32_t n) {
+    return trgsw_update_staged(sel, trgsw != nullptr, first, n, [&](rtfhe_ctx* ctx, size_t words) {
+        HIPCHECK(ctx, hipMemcpy(ctx->d_a, trgsw, words * 4, hipMemcpyHostToDevice));
+        return 0;
+    });
+}
+
+// ... from the seeded form of the new samples (rows first_row .. of the seed, their b halves)
+int rtfhe_trgsw_update_seeded(rtfhe_trgsw* sel, const uint32_t* seed, uint64_t first_row, const uint32_t* b, int32_t first, int32_t n) {
+    rtfhe_ctx* ctx = sel ? sel->ctx : nullptr;
+    if (ctx && seed && b && n >= 1)
+        if (int rc = seeded_ready(ctx, "rtfhe_trgsw_update_seeded", RTFHE_SEEDED_UPLOAD, seed, first_row, b, 2 * ctx->p.l, nullptr, (size_t)n * 2 * ctx->p.l)) return rc;
+    return trgsw_update_staged(sel, seed && b, first, n, [&](rtfhe_ctx* c, size_t) {
+        return stage_seeded(c, seed, first_row, b, 2 * c->p.l, (size_t)n * 2 * c->p.l, c->d_a);
+    });
 }
 
 }  // extern "C"

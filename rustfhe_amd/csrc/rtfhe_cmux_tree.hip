@@ -260,13 +260,11 @@ void trgsw_release(rtfhe_trgsw* t) {
 
 }  // namespace rtfhe_host
 
-extern "C" {
-
 // TRGSWRepF::from (trgsw.rs:68-76) of every sample, as rtfhe_load_bk_torus converts the bootstrapping key: the forward transform of the words
 // viewed as signed i32, written in the canonical device layout [2l][2][R][64]
-int rtfhe_trgsw_create(rtfhe_ctx* ctx, const uint32_t* trgsw, int32_t n_sel, rtfhe_trgsw** out) {
-    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
-    if (!trgsw || !out || n_sel < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_create: null argument or n_sel < 1");
+// (stage(words) queues on ctx->stream what brings the words of the samples into ctx->d_a: the caller's copy, or a seeded set's expansion)
+template <typename Stage>
+static int trgsw_create_staged(rtfhe_ctx* ctx, int32_t n_sel, rtfhe_trgsw** out, Stage stage) {
     *out = nullptr;
     if (int rc = use(ctx)) return rc;
     // the rotation, the demultiplexer and the TRLWE x TRGSW product are granted their dynamic LDS now, so that the first of a context may already
@@ -281,7 +279,7 @@ int rtfhe_trgsw_create(rtfhe_ctx* ctx, const uint32_t* trgsw, int32_t n_sel, rtf
     t->ctx = ctx;
     int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, words * 4);
     if (!rc && hipMalloc((void**)&t->d_spec, words / 2 * sizeof(cplx)) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_trgsw_create: hipMalloc");
-    if (!rc) rc = copy_in(ctx, ctx->d_a, trgsw, words * 4, 0);      // on the stream of the transform below, which is waited for
+    if (!rc) rc = stage(words);      // on the stream of the transform below, which is waited for
     if (!rc) rc = launch_fft(ctx, true, FftArgs{ctx->d_tw, ctx->d_a, t->d_spec, (int32_t)polys, 1, 2 * ctx->p.l, 0}, ctx->stream);
     if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_trgsw_create: hipStreamSynchronize");
     if (rc) {
@@ -293,6 +291,24 @@ int rtfhe_trgsw_create(rtfhe_ctx* ctx, const uint32_t* trgsw, int32_t n_sel, rtf
     ctx->trgsws.push_back(t);
     *out = t;
     return 0;
+}
+
+extern "C" {
+
+int rtfhe_trgsw_create(rtfhe_ctx* ctx, const uint32_t* trgsw, int32_t n_sel, rtfhe_trgsw** out) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!trgsw || !out || n_sel < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_create: null argument or n_sel < 1");
+    return trgsw_create_staged(ctx, n_sel, out, [&](size_t words) { return copy_in(ctx, ctx->d_a, trgsw, words * 4, 0); });
+}
+
+// the same set from its seeded form: the b halves go up, the masks are made on the device
+int rtfhe_trgsw_create_seeded(rtfhe_ctx* ctx, const uint32_t* seed, uint64_t first_row, const uint32_t* b, int32_t n_sel, rtfhe_trgsw** out) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!seed || !b || !out || n_sel < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_create_seeded: null argument or n_sel < 1");
+    const int group = 2 * ctx->p.l;
+    const size_t rows = (size_t)n_sel * group;
+    if (int rc = seeded_ready(ctx, "rtfhe_trgsw_create_seeded", RTFHE_SEEDED_UPLOAD, seed, first_row, b, group, nullptr, rows)) return rc;
+    return trgsw_create_staged(ctx, n_sel, out, [&](size_t) { return stage_seeded(ctx, seed, first_row, b, group, rows, ctx->d_a); });
 }
 
 void rtfhe_trgsw_destroy(rtfhe_trgsw* t) {

@@ -488,13 +488,16 @@ int rtfhe_twiddles_load(rtfhe_ctx* ctx, const char* path, int32_t* entries_chang
     return rtfhe_set_twiddles(ctx, t.data(), t.data() + n2);
 }
 
-int rtfhe_load_bk_torus(rtfhe_ctx* ctx, const uint32_t* bk) {
-    if (int rc = use(ctx)) return rc;
-    if (!bk) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+}  // extern "C"
+
+// rtfhe_load_bk_torus from the point where the key's words are wanted in ctx->d_bk_torus: fill(words) brings them there, done when it returns --
+// the caller's copy, or a seeded key's expansion
+template <typename Fill>
+static int load_bk_torus_filled(rtfhe_ctx* ctx, Fill fill) {
     const size_t words = bk_word_count(ctx->p);
     if (!ctx->d_bk) HIPCHECK(ctx, hipMalloc((void**)&ctx->d_bk, bk_cplx_count(ctx->p) * sizeof(cplx)));
     if (!ctx->d_bk_torus) HIPCHECK(ctx, hipMalloc((void**)&ctx->d_bk_torus, words * 4));
-    HIPCHECK(ctx, hipMemcpy(ctx->d_bk_torus, bk, words * 4, hipMemcpyHostToDevice));
+    if (int rc = fill(words)) return rc;
     if (int rc = transform_bk_from_torus(ctx)) return rc;
     key_changed(ctx);
     ctx->has_bk = true;
@@ -507,6 +510,31 @@ int rtfhe_load_bk_torus(rtfhe_ctx* ctx, const uint32_t* bk) {
     }
     HIPCHECK(ctx, hipSetDevice(ctx->device));
     return 0;
+}
+
+extern "C" {
+
+int rtfhe_load_bk_torus(rtfhe_ctx* ctx, const uint32_t* bk) {
+    if (int rc = use(ctx)) return rc;
+    if (!bk) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    return load_bk_torus_filled(ctx, [&](size_t words) {
+        HIPCHECK(ctx, hipMemcpy(ctx->d_bk_torus, bk, words * 4, hipMemcpyHostToDevice));
+        return 0;
+    });
+}
+
+// the same key from its seeded form (rtfhe_trgsw_encrypt_bits_seeded of key0): the b halves go up, the masks are made on the primary device
+int rtfhe_load_bk_seeded(rtfhe_ctx* ctx, const uint32_t* seed, uint64_t first_row, const uint32_t* b) {
+    if (int rc = use(ctx)) return rc;
+    if (!seed || !b) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    const int group = 2 * ctx->p.l;
+    const size_t rows = (size_t)ctx->p.n * group;
+    if (int rc = seeded_ready(ctx, "rtfhe_load_bk_seeded", RTFHE_SEEDED_UPLOAD, seed, first_row, b, group, nullptr, rows)) return rc;
+    return load_bk_torus_filled(ctx, [&](size_t) {
+        if (int rc = stage_seeded(ctx, seed, first_row, b, group, rows, ctx->d_bk_torus)) return rc;
+        HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+        return 0;
+    });
 }
 
 int rtfhe_load_bk_fft(rtfhe_ctx* ctx, const double* bk_f) {

@@ -19,6 +19,8 @@
 //                            (its argument checks: rtfhe_extract_plan.cpp, host only)
 //   rtfhe_plain.hip          exact TRLWE x plain-polynomial products: plain sets (integer polynomials as spectra), sums of up to eight products per sample
 //                            on the split-FFT exact backend's arithmetic, on every backend (its argument checks: rtfhe_plain_plan.cpp, host only)
+//   rtfhe_seeded.hip         seeded ciphertexts: masks expanded on the device from a public seed (k_seeded_expand), the staging step of the *_seeded
+//                            upload calls, which live beside their unseeded twins (its argument checks and the CPU form: rtfhe_seeded.cpp, host only)
 // Every kernel is instantiated in exactly one of them.  No CPU fallback anywhere: an entry point runs HIP kernels or fails.
 #pragma once
 
@@ -35,6 +37,7 @@
 #include <vector>
 
 #include "rtfhe_kernels.hpp"
+#include "rtfhe_seeded_plan.h"
 
 // ------------------------------------------------------------------------------------------------
 // twiddle tables (host).  Values follow the reference's table builders so that a context created in
@@ -278,6 +281,14 @@ void trgsw_release(rtfhe_trgsw* t);                                       // fre
 void packing_key_release(rtfhe_packing_key* k);                           // frees a packing key's matrix (rtfhe_pack.hip)
 void plain_release(rtfhe_plain* w);                                       // frees a plain set's spectra (rtfhe_plain.hip)
 int prime_trgsw_mac(rtfhe_ctx* ctx);                                      // grants the TRLWE x TRGSW product's twins their LDS (rtfhe_trgsw_mac.hip)
+// ---- seeded ciphertexts (rtfhe_seeded.hip; the checks themselves: rtfhe_seeded.cpp, host only) ----
+// rtfhe_seeded_plan at the context's N with its refusal as the context's error (what: RTFHE_SEEDED_DEVICE / _UPLOAD of rtfhe_seeded_plan.h)
+int seeded_ready(rtfhe_ctx* ctx, const char* name, int what, const void* seed, uint64_t first_row, const void* b, int group, const void* out, size_t rows);
+// the one launch of k_seeded_expand on s: d_out [rows / group][2][group][N] from the seed and d_b [rows][N]; arguments already checked
+int launch_seeded_expand(rtfhe_ctx* ctx, const uint32_t* seed, uint64_t first_row, const uint32_t* d_b, int group, uint32_t* d_out, size_t rows, hipStream_t s);
+// what a *_seeded upload call does where its unseeded twin copies the caller's words in: the host b halves up through ctx->d_b, then the expansion into
+// d_full, both queued on ctx->stream
+int stage_seeded(rtfhe_ctx* ctx, const uint32_t* seed, uint64_t first_row, const uint32_t* b, int group, size_t rows, void* d_full);
 // ---- the lifetime rule of the handles (rtfhe_context.hip) ----
 // a handle as a call's check sees it: its noun and type name for the messages, whether the caller gave one, and the context it hangs on
 struct HandleRef { const char* noun; const char* type; bool given; const rtfhe_ctx* owner; };

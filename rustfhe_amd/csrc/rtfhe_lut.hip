@@ -11,8 +11,17 @@ using namespace rtfhe_host;
 
 namespace {
 
+// lut_upload's fill for rows the caller holds in full
+auto copy_rows(const uint32_t* tv) {
+    return [tv](rtfhe_ctx* c, void* p, size_t bytes) {
+        return hipMemcpy(p, tv, bytes, hipMemcpyHostToDevice) != hipSuccess ? fail(c, RTFHE_ERR_HIP, "rtfhe_lut_create: hipMemcpy") : 0;
+    };
+}
+
 // the rows of a table (plain: [n_lut][N] test polynomials; encrypted: [n_lut][2][N] TRLWEs) uploaded to every entry of the context
-int lut_upload(rtfhe_ctx* ctx, const uint32_t* tv, int32_t n_lut, bool encrypted, rtfhe_lut** out) {
+// (fill(c, p, bytes) brings the rows into p on entry c, done when it returns: the caller's copy, or a seeded table's expansion)
+template <typename Fill>
+int lut_upload(rtfhe_ctx* ctx, int32_t n_lut, bool encrypted, rtfhe_lut** out, Fill fill) {
     *out = nullptr;
     const size_t bytes = (size_t)n_lut * ctx->p.N * (encrypted ? 2 : 1) * 4;
     rtfhe_lut* lut = new rtfhe_lut();
@@ -26,7 +35,7 @@ int lut_upload(rtfhe_ctx* ctx, const uint32_t* tv, int32_t n_lut, bool encrypted
         rc = use(c);
         if (!rc && hipMalloc(&p, bytes) != hipSuccess) rc = fail(c, RTFHE_ERR_HIP, "rtfhe_lut_create: hipMalloc");
         if (p) lut->d_tv.push_back((uint32_t*)p);
-        if (!rc && hipMemcpy(p, tv, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, RTFHE_ERR_HIP, "rtfhe_lut_create: hipMemcpy");
+        if (!rc) rc = fill(c, p, bytes);
         if (rc && c != ctx) rc = fail(ctx, rc, "device " + std::to_string(c->device) + ": " + c->err);
     }
     (void)hipSetDevice(ctx->device);
@@ -84,13 +93,25 @@ extern "C" {
 int rtfhe_lut_create(rtfhe_ctx* ctx, const uint32_t* tv, int32_t n_lut, rtfhe_lut** out) {
     if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
     if (!tv || !out || n_lut < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_create: null argument or n_lut < 1");
-    return lut_upload(ctx, tv, n_lut, false, out);
+    return lut_upload(ctx, n_lut, false, out, copy_rows(tv));
 }
 
 int rtfhe_lut_create_encrypted(rtfhe_ctx* ctx, const uint32_t* trlwe, int32_t n_lut, rtfhe_lut** out) {
     if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
     if (!trlwe || !out || n_lut < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_create_encrypted: null argument or n_lut < 1");
-    return lut_upload(ctx, trlwe, n_lut, true, out);
+    return lut_upload(ctx, n_lut, true, out, copy_rows(trlwe));
+}
+
+// the same table from its seeded form: on every entry the b halves go up and the masks are made there
+int rtfhe_lut_create_encrypted_seeded(rtfhe_ctx* ctx, const uint32_t* seed, uint64_t first_row, const uint32_t* b, int32_t n_lut, rtfhe_lut** out) {
+    if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
+    if (!seed || !b || !out || n_lut < 1) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_lut_create_encrypted_seeded: null argument or n_lut < 1");
+    if (int rc = seeded_ready(ctx, "rtfhe_lut_create_encrypted_seeded", RTFHE_SEEDED_UPLOAD, seed, first_row, b, 1, nullptr, (size_t)n_lut)) return rc;
+    return lut_upload(ctx, n_lut, true, out, [&](rtfhe_ctx* c, void* p, size_t) {
+        if (int rc = stage_seeded(c, seed, first_row, b, 1, (size_t)n_lut, p)) return rc;
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, RTFHE_ERR_HIP, "rtfhe_lut_create_encrypted_seeded: k_seeded_expand");
+        return 0;
+    });
 }
 
 void rtfhe_lut_destroy(rtfhe_lut* lut) {

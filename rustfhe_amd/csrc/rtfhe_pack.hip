@@ -77,11 +77,12 @@ void packing_key_release(rtfhe_packing_key* k) {
 
 }  // namespace rtfhe_host
 
-extern "C" {
-
-int rtfhe_packing_key_create(rtfhe_ctx* ctx, const uint32_t* pk, rtfhe_packing_key** out) {
+// (args_ok: the caller's pointers; fill(d_raw, rows, raw_bytes) brings the key's rows into d_raw, done when it returns: the caller's copy, or a seeded
+// key's expansion)
+template <typename Fill>
+static int packing_key_create_filled(rtfhe_ctx* ctx, bool args_ok, rtfhe_packing_key** out, Fill fill) {
     if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
-    if (!pk || !out) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_packing_key_create: null argument");
+    if (!args_ok) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_packing_key_create: null argument");
     *out = nullptr;
     if (ctx->p.ks_t != 8 || ctx->p.ks_basebit != 2)
         return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_packing_key_create: the packing key switch needs ks_t = 8 and ks_basebit = 2");
@@ -96,7 +97,7 @@ int rtfhe_packing_key_create(rtfhe_ctx* ctx, const uint32_t* pk, rtfhe_packing_k
     int rc = 0;
     if (hipMalloc((void**)&d_raw, raw_bytes) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_packing_key_create: hipMalloc (raw rows)");
     if (!rc && hipMalloc((void**)&k->d_kmat, kmat_v4 * sizeof(uint4)) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_packing_key_create: hipMalloc (key matrix)");
-    if (!rc && hipMemcpy(d_raw, pk, raw_bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_packing_key_create: hipMemcpy");
+    if (!rc) rc = fill(d_raw, rows, raw_bytes);
     if (!rc) {
         PkMatArgs a{d_raw, k->d_kmat, ctx->p.n, k->n16, k->colgroups};
         rc = launch_kernel(ctx, k_pkmat_build<8, 2>, dim3(4096), dim3(256), 0, ctx->stream, a);
@@ -112,6 +113,24 @@ int rtfhe_packing_key_create(rtfhe_ctx* ctx, const uint32_t* pk, rtfhe_packing_k
     ctx->pack_keys.push_back(k);
     *out = k;
     return 0;
+}
+
+extern "C" {
+
+int rtfhe_packing_key_create(rtfhe_ctx* ctx, const uint32_t* pk, rtfhe_packing_key** out) {
+    return packing_key_create_filled(ctx, pk && out, out, [&](uint32_t* d_raw, size_t, size_t raw_bytes) {
+        return hipMemcpy(d_raw, pk, raw_bytes, hipMemcpyHostToDevice) != hipSuccess ? fail(ctx, RTFHE_ERR_HIP, "rtfhe_packing_key_create: hipMemcpy") : 0;
+    });
+}
+
+// the same key from its seeded form (rtfhe_packing_keygen_seeded): the b halves go up, the masks are made on the device
+int rtfhe_packing_key_create_seeded(rtfhe_ctx* ctx, const uint32_t* seed, uint64_t first_row, const uint32_t* b, rtfhe_packing_key** out) {
+    if (ctx && seed && b && out)
+        if (int rc = seeded_ready(ctx, "rtfhe_packing_key_create_seeded", RTFHE_SEEDED_UPLOAD, seed, first_row, b, 1, nullptr, (size_t)ctx->p.n * 8 * 3)) return rc;
+    return packing_key_create_filled(ctx, seed && b && out, out, [&](uint32_t* d_raw, size_t rows, size_t) {
+        if (int rc = stage_seeded(ctx, seed, first_row, b, 1, rows, d_raw)) return rc;
+        return hipStreamSynchronize(ctx->stream) != hipSuccess ? fail(ctx, RTFHE_ERR_HIP, "rtfhe_packing_key_create_seeded: k_seeded_expand") : 0;
+    });
 }
 
 void rtfhe_packing_key_destroy(rtfhe_packing_key* k) {

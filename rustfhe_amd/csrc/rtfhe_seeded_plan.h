@@ -1,0 +1,30 @@
+/* rtfhe_seeded_plan.h -- the host-only argument checks of the seeded-ciphertext calls (include/rtfhe.h: rtfhe_mask_expand, rtfhe_seeded_expand[_dev]
+ * and the *_seeded upload calls), with no device call in it (rtfhe_seeded.cpp).  Internal: rtfhe_seeded.hip and the upload calls run it before anything
+ * is allocated or launched, and tests/c/seeded_sanitize_main.c walks it under the host sanitizers.  Plain C so that a C host can include it. */
+#ifndef RTFHE_SEEDED_PLAN_H
+#define RTFHE_SEEDED_PLAN_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* what is being checked: the CPU expansion, the device expansion (also: 16-byte aligned pointers, rows * N / 16 below 2^31 lanes), or an upload
+ * call, whose output is the library's own buffer (out is not looked at) */
+#define RTFHE_SEEDED_HOST 0
+#define RTFHE_SEEDED_DEVICE 1
+#define RTFHE_SEEDED_UPLOAD 2
+
+/* The checks of one call, in this order: seed, b and (unless an upload) out non-null; N a power of two in 16 .. 2048; group >= 1; rows a multiple of
+ * group; first_row + rows <= 2^64; the device forms' alignment and size; b [rows][N] overlaps no part of out [2 rows][N] (u32 words; compared as
+ * addresses and never dereferenced).  Returns 0, or RTFHE_ERR_INVALID with a message in err (always terminated; err_len >= 1). */
+int rtfhe_seeded_plan(int32_t what, int32_t N, const void *seed, uint64_t first_row, const void *b, int32_t group, const void *out, size_t rows,
+                      char *err, size_t err_len);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

@@ -31,6 +31,13 @@ def _stream(stream):
     return C.c_void_p(stream) if stream else None
 
 
+def _seed(seed):
+    """A mask seed (include/rtfhe.h, "seeded ciphertexts"): u32[8], a ChaCha20 key -- public."""
+    seed = _np(seed, np.uint32).reshape(-1)
+    assert seed.size == 8, "a mask seed is u32[8]"
+    return seed
+
+
 class _Handle:
     """Owns one handle of the library, kept in the attribute named by _slot, and the function that destroys it (self._destroy, set before the
     handle is): close() frees it once, and so do a with block and garbage collection."""
@@ -114,6 +121,13 @@ class Engine(_Handle):
         bk = _np(bk, np.uint32).reshape(-1)
         assert bk.size == self.p.bk_words, "bk must be u32[n][2][2l][N]"
         self._ck(self.L.rtfhe_load_bk_torus(self.h, _ptr(bk)))
+
+    def load_bk_seeded(self, seed, b, first_row=0):
+        """load_bk_torus from the key's seeded form (rtfhe_load_bk_seeded): b u32[n][2l][N], e.g. encrypt_selectors_seeded(params, key1, key0) --
+        half the bytes go up, the masks are made on the device."""
+        b = _np(b, np.uint32).reshape(-1)
+        assert b.size == self.p.bk_words // 2, "b must be u32[n][2l][N]"
+        self._ck(self.L.rtfhe_load_bk_seeded(self.h, _ptr(_seed(seed)), int(first_row), _ptr(b)))
 
     def load_bk_fft(self, bk_f):
         bk_f = _np(bk_f, np.float64).reshape(-1)
@@ -298,6 +312,11 @@ class Engine(_Handle):
         lvl1 key, e.g. from rustfhe_amd.encrypt_lut.  Returns a Lut (lut.encrypted is True) usable wherever a Lut is."""
         return Lut(self, trlwe, encrypted=True)
 
+    def lut_encrypted_seeded(self, seed, b, first_row=0):
+        """lut_encrypted from the table's seeded form (rtfhe_lut_create_encrypted_seeded): b u32[n_lut][N] (or one u32[N]) and the public seed,
+        e.g. from rustfhe_amd.encrypt_lut_seeded; row r's mask is row first_row + r of the seed, made on the device."""
+        return Lut(self, b, encrypted=True, seeded=(_seed(seed), int(first_row)))
+
     def pbs_batch(self, lut, tlwe, lut_idx=None):
         """One programmable bootstrap per ciphertext: gate g evaluates table lut_idx[g] (None: table 0).  Indices are checked here:
         one outside [0, n_lut) raises RtfheError before anything runs."""
@@ -335,6 +354,18 @@ class Engine(_Handle):
         """Uploads TRGSW samples u32[n_sel][2][2l][N] (or one u32[2][2l][N]) under the lvl1 key, e.g. from rustfhe_amd.encrypt_selectors, and
         converts them to spectra on the primary device; a Selectors handle, closed by close() or a with block."""
         return Selectors(self, trgsw)
+
+    def selectors_seeded(self, seed, b, first_row=0):
+        """selectors from the set's seeded form (rtfhe_trgsw_create_seeded): b u32[n_sel][2l][N] (or one u32[2l][N]) and the public seed, e.g. from
+        rustfhe_amd.encrypt_selectors_seeded / encrypt_trgsw_polys_seeded -- half the bytes go up, the masks are made on the device."""
+        return Selectors(self, b, seeded=(_seed(seed), int(first_row)))
+
+    def seeded_expand_dev(self, seed, d_b, group, d_out, rows, first_row=0, stream=None):
+        """One launch (rtfhe_seeded_expand_dev): d_out [rows / group][2][group][N] words = the b halves d_b [rows][N] and the masks of rows
+        first_row .. first_row + rows - 1 of the seed; what rustfhe_amd.seeded_expand computes on the CPU.  Asynchronous on `stream`, nothing
+        allocated: it may be captured first thing on a fresh stream.  The buffers must be 16-byte aligned and must not overlap."""
+        self._ck(self.L.rtfhe_seeded_expand_dev(self.h, _ptr(_seed(seed)), int(first_row), self._dev(d_b), int(group), self._dev(d_out), int(rows),
+                                                _stream(stream)))
 
     def _tree_args(self, sel_idx, depth, row0, coef, count):
         i32 = lambda a, shape: None if a is None else _np(a, np.int32).reshape(shape)      # noqa: E731
@@ -453,6 +484,11 @@ class Engine(_Handle):
         """Uploads a packing key u32[n][t][base-1][2][N] (rustfhe_amd.packing_keygen) to the primary device in the operand order of the matrix
         pipe; a PackingKey handle, closed by close() or a with block."""
         return PackingKey(self, pk)
+
+    def packing_key_seeded(self, seed, b, first_row=0):
+        """packing_key from the key's seeded form (rtfhe_packing_key_create_seeded): b u32[n][t][base-1][N] and the public seed
+        (rustfhe_amd.packing_keygen_seeded)."""
+        return PackingKey(self, b, seeded=(_seed(seed), int(first_row)))
 
     def _pos_arg(self, pos, P):
         if pos is None:
@@ -647,15 +683,19 @@ class Lut(_Handle):
     """Test polynomials of a programmable bootstrap on an Engine's devices (rtfhe_lut), plain or encrypted (TRLWE rows, Engine.lut_encrypted).
     Closing it frees the device copies; a Lut whose Engine was closed first only frees its handle."""
 
-    def __init__(self, engine, tv, encrypted=False):
+    def __init__(self, engine, tv, encrypted=False, seeded=None):
+        """seeded: (seed, first_row) -- tv then holds the b halves u32[n_lut][N] of an encrypted table (Engine.lut_encrypted_seeded)."""
         tv = _np(tv, np.uint32)
-        tv = tv.reshape(-1, 2 * engine.p.N if encrypted else engine.p.N)
+        tv = tv.reshape(-1, 2 * engine.p.N if encrypted and seeded is None else engine.p.N)
         self.engine, self._destroy = engine, engine.L.rtfhe_lut_destroy
         self.encrypted = bool(encrypted)
         self.n_lut = tv.shape[0]
         h = C.c_void_p()
-        create = engine.L.rtfhe_lut_create_encrypted if encrypted else engine.L.rtfhe_lut_create
-        engine._ck(create(engine.h, _ptr(tv), self.n_lut, C.byref(h)))
+        if seeded is not None:
+            engine._ck(engine.L.rtfhe_lut_create_encrypted_seeded(engine.h, _ptr(seeded[0]), seeded[1], _ptr(tv), self.n_lut, C.byref(h)))
+        else:
+            create = engine.L.rtfhe_lut_create_encrypted if encrypted else engine.L.rtfhe_lut_create
+            engine._ck(create(engine.h, _ptr(tv), self.n_lut, C.byref(h)))
         self.h = h
 
     def update_dev(self, d_trlwe, first=0, n=1, stream=None):
@@ -683,13 +723,17 @@ class Selectors(_Handle):
     """The TRGSW selectors of CMUX trees on an Engine's primary device (rtfhe_trgsw), kept as spectra.  Closing it frees the device copy; one
     whose Engine was closed first only frees its handle."""
 
-    def __init__(self, engine, trgsw):
+    def __init__(self, engine, trgsw, seeded=None):
+        """seeded: (seed, first_row) -- trgsw then holds the b halves u32[n_sel][2l][N] (Engine.selectors_seeded)."""
         p = engine.p
-        trgsw = _np(trgsw, np.uint32).reshape(-1, 2 * 2 * p.l * p.N)
+        trgsw = _np(trgsw, np.uint32).reshape(-1, (2 if seeded is None else 1) * 2 * p.l * p.N)
         self.engine, self._destroy = engine, engine.L.rtfhe_trgsw_destroy
         self.n_sel = trgsw.shape[0]
         h = C.c_void_p()
-        engine._ck(engine.L.rtfhe_trgsw_create(engine.h, _ptr(trgsw), self.n_sel, C.byref(h)))
+        if seeded is not None:
+            engine._ck(engine.L.rtfhe_trgsw_create_seeded(engine.h, _ptr(seeded[0]), seeded[1], _ptr(trgsw), self.n_sel, C.byref(h)))
+        else:
+            engine._ck(engine.L.rtfhe_trgsw_create(engine.h, _ptr(trgsw), self.n_sel, C.byref(h)))
         self.h = h
 
     def update(self, words, first=0):
@@ -699,18 +743,30 @@ class Selectors(_Handle):
         words = _np(words, np.uint32).reshape(-1, 2 * 2 * p.l * p.N)
         self.engine._ck(self.engine.L.rtfhe_trgsw_update(self.h, _ptr(words), int(first), words.shape[0]))
 
+    def update_seeded(self, seed, b, first=0, first_row=0):
+        """update from the new samples' seeded form (rtfhe_trgsw_update_seeded): b u32[n][2l][N], sample i's rows masked by rows
+        first_row + 2l i .. of the seed.  A (seed, row) pair masks one ciphertext only: new samples take a fresh seed or unused rows."""
+        p = self.engine.p
+        b = _np(b, np.uint32).reshape(-1, 2 * p.l * p.N)
+        self.engine._ck(self.engine.L.rtfhe_trgsw_update_seeded(self.h, _ptr(_seed(seed)), int(first_row), _ptr(b), int(first), b.shape[0]))
+
 
 class PackingKey(_Handle):
     """A packing key on an Engine's primary device (rtfhe_packing_key), kept as signed byte limbs in the matrix pipe's operand order.  Closing
     it frees the device copy; one whose Engine was closed first only frees its handle."""
 
-    def __init__(self, engine, pk):
+    def __init__(self, engine, pk, seeded=None):
+        """seeded: (seed, first_row) -- pk then holds the b halves u32[n][t][base-1][N] (Engine.packing_key_seeded)."""
         p = engine.p
         pk = _np(pk, np.uint32).reshape(-1)
-        assert pk.size == packing_key_words(p), "pk must be u32[n][t][base-1][2][N]"
         self.engine, self._destroy = engine, engine.L.rtfhe_packing_key_destroy
         h = C.c_void_p()
-        engine._ck(engine.L.rtfhe_packing_key_create(engine.h, _ptr(pk), C.byref(h)))
+        if seeded is not None:
+            assert pk.size == packing_key_words(p) // 2, "b must be u32[n][t][base-1][N]"
+            engine._ck(engine.L.rtfhe_packing_key_create_seeded(engine.h, _ptr(seeded[0]), seeded[1], _ptr(pk), C.byref(h)))
+        else:
+            assert pk.size == packing_key_words(p), "pk must be u32[n][t][base-1][2][N]"
+            engine._ck(engine.L.rtfhe_packing_key_create(engine.h, _ptr(pk), C.byref(h)))
         self.h = h
 
 
@@ -939,6 +995,88 @@ def encrypt_trgsw_polys(params, key1, mu, seed=None):
     if rc != 0:
         raise RtfheError(rc, "rtfhe_trgsw_encrypt_polys failed")
     return out
+
+
+# ---- seeded ciphertexts (include/rtfhe.h, "seeded ciphertexts"): a public seed and the b halves stand for the full rows -------------------
+
+def mask_expand(N, seed, rows, first_row=0):
+    """The masks of rows first_row .. first_row + rows - 1 of a seed at ring degree N (rtfhe_mask_expand): u32[rows][N], the ChaCha20 keystream
+    of the seed with the row number in the nonce."""
+    L = _ffi.load()
+    a = np.empty((int(rows), int(N)), np.uint32)
+    rc = L.rtfhe_mask_expand(int(N), _ptr(_seed(seed)), int(first_row), _ptr(a), int(rows))
+    if rc != 0:
+        raise RtfheError(rc, "rtfhe_mask_expand failed (N not a power of two in 16 .. 2048, or first_row + rows beyond 2^64)")
+    return a
+
+
+def seeded_expand(params, seed, b, group=1, first_row=0):
+    """The full layout of a seeded object on the CPU (rtfhe_seeded_expand): b u32[rows][N] -> u32[rows / group][2][group][N], the b polynomials
+    of each group, then their masks.  group: 1 for TRLWE rows, tables and the packing key, 2l for TRGSW sets and the bootstrapping key."""
+    L = _ffi.load()
+    b = _np(b, np.uint32).reshape(-1, params.N)
+    rows, group = b.shape[0], int(group)
+    out = np.empty(2 * b.size, np.uint32)
+    rc = L.rtfhe_seeded_expand(C.byref(params), _ptr(_seed(seed)), int(first_row), _ptr(b), group, _ptr(out), rows)
+    if rc != 0:
+        raise RtfheError(rc, "rtfhe_seeded_expand failed (group < 1, rows not a multiple of group, or first_row + rows beyond 2^64)")
+    return out.reshape(rows // group, 2, group, params.N)
+
+
+def _seeded_encrypt(name, params, keys, msg, b, noise_seed, seed, first_row, count=()):
+    """One seeded encryptor: the production form (noise_seed None: fresh seed from the OS, rows from 0) or its TEST-ONLY deterministic form
+    (noise_seed, seed and first_row given).  keys / msg: the pointers of the key(s) and of the messages; count: the trailing count argument as a
+    tuple, empty for the packing key."""
+    L = _ffi.load()
+    if noise_seed is None:
+        assert seed is None and first_row == 0, "the production form draws its own seed and numbers rows from 0"
+        seed = np.zeros(8, np.uint32)
+        rc = getattr(L, name)(C.byref(params), *keys, *msg, _ptr(seed), _ptr(b), *count)
+    else:
+        seed = _seed(seed)
+        if name == "rtfhe_packing_keygen_seeded":
+            rc = L.rtfhe_packing_keygen_seeded_deterministic(C.byref(params), int(noise_seed), *keys, _ptr(seed), int(first_row), _ptr(b))
+        else:
+            rc = getattr(L, name + "_deterministic")(C.byref(params), *keys, int(noise_seed), _ptr(seed), int(first_row), *msg, _ptr(b), *count)
+    if rc != 0:
+        raise RtfheError(rc, name + " failed (non-binary key, bad parameters, or rows beyond 2^64)")
+    return seed, b
+
+
+def encrypt_lut_seeded(params, key1, tv, noise_seed=None, seed=None, first_row=0):
+    """encrypt_lut in seeded form: (seed, b) with b u32[n_lut][N] -- half of encrypt_lut's words; Engine.lut_encrypted_seeded uploads it and
+    seeded_expand gives the full rows.  noise_seed None (production): a fresh public seed from the OS, the noise from a separate OS-seeded
+    generator.  An integer noise_seed = TEST-ONLY deterministic noise, with the mask seed (u32[8]) and first_row given by the caller."""
+    tv = _np(tv, np.uint32).reshape(-1, params.N)
+    key1 = _np(key1, np.int32)
+    b = np.empty((tv.shape[0], params.N), np.uint32)
+    return _seeded_encrypt("rtfhe_trlwe_encrypt_torus_seeded", params, (_ptr(key1),), (_ptr(tv),), b, noise_seed, seed, first_row, (tv.shape[0],))
+
+
+def encrypt_selectors_seeded(params, key1, bits, noise_seed=None, seed=None, first_row=0):
+    """encrypt_selectors in seeded form: (seed, b) with b u32[count][2l][N]; Engine.selectors_seeded uploads it.  With bits = key0 this is the
+    seeded bootstrapping key (Engine.load_bk_seeded).  noise_seed / seed / first_row as in encrypt_lut_seeded."""
+    bits = _np(bits, np.uint8).reshape(-1)
+    key1 = _np(key1, np.int32)
+    b = np.empty((bits.size, 2 * params.l, params.N), np.uint32)
+    return _seeded_encrypt("rtfhe_trgsw_encrypt_bits_seeded", params, (_ptr(key1),), (_ptr(bits),), b, noise_seed, seed, first_row, (bits.size,))
+
+
+def encrypt_trgsw_polys_seeded(params, key1, mu, noise_seed=None, seed=None, first_row=0):
+    """encrypt_trgsw_polys in seeded form: (seed, b) with b u32[count][2l][N].  noise_seed / seed / first_row as in encrypt_lut_seeded."""
+    mu = _np(mu, np.int32).reshape(-1, params.N)
+    key1 = _np(key1, np.int32)
+    b = np.empty((mu.shape[0], 2 * params.l, params.N), np.uint32)
+    return _seeded_encrypt("rtfhe_trgsw_encrypt_polys_seeded", params, (_ptr(key1),), (_ptr(mu),), b, noise_seed, seed, first_row, (mu.shape[0],))
+
+
+def packing_keygen_seeded(params, key0, key1, noise_seed=None, seed=None, first_row=0):
+    """packing_keygen in seeded form: (seed, b) with b u32[n][t][base-1][N]; Engine.packing_key_seeded uploads it.  noise_seed / seed /
+    first_row as in encrypt_lut_seeded."""
+    key0, key1 = _np(key0, np.int32).reshape(-1), _np(key1, np.int32).reshape(-1)
+    assert key0.size == params.n and key1.size == params.N
+    b = np.empty((params.n, params.ks_t, (1 << params.ks_basebit) - 1, params.N), np.uint32)
+    return _seeded_encrypt("rtfhe_packing_keygen_seeded", params, (_ptr(key0), _ptr(key1)), (), b, noise_seed, seed, first_row)
 
 
 def trlwe_phase(params, key1, ct):
