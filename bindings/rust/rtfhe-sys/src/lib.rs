@@ -254,6 +254,22 @@ extern "C" {
     pub fn rtfhe_lut_create_encrypted_seeded(ctx: *mut rtfhe_ctx, seed: *const u32, first_row: u64, b: *const u32, n_lut: i32, out: *mut *mut rtfhe_lut) -> c_int;
     pub fn rtfhe_load_bk_seeded(ctx: *mut rtfhe_ctx, seed: *const u32, first_row: u64, b: *const u32) -> c_int;
     pub fn rtfhe_packing_key_create_seeded(ctx: *mut rtfhe_ctx, seed: *const u32, first_row: u64, b: *const u32, out: *mut *mut rtfhe_packing_key) -> c_int;
+    // seeded lvl0 ciphertexts and the seeded key-switching key: (seed [8], first_row, b [rows]) stands for u32[rows][n+1], a[0..n) then b; row R's
+    // mask is the same keystream cut at n words.  *_deterministic: TEST ONLY
+    pub fn rtfhe_tlwe_mask_expand(n: i32, seed: *const u32, first_row: u64, a: *mut u32, rows: usize) -> c_int;
+    pub fn rtfhe_tlwe_seeded_expand(p: *const rtfhe_params, seed: *const u32, first_row: u64, b: *const u32, out: *mut u32, rows: usize) -> c_int;
+    pub fn rtfhe_tlwe_encrypt_bits_seeded(p: *const rtfhe_params, key0: *const i32, bits: *const u8, seed: *mut u32, b: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_tlwe_encrypt_torus_seeded(p: *const rtfhe_params, key0: *const i32, mu: *const u32, seed: *mut u32, b: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_ksk_keygen_seeded(p: *const rtfhe_params, key0: *const i32, key1: *const i32, seed: *mut u32, b: *mut u32) -> c_int;
+    pub fn rtfhe_tlwe_encrypt_bits_seeded_deterministic(p: *const rtfhe_params, key0: *const i32, noise_seed: u64, seed: *const u32, first_row: u64,
+                                                        bits: *const u8, b: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_tlwe_encrypt_torus_seeded_deterministic(p: *const rtfhe_params, key0: *const i32, noise_seed: u64, seed: *const u32, first_row: u64,
+                                                         mu: *const u32, b: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_ksk_keygen_seeded_deterministic(p: *const rtfhe_params, noise_seed: u64, key0: *const i32, key1: *const i32, seed: *const u32,
+                                                 first_row: u64, b: *mut u32) -> c_int;
+    pub fn rtfhe_tlwe_seeded_expand_dev(ctx: *mut rtfhe_ctx, seed: *const u32, first_row: u64, d_b: *const c_void, d_out: *mut c_void, rows: usize,
+                                        stream: *mut c_void) -> c_int;
+    pub fn rtfhe_load_ksk_seeded(ctx: *mut rtfhe_ctx, seed: *const u32, first_row: u64, b: *const u32) -> c_int;
     // TEST ONLY (seeded xoshiro256**, not secure)
     pub fn rtfhe_ksk_expand_ref(p: *const rtfhe_params, key0: *const i32, key1: *const i32, ksk: *const u32, ksk_ref: *mut u32) -> c_int;
     pub fn rtfhe_ksk_expand_ref_deterministic(p: *const rtfhe_params, seed: u64, key0: *const i32, key1: *const i32, ksk: *const u32, ksk_ref: *mut u32) -> c_int;

@@ -974,6 +974,55 @@ int rtfhe_load_bk_seeded(rtfhe_ctx *ctx, const uint32_t *seed, uint64_t first_ro
 int rtfhe_packing_key_create_seeded(rtfhe_ctx *ctx, const uint32_t *seed, uint64_t first_row, const uint32_t *b /* [n][t][base-1][N] */,
                                     rtfhe_packing_key **out);
 
+/* ---- seeded lvl0 ciphertexts and the seeded key-switching key (no reference counterpart) ----
+ * A lvl0 row is n mask words and ONE word of information: gate, MUX, PBS and circuit inputs u32[n+1], and the 24,576 rows of the key-switching
+ * key.  A seeded lvl0 object ships a 32-byte seed and one word per row.
+ *
+ * THE MASK RULE FOR ROWS OF LENGTH n.  The stream is the one of the rule above, cut at n words.  Row R of a lvl0 object has
+ *     a[16 c + i] = word i of the ChaCha20 block (RFC 8439 2.3) with key = seed, the 64-bit block counter c in state words 12-13 and R in state
+ *                   words 14-15, for c = 0 .. ceil(n / 16) - 1; the words with 16 c + i >= n are discarded
+ * so for n a multiple of 16 the masks are rtfhe_mask_expand(N = n, ...)'s.  The mask word is the keystream word itself, all 32 bits.
+ *
+ * A seeded lvl0 object is (seed, first_row, b): b is u32[rows], row r masked by row first_row + r of the seed; the full layout is u32[rows][n+1],
+ * a[0 .. n) then b -- the layout of every lvl0 batch and of the key-switching key u32[N][t][base-1][n+1], whose row (i, l, d) is row
+ * (i t + l)(base - 1) + d.
+ *
+ * SECURITY RULES: those of the seeded ciphertexts above.  The seed is public; the noise never comes from it; the production encryptors draw a fresh
+ * seed per call, write it to `seed` and number rows from 0; only the *_deterministic forms take a seed and a first_row (TEST ONLY -- NOT SECURE).
+ * b = <a, key0> + message + e with the unseeded encryptors' message word and noise sampler (sigma = 2^-15).
+ *
+ * Every call returns RTFHE_ERR_INVALID before anything else happens for: a null pointer; n < 1 (a context's calls: n <= 767 by construction);
+ * rows = 0; first_row + rows beyond 2^64; b overlapping out; (encryptors, key generation) a non-binary key. */
+int rtfhe_tlwe_mask_expand(int32_t n, const uint32_t *seed /* [8] */, uint64_t first_row, uint32_t *a /* [rows][n] */, size_t rows);
+/* the full layout on the CPU: the oracle of the device form below and the path of a server without this library's GPU side */
+int rtfhe_tlwe_seeded_expand(const rtfhe_params *p, const uint32_t *seed /* [8] */, uint64_t first_row, const uint32_t *b /* [rows] */,
+                             uint32_t *out /* [rows][n+1] */, size_t rows);
+/* the seeded forms of rtfhe_tlwe_encrypt_bits and rtfhe_tlwe_encrypt_torus: each writes one b word per message, and the fresh seed */
+int rtfhe_tlwe_encrypt_bits_seeded(const rtfhe_params *p, const int32_t *key0, const uint8_t *bits /* [count] */, uint32_t *seed /* out [8] */,
+                                   uint32_t *b /* [count] */, size_t count);
+int rtfhe_tlwe_encrypt_torus_seeded(const rtfhe_params *p, const int32_t *key0, const uint32_t *mu /* [count] */, uint32_t *seed /* out [8] */,
+                                    uint32_t *b /* [count] */, size_t count);
+/* the key-switching key of rtfhe_keygen in seeded form: row (i, l, d) encrypts (d + 1) key1[i] 2^(32 - basebit (l + 1)) under key0 */
+int rtfhe_ksk_keygen_seeded(const rtfhe_params *p, const int32_t *key0, const int32_t *key1, uint32_t *seed /* out [8] */,
+                            uint32_t *b /* [N][t][base-1] */);
+/* TEST ONLY -- NOT SECURE: the noise reproducible from noise_seed through xoshiro256**, the mask seed and its first row the caller's */
+int rtfhe_tlwe_encrypt_bits_seeded_deterministic(const rtfhe_params *p, const int32_t *key0, uint64_t noise_seed, const uint32_t *seed /* [8] */,
+                                                 uint64_t first_row, const uint8_t *bits, uint32_t *b, size_t count);
+int rtfhe_tlwe_encrypt_torus_seeded_deterministic(const rtfhe_params *p, const int32_t *key0, uint64_t noise_seed, const uint32_t *seed /* [8] */,
+                                                  uint64_t first_row, const uint32_t *mu, uint32_t *b, size_t count);
+int rtfhe_ksk_keygen_seeded_deterministic(const rtfhe_params *p, uint64_t noise_seed, const int32_t *key0, const int32_t *key1,
+                                          const uint32_t *seed /* [8] */, uint64_t first_row, uint32_t *b);
+/* On the device (every backend, no key, the primary device of a multi-device context): one launch of k_tlwe_seeded_expand writes rows * (n + 1)
+ * words at d_out, the masks to columns 0 .. n - 1 and d_b[r] to column n; d_b stays as it is.  Asynchronous and ordered on `stream`; nothing is
+ * allocated and the seed travels in the launch itself, so the call may be captured first thing on a fresh stream.  d_b and d_out need 4-byte
+ * alignment only -- d_out may be a range of rows inside a larger wire table u32[..][n+1] -- and must not overlap; rows * ceil(n / 16) stays below
+ * 2^31.  This is how seeded inputs become the rows the *_dev batch calls read. */
+int rtfhe_tlwe_seeded_expand_dev(rtfhe_ctx *ctx, const uint32_t *seed /* host [8] */, uint64_t first_row, const void *d_b /* [rows] */,
+                                 void *d_out /* [rows][n+1] */, size_t rows, void *stream);
+/* rtfhe_load_ksk from the key's seeded form: uploads b (one word per row), makes the masks on the device in the staging buffer rtfhe_load_ksk copies
+ * its words into, and from there on IS rtfhe_load_ksk: same device layouts, peers' replicas, error codes and memory accounting. */
+int rtfhe_load_ksk_seeded(rtfhe_ctx *ctx, const uint32_t *seed, uint64_t first_row, const uint32_t *b /* [N][t][base-1] */);
+
 /* ---- wire format (flat little-endian files with an FNV-1a checksum; the reference has no serialization) ----
  * key file   "RTFHEKY1" | rtfhe_params | u32 flags (1 bk, 2 ksk, 4 secret keys) | u32 0 | [key0 | key1] | [bk] | [ksk] | u64 fnv
  * batch file "RTFHECT1" | i32 n | i32 0 | u64 count | u32[count][n+1] | u64 fnv */

@@ -6,7 +6,8 @@ package is the thin Python host side above it.  There is no CPU fallback anywher
 from ._ffi import AND, ANDNY, COPY, NAND, NOT, OR, XOR, Params, load  # noqa: F401
 from .engine import (Engine, FftPlan, Lut, PackingKey, PlainPolys, RtfheError, Selectors, decrypt_bits, demux_level_selector, device_link, encrypt_bits, encrypt_lut, encrypt_selectors, encrypt_torus, encrypt_trgsw_polys, keygen, ksk_expand_ref, load_keys,  # noqa: F401
                      load_tlwe, packing_keygen, phases, pinned_empty, save_keys, save_tlwe, shard_range, trlwe_phase,
-                     encrypt_lut_seeded, encrypt_selectors_seeded, encrypt_trgsw_polys_seeded, mask_expand, packing_keygen_seeded, seeded_expand)
+                     encrypt_lut_seeded, encrypt_selectors_seeded, encrypt_trgsw_polys_seeded, mask_expand, packing_keygen_seeded, seeded_expand,
+                     encrypt_bits_seeded, encrypt_torus_seeded, keygen_seeded, ksk_keygen_seeded, tlwe_mask_expand, tlwe_seeded_expand)
 from .pbs import decode_msgs, encode_msgs, lut_pack_layout, lut_polynomial, many_lut_polynomial  # noqa: F401
 from .lut_circuit import LutCircuitRunner, LutNetlist, lut_ripple_adder  # noqa: F401
 from .linear import dense_layer_bias, dense_layer_input, dense_layer_polys, dense_layer_trgsw  # noqa: F401
@@ -17,4 +18,5 @@ __all__ = ["Engine", "FftPlan", "Params", "RtfheError", "keygen", "ksk_expand_re
            "CmuxNetlist", "CmuxCircuit", "bdd_netlist", "cmux_tree_netlist", "trgsw_rotate_netlist", "demux_level_selector",
            "PackingKey", "packing_keygen", "lut_pack_layout", "PlainPolys", "dense_layer_polys", "dense_layer_input", "dense_layer_bias", "encrypt_trgsw_polys", "dense_layer_trgsw",
            "mask_expand", "seeded_expand", "encrypt_lut_seeded", "encrypt_selectors_seeded", "encrypt_trgsw_polys_seeded", "packing_keygen_seeded",
+           "tlwe_mask_expand", "tlwe_seeded_expand", "encrypt_bits_seeded", "encrypt_torus_seeded", "ksk_keygen_seeded", "keygen_seeded",
            "NAND", "AND", "OR", "XOR", "NOT", "COPY", "ANDNY", "load"]

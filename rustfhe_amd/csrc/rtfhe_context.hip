@@ -574,15 +574,16 @@ int rtfhe_export_bk_fft(rtfhe_ctx* ctx, double* bk_f) {
     return 0;
 }
 
-int rtfhe_load_ksk(rtfhe_ctx* ctx, const uint32_t* ksk) {
-    if (int rc = use(ctx)) return rc;
-    if (!ksk) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
-    const size_t rows = ksk_rows(ctx->p), w = (size_t)ctx->p.n + 1, ksw = (size_t)ctx->ksw;
-    // staging: rows padded to a multiple of 4 words (16-byte loads) + one all-zero row
-    std::vector<uint32_t> padded((rows + 1) * ksw, 0u);
-    for (size_t r = 0; r < rows; r++) std::memcpy(padded.data() + r * ksw, ksk + r * w, w * 4);
-    if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, padded.size() * 4)) return rc;
-    HIPCHECK(ctx, hipMemcpy(ctx->d_a, padded.data(), padded.size() * 4, hipMemcpyHostToDevice));
+}  // extern "C"
+
+// rtfhe_load_ksk from the point where the key's rows are wanted in the staging buffer ctx->d_a -- rows padded to ksw words, a multiple of 4 (16-byte
+// loads), plus one all-zero row: fill(rows, ksw) brings them there, done when the stream is next synchronised -- the caller's padded copy, or a
+// seeded key's expansion
+template <typename Fill>
+static int load_ksk_filled(rtfhe_ctx* ctx, Fill fill) {
+    const size_t rows = ksk_rows(ctx->p), ksw = (size_t)ctx->ksw;
+    if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, (rows + 1) * ksw * 4)) return rc;
+    if (int rc = fill(rows, ksw)) return rc;
     // device layout: the rows of two adjacent levels pre-summed (see ks_accumulate) + one all-zero row that "both digits 0" selects
     const size_t dev_rows = (size_t)ks_dev_rows(ctx->p.N, ctx->p.ks_t, ctx->p.ks_basebit);
     ctx->ksk_bytes = (dev_rows + 1) * ksw * 4;
@@ -611,6 +612,34 @@ int rtfhe_load_ksk(rtfhe_ctx* ctx, const uint32_t* ksk) {
         peer->has_ksk = true;
     }
     return 0;
+}
+
+extern "C" {
+
+int rtfhe_load_ksk(rtfhe_ctx* ctx, const uint32_t* ksk) {
+    if (int rc = use(ctx)) return rc;
+    if (!ksk) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    return load_ksk_filled(ctx, [&](size_t rows, size_t ksw) {
+        const size_t w = (size_t)ctx->p.n + 1;
+        std::vector<uint32_t> padded((rows + 1) * ksw, 0u);
+        for (size_t r = 0; r < rows; r++) std::memcpy(padded.data() + r * ksw, ksk + r * w, w * 4);
+        HIPCHECK(ctx, hipMemcpy(ctx->d_a, padded.data(), padded.size() * 4, hipMemcpyHostToDevice));
+        return 0;
+    });
+}
+
+// the same key from its seeded form (rtfhe_ksk_keygen_seeded): one b word per row goes up, the staging range is cleared (it is a reused buffer, and the
+// padding columns and the last row must be zero) and the masks are made in it on the primary device, rows ksw words apart
+int rtfhe_load_ksk_seeded(rtfhe_ctx* ctx, const uint32_t* seed, uint64_t first_row, const uint32_t* b) {
+    if (int rc = use(ctx)) return rc;
+    if (!seed || !b) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
+    if (int rc = tlwe_seeded_ready(ctx, "rtfhe_load_ksk_seeded", RTFHE_TLWE_SEEDED_UPLOAD, seed, first_row, b, nullptr, ksk_rows(ctx->p))) return rc;
+    return load_ksk_filled(ctx, [&](size_t rows, size_t ksw) {
+        if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, rows * 4)) return rc;
+        if (int rc = copy_in(ctx, ctx->d_b, b, rows * 4, 1)) return rc;
+        HIPCHECK(ctx, hipMemsetAsync(ctx->d_a, 0, (rows + 1) * ksw * 4, ctx->stream));
+        return launch_tlwe_seeded_expand(ctx, seed, first_row, (const uint32_t*)ctx->d_b, (uint32_t*)ctx->d_a, ksw, rows, ctx->stream);
+    });
 }
 
 // The reference's own container shape: KeySwitchingKey(Vec<[[TLWERep<M>; IKS_T]; IKS_L]>) with IKS_T = 2^IKS_BASEBIT = 4 entries per

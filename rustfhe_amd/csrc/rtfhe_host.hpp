@@ -19,8 +19,9 @@
 //                            (its argument checks: rtfhe_extract_plan.cpp, host only)
 //   rtfhe_plain.hip          exact TRLWE x plain-polynomial products: plain sets (integer polynomials as spectra), sums of up to eight products per sample
 //                            on the split-FFT exact backend's arithmetic, on every backend (its argument checks: rtfhe_plain_plan.cpp, host only)
-//   rtfhe_seeded.hip         seeded ciphertexts: masks expanded on the device from a public seed (k_seeded_expand), the staging step of the *_seeded
-//                            upload calls, which live beside their unseeded twins (its argument checks and the CPU form: rtfhe_seeded.cpp, host only)
+//   rtfhe_seeded.hip         seeded ciphertexts: masks expanded on the device from a public seed (k_seeded_expand for TRLWE rows, k_tlwe_seeded_expand
+//                            for lvl0 rows), the staging step of the *_seeded upload calls, which live beside their unseeded twins (its argument
+//                            checks and the CPU forms: rtfhe_seeded.cpp, rtfhe_tlwe_seeded.cpp, host only)
 // Every kernel is instantiated in exactly one of them.  No CPU fallback anywhere: an entry point runs HIP kernels or fails.
 #pragma once
 
@@ -38,6 +39,7 @@
 
 #include "rtfhe_kernels.hpp"
 #include "rtfhe_seeded_plan.h"
+#include "rtfhe_tlwe_seeded_plan.h"
 
 // ------------------------------------------------------------------------------------------------
 // twiddle tables (host).  Values follow the reference's table builders so that a context created in
@@ -289,6 +291,11 @@ int launch_seeded_expand(rtfhe_ctx* ctx, const uint32_t* seed, uint64_t first_ro
 // what a *_seeded upload call does where its unseeded twin copies the caller's words in: the host b halves up through ctx->d_b, then the expansion into
 // d_full, both queued on ctx->stream
 int stage_seeded(rtfhe_ctx* ctx, const uint32_t* seed, uint64_t first_row, const uint32_t* b, int group, size_t rows, void* d_full);
+// the same two for lvl0 rows (rtfhe_tlwe_seeded_plan at the context's n; k_tlwe_seeded_expand): d_out rows of `stride` >= n + 1 words, of which
+// columns 0 .. n are written -- the masks, then d_b [rows]
+int tlwe_seeded_ready(rtfhe_ctx* ctx, const char* name, int what, const void* seed, uint64_t first_row, const void* b, const void* out, size_t rows);
+int launch_tlwe_seeded_expand(rtfhe_ctx* ctx, const uint32_t* seed, uint64_t first_row, const uint32_t* d_b, uint32_t* d_out, size_t stride, size_t rows,
+                              hipStream_t s);
 // ---- the lifetime rule of the handles (rtfhe_context.hip) ----
 // a handle as a call's check sees it: its noun and type name for the messages, whether the caller gave one, and the context it hangs on
 struct HandleRef { const char* noun; const char* type; bool given; const rtfhe_ctx* owner; };

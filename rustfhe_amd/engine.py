@@ -144,6 +144,13 @@ class Engine(_Handle):
         assert ksk.size == self.p.ksk_words, "ksk must be u32[N][t][base-1][n+1]"
         self._ck(self.L.rtfhe_load_ksk(self.h, _ptr(ksk)))
 
+    def load_ksk_seeded(self, seed, b, first_row=0):
+        """load_ksk from the key's seeded form (rtfhe_load_ksk_seeded): b u32[N][t][base-1], one word per row, and the public seed
+        (rustfhe_amd.ksk_keygen_seeded) -- 98 KB go up where load_ksk ships 62.5 MB; the masks are made on the device."""
+        b = _np(b, np.uint32).reshape(-1)
+        assert b.size == self.p.ksk_words // (self.p.n + 1), "b must be u32[N][t][base-1]"
+        self._ck(self.L.rtfhe_load_ksk_seeded(self.h, _ptr(_seed(seed)), int(first_row), _ptr(b)))
+
     def load_ksk_ref(self, ksk_ref):
         """The reference's own shape, KeySwitchingKey(Vec<[[TLWERep; 4]; 8]>) flattened to u32[N][t][base][n+1]
         (hom_nand/src/tlwe.rs:243-245); the never-read entry t = base of every level is dropped by the library."""
@@ -484,6 +491,25 @@ class Engine(_Handle):
         """Uploads a packing key u32[n][t][base-1][2][N] (rustfhe_amd.packing_keygen) to the primary device in the operand order of the matrix
         pipe; a PackingKey handle, closed by close() or a with block."""
         return PackingKey(self, pk)
+
+    def tlwe_seeded_expand_dev(self, seed, d_b, d_out, rows, first_row=0, stream=None):
+        """One launch (rtfhe_tlwe_seeded_expand_dev): d_out [rows][n+1] words = the masks of rows first_row .. first_row + rows - 1 of the seed in
+        columns 0 .. n - 1 and d_b [rows] in column n; what rustfhe_amd.tlwe_seeded_expand computes on the CPU.  d_out needs 4-byte alignment only:
+        it may be a range of rows of a larger wire table.  Asynchronous on `stream`, nothing allocated, capturable first thing on a fresh stream."""
+        self._ck(self.L.rtfhe_tlwe_seeded_expand_dev(self.h, _ptr(_seed(seed)), int(first_row), self._dev(d_b), self._dev(d_out), int(rows),
+                                                     _stream(stream)))
+
+    def upload_tlwe_seeded(self, seed, b, first_row=0):
+        """Seeded lvl0 inputs (rustfhe_amd.encrypt_bits_seeded / encrypt_torus_seeded) to the device: copies b u32[rows] up, expands it there and
+        returns the int32 device tensor [rows][n+1] the *_dev batch calls read -- 4 bytes per row cross the bus, not 4 (n + 1).  Queued on torch's
+        current stream."""
+        import torch
+        b = _np(b, np.uint32).reshape(-1)
+        with torch.cuda.device(self.device):
+            d_b = torch.from_numpy(b.view(np.int32)).cuda()
+            d_out = torch.empty((b.size, self.p.n + 1), dtype=torch.int32, device="cuda")
+            self.tlwe_seeded_expand_dev(seed, d_b, d_out, b.size, first_row, torch.cuda.current_stream().cuda_stream)
+        return d_out
 
     def packing_key_seeded(self, seed, b, first_row=0):
         """packing_key from the key's seeded form (rtfhe_packing_key_create_seeded): b u32[n][t][base-1][N] and the public seed
@@ -1034,8 +1060,8 @@ def _seeded_encrypt(name, params, keys, msg, b, noise_seed, seed, first_row, cou
         rc = getattr(L, name)(C.byref(params), *keys, *msg, _ptr(seed), _ptr(b), *count)
     else:
         seed = _seed(seed)
-        if name == "rtfhe_packing_keygen_seeded":
-            rc = L.rtfhe_packing_keygen_seeded_deterministic(C.byref(params), int(noise_seed), *keys, _ptr(seed), int(first_row), _ptr(b))
+        if name in ("rtfhe_packing_keygen_seeded", "rtfhe_ksk_keygen_seeded"):
+            rc = getattr(L, name + "_deterministic")(C.byref(params), int(noise_seed), *keys, _ptr(seed), int(first_row), _ptr(b))
         else:
             rc = getattr(L, name + "_deterministic")(C.byref(params), *keys, int(noise_seed), _ptr(seed), int(first_row), *msg, _ptr(b), *count)
     if rc != 0:
@@ -1077,6 +1103,71 @@ def packing_keygen_seeded(params, key0, key1, noise_seed=None, seed=None, first_
     assert key0.size == params.n and key1.size == params.N
     b = np.empty((params.n, params.ks_t, (1 << params.ks_basebit) - 1, params.N), np.uint32)
     return _seeded_encrypt("rtfhe_packing_keygen_seeded", params, (_ptr(key0), _ptr(key1)), (), b, noise_seed, seed, first_row)
+
+
+# ---- seeded lvl0 ciphertexts (include/rtfhe.h, "seeded lvl0 ciphertexts"): a public seed and one b word per row stand for u32[rows][n+1] -------
+
+def tlwe_mask_expand(n, seed, rows, first_row=0):
+    """The masks of rows first_row .. first_row + rows - 1 of a seed at TLWE dimension n (rtfhe_tlwe_mask_expand): u32[rows][n], the keystream of
+    mask_expand cut at n words."""
+    L = _ffi.load()
+    a = np.empty((int(rows), max(int(n), 0)), np.uint32)
+    rc = L.rtfhe_tlwe_mask_expand(int(n), _ptr(_seed(seed)), int(first_row), _ptr(a), int(rows))
+    if rc != 0:
+        raise RtfheError(rc, "rtfhe_tlwe_mask_expand failed (n < 1, rows = 0, or first_row + rows beyond 2^64)")
+    return a
+
+
+def tlwe_seeded_expand(params, seed, b, first_row=0):
+    """The full rows of a seeded lvl0 object on the CPU (rtfhe_tlwe_seeded_expand): b u32[rows] -> u32[rows][n+1], a[0 .. n) then b."""
+    L = _ffi.load()
+    b = _np(b, np.uint32).reshape(-1)
+    out = np.empty((b.size, params.n + 1), np.uint32)
+    rc = L.rtfhe_tlwe_seeded_expand(C.byref(params), _ptr(_seed(seed)), int(first_row), _ptr(b), _ptr(out), b.size)
+    if rc != 0:
+        raise RtfheError(rc, "rtfhe_tlwe_seeded_expand failed (n < 1, rows = 0, or first_row + rows beyond 2^64)")
+    return out
+
+
+def encrypt_bits_seeded(params, key0, bits, noise_seed=None, seed=None, first_row=0):
+    """encrypt_bits in seeded form: (seed, b) with b u32[count], one word per bit; tlwe_seeded_expand gives encrypt_bits' rows and
+    Engine.upload_tlwe_seeded makes them on the device.  noise_seed / seed / first_row as in encrypt_lut_seeded."""
+    bits = _np(bits, np.uint8).reshape(-1)
+    key0 = _np(key0, np.int32)
+    b = np.empty(bits.size, np.uint32)
+    return _seeded_encrypt("rtfhe_tlwe_encrypt_bits_seeded", params, (_ptr(key0),), (_ptr(bits),), b, noise_seed, seed, first_row, (bits.size,))
+
+
+def encrypt_torus_seeded(params, key0, mu, noise_seed=None, seed=None, first_row=0):
+    """encrypt_torus in seeded form: (seed, b) with b u32[count].  noise_seed / seed / first_row as in encrypt_lut_seeded."""
+    mu = _np(mu, np.uint32).reshape(-1)
+    key0 = _np(key0, np.int32)
+    b = np.empty(mu.size, np.uint32)
+    return _seeded_encrypt("rtfhe_tlwe_encrypt_torus_seeded", params, (_ptr(key0),), (_ptr(mu),), b, noise_seed, seed, first_row, (mu.size,))
+
+
+def ksk_keygen_seeded(params, key0, key1, noise_seed=None, seed=None, first_row=0):
+    """The key-switching key of keygen in seeded form: (seed, b) with b u32[N][t][base-1], one word per row (98 KB at the default parameters
+    where the key is 62.5 MB); Engine.load_ksk_seeded uploads it.  noise_seed / seed / first_row as in encrypt_lut_seeded."""
+    key0, key1 = _np(key0, np.int32).reshape(-1), _np(key1, np.int32).reshape(-1)
+    assert key0.size == params.n and key1.size == params.N
+    b = np.empty((params.N, params.ks_t, (1 << params.ks_basebit) - 1), np.uint32)
+    return _seeded_encrypt("rtfhe_ksk_keygen_seeded", params, (_ptr(key0), _ptr(key1)), (), b, noise_seed, seed, first_row)
+
+
+def keygen_seeded(params, seed=None):
+    """The secret keys and both halves of the evaluation key in seeded form: (key0, key1, (bk_seed, bk_b), (ksk_seed, ksk_b)) for
+    Engine.load_bk_seeded and Engine.load_ksk_seeded -- 15.7 MB at the default parameters where keygen's keys are 93.7 MB.  The bootstrapping key
+    is encrypt_selectors_seeded with bits = key0; the two mask seeds are independent.  seed None (production): everything from the OS CSPRNG; an
+    integer seed = TEST-ONLY deterministic generation (mask seeds and noise derived from it)."""
+    key0, key1, _, _ = keygen(params, seed, want_bk=False, want_ksk=False)
+    if seed is None:
+        return key0, key1, encrypt_selectors_seeded(params, key1, key0), ksk_keygen_seeded(params, key0, key1)
+    rng = np.random.default_rng(int(seed))
+    masks = rng.integers(0, 1 << 32, (2, 8), dtype=np.uint64).astype(np.uint32)
+    noise = [int(v) for v in rng.integers(0, 1 << 63, 2)]
+    return (key0, key1, encrypt_selectors_seeded(params, key1, key0, noise_seed=noise[0], seed=masks[0]),
+            ksk_keygen_seeded(params, key0, key1, noise_seed=noise[1], seed=masks[1]))
 
 
 def trlwe_phase(params, key1, ct):
