@@ -4,10 +4,11 @@ The product is the C-ABI shared library librtfhe_hip.so (include/rtfhe.h, rustfh
 package is the thin Python host side above it.  There is no CPU fallback anywhere in the package.
 """
 from ._ffi import AND, ANDNY, COPY, NAND, NOT, OR, XOR, Params, load  # noqa: F401
-from .engine import (Engine, FftPlan, Lut, PackingKey, PlainPolys, RtfheError, Selectors, decrypt_bits, demux_level_selector, device_link, encrypt_bits, encrypt_lut, encrypt_selectors, encrypt_torus, encrypt_trgsw_polys, keygen, ksk_expand_ref, load_keys,  # noqa: F401
-                     load_tlwe, packing_keygen, phases, pinned_empty, save_keys, save_tlwe, shard_range, trlwe_phase,
+from .client import (RtfheError, decrypt_bits, encrypt_bits, encrypt_lut, encrypt_selectors, encrypt_torus, encrypt_trgsw_polys, keygen, ksk_expand_ref, load_keys,  # noqa: F401
+                     load_tlwe, packing_keygen, phases, save_keys, save_tlwe, trlwe_phase,
                      encrypt_lut_seeded, encrypt_selectors_seeded, encrypt_trgsw_polys_seeded, mask_expand, packing_keygen_seeded, seeded_expand,
                      encrypt_bits_seeded, encrypt_torus_seeded, keygen_seeded, ksk_keygen_seeded, tlwe_mask_expand, tlwe_seeded_expand)
+from .engine import Engine, FftPlan, Lut, PackingKey, PlainPolys, Selectors, demux_level_selector, device_link, pinned_empty, shard_range  # noqa: F401
 from .pbs import decode_msgs, encode_msgs, lut_pack_layout, lut_polynomial, many_lut_polynomial  # noqa: F401
 from .lut_circuit import LutCircuitRunner, LutNetlist, lut_ripple_adder  # noqa: F401
 from .linear import dense_layer_bias, dense_layer_input, dense_layer_polys, dense_layer_trgsw  # noqa: F401

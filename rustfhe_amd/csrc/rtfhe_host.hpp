@@ -21,7 +21,8 @@
 //                            on the split-FFT exact backend's arithmetic, on every backend (its argument checks: rtfhe_plain_plan.cpp, host only)
 //   rtfhe_seeded.hip         seeded ciphertexts: masks expanded on the device from a public seed (k_seeded_expand for TRLWE rows, k_tlwe_seeded_expand
 //                            for lvl0 rows), the staging step of the *_seeded upload calls, which live beside their unseeded twins (its argument
-//                            checks and the CPU forms: rtfhe_seeded.cpp, rtfhe_tlwe_seeded.cpp, host only)
+//                            checks and the CPU forms: rtfhe_seeded.cpp, host only; the encryptor core it shares with rtfhe_keygen.cpp:
+//                            rtfhe_encrypt.hpp)
 // Every kernel is instantiated in exactly one of them.  No CPU fallback anywhere: an entry point runs HIP kernels or fails.
 #pragma once
 
@@ -39,7 +40,6 @@
 
 #include "rtfhe_kernels.hpp"
 #include "rtfhe_seeded_plan.h"
-#include "rtfhe_tlwe_seeded_plan.h"
 
 // ------------------------------------------------------------------------------------------------
 // twiddle tables (host).  Values follow the reference's table builders so that a context created in

@@ -1,6 +1,6 @@
 // rtfhe_kernels_tlwe_seeded.hpp -- k_tlwe_seeded_expand: a seeded lvl0 object (public seed, first row, one b word per row) into rows of
 // n + 1 words, a[0 .. n) then b, in one launch (include/rtfhe.h, "seeded lvl0 ciphertexts"; the CPU form and oracle: rtfhe_tlwe_seeded_expand in
-// rtfhe_tlwe_seeded.cpp).  A lane owns one ChaCha20 block (row r, block c) of the rows * ceil(n / 16) there are, but does not store it itself: n is
+// rtfhe_seeded.cpp).  A lane owns one ChaCha20 block (row r, block c) of the rows * ceil(n / 16) there are, but does not store it itself: n is
 // no multiple of 16 and a row starts at any word, so no 16-byte store can be assumed, and 16 dword stores per lane would touch 64 separate 4-byte
 // pieces each.  The wave's 64 blocks pass through a wave-private LDS image instead (17-word pitch: the 32 lanes of a ds_write_b32 group land
 // on 32 banks), and in each of the 16 store instructions lane L writes word 64 j + L of the image: consecutive lanes, consecutive words of a row, a

@@ -1,5 +1,5 @@
-// rtfhe_sampling.hpp -- host only: the random generators and the torus samplers behind the host-side key generation and encryption, shared by
-// rtfhe_keygen.cpp and rtfhe_seeded.cpp so that a seeded ciphertext's noise and message words are drawn exactly as an unseeded one's.
+// rtfhe_sampling.hpp -- host only: the random generators and the torus samplers behind the host-side key generation and encryption: what the
+// encryptor core (rtfhe_encrypt.hpp) of rtfhe_keygen.cpp and rtfhe_seeded.cpp draws every noise sample and forms every message word with.
 //   torus!(f32)                utils/src/math.rs:691-696
 // Randomness.  The reference draws every mask, noise sample and key bit from rand::thread_rng (a ChaCha-based CSPRNG seeded from the OS;
 // utils/src/math.rs:417-479).  The production entry points do the same: a 256-bit key from getrandom(2) (falling back to /dev/urandom), expanded

@@ -2,14 +2,12 @@
 // upload calls): the one launch of k_seeded_expand (TRLWE rows) and of k_tlwe_seeded_expand (lvl0 rows), and the staging step the upload calls
 // share -- the b halves go up through the context's staging buffer d_b (half the bytes of the unseeded upload) and are expanded into the buffer
 // the unseeded twin copies its words into; from there on each upload call runs its twin's own code (the twins' units; rtfhe_load_ksk_seeded,
-// whose b is one word per row, stages it beside rtfhe_load_ksk in rtfhe_context.hip).  The argument checks are host-only: rtfhe_seeded.cpp,
-// rtfhe_tlwe_seeded.cpp.
+// whose b is one word per row, stages it beside rtfhe_load_ksk in rtfhe_context.hip).  The argument checks are host-only: rtfhe_seeded.cpp.
 #include "rtfhe_host.hpp"
 
 #include "rtfhe_kernels_seeded.hpp"
 #include "rtfhe_kernels_tlwe_seeded.hpp"
 #include "rtfhe_seeded_plan.h"
-#include "rtfhe_tlwe_seeded_plan.h"
 
 using namespace rtfhe;
 using namespace rtfhe_host;

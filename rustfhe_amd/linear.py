@@ -32,7 +32,7 @@ def dense_layer_trgsw(rp, key1, W, d, seed=None):
     """dense_layer_polys with the weights encrypted by the key holder: (trgsw, coef), trgsw u32[n_poly][2][2l][N] the TRGSW encryptions under
     key1 of the weight polynomials (encrypt_trgsw_polys; Engine.selectors uploads them, Engine.trlwe_mul_trgsw_batch multiplies), coef as
     dense_layer_polys gives it.  seed: encrypt_trgsw_polys's (None in production)."""
-    from .engine import encrypt_trgsw_polys
+    from .client import encrypt_trgsw_polys
     polys, coef = dense_layer_polys(W, d, rp.N)
     return encrypt_trgsw_polys(rp, key1, polys, seed), coef
 

@@ -173,7 +173,7 @@ class LutCircuitRunner(_Handle):
             d = self.desc
             tv = self.net.polynomials(self.e.p.N)
             if self.key1 is not None:
-                from .engine import encrypt_lut
+                from .client import encrypt_lut
                 lut = self.e.lut_encrypted(encrypt_lut(self.e.p, self.key1, tv, self.seed))
             else:
                 lut = self.e.lut(tv)

@@ -1,4 +1,4 @@
-/* Walks the host-only unit of the seeded lvl0 ciphertexts (rustfhe_amd/csrc/rtfhe_tlwe_seeded.cpp: the mask rule for rows of length n on the CPU,
+/* Walks the host-only unit of the seeded lvl0 ciphertexts (rustfhe_amd/csrc/rtfhe_seeded.cpp: the mask rule for rows of length n on the CPU,
  * the seeded lvl0 encryptors, the seeded key-switching key and every argument check of the seeded lvl0 calls) under AddressSanitizer +
  * UndefinedBehaviorSanitizer.  No device is needed: nothing in that unit makes a HIP call.  Every buffer is heap-allocated at exactly the size
  * the header promises, so that an access past it is caught -- a row of n words whose last ChaCha20 block is partial above all; the plan's buffers
@@ -8,7 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "rtfhe.h"
-#include "rtfhe_tlwe_seeded_plan.h"
+#include "rtfhe_seeded_plan.h"
 
 #define CHECK(c) do { if (!(c)) { fprintf(stderr, "CHECK failed: %s (line %d)\n", #c, __LINE__); exit(1); } } while (0)
 

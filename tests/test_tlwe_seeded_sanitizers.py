@@ -1,4 +1,4 @@
-"""CPU: the host-only unit of the seeded lvl0 ciphertexts (rustfhe_amd/csrc/rtfhe_tlwe_seeded.cpp: the mask rule for rows of length n, the
+"""CPU: the host-only unit of the seeded lvl0 ciphertexts (rustfhe_amd/csrc/rtfhe_seeded.cpp: the mask rule for rows of length n, the
 seeded lvl0 encryptors, the seeded key-switching key, every argument check of the seeded lvl0 calls) compiled by g++ under AddressSanitizer +
 UndefinedBehaviorSanitizer and driven from a stand-alone C host (tests/c/tlwe_seeded_sanitize_main.c), together with rtfhe_seeded.cpp, whose
 rtfhe_mask_expand the walk ties the new rule to.  Nothing in them makes a HIP call, so no device is needed, and nothing is loaded into Python."""
@@ -18,7 +18,7 @@ def test_tlwe_seeded_unit_under_asan_and_ubsan(tmp_path):
     san = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Wextra", "-pthread"]
     inc = ["-I", os.path.join(ROOT, "include"), "-I", csrc]
     units = []
-    for name in ("rtfhe_tlwe_seeded", "rtfhe_seeded"):
+    for name in ("rtfhe_seeded",):
         units.append(str(tmp_path / (name + ".o")))
         subprocess.check_call(["g++", "-std=c++17"] + san + inc + ["-c", os.path.join(csrc, name + ".cpp"), "-o", units[-1]])
     main = tmp_path / "main.o"
