@@ -21,17 +21,58 @@ void circuit_release(rtfhe_circuit* c) {
     c->exec = nullptr; c->graph = nullptr; c->d_samples = nullptr; c->d_owned.clear();
 }
 
-// ---- LUT circuits: the gather / scatter launches around a wave's many-LUT PBS ----
+// a circuit's own device buffers: listed in d_owned as they are allocated, so that circuit_release frees the ones that exist
+int circuit_own(rtfhe_ctx* ctx, rtfhe_circuit* c, const char* name, std::initializer_list<std::pair<void**, size_t>> bufs) {
+    for (const auto& [pp, bytes] : bufs) {
+        if (hipMalloc(pp, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, RTFHE_ERR_HIP, std::string(name) + ": hipMalloc"); }
+        c->d_owned.push_back(*pp);
+    }
+    return 0;
+}
+
+int circuit_fill(rtfhe_ctx* ctx, const char* name, void* d_desc, const std::vector<int32_t>& desc, void* d_tv, const rtfhe_lut* lut, void* d_zero, size_t zero_bytes) {
+    if (hipMemcpy(d_desc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_tv, lut->d_tv[0], lut_bytes(ctx, lut), hipMemcpyDeviceToDevice) != hipSuccess || hipMemset(d_zero, 0, zero_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, RTFHE_ERR_HIP, std::string(name) + ": hipMemcpy / hipMemset");
+    }
+    return 0;
+}
+
+// The recorder's rule.  Nothing but kernel launches may happen inside the capture, so whatever allocates or synchronises is the
+// caller's business before it calls.  Once the capture has begun there is no return before it has ended: enqueue's failure is kept and reported
+// first, then the capture's.  tlwe1_capture is never left set, and the launches enqueue counted leave the context's counter whether it failed
+// or not: a replay adds them (rtfhe_circuit_launch), the recording adds nothing.  On every failure c goes with this function's return
+// (CircuitDrop), no context lists it and *out stays as the caller set it: null.
+int circuit_record(rtfhe_ctx* ctx, NewCircuit c, StreamScratch* capture_samples, rtfhe_circuit** out, const std::function<int()>& enqueue) {
+    const auto hip_fail = [&](const char* call, hipError_t e) { return fail(ctx, RTFHE_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e)); };
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return hip_fail("hipStreamSynchronize", e);
+    e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) return hip_fail("hipStreamBeginCapture", e);
+    const int64_t before = ctx->launches;
+    ctx->tlwe1_capture = capture_samples;
+    const int rc = enqueue();
+    ctx->tlwe1_capture = nullptr;
+    e = hipStreamEndCapture(ctx->stream, &c->graph);
+    c->launches = ctx->launches - before;
+    ctx->launches = before;
+    if (rc) return rc;
+    if (e != hipSuccess) return hip_fail("hipStreamEndCapture", e);
+    e = hipGraphInstantiate(&c->exec, c->graph, nullptr, nullptr, 0);
+    if (e != hipSuccess) return hip_fail("hipGraphInstantiate", e);
+    ctx->circuits.push_back(c.get());
+    *out = c.release();
+    return 0;
+}
+
+// ---- LUT circuits: the gather / scatter launches around a wave's many-LUT PBS (a wave per node / per output row, LUTC_WAVES waves per workgroup) ----
 namespace {
 
 template <int F>
 int launch_lut_gather_f(rtfhe_ctx* ctx, bool vec, const LutGatherArgs& a, hipStream_t s) {
     const dim3 grid((a.count + LUTC_WAVES - 1) / LUTC_WAVES), block(64 * LUTC_WAVES);
-    if (vec) hipLaunchKernelGGL((k_lut_gather<F, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_lut_gather<F, false>), grid, block, 0, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
+    return vec ? launch_kernel(ctx, k_lut_gather<F, true>, grid, block, 0, s, a) : launch_kernel(ctx, k_lut_gather<F, false>, grid, block, 0, s, a);
 }
 
 int launch_lut_gather(rtfhe_ctx* ctx, int fan_in, bool vec, const LutGatherArgs& a, hipStream_t s) {
@@ -50,11 +91,7 @@ int launch_lut_gather(rtfhe_ctx* ctx, int fan_in, bool vec, const LutGatherArgs&
 
 int launch_lut_scatter(rtfhe_ctx* ctx, bool vec, const LutScatterArgs& a, hipStream_t s) {
     const dim3 grid((a.rows + LUTC_WAVES - 1) / LUTC_WAVES), block(64 * LUTC_WAVES);
-    if (vec) hipLaunchKernelGGL((k_lut_scatter<true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_lut_scatter<false>), grid, block, 0, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
+    return vec ? launch_kernel(ctx, k_lut_scatter<true>, grid, block, 0, s, a) : launch_kernel(ctx, k_lut_scatter<false>, grid, block, 0, s, a);
 }
 
 std::string at(int32_t w, int64_t g) { return "wave " + std::to_string(w) + ", node " + std::to_string(g) + ": "; }
@@ -91,39 +128,27 @@ int rtfhe_circuit_create(rtfhe_ctx* ctx, const void* d_ops, const void* d_idx0, 
     if (int rc = backend_prepare(ctx)) return rc;          // nothing but kernel launches may happen inside the capture
     for (int32_t w = 0; w < num_waves; w++)                // ... so the key layouts the waves' dispatches read are built now
         if (int rc = ensure_bk_layouts(ctx, (size_t)(wave_offsets[w + 1] - wave_offsets[w]), MODE_GATE)) return rc;
+    NewCircuit c(new (std::nothrow) rtfhe_circuit());
+    if (!c) return fail(ctx, RTFHE_ERR_NOMEM, "out of host memory");
+    c->ctx = ctx; c->device = ctx->device; c->waves = num_waves; c->backend = ctx->backend;
     StreamScratch cbuf;                                 // ... so the circuit's own sample buffer (split path) is allocated now
     if (ctx->ks_mm_min > 0 && ctx->d_ksmat) {
         size_t widest = 0;
         for (int32_t w = 0; w < num_waves; w++) widest = std::max(widest, (size_t)(wave_offsets[w + 1] - wave_offsets[w]));
         if (int rc = ensure_tlwe1(ctx, cbuf, widest)) return rc;
+        c->d_samples = cbuf.d[0];
     }
-    rtfhe_circuit* c = new (std::nothrow) rtfhe_circuit();
-    if (!c) { if (cbuf.d[0]) (void)hipFree(cbuf.d[0]); return fail(ctx, RTFHE_ERR_NOMEM, "out of host memory"); }
-    c->ctx = ctx; c->device = ctx->device; c->waves = num_waves; c->d_samples = cbuf.d[0]; c->backend = ctx->backend;
-    const int64_t before = ctx->launches;
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { circuit_release(c); delete c; return fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e)); }
-    e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) { circuit_release(c); delete c; return fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e)); }
-    int rc = 0;
-    ctx->tlwe1_capture = cbuf.d[0] ? &cbuf : nullptr;
-    for (int32_t w = 0; w < num_waves && !rc; w++) {
-        const size_t off = (size_t)wave_offsets[w], cnt = (size_t)(wave_offsets[w + 1] - wave_offsets[w]);
-        rc = launch_bootstrap(ctx, RTFHE_COPY, MODE_GATE, ctx->p.n, d_wires, d_wires, d_wires, cnt, ctx->stream,
-                              (const int32_t*)d_ops + off, (const int32_t*)d_idx0 + off, (const int32_t*)d_idx1 + off,
-                              (const int32_t*)d_idx_out + off, (int32_t)num_wires);
-    }
-    ctx->tlwe1_capture = nullptr;
-    e = hipStreamEndCapture(ctx->stream, &c->graph);
-    c->launches = ctx->launches - before;
-    ctx->launches = before;
-    if (rc) { circuit_release(c); delete c; return rc; }
-    if (e != hipSuccess) { circuit_release(c); delete c; return fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e)); }
-    e = hipGraphInstantiate(&c->exec, c->graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) { circuit_release(c); delete c; return fail(ctx, RTFHE_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
-    ctx->circuits.push_back(c);
-    *out = c;
-    return 0;
+    // recorded by circuit_record, under its rule; no sample buffer, no split path: split_ok and the key switch's timer bracketing read tlwe1_capture
+    return circuit_record(ctx, std::move(c), cbuf.d[0] ? &cbuf : nullptr, out, [&] {
+        int rc = 0;
+        for (int32_t w = 0; w < num_waves && !rc; w++) {
+            const size_t off = (size_t)wave_offsets[w], cnt = (size_t)(wave_offsets[w + 1] - wave_offsets[w]);
+            rc = launch_bootstrap(ctx, RTFHE_COPY, MODE_GATE, ctx->p.n, d_wires, d_wires, d_wires, cnt, ctx->stream,
+                                  (const int32_t*)d_ops + off, (const int32_t*)d_idx0 + off, (const int32_t*)d_idx1 + off,
+                                  (const int32_t*)d_idx_out + off, (int32_t)num_wires);
+        }
+        return rc;
+    });
 }
 
 // ---- a LUT circuit: waves of "weighted sum of wires, then a many-LUT PBS", recorded like rtfhe_circuit_create ----
@@ -184,12 +209,11 @@ int rtfhe_lut_circuit_create(rtfhe_ctx* ctx, const rtfhe_lut* lut, int32_t fan_i
         if (int rc = ensure_bk_layouts(ctx, (size_t)(wave_offsets[w + 1] - wave_offsets[w]), MODE_EXTRACT)) return rc;
     const int32_t first = wave_offsets[0], nodes = wave_offsets[num_waves] - first, rows = out_base[num_waves];
     const size_t n1 = (size_t)ctx->p.n + 1;
-    rtfhe_circuit* c = new (std::nothrow) rtfhe_circuit();
+    NewCircuit c(new (std::nothrow) rtfhe_circuit());
     if (!c) return fail(ctx, RTFHE_ERR_NOMEM, "out of host memory");
     c->ctx = ctx; c->device = ctx->device; c->waves = num_waves; c->backend = ctx->backend;
-    auto bail = [&](int rc) { circuit_release(c); delete c; return rc; };
     StreamScratch cbuf;
-    if (int rc = ensure_tlwe1(ctx, cbuf, widest_rows)) return bail(rc);
+    if (int rc = ensure_tlwe1(ctx, cbuf, widest_rows)) return rc;
     c->d_samples = cbuf.d[0];
     // description: in_idx, weights [nodes][fan_in] | cst, lut_idx [nodes] | out_idx [rows]
     const size_t desc_words = (size_t)nodes * (2 * fan_in + 2) + rows;
@@ -205,53 +229,31 @@ int rtfhe_lut_circuit_create(rtfhe_ctx* ctx, const rtfhe_lut* lut, int32_t fan_i
     if (lut_idx) std::memcpy(h_lut, lut_idx + first, (size_t)nodes * 4);
     std::memcpy(h_out, out_idx, (size_t)rows * 4);
     void *d_desc = nullptr, *d_gather = nullptr, *d_ks = nullptr, *d_tv = nullptr;
-    const size_t tv_bytes = (size_t)lut->n_lut * ctx->p.N * (lut->encrypted ? 2 : 1) * 4;      // an encrypted table's rows are TRLWEs: 2N words
-    const std::pair<void**, size_t> bufs[] = {{&d_desc, desc_words * 4}, {&d_gather, widest * n1 * 4}, {&d_ks, widest_rows * n1 * 4}, {&d_tv, tv_bytes}};
-    for (const auto& [pp, bytes] : bufs) {
-        if (hipMalloc(pp, bytes) != hipSuccess) { (void)hipGetLastError(); return bail(fail(ctx, RTFHE_ERR_HIP, "rtfhe_lut_circuit_create: hipMalloc")); }
-        c->d_owned.push_back(*pp);
-    }
-    if (hipMemcpy(d_desc, desc.data(), desc_words * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_tv, lut->d_tv[0], tv_bytes, hipMemcpyDeviceToDevice) != hipSuccess ||
-        hipMemset(d_ks, 0, widest_rows * n1 * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        return bail(fail(ctx, RTFHE_ERR_HIP, "rtfhe_lut_circuit_create: hipMemcpy / hipMemset"));
-    }
+    if (int rc = circuit_own(ctx, c.get(), "rtfhe_lut_circuit_create",
+                             {{&d_desc, desc_words * 4}, {&d_gather, widest * n1 * 4}, {&d_ks, widest_rows * n1 * 4}, {&d_tv, lut_bytes(ctx, lut)}})) return rc;
+    if (int rc = circuit_fill(ctx, "rtfhe_lut_circuit_create", d_desc, desc, d_tv, lut, d_ks, widest_rows * n1 * 4)) return rc;
     const int32_t* d_in = (const int32_t*)d_desc;
     const int32_t* d_wt = d_in + (size_t)nodes * fan_in;
     const uint32_t* d_cst = (const uint32_t*)(d_wt + (size_t)nodes * fan_in);
     const int32_t* d_lut = (const int32_t*)d_cst + nodes;
     const int32_t* d_out = d_lut + nodes;
     const bool vec = n1 % 4 == 0 && (uintptr_t)d_wires % 16 == 0;      // (the circuit's own buffers come from hipMalloc)
-    const int64_t before = ctx->launches;
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return bail(fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e)));
-    e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) return bail(fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e)));
-    int rc = 0;
-    ctx->tlwe1_capture = &cbuf;
-    for (int32_t w = 0; w < num_waves && !rc; w++) {
-        const int32_t off = wave_offsets[w] - first, cnt = wave_offsets[w + 1] - wave_offsets[w], th = wave_n_out[w];
-        const int32_t shift = th == 1 ? 0 : th == 2 ? 1 : th == 4 ? 2 : 3;
-        const LutGatherArgs ga{(const uint32_t*)d_wires, (uint32_t*)d_gather, d_in + (size_t)off * fan_in, d_wt + (size_t)off * fan_in, d_cst + off, cnt,
-                               (int32_t)n1, nw};
-        rc = launch_lut_gather(ctx, fan_in, vec, ga, ctx->stream);
-        if (!rc) rc = launch_pbs_many(ctx, LutRef{(const uint32_t*)d_tv, lut_idx ? d_lut + off : nullptr, lut->n_lut, shift, lut->encrypted, ctx->decomp == RTFHE_DECOMP_ROUNDED}, d_gather, d_ks, (size_t)cnt,
-                                      ctx->stream, false);      // (d_ks is zero: cleared at creation and by every scatter, no memset node)
-        const LutScatterArgs sa{(uint32_t*)d_ks, (uint32_t*)d_wires, d_out + out_base[w], cnt * th, (int32_t)n1, nw};
-        if (!rc) rc = launch_lut_scatter(ctx, vec, sa, ctx->stream);
-    }
-    ctx->tlwe1_capture = nullptr;
-    e = hipStreamEndCapture(ctx->stream, &c->graph);
-    c->launches = ctx->launches - before;
-    ctx->launches = before;
-    if (rc) return bail(rc);
-    if (e != hipSuccess) return bail(fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e)));
-    e = hipGraphInstantiate(&c->exec, c->graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) return bail(fail(ctx, RTFHE_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)));
-    ctx->circuits.push_back(c);
-    *out = c;
-    return 0;
+    // recorded by circuit_record, under its rule
+    return circuit_record(ctx, std::move(c), &cbuf, out, [&] {
+        int rc = 0;
+        for (int32_t w = 0; w < num_waves && !rc; w++) {
+            const int32_t off = wave_offsets[w] - first, cnt = wave_offsets[w + 1] - wave_offsets[w], th = wave_n_out[w];
+            const int32_t shift = th == 1 ? 0 : th == 2 ? 1 : th == 4 ? 2 : 3;
+            const LutGatherArgs ga{(const uint32_t*)d_wires, (uint32_t*)d_gather, d_in + (size_t)off * fan_in, d_wt + (size_t)off * fan_in, d_cst + off, cnt,
+                                   (int32_t)n1, nw};
+            rc = launch_lut_gather(ctx, fan_in, vec, ga, ctx->stream);
+            if (!rc) rc = launch_pbs_many(ctx, LutRef{(const uint32_t*)d_tv, lut_idx ? d_lut + off : nullptr, lut->n_lut, shift, lut->encrypted, ctx->decomp == RTFHE_DECOMP_ROUNDED}, d_gather, d_ks, (size_t)cnt,
+                                          ctx->stream, false);      // (d_ks is zero: cleared at creation and by every scatter, no memset node)
+            const LutScatterArgs sa{(uint32_t*)d_ks, (uint32_t*)d_wires, d_out + out_base[w], cnt * th, (int32_t)n1, nw};
+            if (!rc) rc = launch_lut_scatter(ctx, vec, sa, ctx->stream);
+        }
+        return rc;
+    });
 }
 
 int rtfhe_circuit_launch(rtfhe_circuit* c, void* stream) {

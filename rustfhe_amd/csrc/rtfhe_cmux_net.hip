@@ -51,14 +51,13 @@ int rtfhe_cmux_circuit_create(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const rtfh
     // everything that allocates or synchronises happens now, outside the capture
     const LeveledTwins<CmuxNetArgs> net = net_twins(ctx);
     if (int rc = prime_leveled(ctx, net)) return rc;
-    rtfhe_circuit* c = new (std::nothrow) rtfhe_circuit();
+    NewCircuit c(new (std::nothrow) rtfhe_circuit());
     if (!c) return fail(ctx, RTFHE_ERR_NOMEM, "out of host memory");
     c->ctx = ctx; c->device = ctx->device; c->waves = n_levels; c->backend = ctx->backend; c->sel = sel;
-    auto bail = [&](int rc) { circuit_release(c); delete c; return rc; };
     const size_t samples = count * (size_t)n_out;
     StreamScratch cbuf;
     if (extract) {
-        if (int rc = ensure_tlwe1(ctx, cbuf, samples)) return bail(rc);
+        if (int rc = ensure_tlwe1(ctx, cbuf, samples)) return rc;
         c->d_samples = cbuf.d[0];
     }
     // description: var, hi, lo, rot, order [n_nodes] each | out_ref, out_coef [n_out] each
@@ -72,17 +71,9 @@ int rtfhe_cmux_circuit_create(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const rtfh
     std::memcpy(&desc[(size_t)n_nodes * 5], out_ref, (size_t)n_out * 4);
     if (out_coef) std::memcpy(&desc[(size_t)n_nodes * 5 + n_out], out_coef, (size_t)n_out * 4);
     void *d_desc = nullptr, *d_nodes = nullptr, *d_ok = nullptr, *d_tv = nullptr;
-    const size_t tv_bytes = (size_t)lut->n_lut * ctx->p.N * (lut->encrypted ? 2 : 1) * 4;      // an encrypted table's rows are TRLWEs: 2N words
-    const std::pair<void**, size_t> bufs[] = {{&d_desc, desc_words * 4}, {&d_nodes, node_bytes}, {&d_ok, count * 4}, {&d_tv, tv_bytes}};
-    for (const auto& [pp, bytes] : bufs) {
-        if (hipMalloc(pp, bytes) != hipSuccess) { (void)hipGetLastError(); return bail(fail(ctx, RTFHE_ERR_HIP, "rtfhe_cmux_circuit_create: hipMalloc")); }
-        c->d_owned.push_back(*pp);
-    }
-    if (hipMemcpy(d_desc, desc.data(), desc_words * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_tv, lut->d_tv[0], tv_bytes, hipMemcpyDeviceToDevice) != hipSuccess || hipMemset(d_ok, 0, count * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        return bail(fail(ctx, RTFHE_ERR_HIP, "rtfhe_cmux_circuit_create: hipMemcpy / hipMemset"));
-    }
+    if (int rc = circuit_own(ctx, c.get(), "rtfhe_cmux_circuit_create",
+                             {{&d_desc, desc_words * 4}, {&d_nodes, node_bytes}, {&d_ok, count * 4}, {&d_tv, lut_bytes(ctx, lut)}})) return rc;
+    if (int rc = circuit_fill(ctx, "rtfhe_cmux_circuit_create", d_desc, desc, d_tv, lut, d_ok, count * 4)) return rc;
     const int32_t* dd = (const int32_t*)d_desc;
     CmuxNetArgs a{};
     a.tw = ctx->d_tw; a.sel = sel->d_spec; a.sel_idx = (const int32_t*)d_sel_idx; a.row0 = (const int32_t*)d_row0; a.table = (const uint32_t*)d_tv;
@@ -92,42 +83,27 @@ int rtfhe_cmux_circuit_create(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const rtfh
     a.out = extract ? nullptr : (uint32_t*)d_out; a.ext = extract ? cbuf.d[0] : nullptr; a.fault = ctx->d_fault;
     a.count = (int32_t)count; a.n_nodes = n_nodes; a.n_vars = n_vars; a.n_out = n_out; a.n_sel = sel->n_sel; a.n_lut = lut->n_lut;
     a.leaf_min = leaf_span[0]; a.leaf_max = leaf_span[1]; a.enc = lut->encrypted ? 1 : 0;
-    const int64_t before = ctx->launches;
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return bail(fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e)));
-    e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) return bail(fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e)));
-    ctx->tlwe1_capture = &cbuf;      // (the key switch brackets nothing with timer events inside a circuit's capture)
-    // (every failure from here on still reaches hipStreamEndCapture: return codes, no early return)
-    int rc = launch_net_plain(ctx, k_cmux_net_check<LEVELED_WAVES>, count, a, ctx->stream);
-    for (int32_t k = 0; k < n_levels && !rc; k++) {
-        a.level = dd + (size_t)n_nodes * 4 + level_off[(size_t)k];
-        a.n_level = level_off[(size_t)k + 1] - level_off[(size_t)k];
-        rc = launch_leveled(ctx, net, count * (size_t)a.n_level, ctx->stream, a);      // the twin of the leveled mode in force: the graph keeps it
-    }
-    if (!rc) rc = ctx->logn == 11 ? launch_net_plain(ctx, k_cmux_net_out<11, LEVELED_WAVES>, samples, a, ctx->stream)
-                                  : launch_net_plain(ctx, k_cmux_net_out<10, LEVELED_WAVES>, samples, a, ctx->stream);
-    // identity_key_switch of the count * n_out samples, as the tree's extract form does it
-    if (!rc && extract) rc = launch_key_switch_rows(ctx, cbuf.d[0], (uint32_t*)d_out, samples, ctx->stream);
-    ctx->tlwe1_capture = nullptr;
-    e = hipStreamEndCapture(ctx->stream, &c->graph);
-    c->launches = ctx->launches - before;
-    ctx->launches = before;
-    if (rc) return bail(rc);
-    if (e != hipSuccess) return bail(fail(ctx, RTFHE_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e)));
-    e = hipGraphInstantiate(&c->exec, c->graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) return bail(fail(ctx, RTFHE_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)));
-    ctx->circuits.push_back(c);
-    *out = c;
-    return 0;
+    // recorded by circuit_record, under its rule; &cbuf also in the TRLWE form: the key switch brackets nothing with timer events inside a circuit's capture
+    return circuit_record(ctx, std::move(c), &cbuf, out, [&] {
+        int rc = launch_net_plain(ctx, k_cmux_net_check<LEVELED_WAVES>, count, a, ctx->stream);
+        for (int32_t k = 0; k < n_levels && !rc; k++) {
+            a.level = dd + (size_t)n_nodes * 4 + level_off[(size_t)k];
+            a.n_level = level_off[(size_t)k + 1] - level_off[(size_t)k];
+            rc = launch_leveled(ctx, net, count * (size_t)a.n_level, ctx->stream, a);      // the twin of the leveled mode in force: the graph keeps it
+        }
+        if (!rc) rc = ctx->logn == 11 ? launch_net_plain(ctx, k_cmux_net_out<11, LEVELED_WAVES>, samples, a, ctx->stream)
+                                      : launch_net_plain(ctx, k_cmux_net_out<10, LEVELED_WAVES>, samples, a, ctx->stream);
+        // identity_key_switch of the count * n_out samples, as the tree's extract form does it
+        if (!rc && extract) rc = launch_key_switch_rows(ctx, cbuf.d[0], (uint32_t*)d_out, samples, ctx->stream);
+        return rc;
+    });
 }
 
 }  // extern "C"
 
-// rtfhe_trgsw_create's conversion of selectors [first, first + n) of a live set, in place and synchronous
-// (args_ok: the caller's other pointers; stage(words) brings the words of the new samples into ctx->d_a: the caller's copy, or a seeded form's expansion)
-template <typename Stage>
-static int trgsw_update_staged(rtfhe_trgsw* sel, bool args_ok, int32_t first, int32_t n, Stage stage) {
+// rtfhe_trgsw_create's conversion (convert_selectors) of selectors [first, first + n) of a live set, in place and synchronous
+// (args_ok: the caller's other pointers; stage: convert_selectors')
+static int trgsw_update_staged(rtfhe_trgsw* sel, bool args_ok, int32_t first, int32_t n, const std::function<int(size_t)>& stage) {
     rtfhe_ctx* ctx = sel ? sel->ctx : nullptr;
     if (int rc = handles_ready(ctx, {ref(sel)})) return rc;
     if (!args_ok) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
@@ -135,11 +111,9 @@ static int trgsw_update_staged(rtfhe_trgsw* sel, bool args_ok, int32_t first, in
         return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_update: selectors [" + std::to_string(first) + ", " + std::to_string((long long)first + n) +
                                             ") are outside the set's [0, " + std::to_string(sel->n_sel) + ")");
     if (int rc = use(ctx)) return rc;
-    const size_t polys = (size_t)n * 2 * 2 * ctx->p.l, words = polys * ctx->p.N, per_sel = (size_t)2 * 2 * ctx->p.l * (ctx->p.N / 2);
+    const size_t per_sel = (size_t)2 * 2 * ctx->p.l * (ctx->p.N / 2);
     HIPCHECK(ctx, hipDeviceSynchronize());            // replays on any stream may still read the old spectra
-    if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, words * 4)) return rc;
-    if (int rc = stage(ctx, words)) return rc;
-    if (int rc = launch_fft(ctx, true, FftArgs{ctx->d_tw, ctx->d_a, sel->d_spec + (size_t)first * per_sel, (int32_t)polys, 1, 2 * ctx->p.l, 0}, ctx->stream)) return rc;
+    if (int rc = convert_selectors(ctx, sel->d_spec + (size_t)first * per_sel, n, stage)) return rc;
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -147,7 +121,8 @@ static int trgsw_update_staged(rtfhe_trgsw* sel, bool args_ok, int32_t first, in
 extern "C" {
 
 int rtfhe_trgsw_update(rtfhe_trgsw* sel, const uint32_t* trgsw, int32_t first, int32_t n) {
-    return trgsw_update_staged(sel, trgsw != nullptr, first, n, [&](rtfhe_ctx* ctx, size_t words) {
+    rtfhe_ctx* ctx = sel ? sel->ctx : nullptr;      // (staging runs behind the handle check)
+    return trgsw_update_staged(sel, trgsw != nullptr, first, n, [&](size_t words) {
         HIPCHECK(ctx, hipMemcpy(ctx->d_a, trgsw, words * 4, hipMemcpyHostToDevice));
         return 0;
     });
@@ -158,8 +133,8 @@ int rtfhe_trgsw_update_seeded(rtfhe_trgsw* sel, const uint32_t* seed, uint64_t f
     rtfhe_ctx* ctx = sel ? sel->ctx : nullptr;
     if (ctx && seed && b && n >= 1)
         if (int rc = seeded_ready(ctx, "rtfhe_trgsw_update_seeded", RTFHE_SEEDED_UPLOAD, seed, first_row, b, 2 * ctx->p.l, nullptr, (size_t)n * 2 * ctx->p.l)) return rc;
-    return trgsw_update_staged(sel, seed && b, first, n, [&](rtfhe_ctx* c, size_t) {
-        return stage_seeded(c, seed, first_row, b, 2 * c->p.l, (size_t)n * 2 * c->p.l, c->d_a);
+    return trgsw_update_staged(sel, seed && b, first, n, [&](size_t) {
+        return stage_seeded(ctx, seed, first_row, b, 2 * ctx->p.l, (size_t)n * 2 * ctx->p.l, ctx->d_a);
     });
 }
 

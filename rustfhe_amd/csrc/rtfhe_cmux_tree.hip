@@ -258,13 +258,21 @@ void trgsw_release(rtfhe_trgsw* t) {
     t->d_spec = nullptr;
 }
 
+// TRGSWRepF::from (trgsw.rs:68-76) of n samples, as rtfhe_load_bk_torus converts the bootstrapping key: the forward transform of the words
+// viewed as signed i32, written in the canonical device layout [2l][2][R][64] at dst_spec.  Queued on ctx->stream: ctx->d_a grown to the
+// samples' words, stage(words) -- what brings them there: the caller's copy, or a seeded form's expansion --, the transform.  The caller waits
+// for the stream (rtfhe_trgsw_create and rtfhe_trgsw_update word that failure differently).
+int convert_selectors(rtfhe_ctx* ctx, cplx* dst_spec, int32_t n, const std::function<int(size_t)>& stage) {
+    const size_t polys = (size_t)n * 2 * 2 * ctx->p.l, words = polys * ctx->p.N;
+    if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, words * 4)) return rc;
+    if (int rc = stage(words)) return rc;
+    return launch_fft(ctx, true, FftArgs{ctx->d_tw, ctx->d_a, dst_spec, (int32_t)polys, 1, 2 * ctx->p.l, 0}, ctx->stream);
+}
+
 }  // namespace rtfhe_host
 
-// TRGSWRepF::from (trgsw.rs:68-76) of every sample, as rtfhe_load_bk_torus converts the bootstrapping key: the forward transform of the words
-// viewed as signed i32, written in the canonical device layout [2l][2][R][64]
-// (stage(words) queues on ctx->stream what brings the words of the samples into ctx->d_a: the caller's copy, or a seeded set's expansion)
-template <typename Stage>
-static int trgsw_create_staged(rtfhe_ctx* ctx, int32_t n_sel, rtfhe_trgsw** out, Stage stage) {
+// a new selector set: what only creation does around convert_selectors
+static int trgsw_create_staged(rtfhe_ctx* ctx, int32_t n_sel, rtfhe_trgsw** out, const std::function<int(size_t)>& stage) {
     *out = nullptr;
     if (int rc = use(ctx)) return rc;
     // the rotation, the demultiplexer and the TRLWE x TRGSW product are granted their dynamic LDS now, so that the first of a context may already
@@ -277,10 +285,8 @@ static int trgsw_create_staged(rtfhe_ctx* ctx, int32_t n_sel, rtfhe_trgsw** out,
     rtfhe_trgsw* t = new rtfhe_trgsw();
     t->n_sel = n_sel;
     t->ctx = ctx;
-    int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, words * 4);
-    if (!rc && hipMalloc((void**)&t->d_spec, words / 2 * sizeof(cplx)) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_trgsw_create: hipMalloc");
-    if (!rc) rc = stage(words);      // on the stream of the transform below, which is waited for
-    if (!rc) rc = launch_fft(ctx, true, FftArgs{ctx->d_tw, ctx->d_a, t->d_spec, (int32_t)polys, 1, 2 * ctx->p.l, 0}, ctx->stream);
+    int rc = hipMalloc((void**)&t->d_spec, words / 2 * sizeof(cplx)) == hipSuccess ? 0 : fail(ctx, RTFHE_ERR_HIP, "rtfhe_trgsw_create: hipMalloc");
+    if (!rc) rc = convert_selectors(ctx, t->d_spec, n_sel, stage);
     if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_trgsw_create: hipStreamSynchronize");
     if (rc) {
         (void)hipGetLastError();

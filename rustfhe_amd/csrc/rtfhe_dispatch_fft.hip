@@ -237,6 +237,7 @@ static int build_bk_layout(rtfhe_ctx* ctx, int which) {
     bool* valid = which == LAYOUT_EO ? &ctx->ebk_valid : &ctx->p4bk_valid;
     const size_t polys = bk_word_count(ctx->p) / ctx->p.N;
     if (!*dst) HIPCHECK(ctx, hipMalloc((void**)dst, bk_cplx_count(ctx->p) * sizeof(cplx)));
+    // (three scalar arguments, not one struct: launched by hand, not counted)
     if (which == LAYOUT_EO) hipLaunchKernelGGL(k_bk_to_eo, dim3(2048), dim3(256), 0, ctx->stream, (const cplx*)ctx->d_bk, *dst, polys);
     else hipLaunchKernelGGL(k_bk_to_p4, dim3(2048), dim3(256), 0, ctx->stream, (const cplx*)ctx->d_bk, *dst, polys);
     HIPCHECK(ctx, hipGetLastError());

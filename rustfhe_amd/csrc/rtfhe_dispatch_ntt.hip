@@ -130,18 +130,11 @@ int ntt_prepare(rtfhe_ctx* ctx) {
     const int32_t polys = (int32_t)(words / ctx->p.N);
     const double ninv = centred_p(powmod_p((uint64_t)ctx->p.N, ntt::P_U64 - 2));
     int grid = (polys + W - 1) / W; if (grid > 2048) grid = 2048;
-    if (halves) {
-        NttHalvesBkArgs a{ctx->d_ntt_tw, ctx->d_bk_torus, ctx->d_ntt_bk, polys, 2 * ctx->p.l, ninv};
-        const size_t lds = (size_t)(NttHalvesTw::TOTAL + W * ntt::XSLOTS) * sizeof(double);
-        if (int rc = allow_lds(ctx, k_ntt_bk_halves<W>, lds)) return rc;
-        hipLaunchKernelGGL(k_ntt_bk_halves<W>, dim3(grid), dim3(64 * W), lds, ctx->stream, a);
-    } else {
-        NttBkArgs a{ctx->d_ntt_tw, ctx->d_bk_torus, ctx->d_ntt_bk, polys, 2 * ctx->p.l, ninv};
-        const size_t lds = (size_t)(ntt::TW_DIR_PAD + W * ntt::XSLOTS) * sizeof(double);
-        if (int rc = allow_lds(ctx, k_ntt_bk<W>, lds)) return rc;
-        hipLaunchKernelGGL(k_ntt_bk<W>, dim3(grid), dim3(64 * W), lds, ctx->stream, a);
-    }
-    HIPCHECK(ctx, hipGetLastError());
+    if (int rc = halves ? launch_kernel(ctx, k_ntt_bk_halves<W>, dim3(grid), dim3(64 * W), (size_t)(NttHalvesTw::TOTAL + W * ntt::XSLOTS) * sizeof(double), ctx->stream,
+                                        NttHalvesBkArgs{ctx->d_ntt_tw, ctx->d_bk_torus, ctx->d_ntt_bk, polys, 2 * ctx->p.l, ninv}, false)
+                        : launch_kernel(ctx, k_ntt_bk<W>, dim3(grid), dim3(64 * W), (size_t)(ntt::TW_DIR_PAD + W * ntt::XSLOTS) * sizeof(double), ctx->stream,
+                                        NttBkArgs{ctx->d_ntt_tw, ctx->d_bk_torus, ctx->d_ntt_bk, polys, 2 * ctx->p.l, ninv}, false))
+        return rc;
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->ntt_ready = true;
     return 0;

@@ -142,18 +142,12 @@ int xfft_prepare(rtfhe_ctx* ctx) {
     if (!ctx->d_xbk) HIPCHECK(ctx, hipMalloc((void**)&ctx->d_xbk, 2 * bk_cplx_count(ctx->p) * sizeof(cplx)));
     constexpr int W = 4;
     XBkArgs a{ctx->d_xtw, ctx->d_bk_torus, ctx->d_xbk, (int32_t)polys, 2 * ctx->p.l};
-    if (big) {      // a work item = (polynomial, half of its spectrum)
-        int grid = (int)((2 * polys + W - 1) / W); if (grid > 2048) grid = 2048;
-        const size_t lds = (size_t)xfft::XTw2::TOTAL * sizeof(cplx) + (size_t)W * 2 * Geo<10>::XSLOTS * sizeof(double);
-        if (int rc = allow_lds(ctx, k_xbk_build2<W>, lds)) return rc;
-        hipLaunchKernelGGL(k_xbk_build2<W>, dim3(grid), dim3(64 * W), lds, ctx->stream, a);
-    } else {
-        int grid = (int)((polys + W - 1) / W); if (grid > 2048) grid = 2048;
-        const size_t lds = (size_t)XTw::TOTAL * sizeof(cplx) + (size_t)W * 2 * Geo<10>::XSLOTS * sizeof(double);
-        if (int rc = allow_lds(ctx, k_xbk_build<W>, lds)) return rc;
-        hipLaunchKernelGGL(k_xbk_build<W>, dim3(grid), dim3(64 * W), lds, ctx->stream, a);
-    }
-    HIPCHECK(ctx, hipGetLastError());
+    const size_t items = big ? 2 * polys : polys;      // N = 2048: a work item = (polynomial, half of its spectrum)
+    const int grid = (int)std::min((items + W - 1) / W, (size_t)2048);
+    const size_t lds = (size_t)(big ? xfft::XTw2::TOTAL : XTw::TOTAL) * sizeof(cplx) + (size_t)W * 2 * Geo<10>::XSLOTS * sizeof(double);
+    if (int rc = big ? launch_kernel(ctx, k_xbk_build2<W>, dim3(grid), dim3(64 * W), lds, ctx->stream, a, false)
+                     : launch_kernel(ctx, k_xbk_build<W>, dim3(grid), dim3(64 * W), lds, ctx->stream, a, false))
+        return rc;
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->xfft_ready = true;
     return 0;

@@ -33,9 +33,12 @@
 #include <climits>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
+#include <memory>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "rtfhe_kernels.hpp"
@@ -113,7 +116,7 @@ struct rtfhe_ctx {
     size_t ksk_bytes = 0, ksmat_bytes = 0;
     // lvl1 samples between the two launches of the split path (d[0]; cap in samples), plus a circuit's own during its capture
     ScratchMap tlwe1;
-    StreamScratch* tlwe1_capture = nullptr;   // set by rtfhe_circuit_create around its capture: the circuit's buffer
+    StreamScratch* tlwe1_capture = nullptr;   // set by circuit_record around a circuit's capture: the circuit's buffer
     bool foreign_capture = false;     // set by launch_bootstrap for the duration of a call made inside a stream capture that is NOT
                                       // rtfhe_circuit_create's: such a batch stays on the fused kernel (see split_ok)
     int ks_mm_min = 1;                // batches of at least this many gates take the split path (0 = never: fused kernel); RTFHE_KS_MM_MIN
@@ -278,6 +281,20 @@ int device_pointers(rtfhe_ctx* ctx, const char* name, std::initializer_list<cons
 struct StagedIdx { const int32_t* first = nullptr; const int32_t* second = nullptr; };
 int stage_idx(rtfhe_ctx* ctx, void** buf, size_t* cap, size_t words, const int32_t* first, const int32_t* second, StagedIdx& d);
 void circuit_release(rtfhe_circuit* c);                                   // rtfhe_circuit.hip
+// ---- circuits in the making (rtfhe_circuit.hip; the recorder's rule: DESIGN.md 6.1) ----
+// a circuit that no context lists yet: released and deleted when its *_create returns without having handed it to the caller
+struct CircuitDrop { void operator()(rtfhe_circuit* c) const { circuit_release(c); delete c; } };
+typedef std::unique_ptr<rtfhe_circuit, CircuitDrop> NewCircuit;
+// its own device buffers: every (pointer, bytes) allocated and listed in c->d_owned; a failed one is RTFHE_ERR_HIP "`name`: hipMalloc"
+int circuit_own(rtfhe_ctx* ctx, rtfhe_circuit* c, const char* name, std::initializer_list<std::pair<void**, size_t>> bufs);
+// a table's rows in bytes (an encrypted table's rows are TRLWEs: 2N words), and what both circuit kinds over a table put into their buffers before
+// the recording: the description's words, the circuit's own copy of the rows, `zero_bytes` of zeros; a failure is "`name`: hipMemcpy / hipMemset"
+inline size_t lut_bytes(const rtfhe_ctx* ctx, const rtfhe_lut* lut) { return (size_t)lut->n_lut * ctx->p.N * (lut->encrypted ? 2 : 1) * 4; }
+int circuit_fill(rtfhe_ctx* ctx, const char* name, void* d_desc, const std::vector<int32_t>& desc, void* d_tv, const rtfhe_lut* lut, void* d_zero, size_t zero_bytes);
+// THE recorder of every circuit kind: waits for ctx->stream, captures what enqueue() launches on it (ctx->tlwe1_capture = capture_samples
+// meanwhile) into c's graph, moves the launches counted meanwhile from the context's counter to c->launches, instantiates, lists c in
+// ctx->circuits and hands it out.  enqueue() returns the library's int; its error is reported before the capture's.
+int circuit_record(rtfhe_ctx* ctx, NewCircuit c, StreamScratch* capture_samples, rtfhe_circuit** out, const std::function<int()>& enqueue);
 void lut_release(rtfhe_lut* lut);                                         // frees a table's device copies (rtfhe_lut.hip)
 void trgsw_release(rtfhe_trgsw* t);                                       // frees a selector set's spectra (rtfhe_cmux_tree.hip)
 void packing_key_release(rtfhe_packing_key* k);                           // frees a packing key's matrix (rtfhe_pack.hip)
@@ -321,6 +338,9 @@ void orphan_all(std::vector<H*>& live, void (*release)(H*)) {
 // what every entry point over a selector set checks first (rtfhe_cmux_tree.hip): the handles (lut only with_table), the caller's other pointers
 // (args_ok), the mirror backend -- who: "the CMUX tree runs", for the message
 int selector_set_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, bool with_table, const rtfhe_lut* lut, bool args_ok, const char* who);
+// what rtfhe_trgsw_create[_seeded] and rtfhe_trgsw_update[_seeded] share (rtfhe_cmux_tree.hip): n TRGSW samples, brought into ctx->d_a by
+// stage(words), transformed into the spectra at dst_spec; queued on ctx->stream, which the caller then waits for
+int convert_selectors(rtfhe_ctx* ctx, rtfhe::cplx* dst_spec, int32_t n, const std::function<int(size_t)>& stage);
 
 // ---- twiddles (rtfhe_twiddles.hip) ----
 bool unit_twiddles_ok(const HostTw& tw);
@@ -449,11 +469,15 @@ int launch_split(rtfhe_ctx* ctx, BootstrapArgs a, hipStream_t s, F blind_rotate)
 }
 
 // ---- kernel shapes and their launches (the three rtfhe_dispatch_*.hip units) ----
-// One launch: grants the kernel its dynamic LDS (once per device, allow_lds_raw), launches and checks.  counted: a bootstrap launch, which
-// rtfhe_timer_end reports; the stage-level external products are not.
+// One launch, and the only place but two that moves ctx->launches (launch_key_switch_mm: one for a whole batch; rtfhe_circuit_launch: what a
+// recording counted): grants the kernel its dynamic LDS (once per device, allow_lds_raw; at 0 bytes that calls nothing in HIP and notes the
+// kernel in two maps), launches and checks.  counted: a launch that rtfhe_timer_end reports; the stage-level calls and the key builds are not.
+// grant = false: the two per-sample key switches, whose LDS (4N bytes per wave) has never needed a grant and whose first launch of a context may
+// sit in a circuit's capture, where nothing but launches may happen.
 template <typename K, typename A>
-int launch_kernel(rtfhe_ctx* ctx, K k, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A& a, bool counted = true) {
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
+int launch_kernel(rtfhe_ctx* ctx, K k, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A& a, bool counted = true, bool grant = true) {
+    if (grant)
+        if (int rc = allow_lds(ctx, k, lds)) return rc;
     hipLaunchKernelGGL(k, grid, block, lds, s, a);
     HIPCHECK(ctx, hipGetLastError());
     if (counted) ctx->launches++;

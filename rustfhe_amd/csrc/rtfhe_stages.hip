@@ -19,41 +19,19 @@ int launch_fft_t(rtfhe_ctx* ctx, bool forward, FftArgs a, hipStream_t s) {
     const size_t lds = (size_t)G::TW_DIR * sizeof(cplx) + (size_t)W * G::XSLOTS * sizeof(double);
     int grid = (a.count + W - 1) / W;
     if (grid > 2048) grid = 2048;
-    if (forward) {
-        auto k = k_fft_forward<LOGN, W>;
-        if (int rc = allow_lds(ctx, k, lds)) return rc;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(64 * W), lds, s, a);
-    } else {
-        auto k = k_fft_inverse<LOGN, W>;
-        if (int rc = allow_lds(ctx, k, lds)) return rc;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(64 * W), lds, s, a);
-    }
-    HIPCHECK(ctx, hipGetLastError());
-    return 0;
+    return launch_kernel(ctx, forward ? k_fft_forward<LOGN, W> : k_fft_inverse<LOGN, W>, dim3(grid), dim3(64 * W), lds, s, a, false);
 }
 RTFHE_LEVELED_FAMILY(extprod_twins, ExtProdArgs, k_external_product, bootstrap_lds_bytes<LOGN>(LEVELED_WAVES, 0))      // (its own LDS: no accumulator)
 
-template <int LOGN>
-int launch_keyswitch_t(rtfhe_ctx* ctx, KeySwitchArgs a, hipStream_t s) {
-    constexpr int W = 4;
-    auto k = k_key_switch<LOGN, 8, 2, KSQ, W>;
-    const size_t lds = (size_t)W * (1 << LOGN) * 4;
-    hipLaunchKernelGGL(k, dim3((a.count + W - 1) / W), dim3(64 * W), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    return 0;
+// the two per-sample key switches, W samples per workgroup with a lvl1 sample in LDS each; no grant (launch_kernel).  The stage-level one
+// (rtfhe_key_switch_batch) is not counted; _ext, the extract tail without the matrix key, is
+constexpr int KS_W = 4;
+template <int LOGN, typename K, typename A>
+int launch_keyswitch_t(rtfhe_ctx* ctx, K k, const A& a, hipStream_t s, bool counted) {
+    return launch_kernel(ctx, k, dim3((a.count + KS_W - 1) / KS_W), dim3(64 * KS_W), (size_t)KS_W * (1 << LOGN) * 4, s, a, counted, false);
 }
 
-template <int LOGN>
-int launch_keyswitch_ext_t(rtfhe_ctx* ctx, KeySwitchExtArgs a, hipStream_t s) {
-    constexpr int W = 4;
-    auto k = k_key_switch_ext<LOGN, 8, 2, KSQ, W>;
-    const size_t lds = (size_t)W * (1 << LOGN) * 4;
-    hipLaunchKernelGGL(k, dim3((a.count + W - 1) / W), dim3(64 * W), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    ctx->launches++;
-    return 0;
-}
-
+// (five scalar arguments, not one struct: launched by hand, not counted)
 template <int LOGN>
 int launch_permute_t(rtfhe_ctx* ctx, const double* src, double* dst, size_t count, int dir, int rows, hipStream_t s) {
     hipLaunchKernelGGL(k_bk_permute<LOGN>, dim3(2048), dim3(256), 0, s, src, dst, count, dir, rows);
@@ -65,14 +43,10 @@ template <int LOGN>
 int launch_poly_mul_t(rtfhe_ctx* ctx, PolyMulArgs a, hipStream_t s) {
     constexpr int W = 4;
     typedef Geo<LOGN> G;
-    auto k = k_poly_mul<LOGN, W>;
     const size_t lds = (size_t)G::TW_TOTAL * sizeof(cplx) + (size_t)W * G::XSLOTS * sizeof(double);
-    if (int rc = allow_lds(ctx, k, lds)) return rc;
     int grid = (a.count + W - 1) / W;
     if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * W), lds, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    return 0;
+    return launch_kernel(ctx, k_poly_mul<LOGN, W>, dim3(grid), dim3(64 * W), lds, s, a, false);
 }
 
 }  // namespace
@@ -91,18 +65,12 @@ int launch_bk_permute(rtfhe_ctx* ctx, const double* src, double* dst, size_t pol
 
 // device layout of the key-switching key: the rows of two adjacent levels pre-summed (see ks_accumulate) + one all-zero row that "both digits 0" selects
 int launch_ksk_combine(rtfhe_ctx* ctx, const uint32_t* d_raw, hipStream_t s) {
-    KskCombineArgs a{d_raw, ctx->d_ksk, ctx->p.N, ctx->ksw};
-    hipLaunchKernelGGL((k_ksk_combine<8, 2>), dim3(4096), dim3(256), 0, s, a);
-    HIPCHECK(ctx, hipGetLastError());
-    return 0;
+    return launch_kernel(ctx, k_ksk_combine<8, 2>, dim3(4096), dim3(256), 0, s, KskCombineArgs{d_raw, ctx->d_ksk, ctx->p.N, ctx->ksw}, false);
 }
 
 // the same key as signed byte limbs in i8-MFMA operand order, for the batch key switch of the split path
 int launch_ksmat_build(rtfhe_ctx* ctx, const uint32_t* d_raw, int colgroups, hipStream_t s) {
-    KsMatArgs m{d_raw, ctx->d_ksmat, ctx->p.N, ctx->p.n, ctx->ksw, colgroups};
-    hipLaunchKernelGGL((k_ksmat_build<8, 2>), dim3(4096), dim3(256), 0, s, m);
-    HIPCHECK(ctx, hipGetLastError());
-    return 0;
+    return launch_kernel(ctx, k_ksmat_build<8, 2>, dim3(4096), dim3(256), 0, s, KsMatArgs{d_raw, ctx->d_ksmat, ctx->p.N, ctx->p.n, ctx->ksw, colgroups}, false);
 }
 
 int launch_key_switch_mm(rtfhe_ctx* ctx, const BootstrapArgs& a, const uint32_t* samples, hipStream_t s) {
@@ -137,17 +105,17 @@ int launch_key_switch_mm(rtfhe_ctx* ctx, const BootstrapArgs& a, const uint32_t*
         const int mg = (int)((cnt + per_block - 1) / per_block);
         KsMmArgs k{samples + off * w1, ctx->d_ksmat, a.idx_out ? a.out : a.out + off * ((size_t)ctx->p.n + 1), (int32_t)cnt, ctx->p.n, ctx->p.N, colgroups, splitk, mg,
                    a.ops ? a.ops + off : nullptr, a.idx0 ? a.idx0 + off : nullptr, a.idx1 ? a.idx1 + off : nullptr, a.idx_out ? a.idx_out + off : nullptr, a.num_wires};
-        hipLaunchKernelGGL((k_key_switch_mm<8, 2>), dim3(mg * ((colgroups + 7) / 8 * 8) * splitk), dim3(64 * KSMM_WAVES), 0, s, k);
-        HIPCHECK(ctx, hipGetLastError());
+        if (int rc = launch_kernel(ctx, k_key_switch_mm<8, 2>, dim3(mg * ((colgroups + 7) / 8 * 8) * splitk), dim3(64 * KSMM_WAVES), 0, s, k, false)) return rc;
     }
     if (ev_b) HIPCHECK(ctx, hipEventRecord(ev_b, s));
-    ctx->launches++;
+    ctx->launches++;      // ONE for the batch key switch, however many 2 GiB segments it took: the segments above go uncounted
     return 0;
 }
 
 int launch_key_switch_ext(rtfhe_ctx* ctx, uint32_t* samples, uint32_t* d_out, size_t count, hipStream_t s) {
     const KeySwitchExtArgs a{ctx->d_ksk, samples, d_out, (int32_t)count, ctx->p.n, ctx->ksw};
-    return ctx->logn == 10 ? launch_keyswitch_ext_t<10>(ctx, a, s) : launch_keyswitch_ext_t<11>(ctx, a, s);
+    return ctx->logn == 10 ? launch_keyswitch_t<10>(ctx, k_key_switch_ext<10, 8, 2, KSQ, KS_W>, a, s, true)
+                           : launch_keyswitch_t<11>(ctx, k_key_switch_ext<11, 8, 2, KSQ, KS_W>, a, s, true);
 }
 
 int launch_key_switch_rows(rtfhe_ctx* ctx, uint32_t* samples, uint32_t* d_out, size_t rows, hipStream_t s, bool zero_out) {
@@ -207,7 +175,8 @@ int rtfhe_key_switch_batch(rtfhe_ctx* ctx, const uint32_t* tlwe1, uint32_t* out,
     if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
     HIPCHECK(ctx, hipMemcpyAsync(ctx->d_a, tlwe1, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     KeySwitchArgs a{ctx->d_ksk, (const uint32_t*)ctx->d_a, (uint32_t*)ctx->d_c, (int32_t)count, ctx->p.n, ctx->ksw};
-    int rc = ctx->logn == 10 ? launch_keyswitch_t<10>(ctx, a, ctx->stream) : launch_keyswitch_t<11>(ctx, a, ctx->stream);
+    int rc = ctx->logn == 10 ? launch_keyswitch_t<10>(ctx, k_key_switch<10, 8, 2, KSQ, KS_W>, a, ctx->stream, false)
+                             : launch_keyswitch_t<11>(ctx, k_key_switch<11, 8, 2, KSQ, KS_W>, a, ctx->stream, false);
     if (rc) return rc;
     HIPCHECK(ctx, hipMemcpyAsync(out, ctx->d_c, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -321,7 +290,7 @@ int plan_run(rtfhe_fft_plan* pl, int mode, const void* src, const void* src2, vo
     if (mode == ANYN_POLY_MUL) PLANCHECK(hipMemcpyAsync(pl->d_in2, src2, in_bytes, hipMemcpyHostToDevice, pl->stream));
     AnyNArgs a{pl->d_tab, pl->d_in, pl->d_in2, pl->d_out, pl->N, (int32_t)count, mode};
     const unsigned grid = (unsigned)(count < 4096 ? count : 4096);
-    hipLaunchKernelGGL(k_fft_anyn, dim3(grid), dim3(ANYN_THREADS), 0, pl->stream, a);
+    hipLaunchKernelGGL(k_fft_anyn, dim3(grid), dim3(ANYN_THREADS), 0, pl->stream, a);      // (a plan has no rtfhe_ctx: launched by hand)
     PLANCHECK(hipGetLastError());
     PLANCHECK(hipMemcpyAsync(res, pl->d_out, out_bytes, hipMemcpyDeviceToHost, pl->stream));
     PLANCHECK(hipStreamSynchronize(pl->stream));

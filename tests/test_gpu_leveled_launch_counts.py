@@ -1,6 +1,7 @@
-"""GPU: how many kernels the leveled and the pack entry points enqueue, counted with the counter rtfhe_timer_end returns (a netlist: the launches
-its circuit recorded, which a replay adds to that counter).  The expected counts restate the host code of rtfhe_cmux_tree.hip, rtfhe_cmux_net.hip,
-rtfhe_pack.hip and rtfhe_stages.hip:
+"""GPU: how many kernels the leveled and the pack entry points and the replay of a recorded circuit enqueue, counted with the counter
+rtfhe_timer_end returns (a circuit of any kind: the launches its recording counted, which every replay adds to that counter; the recording itself
+and a refused one add nothing).  The expected counts restate the host code of rtfhe_cmux_tree.hip, rtfhe_cmux_net.hip, rtfhe_pack.hip,
+rtfhe_circuit.hip, rtfhe_batch.hip and rtfhe_stages.hip:
 
   tree, depth d                  d           one k_cmux_tree per level
   tree with extraction           d + 1       ... and the batch key switch: 1 with the matrix key (k_key_switch_mm) and without (RTFHE_KS_MM_MIN=0,
@@ -12,10 +13,15 @@ rtfhe_pack.hip and rtfhe_stages.hip:
   netlist of L levels            L + 2       k_cmux_net_check, one k_cmux_net per level, k_cmux_net_out; + 1 key switch in the extract form
   pack of P positions            1 + ceil(P / 512)      k_pack_ks_mm, then k_pack_combine per PACK_POS_MAX = 512 positions
   external_product_batch         0           a stage-level call: launched, not counted
+  gate circuit of W waves        2 W         per wave (at most one gate per CU: one rung of the ladder) the bootstrap launch and the batch key
+                                             switch of the split path (k_key_switch_mm); W without the matrix key: one fused launch per wave
+  LUT circuit of W waves         4 W         per wave k_lut_gather, the many-LUT launch, the key switch of its count * n_out rows (k_key_switch_mm,
+                                             or k_key_switch_ext without the matrix key) and k_lut_scatter
 
 Both rings at the small mask lengths of the other leveled tests (n = 40 at N = 1024, n = 24 at N = 2048); 5 and 9 lookups, so that the last
 workgroup of four waves holds one wave; depths 1, 2, 3; the tree and the rotation in both leveled modes.  The extract forms' words are compared
-between the two key-switch routes on the way: both are exact."""
+between the two key-switch routes on the way: both are exact.  The two circuits have three waves of 1, 2 and 5 nodes, one replica, the LUT circuit's
+second wave with two outputs per node."""
 import types
 
 import numpy as np
@@ -164,3 +170,90 @@ def test_external_product_is_not_counted(world, count, rounded):
         e.set_leveled_decomposition(_mode(w, False))
     print("N = %d %s count %d: external product %d launches" % (w.N, "rounded" if rounded else "reference", count, k))
     assert k == 0 and out.any()
+
+
+# ---- recorded circuits: what a replay adds, twice over, and that neither a recording nor a refused one adds anything ----
+WAVES = (1, 2, 5)        # nodes per wave
+INPUTS = 8               # wires 0 .. 7 are inputs, every node writes the next free wire(s)
+
+
+def _refused(R, create, msg):
+    with pytest.raises(R.RtfheError) as ei:
+        create()
+    assert ei.value.code == R._ffi.ERR_INVALID and msg in str(ei.value), str(ei.value)
+
+
+def _replays(e, handle, st):
+    """what one replay adds to the counter, and what two add"""
+    one, _ = _counted(e, lambda: e.circuit_launch(handle, st), st)
+    two, _ = _counted(e, lambda: (e.circuit_launch(handle, st), e.circuit_launch(handle, st)), st)
+    e.sync(st)
+    return one, two
+
+
+def _sources(rng, written):
+    """for every node, wave by wave, a wire it may read: an input or one of the wires the earlier waves wrote (written: wires per wave)"""
+    before = np.concatenate([[0], np.cumsum(written)])
+    return np.concatenate([rng.integers(0, INPUTS + before[v], k) for v, k in enumerate(WAVES)])
+
+
+def test_gate_circuit(world):
+    import torch
+    w = world
+    rng = np.random.default_rng(w.N + 23)
+    nodes, offs = sum(WAVES), np.concatenate([[0], np.cumsum(WAVES)]).astype(np.int32)
+    ops = rng.choice([w.R.NAND, w.R.AND, w.R.OR, w.R.XOR], nodes)
+    idx0, idx1 = _sources(rng, WAVES), rng.integers(0, INPUTS, nodes)
+    idx_out = INPUTS + np.arange(nodes)
+    wires0 = random_words(rng, (INPUTS + nodes, w.rp.n + 1))
+    st = torch.cuda.current_stream().cuda_stream
+    words = {}
+    for name, e, per_wave in (("mm", w.mm, 2), ("ext", w.ext, 1)):
+        d = [gk.to_device(a) for a in (ops, idx0, idx1, idx_out)]
+        d_wires = gk.to_device(wires0, np.uint32)
+        k_refused, _ = _counted(e, lambda: (_refused(w.R, lambda: e.circuit_create(*d, np.array([0, 1, 1, 8], np.int32), d_wires, INPUTS + nodes), "wave_offsets"),
+                                            _refused(w.R, lambda: e.circuit_create(*d, offs, d_wires, 0), "num_wires")), st)
+        k_create, c = _counted(e, lambda: e.circuit_create(*d, offs, d_wires, INPUTS + nodes), st)
+        try:
+            one, two = _replays(e, c, st)
+        finally:
+            e.circuit_destroy(c)
+        print("N = %d, key switch %s: gate circuit of %d waves: refused %d, recording %d, one replay %d, two replays %d launches" %
+              (w.N, name, len(WAVES), k_refused, k_create, one, two))
+        assert (k_refused, k_create) == (0, 0), "recording counts nothing: a replay does"
+        assert (one, two) == (per_wave * len(WAVES), 2 * per_wave * len(WAVES)), (w.N, name)
+        words[name] = gk.words_of(d_wires)
+    assert np.array_equal(words["mm"], words["ext"]) and not np.array_equal(words["mm"], wires0)
+
+
+def test_lut_circuit(world):
+    import torch
+    from lut_circuit_kit import create
+    w = world
+    rng = np.random.default_rng(w.N + 29)
+    n_out = np.array([1, 2, 1], np.int32)
+    nodes, rows = sum(WAVES), int(np.dot(WAVES, n_out))
+    in_idx = np.stack([_sources(rng, WAVES * n_out), rng.integers(-1, INPUTS, nodes)], axis=1)      # (-1: an unused slot)
+    d = {"fan_in": 2, "in_idx": in_idx.astype(np.int32), "weights": rng.integers(-(1 << 31), 1 << 31, (nodes, 2)).astype(np.int32),
+         "cst": random_words(rng, (nodes,)), "lut_idx": rng.integers(0, 2, nodes).astype(np.int32),
+         "wave_offsets": np.concatenate([[0], np.cumsum(WAVES)]).astype(np.int32), "wave_n_out": n_out,
+         "out_idx": (INPUTS + np.arange(rows)).astype(np.int32), "num_wires": INPUTS + rows}
+    wires0 = random_words(rng, (INPUTS + rows, w.rp.n + 1))
+    tv = random_words(rng, (2, w.N))
+    st = torch.cuda.current_stream().cuda_stream
+    words = {}
+    for name, e in (("mm", w.mm), ("ext", w.ext)):
+        d_wires = gk.to_device(wires0, np.uint32)
+        with e.lut(tv) as lut:
+            k_refused, _ = _counted(e, lambda: _refused(w.R, lambda: create(e, lut, dict(d, wave_n_out=np.array([1, 3, 1], np.int32)), d_wires), "n_out = 3"), st)
+            k_create, c = _counted(e, lambda: create(e, lut, d, d_wires), st)
+        try:
+            one, two = _replays(e, c, st)
+        finally:
+            e.circuit_destroy(c)
+        print("N = %d, key switch %s: LUT circuit of %d waves: refused %d, recording %d, one replay %d, two replays %d launches" %
+              (w.N, name, len(WAVES), k_refused, k_create, one, two))
+        assert (k_refused, k_create) == (0, 0), "recording counts nothing: a replay does"
+        assert (one, two) == (4 * len(WAVES), 8 * len(WAVES)), (w.N, name)
+        words[name] = gk.words_of(d_wires)
+    assert np.array_equal(words["mm"], words["ext"]) and not np.array_equal(words["mm"], wires0)
