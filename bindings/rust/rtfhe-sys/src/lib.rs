@@ -35,6 +35,7 @@ pub enum rtfhe_lut {}
 pub enum rtfhe_trgsw {}
 pub enum rtfhe_packing_key {}
 pub enum rtfhe_plain {}
+pub enum rtfhe_dense {}
 pub enum rtfhe_fft_plan {}
 
 pub const RTFHE_NAND: c_int = 0;
@@ -195,6 +196,14 @@ extern "C" {
                                        accumulate: c_int, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_trlwe_mul_trgsw_batch_dev(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, d_s_idx: *const c_void, d_x: *const c_void, n_x: i32,
                                            d_x_idx: *const c_void, K: i32, accumulate: c_int, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
+    // lvl0 dense layers: out[g][o][c] = (accumulate ? out[g][o][c] : 0) + [c == n] bias[o] + sum_i W[o][i] x[g][i][c] mod 2^32, exact on every
+    // backend; W [O][I] with every entry in -128 ..= 127; x [count][I][n+1], out [count][O][n+1]; bias a HOST array [O] or null in both forms
+    pub fn rtfhe_dense_create(ctx: *mut rtfhe_ctx, W: *const i32, O: i32, I: i32, out: *mut *mut rtfhe_dense) -> c_int;
+    pub fn rtfhe_dense_destroy(w: *mut rtfhe_dense);
+    pub fn rtfhe_tlwe_dense_batch(ctx: *mut rtfhe_ctx, w: *const rtfhe_dense, x: *const u32, bias: *const u32, accumulate: i32, out: *mut u32,
+                                  count: usize) -> c_int;
+    pub fn rtfhe_tlwe_dense_batch_dev(ctx: *mut rtfhe_ctx, w: *const rtfhe_dense, d_x: *const c_void, bias: *const u32, accumulate: i32,
+                                      d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
     pub fn rtfhe_sync(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_begin(ctx: *mut rtfhe_ctx, stream: *mut c_void) -> c_int;
     pub fn rtfhe_timer_end(ctx: *mut rtfhe_ctx, stream: *mut c_void, ms: *mut f64, launches: *mut i64) -> c_int;

@@ -57,6 +57,9 @@
  *                                    <- TRGSWRepF::cross (hom_nand/src/trgsw.rs:264-306) on caller-supplied TRGSW samples of small-integer polynomials
  *                                       (Crypto<i32> for TRGSW, trgsw.rs:118-138, with a polynomial in the bit's place), its fold-add carried over
  *                                       up to eight products per sample (the reference has the product, not the sum)
+ *   rtfhe_dense_create / rtfhe_tlwe_dense_batch[_dev]
+ *                                    <- the Add / scalar multiples of TLWERep (hom_nand/src/tlwe.rs) carried over a whole integer matrix: the weighted sums of
+ *                                       lvl0 ciphertexts in front of a bootstrap (the reference has the row operations, not the layer)
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch          <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -798,6 +801,42 @@ int rtfhe_trlwe_mul_trgsw_batch(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const in
 int rtfhe_trlwe_mul_trgsw_batch_dev(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const void *d_s_idx /* [count][K] or NULL */, const void *d_x /* [n_x][2][N] */,
                                     int32_t n_x, const void *d_x_idx /* [count][K] or NULL */, int32_t K, int accumulate,
                                     void *d_out /* [count][2][N] */, size_t count, void *stream);
+/* ---- lvl0 dense layers: integer matrix x TLWE batch, the linear layer of the bootstrapped mode ----
+ * A dense layer holds an integer matrix W, int32[O][I] with every entry in [-128, 127], as signed bytes in the matrix pipe's operand order,
+ * built once at creation together with one correction word per output.  A call computes, for g in [0, count), o in [0, O), c = 0 .. n:
+ *
+ *   out[g][o][c] = (accumulate ? out[g][o][c] : 0) + [c == n] * bias[o] + sum_{i < I} W[o][i] * x[g][i][c]        mod 2^32
+ *
+ * on all n + 1 words of the lvl0 rows (mask words 0 .. n-1, then b): sample g's I input ciphertexts in, its O weighted sums out.  The result is
+ * EXACT word for word: the ciphertext words are split into signed byte limbs, the products are summed in i32 on the i8 matrix pipe
+ * (|sum| <= I * 2^14 <= 2^30) and recombined mod 2^32, so it equals the row-by-row wrapping sum, does not depend on the backend and adds no noise
+ * of its own.  The output noise is the inputs' scaled by the weights: variance sum_i W[o][i]^2 sigma_i^2.  A bias is a torus word added to b
+ * (word n) of every sample's output o.
+ *
+ * Parameters.
+ *   - Limits: 1 <= O <= 65,536, 1 <= I <= 65,536, count * max(I, O) * (n + 1) < 2^31 words.  Rows are n + 1 words at 4-byte alignment; any n the
+ *     context accepts works.  accumulate = 1 adds into out (residual sums, more than one matrix into one output), accumulate = 0 overwrites it.
+ *   - Checked on the host before anything is allocated or launched, RTFHE_ERR_INVALID: at creation W and out non-null, O, I, every entry's range
+ *     (the first offender is named); per call handle and buffers non-null, the limits above, out overlaps no part of x.  count == 0 returns 0.
+ *   - bias is a HOST array in both forms and is read before the call returns (it rides in the launch's arguments).
+ *
+ * Keys, backends and devices.  It needs no key at all and runs on every rtfhe_backend; on an rtfhe_ctx_create_multi context on the primary
+ * device.  Lifetime is rtfhe_trgsw's: the matrix (O x I bytes, padded to 16 x 64) lives on the primary device and goes with the context if
+ * it is destroyed first; a call then returns RTFHE_ERR_STATE and rtfhe_dense_destroy only frees the handle.
+ *
+ * Scratch and captures.  The _dev form allocates nothing: it may sit in a caller's stream capture first thing on a fresh stream
+ * (rtfhe_dense_create is synchronous and builds what the kernel needs).  Without a bias it is ONE kernel launch, counted by rtfhe_timer_end;
+ * with a bias ceil(O / 512) launches (one for O <= 512; up to 128 at O = 65,536, each reading x again), back to back on the stream.  A
+ * small launch (fewer than two workgroups per CU) shares I among workgroups whose parts meet as wrapping atomic adds; if any launch of a
+ * call that does not accumulate does so, the whole output is cleared once, before the call's first launch, by a memset on the same stream
+ * (no kernel). */
+typedef struct rtfhe_dense rtfhe_dense;
+int rtfhe_dense_create(rtfhe_ctx *ctx, const int32_t *W /* [O][I], every entry in [-128, 127] */, int32_t O, int32_t I, rtfhe_dense **out);
+void rtfhe_dense_destroy(rtfhe_dense *w);
+int rtfhe_tlwe_dense_batch(rtfhe_ctx *ctx, const rtfhe_dense *w, const uint32_t *x /* [count][I][n+1] */, const uint32_t *bias /* [O] or NULL */,
+                           int32_t accumulate, uint32_t *out /* [count][O][n+1] */, size_t count);
+int rtfhe_tlwe_dense_batch_dev(rtfhe_ctx *ctx, const rtfhe_dense *w, const void *d_x /* [count][I][n+1] */, const uint32_t *bias /* HOST [O] or NULL */,
+                               int32_t accumulate, void *d_out /* [count][O][n+1] */, size_t count, void *stream);
 /* waits for `stream`; also reports (once) a netlist gate skipped since the previous call */
 int rtfhe_sync(rtfhe_ctx *ctx, void *stream);
 /* device-side timing of the launches enqueued by the *_dev calls between begin and end (HIP events on

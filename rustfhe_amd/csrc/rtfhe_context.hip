@@ -356,6 +356,7 @@ void rtfhe_ctx_destroy(rtfhe_ctx* ctx) {
     orphan_all(ctx->trgsws, trgsw_release);
     orphan_all(ctx->pack_keys, packing_key_release);
     orphan_all(ctx->plains, plain_release);
+    orphan_all(ctx->denses, dense_release);
     for (rtfhe_ctx* peer : ctx->peers) rtfhe_ctx_destroy(peer);
     ctx->peers.clear();
     (void)hipSetDevice(ctx->device);

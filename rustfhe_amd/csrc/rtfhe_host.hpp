@@ -19,6 +19,8 @@
 //                            (its argument checks: rtfhe_extract_plan.cpp, host only)
 //   rtfhe_plain.hip          exact TRLWE x plain-polynomial products: plain sets (integer polynomials as spectra), sums of up to eight products per sample
 //                            on the split-FFT exact backend's arithmetic, on every backend (its argument checks: rtfhe_plain_plan.cpp, host only)
+//   rtfhe_dense.hip          lvl0 dense layers: an integer matrix (signed bytes in i8-MFMA operand order) times a batch of TLWE rows, exact, on every
+//                            backend (its argument checks, correction words and launch rule: rtfhe_dense_plan.cpp, host only)
 //   rtfhe_seeded.hip         seeded ciphertexts: masks expanded on the device from a public seed (k_seeded_expand for TRLWE rows, k_tlwe_seeded_expand
 //                            for lvl0 rows), the staging step of the *_seeded upload calls, which live beside their unseeded twins (its argument
 //                            checks and the CPU forms: rtfhe_seeded.cpp, host only; the encryptor core it shares with rtfhe_keygen.cpp:
@@ -80,6 +82,7 @@ struct rtfhe_lut;
 struct rtfhe_trgsw;
 struct rtfhe_packing_key;
 struct rtfhe_plain;
+struct rtfhe_dense;
 struct rtfhe_ctx {
     rtfhe_params p{};
     int device = 0;
@@ -159,13 +162,14 @@ struct rtfhe_ctx {
     ScratchMap pack;
     std::vector<rtfhe_packing_key*> pack_keys;      // live packing keys of this context: their matrices go with it, the handles stay
     std::vector<rtfhe_plain*> plains;      // live plain sets of this context: their spectra go with it, the handles stay
+    std::vector<rtfhe_dense*> denses;      // live dense layers of this context: their matrices go with it, the handles stay
     int num_cus = 256;
     int force_waves = 0;   // RTFHE_FORCE_WAVES=1|2|4|8: one kernel shape for every batch (the parity tests' second opinions)
     int wg_max = 512;      // RTFHE_WG_MAX_GATES: largest batch routed to the workgroup-per-gate kernel
     std::string err;
 };
 
-// The five handle types below hang on their context by one rule.  `ctx` points back at it and the context lists the live handles of each type.
+// The six handle types below hang on their context by one rule.  `ctx` points back at it and the context lists the live handles of each type.
 // A handle destroyed first detaches itself from that list (rtfhe_host::detach) and releases its device memory; a context destroyed first releases
 // the device memory of every listed handle and clears their `ctx` (rtfhe_host::orphan_all): the handle then only remains to be freed, and every
 // call made with it is refused by rtfhe_host::handles_ready.
@@ -215,6 +219,16 @@ struct rtfhe_plain {
     rtfhe::cplx* d_spec = nullptr;      // N = 1024: [n_w][512]; N = 2048: [n_w][2 halves][512] (rtfhe_kernels_plain.hpp)
     int32_t n_w = 0;
     int64_t wmax = 0;                   // max over the set of a polynomial's l1 norm: a call is accepted iff K * wmax <= 192 N
+};
+
+// a dense layer (rtfhe_dense_create): the matrix as signed bytes in i8-MFMA operand order on the primary device, the small operand of
+// rtfhe_tlwe_dense_batch
+struct rtfhe_dense {
+    rtfhe_ctx* ctx = nullptr;
+    uint4* d_wmat = nullptr;            // [planes][otiles][ksteps][64 lanes] x 16 B (rtfhe_kernels_dense.hpp)
+    uint32_t* d_corr = nullptr;         // [O]: 128 * 0x01010101 * sum_i W[o][i], what the signed byte limbs of the ciphertext drop
+    int32_t O = 0, I = 0, ksteps = 0, otiles = 0;
+    int32_t planes = 1;                 // byte planes of the weights (W = sum_p 256^p W_p): one today
 };
 
 namespace rtfhe_host {
@@ -299,6 +313,7 @@ void lut_release(rtfhe_lut* lut);                                         // fre
 void trgsw_release(rtfhe_trgsw* t);                                       // frees a selector set's spectra (rtfhe_cmux_tree.hip)
 void packing_key_release(rtfhe_packing_key* k);                           // frees a packing key's matrix (rtfhe_pack.hip)
 void plain_release(rtfhe_plain* w);                                       // frees a plain set's spectra (rtfhe_plain.hip)
+void dense_release(rtfhe_dense* w);                                       // frees a dense layer's matrix and correction words (rtfhe_dense.hip)
 int prime_trgsw_mac(rtfhe_ctx* ctx);                                      // grants the TRLWE x TRGSW product's twins their LDS (rtfhe_trgsw_mac.hip)
 // ---- seeded ciphertexts (rtfhe_seeded.hip; the checks themselves: rtfhe_seeded.cpp, host only) ----
 // rtfhe_seeded_plan at the context's N with its refusal as the context's error (what: RTFHE_SEEDED_DEVICE / _UPLOAD of rtfhe_seeded_plan.h)
@@ -320,6 +335,7 @@ inline HandleRef ref(const rtfhe_lut* h) { return {"table", "rtfhe_lut", h != nu
 inline HandleRef ref(const rtfhe_trgsw* h) { return {"selector set", "rtfhe_trgsw", h != nullptr, h ? h->ctx : nullptr}; }
 inline HandleRef ref(const rtfhe_packing_key* h) { return {"packing key", "rtfhe_packing_key", h != nullptr, h ? h->ctx : nullptr}; }
 inline HandleRef ref(const rtfhe_plain* h) { return {"plain set", "rtfhe_plain", h != nullptr, h ? h->ctx : nullptr}; }
+inline HandleRef ref(const rtfhe_dense* h) { return {"dense layer", "rtfhe_dense", h != nullptr, h ? h->ctx : nullptr}; }
 // The ownership check of the one or two handles of a call made on ctx (a call made through a handle alone passes that handle's own context,
 // null for a null handle): first every null one (RTFHE_ERR_INVALID "null NOUN (TYPE)"), then every one whose context is gone (RTFHE_ERR_STATE),
 // then every one of another context (RTFHE_ERR_INVALID).

@@ -628,6 +628,32 @@ class Engine(_Handle):
         self._ck(self.L.rtfhe_trlwe_mul_trgsw_batch_dev(self.h, sel.h, self._dev(d_s_idx), self._dev(d_x), int(n_x), self._dev(d_x_idx), int(K),
                                                         1 if accumulate else 0, self._dev(d_out), count, _stream(stream)))
 
+    # ---- lvl0 dense layers (include/rtfhe.h: rtfhe_dense_create, rtfhe_tlwe_dense_batch[_dev]) -------------------------------------------------------
+    def dense(self, W):
+        """Keeps an integer matrix int[O][I], every entry in [-128, 127], on the primary device in the matrix pipe's operand order; a Dense
+        handle (.O, .I), closed by close() or a with block.  Needs no key."""
+        return Dense(self, W)
+
+    def tlwe_dense_batch(self, dense, x, bias=None, acc=None):
+        """out[g][o] = (acc[g][o] if acc is given else 0) + bias[o] on word n + sum_i W[o][i] x[g][i] on all n + 1 words of the lvl0 rows,
+        wrapping: u32[count][O][n+1], exact word for word.  x: u32[count][I][n+1]; bias: u32[O] torus words (linear.dense_bias) or None.
+        Arguments are checked here: a bad one raises RtfheError before anything runs."""
+        w = self.p.n + 1
+        x = _np(x, np.uint32).reshape(-1, dense.I, w)
+        count = x.shape[0]
+        bias = None if bias is None else _np(bias, np.uint32).reshape(dense.O)
+        out = np.array(_np(acc, np.uint32).reshape(count, dense.O, w)) if acc is not None else np.empty((count, dense.O, w), np.uint32)
+        self._ck(self.L.rtfhe_tlwe_dense_batch(self.h, dense.h, _ptr(x), _ptr(bias), 1 if acc is not None else 0, _ptr(out), count))
+        return out
+
+    def tlwe_dense_batch_dev(self, dense, d_x, d_out, count, bias=None, accumulate=False, stream=None):
+        """... on device buffers (d_x: [count][I][n+1] words, d_out: [count][O][n+1] words, not overlapping), asynchronous on `stream`; bias stays
+        a HOST array u32[O] and is read before the call returns; accumulate adds into d_out.  Nothing allocated, one launch (with a bias: one per
+        512 outputs): it may be captured first thing on a fresh stream."""
+        bias = None if bias is None else _np(bias, np.uint32).reshape(dense.O)
+        self._ck(self.L.rtfhe_tlwe_dense_batch_dev(self.h, dense.h, self._dev(d_x), _ptr(bias), 1 if accumulate else 0, self._dev(d_out), count,
+                                                   _stream(stream)))
+
     # ---- stage level ------------------------------------------------------------------------
     def blind_rotate_batch(self, tlwe, steps=None):
         tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)
@@ -787,6 +813,23 @@ class PlainPolys(_Handle):
         self.wmax = int(np.abs(w.astype(np.int64)).sum(axis=1).max()) if self.n else 0
         h = C.c_void_p()
         engine._ck(engine.L.rtfhe_plain_create(engine.h, _ptr(w), self.n, C.byref(h)))
+        self.h = h
+
+
+class Dense(_Handle):
+    """An integer matrix on an Engine's primary device (rtfhe_dense), kept as signed bytes in the matrix pipe's operand order with one correction
+    word per output: the small operand of Engine.tlwe_dense_batch[_dev].  Closing it frees the device copy; one whose Engine was closed first
+    only frees its handle."""
+
+    def __init__(self, engine, W):
+        W = np.asarray(W)
+        assert W.ndim == 2 and (W.size == 0 or np.issubdtype(W.dtype, np.integer)), "W must be an integer matrix [O][I]"
+        assert W.size == 0 or np.abs(W.astype(np.int64)).max() < 1 << 31, "weights must fit int32 (the library then checks [-128, 127])"
+        self.engine, self._destroy = engine, engine.L.rtfhe_dense_destroy
+        self.O, self.I = int(W.shape[0]), int(W.shape[1])
+        W = _np(W, np.int32)
+        h = C.c_void_p()
+        engine._ck(engine.L.rtfhe_dense_create(engine.h, _ptr(W), self.O, self.I, C.byref(h)))
         self.h = h
 
 

@@ -56,3 +56,11 @@ def dense_layer_bias(bias, d, N=1024, unit=1):
         q, r = divmod(j, per)
         rows[q, 0, r * d + d - 1] = int(b) * int(unit)
     return (rows & 0xFFFFFFFF).astype(np.uint32)
+
+
+def dense_bias(b, unit):
+    """The torus words of integer biases at a message unit, for Engine.tlwe_dense_batch[_dev] (include/rtfhe.h: rtfhe_tlwe_dense_batch; DESIGN.md
+    5.20): b[o] * unit mod 2^32, u32[O].  `unit` is the torus word of message 1 (e.g. 1 << 27 for 1/32)."""
+    b = np.asarray(b)
+    assert b.size == 0 or np.issubdtype(b.dtype, np.integer), "integer biases"
+    return np.array([(int(v) * int(unit)) & 0xFFFFFFFF for v in b.reshape(-1)], np.uint32)
