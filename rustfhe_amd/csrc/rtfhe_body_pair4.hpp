@@ -42,22 +42,11 @@
 #define P4_HANDOFF() pair_sync(my_hflag, other_hflag, ++hand_k)
 
     const int n = a.n;
-    {   // pre-step + mod switch (tfhe.rs:41-71, 97, 107-108) to [0, 2N)
-        constexpr int SH = 32 - LOGN - 1;
-        for (int i = lane0 + 64 * q; i <= n; i += 256) {
-            const uint32_t t = gate_linear(io.op, io.p0[i], io.p1[i], i == n);
-            if constexpr (decltype(tvs)::MANY) abar[i] = (uint16_t)mod_switch<SH>(t, i == n, tv_shift(tvs));   // many-LUT: at SH + t, scaled back
-            else abar[i] = (uint16_t)((i == n) ? (t >> SH) : ((t + (1u << (SH - 1))) >> SH));
-        }
-    }
+    gate_mask<LOGN>(io, tvs, n, abar, lane0 + 64 * q, 256);
     __syncthreads();
-    {   // acc = X^{-bbar} * testvec (tfhe.rs:85, 98-106); each wave initialises a quarter of the words
+    {   // each wave initialises a quarter of the words
         const int bbar = (int)abar[n];
-        for (int c = lane0 + 64 * q; c < 2 * N; c += 256) {
-            const int e = (c + bbar) & (2 * N - 1);
-            if constexpr (decltype(tvs)::ENC) accbuf[c] = c < N ? tv_word<LOGN>(tv, e) : tv_word_a<LOGN>(tv, e ^ N);   // encrypted table: a coefficient c - N, (c - N + bbar) mod 2N = e ^ N
-            else accbuf[c] = c < N ? tv_word<LOGN>(tv, e) : 0u;
-        }
+        for (int c = lane0 + 64 * q; c < 2 * N; c += 256) accbuf[c] = acc_start<LOGN>(tvs, tv, bbar, c);
     }
     __syncthreads();
 
@@ -257,27 +246,8 @@
         }
         return;
     }
-    // sample extract index 0 (trlwe.rs:110-121): a'_0 = a_0, a'_k = -a_{N-k}; b' = b_0
-    {
-        uint32_t av[R];
-#pragma unroll
-        for (int mm = 0; mm < R; mm++) av[mm] = accbuf[N + lane0 + 64 * mm + 256 * q];
-        __syncthreads();
-#pragma unroll
-        for (int mm = 0; mm < R; mm++) {
-            const int c = lane0 + 64 * mm + 256 * q;
-            accbuf[N + ((N - c) & (N - 1))] = (c == 0) ? av[mm] : (0u - av[mm]);
-        }
-    }
+    // sample extract index 0: each of the gate's four waves moves a quarter of the a-poly
+    extract_flip<N, R>(accbuf + N, lane0 + 256 * q, 64, [] { __syncthreads(); });
     __syncthreads();
-    // MODE_EXTRACT: the key switch of the whole batch follows as its own launch (k_key_switch_mm)
-    if constexpr (decltype(tvs)::MANY) {      // many-LUT PBS: every output (the batch key switch writes the output rows)
-        if (live) many_extract<N>(a.ext, a.ext_first + g, tv_shift(tvs), accbuf, q * (N / 4) + lane0, (q + 1) * (N / 4), 64, q ? -1 : lane0);
-        return;
-    }
-    if (live) {
-        const int ge = a.ext_first + g;      // batch-wide gate number: the sample buffer is laid out for the key switch (ext_slot)
-        for (int c = q * (N / 4) + lane0; c < (q + 1) * (N / 4); c += 64) *ext_slot(a.ext, ge, c, N) = accbuf[N + c];
-        if (q == 0 && lane0 == 0) *ext_slot(a.ext, ge, N, N) = accbuf[0];
-        for (int c = q * 64 + lane0; c <= n; c += 256) io.out[c] = 0u;
-    }
+    // MODE_EXTRACT (the only mode besides MODE_BLIND_ROTATE this kernel is launched in): the key switch of the whole batch follows as its own launch (k_key_switch_mm)
+    if (live) gate_extract_store<N>(a.ext, io.out, tvs, n, a.ext_first + g, accbuf, accbuf + N, q * (N / 4) + lane0, (q + 1) * (N / 4), 64, q ? -1 : lane0, q * 64 + lane0, 256);

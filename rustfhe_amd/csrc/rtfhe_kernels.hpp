@@ -95,10 +95,11 @@ __device__ __forceinline__ GateIo gate_io(const BootstrapArgs& a, int g) {
     return io;
 }
 
-// Where the accumulator of gate g starts: acc = X^{-bbar} * (tv, 0), coefficient c = tv_word<LOGN>(row, (c + bbar) mod 2N).  Every bootstrap
-// kernel family has one body (rtfhe_body_*.hpp) included into two __global__ entries that differ only in this source: k_bootstrap_* with
-// TvGate, the gates' test vector (1/8, ..., 1/8) -- its row is always valid and its words are constants, so those kernels compile to what
-// they were before the twins existed -- and k_pbs_* with TvLut, the programmable bootstrap's caller-supplied tables (include/rtfhe.h).
+// Where the accumulator of gate g starts: acc = X^{-bbar} * (tv, 0), coefficient c = tv_word<LOGN>(row, (c + bbar) mod 2N) (acc_start,
+// rtfhe_gate_frame.hpp, states it once; the bodies that do not call the frame yet restate it).  Every mirror kernel family has one body
+// (rtfhe_body_*.hpp) included into six __global__ entries that differ only in this source: k_bootstrap_* with TvGate, the gates' test vector
+// (1/8, ..., 1/8) -- its row is always valid and its words are constants, so those kernels compile to what they were before the twins existed
+// -- k_pbs_* with TvLut, the programmable bootstrap's caller-supplied tables (include/rtfhe.h), and the four further sources below.
 struct TvGate {
     static constexpr bool MANY = false;      // one output per gate (k_pbs_many_*: several, see TvMany)
     static constexpr bool ENC = false;       // the a half starts at zero (k_pbs_enc_*: from an encrypted table, see TvEnc)
@@ -200,9 +201,9 @@ __device__ __forceinline__ auto tv_round(const ManyArgs<A>& p, int32_t* fault) {
 }
 
 // The mod switch (tfhe.rs:97, 107-108) of one pre-stepped word at SH + k, scaled back by 2^k: b floor, a_i rounded, both to multiples of 2^k
-// in [0, 2N).  k = tv_shift(tvs): t for many-LUT, 0 otherwise.  The bodies call it under `if constexpr (MANY)` and keep their own k = 0
-// expression for the gates' and the PBS's kernels: routed through this function (k a compile-time 0) those kernels' code changed by a few
-// instructions.
+// in [0, 2N).  k = tv_shift(tvs): t for many-LUT, 0 otherwise.  gate_mask (rtfhe_gate_frame.hpp) and the bodies that still carry their own
+// pre-step call it under `if constexpr (MANY)` and keep the literal k = 0 expression for the gates' and the PBS's kernels: routed through this
+// function (k a compile-time 0) those kernels' code changed by a few instructions.
 __device__ __forceinline__ int tv_shift(const TvGate&) { return 0; }
 __device__ __forceinline__ int tv_shift(const TvLut&) { return 0; }
 __device__ __forceinline__ int tv_shift(const TvMany& t) { return t.t; }
@@ -402,6 +403,13 @@ __device__ __forceinline__ void key_switch_wave(const uint32_t* __restrict__ apr
             if (col + e <= n) out[col + e] = ((col + e == n) ? bprime : 0u) - s[e];
     }
 }
+
+}  // namespace rtfhe
+
+// the prologue and epilogue of every bootstrap kernel, built from the pieces above
+#include "rtfhe_gate_frame.hpp"
+
+namespace rtfhe {
 
 // one wave per SIMD (<= 4 waves per workgroup, N = 1024): separate real/imaginary exchange buffers (see exchange<>)
 __host__ __device__ constexpr bool bootstrap_dual_xbuf(int logn, int waves) { return logn == 10 && waves <= 4; }

@@ -210,20 +210,13 @@ __global__ __launch_bounds__(128 * GATES, 1) void k_bootstrap_ntt_halves(const N
     unsigned sync_k = 0;
 
     const int n = a.n;
-    {   // pre-step + mod switch (tfhe.rs:41-71, 97, 107-108) to [0, 2N)
-        constexpr int SH = 32 - LOGN - 1;
-        for (int i = lane0 + 64 * H; i <= n; i += 128) {
-            const uint32_t t = gate_linear(io.op, io.p0[i], io.p1[i], i == n);
-            abar[i] = (uint16_t)((i == n) ? (t >> SH) : ((t + (1u << (SH - 1))) >> SH));
-        }
-    }
+    const TvGate tvs{};      // the gates' test vector (the exact backends have no PBS twins)
+    const TvGate::Row tv{};
+    gate_mask<LOGN>(io, tvs, n, abar, lane0 + 64 * H, 128);
     __syncthreads();
-    {   // acc = X^{-bbar} * testvec (tfhe.rs:85, 98-106); each wave initialises half of the words
+    {   // each wave initialises half of the words
         const int bbar = (int)abar[n];
-        for (int c = lane0 + 64 * H; c < 2 * N; c += 128) {
-            const int e = (c + bbar) & (2 * N - 1);
-            accbuf[c] = c < N ? ((e >> LOGN) ? 0xE0000000u : 0x20000000u) : 0u;
-        }
+        for (int c = lane0 + 64 * H; c < 2 * N; c += 128) accbuf[c] = acc_start<LOGN>(tvs, tv, bbar, c);
     }
     __syncthreads();
 
@@ -244,49 +237,15 @@ __global__ __launch_bounds__(128 * GATES, 1) void k_bootstrap_ntt_halves(const N
         }
         return;
     }
-    // sample extract index 0 (trlwe.rs:110-121): a'_0 = a_0, a'_k = -a_{N-k}; b' = b_0
-    {
-        uint32_t av[R];
-#pragma unroll
-        for (int m = 0; m < R; m++) av[m] = accbuf[N + lane0 + 64 * m + 1024 * H];
-        __syncthreads();
-#pragma unroll
-        for (int m = 0; m < R; m++) {
-            const int c = lane0 + 64 * m + 1024 * H;
-            accbuf[N + ((N - c) & (N - 1))] = (c == 0) ? av[m] : (0u - av[m]);
-        }
-    }
+    // sample extract index 0: each of the gate's two waves moves half of the a-poly
+    extract_flip<N, R>(accbuf + N, lane0 + 1024 * H, 64, [] { __syncthreads(); });
     __syncthreads();
     if (a.mode == MODE_EXTRACT) {      // the key switch of the whole batch follows as its own launch (k_key_switch_mm)
-        if (live) {
-            const int ge = a.ext_first + g;      // batch-wide gate number: the sample buffer is laid out for the key switch (ext_slot)
-            for (int c = H * (N / 2) + lane0; c < (H + 1) * (N / 2); c += 64) *ext_slot(a.ext, ge, c, N) = accbuf[N + c];
-            if (H == 0 && lane0 == 0) *ext_slot(a.ext, ge, N, N) = accbuf[0];
-            for (int c = H * 64 + lane0; c <= n; c += 128) io.out[c] = 0u;
-        }
+        if (live) gate_extract_store<N>(a.ext, io.out, tvs, n, a.ext_first + g, accbuf, accbuf + N, H * (N / 2) + lane0, (H + 1) * (N / 2), 64, H ? -1 : lane0, H * 64 + lane0, 128);
         return;
     }
-    // identity key switch (tlwe.rs:43-73): each wave sums the rows of half of the coefficients
-    uint4 sum[KSQ];
-    ks_accumulate<LOGN, KS_T, KS_BB, KSQ>(accbuf + N, H * (N / 2), (H + 1) * (N / 2), a.ksk, a.ksw, sum, lane0);
-    uint4* part = reinterpret_cast<uint4*>(xb1) + lane0;   // [KSQ][64] uint4
-    if (H == 1) {
-#pragma unroll
-        for (int q = 0; q < KSQ; q++) part[q * 64] = sum[q];
-    }
-    __syncthreads();
-    if (H == 0 && live) {
-        const uint32_t bprime = accbuf[0];
-#pragma unroll
-        for (int q = 0; q < KSQ; q++) {
-            const uint4 o = part[q * 64];
-            const int col = 4 * (lane0 + 64 * q);
-            const uint32_t s[4] = {sum[q].x + o.x, sum[q].y + o.y, sum[q].z + o.z, sum[q].w + o.w};
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-                if (col + e <= n) io.out[col + e] = ((col + e == n) ? bprime : 0u) - s[e];
-        }
-    }
+    // each wave sums the rows of half of the coefficients; wave 1's sums travel through its exchange buffer
+    gate_key_switch<LOGN, KS_T, KS_BB, KSQ, 2>(a.ksk, a.ksw, io.out, n, accbuf, accbuf + N, reinterpret_cast<uint4*>(xb1), H, lane0, live, [] { __syncthreads(); });
 }
 
 struct NttHalvesBkArgs {

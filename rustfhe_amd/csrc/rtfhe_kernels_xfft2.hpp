@@ -98,21 +98,16 @@ __global__ __launch_bounds__(256 * GATES, 1) void k_bootstrap_xquad(const XBoots
     uint32_t* poly = accbuf + side * N;
 
     const int n = a.n;
-    {   // pre-step + mod switch (tfhe.rs:41-71, 97, 107-108)
-        constexpr int SH = 32 - LOGN - 1;
-        for (int i = lane + 64 * role; i <= n; i += 256) {
-            const uint32_t t = gate_linear(io.op, io.p0[i], io.p1[i], i == n);
-            abar[i] = (i == n) ? (t >> SH) : ((t + (1u << (SH - 1))) >> SH);
-        }
-    }
+    const TvGate tvs{};      // the gates' test vector (the exact backends have no PBS twins)
+    const TvGate::Row tv{};
+    gate_mask<LOGN>(io, tvs, n, abar, lane + 64 * role, 256);
     __syncthreads();
-    {   // acc = X^{-bbar} * testvec (tfhe.rs:85, 98-106): each wave fills the half of its polynomial it will go on updating first
+    {   // each wave fills the half of its polynomial it will go on updating first
         const int bbar = (int)abar[n];
 #pragma unroll
         for (int mm = 0; mm < 2 * R; mm++) {
             const int c = lane + 64 * (mm + 16 * h);
-            const int e = (c + bbar) & (2 * N - 1);
-            poly[c] = side ? 0u : ((e >> LOGN) ? 0xE0000000u : 0x20000000u);
+            poly[c] = side ? acc_start<LOGN>(tvs, tv, bbar, N + c) : acc_start<LOGN>(tvs, tv, bbar, c);
         }
     }
     __syncthreads();
@@ -304,9 +299,9 @@ __global__ __launch_bounds__(256 * GATES, 1) void k_bootstrap_xquad(const XBoots
         }
         return;
     }
-    // sample extract index 0 (trlwe.rs:110-121) on the a-polynomial: a'[0] = a[0], a'[c] = -a[N - c].  Reversed in place, every source would have to
-    // be read before any destination is written; the two waves of side 1 write the reversed polynomial into an idle exchange buffer instead
-    // (N words fit in one), half each.
+    // sample extract index 0 (trlwe.rs:110-121) on the a-polynomial: a'[0] = a[0], a'[c] = -a[N - c].  Reversed in place (extract_flip), every source
+    // would have to be read before any destination is written, one more barrier between the two waves of side 1; they write the reversed polynomial
+    // into an idle exchange buffer instead (N words fit in one), half each: the one kernel whose a' does not lie behind its b-polynomial.
     uint32_t* rev = reinterpret_cast<uint32_t*>(xbase + (size_t)2 * XQuadLds::XB);      // role 2's buffer: free after the step loop
     static_assert((size_t)N * 4 <= XQuadLds::XB, "the reversed a-polynomial fits one exchange buffer");
     if (side == 1) {
@@ -320,40 +315,12 @@ __global__ __launch_bounds__(256 * GATES, 1) void k_bootstrap_xquad(const XBoots
     __syncthreads();
     const uint32_t* aprime = rev;
     if (a.mode == MODE_EXTRACT) {      // the key switch of the whole batch follows as its own launch (k_key_switch_mm)
-        if (live) {
-            const int ge = a.ext_first + g;
-            for (int c = role * (N / 4) + lane; c < (role + 1) * (N / 4); c += 64) *ext_slot(a.ext, ge, c, N) = aprime[c];
-            if (role == 0 && lane == 0) *ext_slot(a.ext, ge, N, N) = accbuf[0];
-            for (int c = role * 64 + lane; c <= n; c += 256) io.out[c] = 0u;
-        }
+        if (live) gate_extract_store<N>(a.ext, io.out, tvs, n, a.ext_first + g, accbuf, aprime, role * (N / 4) + lane, (role + 1) * (N / 4), 64, role ? -1 : lane, role * 64 + lane, 256);
         return;
     }
-    // identity key switch (tlwe.rs:43-73): each wave sums the rows of a quarter of the coefficients; partial sums meet in role 3's buffer
-    uint4 sum[KSQ];
-    ks_accumulate<LOGN, KS_T, KS_BB, KSQ>(aprime, role * (N / 4), (role + 1) * (N / 4), a.ksk, a.ksw, sum, lane);
-    uint4* part = reinterpret_cast<uint4*>(xbase + (size_t)3 * XQuadLds::XB) + lane;   // [3 roles][KSQ][64] uint4
+    // each wave sums the rows of a quarter of the coefficients; the sums of roles 1 .. 3 meet role 0's in role 3's buffer
     static_assert((size_t)3 * KSQ * 64 * sizeof(uint4) <= XQuadLds::XB, "three partial sums in one exchange buffer");
-    if (role != 0) {
-#pragma unroll
-        for (int q = 0; q < KSQ; q++) part[((role - 1) * KSQ + q) * 64] = sum[q];
-    }
-    __syncthreads();
-    if (role == 0 && live) {
-        const uint32_t bprime = accbuf[0];
-#pragma unroll
-        for (int q = 0; q < KSQ; q++) {
-            uint32_t s[4] = {sum[q].x, sum[q].y, sum[q].z, sum[q].w};
-#pragma unroll
-            for (int w = 0; w < 3; w++) {
-                const uint4 o = part[(w * KSQ + q) * 64];
-                s[0] += o.x; s[1] += o.y; s[2] += o.z; s[3] += o.w;
-            }
-            const int col = 4 * (lane + 64 * q);
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-                if (col + e <= n) io.out[col + e] = ((col + e == n) ? bprime : 0u) - s[e];
-        }
-    }
+    gate_key_switch<LOGN, KS_T, KS_BB, KSQ, 4>(a.ksk, a.ksw, io.out, n, accbuf, aprime, reinterpret_cast<uint4*>(xbase + (size_t)3 * XQuadLds::XB), role, lane, live, [] { __syncthreads(); });
 }
 
 // ---- key rows -> split spectra, N = 2048: source polynomial g = (i, comp, row) -> for each key half (hi, lo) and each spectrum half h one row of
