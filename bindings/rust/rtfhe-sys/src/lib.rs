@@ -279,6 +279,15 @@ extern "C" {
     pub fn rtfhe_tlwe_seeded_expand_dev(ctx: *mut rtfhe_ctx, seed: *const u32, first_row: u64, d_b: *const c_void, d_out: *mut c_void, rows: usize,
                                         stream: *mut c_void) -> c_int;
     pub fn rtfhe_load_ksk_seeded(ctx: *mut rtfhe_ctx, seed: *const u32, first_row: u64, b: *const u32) -> c_int;
+    // compressed results: k-bit, bit-packed rows off the GPU; the CPU twins and inverses need no context
+    pub fn rtfhe_tlwe_compress_batch_dev(ctx: *mut rtfhe_ctx, k: i32, d_tlwe: *const c_void, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
+    pub fn rtfhe_trlwe_compress_batch_dev(ctx: *mut rtfhe_ctx, k: i32, d_trlwe: *const c_void, P: i32, coef: *const i32, stride: i32, d_out: *mut c_void,
+                                          count: usize, stream: *mut c_void) -> c_int;
+    pub fn rtfhe_compressed_words(L: usize, k: i32) -> usize;
+    pub fn rtfhe_tlwe_compress(n: i32, k: i32, input: *const u32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_tlwe_expand(n: i32, k: i32, input: *const u32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trlwe_compress(N: i32, k: i32, P: i32, coef: *const i32, stride: i32, input: *const u32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trlwe_expand(N: i32, k: i32, P: i32, coef: *const i32, stride: i32, input: *const u32, out: *mut u32, count: usize) -> c_int;
     // TEST ONLY (seeded xoshiro256**, not secure)
     pub fn rtfhe_ksk_expand_ref(p: *const rtfhe_params, key0: *const i32, key1: *const i32, ksk: *const u32, ksk_ref: *mut u32) -> c_int;
     pub fn rtfhe_ksk_expand_ref_deterministic(p: *const rtfhe_params, seed: u64, key0: *const i32, key1: *const i32, ksk: *const u32, ksk_ref: *mut u32) -> c_int;
@@ -295,5 +304,8 @@ extern "C" {
     pub fn rtfhe_keys_read(path: *const c_char, key0: *mut i32, key1: *mut i32, bk: *mut u32, ksk: *mut u32) -> c_int;
     pub fn rtfhe_tlwe_write(path: *const c_char, n: i32, cts: *const u32, count: usize) -> c_int;
     pub fn rtfhe_tlwe_read(path: *const c_char, n: *mut i32, count: *mut u64, cts: *mut u32, capacity: usize) -> c_int;
+    pub fn rtfhe_compressed_write(path: *const c_char, kind: i32, dim: i32, k: i32, P: i32, coef: *const i32, words: *const u32, count: usize) -> c_int;
+    pub fn rtfhe_compressed_read_header(path: *const c_char, kind: *mut i32, dim: *mut i32, k: *mut i32, P: *mut i32, count: *mut u64) -> c_int;
+    pub fn rtfhe_compressed_read(path: *const c_char, coef: *mut i32, words: *mut u32, capacity: usize) -> c_int;
     pub fn rtfhe_tlwe_phase(p: *const rtfhe_params, key0: *const i32, input: *const u32, phase: *mut u32, count: usize) -> c_int;
 }

@@ -60,6 +60,8 @@
  *   rtfhe_dense_create / rtfhe_tlwe_dense_batch[_dev]
  *                                    <- the Add / scalar multiples of TLWERep (hom_nand/src/tlwe.rs) carried over a whole integer matrix: the weighted sums of
  *                                       lvl0 ciphertexts in front of a bootstrap (the reference has the row operations, not the layer)
+ *   rtfhe_tlwe_compress_batch_dev / rtfhe_trlwe_compress_batch_dev / rtfhe_tlwe_compress / _expand / rtfhe_trlwe_compress / _expand
+ *                                    (no reference counterpart) results rounded to k bits per word and bit-packed on the GPU, expanded by the key holder
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch          <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -1062,6 +1064,54 @@ int rtfhe_tlwe_seeded_expand_dev(rtfhe_ctx *ctx, const uint32_t *seed /* host [8
  * its words into, and from there on IS rtfhe_load_ksk: same device layouts, peers' replicas, error codes and memory accounting. */
 int rtfhe_load_ksk_seeded(rtfhe_ctx *ctx, const uint32_t *seed, uint64_t first_row, const uint32_t *b /* [N][t][base-1] */);
 
+/* ---- compressed results: k-bit, bit-packed ciphertexts off the GPU ----
+ * The seeded forms above cut what a client sends; this cuts what comes back.  A result's mask is computed, so no seed stands for it -- but its low
+ * bits are noise (a bootstrapped lvl0 ciphertext has sigma ~ 0.0116 of the torus in reference mode, 0.0028 in rounded mode, on messages spaced
+ * 1/8 .. 1/32 apart).  Keeping the top k bits of every word and packing them densely is modulus switching plus bit packing: a lvl0 result is 795
+ * bytes at k = 10 instead of 2,544, and 1,024 results packed into one TRLWE (rtfhe_pack_batch) are 3 KB at k = 12.  The rounding and packing run
+ * on the GPU, in the stream or captured graph of the computation, so only the small buffer crosses the bus; the key holder expands on the CPU.
+ *
+ * One row.  A row of L torus words v[0 .. L) and a width k, 2 <= k <= 32:
+ *   - rounding: r[i] = ((v[i] + 2^(31-k)) mod 2^32) >> (32 - k), a k-bit value: round to nearest, ties up, wrapping -- a word that rounds up to
+ *     2^k becomes 0.  For k = 32, r[i] = v[i].
+ *   - packing: the row is a little-endian bit stream of L k bits.  Bit j of r[i] is stream bit i k + j; stream bit s is bit s mod 32 of output
+ *     word s / 32.
+ *   - size: a row occupies W(L, k) = ceil(L k / 32) u32 words (rtfhe_compressed_words); the unused high bits of the last word are ZERO; every row
+ *     starts on a word boundary: the output is u32[count][W].
+ *   - expansion: v'[i] = r[i] << (32 - k), so |v' - v| <= 2^(31-k) on every word, mod 2^32.
+ *
+ * Noise, and choosing k.  Under a binary key with h ones the phase of the expanded ciphertext differs from the original's by at most
+ * (h + 1) 2^-(k+1) of the torus; the spread is about sqrt((h + 1) / 12) 2^-k.  At k = 12, N = 1024 and a random binary key that is a spread of
+ * 0.0015 (measured; worst case seen 0.0054 against the bound 0.062).  The bound is a worst case no real row comes near; size k by the spread,
+ * against the distance between messages and the noise the result already has.  Choosing k is the caller's job: nothing here knows the message space.
+ *
+ * lvl0 form.  The input is [count][n+1]; the row is the whole sample, L = n + 1.
+ * TRLWE form.  The input is [count][2][N], b then a, with a coefficient list exactly as rtfhe_trlwe_extract_batch takes it: a host coef[P], or
+ * NULL for p * stride; 1 <= P <= N; duplicates allowed; copied into the launch arguments when the call is enqueued (a stream capture bakes it
+ * in).  The row is a[0 .. N) followed by b[coef[0]], .., b[coef[P-1]], so L = N + P: the key holder only needs the b coefficients that carry a
+ * result (P = N, k = 12 at N = 1024: 768 words instead of 2,048).  Expansion gives a full [2][N] row whose b is zero at the coefficients that
+ * were not kept -- rtfhe_trlwe_phase and the extract calls read it as it stands; with duplicate coefficients the later entry wins.
+ *
+ * On the device: asynchronous and ordered on `stream`, on the context's primary device, on every backend, with no key loaded.  Nothing is
+ * allocated, so a call may be captured first thing on a fresh stream.  One launch of k_compress_rows, one more per further 512 coefficients.
+ * Checked before anything is launched, RTFHE_ERR_INVALID with a message: null handles or buffers; k outside 2 .. 32; the coefficient list's
+ * rules; count * L < 2^31; the output overlapping the input.  count == 0 returns 0. */
+int rtfhe_tlwe_compress_batch_dev(rtfhe_ctx *ctx, int32_t k, const void *d_tlwe /* [count][n+1] */, void *d_out /* u32[count][W(n+1,k)] */,
+                                  size_t count, void *stream);
+int rtfhe_trlwe_compress_batch_dev(rtfhe_ctx *ctx, int32_t k, const void *d_trlwe /* [count][2][N] */, int32_t P,
+                                   const int32_t *coef /* HOST [P] or NULL */, int32_t stride, void *d_out /* u32[count][W(N+P,k)] */, size_t count,
+                                   void *stream);
+/* The key holder's side, and the host-buffer form of this feature: the same words on the CPU and their inverses, from a plain n or N, with no
+ * context and no GPU (there is no upload-compress-download call: rows that are already on the host are compressed here).  Same checks, returned as
+ * RTFHE_ERR_INVALID; in and out must not overlap. */
+size_t rtfhe_compressed_words(size_t L, int32_t k);            /* W(L, k); 0 for k outside 2 .. 32 */
+int rtfhe_tlwe_compress(int32_t n, int32_t k, const uint32_t *in /* [count][n+1] */, uint32_t *out /* [count][W] */, size_t count);
+int rtfhe_tlwe_expand(int32_t n, int32_t k, const uint32_t *in /* [count][W] */, uint32_t *out /* [count][n+1] */, size_t count);
+int rtfhe_trlwe_compress(int32_t N, int32_t k, int32_t P, const int32_t *coef /* [P] or NULL */, int32_t stride, const uint32_t *in /* [count][2][N] */,
+                         uint32_t *out /* [count][W] */, size_t count);
+int rtfhe_trlwe_expand(int32_t N, int32_t k, int32_t P, const int32_t *coef /* [P] or NULL */, int32_t stride, const uint32_t *in /* [count][W] */,
+                       uint32_t *out /* [count][2][N] */, size_t count);
+
 /* ---- wire format (flat little-endian files with an FNV-1a checksum; the reference has no serialization) ----
  * key file   "RTFHEKY1" | rtfhe_params | u32 flags (1 bk, 2 ksk, 4 secret keys) | u32 0 | [key0 | key1] | [bk] | [ksk] | u64 fnv
  * batch file "RTFHECT1" | i32 n | i32 0 | u64 count | u32[count][n+1] | u64 fnv */
@@ -1073,6 +1123,16 @@ int rtfhe_keys_read_header(const char *path, rtfhe_params *p, uint32_t *flags);
 int rtfhe_keys_read(const char *path, int32_t *key0, int32_t *key1, uint32_t *bk, uint32_t *ksk);
 int rtfhe_tlwe_write(const char *path, int32_t n, const uint32_t *cts, size_t count);
 int rtfhe_tlwe_read(const char *path, int32_t *n, uint64_t *count, uint32_t *cts /* NULL: header only */, size_t capacity);
+/* compressed file "RTFHECZ1" | i32 kind | i32 n or N | i32 k | i32 P (lvl0: 0) | u64 count | i32 coef[P] | u32[count][W] | u64 fnv
+ * Compressed results (above) with what it takes to expand them.  dim is n for lvl0 rows and N for TRLWE rows; coef is the resolved list of kept
+ * coefficients (rows compressed with coef NULL: p * stride), NULL with P = 0 for lvl0 rows.  Read the header first and size coef [P] and words
+ * [count][W] from it; capacity is in rows.  A bad header field, a flipped bit or a short file is RTFHE_ERR_INVALID. */
+#define RTFHE_COMPRESSED_TLWE 0
+#define RTFHE_COMPRESSED_TRLWE 1
+int rtfhe_compressed_write(const char *path, int32_t kind, int32_t dim, int32_t k, int32_t P, const int32_t *coef /* [P] or NULL */,
+                           const uint32_t *words /* [count][W] */, size_t count);
+int rtfhe_compressed_read_header(const char *path, int32_t *kind, int32_t *dim, int32_t *k, int32_t *P, uint64_t *count);
+int rtfhe_compressed_read(const char *path, int32_t *coef /* [P] */, uint32_t *words /* [capacity][W] */, size_t capacity);
 
 #ifdef __cplusplus
 }

@@ -210,6 +210,13 @@ _SIGNATURES = {
     "rtfhe_ksk_keygen_seeded_deterministic": (C.c_int, ["PP", C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "rtfhe_tlwe_seeded_expand_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtfhe_load_ksk_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "rtfhe_tlwe_compress_batch_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtfhe_trlwe_compress_batch_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtfhe_compressed_words": (C.c_size_t, [C.c_size_t, C.c_int32]),
+    "rtfhe_tlwe_compress": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rtfhe_tlwe_expand": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rtfhe_trlwe_compress": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rtfhe_trlwe_expand": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t]),
     "rtfhe_tlwe_decrypt_bits": (C.c_int, ["PP", C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "rtfhe_tlwe_phase": (C.c_int, ["PP", C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "rtfhe_keys_write": (C.c_int, [C.c_char_p, "PP", C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -217,6 +224,10 @@ _SIGNATURES = {
     "rtfhe_keys_read": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtfhe_tlwe_write": (C.c_int, [C.c_char_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "rtfhe_tlwe_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t]),
+    "rtfhe_compressed_write": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rtfhe_compressed_read_header": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_uint64)]),
+    "rtfhe_compressed_read": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_size_t]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -1,5 +1,6 @@
-"""The key holder's side: key generation, encryption, decryption, phases, the CPU expansions of seeded objects and the file formats, through
-the host-only part of the C ABI (rtfhe_keygen.cpp, rtfhe_seeded.cpp, rtfhe_wire.cpp).  Nothing here touches an Engine or needs a GPU.
+"""The key holder's side: key generation, encryption, decryption, phases, the CPU expansions of seeded objects and of compressed results, and the
+file formats, through the host-only part of the C ABI (rtfhe_keygen.cpp, rtfhe_seeded.cpp, rtfhe_compress_plan.cpp, rtfhe_wire.cpp).  Nothing
+here touches an Engine or needs a GPU.
 """
 import ctypes as C
 
@@ -272,6 +273,76 @@ def keygen_seeded(params, seed=None):
             ksk_keygen_seeded(params, key0, key1, noise_seed=noise[1], seed=masks[1]))
 
 
+# ---- compressed results (include/rtfhe.h, "compressed results"): k-bit, bit-packed rows; the key holder expands them here ----------------------
+
+def compressed_words(L, k):
+    """W(L, k) = ceil(L k / 32): the u32 words of one compressed row of L values at k bits (rtfhe_compressed_words); 0 for k outside 2 .. 32."""
+    return int(_ffi.load().rtfhe_compressed_words(int(L), int(k)))
+
+
+def _compress_ck(rc, name):
+    if rc != 0:
+        raise RtfheError(rc, name + " failed (k outside 2 .. 32, a bad coefficient list, count * L not below 2^31, or overlapping buffers)")
+
+
+def _row_words(L, k):
+    """compressed_words for a call that goes on to use it: k outside 2 .. 32 is refused here"""
+    W = compressed_words(L, k)
+    if W == 0:
+        raise RtfheError(ERR_INVALID, "k = %d is outside 2 .. 32 (or the row is empty)" % int(k))
+    return W
+
+
+def _coef(coef, P):
+    if coef is None:
+        return None
+    coef = _np(coef, np.int32).reshape(-1)
+    assert coef.size == int(P), "one coefficient per kept value"
+    return coef
+
+
+def tlwe_compress(n, k, tlwe):
+    """lvl0 rows u32[count][n+1] -> u32[count][W(n+1, k)]: every word rounded to its top k bits (to nearest, ties up, wrapping) and the values
+    packed into a little-endian bit stream (rtfhe_tlwe_compress) -- word for word what Engine.tlwe_compress_dev writes on the GPU."""
+    n, k = int(n), int(k)
+    tlwe = _np(tlwe, np.uint32).reshape(-1, n + 1)
+    out = np.empty((tlwe.shape[0], _row_words(n + 1, k)), np.uint32)
+    _compress_ck(_ffi.load().rtfhe_tlwe_compress(n, k, _ptr(tlwe), _ptr(out), tlwe.shape[0]), "rtfhe_tlwe_compress")
+    return out
+
+
+def tlwe_expand(n, k, words):
+    """The inverse on the key holder's side (rtfhe_tlwe_expand): u32[count][W(n+1, k)] -> u32[count][n+1], each value back at the top of its
+    word, within 2^(31-k) of the original; phases / decrypt_bits read the rows as they are."""
+    n, k = int(n), int(k)
+    words = _np(words, np.uint32).reshape(-1, _row_words(n + 1, k))
+    out = np.empty((words.shape[0], n + 1), np.uint32)
+    _compress_ck(_ffi.load().rtfhe_tlwe_expand(n, k, _ptr(words), _ptr(out), words.shape[0]), "rtfhe_tlwe_expand")
+    return out
+
+
+def trlwe_compress(N, k, trlwe, P, coef=None, stride=1):
+    """TRLWE rows u32[count][2][N] (b then a) -> u32[count][W(N+P, k)]: the a polynomial, then b at the P kept coefficients coef (None:
+    p * stride), rounded and packed as in tlwe_compress (rtfhe_trlwe_compress); what Engine.trlwe_compress_dev writes on the GPU."""
+    N, k, P = int(N), int(k), int(P)
+    trlwe = _np(trlwe, np.uint32).reshape(-1, 2, N)
+    out = np.empty((trlwe.shape[0], _row_words(N + max(P, 0), k)), np.uint32)
+    coef = _coef(coef, P)      # (kept in a name: _ptr holds an address, not the array)
+    _compress_ck(_ffi.load().rtfhe_trlwe_compress(N, k, P, _ptr(coef), int(stride), _ptr(trlwe), _ptr(out), trlwe.shape[0]), "rtfhe_trlwe_compress")
+    return out
+
+
+def trlwe_expand(N, k, words, P, coef=None, stride=1):
+    """The inverse (rtfhe_trlwe_expand): u32[count][W(N+P, k)] -> full rows u32[count][2][N] whose b is zero at the coefficients that were not
+    kept (duplicates: the later entry wins); trlwe_phase and the extract calls read them as they are."""
+    N, k, P = int(N), int(k), int(P)
+    words = _np(words, np.uint32).reshape(-1, _row_words(N + max(P, 0), k))
+    out = np.empty((words.shape[0], 2, N), np.uint32)
+    coef = _coef(coef, P)      # (kept in a name: _ptr holds an address, not the array)
+    _compress_ck(_ffi.load().rtfhe_trlwe_expand(N, k, P, _ptr(coef), int(stride), _ptr(words), _ptr(out), words.shape[0]), "rtfhe_trlwe_expand")
+    return out
+
+
 def trlwe_phase(params, key1, ct):
     """b - a * s of TRLWE ciphertexts u32[count][2][N] under key1: u32[count][N] (the plaintext plus the noise)."""
     L = _ffi.load()
@@ -360,3 +431,29 @@ def load_tlwe(path):
     if L.rtfhe_tlwe_read(path.encode(), C.byref(n), C.byref(count), _ptr(out), count.value) != 0:
         raise RtfheError(ERR_INVALID, "corrupt rtfhe ciphertext file: " + path)
     return out
+
+
+def write_compressed(path, words, k, n=None, N=None, coef=None):
+    """Compressed rows with what it takes to expand them (rtfhe_compressed_write): n for lvl0 rows (tlwe_compress / Engine.tlwe_compress_dev), or
+    N and the resolved list of kept coefficients for TRLWE rows -- rows compressed with coef None pass np.arange(P) * stride."""
+    assert (n is None) != (N is None) and (N is None) == (coef is None), "either n (lvl0 rows) or N and coef (TRLWE rows)"
+    kind, dim = (0, int(n)) if N is None else (1, int(N))
+    coef = None if N is None else _np(coef, np.int32).reshape(-1)
+    P = 0 if coef is None else coef.size
+    words = _np(words, np.uint32).reshape(-1, _row_words(dim + (1 if N is None else P), k))
+    if _ffi.load().rtfhe_compressed_write(path.encode(), kind, dim, int(k), P, _ptr(coef), _ptr(words), words.shape[0]) != 0:
+        raise RtfheError(ERR_INVALID, "rtfhe_compressed_write failed")
+
+
+def read_compressed(path):
+    """Returns (words u32[count][W], k, n, N, coef): n set and N, coef None for lvl0 rows; N and coef set and n None for TRLWE rows -- the
+    arguments of tlwe_expand(n, k, words) or trlwe_expand(N, k, words, len(coef), coef)."""
+    L = _ffi.load()
+    kind, dim, k, P, count = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint64()
+    if L.rtfhe_compressed_read_header(path.encode(), C.byref(kind), C.byref(dim), C.byref(k), C.byref(P), C.byref(count)) != 0:
+        raise RtfheError(ERR_INVALID, "not an rtfhe compressed file: " + path)
+    coef = np.empty(P.value, np.int32) if kind.value == 1 else None
+    words = np.empty((count.value, compressed_words(dim.value + (P.value if kind.value == 1 else 1), k.value)), np.uint32)
+    if L.rtfhe_compressed_read(path.encode(), _ptr(coef), _ptr(words), count.value) != 0:
+        raise RtfheError(ERR_INVALID, "corrupt rtfhe compressed file: " + path)
+    return (words, k.value, None, dim.value, coef) if kind.value == 1 else (words, k.value, dim.value, None, None)

@@ -5,6 +5,8 @@
 //   key file   : "RTFHEKY1" | rtfhe_params (7 x i32) | u32 flags (bit0 bk, bit1 ksk, bit2 secret keys) | u32 reserved
 //                | [key0 i32[n] | key1 i32[N]]  | [bk u32[n][2][2l][N]] | [ksk u32[N][t][base-1][n+1]] | u64 fnv1a of all previous bytes
 //   batch file : "RTFHECT1" | i32 n | i32 reserved | u64 count | u32[count][n+1] | u64 fnv1a
+//   compressed : "RTFHECZ1" | i32 kind (0 lvl0, 1 TRLWE) | i32 n or N | i32 k | i32 P (lvl0: 0) | u64 count | i32 coef[P]
+//                | u32[count][W] (include/rtfhe.h, "compressed results": W = ceil(L k / 32), L = n + 1 or N + P) | u64 fnv1a
 //   table file : "RTFHETW1" | i32 N | i32 reserved | f64 ifft_table[2N] | f64 fft_table[2N] | u64 fnv1a
 //                (the reference's two twiddle tables in its own memory layout, new_ifft_table / new_fft_table,
 //                 utils/src/spqlios/spqlios-fft-impl.cpp:400-437 / 158-193: what rtfhe_set_twiddles takes)
@@ -31,6 +33,24 @@ bool sane(const rtfhe_params& p) {
 const char KEY_MAGIC[8] = {'R', 'T', 'F', 'H', 'E', 'K', 'Y', '1'};
 const char CT_MAGIC[8] = {'R', 'T', 'F', 'H', 'E', 'C', 'T', '1'};
 const char TW_MAGIC[8] = {'R', 'T', 'F', 'H', 'E', 'T', 'W', '1'};
+const char CZ_MAGIC[8] = {'R', 'T', 'F', 'H', 'E', 'C', 'Z', '1'};
+
+// the fixed part of a compressed file's header, as it lies in the file (24 bytes, no padding)
+struct CzHeader { int32_t kind, dim, k, P; uint64_t count; };
+static_assert(sizeof(CzHeader) == 24, "the compressed file's header is 4 x i32 | u64");
+// lvl0 rows carry no coefficient list; TRLWE rows keep 1 .. N coefficients; dim < 2^20 as every other file here, count * L within what the calls take
+bool cz_sane(const CzHeader& h) {
+    if (h.dim < 1 || h.dim >= (1 << 20) || h.k < 2 || h.k > 32) return false;
+    if (h.kind == RTFHE_COMPRESSED_TLWE ? h.P != 0 : (h.kind != RTFHE_COMPRESSED_TRLWE || h.P < 1 || h.P > h.dim)) return false;
+    return h.count <= 0x7fffffffull / ((uint64_t)h.dim + (h.kind == RTFHE_COMPRESSED_TLWE ? 1u : (uint32_t)h.P));
+}
+bool cz_coef_sane(const CzHeader& h, const int32_t* coef) {
+    if (!coef) return false;
+    for (int32_t p = 0; p < h.P; p++) if (coef[p] < 0 || coef[p] >= h.dim) return false;
+    return true;
+}
+// W(L, k) of include/rtfhe.h, restated so that this unit keeps linking on its own
+size_t cz_row_words(const CzHeader& h) { return (((size_t)h.dim + (h.kind == RTFHE_COMPRESSED_TLWE ? 1u : (size_t)h.P)) * (size_t)h.k + 31) / 32; }
 
 }  // namespace
 
@@ -112,6 +132,47 @@ int rtfhe_tlwe_read(const char* path, int32_t* n, uint64_t* count, uint32_t* cts
         uint64_t sum = 0;
         ok = ok && std::fread(&sum, 1, 8, f) == 8 && sum == h.h;
     }
+    std::fclose(f);
+    return ok ? 0 : RTFHE_ERR_INVALID;
+}
+
+// Compressed results as a file: the header says how the rows were made -- kind, n or N, k, and for TRLWE rows the P kept coefficients, resolved
+// (a writer that compressed with coef NULL passes p * stride) -- so that the reader can expand them with nothing else in hand.
+int rtfhe_compressed_write(const char* path, int32_t kind, int32_t dim, int32_t k, int32_t P, const int32_t* coef, const uint32_t* words, size_t count) {
+    const CzHeader hd{kind, dim, k, P, (uint64_t)count};
+    if (!path || !cz_sane(hd) || (P && !cz_coef_sane(hd, coef)) || (!words && count)) return RTFHE_ERR_INVALID;
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return RTFHE_ERR_INVALID;
+    Fnv h;
+    bool ok = wr(f, h, CZ_MAGIC, 8) && wr(f, h, &hd, sizeof hd) && (P == 0 || wr(f, h, coef, (size_t)P * 4)) && (count == 0 || wr(f, h, words, count * cz_row_words(hd) * 4));
+    const uint64_t sum = h.h;
+    ok = ok && std::fwrite(&sum, 1, 8, f) == 8;
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? 0 : RTFHE_ERR_INVALID;
+}
+
+int rtfhe_compressed_read_header(const char* path, int32_t* kind, int32_t* dim, int32_t* k, int32_t* P, uint64_t* count) {
+    if (!path || !kind || !dim || !k || !P || !count) return RTFHE_ERR_INVALID;
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return RTFHE_ERR_INVALID;
+    Fnv h; char magic[8]; CzHeader hd{};
+    const bool ok = rd(f, h, magic, 8) && !std::memcmp(magic, CZ_MAGIC, 8) && rd(f, h, &hd, sizeof hd) && cz_sane(hd);
+    std::fclose(f);
+    if (ok) { *kind = hd.kind; *dim = hd.dim; *k = hd.k; *P = hd.P; *count = hd.count; }
+    return ok ? 0 : RTFHE_ERR_INVALID;
+}
+
+// buffers sized from the header: coef [P] (not looked at for lvl0 rows, P = 0), words [capacity >= count][W].  Verifies the checksum.
+int rtfhe_compressed_read(const char* path, int32_t* coef, uint32_t* words, size_t capacity) {
+    if (!path) return RTFHE_ERR_INVALID;
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return RTFHE_ERR_INVALID;
+    Fnv h; char magic[8]; CzHeader hd{};
+    bool ok = rd(f, h, magic, 8) && !std::memcmp(magic, CZ_MAGIC, 8) && rd(f, h, &hd, sizeof hd) && cz_sane(hd);
+    ok = ok && (hd.P == 0 || (coef && rd(f, h, coef, (size_t)hd.P * 4) && cz_coef_sane(hd, coef)));
+    ok = ok && hd.count <= capacity && (hd.count == 0 || (words && rd(f, h, words, (size_t)hd.count * cz_row_words(hd) * 4)));
+    uint64_t sum = 0;
+    ok = ok && std::fread(&sum, 1, 8, f) == 8 && sum == h.h;
     std::fclose(f);
     return ok ? 0 : RTFHE_ERR_INVALID;
 }

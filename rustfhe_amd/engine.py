@@ -561,6 +561,21 @@ class Engine(_Handle):
         self._ck(self.L.rtfhe_trlwe_extract_lvl1_batch_dev(self.h, self._dev(d_trlwe), int(P), _ptr(self._coef_arg(coef, P)), int(stride), self._dev(d_out),
                                                            count, _stream(stream)))
 
+    # ---- compressed results (include/rtfhe.h: rtfhe_tlwe_compress_batch_dev, rtfhe_trlwe_compress_batch_dev) ---------------------------------------
+    def tlwe_compress_dev(self, d_tlwe, k, d_out, count, stream=None):
+        """lvl0 rows on the device ([count][n+1] words) -> d_out u32[count][W(n+1, k)], every word rounded to its top k bits and bit-packed
+        (rustfhe_amd.compressed_words gives W, rustfhe_amd.tlwe_expand undoes it on the CPU).  One launch, asynchronous on `stream`, no key, every
+        backend; allocates nothing: it may be captured first thing on a fresh stream.  d_out must not overlap d_tlwe."""
+        self._ck(self.L.rtfhe_tlwe_compress_batch_dev(self.h, int(k), self._dev(d_tlwe), self._dev(d_out), count, _stream(stream)))
+
+    def trlwe_compress_dev(self, d_trlwe, k, P, d_out, count, coef=None, stride=1, stream=None):
+        """TRLWE rows on the device ([count][2][N] words, b then a) -> d_out u32[count][W(N+P, k)]: the a polynomial and b at the P kept
+        coefficients coef (a host array, copied at enqueue time; None: p * stride), rounded and bit-packed; rustfhe_amd.trlwe_expand undoes it on
+        the CPU.  Asynchronous on `stream`, no key, every backend, nothing allocated."""
+        coef = self._coef_arg(coef, P)      # (kept in a name: _ptr holds an address, not the array)
+        self._ck(self.L.rtfhe_trlwe_compress_batch_dev(self.h, int(k), self._dev(d_trlwe), int(P), _ptr(coef), int(stride), self._dev(d_out), count,
+                                                       _stream(stream)))
+
     # ---- exact TRLWE x plain-polynomial products (include/rtfhe.h: rtfhe_plain_create, rtfhe_trlwe_mul_plain_batch[_dev]) --------------------------
     def plain_polys(self, w):
         """Transforms integer polynomials int32[n_w][N] once and keeps them as spectra on the primary device; a PlainPolys handle (.n polynomials,
