@@ -270,13 +270,6 @@ int rtfhe_circuit_launch(rtfhe_circuit* c, void* stream) {
     return 0;
 }
 
-void rtfhe_circuit_destroy(rtfhe_circuit* c) {
-    if (!c) return;
-    if (c->ctx) {      // still attached
-        detach(c->ctx->circuits, c);
-        circuit_release(c);
-    }
-    delete c;
-}
+void rtfhe_circuit_destroy(rtfhe_circuit* c) { handle_destroy(&rtfhe_ctx::circuits, c, circuit_release); }
 
 }  // extern "C"

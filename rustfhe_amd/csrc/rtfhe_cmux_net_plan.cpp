@@ -2,28 +2,17 @@
 // rtfhe_cmux_circuit_create (rtfhe_cmux_net.hip) allocates or launches anything.
 #include "rtfhe_cmux_net_plan.h"
 
-#include <cstdio>
-#include <string>
 #include <vector>
 
-#include "../../include/rtfhe.h"
+#include "rtfhe_plan_kit.hpp"
 
-namespace {
-
-int refuse(char* err, size_t err_len, const std::string& msg) {
-    if (err && err_len) std::snprintf(err, err_len, "%s", msg.c_str());
-    return RTFHE_ERR_INVALID;
-}
-
-std::string num(long long v) { return std::to_string(v); }
-
-}  // namespace
+using namespace rtfhe_plan;
 
 extern "C" int rtfhe_cmux_net_plan(const rtfhe_cmux_net_world* w, const int32_t* var, const int32_t* hi, const int32_t* lo, const int32_t* rot,
                                    int32_t n_nodes, int32_t n_vars, const int32_t* out_ref, const int32_t* out_coef, int32_t n_out,
                                    int32_t* order, int32_t* level_off, int32_t* n_levels, int32_t* leaf_span, size_t* node_bytes, char* err,
                                    size_t err_len) {
-    if (err && err_len) err[0] = 0;
+    begin(err, err_len);
     if (!w || !var || !hi || !lo || !out_ref || !order || !level_off || !n_levels || !leaf_span || !node_bytes)
         return refuse(err, err_len, "rtfhe_cmux_circuit_create: null argument");
     if (n_nodes < 1 || n_vars < 1 || n_out < 1 || w->count < 1)
@@ -70,7 +59,7 @@ extern "C" int rtfhe_cmux_net_plan(const rtfhe_cmux_net_world* w, const int32_t*
     // count * n_nodes * 2N words of 4 bytes, and count * max(n_nodes, n_out) waves per launch as a 32-bit number
     const size_t per = (size_t)n_nodes * 2 * (size_t)N * 4, most = n_nodes > n_out ? (size_t)n_nodes : (size_t)n_out;
     if (w->count > (size_t)-1 / per) return refuse(err, err_len, "the node buffer count * n_nodes * 8N bytes does not fit size_t");
-    if (w->count > (size_t)0x7fffffff / most) return refuse(err, err_len, "count * max(n_nodes, n_out) too large");
+    if (!count_fits(w->count, most)) return refuse(err, err_len, "count * max(n_nodes, n_out) too large");
     *node_bytes = w->count * per;
     // counting sort by level: index order within a level
     const int32_t levels = deepest + 1;

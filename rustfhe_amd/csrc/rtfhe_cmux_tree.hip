@@ -13,9 +13,11 @@
 #include "rtfhe_kernels_cmux_tree.hpp"
 #include "rtfhe_kernels_demux_tree.hpp"
 #include "rtfhe_kernels_trgsw_rotate.hpp"
+#include "rtfhe_plan_kit.hpp"
 
 using namespace rtfhe;
 using namespace rtfhe_host;
+using rtfhe_plan::rows_overlap;
 
 namespace {
 
@@ -45,11 +47,6 @@ int sel_idx_ready(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, int32_t depth, size_t 
                     return fail(ctx, RTFHE_ERR_INVALID, "lookup " + std::to_string(g) + ": sel_idx[" + std::to_string(k) + "] = " + std::to_string(host_sel_idx[g * depth + k]) +
                                                         " is outside [0, " + std::to_string(n_sel) + ")");
     return 0;
-}
-
-bool overlaps(const void* in, size_t in_bytes, const void* out, size_t out_bytes) {
-    const char *i0 = (const char*)in, *o0 = (const char*)out;
-    return i0 < o0 + out_bytes && o0 < i0 + in_bytes;
 }
 
 // the ping-pong buffers of a tree's or a demultiplexer's levels on stream s, `need` words each (0: a single level, no buffer, nothing to refuse)
@@ -124,15 +121,11 @@ int tree_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int3
 int tree_host(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, int32_t depth, const rtfhe_lut* lut, const int32_t* row0, const int32_t* coef,
               uint32_t* out, size_t count, bool extract) {
     if (int rc = tree_ready(ctx, sel, lut, depth, count, sel_idx != nullptr, row0 != nullptr, sel_idx, row0, coef, out, extract)) return rc;
-    if (int rc = use(ctx)) return rc;
-    if (count == 0) return 0;
     const size_t out_bytes = count * (extract ? (size_t)ctx->p.n + 1 : (size_t)2 * ctx->p.N) * 4;
-    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
-    StagedIdx d_sel, d_rows;
-    if (int rc = stage_idx(ctx, &ctx->d_a, &ctx->cap_a, count * depth, sel_idx, nullptr, d_sel)) return rc;
-    if (int rc = stage_idx(ctx, &ctx->d_b, &ctx->cap_b, count, row0, coef, d_rows)) return rc;
-    if (int rc = launch_tree(ctx, sel, d_sel.first, depth, lut, d_rows.first, d_rows.second, ctx->d_c, count, extract, ctx->stream)) return rc;
-    return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+    return host_form(ctx, count, {staging_a(ctx), nullptr, 0}, {staging_c(ctx), out, out_bytes, false},
+                     {{staging_a(ctx), count * depth, sel_idx, nullptr}, {staging_b(ctx), count, row0, coef}}, [&](const void*, const StagedIdx* idx, void* d_out) {
+        return launch_tree(ctx, sel, idx[0].first, depth, lut, idx[1].first, idx[1].second, d_out, count, extract, ctx->stream);
+    });
 }
 
 // ---- CMUX demultiplexer tree ----
@@ -218,7 +211,7 @@ int rotate_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, in
     if (int rc = use(ctx)) return rc;
     if (int rc = device_pointers(ctx, name, {d_out, d_trlwe}, {d_sel_idx})) return rc;
     const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = extract ? count * ((size_t)ctx->p.n + 1) * 4 : in_bytes;
-    if (d_out != d_trlwe ? overlaps(d_trlwe, in_bytes, d_out, out_bytes) : extract)
+    if (d_out != d_trlwe ? rows_overlap(d_trlwe, in_bytes, d_out, out_bytes) : extract)
         return fail(ctx, RTFHE_ERR_INVALID, std::string(name) + ": d_out overlaps d_trlwe (it may only be exactly d_trlwe, in the form without extraction)");
     return launch_rotate(ctx, sel, (const int32_t*)d_sel_idx, depth, rot, d_trlwe, d_out, count, extract, (hipStream_t)stream);
 }
@@ -227,16 +220,11 @@ int rotate_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, in
 int rotate_host(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, int32_t depth, const int32_t* rot, const uint32_t* trlwe, uint32_t* out, size_t count,
                 bool extract) {
     if (int rc = rotate_ready(ctx, sel, depth, rot, count, sel_idx != nullptr, sel_idx, trlwe, out, extract)) return rc;
-    if (int rc = use(ctx)) return rc;
-    if (count == 0) return 0;
     const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = extract ? count * ((size_t)ctx->p.n + 1) * 4 : in_bytes;
-    if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, in_bytes)) return rc;
-    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
-    StagedIdx d_sel;
-    if (int rc = stage_idx(ctx, &ctx->d_a, &ctx->cap_a, count * depth, sel_idx, nullptr, d_sel)) return rc;
-    if (int rc = copy_in(ctx, ctx->d_b, trlwe, in_bytes, 1)) return rc;
-    if (int rc = launch_rotate(ctx, sel, d_sel.first, depth, rot, ctx->d_b, ctx->d_c, count, extract, ctx->stream)) return rc;
-    return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+    return host_form(ctx, count, {staging_b(ctx), trlwe, in_bytes}, {staging_c(ctx), out, out_bytes, false}, {{staging_a(ctx), count * depth, sel_idx, nullptr}},
+                     [&](const void* d_trlwe, const StagedIdx* idx, void* d_out) {
+        return launch_rotate(ctx, sel, idx[0].first, depth, rot, d_trlwe, d_out, count, extract, ctx->stream);
+    });
 }
 
 }  // namespace
@@ -282,21 +270,12 @@ static int trgsw_create_staged(rtfhe_ctx* ctx, int32_t n_sel, rtfhe_trgsw** out,
     if (int rc = prime_trgsw_mac(ctx)) return rc;
     const size_t polys = (size_t)n_sel * 2 * 2 * ctx->p.l, words = polys * ctx->p.N;
     if (polys > 0x7fffffff) return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_trgsw_create: n_sel too large");
-    rtfhe_trgsw* t = new rtfhe_trgsw();
+    NewHandle<rtfhe_trgsw> t = new_handle(ctx, trgsw_release);
     t->n_sel = n_sel;
-    t->ctx = ctx;
     int rc = hipMalloc((void**)&t->d_spec, words / 2 * sizeof(cplx)) == hipSuccess ? 0 : fail(ctx, RTFHE_ERR_HIP, "rtfhe_trgsw_create: hipMalloc");
     if (!rc) rc = convert_selectors(ctx, t->d_spec, n_sel, stage);
     if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_trgsw_create: hipStreamSynchronize");
-    if (rc) {
-        (void)hipGetLastError();
-        trgsw_release(t);
-        delete t;
-        return rc;
-    }
-    ctx->trgsws.push_back(t);
-    *out = t;
-    return 0;
+    return rc ? rc : handle_publish(ctx->trgsws, std::move(t), out);
 }
 
 extern "C" {
@@ -318,13 +297,9 @@ int rtfhe_trgsw_create_seeded(rtfhe_ctx* ctx, const uint32_t* seed, uint64_t fir
 }
 
 void rtfhe_trgsw_destroy(rtfhe_trgsw* t) {
-    if (!t) return;
-    if (rtfhe_ctx* ctx = t->ctx) {     // still attached
-        detach(ctx->trgsws, t);
+    handle_destroy(&rtfhe_ctx::trgsws, t, trgsw_release, [t](rtfhe_ctx* ctx) {
         for (rtfhe_circuit* c : ctx->circuits) if (c->sel == t) { c->sel = nullptr; c->sel_gone = true; }      // CMUX netlists recorded on this set
-        trgsw_release(t);
-    }
-    delete t;
+    });
 }
 
 int rtfhe_cmux_tree_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, int32_t depth, const rtfhe_lut* lut, const int32_t* row0,
@@ -349,17 +324,10 @@ int rtfhe_cmux_tree_extract_batch_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, co
 
 int rtfhe_demux_tree_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* sel_idx, int32_t depth, const uint32_t* x, uint32_t* out, size_t count) {
     if (int rc = demux_ready(ctx, sel, depth, count, sel_idx != nullptr, sel_idx, x, out)) return rc;
-    if (int rc = use(ctx)) return rc;
-    if (count == 0) return 0;
     // host buffers: sel_idx rides in d_a, the inputs in d_b, the leaves come back through d_c
     const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = in_bytes << depth;
-    if (int rc = ensure(ctx, &ctx->d_b, &ctx->cap_b, in_bytes)) return rc;
-    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
-    StagedIdx d_sel;
-    if (int rc = stage_idx(ctx, &ctx->d_a, &ctx->cap_a, count * depth, sel_idx, nullptr, d_sel)) return rc;
-    if (int rc = copy_in(ctx, ctx->d_b, x, in_bytes, 1)) return rc;
-    if (int rc = launch_demux(ctx, sel, d_sel.first, depth, ctx->d_b, ctx->d_c, count, ctx->stream)) return rc;
-    return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+    return host_form(ctx, count, {staging_b(ctx), x, in_bytes}, {staging_c(ctx), out, out_bytes, false}, {{staging_a(ctx), count * depth, sel_idx, nullptr}},
+                     [&](const void* d_x, const StagedIdx* idx, void* d_out) { return launch_demux(ctx, sel, idx[0].first, depth, d_x, d_out, count, ctx->stream); });
 }
 
 int rtfhe_demux_tree_batch_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int32_t depth, const void* d_x, void* d_out, size_t count,
@@ -368,7 +336,7 @@ int rtfhe_demux_tree_batch_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const voi
     if (int rc = use(ctx)) return rc;
     if (int rc = device_pointers(ctx, "rtfhe_demux_tree_batch_dev", {d_out, d_x}, {d_sel_idx})) return rc;
     const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = in_bytes << depth;
-    if (overlaps(d_x, in_bytes, d_out, out_bytes))      // the last level stores leaves while other waves still read their nodes (depth 1: x itself)
+    if (rows_overlap(d_x, in_bytes, d_out, out_bytes))      // the last level stores leaves while other waves still read their nodes (depth 1: x itself)
         return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_demux_tree_batch_dev: d_out overlaps d_x");
     return launch_demux(ctx, sel, (const int32_t*)d_sel_idx, depth, d_x, d_out, count, (hipStream_t)stream);
 }

@@ -4,30 +4,22 @@
 // coefficient list of the TRLWE form is rtfhe_extract_plan's (rtfhe_extract_plan.cpp), called here and not restated.
 #include "rtfhe_compress_plan.h"
 
-#include <cstdio>
-#include <string>
 #include <vector>
 
-#include "../../include/rtfhe.h"
 #include "rtfhe_extract_plan.h"
+#include "rtfhe_plan_kit.hpp"
+
+using namespace rtfhe_plan;
 
 namespace {
-
-int refuse(char* err, size_t err_len, const std::string& msg) {
-    if (err && err_len) std::snprintf(err, err_len, "%s", msg.c_str());
-    return RTFHE_ERR_INVALID;
-}
-
-std::string num(long long v) { return std::to_string(v); }
 
 // k in range, count * L < 2^31, and the full rows [count][full_words] against the packed rows [count][W(L, k)]
 int size_and_overlap(int32_t dir, int32_t k, size_t L, size_t full_words, size_t count, const void* in, const void* out, char* err, size_t err_len) {
     if (k < 2 || k > 32) return refuse(err, err_len, "k = " + num(k) + " is outside [2, 32]");
-    if (count > (size_t)0x7fffffff / L) return refuse(err, err_len, "count * L too large (count * " + num((long long)L) + " words must be below 2^31)");
+    if (!count_fits(count, L)) return refuse(err, err_len, "count * L too large (count * " + num((long long)L) + " words must be below 2^31)");
     const size_t packed_bytes = count * rtfhe_compressed_words(L, k) * 4, full_bytes = count * full_words * 4;
     const size_t in_bytes = dir == RTFHE_COMPRESS_PACK ? full_bytes : packed_bytes, out_bytes = dir == RTFHE_COMPRESS_PACK ? packed_bytes : full_bytes;
-    const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
-    if (i0 < o0 + out_bytes && o0 < i0 + in_bytes) return refuse(err, err_len, "the output overlaps the input rows");
+    if (rows_overlap(in, in_bytes, out, out_bytes)) return refuse(err, err_len, "the output overlaps the input rows");
     return 0;
 }
 
@@ -61,7 +53,7 @@ extern "C" {
 size_t rtfhe_compressed_words(size_t L, int32_t k) { return k < 2 || k > 32 ? 0 : (L * (size_t)k + 31) / 32; }
 
 int rtfhe_tlwe_compress_plan(int32_t dir, int32_t n, int32_t k, size_t count, const void* in, const void* out, char* err, size_t err_len) {
-    if (err && err_len) err[0] = 0;
+    begin(err, err_len);
     if (!in || !out) return refuse(err, err_len, "null argument");
     if (n < 1) return refuse(err, err_len, "n = " + num(n) + " is below 1");
     return size_and_overlap(dir, k, (size_t)n + 1, (size_t)n + 1, count, in, out, err, err_len);
@@ -69,7 +61,7 @@ int rtfhe_tlwe_compress_plan(int32_t dir, int32_t n, int32_t k, size_t count, co
 
 int rtfhe_trlwe_compress_plan(int32_t dir, int32_t N, int32_t k, int32_t P, const int32_t* coef, int32_t stride, size_t count, const void* in,
                               const void* out, int32_t* idx, char* err, size_t err_len) {
-    if (err && err_len) err[0] = 0;
+    begin(err, err_len);
     if (!in || !out || !idx) return refuse(err, err_len, "null argument");
     if (N < 1) return refuse(err, err_len, "N = " + num(N) + " is below 1");
     // the list alone: with count = 0 rtfhe_extract_plan has no size and no overlap left to look at

@@ -85,8 +85,8 @@ int rtfhe_dense_create(rtfhe_ctx* ctx, const int32_t* W, int32_t O, int32_t I, r
     if (int rc = allow_lds(ctx, k_tlwe_dense<1>, 0)) return rc;
     if (int rc = allow_lds(ctx, k_tlwe_dense<2>, 0)) return rc;
     if (int rc = allow_lds(ctx, k_tlwe_dense<4>, 0)) return rc;
-    rtfhe_dense* t = new rtfhe_dense();
-    t->ctx = ctx; t->O = O; t->I = I; t->ksteps = (I + 63) / 64; t->otiles = (O + 15) / 16;
+    NewHandle<rtfhe_dense> t = new_handle(ctx, dense_release);
+    t->O = O; t->I = I; t->ksteps = (I + 63) / 64; t->otiles = (O + 15) / 16;
     const size_t raw_bytes = (size_t)O * (size_t)I * 4, mat_v4 = (size_t)t->otiles * (size_t)t->ksteps * 64;
     int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, raw_bytes);
     if (!rc && hipMalloc((void**)&t->d_wmat, mat_v4 * sizeof(uint4)) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_dense_create: hipMalloc");
@@ -99,39 +99,17 @@ int rtfhe_dense_create(rtfhe_ctx* ctx, const int32_t* W, int32_t O, int32_t I, r
         rc = launch_kernel(ctx, k_dense_build, dim3((unsigned)std::min<size_t>((mat_v4 + 255) / 256, 2048)), dim3(256), 0, ctx->stream, a, false);
     }
     if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_dense_create: hipStreamSynchronize");
-    if (rc) {
-        (void)hipGetLastError();
-        dense_release(t);
-        delete t;
-        return rc;
-    }
-    ctx->denses.push_back(t);
-    *out = t;
-    return 0;
+    return rc ? rc : handle_publish(ctx->denses, std::move(t), out);
 }
 
-void rtfhe_dense_destroy(rtfhe_dense* w) {
-    if (!w) return;
-    if (rtfhe_ctx* ctx = w->ctx) {     // still attached
-        detach(ctx->denses, w);
-        dense_release(w);
-    }
-    delete w;
-}
+void rtfhe_dense_destroy(rtfhe_dense* w) { handle_destroy(&rtfhe_ctx::denses, w, dense_release); }
 
 // host buffers: the rows ride in d_a, the result comes back through d_c (which takes the caller's out first when accumulating)
 int rtfhe_tlwe_dense_batch(rtfhe_ctx* ctx, const rtfhe_dense* w, const uint32_t* x, const uint32_t* bias, int32_t accumulate, uint32_t* out, size_t count) {
     if (int rc = dense_ready(ctx, w, x, out, count)) return rc;
-    if (int rc = use(ctx)) return rc;
-    if (count == 0) return 0;
-    const size_t row = ((size_t)ctx->p.n + 1) * 4, in_bytes = count * (size_t)w->I * row, out_bytes = count * (size_t)w->O * row;
-    if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, in_bytes)) return rc;
-    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
-    if (int rc = copy_in(ctx, ctx->d_a, x, in_bytes, 0)) return rc;
-    if (accumulate)
-        if (int rc = copy_in(ctx, ctx->d_c, out, out_bytes, 1)) return rc;
-    if (int rc = launch_dense(ctx, w, ctx->d_a, bias, accumulate, ctx->d_c, count, ctx->stream)) return rc;
-    return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+    const size_t row = ((size_t)ctx->p.n + 1) * 4;
+    return host_form(ctx, count, {staging_a(ctx), x, count * (size_t)w->I * row}, {staging_c(ctx), out, count * (size_t)w->O * row, accumulate != 0}, {},
+                     [&](const void* d_x, const StagedIdx*, void* d_out) { return launch_dense(ctx, w, d_x, bias, accumulate, d_out, count, ctx->stream); });
 }
 
 int rtfhe_tlwe_dense_batch_dev(rtfhe_ctx* ctx, const rtfhe_dense* w, const void* d_x, const uint32_t* bias, int32_t accumulate, void* d_out, size_t count,

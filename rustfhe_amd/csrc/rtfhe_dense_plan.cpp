@@ -2,19 +2,11 @@
 // before rtfhe_dense_create and rtfhe_tlwe_dense_batch[_dev] (rtfhe_dense.hip) allocate or launch anything.
 #include "rtfhe_dense_plan.h"
 
-#include <cstdio>
-#include <string>
+#include "rtfhe_plan_kit.hpp"
 
-#include "../../include/rtfhe.h"
+using namespace rtfhe_plan;
 
 namespace {
-
-int refuse(char* err, size_t err_len, const std::string& msg) {
-    if (err && err_len) std::snprintf(err, err_len, "%s", msg.c_str());
-    return RTFHE_ERR_INVALID;
-}
-
-std::string num(long long v) { return std::to_string(v); }
 
 // 1 <= O, I <= RTFHE_DENSE_MAX, else the message
 std::string dims(int32_t O, int32_t I) {
@@ -26,7 +18,7 @@ std::string dims(int32_t O, int32_t I) {
 }  // namespace
 
 extern "C" int rtfhe_dense_weights_plan(const int32_t* W, int32_t O, int32_t I, uint32_t* corr, char* err, size_t err_len) {
-    if (err && err_len) err[0] = 0;
+    begin(err, err_len);
     if (!W || !corr) return refuse(err, err_len, "null argument");
     const std::string bad = dims(O, I);
     if (!bad.empty()) return refuse(err, err_len, bad);
@@ -44,16 +36,15 @@ extern "C" int rtfhe_dense_weights_plan(const int32_t* W, int32_t O, int32_t I, 
 }
 
 extern "C" int rtfhe_dense_plan(int32_t n, int32_t O, int32_t I, size_t count, const void* x, const void* out, char* err, size_t err_len) {
-    if (err && err_len) err[0] = 0;
+    begin(err, err_len);
     if (!x || !out) return refuse(err, err_len, "null argument");
     if (n < 1) return refuse(err, err_len, "n = " + num(n) + " is below 1");
     const std::string bad = dims(O, I);
     if (!bad.empty()) return refuse(err, err_len, bad);
     const size_t words = (size_t)n + 1, widest = (size_t)(I > O ? I : O) * words;       // <= 2^16 * 2^31: no overflow in 64 bits
-    if (count > (size_t)0x7fffffff / widest) return refuse(err, err_len, "count * max(I, O) * (n + 1) too large (it must be below 2^31 words)");
+    if (!count_fits(count, widest)) return refuse(err, err_len, "count * max(I, O) * (n + 1) too large (it must be below 2^31 words)");
     const size_t in_bytes = count * (size_t)I * words * 4, out_bytes = count * (size_t)O * words * 4;
-    const uintptr_t i0 = (uintptr_t)x, o0 = (uintptr_t)out;
-    if (count && i0 < o0 + out_bytes && o0 < i0 + in_bytes) return refuse(err, err_len, "the output overlaps the input rows x");
+    if (count && rows_overlap(x, in_bytes, out, out_bytes)) return refuse(err, err_len, "the output overlaps the input rows x");
     return 0;
 }
 

@@ -70,14 +70,10 @@ int extract_dev(rtfhe_ctx* ctx, const void* d_trlwe, int32_t P, const int32_t* c
 int extract_host(rtfhe_ctx* ctx, const uint32_t* trlwe, int32_t P, const int32_t* coef, int32_t stride, uint32_t* out, size_t count, bool lvl1) {
     std::vector<int32_t> idx;
     if (int rc = extract_ready(ctx, trlwe, P, coef, stride, out, count, lvl1, idx)) return rc;
-    if (int rc = use(ctx)) return rc;
-    if (count == 0) return 0;
     const size_t in_bytes = count * 2 * (size_t)ctx->p.N * 4, out_bytes = count * (size_t)P * ((size_t)(lvl1 ? ctx->p.N : ctx->p.n) + 1) * 4;
-    if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, in_bytes)) return rc;
-    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
-    if (int rc = copy_in(ctx, ctx->d_a, trlwe, in_bytes, 0)) return rc;
-    if (int rc = launch_extract(ctx, ctx->d_a, P, idx, ctx->d_c, count, lvl1, ctx->stream)) return rc;
-    return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+    return host_form(ctx, count, {staging_a(ctx), trlwe, in_bytes}, {staging_c(ctx), out, out_bytes, false}, {}, [&](const void* d_trlwe, const StagedIdx*, void* d_out) {
+        return launch_extract(ctx, d_trlwe, P, idx, d_out, count, lvl1, ctx->stream);
+    });
 }
 
 }  // namespace

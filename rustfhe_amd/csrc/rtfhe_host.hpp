@@ -1,4 +1,8 @@
-// rtfhe_host.hpp -- host-side internals shared by the translation units behind the C ABI (include/rtfhe.h):
+// rtfhe_host.hpp -- host-side internals shared by the translation units behind the C ABI (include/rtfhe.h).  Beside the declarations it holds
+// the host rules that every family follows, each in one place: handles_ready / detach / orphan_all (the lifetime rule),
+// NewHandle / handle_publish / handle_destroy (the handle owner), host_form (the host-buffer form), stream_scratch, launch_kernel and
+// launch_leveled, circuit_record.  The argument checks that need no context are not here: rtfhe_plan_kit.hpp (header only, no HIP) and the
+// host-only plan units built on it.  The units:
 //   rtfhe_context.hip        contexts, keys (load / layouts on demand / footprint), twiddle-table calls, copies, error plumbing, the handle and
 //                            device-pointer checks of the entry points
 //   rtfhe_twiddles.hip       host twiddle tables (the reference's builders restated) and the per-kernel device tables
@@ -14,9 +18,12 @@
 //   rtfhe_cmux_tree.hip      CMUX-tree table lookup: selector sets (caller-supplied TRGSW samples), one launch per tree level; TRGSW blind rotation
 //                            and the CMUX demultiplexer tree
 //   rtfhe_cmux_net.hip       CMUX netlists: decision diagrams over a selector set, levelised (rtfhe_cmux_net_plan.cpp, host only) and recorded into a HIP graph
-//   rtfhe_pack.hip           packing key switch: packing keys (signed byte limbs in operand order), lvl0 samples into TRLWE rows
+//   rtfhe_pack.hip           packing key switch: packing keys (signed byte limbs in operand order), lvl0 samples into TRLWE rows (its argument
+//                            checks: rtfhe_pack_plan in rtfhe_extract_plan.cpp, host only)
 //   rtfhe_extract.hip        TRLWE sample extraction: chosen coefficients of existing TRLWEs as lvl1 samples or, through the extract tail, lvl0 ciphertexts
 //                            (its argument checks: rtfhe_extract_plan.cpp, host only)
+//   rtfhe_trgsw_mac.hip      TRLWE x TRGSW multiply-accumulate over the selector sets of rtfhe_cmux_tree.hip (its argument checks:
+//                            rtfhe_trgsw_mac_plan.cpp, host only, the sum-of-products body it shares with rtfhe_plain_plan.cpp)
 //   rtfhe_plain.hip          exact TRLWE x plain-polynomial products: plain sets (integer polynomials as spectra), sums of up to eight products per sample
 //                            on the split-FFT exact backend's arithmetic, on every backend (its argument checks: rtfhe_plain_plan.cpp, host only)
 //   rtfhe_dense.hip          lvl0 dense layers: an integer matrix (signed bytes in i8-MFMA operand order) times a batch of TLWE rows, exact, on every
@@ -353,6 +360,74 @@ template <typename H>
 void orphan_all(std::vector<H*>& live, void (*release)(H*)) {
     for (H* h : live) { release(h); h->ctx = nullptr; }
     live.clear();
+}
+// ---- the handle owner (the rule: DESIGN.md 6.1) ----
+// A data handle that no context lists yet, `ctx` set: released (X_release, after the one hipGetLastError() that clears what made the creation
+// fail) and deleted when its *_create returns without having published it.  No *_create rolls back by hand.
+template <typename H>
+struct HandleDrop {
+    void (*release)(H*);
+    void operator()(H* h) const { (void)hipGetLastError(); release(h); delete h; }
+};
+template <typename H>
+using NewHandle = std::unique_ptr<H, HandleDrop<H>>;
+template <typename H>
+NewHandle<H> new_handle(rtfhe_ctx* ctx, void (*release)(H*)) {
+    NewHandle<H> h(new H(), HandleDrop<H>{release});
+    h->ctx = ctx;
+    return h;
+}
+// THE place a data handle is listed in its context and handed out
+template <typename H>
+int handle_publish(std::vector<H*>& live, NewHandle<H> h, H** out) {
+    live.push_back(h.get());
+    *out = h.release();
+    return 0;
+}
+// THE body of the five rtfhe_*_destroy: a handle still attached leaves its context's list and, after before(ctx) -- what has to happen while its
+// device memory still stands --, releases that memory; then it is freed
+template <typename H, typename Before>
+void handle_destroy(std::vector<H*> rtfhe_ctx::*live, H* h, void (*release)(H*), Before before) {
+    if (!h) return;
+    if (rtfhe_ctx* ctx = h->ctx) {     // still attached
+        detach(ctx->*live, h);
+        before(ctx);
+        release(h);
+    }
+    delete h;
+}
+template <typename H>
+void handle_destroy(std::vector<H*> rtfhe_ctx::*live, H* h, void (*release)(H*)) { handle_destroy(live, h, release, [](rtfhe_ctx*) {}); }
+
+// ---- the host-buffer form (the rule: DESIGN.md 6.1) ----
+// A staging buffer of the context with its capacity and the pinned slot its copies go through; a call says which carries what.
+struct Staging { void** buf; size_t* cap; int slot; };
+inline Staging staging_a(rtfhe_ctx* ctx) { return {&ctx->d_a, &ctx->cap_a, 0}; }
+inline Staging staging_b(rtfhe_ctx* ctx) { return {&ctx->d_b, &ctx->cap_b, 1}; }
+inline Staging staging_c(rtfhe_ctx* ctx) { return {&ctx->d_c, &ctx->cap_c, 2}; }
+struct HostRows { Staging via; const void* rows; size_t bytes; };                     // the caller's input rows (rows null: the call has none)
+struct HostResult { Staging via; void* out; size_t bytes; bool accumulate; };         // the caller's result; accumulate: it goes up first, through pinned slot 1
+struct HostIdx { Staging via; size_t words; const int32_t* first; const int32_t* second; };      // one stage_idx request
+// THE host-pointer form of a leveled call, behind its argument checks: the device made current; count = 0 returns before anything is allocated;
+// the staging buffers grown; the index arrays, the rows and -- when accumulating -- the caller's result copied up; launch(d_rows, d_idx, d_out)
+// on ctx->stream (d_idx[i]: the device addresses of request i); the result copied down, synchronous on return.
+template <typename Launch>
+int host_form(rtfhe_ctx* ctx, size_t count, const HostRows& in, const HostResult& res, std::initializer_list<HostIdx> idx, Launch launch) {
+    if (int rc = use(ctx)) return rc;
+    if (count == 0) return 0;
+    if (in.rows)
+        if (int rc = ensure(ctx, in.via.buf, in.via.cap, in.bytes)) return rc;
+    if (int rc = ensure(ctx, res.via.buf, res.via.cap, res.bytes)) return rc;
+    StagedIdx d_idx[2];
+    size_t i = 0;
+    for (const HostIdx& r : idx)
+        if (int rc = stage_idx(ctx, r.via.buf, r.via.cap, r.words, r.first, r.second, d_idx[i++])) return rc;
+    if (in.rows)
+        if (int rc = copy_in(ctx, *in.via.buf, in.rows, in.bytes, in.via.slot)) return rc;
+    if (res.accumulate)
+        if (int rc = copy_in(ctx, *res.via.buf, res.out, res.bytes, 1)) return rc;
+    if (int rc = launch(in.rows ? (const void*)*in.via.buf : nullptr, d_idx, *res.via.buf)) return rc;
+    return copy_out(ctx, res.out, *res.via.buf, res.bytes, res.via.slot);
 }
 // what every entry point over a selector set checks first (rtfhe_cmux_tree.hip): the handles (lut only with_table), the caller's other pointers
 // (args_ok), the mirror backend -- who: "the CMUX tree runs", for the message

@@ -24,7 +24,7 @@ template <typename Fill>
 int lut_upload(rtfhe_ctx* ctx, int32_t n_lut, bool encrypted, rtfhe_lut** out, Fill fill) {
     *out = nullptr;
     const size_t bytes = (size_t)n_lut * ctx->p.N * (encrypted ? 2 : 1) * 4;
-    rtfhe_lut* lut = new rtfhe_lut();
+    NewHandle<rtfhe_lut> lut = new_handle(ctx, lut_release);      // (lut_release frees as many copies as d_tv lists)
     lut->n_lut = n_lut;
     lut->encrypted = encrypted;
     const int entries = 1 + (int)ctx->peers.size();
@@ -39,20 +39,7 @@ int lut_upload(rtfhe_ctx* ctx, int32_t n_lut, bool encrypted, rtfhe_lut** out, F
         if (rc && c != ctx) rc = fail(ctx, rc, "device " + std::to_string(c->device) + ": " + c->err);
     }
     (void)hipSetDevice(ctx->device);
-    if (rc) {
-        (void)hipGetLastError();
-        for (size_t d = 0; d < lut->d_tv.size(); d++) {
-            (void)hipSetDevice(d ? ctx->peers[d - 1]->device : ctx->device);
-            (void)hipFree(lut->d_tv[d]);
-        }
-        (void)hipSetDevice(ctx->device);
-        delete lut;
-        return rc;
-    }
-    lut->ctx = ctx;
-    ctx->luts.push_back(lut);
-    *out = lut;
-    return 0;
+    return rc ? rc : handle_publish(ctx->luts, std::move(lut), out);
 }
 
 // What the three row calls check before anything is queued, in this order: the handle, the caller's pointer, an encrypted table, a
@@ -114,14 +101,7 @@ int rtfhe_lut_create_encrypted_seeded(rtfhe_ctx* ctx, const uint32_t* seed, uint
     });
 }
 
-void rtfhe_lut_destroy(rtfhe_lut* lut) {
-    if (!lut) return;
-    if (rtfhe_ctx* ctx = lut->ctx) {     // still attached
-        detach(ctx->luts, lut);
-        lut_release(lut);
-    }
-    delete lut;
-}
+void rtfhe_lut_destroy(rtfhe_lut* lut) { handle_destroy(&rtfhe_ctx::luts, lut, lut_release); }
 
 int rtfhe_lut_update_dev(rtfhe_lut* lut, const void* d_trlwe, int32_t first, int32_t n, void* stream) {
     rtfhe_ctx* ctx = nullptr;

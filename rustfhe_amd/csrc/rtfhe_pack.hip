@@ -1,9 +1,10 @@
 // rtfhe_pack.hip -- the packing key switch (include/rtfhe.h: rtfhe_packing_key_create, rtfhe_pack_batch[_dev]): packing keys as signed byte
-// limbs in operand order (k_pkmat_build), the argument checks, the stream's buffer of key-switched samples and the rules around stream
+// limbs in operand order (k_pkmat_build), the stream's buffer of key-switched samples and the rules around stream
 // captures, k_pack_ks_mm then k_pack_combine per call.  (Its rows go into an encrypted table through rtfhe_lut_update_dev, rtfhe_lut.hip.)
 // Nothing here multiplies polynomials: the calls work on every backend and never read the bootstrapping key.
 #include "rtfhe_host.hpp"
 
+#include "rtfhe_extract_plan.h"
 #include "rtfhe_kernels_pack.hpp"
 
 using namespace rtfhe;
@@ -11,24 +12,16 @@ using namespace rtfhe_host;
 
 namespace {
 
-// what both pack entries check before anything is allocated or launched; fills shift[P] with the positions (pos NULL: p * rep)
+// what both pack entries check before anything is allocated or launched: the handle, then the arguments themselves (rtfhe_pack_plan, host only);
+// fills shift[P] with the positions (pos NULL: p * rep)
 int pack_ready(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const void* in, int32_t P, const int32_t* pos, int32_t rep, const void* out, size_t count,
                std::vector<int32_t>& shift) {
     if (!ctx) return fail(nullptr, RTFHE_ERR_INVALID, "null context");
     if (int rc = handles_ready(ctx, {ref(pk)})) return rc;
-    if (!in || !out) return fail(ctx, RTFHE_ERR_INVALID, "null argument");
     const int N = ctx->p.N;
-    if (P < 1 || P > N) return fail(ctx, RTFHE_ERR_INVALID, "P = " + std::to_string(P) + " is outside [1, " + std::to_string(N) + "]");
-    if (rep < 1 || rep > N) return fail(ctx, RTFHE_ERR_INVALID, "rep = " + std::to_string(rep) + " is outside [1, " + std::to_string(N) + "]");
-    if (count > (size_t)0x7fffffff / (size_t)P) return fail(ctx, RTFHE_ERR_INVALID, "count * P too large");
-    shift.resize((size_t)P);
-    for (int p = 0; p < P; p++) {
-        const long long v = pos ? (long long)pos[p] : (long long)p * rep;
-        if (v < 0 || v >= 2 * N)
-            return fail(ctx, RTFHE_ERR_INVALID, "sample " + std::to_string(p) + ": pos = " + std::to_string(v) + " is outside [0, " + std::to_string(2 * N) + ")" +
-                                                (pos ? "" : " (pos NULL: p * rep)"));
-        shift[(size_t)p] = (int32_t)v;
-    }
+    shift.assign(P >= 1 && P <= N ? (size_t)P : 1, 0);
+    char err[256];
+    if (int rc = rtfhe_pack_plan(N, P, pos, rep, count, in, out, shift.data(), err, sizeof err)) return fail(ctx, rc, err);
     return 0;
 }
 
@@ -88,8 +81,7 @@ static int packing_key_create_filled(rtfhe_ctx* ctx, bool args_ok, rtfhe_packing
         return fail(ctx, RTFHE_ERR_INVALID, "rtfhe_packing_key_create: the packing key switch needs ks_t = 8 and ks_basebit = 2");
     if (int rc = use(ctx)) return rc;
     const size_t n = (size_t)ctx->p.n, N = (size_t)ctx->p.N, rows = n * 8 * 3, raw_bytes = rows * 2 * N * 4;
-    rtfhe_packing_key* k = new rtfhe_packing_key();
-    k->ctx = ctx;
+    NewHandle<rtfhe_packing_key> k = new_handle(ctx, packing_key_release);
     k->n16 = (int32_t)((n + 15) / 16 * 16);
     k->colgroups = (int32_t)(2 * N / 16);
     const size_t kmat_v4 = (size_t)k->colgroups * (k->n16 / 2) * 4 * 64;
@@ -104,15 +96,7 @@ static int packing_key_create_filled(rtfhe_ctx* ctx, bool args_ok, rtfhe_packing
         if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_packing_key_create: k_pkmat_build");
     }
     if (d_raw) (void)hipFree(d_raw);      // the operand form is all the calls read
-    if (rc) {
-        (void)hipGetLastError();
-        packing_key_release(k);
-        delete k;
-        return rc;
-    }
-    ctx->pack_keys.push_back(k);
-    *out = k;
-    return 0;
+    return rc ? rc : handle_publish(ctx->pack_keys, std::move(k), out);
 }
 
 extern "C" {
@@ -134,14 +118,10 @@ int rtfhe_packing_key_create_seeded(rtfhe_ctx* ctx, const uint32_t* seed, uint64
 }
 
 void rtfhe_packing_key_destroy(rtfhe_packing_key* k) {
-    if (!k) return;
-    if (rtfhe_ctx* ctx = k->ctx) {     // still attached
-        detach(ctx->pack_keys, k);
+    handle_destroy(&rtfhe_ctx::pack_keys, k, packing_key_release, [](rtfhe_ctx* ctx) {
         (void)hipSetDevice(ctx->device);
         (void)hipDeviceSynchronize();      // a pack in flight may still read the matrix
-        packing_key_release(k);
-    }
-    delete k;
+    });
 }
 
 int rtfhe_pack_batch_dev(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const void* d_tlwe, int32_t P, const int32_t* pos, int32_t rep, void* d_out, size_t count,
@@ -157,14 +137,10 @@ int rtfhe_pack_batch_dev(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const void
 int rtfhe_pack_batch(rtfhe_ctx* ctx, const rtfhe_packing_key* pk, const uint32_t* tlwe, int32_t P, const int32_t* pos, int32_t rep, uint32_t* out, size_t count) {
     std::vector<int32_t> shift;
     if (int rc = pack_ready(ctx, pk, tlwe, P, pos, rep, out, count, shift)) return rc;
-    if (int rc = use(ctx)) return rc;
-    if (count == 0) return 0;
     const size_t in_bytes = count * (size_t)P * ((size_t)ctx->p.n + 1) * 4, out_bytes = count * 2 * (size_t)ctx->p.N * 4;
-    if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, in_bytes)) return rc;
-    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
-    if (int rc = copy_in(ctx, ctx->d_a, tlwe, in_bytes, 0)) return rc;
-    if (int rc = launch_pack(ctx, pk, ctx->d_a, P, shift, rep, ctx->d_c, count, ctx->stream)) return rc;
-    return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+    return host_form(ctx, count, {staging_a(ctx), tlwe, in_bytes}, {staging_c(ctx), out, out_bytes, false}, {}, [&](const void* d_tlwe, const StagedIdx*, void* d_out) {
+        return launch_pack(ctx, pk, d_tlwe, P, shift, rep, d_out, count, ctx->stream);
+    });
 }
 
 }  // extern "C"

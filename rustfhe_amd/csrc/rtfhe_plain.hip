@@ -88,8 +88,8 @@ int rtfhe_plain_create(rtfhe_ctx* ctx, const int32_t* w, int32_t n_w, rtfhe_plai
     if (int rc = xfft_table_ensure(ctx)) return rc;
     if (int rc = prime_plain(ctx)) return rc;
     const size_t words = (size_t)n_w * ctx->p.N;
-    rtfhe_plain* t = new rtfhe_plain();
-    t->n_w = n_w; t->wmax = wmax; t->ctx = ctx;
+    NewHandle<rtfhe_plain> t = new_handle(ctx, plain_release);
+    t->n_w = n_w; t->wmax = wmax;
     int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, words * 4);
     if (!rc && hipMalloc((void**)&t->d_spec, words / 2 * sizeof(cplx)) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_plain_create: hipMalloc");
     if (!rc) rc = copy_in(ctx, ctx->d_a, w, words * 4, 0);      // on the stream of the build below, which is waited for
@@ -98,43 +98,21 @@ int rtfhe_plain_create(rtfhe_ctx* ctx, const int32_t* w, int32_t n_w, rtfhe_plai
         rc = ctx->logn == 11 ? launch_build<11>(ctx, a) : launch_build<10>(ctx, a);
     }
     if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RTFHE_ERR_HIP, "rtfhe_plain_create: hipStreamSynchronize");
-    if (rc) {
-        (void)hipGetLastError();
-        plain_release(t);
-        delete t;
-        return rc;
-    }
-    ctx->plains.push_back(t);
-    *out = t;
-    return 0;
+    return rc ? rc : handle_publish(ctx->plains, std::move(t), out);
 }
 
-void rtfhe_plain_destroy(rtfhe_plain* w) {
-    if (!w) return;
-    if (rtfhe_ctx* ctx = w->ctx) {     // still attached
-        detach(ctx->plains, w);
-        plain_release(w);
-    }
-    delete w;
-}
+void rtfhe_plain_destroy(rtfhe_plain* w) { handle_destroy(&rtfhe_ctx::plains, w, plain_release); }
 
 // host buffers: the rows ride in d_a, the index arrays in d_b (w_idx, then x_idx), the result comes back through d_c (which takes the caller's out
 // first when accumulating)
 int rtfhe_trlwe_mul_plain_batch(rtfhe_ctx* ctx, const rtfhe_plain* w, const int32_t* w_idx, const uint32_t* x, int32_t n_x, const int32_t* x_idx, int32_t K,
                                 int32_t accumulate, uint32_t* out, size_t count) {
     if (int rc = plain_ready(ctx, w, w_idx != nullptr, w_idx, x, n_x, x_idx != nullptr, x_idx, K, out, count)) return rc;
-    if (int rc = use(ctx)) return rc;
-    if (count == 0) return 0;
-    const size_t row = 2 * (size_t)ctx->p.N * 4, in_bytes = (size_t)n_x * row, out_bytes = count * row;
-    if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, in_bytes)) return rc;
-    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
-    StagedIdx idx;
-    if (int rc = stage_idx(ctx, &ctx->d_b, &ctx->cap_b, count * (size_t)K, w_idx, x_idx, idx)) return rc;
-    if (int rc = copy_in(ctx, ctx->d_a, x, in_bytes, 0)) return rc;
-    if (accumulate)
-        if (int rc = copy_in(ctx, ctx->d_c, out, out_bytes, 1)) return rc;
-    if (int rc = launch_mul_plain(ctx, w, idx.first, ctx->d_a, n_x, idx.second, K, accumulate, ctx->d_c, count, ctx->stream)) return rc;
-    return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+    const size_t row = 2 * (size_t)ctx->p.N * 4;
+    return host_form(ctx, count, {staging_a(ctx), x, (size_t)n_x * row}, {staging_c(ctx), out, count * row, accumulate != 0},
+                     {{staging_b(ctx), count * (size_t)K, w_idx, x_idx}}, [&](const void* d_x, const StagedIdx* idx, void* d_out) {
+        return launch_mul_plain(ctx, w, idx[0].first, d_x, n_x, idx[0].second, K, accumulate, d_out, count, ctx->stream);
+    });
 }
 
 int rtfhe_trlwe_mul_plain_batch_dev(rtfhe_ctx* ctx, const rtfhe_plain* w, const void* d_w_idx, const void* d_x, int32_t n_x, const void* d_x_idx, int32_t K,

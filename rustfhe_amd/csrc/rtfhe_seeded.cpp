@@ -10,21 +10,14 @@
 // rtfhe_tlwe_seeded_plan.
 #include "rtfhe_seeded_plan.h"
 
-#include <cstdio>
-#include <string>
-
 #include "rtfhe_encrypt.hpp"
+#include "rtfhe_plan_kit.hpp"
 
 namespace {
 
 using namespace rtfhe_encrypt;
+using namespace rtfhe_plan;
 
-int refuse(char* err, size_t err_len, const std::string& msg) {
-    if (err && err_len) std::snprintf(err, err_len, "%s", msg.c_str());
-    return RTFHE_ERR_INVALID;
-}
-
-std::string num(long long v) { return std::to_string(v); }
 std::string row_range(uint64_t first_row, size_t rows) {
     return "rows [" + std::to_string(first_row) + ", " + std::to_string(first_row) + " + " + std::to_string(rows) + ") pass 2^64";
 }
@@ -64,38 +57,37 @@ extern "C" {
 
 int rtfhe_seeded_plan(int32_t what, int32_t N, const void* seed, uint64_t first_row, const void* b, int32_t group, const void* out, size_t rows, char* err,
                       size_t err_len) {
-    if (err && err_len) err[0] = 0;
+    begin(err, err_len);
     const bool upload = what == RTFHE_SEEDED_UPLOAD;
     if (!seed || !b || (!upload && !out)) return refuse(err, err_len, "null argument");
     if (!ring_ok(N)) return refuse(err, err_len, "N = " + num(N) + " is not a power of two in [16, 2048]");
     if (group < 1) return refuse(err, err_len, "group = " + num(group) + " is below 1");
     if (rows % (size_t)group) return refuse(err, err_len, "rows = " + std::to_string(rows) + " is not a multiple of group = " + num(group));
     if (!rows_ok(first_row, rows)) return refuse(err, err_len, row_range(first_row, rows));
-    if (what != RTFHE_SEEDED_HOST && rows > (size_t)0x7fffffff / (size_t)(N / 16)) return refuse(err, err_len, "rows * N / 16 too large (it must be below 2^31)");
+    if (what != RTFHE_SEEDED_HOST && !count_fits(rows, (size_t)(N / 16))) return refuse(err, err_len, "rows * N / 16 too large (it must be below 2^31)");
     if (upload) return 0;
     const uintptr_t i0 = (uintptr_t)b, o0 = (uintptr_t)out;
     if (what == RTFHE_SEEDED_DEVICE && ((i0 | o0) & 15)) return refuse(err, err_len, "d_b and d_out must be 16-byte aligned");
-    const size_t in_bytes = rows * (size_t)N * 4, out_bytes = 2 * in_bytes;
-    if (i0 < o0 + out_bytes && o0 < i0 + in_bytes) return refuse(err, err_len, "the output overlaps the b rows");
+    const size_t in_bytes = rows * (size_t)N * 4;
+    if (rows_overlap(b, in_bytes, out, 2 * in_bytes)) return refuse(err, err_len, "the output overlaps the b rows");
     return 0;
 }
 
 int rtfhe_tlwe_seeded_plan(int32_t what, int32_t n, const void* seed, uint64_t first_row, const void* b, const void* out, size_t rows, char* err,
                            size_t err_len) {
-    if (err && err_len) err[0] = 0;
+    begin(err, err_len);
     const bool upload = what == RTFHE_TLWE_SEEDED_UPLOAD, host = what == RTFHE_TLWE_SEEDED_HOST;
     if (!seed || !b || (!upload && !out)) return refuse(err, err_len, "null argument");
     if (n < 1 || (!host && n > 767)) return refuse(err, err_len, "n = " + num(n) + (host ? " is below 1" : " is outside [1, 767]"));
     if (rows < 1) return refuse(err, err_len, "rows = 0: a seeded lvl0 object has at least one row");
     if (!rows_ok(first_row, rows)) return refuse(err, err_len, row_range(first_row, rows));
     const size_t w = (size_t)n + 1, nb = ((size_t)n + 15) / 16;
-    if (!host && rows > (size_t)0x7fffffff / nb) return refuse(err, err_len, "rows * ceil(n / 16) too large (it must be below 2^31)");
+    if (!host && !count_fits(rows, nb)) return refuse(err, err_len, "rows * ceil(n / 16) too large (it must be below 2^31)");
     if (host && rows > ((size_t)-1 / 4) / w) return refuse(err, err_len, "rows * (n + 1) words too large");
     if (upload) return 0;
     const uintptr_t i0 = (uintptr_t)b, o0 = (uintptr_t)out;
     if (what == RTFHE_TLWE_SEEDED_DEVICE && ((i0 | o0) & 3)) return refuse(err, err_len, "d_b and d_out must be 4-byte aligned");
-    const size_t in_bytes = rows * 4, out_bytes = rows * w * 4;
-    if (i0 < o0 + out_bytes && o0 < i0 + in_bytes) return refuse(err, err_len, "the output overlaps the b words");
+    if (rows_overlap(b, rows * 4, out, rows * w * 4)) return refuse(err, err_len, "the output overlaps the b words");
     return 0;
 }
 

@@ -54,18 +54,11 @@ extern "C" {
 int rtfhe_trlwe_mul_trgsw_batch(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* s_idx, const uint32_t* x, int32_t n_x, const int32_t* x_idx, int32_t K,
                                 int accumulate, uint32_t* out, size_t count) {
     if (int rc = mac_ready(ctx, sel, s_idx != nullptr, s_idx, x, n_x, x_idx != nullptr, x_idx, K, out, count)) return rc;
-    if (int rc = use(ctx)) return rc;
-    if (count == 0) return 0;
-    const size_t row = 2 * (size_t)ctx->p.N * 4, in_bytes = (size_t)n_x * row, out_bytes = count * row;
-    if (int rc = ensure(ctx, &ctx->d_a, &ctx->cap_a, in_bytes)) return rc;
-    if (int rc = ensure(ctx, &ctx->d_c, &ctx->cap_c, out_bytes)) return rc;
-    StagedIdx idx;
-    if (int rc = stage_idx(ctx, &ctx->d_b, &ctx->cap_b, count * (size_t)K, s_idx, x_idx, idx)) return rc;
-    if (int rc = copy_in(ctx, ctx->d_a, x, in_bytes, 0)) return rc;
-    if (accumulate)
-        if (int rc = copy_in(ctx, ctx->d_c, out, out_bytes, 1)) return rc;
-    if (int rc = launch_mac(ctx, sel, idx.first, ctx->d_a, n_x, idx.second, K, accumulate, ctx->d_c, count, ctx->stream)) return rc;
-    return copy_out(ctx, out, ctx->d_c, out_bytes, 2);
+    const size_t row = 2 * (size_t)ctx->p.N * 4;
+    return host_form(ctx, count, {staging_a(ctx), x, (size_t)n_x * row}, {staging_c(ctx), out, count * row, accumulate != 0},
+                     {{staging_b(ctx), count * (size_t)K, s_idx, x_idx}}, [&](const void* d_x, const StagedIdx* idx, void* d_out) {
+        return launch_mac(ctx, sel, idx[0].first, d_x, n_x, idx[0].second, K, accumulate, d_out, count, ctx->stream);
+    });
 }
 
 int rtfhe_trlwe_mul_trgsw_batch_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_s_idx, const void* d_x, int32_t n_x, const void* d_x_idx, int32_t K,

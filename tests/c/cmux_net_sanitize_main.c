@@ -2,13 +2,9 @@
  * description, and its levelisation) under AddressSanitizer + UndefinedBehaviorSanitizer.  No device is needed: this code runs before any HIP
  * call.  The output arrays are allocated at exactly the sizes the header promises, so that a write past them is caught. */
 #include <limits.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "rtfhe.h"
+#include "sanitize_kit.h"
 #include "rtfhe_cmux_net_plan.h"
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "CHECK failed: %s (line %d)\n", #c, __LINE__); exit(1); } } while (0)
 
 typedef struct { int32_t *order, *level_off, n_levels, leaf_span[2]; size_t node_bytes; char err[200]; } plan_out;
 

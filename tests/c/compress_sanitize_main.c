@@ -3,14 +3,9 @@
  * the coefficient list comes from rtfhe_extract_plan.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer.  No device is needed.  Every
  * buffer the twins read or write is allocated at exactly the size the header promises, so that an access one word past a ragged row is caught;
  * the buffers of the refused calls are addresses only and are never dereferenced. */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "rtfhe.h"
+#include "sanitize_kit.h"
 #include "rtfhe_compress_plan.h"
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "CHECK failed: %s (line %d)\n", #c, __LINE__); exit(1); } } while (0)
 
 static char err[200];
 static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
@@ -109,7 +104,6 @@ int main(void) {
           rtfhe_compressed_words(2048, 12) == 768 && rtfhe_compressed_words(0, 12) == 0);
     /* the checks: addresses only */
     const uintptr_t base = 0x10000000;
-#define AT(a) ((const void *)(uintptr_t)(a))
     const void *in = AT(base), *out = AT(0x40000000);
     for (int32_t dir = RTFHE_COMPRESS_PACK; dir <= RTFHE_COMPRESS_EXPAND; dir++) {
         memset(err, 'x', sizeof err);

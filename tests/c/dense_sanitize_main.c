@@ -2,16 +2,9 @@
  * that needs no context, the correction words, the launch rule) under AddressSanitizer + UndefinedBehaviorSanitizer.  No device is needed: this
  * code runs before any HIP call.  The matrices and the correction words are allocated at exactly the sizes the header promises, so that an
  * access past them is caught; the two buffers are addresses only and are never dereferenced. */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "rtfhe.h"
+#include "sanitize_kit.h"
 #include "rtfhe_dense_plan.h"
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "CHECK failed: %s (line %d)\n", #c, __LINE__); exit(1); } } while (0)
-
-static char err[200];
 
 static int plan(int32_t n, int32_t O, int32_t I, size_t count, const void *x, const void *out) {
     memset(err, 'x', sizeof err);
@@ -38,7 +31,6 @@ static int weights(const int32_t *W, int32_t O, int32_t I, uint32_t *corr) {
 
 int main(void) {
     const uintptr_t base = 0x10000000;                                              /* addresses only: integers, so that no pointer arithmetic leaves an object */
-#define AT(a) ((const void *)(uintptr_t)(a))
     const void *x = AT(base), *out = AT(0x4000000000ull);
 
     {   /* correction words: 128 * 0x01010101 * the row sum, both signs, and the widest row */

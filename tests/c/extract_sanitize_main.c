@@ -2,16 +2,9 @@
  * every argument check that needs no context) under AddressSanitizer + UndefinedBehaviorSanitizer.  No device is needed: this code runs before
  * any HIP call.  The coefficient array is allocated at exactly the size the header promises, so that a write past it is caught; the two buffers
  * are addresses only and are never dereferenced. */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "rtfhe.h"
+#include "sanitize_kit.h"
 #include "rtfhe_extract_plan.h"
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "CHECK failed: %s (line %d)\n", #c, __LINE__); exit(1); } } while (0)
-
-static char err[160];
 
 /* idx has room for P entries when 1 <= P <= N and for one entry otherwise, as rtfhe_extract.hip sizes it */
 static int plan(int32_t N, int32_t P, const int32_t *coef, int32_t stride, size_t count, const void *in, const void *out, size_t out_words, int32_t **idx) {
@@ -31,7 +24,6 @@ static void refused(int32_t N, int32_t P, const int32_t *coef, int32_t stride, s
 int main(void) {
     enum { N = 1024, n1 = 636 };
     const uintptr_t base = 0x10000000;                                              /* addresses only: integers, so that no pointer arithmetic leaves an object */
-#define AT(a) ((const void *)(uintptr_t)(a))
     const void *in = AT(base), *out = AT(0x40000000);                               /* far apart: 3 rows are 24 KiB */
     int32_t *idx;
     {   /* a list with duplicates and both ends */

@@ -1,12 +1,8 @@
 /* Walks the product's host-only sources (key generation / encryption, wire format: rustfhe_amd/csrc/rtfhe_keygen.cpp, rtfhe_wire.cpp)
  * under AddressSanitizer + UndefinedBehaviorSanitizer on a small parameter set: secure and deterministic key generation, encrypt ->
  * decrypt, key file and ciphertext file round trips, a truncated and a corrupted file. */
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "rtfhe.h"
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "CHECK failed: %s (line %d)\n", #c, __LINE__); exit(1); } } while (0)
+#include "sanitize_kit.h"
 
 int main(int argc, char **argv) {
     const char *dir = argc > 1 ? argv[1] : "/tmp";

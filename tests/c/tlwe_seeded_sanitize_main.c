@@ -3,14 +3,9 @@
  * UndefinedBehaviorSanitizer.  No device is needed: nothing in that unit makes a HIP call.  Every buffer is heap-allocated at exactly the size
  * the header promises, so that an access past it is caught -- a row of n words whose last ChaCha20 block is partial above all; the plan's buffers
  * are addresses only and are never dereferenced. */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "rtfhe.h"
+#include "sanitize_kit.h"
 #include "rtfhe_seeded_plan.h"
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "CHECK failed: %s (line %d)\n", #c, __LINE__); exit(1); } } while (0)
 
 static char err[200];
 static const uint32_t seed[8] = {0x03020100u, 0x07060504u, 0x0b0a0908u, 0x0f0e0d0cu, 0x13121110u, 0x17161514u, 0x1b1a1918u, 0x1f1e1d1cu};
@@ -43,7 +38,6 @@ static int32_t dist(uint32_t x, uint32_t y) { int32_t d = (int32_t)(x - y); retu
 
 int main(void) {
     const uint64_t TOP = ~(uint64_t)0;                                              /* 2^64 - 1 */
-#define AT(a) ((const void *)(uintptr_t)(a))
     const void *b = AT(0x10000000), *out = AT(0x40000000);
     const int HOST = RTFHE_TLWE_SEEDED_HOST, DEV = RTFHE_TLWE_SEEDED_DEVICE, UP = RTFHE_TLWE_SEEDED_UPLOAD;
 

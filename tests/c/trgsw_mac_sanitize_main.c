@@ -2,16 +2,9 @@
  * context) under AddressSanitizer + UndefinedBehaviorSanitizer.  No device is needed: this code runs before any HIP call.  The index arrays are
  * allocated at exactly the sizes the header promises, so that a read past them is caught; the two buffers are addresses only and are never
  * dereferenced. */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include "rtfhe.h"
+#include "sanitize_kit.h"
 #include "rtfhe_trgsw_mac_plan.h"
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "CHECK failed: %s (line %d)\n", #c, __LINE__); exit(1); } } while (0)
-
-static char err[200];
 
 static int plan(int32_t N, int32_t n_sel, int32_t K, int32_t sg, const int32_t *s_idx, int32_t n_x, int32_t xg, const int32_t *x_idx, size_t count,
                 const void *x, const void *out) {
@@ -36,7 +29,6 @@ static int32_t *indices(size_t count, int K, int32_t fill) {
 int main(void) {
     enum { N = 1024 };
     const uintptr_t base = 0x10000000;                                              /* addresses only: integers, so that no pointer arithmetic leaves an object */
-#define AT(a) ((const void *)(uintptr_t)(a))
     const void *x = AT(base), *out = AT(0x40000000);                                /* far apart: a row is 8 KiB */
 
     /* accepted: K at both ends; NULL indices at their exact needs; count = 0; the largest count * K */

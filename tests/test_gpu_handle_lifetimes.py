@@ -95,3 +95,42 @@ def test_foreign_orphaned_null_and_early_closed_handles(kind):
     finally:
         other.close()
         mine.close()
+
+
+def test_a_refused_create_leaves_no_handle_and_the_context_goes_on():
+    """Each of the five data handle types (the four above and rtfhe_dense), through the C entry points themselves: a create that its argument checks
+    refuse returns ERR_INVALID and leaves *out null; a valid create and destroy on the same context then work, and the context destroys cleanly.
+    n = 8, N = 1024: one table row, one selector, a packing key of n * 8 * 3 rows (1.5 MB), one plain polynomial, a 1 x 1 matrix."""
+    import ctypes as C
+    import rustfhe_amd as R
+    p = R.Params(n=8, N=N)
+    eng = R.Engine(p, 0)
+    try:
+        L, ctx = eng.L, eng.h
+        rng = np.random.default_rng(31)
+        words = lambda *shape: rng.integers(0, 1 << 32, shape, dtype=np.uint64).astype(np.uint32)
+        tv, trgsw, pk = words(1, N), words(1, 2, 2 * p.l, N), words(*np.atleast_1d(R.engine.packing_key_words(p)))
+        assert pk.size == p.n * 8 * 3 * 2 * N
+        poly, one, wide = np.zeros((1, N), np.int32), np.ones((1, 1), np.int32), np.full((1, 1), 128, np.int32)
+        poly[0, :3] = (1, -2, 3)
+        ptr = lambda a: a.ctypes.data
+        # (create, destroy, [(arguments its checks refuse, a word of the message)], valid arguments)
+        kinds = [
+            (L.rtfhe_lut_create, L.rtfhe_lut_destroy, [((ptr(tv), 0), "n_lut < 1"), ((None, 1), "null argument")], (ptr(tv), 1)),
+            (L.rtfhe_trgsw_create, L.rtfhe_trgsw_destroy, [((ptr(trgsw), 0), "n_sel < 1"), ((ptr(trgsw), 1 << 28), "n_sel too large")], (ptr(trgsw), 1)),
+            (L.rtfhe_packing_key_create, L.rtfhe_packing_key_destroy, [((None,), "null argument")], (ptr(pk),)),
+            (L.rtfhe_plain_create, L.rtfhe_plain_destroy, [((ptr(poly), 0), "n_w = 0"), ((None, 1), "null argument")], (ptr(poly), 1)),
+            (L.rtfhe_dense_create, L.rtfhe_dense_destroy, [((ptr(one), 0, 1), "O = 0"), ((ptr(wide), 1, 1), "W[0][0] = 128")], (ptr(one), 1, 1)),
+        ]
+        for create, destroy, refusals, valid in kinds:
+            for args, word in refusals:
+                h = C.c_void_p()
+                _refused(R, eng, create(ctx, *args, C.byref(h)), R._ffi.ERR_INVALID, word)
+                assert h.value is None, (create.__name__, args)
+            h = C.c_void_p()
+            eng._ck(create(ctx, *valid, C.byref(h)))
+            assert h.value
+            destroy(h)
+        eng.sync()
+    finally:
+        eng.close()

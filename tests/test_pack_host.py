@@ -91,3 +91,59 @@ def test_noise_through_the_oracle(real, case):
     ph = w.R.trlwe_phase(w.rp, w.key1, out)
     if case == "P1024_rep1":
         assert np.array_equal(ph[0] >> 31, w.mu >> 31)
+
+
+def _pack_plan(N, P, pos, rep, count, tlwe=0x10000000, out=0x40000000):
+    """(rc, message, shift) of rtfhe_pack_plan (rustfhe_amd/csrc/rtfhe_extract_plan.cpp) through ctypes; the two buffers are addresses only"""
+    import ctypes as C
+    import rustfhe_amd as R
+    f = R.load().rtfhe_pack_plan
+    f.restype = C.c_int
+    f.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    pos = None if pos is None else np.ascontiguousarray(pos, np.int32)
+    shift = np.full(P if 1 <= P <= N else 1, -7, np.int32)
+    err = C.create_string_buffer(256)
+    rc = f(N, P, None if pos is None else pos.ctypes.data, rep, count, tlwe, out, shift.ctypes.data, err, len(err))
+    return rc, err.value.decode(), shift
+
+
+def test_the_pack_plan_fills_the_positions():
+    import rustfhe_amd as R
+    rc, msg, shift = _pack_plan(1024, 1024, None, 2, 3)
+    assert (rc, msg) == (0, "") and np.array_equal(shift, 2 * np.arange(1024))
+    pos, rep = R.lut_pack_layout(1024, 2)
+    rc, msg, shift = _pack_plan(1024, 4, pos, rep, 1)
+    assert (rc, msg) == (0, "") and np.array_equal(shift, pos)
+    assert _pack_plan(2048, 2048, None, 2, 0)[0] == 0 and _pack_plan(1024, 1, None, 1024, (1 << 31) - 1)[0] == 0
+    assert _pack_plan(1024, 1, None, 1, 1, out=0x10000000)[0] == 0          # the buffers' addresses are not compared
+
+
+@pytest.mark.parametrize("args,message", [
+    ((1024, 0, None, 1, 1), "P = 0 is outside [1, 1024]"),
+    ((1024, 1025, None, 1, 1), "P = 1025 is outside [1, 1024]"),
+    ((1024, 1, None, 0, 1), "rep = 0 is outside [1, 1024]"),
+    ((2048, 1, None, 2049, 1), "rep = 2049 is outside [1, 2048]"),
+    ((1024, 1, None, 1, 1 << 31), "count * P too large"),
+    ((1024, 3, None, 1, (1 << 31) // 3 + 1), "count * P too large"),
+    ((1024, 3, [0, -1, 5], 1, 1), "sample 1: pos = -1 is outside [0, 2048)"),
+    ((1024, 3, [0, 2047, 2048], 1, 1), "sample 2: pos = 2048 is outside [0, 2048)"),
+    ((16, 3, None, 16, 1), "sample 2: pos = 32 is outside [0, 32) (pos NULL: p * rep)"),
+    ((1024, 1, None, 1, 1, 0), "null argument"),
+    ((1024, 1, None, 1, 1, 0x10000000, 0), "null argument"),
+])
+def test_the_pack_plan_refuses_with_the_entry_points_messages(args, message):
+    """the whole message: what rtfhe_pack_batch[_dev] reported before the checks moved into the plan"""
+    import rustfhe_amd as R
+    rc, msg, shift = _pack_plan(*args)
+    assert rc == R._ffi.ERR_INVALID and msg == message
+    if not message.startswith("sample"):
+        assert (shift == -7).all(), "nothing is written on a refusal that comes before the list"
+
+
+def test_the_pack_plan_needs_room_for_the_positions():
+    import rustfhe_amd as R
+    import ctypes as C
+    assert _pack_plan(1024, 1, None, 1, 1)[0] == 0          # (sets the argument types)
+    f = R.load().rtfhe_pack_plan
+    err = C.create_string_buffer(64)
+    assert f(1024, 1, None, 1, 1, 0x10000000, 0x40000000, None, err, len(err)) == R._ffi.ERR_INVALID and b"null" in err.value
