@@ -142,6 +142,12 @@ typedef enum {
 } rtfhe_backend;
 
 /* ---- context ---- */
+/* Sizes.  Every array a call takes or fills -- and the context's own scratch, 4 (N + 1) bytes per sample between the two launches of a batch:
+ * 4.3 GB at a million gates -- may exceed 4 GiB: rows are addressed with 64-bit offsets wherever they lie, and a count is a size_t.  What bounds
+ * a call is its number of ITEMS, stated with each entry point and refused with RTFHE_ERR_INVALID above it: count, count * P, count * K,
+ * count << log2(n_out), count * depth or count * 2^(depth-1), rows * N / 16 and n_x are at most 2^31 - 1; the compressed results also keep
+ * count * L, and a dense layer count * max(I, O) * (n + 1), below 2^31 words.  One item is at most 16 KiB (a TRLWE row at N = 2048).  Past that
+ * only the device's memory bounds an array. */
 void rtfhe_default_params(rtfhe_params *p);
 int rtfhe_ctx_create(const rtfhe_params *p, int device_id, rtfhe_ctx **out);
 /* One context over n_dev GPUs of the node (what a Rust `hom_nand_batch` binds for a whole-node batch).

@@ -63,6 +63,7 @@ inline int idx_null_ready(const TermIdx& t, size_t count, int32_t K, char* err, 
 
 // every entry of both host arrays in [0, n), sample by sample: a's entry k before b's
 inline int idx_walk(const TermIdx& a, const TermIdx& b, size_t count, int32_t K, char* err, size_t err_len) {
+    if (!a.idx && !b.idx) return 0;      // the _dev forms: nothing to walk (count * K goes up to 2^31 - 1: seconds of empty iterations)
     for (size_t g = 0; g < count; g++)
         for (int32_t k = 0; k < K; k++)
             for (const TermIdx* t : {&a, &b})

@@ -20,6 +20,18 @@ static int plan(const rtfhe_cmux_net_world *w, const int32_t *var, const int32_t
 }
 static void done(plan_out *p) { free(p->order); free(p->level_off); }
 
+/* buffers past 4 GiB and 16 GiB, and the item rule where the bytes are terabytes (sanitize_kit.h: large_cases, large_limit) */
+/* (a netlist has no caller buffers: the item rule and the node buffer's size in bytes) */
+static size_t large_node_bytes;
+static int large_plan(size_t count, const void *in, const void *out) {
+    const rtfhe_cmux_net_world lw = {1024, 2, 1, 1, 1, count};
+    const int32_t v[1] = {0}, h[1] = {-1}, l[1] = {-2}, o[1] = {0};
+    int32_t order[1], level_off[2], n_levels, span[2];
+    (void)in; (void)out;
+    memset(err, 'x', sizeof err);
+    return rtfhe_cmux_net_plan(&lw, v, h, l, NULL, 1, 1, o, NULL, 1, order, level_off, &n_levels, span, &large_node_bytes, err, sizeof err);
+}
+
 int main(void) {
     const rtfhe_cmux_net_world w = {1024, 23, 185, 0, 0, 37};
     /* the mixed netlist of the GPU test's shape: 11 nodes on 5 variables, levels of 4, 3, 3 and 1 nodes */
@@ -123,6 +135,8 @@ int main(void) {
         CHECK(strlen(small) == sizeof small - 1 && !strcmp(small, "node 7:"));
         CHECK(rtfhe_cmux_net_plan(&w, b, hi, lo, rot, 11, 5, out_ref, out_coef, 3, order, off, &nl, span, &nb, NULL, 0) == RTFHE_ERR_INVALID);
     }
+    large_limit(large_plan, 0x7fffffff, 0, "count * max(n_nodes, n_out)");
+    CHECK(large_plan(((size_t)1 << 21) + 3, NULL, NULL) == 0 && large_node_bytes == (((size_t)1 << 21) + 3) * 8192);
     printf("cmux net sanitizer walk ok\n");
     return 0;
 }

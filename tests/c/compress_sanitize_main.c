@@ -85,6 +85,17 @@ static void refused_trlwe(int32_t dir, int32_t N, int32_t k, int32_t P, const in
     free(idx);
 }
 
+/* buffers past 4 GiB and 16 GiB, and the item rule where the bytes are terabytes (sanitize_kit.h: large_cases, large_limit) */
+static int32_t large_idx[1];
+static int large_trlwe(size_t count, const void *in, const void *out) {
+    memset(err, 'x', sizeof err);
+    return rtfhe_trlwe_compress_plan(RTFHE_COMPRESS_PACK, 2048, 10, 1, NULL, 1, count, in, out, large_idx, err, sizeof err);
+}
+static int large_tlwe(size_t count, const void *in, const void *out) {
+    memset(err, 'x', sizeof err);
+    return rtfhe_tlwe_compress_plan(RTFHE_COMPRESS_PACK, 767, 10, count, in, out, err, sizeof err);
+}
+
 int main(void) {
     enum { N = 1024, n = 635 };
     /* the twins at the ragged shapes, buffers at exact size */
@@ -161,6 +172,16 @@ int main(void) {
     /* the public twins refuse through the same checks, before they touch a buffer */
     CHECK(rtfhe_tlwe_compress(n, 1, in, (uint32_t *)(uintptr_t)0x40000000, 3) == RTFHE_ERR_INVALID);
     CHECK(rtfhe_trlwe_expand(N, 12, N + 1, NULL, 1, in, (uint32_t *)(uintptr_t)0x40000000, 3) == RTFHE_ERR_INVALID);
+    {
+        const size_t most_trlwe = (size_t)0x7fffffff / 2049, most_tlwe = (size_t)0x7fffffff / 768;
+        const size_t trlwe[2] = {((size_t)1 << 18) + 3, most_trlwe}, tlwe[2] = {1398102 + 3, most_tlwe};
+        for (int t = 0; t < 2; t++) {
+            large_cases(large_trlwe, trlwe[t], trlwe[t] * 16384, trlwe[t] * 4 * rtfhe_compressed_words(2049, 10), 4, "overlaps");
+            large_cases(large_tlwe, tlwe[t], tlwe[t] * 3072, tlwe[t] * 4 * rtfhe_compressed_words(768, 10), 4, "overlaps");
+        }
+        large_limit(large_trlwe, most_trlwe, 16384, "count * L");
+        large_limit(large_tlwe, most_tlwe, 3072, "count * L");
+    }
     printf("compress sanitizer walk ok\n");
     return 0;
 }

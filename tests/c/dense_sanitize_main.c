@@ -29,6 +29,9 @@ static int weights(const int32_t *W, int32_t O, int32_t I, uint32_t *corr) {
     return rtfhe_dense_weights_plan(W, O, I, corr, err, sizeof err);
 }
 
+/* buffers past 4 GiB and 16 GiB, and the item rule where the bytes are terabytes (sanitize_kit.h: large_cases, large_limit) */
+static int large_plan(size_t count, const void *x, const void *out) { return plan(767, 16, 64, count, x, out); }
+
 int main(void) {
     const uintptr_t base = 0x10000000;                                              /* addresses only: integers, so that no pointer arithmetic leaves an object */
     const void *x = AT(base), *out = AT(0x4000000000ull);
@@ -124,6 +127,11 @@ int main(void) {
         CHECK(s.tiles == 2 && s.groups == 1 && s.cwgs == 5 && s.ksteps == 13 && s.slices == 1 && s.steps == 13);
         rtfhe_dense_launch_shape(635, 32, 784, 1, 0, &s);                            /* cus below 1 counts as 1 */
         CHECK(s.slices == 1);
+    }
+    {
+        const size_t most = (size_t)0x7fffffff / (64 * 768), counts[2] = {21900, most};
+        for (int t = 0; t < 2; t++) large_cases(large_plan, counts[t], counts[t] * 64 * 3072, counts[t] * 16 * 3072, 4, "overlaps");
+        large_limit(large_plan, most, 64 * 3072, "count * max(I, O)");
     }
     printf("dense sanitizer walk ok\n");
     return 0;

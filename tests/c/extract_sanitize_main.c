@@ -21,6 +21,13 @@ static void refused(int32_t N, int32_t P, const int32_t *coef, int32_t stride, s
     free(idx);
 }
 
+/* buffers past 4 GiB and 16 GiB, and the item rule where the bytes are terabytes (sanitize_kit.h: large_cases, large_limit) */
+static int32_t large_idx[1];
+static int large_plan(size_t count, const void *in, const void *out) {
+    memset(err, 'x', sizeof err);
+    return rtfhe_extract_plan(2048, 1, NULL, 1, count, in, out, 2049, large_idx, err, sizeof err);
+}
+
 int main(void) {
     enum { N = 1024, n1 = 636 };
     const uintptr_t base = 0x10000000;                                              /* addresses only: integers, so that no pointer arithmetic leaves an object */
@@ -81,6 +88,9 @@ int main(void) {
         CHECK(rtfhe_extract_plan(N, 1, neg, 1, 1, in, out, n1, idx, NULL, 0) == RTFHE_ERR_INVALID);
         free(idx);
     }
+    for (size_t count = ((size_t)1 << 18) + 3; count <= ((size_t)1 << 20) + 3; count += ((size_t)1 << 20) - ((size_t)1 << 18))
+        large_cases(large_plan, count, count * 16384, count * 8196, 4, "overlaps");
+    large_limit(large_plan, 0x7fffffff, 16384, "count * P");
     printf("extract sanitizer walk ok\n");
     return 0;
 }

@@ -30,6 +30,14 @@ static int32_t *list(int32_t P, int32_t fill, int32_t at, int32_t v) {
     return pos;
 }
 
+/* buffers past 4 GiB and 16 GiB, and the item rule where the bytes are terabytes (sanitize_kit.h: large_cases, large_limit) */
+/* (the packing key switch compares no addresses: the item rule alone) */
+static int32_t large_shift[1024];
+static int large_plan(size_t count, const void *in, const void *out) {
+    memset(err, 'x', sizeof err);
+    return rtfhe_pack_plan(1024, 1024, NULL, 1, count, in, out, large_shift, err, sizeof err);
+}
+
 int main(void) {
     enum { N = 1024 };
     const void *in = AT(0x10000000), *out = AT(0x40000000);
@@ -92,6 +100,7 @@ int main(void) {
         free(shift);
         free(pos);
     }
+    large_limit(large_plan, (size_t)0x7fffffff / 1024, 1024 * 4 * 9, "count * P");
     printf("pack sanitizer walk ok\n");
     return 0;
 }

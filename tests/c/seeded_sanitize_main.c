@@ -38,6 +38,10 @@ static void phase(int N, const int32_t *key, const uint32_t *b, const uint32_t *
 
 static int32_t dist(uint32_t x, uint32_t y) { int32_t d = (int32_t)(x - y); return d < 0 ? -d : d; }
 
+/* buffers past 4 GiB and 16 GiB, and the item rule where the bytes are terabytes (sanitize_kit.h: large_cases, large_limit) */
+/* (the device form asks for 16-byte alignment first: the shared piece is 16 bytes) */
+static int large_plan(size_t rows, const void *b, const void *out) { return plan(RTFHE_SEEDED_DEVICE, 2048, seed, 5, b, 1, out, rows); }
+
 int main(void) {
     const uint64_t TOP = ~(uint64_t)0;                                              /* 2^64 - 1 */
     const void *b = AT(0x10000000), *out = AT(0x40000000);
@@ -168,6 +172,9 @@ int main(void) {
         CHECK(rtfhe_trgsw_encrypt_bits_seeded(NULL, key1, &one, fresh, bt, 1) == RTFHE_ERR_INVALID);
         free(bp); free(pfull); free(mu); free(bt); free(ph); free(key1); free(key0);
     }
+    for (size_t rows = ((size_t)1 << 19) + 3; rows <= ((size_t)1 << 21) + 3; rows += ((size_t)1 << 21) - ((size_t)1 << 19))
+        large_cases(large_plan, rows, rows * 8192, rows * 16384, 16, "overlaps");
+    large_limit(large_plan, (size_t)0x7fffffff / 128, 8192, "rows * N / 16");
     printf("seeded sanitizer walk ok\n");
     return 0;
 }

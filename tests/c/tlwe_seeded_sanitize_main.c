@@ -36,6 +36,10 @@ static uint32_t phase(int n, const int32_t *key, const uint32_t *row) {
 
 static int32_t dist(uint32_t x, uint32_t y) { int32_t d = (int32_t)(x - y); return d < 0 ? -d : d; }
 
+/* buffers past 4 GiB and 16 GiB, and the item rule where the bytes are terabytes (sanitize_kit.h: large_cases, large_limit) */
+/* (b is one word per row: the output is the array that passes 2^32 bytes) */
+static int large_plan(size_t rows, const void *b, const void *out) { return plan(RTFHE_TLWE_SEEDED_DEVICE, 767, seed, 5, b, out, rows); }
+
 int main(void) {
     const uint64_t TOP = ~(uint64_t)0;                                              /* 2^64 - 1 */
     const void *b = AT(0x10000000), *out = AT(0x40000000);
@@ -153,6 +157,11 @@ int main(void) {
         CHECK(rtfhe_tlwe_encrypt_bits_seeded(&p, NULL, bits, fresh, eb, 3) == RTFHE_ERR_INVALID);
         CHECK(rtfhe_tlwe_encrypt_torus_seeded(NULL, key0, mu, fresh, eb, 3) == RTFHE_ERR_INVALID);
         free(kb); free(kfull); free(eb); free(full); free(key0); free(key1);
+    }
+    {
+        const size_t rows[2] = {1398102 + 3, 5592405 + 3};
+        for (int t = 0; t < 2; t++) large_cases(large_plan, rows[t], rows[t] * 4, rows[t] * 3072, 4, "overlaps");
+        large_limit(large_plan, (size_t)0x7fffffff / 48, 4, "rows * ceil(n / 16)");
     }
     printf("tlwe seeded sanitizer walk ok\n");
     return 0;

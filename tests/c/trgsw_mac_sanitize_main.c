@@ -26,6 +26,11 @@ static int32_t *indices(size_t count, int K, int32_t fill) {
     return p;
 }
 
+/* buffers past 4 GiB and 16 GiB, and the item rule where the bytes are terabytes (sanitize_kit.h: large_cases, large_limit) */
+/* x of `rows` rows read by 64 samples (x_idx given: on the device), then 64 rows of x and `count` samples: the output is the far array */
+static int large_x(size_t rows, const void *x, const void *out) { return plan(2048, 1, 1, 1, NULL, (int32_t)rows, 1, NULL, 64, x, out); }
+static int large_out(size_t count, const void *x, const void *out) { return plan(2048, 1, 1, 1, NULL, 64, 1, NULL, count, x, out); }
+
 int main(void) {
     enum { N = 1024 };
     const uintptr_t base = 0x10000000;                                              /* addresses only: integers, so that no pointer arithmetic leaves an object */
@@ -95,6 +100,14 @@ int main(void) {
         char tiny[8];
         CHECK(rtfhe_trgsw_mac_plan(N, 1, 9, 0, NULL, 1, 0, NULL, 1, x, out, tiny, sizeof tiny) == RTFHE_ERR_INVALID && strlen(tiny) == sizeof tiny - 1);
         CHECK(rtfhe_trgsw_mac_plan(N, 1, 9, 0, NULL, 1, 0, NULL, 1, x, out, NULL, 0) == RTFHE_ERR_INVALID);
+    }
+    {
+        const size_t rows[2] = {((size_t)1 << 18) + 3, ((size_t)1 << 20) + 4};
+        for (int t = 0; t < 2; t++) {
+            large_cases(large_x, rows[t], rows[t] * 16384, 64 * 16384, 4, "overlaps");
+            large_cases(large_out, rows[t], 64 * 16384, rows[t] * 16384, 4, "overlaps");
+        }
+        large_limit(large_out, 0x7fffffff, 0, "count * K");
     }
     printf("trgsw mac sanitizer walk ok\n");
     return 0;

@@ -15,12 +15,12 @@ TREE_N_SEL = 37 * 4          # sel_idx = NULL at depth 4 and 37 lookups reads se
 TREE_N_ROWS = 16 + 7         # row0 up to 7 at depth 4
 
 
-def selector_world(orc, N, key_seed, rng_seed, n_sel, sel_seed, known=(0, 1)):
-    """What every leveled world starts with: keys from the product's keygen at the stage tests' n, the oracle's parameters and plan, n_sel
+def selector_world(orc, N, key_seed, rng_seed, n_sel, sel_seed, known=(0, 1), n=None):
+    """What every leveled world starts with: keys from the product's keygen at the stage tests' n (or at `n`), the oracle's parameters and plan, n_sel
     selectors of random bits (the first ones `known`) as torus words and as the oracle's spectra of them.  Returns (w, rng): the module's
     fixture draws its tables and rows from rng next, then creates its engine and handles."""
     import rustfhe_amd as R
-    rp = R.Params(n=SMALL_N[N], N=N)
+    rp = R.Params(n=n or SMALL_N[N], N=N)
     key0, key1, bk, ksk = R.keygen(rp, key_seed)
     w = types.SimpleNamespace(R=R, N=N, logn=N.bit_length() - 1, rp=rp, key0=key0, key1=key1, bk=bk, ksk=ksk)
     w.P = orc.Params(n=rp.n, N=N)
