@@ -283,6 +283,10 @@ extern "C" {
     pub fn rtfhe_tlwe_compress_batch_dev(ctx: *mut rtfhe_ctx, k: i32, d_tlwe: *const c_void, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
     pub fn rtfhe_trlwe_compress_batch_dev(ctx: *mut rtfhe_ctx, k: i32, d_trlwe: *const c_void, P: i32, coef: *const i32, stride: i32, d_out: *mut c_void,
                                           count: usize, stream: *mut c_void) -> c_int;
+    // ... and back: packed rows that came up from the host, expanded on the device in the computation's stream
+    pub fn rtfhe_tlwe_expand_batch_dev(ctx: *mut rtfhe_ctx, k: i32, d_words: *const c_void, d_tlwe: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
+    pub fn rtfhe_trlwe_expand_batch_dev(ctx: *mut rtfhe_ctx, k: i32, d_words: *const c_void, P: i32, coef: *const i32, stride: i32, d_trlwe: *mut c_void,
+                                        count: usize, stream: *mut c_void) -> c_int;
     pub fn rtfhe_compressed_words(L: usize, k: i32) -> usize;
     pub fn rtfhe_tlwe_compress(n: i32, k: i32, input: *const u32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_tlwe_expand(n: i32, k: i32, input: *const u32, out: *mut u32, count: usize) -> c_int;

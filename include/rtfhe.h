@@ -62,6 +62,8 @@
  *                                       lvl0 ciphertexts in front of a bootstrap (the reference has the row operations, not the layer)
  *   rtfhe_tlwe_compress_batch_dev / rtfhe_trlwe_compress_batch_dev / rtfhe_tlwe_compress / _expand / rtfhe_trlwe_compress / _expand
  *                                    (no reference counterpart) results rounded to k bits per word and bit-packed on the GPU, expanded by the key holder
+ *   rtfhe_tlwe_expand_batch_dev / rtfhe_trlwe_expand_batch_dev
+ *                                    (no reference counterpart) packed rows expanded on the GPU: stored or forwarded results as inputs again
  *   rtfhe_external_product_batch     <- Cross for TRGSWRepF (hom_nand/src/trgsw.rs:264-306)
  *   rtfhe_key_switch_batch          <- TLWERep::identity_key_switch (hom_nand/src/tlwe.rs:43-73)
  *   rtfhe_ifft_i32_batch             <- Spqlios_ifft_i32 / _u32 (utils/src/spqlios.rs:22-23, spqlios-wrapper.cpp:22-28)
@@ -1075,7 +1077,8 @@ int rtfhe_load_ksk_seeded(rtfhe_ctx *ctx, const uint32_t *seed, uint64_t first_r
  * bits are noise (a bootstrapped lvl0 ciphertext has sigma ~ 0.0116 of the torus in reference mode, 0.0028 in rounded mode, on messages spaced
  * 1/8 .. 1/32 apart).  Keeping the top k bits of every word and packing them densely is modulus switching plus bit packing: a lvl0 result is 795
  * bytes at k = 10 instead of 2,544, and 1,024 results packed into one TRLWE (rtfhe_pack_batch) are 3 KB at k = 12.  The rounding and packing run
- * on the GPU, in the stream or captured graph of the computation, so only the small buffer crosses the bus; the key holder expands on the CPU.
+ * on the GPU, in the stream or captured graph of the computation, so only the small buffer crosses the bus; the key holder expands on the CPU, and a
+ * server that takes stored or forwarded rows up again expands them on the GPU (rtfhe_tlwe_expand_batch_dev, rtfhe_trlwe_expand_batch_dev below).
  *
  * One row.  A row of L torus words v[0 .. L) and a width k, 2 <= k <= 32:
  *   - rounding: r[i] = ((v[i] + 2^(31-k)) mod 2^32) >> (32 - k), a k-bit value: round to nearest, ties up, wrapping -- a word that rounds up to
@@ -1107,6 +1110,24 @@ int rtfhe_tlwe_compress_batch_dev(rtfhe_ctx *ctx, int32_t k, const void *d_tlwe 
 int rtfhe_trlwe_compress_batch_dev(rtfhe_ctx *ctx, int32_t k, const void *d_trlwe /* [count][2][N] */, int32_t P,
                                    const int32_t *coef /* HOST [P] or NULL */, int32_t stride, void *d_out /* u32[count][W(N+P,k)] */, size_t count,
                                    void *stream);
+/* The other direction on the device: packed rows that came up from the host -- results kept at rest, handed over by another server, read from an
+ * "RTFHECZ1" file -- become full rows in the computation's own stream, so the packed bytes are all that cross the bus (lvl0, k = 10: 796 bytes
+ * instead of 2,544).  Word for word the CPU twins below: value i of a row is the k-bit field at stream bits [i k, i k + k) of its W words and
+ * the expanded word is value << (32 - k) (k = 32: the word itself).  lvl0 form: d_tlwe[g][i] = value i, i = 0 .. n.  TRLWE form: the a
+ * polynomial d_trlwe[g][1][i] = value i, i < N; b[j] = value N + p for the LAST p with coef[p] = j (the later entry wins) and 0 at every other
+ * j.  The list follows the compress call's rules (a host coef[P], or NULL for p * stride) and is copied into the launch arguments when the call is
+ * enqueued.  Bits of a row's last word past L k reach no result; no packed word outside a row's W words is read.
+ *   Each call writes exactly count * (n + 1), or count * 2 N, words, each once by a plain store, whatever the buffer held; rows past `count` keep
+ * their bytes.  d_words and the output need 4-byte alignment only: d_tlwe may be a range of rows of a wire table.  The contract is the compress
+ * calls': asynchronous and ordered on `stream`, primary device, every backend, no key, nothing allocated, capturable first thing on a fresh
+ * stream; the same checks before anything is launched (the full rows are now the output), RTFHE_ERR_INVALID with a message; count == 0 returns 0.
+ *   Launches of k_expand_rows: one for lvl0 rows and for coef == NULL.  With a list the kept coefficients travel as an inverse map (for each
+ * j, -1 or the last p) in the launch arguments, 1,024 entries a launch: ceil(N / 1024) launches -- one at N = 1024, two at N = 2048. */
+int rtfhe_tlwe_expand_batch_dev(rtfhe_ctx *ctx, int32_t k, const void *d_words /* u32[count][W(n+1,k)] */, void *d_tlwe /* [count][n+1] */,
+                                size_t count, void *stream);
+int rtfhe_trlwe_expand_batch_dev(rtfhe_ctx *ctx, int32_t k, const void *d_words /* u32[count][W(N+P,k)] */, int32_t P,
+                                 const int32_t *coef /* HOST [P] or NULL */, int32_t stride, void *d_trlwe /* [count][2][N] */, size_t count,
+                                 void *stream);
 /* The key holder's side, and the host-buffer form of this feature: the same words on the CPU and their inverses, from a plain n or N, with no
  * context and no GPU (there is no upload-compress-download call: rows that are already on the host are compressed here).  Same checks, returned as
  * RTFHE_ERR_INVALID; in and out must not overlap. */

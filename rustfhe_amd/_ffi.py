@@ -212,6 +212,8 @@ _SIGNATURES = {
     "rtfhe_load_ksk_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "rtfhe_tlwe_compress_batch_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtfhe_trlwe_compress_batch_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtfhe_tlwe_expand_batch_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtfhe_trlwe_expand_batch_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtfhe_compressed_words": (C.c_size_t, [C.c_size_t, C.c_int32]),
     "rtfhe_tlwe_compress": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t]),
     "rtfhe_tlwe_expand": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t]),

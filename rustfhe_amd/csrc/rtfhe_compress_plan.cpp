@@ -1,7 +1,9 @@
 // rtfhe_compress_plan.cpp -- host only: compressed results (rtfhe_compress_plan.h; include/rtfhe.h, "compressed results").  The argument checks
 // that rtfhe_tlwe_compress_batch_dev / rtfhe_trlwe_compress_batch_dev (rtfhe_compress.hip) run before they launch anything, the row size, and the
 // key holder's CPU forms: rtfhe_tlwe_compress / _expand and rtfhe_trlwe_compress / _expand, which take a plain n or N and no context.  The
-// coefficient list of the TRLWE form is rtfhe_extract_plan's (rtfhe_extract_plan.cpp), called here and not restated.
+// coefficient list of the TRLWE form is rtfhe_extract_plan's (rtfhe_extract_plan.cpp), called here and not restated.  The device-side expansion
+// (rtfhe_tlwe_expand_batch_dev / rtfhe_trlwe_expand_batch_dev) runs the same checks with RTFHE_COMPRESS_EXPAND and takes its inverse map of the
+// coefficient list from rtfhe_expand_inverse_map.
 #include "rtfhe_compress_plan.h"
 
 #include <vector>
@@ -67,6 +69,15 @@ int rtfhe_trlwe_compress_plan(int32_t dir, int32_t N, int32_t k, int32_t P, cons
     // the list alone: with count = 0 rtfhe_extract_plan has no size and no overlap left to look at
     if (int rc = rtfhe_extract_plan(N, P, coef, stride, 0, in, out, 0, idx, err, err_len)) return rc;
     return size_and_overlap(dir, k, (size_t)N + (size_t)P, 2 * (size_t)N, count, in, out, err, err_len);
+}
+
+int rtfhe_expand_inverse_map(int32_t N, int32_t P, const int32_t* idx, int16_t* inv) {
+    if (!idx || !inv || N < 1 || N > 32768 || P < 1 || P > N) return RTFHE_ERR_INVALID;
+    for (int32_t p = 0; p < P; p++)
+        if (idx[p] < 0 || idx[p] >= N) return RTFHE_ERR_INVALID;
+    for (int32_t j = 0; j < N; j++) inv[j] = -1;
+    for (int32_t p = 0; p < P; p++) inv[idx[p]] = (int16_t)p;      // in list order: the later entry wins
+    return 0;
 }
 
 int rtfhe_tlwe_compress(int32_t n, int32_t k, const uint32_t* in, uint32_t* out, size_t count) {

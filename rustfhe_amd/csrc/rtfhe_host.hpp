@@ -33,8 +33,8 @@
 //                            checks and the CPU forms: rtfhe_seeded.cpp, host only; the encryptor core it shares with rtfhe_keygen.cpp:
 //                            rtfhe_encrypt.hpp)
 //   rtfhe_compress.hip       compressed results: result rows rounded to k bits per word and bit-packed on the device (k_compress_rows), lvl0 rows and
-//                            TRLWE rows with a list of kept coefficients (its argument checks and the key holder's CPU forms: rtfhe_compress_plan.cpp,
-//                            host only)
+//                            TRLWE rows with a list of kept coefficients, and packed rows expanded on the device again (k_expand_rows) (its argument
+//                            checks, the inverse map of the list and the key holder's CPU forms: rtfhe_compress_plan.cpp, host only)
 // Every kernel is instantiated in exactly one of them.  No CPU fallback anywhere: an entry point runs HIP kernels or fails.
 #pragma once
 

@@ -70,4 +70,78 @@ __global__ __launch_bounds__(COMPRESS_THREADS) void k_compress_rows(const Compre
     a.out[(size_t)g * a.W + w] = word;
 }
 
+// ---- the other direction (include/rtfhe.h: rtfhe_tlwe_expand_batch_dev, rtfhe_trlwe_expand_batch_dev) ----
+// k_expand_rows mirrors k_compress_rows: one lane per OUTPUT word, here a word of a full row.  A full row is `out_stride` words: the L0 words at
+// `seg` are the values 0 .. L0 - 1 of its packed row, and (TRLWE form) word j of the b polynomial, which lies at word j of the row, is value
+// L0 + p for the LAST p with coef[p] = j, or 0 where no entry names j.
+//   lvl0:   seg = 0, L0 = out_stride = n + 1: every lane has a value
+//   TRLWE:  seg = N (the a polynomial), L0 = N, out_stride = 2 N; "the last p, or none" is arithmetic for a NULL list (stride >= 1: j is kept
+//           iff j % stride == 0 and j / stride < P) and a lookup in inv[] for a list (stride == 0): inv[j - j0] is -1 or p, built on the host
+//           (rtfhe_expand_inverse_map) and carried in the arguments, EXPAND_MAP_MAX entries of int16 a launch (P <= N <= 2048 fits)
+// Value i is the k-bit field at stream bits [i k, i k + k) of the row's W words: with s = i k the lane loads word s / 32 and the word after it,
+// takes the 64-bit concatenation down by s % 32 (0 .. 31: never a shift by 32) and the low word of that up by 32 - k (0 .. 30), which drops every
+// bit above the field -- the mask -- and leaves the value at the top of the word; k = 32 moves nothing.  THE SECOND WORD'S INDEX IS CLAMPED TO
+// W - 1: no packed word at index >= W of its row is ever loaded.  The clamp only bites when the field ends inside word W - 1 (i k + k <= L k <=
+// 32 W), where s % 32 + k <= 32 and no bit of the second word survives the two shifts; for the same reason the padding bits of the last word past
+// L k reach no result.  Packed rows are 4-byte aligned only (W may be odd): both loads are dword loads.
+//
+// One plain store a lane, each output word written by exactly one lane of one launch (no memset-then-scatter: duplicates in the list would race);
+// a wave writes 256 contiguous bytes and reads the 8 k contiguous bytes under them.  No LDS, no atomics.
+//
+// A launch owns words [o0, o0 + no) of every full row.  lvl0 and a NULL list: the whole row, one launch.  With a list: the first launch owns the
+// a polynomial and the EXPAND_MAP_MAX words of b before it (o0 = N - 1024: the whole row at N = 1024), each further launch the 1,024 words of b
+// before that (one more at N = 2048).
+//
+// Indexing: count * L < 2^31 bounds the packed values, not the output: count * 2 N reaches just under 2^32 words (P small) and byte offsets pass
+// 2^32 long before.  total = count * no < 2^32 fits a u32, but the lane index of the last workgroup may pass 2^32, so it is formed and compared
+// in 64 bits; row offsets are size_t.
+constexpr int EXPAND_MAP_MAX = 1024;       // entries of the inverse map one k_expand_rows launch carries in its arguments (2 KB)
+constexpr int EXPAND_THREADS = 256;
+
+struct ExpandArgs {
+    const uint32_t* in;      // [count][W]
+    uint32_t* out;           // [count][out_stride]
+    uint32_t W;              // words of a packed row: ceil(L k / 32)
+    uint32_t out_stride;     // words of a full row
+    uint32_t seg, L0;        // words [seg, seg + L0) of a full row are values 0 .. L0 - 1; every other word j is b[j]
+    uint32_t k;              // 2 .. 32
+    uint32_t o0, no;         // this launch writes words [o0, o0 + no) of every full row
+    uint32_t total;          // lanes: count * no (< 2^32)
+    uint32_t no_rcp;         // floor(2^32 / no) (no = 1: 2^32 - 1): t / no without a division
+    uint32_t P, stride;      // stride >= 1: coef[p] = p * stride (the NULL list); stride == 0: inv[]
+    uint32_t j0;             // inv[] starts at b[j0]
+    int16_t inv[EXPAND_MAP_MAX];     // -1, or the last p with coef[p] = j0 + index
+};
+
+// grid: ceil(total / EXPAND_THREADS) workgroups; lane t writes word o0 + t % no of row t / no
+__global__ __launch_bounds__(EXPAND_THREADS) void k_expand_rows(const ExpandArgs a) {
+    const uint64_t t64 = (uint64_t)blockIdx.x * (uint32_t)EXPAND_THREADS + threadIdx.x;      // may pass 2^32 in the last workgroup: 64 bits
+    if (t64 >= a.total) return;
+    const uint32_t t = (uint32_t)t64;
+    // t / no by the host's reciprocal: q = floor(t * floor(2^32 / no) / 2^32) is g or g - 1 (t * m / 2^32 > t / no - t / 2^32 > g - 1), so one
+    // correction makes it exact -- a mul_hi and a mul_lo where a per-lane division is a float reciprocal and four multiplies (3 % of the kernel's
+    // time at 131,072 lvl0 rows)
+    uint32_t g = __umulhi(t, a.no_rcp), r = t - g * a.no;
+    if (r >= a.no) { g++; r -= a.no; }
+    const uint32_t o = a.o0 + r;
+    uint32_t* dst = a.out + ((size_t)g * a.out_stride + o);
+    uint32_t i = o - a.seg;                                                        // the value under this word (wraps above L0 where o < seg)
+    if (i >= a.L0) {                                                               // a word of b: the last p that names it, or none
+        int32_t p;
+        if (a.stride) {
+            const uint32_t q = o / a.stride;
+            p = (q * a.stride == o && q < a.P) ? (int32_t)q : -1;
+        } else {
+            p = a.inv[o - a.j0];                                                   // o - j0 < EXPAND_MAP_MAX: the launch's own words of b
+        }
+        if (p < 0) { *dst = 0u; return; }
+        i = a.L0 + (uint32_t)p;
+    }
+    const uint32_t* row = a.in + (size_t)g * a.W;
+    const uint32_t s = __umul24(i, a.k);                                           // i < L <= 2 N = 4096, k <= 32: both fit 24 bits, s < 2^17
+    const uint32_t w = s >> 5, w1 = w + 1u < a.W ? w + 1u : a.W - 1u;              // the clamp: index W is never loaded
+    const uint64_t cat = (uint64_t)row[w1] << 32 | row[w];
+    *dst = (uint32_t)(cat >> (s & 31u)) << (32u - a.k);
+}
+
 }  // namespace rtfhe

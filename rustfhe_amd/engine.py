@@ -42,6 +42,20 @@ class _Handle:
             pass
 
 
+def packed_rows(words, L, k):
+    """The host side of the upload_*_compressed helpers, checked before any device is touched: compressed rows of L values at k bits as a
+    contiguous u32[count][W(L, k)] -- what read_compressed returns goes through as it is, a flat array is cut into rows.  RtfheError for k
+    outside 2 .. 32 or a size that is no whole number of rows."""
+    k, L = int(k), int(L)
+    W = (L * k + 31) // 32
+    if not 2 <= k <= 32 or L < 1:
+        raise RtfheError(ERR_INVALID, "k = %d is outside 2 .. 32 (or the row is empty)" % k)
+    words = _np(words, np.uint32)
+    if words.size % W or (words.ndim > 1 and words.shape[-1] != W):
+        raise RtfheError(ERR_INVALID, "compressed rows of %d values at k = %d are %d words each; got an array of shape %s" % (L, k, W, words.shape))
+    return words.reshape(-1, W)
+
+
 ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
 
 
@@ -575,6 +589,50 @@ class Engine(_Handle):
         coef = self._coef_arg(coef, P)      # (kept in a name: _ptr holds an address, not the array)
         self._ck(self.L.rtfhe_trlwe_compress_batch_dev(self.h, int(k), self._dev(d_trlwe), int(P), _ptr(coef), int(stride), self._dev(d_out), count,
                                                        _stream(stream)))
+
+    # ---- ... and back on the device (include/rtfhe.h: rtfhe_tlwe_expand_batch_dev, rtfhe_trlwe_expand_batch_dev) ------------------------------------
+    def tlwe_expand_dev(self, d_words, k, d_out, count, stream=None):
+        """Packed lvl0 rows on the device (u32[count][W(n+1, k)]) -> d_out [count][n+1] words, each value back at the top of its word: what
+        rustfhe_amd.tlwe_expand computes on the CPU.  One launch, asynchronous on `stream`, no key, every backend, nothing allocated; writes
+        exactly count * (n + 1) words, so d_out may be a range of rows of a larger wire table (4-byte alignment is all it needs)."""
+        self._ck(self.L.rtfhe_tlwe_expand_batch_dev(self.h, int(k), self._dev(d_words), self._dev(d_out), count, _stream(stream)))
+
+    def trlwe_expand_dev(self, d_words, k, P, d_out, count, coef=None, stride=1, stream=None):
+        """Packed TRLWE rows on the device (u32[count][W(N+P, k)]) -> d_out [count][2][N] words (b then a): the a polynomial, b at the P kept
+        coefficients coef (a host array, copied at enqueue time; None: p * stride; duplicates: the later entry wins) and zero everywhere else --
+        rustfhe_amd.trlwe_expand on the GPU.  One launch (with a list at N = 2048: two), asynchronous on `stream`, nothing allocated."""
+        coef = self._coef_arg(coef, P)      # (kept in a name: _ptr holds an address, not the array)
+        self._ck(self.L.rtfhe_trlwe_expand_batch_dev(self.h, int(k), self._dev(d_words), int(P), _ptr(coef), int(stride), self._dev(d_out), count,
+                                                     _stream(stream)))
+
+    def _upload_compressed(self, words, row_words, expand):
+        """what both upload helpers do with their checked rows: copy them up, expand(d_words, d_out, count, stream) on torch's current stream"""
+        import torch
+        with torch.cuda.device(self.device):
+            d_words = torch.from_numpy(words.view(np.int32)).cuda()
+            d_out = torch.empty((words.shape[0],) + tuple(row_words), dtype=torch.int32, device="cuda")
+            if words.shape[0]:
+                expand(d_words, d_out, words.shape[0], torch.cuda.current_stream().cuda_stream)
+        return d_out
+
+    def upload_tlwe_compressed(self, words, k):
+        """Compressed lvl0 rows (tlwe_compress, Engine.tlwe_compress_dev, read_compressed) to the device: copies u32[count][W(n+1, k)] up,
+        expands it there and returns the int32 device tensor [count][n+1] the *_dev batch calls read -- 796 bytes per row cross the bus at
+        k = 10, not 2,544.  Queued on torch's current stream."""
+        words = packed_rows(words, self.p.n + 1, k)
+        return self._upload_compressed(words, (self.p.n + 1,), lambda d_w, d_out, count, st: self.tlwe_expand_dev(d_w, k, d_out, count, st))
+
+    def upload_trlwe_compressed(self, words, k, P, coef=None, stride=1):
+        """Compressed TRLWE rows to the device: copies u32[count][W(N+P, k)] up, expands it there and returns the int32 device tensor
+        [count][2][N] that trlwe_extract_batch_dev, Lut.update_dev and the leveled calls read.  coef / stride as in trlwe_compress_dev --
+        read_compressed's (words, k, _, N, coef) go in as upload_trlwe_compressed(words, k, len(coef), coef)."""
+        P = int(P)
+        if not 1 <= P <= self.p.N:
+            raise RtfheError(ERR_INVALID, "P = %d is outside 1 .. N = %d" % (P, self.p.N))
+        coef = self._coef_arg(coef, P)
+        words = packed_rows(words, self.p.N + P, k)
+        return self._upload_compressed(words, (2, self.p.N),
+                                       lambda d_w, d_out, count, st: self.trlwe_expand_dev(d_w, k, P, d_out, count, coef, stride, st))
 
     # ---- exact TRLWE x plain-polynomial products (include/rtfhe.h: rtfhe_plain_create, rtfhe_trlwe_mul_plain_batch[_dev]) --------------------------
     def plain_polys(self, w):
