@@ -34,6 +34,7 @@ pub enum rtfhe_circuit {}
 pub enum rtfhe_lut {}
 pub enum rtfhe_trgsw {}
 pub enum rtfhe_packing_key {}
+pub enum rtfhe_mbk {}
 pub enum rtfhe_plain {}
 pub enum rtfhe_dense {}
 pub enum rtfhe_fft_plan {}
@@ -161,6 +162,18 @@ extern "C" {
     pub fn rtfhe_packing_keygen(p: *const rtfhe_params, key0: *const i32, key1: *const i32, pk: *mut u32) -> c_int;
     pub fn rtfhe_packing_keygen_deterministic(p: *const rtfhe_params, seed: u64, key0: *const i32, key1: *const i32, pk: *mut u32) -> c_int;
     pub fn rtfhe_packing_key_create(ctx: *mut rtfhe_ctx, pk: *const u32, out: *mut *mut rtfhe_packing_key) -> c_int;
+    // multi-bit blind rotation (g = 2 or 3 key bits per step)
+    pub fn rtfhe_mbk_words(p: *const rtfhe_params, g: i32) -> usize;
+    pub fn rtfhe_mbk_keygen(p: *const rtfhe_params, g: i32, key0: *const i32, key1: *const i32, out: *mut u32) -> c_int;
+    pub fn rtfhe_mbk_keygen_deterministic(p: *const rtfhe_params, seed: u64, g: i32, key0: *const i32, key1: *const i32, out: *mut u32) -> c_int;
+    pub fn rtfhe_mb_roots(N: i32, out: *mut f64) -> c_int;
+    pub fn rtfhe_mb_point_exponents(N: i32, out: *mut i32) -> c_int;
+    pub fn rtfhe_mbk_create(ctx: *mut rtfhe_ctx, words: *const u32, g: i32, out: *mut *mut rtfhe_mbk) -> c_int;
+    pub fn rtfhe_mbk_destroy(k: *mut rtfhe_mbk);
+    pub fn rtfhe_pbs_mb_batch(ctx: *mut rtfhe_ctx, mbk: *const rtfhe_mbk, lut: *const rtfhe_lut, lut_idx: *const i32, tlwe: *const u32, out: *mut u32,
+                              count: usize) -> c_int;
+    pub fn rtfhe_pbs_mb_batch_dev(ctx: *mut rtfhe_ctx, mbk: *const rtfhe_mbk, lut: *const rtfhe_lut, d_lut_idx: *const c_void, d_tlwe: *const c_void,
+                                  d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
     pub fn rtfhe_packing_key_destroy(pk: *mut rtfhe_packing_key);
     pub fn rtfhe_pack_batch(ctx: *mut rtfhe_ctx, pk: *const rtfhe_packing_key, tlwe: *const u32, P: i32, pos: *const i32, rep: i32, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_pack_batch_dev(ctx: *mut rtfhe_ctx, pk: *const rtfhe_packing_key, d_tlwe: *const c_void, P: i32, pos: *const i32, rep: i32, d_out: *mut c_void,

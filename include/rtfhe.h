@@ -1161,6 +1161,58 @@ int rtfhe_compressed_write(const char *path, int32_t kind, int32_t dim, int32_t 
 int rtfhe_compressed_read_header(const char *path, int32_t *kind, int32_t *dim, int32_t *k, int32_t *P, uint64_t *count);
 int rtfhe_compressed_read(const char *path, int32_t *coef /* [P] */, uint32_t *words /* [capacity][W] */, size_t capacity);
 
+/* ---- multi-bit blind rotation: a programmable bootstrap in ceil(n / g) dependent steps instead of n ----
+ * The key bits are cut into groups of g = 2 or 3: group t covers bits [t g, min(n, t g + g)), the last one ragged when g does not divide n.
+ * With abar_i, bbar, the table row tv and the starting accumulator acc = X^{-bbar} (tv, 0) exactly as in rtfhe_pbs_batch, one step per group:
+ *
+ *     acc = acc + (Sum_{j = 1 .. J} F_{e_j} . BK_{t,j}) [.] acc            J = 2^g' - 1, g' the bits of the group
+ *     e_j = Sum_{q in j} abar_{t g + q}  mod 2N                            bit q of the subset number j = bit t g + q of the key
+ *     out[g] = identity_key_switch(sample_extract_0(acc))                  after the last group
+ *
+ * BK_{t,j} is a TRGSW sample under key1 of the constant  prod_{q in j} s_q  prod_{q not in j} (1 - s_q)  -- 1 exactly when the set bits of the
+ * group are those of j -- with the bootstrapping key's gadget and noise, and [.] the external product of rtfhe_external_product_batch in the
+ * decomposition rtfhe_set_decomposition selects.  F_e is the spectrum of X^e - 1 in the transform's own point order:
+ * F_e[p] = W[(e q_p) mod 2N] - 1, W[t] = exp(i pi t / N) (rtfhe_mb_roots: double[2N][2], cos then sin of the double pi * t / N, W[0] = 1 exactly)
+ * and q_p the odd exponent at which the forward transform leaves its value at point p = m * 64 + lane of the device layout
+ * (rtfhe_mb_point_exponents: int32[N/2]).  Both tables are plain functions of N and need no context.
+ * Every product and sum is rounded on its own, in this order per digit row, output component and point: K = F_{e_1} B_1, then
+ * K = K + F_{e_j} B_j for j = 2 .. J, each complex product as (re re - im im, im re + re im); K then stands where the single-bit step has its
+ * key row; the truncated product is added into acc.  No subset is left out when e_j = 0.
+ * The output decrypts like rtfhe_pbs_batch's; its words differ (another key, another order of roundings).
+ *
+ * The key.  rtfhe_mbk_words gives its size in words (0 for bad arguments): n_trgsw * 4 l N, n_trgsw = floor(n / g) (2^g - 1) + 2^(n mod g) - 1,
+ * i.e. 1.5 x the bootstrapping key at g = 2 and 2.33 x at g = 3.  rtfhe_mbk_keygen fills u32[n_trgsw][2][2l][N], every sample in the layout
+ * of one bootstrapping-key entry, groups in order, j ascending, from the OS CSPRNG; rtfhe_mbk_keygen_deterministic (TEST ONLY) from a seed.
+ * Both refuse g outside {2, 3} and non-binary keys (RTFHE_ERR_INVALID).
+ * rtfhe_mbk_create converts it to spectra on the primary device (as rtfhe_load_bk_torus converts the bootstrapping key; 93.6 MB at the default
+ * parameters and g = 2, 145.5 MB at g = 3, counted by rtfhe_ctx_memory_bytes) under the lifetime rule of every handle: normally destroyed before
+ * its context; if the context goes first, the device copy goes with it, a later call with the key fails with RTFHE_ERR_STATE and
+ * rtfhe_mbk_destroy only frees the handle.  The bootstrapping key itself is not needed; the key-switching key is.
+ *
+ * The calls follow rtfhe_pbs_batch[_dev]: plain tables from rtfhe_lut_create (an encrypted one: RTFHE_ERR_INVALID), lut_idx NULL = table 0,
+ * indices checked on the host before anything is launched / on the device (a gate with a bad index is skipped, its output row is not a valid
+ * ciphertext, and the next rtfhe_sync returns RTFHE_ERR_INVALID); every check happens before any launch; the FP64 mirror backend only
+ * (the exact backends: RTFHE_ERR_INVALID, the context stays usable); N = 1024 and 2048.  On a multi-device context the batch runs on the primary.
+ * Inside a stream capture rtfhe_pbs_mb_batch_dev allocates nothing and needs no earlier call on the stream: there, and in a context without
+ * the matrix form of the key-switching key (RTFHE_KS_MM_MIN=0), the kernel switches keys itself; otherwise the samples go through the stream's
+ * sample buffer into the batch key switch, as a many-LUT PBS's do.  Both routes give the same words.
+ * Two kernel shapes: a wave per gate (any count, both N; what N = 2048 runs on) and, at N = 1024, a workgroup of six waves per gate, which
+ * every N = 1024 batch takes; they give the same words.  RTFHE_MB_SHAPE=wave|wg in the environment forces one (wg at N = 2048:
+ * RTFHE_ERR_INVALID). */
+typedef struct rtfhe_mbk rtfhe_mbk;
+size_t rtfhe_mbk_words(const rtfhe_params *p, int32_t g);
+int rtfhe_mbk_keygen(const rtfhe_params *p, int32_t g, const int32_t *key0, const int32_t *key1, uint32_t *out /* [n_trgsw][2][2l][N] */);
+/* TEST ONLY (deterministic from a seed; NOT secure) */
+int rtfhe_mbk_keygen_deterministic(const rtfhe_params *p, uint64_t seed, int32_t g, const int32_t *key0, const int32_t *key1, uint32_t *out);
+int rtfhe_mb_roots(int32_t N, double *out /* [2N][2] */);
+int rtfhe_mb_point_exponents(int32_t N, int32_t *out /* [N/2] */);
+int rtfhe_mbk_create(rtfhe_ctx *ctx, const uint32_t *words, int32_t g, rtfhe_mbk **out);
+void rtfhe_mbk_destroy(rtfhe_mbk *k);
+int rtfhe_pbs_mb_batch(rtfhe_ctx *ctx, const rtfhe_mbk *mbk, const rtfhe_lut *lut, const int32_t *lut_idx /* [count] or NULL */,
+                       const uint32_t *tlwe /* [count][n+1] */, uint32_t *out /* [count][n+1] */, size_t count);
+int rtfhe_pbs_mb_batch_dev(rtfhe_ctx *ctx, const rtfhe_mbk *mbk, const rtfhe_lut *lut, const void *d_lut_idx /* int32[count] or NULL */,
+                           const void *d_tlwe, void *d_out, size_t count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

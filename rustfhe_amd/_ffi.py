@@ -120,6 +120,15 @@ _SIGNATURES = {
     "rtfhe_trgsw_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "rtfhe_packing_keygen": (C.c_int, ["PP", C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtfhe_packing_keygen_deterministic": (C.c_int, ["PP", C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtfhe_mbk_words": (C.c_size_t, ["PP", C.c_int32]),
+    "rtfhe_mbk_keygen": (C.c_int, ["PP", C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtfhe_mbk_keygen_deterministic": (C.c_int, ["PP", C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtfhe_mb_roots": (C.c_int, [C.c_int32, C.c_void_p]),
+    "rtfhe_mb_point_exponents": (C.c_int, [C.c_int32, C.c_void_p]),
+    "rtfhe_mbk_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "rtfhe_mbk_destroy": (None, [C.c_void_p]),
+    "rtfhe_pbs_mb_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rtfhe_pbs_mb_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtfhe_packing_key_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "rtfhe_packing_key_destroy": (None, [C.c_void_p]),
     "rtfhe_pack_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),

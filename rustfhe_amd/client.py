@@ -73,6 +73,47 @@ def packing_keygen(params, key0, key1, seed=None):
     return pk
 
 
+def mbk_words(params, g):
+    """Words of a multi-bit bootstrapping key at g key bits per step (include/rtfhe.h: rtfhe_mbk_words); RtfheError for g outside {2, 3}."""
+    w = _ffi.load().rtfhe_mbk_words(C.byref(params), int(g))
+    if not w:
+        raise RtfheError(ERR_INVALID, "rtfhe_mbk_words: g = %d is outside {2, 3} (or bad parameters)" % int(g))
+    return w
+
+
+def mbk_keygen(params, key0, key1, g, seed=None):
+    """The multi-bit bootstrapping key of the lvl0 key key0 under the lvl1 key key1 (include/rtfhe.h: rtfhe_mbk_keygen): u32[n_trgsw][2][2l][N],
+    for every group of g key bits a TRGSW sample per non-empty subset j of its bits, encrypting 1 exactly when the group's set bits are those
+    of j; each sample in the layout of one bootstrapping-key entry, with its noise (1.5 x the bootstrapping key's size at g = 2, 2.33 x at
+    g = 3).  Engine.multibit_key uploads it.  seed None (production): OS CSPRNG; an integer seed = TEST-ONLY deterministic generation.
+    g outside {2, 3} and non-binary keys are refused."""
+    key0, key1 = _np(key0, np.int32).reshape(-1), _np(key1, np.int32).reshape(-1)
+    assert key0.size == params.n and key1.size == params.N
+    words = mbk_words(params, g)
+    out = np.empty((words // (4 * params.l * params.N), 2, 2 * params.l, params.N), np.uint32)
+    _unseeded("rtfhe_mbk_keygen", params, seed, 0, (int(g), _ptr(key0), _ptr(key1), _ptr(out)), " (non-binary key)")
+    return out
+
+
+def mb_roots(N):
+    """The roots table of the multi-bit key combination (rtfhe_mb_roots): float64[2N][2], row t = (cos, sin) of pi t / N."""
+    out = np.empty((2 * int(N) if 2 <= int(N) <= 1 << 20 else 1, 2), np.float64)      # (a refused N writes nothing)
+    rc = _ffi.load().rtfhe_mb_roots(int(N), _ptr(out))
+    if rc != 0:
+        raise RtfheError(rc, "rtfhe_mb_roots: N = %d" % int(N))
+    return out
+
+
+def mb_point_exponents(N):
+    """The point map of the multi-bit key combination (rtfhe_mb_point_exponents): int32[N/2], the odd exponent q_p of spectrum point
+    p = m * 64 + lane of the device layout."""
+    out = np.empty(int(N) // 2 if 128 <= int(N) <= 1 << 20 else 1, np.int32)      # (a refused N writes nothing)
+    rc = _ffi.load().rtfhe_mb_point_exponents(int(N), _ptr(out))
+    if rc != 0:
+        raise RtfheError(rc, "rtfhe_mb_point_exponents: N = %d" % int(N))
+    return out
+
+
 def encrypt_bits(params, key0, bits, seed=None):
     """seed None (production): mask and noise from the OS CSPRNG; an integer seed = TEST-ONLY deterministic encryption."""
     bits = _np(bits, np.uint8).reshape(-1)

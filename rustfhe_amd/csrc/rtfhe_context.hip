@@ -326,6 +326,7 @@ int rtfhe_ctx_memory_bytes(const rtfhe_ctx* ctx, int d, size_t* bytes) {
     for (const auto& kv : c->tlwe1) b += kv.second.cap * ((size_t)c->p.N + 1) * 4;
     b += c->cap_a + c->cap_b + c->cap_c;
     for (const auto& kv : c->mux) b += 2 * kv.second.cap;
+    for (const rtfhe_mbk* k : c->mbks) b += k->bytes;
     *bytes = b;
     return 0;
 }
@@ -357,6 +358,7 @@ void rtfhe_ctx_destroy(rtfhe_ctx* ctx) {
     orphan_all(ctx->pack_keys, packing_key_release);
     orphan_all(ctx->plains, plain_release);
     orphan_all(ctx->denses, dense_release);
+    orphan_all(ctx->mbks, mbk_release);
     for (rtfhe_ctx* peer : ctx->peers) rtfhe_ctx_destroy(peer);
     ctx->peers.clear();
     (void)hipSetDevice(ctx->device);

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "rtfhe_encrypt.hpp"
+#include "rtfhe_mb_plan.h"
 
 namespace {
 
@@ -29,6 +30,25 @@ int keygen_material(const rtfhe_params* p, const Source& src, const int32_t* key
         striped(src, 1, root_word(src, 1), 0x9e3779b97f4a7c15ull, p->n,
                 [&](Rng& r, int i) { trgsw_rows(r, DRAWN, 0, p, key1, BitShare(p, key0[i]), bk + (size_t)i * trgsw, nullptr); });
     if (ksk) ksk_keygen(p, src, DRAWN, key0, key1, ksk);
+    return 0;
+}
+
+// The multi-bit bootstrapping key (include/rtfhe.h: rtfhe_mbk_keygen): key0's bits in groups of g, group t = bits [t g, min(n, t g + g)); a group
+// of g' bits holds a TRGSW sample under key1 for every non-empty subset j = 1 .. 2^g' - 1 of its bits (bit q of j = bit t g + q of the key), a
+// sample of the constant  prod_{q in j} s_q  prod_{q not in j} (1 - s_q)  -- exactly one of them 1, unless every bit of the group is 0.  Each is
+// a bootstrapping-key entry in everything else: the same gadget, the same noise, the same rows from the encryptor core.  Groups in order, j
+// ascending; one generator per sample (secure: ChaCha domain 5).
+int mbk_material(const rtfhe_params* p, const Source& src, int32_t g, const int32_t* key0, const int32_t* key1, uint32_t* out) {
+    const int64_t total = rtfhe_mb_trgsw_count(p->n, g);
+    if (total < 0 || total > 0x7fffffff || !binary(key0, p->n) || !binary(key1, p->N)) return RTFHE_ERR_INVALID;
+    const size_t trgsw = (size_t)2 * 2 * p->l * p->N;
+    const int J = (1 << g) - 1, full = p->n / g;
+    striped(src, 5, root_word(src, 4), 0xda942042e4dd58b5ull, (int)total, [&](Rng& r, int e) {
+        const int t = e < full * J ? e / J : full, j = e - t * J + 1, bits = t < full ? g : p->n % g;
+        int32_t mu = 1;
+        for (int q = 0; q < bits; q++) mu &= ((j >> q) & 1) ? key0[t * g + q] : 1 - key0[t * g + q];
+        trgsw_rows(r, DRAWN, 0, p, key1, BitShare(p, mu), out + (size_t)e * trgsw, nullptr);
+    });
     return 0;
 }
 
@@ -142,7 +162,17 @@ int rtfhe_packing_keygen(const rtfhe_params* p, const int32_t* key0, const int32
     return production_source(nullptr, [&](const Source& src) { return packing_key(p, src, key0, key1, pk); });
 }
 
+int rtfhe_mbk_keygen(const rtfhe_params* p, int32_t g, const int32_t* key0, const int32_t* key1, uint32_t* out) {
+    if (!valid(p) || !key0 || !key1 || !out) return RTFHE_ERR_INVALID;
+    return production_source(nullptr, [&](const Source& src) { return mbk_material(p, src, g, key0, key1, out); });
+}
+
 // ---- TEST ONLY: reproducible from a 64-bit seed (xoshiro256**, not a CSPRNG) ----
+int rtfhe_mbk_keygen_deterministic(const rtfhe_params* p, uint64_t seed, int32_t g, const int32_t* key0, const int32_t* key1, uint32_t* out) {
+    if (!valid(p) || !key0 || !key1 || !out) return RTFHE_ERR_INVALID;
+    return mbk_material(p, Source::from_seed(seed), g, key0, key1, out);
+}
+
 int rtfhe_packing_keygen_deterministic(const rtfhe_params* p, uint64_t seed, const int32_t* key0, const int32_t* key1, uint32_t* pk) {
     if (!valid(p) || !key0 || !key1 || !pk) return RTFHE_ERR_INVALID;
     return packing_key(p, Source::from_seed(seed), key0, key1, pk);

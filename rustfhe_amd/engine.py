@@ -334,6 +334,27 @@ class Engine(_Handle):
         self._ck(self.L.rtfhe_pbs_batch_dev(self.h, lut.h, self._dev(d_lut_idx), self._dev(d_tlwe), self._dev(d_out), count,
                                             _stream(stream)))
 
+    # ---- multi-bit blind rotation (include/rtfhe.h: rtfhe_mbk_create, rtfhe_pbs_mb_batch[_dev]) ----------------------------------------------
+    def multibit_key(self, words, g):
+        """Uploads a multi-bit bootstrapping key (rustfhe_amd.mbk_keygen at the same g) to the primary device as spectra; a MultibitKey handle,
+        closed by close() or a with block."""
+        return MultibitKey(self, words, g)
+
+    def pbs_mb_batch(self, mbk, lut, tlwe, lut_idx=None):
+        """pbs_batch through the multi-bit blind rotation: ceil(n / g) dependent steps instead of n, g the key's.  Plain tables only.  The outputs
+        decrypt like pbs_batch's; their words differ.  Indices are checked here: a bad one raises RtfheError before anything runs."""
+        tlwe = _np(tlwe, np.uint32).reshape(-1, self.p.n + 1)
+        idx = None if lut_idx is None else _np(lut_idx, np.int32).reshape(-1)
+        assert idx is None or idx.size == tlwe.shape[0], "one table index per ciphertext"
+        out = np.empty_like(tlwe)
+        self._ck(self.L.rtfhe_pbs_mb_batch(self.h, mbk.h, lut.h, _ptr(idx), _ptr(tlwe), _ptr(out), tlwe.shape[0]))
+        return out
+
+    def pbs_mb_batch_dev(self, mbk, lut, d_tlwe, d_out, count, d_lut_idx=None, stream=None):
+        """... on device buffers (d_lut_idx: int32[count] on the device or None), asynchronous on `stream`; a gate with a bad index is skipped and
+        the next sync() raises.  Inside a stream capture it allocates nothing and needs no earlier call on the stream."""
+        self._ck(self.L.rtfhe_pbs_mb_batch_dev(self.h, mbk.h, lut.h, self._dev(d_lut_idx), self._dev(d_tlwe), self._dev(d_out), count, _stream(stream)))
+
     def pbs_many_batch(self, lut, tlwe, n_out, lut_idx=None):
         """Many-LUT PBS (include/rtfhe.h: rtfhe_pbs_many_batch): n_out (1, 2, 4 or 8) functions of each ciphertext from ONE blind rotation,
         u32[count][n_out][n+1].  Tables interleave the functions (rustfhe_amd.many_lut_polynomial); indices are checked as in pbs_batch."""
@@ -872,6 +893,20 @@ class PackingKey(_Handle):
         else:
             assert pk.size == packing_key_words(p), "pk must be u32[n][t][base-1][2][N]"
             engine._ck(engine.L.rtfhe_packing_key_create(engine.h, _ptr(pk), C.byref(h)))
+        self.h = h
+
+
+class MultibitKey(_Handle):
+    """A multi-bit bootstrapping key on an Engine's primary device (rtfhe_mbk), kept as spectra.  Closing it frees the device copy; one whose
+    Engine was closed first only frees its handle."""
+
+    def __init__(self, engine, words, g):
+        words = _np(words, np.uint32).reshape(-1)
+        self.engine, self._destroy, self.g = engine, engine.L.rtfhe_mbk_destroy, int(g)
+        need = engine.L.rtfhe_mbk_words(C.byref(engine.p), int(g))
+        assert need == 0 or words.size == need, "words must be u32[n_trgsw][2][2l][N] of this g (rustfhe_amd.mbk_keygen)"
+        h = C.c_void_p()
+        engine._ck(engine.L.rtfhe_mbk_create(engine.h, _ptr(words), int(g), C.byref(h)))
         self.h = h
 
 
