@@ -37,6 +37,7 @@ pub enum rtfhe_packing_key {}
 pub enum rtfhe_mbk {}
 pub enum rtfhe_plain {}
 pub enum rtfhe_dense {}
+pub enum rtfhe_trlwe_ksk {}
 pub enum rtfhe_fft_plan {}
 
 pub const RTFHE_NAND: c_int = 0;
@@ -209,6 +210,19 @@ extern "C" {
                                        accumulate: c_int, out: *mut u32, count: usize) -> c_int;
     pub fn rtfhe_trlwe_mul_trgsw_batch_dev(ctx: *mut rtfhe_ctx, sel: *const rtfhe_trgsw, d_s_idx: *const c_void, d_x: *const c_void, n_x: i32,
                                            d_x_idx: *const c_void, K: i32, accumulate: c_int, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
+    // TRLWE key switching: a program of 1 ..= 16 steps on every row, step k = sigma_t (X -> X^t, t = t[entry[k]]) followed by the key switch with
+    // entry entry[k] of the switching key, replacing the row or (add[k] = 1) added into it; entry / add HOST arrays in both forms (add null: all
+    // replace); words [n_t][l][2][N], t [n_t] distinct odd exponents in [1, 2N); d_out may be exactly d_x; FP64 mirror backend only, no key of the context
+    pub fn rtfhe_trlwe_ksk_keygen(p: *const rtfhe_params, key_from: *const i32, key_to: *const i32, t: *const i32, n_t: i32, out: *mut u32) -> c_int;
+    pub fn rtfhe_trlwe_ksk_keygen_deterministic(p: *const rtfhe_params, key_from: *const i32, key_to: *const i32, seed: u64, t: *const i32, n_t: i32,
+                                                out: *mut u32) -> c_int;
+    pub fn rtfhe_trlwe_automorphism(N: i32, t: i32, x: *const u32, out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trlwe_ksk_create(ctx: *mut rtfhe_ctx, words: *const u32, t: *const i32, n_t: i32, out: *mut *mut rtfhe_trlwe_ksk) -> c_int;
+    pub fn rtfhe_trlwe_ksk_destroy(key: *mut rtfhe_trlwe_ksk);
+    pub fn rtfhe_trlwe_auto_batch(ctx: *mut rtfhe_ctx, key: *const rtfhe_trlwe_ksk, entry: *const i32, add: *const i32, n_steps: i32, x: *const u32,
+                                  out: *mut u32, count: usize) -> c_int;
+    pub fn rtfhe_trlwe_auto_batch_dev(ctx: *mut rtfhe_ctx, key: *const rtfhe_trlwe_ksk, entry: *const i32, add: *const i32, n_steps: i32,
+                                      d_x: *const c_void, d_out: *mut c_void, count: usize, stream: *mut c_void) -> c_int;
     // lvl0 dense layers: out[g][o][c] = (accumulate ? out[g][o][c] : 0) + [c == n] bias[o] + sum_i W[o][i] x[g][i][c] mod 2^32, exact on every
     // backend; W [O][I] with every entry in -128 ..= 127; x [count][I][n+1], out [count][O][n+1]; bias a HOST array [O] or null in both forms
     pub fn rtfhe_dense_create(ctx: *mut rtfhe_ctx, W: *const i32, O: i32, I: i32, out: *mut *mut rtfhe_dense) -> c_int;

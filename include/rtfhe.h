@@ -57,6 +57,9 @@
  *                                    <- TRGSWRepF::cross (hom_nand/src/trgsw.rs:264-306) on caller-supplied TRGSW samples of small-integer polynomials
  *                                       (Crypto<i32> for TRGSW, trgsw.rs:118-138, with a polynomial in the bit's place), its fold-add carried over
  *                                       up to eight products per sample (the reference has the product, not the sum)
+ *   rtfhe_trlwe_ksk_keygen[_deterministic] / rtfhe_trlwe_ksk_create / rtfhe_trlwe_auto_batch[_dev] / rtfhe_trlwe_automorphism
+ *                                    <- TRGSWRepF::cross (hom_nand/src/trgsw.rs:264-306) with a switching key in the sample's place: the TRLWE -> TRLWE key
+ *                                       switch, for the automorphisms X -> X^t and for re-keying (the reference has the product, not the key switch)
  *   rtfhe_dense_create / rtfhe_tlwe_dense_batch[_dev]
  *                                    <- the Add / scalar multiples of TLWERep (hom_nand/src/tlwe.rs) carried over a whole integer matrix: the weighted sums of
  *                                       lvl0 ciphertexts in front of a bootstrap (the reference has the row operations, not the layer)
@@ -811,6 +814,56 @@ int rtfhe_trlwe_mul_trgsw_batch(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const in
 int rtfhe_trlwe_mul_trgsw_batch_dev(rtfhe_ctx *ctx, const rtfhe_trgsw *sel, const void *d_s_idx /* [count][K] or NULL */, const void *d_x /* [n_x][2][N] */,
                                     int32_t n_x, const void *d_x_idx /* [count][K] or NULL */, int32_t K, int accumulate,
                                     void *d_out /* [count][2][N] */, size_t count, void *stream);
+/* ---- TRLWE key switching: automorphisms X -> X^t and re-keying ----
+ * The automorphism sigma_t : X -> X^t (t odd) permutes a polynomial's coefficients with signs: coefficient j goes to j t mod 2N and is negated
+ * past N.  sigma_t(ct) decrypts under sigma_t(s); a TRLWE -> TRLWE key switch brings it back under s -- or, with t = 1 and two different keys,
+ * moves a row from one key to another.  Both are one primitive.
+ *
+ * A SWITCHING KEY for the exponents t[0 .. n_t) is u32[n_t][l][2][N]: row (e, j) is a TRLWE (b then a) under key_to whose phase is
+ * -sigma_{t[e]}(key_from) * 2^(32 - (j+1) bgbit), with noise alpha = 2^-25 (rtfhe_trlwe_ksk_keygen below).  key_from == key_to gives
+ * automorphism keys; t = 1 with two different keys gives a re-keying key; both at once is allowed.
+ *
+ * One STEP with entry e on a row x = (b, a), t = t[e]:
+ *
+ *   a' = sigma_t(a),  b' = sigma_t(b)                    sigma_t(p)[j t mod 2N mod N] = +-p[j], negated when j t mod 2N >= N; wrapping
+ *   sum_c = 0.0;  for j = 0 .. l-1:  sum_c = sum_c + hadamard(K[e].row(c, j), ifft_i32(digit_j(a')))          c = 0 (b), 1 (a)
+ *   y = (b' + fft_u32(sum_0),  fft_u32(sum_1))
+ *   x <- y   (replace)      or      x <- x + y   (add; wrapping)
+ *
+ * The blocks are those of rtfhe_external_product_batch on the FP64 mirror backend: the digits of the leveled decomposition in force when the
+ * call is made (rtfhe_set_leveled_decomposition), the reference's transforms, the unfused multiply-add with the rows in order j = 0 .. l-1, one
+ * inverse transform per polynomial with truncation toward zero -- exact, a single product stays below l * N * (Bg/2) * 2^31 < 2^49.  Both
+ * decompositions give the digits 0 for the word 0, so a step equals, word for word,
+ *
+ *   (sigma_t b, 0) + rtfhe_external_product_batch(T, (b := sigma_t a, a := 0))
+ *
+ * with T the TRGSW whose rows (c, h = b, j) are K[e]'s rows and whose rows (c, h = a, j) are zero.  If x decrypts to mu under key_from, a replace
+ * step decrypts to sigma_t(mu) under key_to, plus one gadget level of noise.  sigma_{N / 2^i + 1} added to the identity is the
+ * partial trace: it keeps every 2^(i+1)-th coefficient, doubled, and cancels the others.
+ *
+ * A call runs a PROGRAM of 1 .. 16 steps on every row of a batch: entry[k] and add[k] (NULL: every step replaces) are HOST arrays in both forms,
+ * shared by the batch and read before the call returns (they ride in the launch's arguments, as rot does for rtfhe_trgsw_rotate_batch).
+ *
+ * Parameters.
+ *   - Checked on the host before anything is allocated or launched, RTFHE_ERR_INVALID with a message: handle, entry and buffers non-null;
+ *     1 <= n_steps <= 16; every entry[k] in [0, n_t); every add[k] 0 or 1; count < 2^31; out is exactly x (in place) or shares no byte with it.
+ *     count == 0 returns 0.  At creation: words and t non-null, 1 <= n_t <= 64, every t odd and in [1, 2N), no exponent twice.
+ *
+ * Keys, backends and devices.  It needs no key of the context.  FP64 mirror backend only: on an exact backend the call returns
+ * RTFHE_ERR_INVALID and the context stays usable.  On an rtfhe_ctx_create_multi context it runs on the primary device.  Lifetime is
+ * rtfhe_trgsw's: the spectra (8 N bytes per polynomial) live on the primary device and go with the context if it is destroyed first; a call
+ * then returns RTFHE_ERR_STATE and rtfhe_trlwe_ksk_destroy only frees the handle.
+ *
+ * Scratch and captures.  The _dev form allocates nothing and is ONE launch, counted by rtfhe_timer_end: it may sit in a caller's stream
+ * capture first thing on a fresh stream (rtfhe_trlwe_ksk_create is synchronous and grants the kernel what it needs). */
+typedef struct rtfhe_trlwe_ksk rtfhe_trlwe_ksk;
+int rtfhe_trlwe_ksk_create(rtfhe_ctx *ctx, const uint32_t *words /* [n_t][l][2][N] */, const int32_t *t /* [n_t] */, int32_t n_t, rtfhe_trlwe_ksk **out);
+void rtfhe_trlwe_ksk_destroy(rtfhe_trlwe_ksk *key);
+int rtfhe_trlwe_auto_batch(rtfhe_ctx *ctx, const rtfhe_trlwe_ksk *key, const int32_t *entry /* [n_steps] */, const int32_t *add /* [n_steps] or NULL */,
+                           int32_t n_steps, const uint32_t *x /* [count][2][N] */, uint32_t *out /* [count][2][N], may be x */, size_t count);
+int rtfhe_trlwe_auto_batch_dev(rtfhe_ctx *ctx, const rtfhe_trlwe_ksk *key, const int32_t *entry /* HOST [n_steps] */,
+                               const int32_t *add /* HOST [n_steps] or NULL */, int32_t n_steps, const void *d_x /* [count][2][N] */,
+                               void *d_out /* [count][2][N], may be d_x */, size_t count, void *stream);
 /* ---- lvl0 dense layers: integer matrix x TLWE batch, the linear layer of the bootstrapped mode ----
  * A dense layer holds an integer matrix W, int32[O][I] with every entry in [-128, 127], as signed bytes in the matrix pipe's operand order,
  * built once at creation together with one correction word per output.  A call computes, for g in [0, count), o in [0, O), c = 0 .. n:
@@ -925,6 +978,15 @@ int rtfhe_trgsw_encrypt_bits(const rtfhe_params *p, const int32_t *key1, const u
  * order of the mask and noise draws: the encrypted weights of rtfhe_trlwe_mul_trgsw_batch, uploaded through rtfhe_trgsw_create. */
 int rtfhe_trgsw_encrypt_polys(const rtfhe_params *p, const int32_t *key1, const int32_t *mu /* [count][N] */,
                               uint32_t *out /* [count][2][2l][N] */, size_t count);
+/* The switching key of rtfhe_trlwe_auto_batch for the exponents t[n_t] (OS CSPRNG): row (e, j) a TRLWE under key_to [N] of the polynomial
+ * -sigma_{t[e]}(key_from) * 2^(32 - (j+1) bgbit), a zero encryption as the bootstrapping key's rows (noise alpha = 2^-25) plus that message.
+ * Refused with RTFHE_ERR_INVALID: a null argument, a key that is not binary, n_t outside [1, 64], a t that is even or outside [1, 2N), an
+ * exponent given twice.  key_from == key_to: automorphism keys; t = 1 and two keys: a re-keying key. */
+int rtfhe_trlwe_ksk_keygen(const rtfhe_params *p, const int32_t *key_from /* [N] */, const int32_t *key_to /* [N] */, const int32_t *t /* [n_t] */,
+                           int32_t n_t, uint32_t *out /* [n_t][l][2][N] */);
+/* sigma_t : X -> X^t on count polynomials of u32 coefficients, on the CPU: x[j] goes to out[j t mod 2N mod N], negated when j t mod 2N >= N.
+ * N a power of two, t odd and in [1, 2N); out may be exactly x.  For clients (sigma_t of a plaintext, of a key) and tests. */
+int rtfhe_trlwe_automorphism(int32_t N, int32_t t, const uint32_t *x /* [count][N] */, uint32_t *out /* [count][N] */, size_t count);
 /* the reference's KeySwitchingKey shape from the compact one: entries t = 1 .. base-1 of every level copied, entry t = base =
  * TLWE(base * s_i / 2^(basebit (l+1))) freshly encrypted as KeySwitchingKey::new fills it (hom_nand/src/tlwe.rs:252-274) */
 int rtfhe_ksk_expand_ref(const rtfhe_params *p, const int32_t *key0, const int32_t *key1,
@@ -948,6 +1010,8 @@ int rtfhe_trgsw_encrypt_bits_deterministic(const rtfhe_params *p, const int32_t 
 /* (with a constant polynomial mu = bit and the same seed: the words of rtfhe_trgsw_encrypt_bits_deterministic; trgsw.rs:118-138, 264-306) */
 int rtfhe_trgsw_encrypt_polys_deterministic(const rtfhe_params *p, const int32_t *key1, uint64_t seed, const int32_t *mu /* [count][N] */,
                                             uint32_t *out /* [count][2][2l][N] */, size_t count);
+int rtfhe_trlwe_ksk_keygen_deterministic(const rtfhe_params *p, const int32_t *key_from, const int32_t *key_to, uint64_t seed,
+                                         const int32_t *t /* [n_t] */, int32_t n_t, uint32_t *out /* [n_t][l][2][N] */);
 int rtfhe_tlwe_decrypt_bits(const rtfhe_params *p, const int32_t *key0, const uint32_t *in,
                             uint8_t *bits, size_t count);
 int rtfhe_tlwe_phase(const rtfhe_params *p, const int32_t *key0, const uint32_t *in, uint32_t *phase, size_t count);

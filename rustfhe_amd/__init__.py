@@ -8,8 +8,9 @@ from .client import (RtfheError, decrypt_bits, encrypt_bits, encrypt_lut, encryp
                      load_tlwe, mb_point_exponents, mb_roots, mbk_keygen, mbk_words, packing_keygen, phases, save_keys, save_tlwe, trlwe_phase,
                      encrypt_lut_seeded, encrypt_selectors_seeded, encrypt_trgsw_polys_seeded, mask_expand, packing_keygen_seeded, seeded_expand,
                      encrypt_bits_seeded, encrypt_torus_seeded, keygen_seeded, ksk_keygen_seeded, tlwe_mask_expand, tlwe_seeded_expand,
-                     compressed_words, read_compressed, tlwe_compress, tlwe_expand, trlwe_compress, trlwe_expand, write_compressed)
-from .engine import Dense, Engine, FftPlan, Lut, MultibitKey, PackingKey, PlainPolys, Selectors, demux_level_selector, device_link, pinned_empty, shard_range  # noqa: F401
+                     compressed_words, read_compressed, tlwe_compress, tlwe_expand, trlwe_compress, trlwe_expand, write_compressed,
+                     trace_exponents, trlwe_automorphism, trlwe_ksk_keygen)
+from .engine import Dense, Engine, FftPlan, Lut, MultibitKey, PackingKey, PlainPolys, Selectors, TrlweSwitchKey, demux_level_selector, device_link, pinned_empty, shard_range  # noqa: F401
 from .pbs import decode_msgs, encode_msgs, lut_pack_layout, lut_polynomial, many_lut_polynomial  # noqa: F401
 from .lut_circuit import LutCircuitRunner, LutNetlist, lut_ripple_adder  # noqa: F401
 from .linear import dense_bias, dense_layer_bias, dense_layer_input, dense_layer_polys, dense_layer_trgsw  # noqa: F401
@@ -23,4 +24,5 @@ __all__ = ["Engine", "FftPlan", "Params", "RtfheError", "keygen", "ksk_expand_re
            "tlwe_mask_expand", "tlwe_seeded_expand", "encrypt_bits_seeded", "encrypt_torus_seeded", "ksk_keygen_seeded", "keygen_seeded",
            "compressed_words", "tlwe_compress", "tlwe_expand", "trlwe_compress", "trlwe_expand", "write_compressed", "read_compressed",
            "MultibitKey", "mbk_keygen", "mbk_words", "mb_roots", "mb_point_exponents",
+           "TrlweSwitchKey", "trlwe_ksk_keygen", "trlwe_automorphism", "trace_exponents",
            "NAND", "AND", "OR", "XOR", "NOT", "COPY", "ANDNY", "load"]

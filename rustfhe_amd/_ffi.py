@@ -150,6 +150,13 @@ _SIGNATURES = {
     "rtfhe_trlwe_mul_trgsw_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_size_t]),
     "rtfhe_trlwe_mul_trgsw_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_size_t,
                                                   C.c_void_p]),
+    "rtfhe_trlwe_ksk_keygen": (C.c_int, ["PP", C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rtfhe_trlwe_ksk_keygen_deterministic": (C.c_int, ["PP", C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rtfhe_trlwe_automorphism": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rtfhe_trlwe_ksk_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "rtfhe_trlwe_ksk_destroy": (None, [C.c_void_p]),
+    "rtfhe_trlwe_auto_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rtfhe_trlwe_auto_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtfhe_dense_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "rtfhe_dense_destroy": (None, [C.c_void_p]),
     "rtfhe_tlwe_dense_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),

@@ -16,9 +16,9 @@ OBJ = os.path.join(HERE, "..", "build", "obj")
 # device code lives in the .hip units (every kernel is instantiated in exactly one of them); the .cpp units are host-only
 HIP_SOURCES = ["rtfhe_dispatch_fft.hip", "rtfhe_dispatch_ntt.hip", "rtfhe_dispatch_xfft.hip", "rtfhe_stages.hip", "rtfhe_context.hip", "rtfhe_twiddles.hip",
                "rtfhe_batch.hip", "rtfhe_lut.hip", "rtfhe_circuit.hip", "rtfhe_multi.hip", "rtfhe_cmux_tree.hip", "rtfhe_cmux_net.hip", "rtfhe_pack.hip", "rtfhe_extract.hip", "rtfhe_plain.hip",
-               "rtfhe_trgsw_mac.hip", "rtfhe_seeded.hip", "rtfhe_dense.hip", "rtfhe_compress.hip", "rtfhe_pbs_mb.hip"]
+               "rtfhe_trgsw_mac.hip", "rtfhe_seeded.hip", "rtfhe_dense.hip", "rtfhe_compress.hip", "rtfhe_pbs_mb.hip", "rtfhe_trlwe_auto.hip"]
 CPP_SOURCES = ["rtfhe_keygen.cpp", "rtfhe_wire.cpp", "rtfhe_spqlios.cpp", "rtfhe_cmux_net_plan.cpp", "rtfhe_extract_plan.cpp", "rtfhe_plain_plan.cpp", "rtfhe_trgsw_mac_plan.cpp",
-               "rtfhe_seeded.cpp", "rtfhe_dense_plan.cpp", "rtfhe_compress_plan.cpp", "rtfhe_mb_plan.cpp"]
+               "rtfhe_seeded.cpp", "rtfhe_dense_plan.cpp", "rtfhe_compress_plan.cpp", "rtfhe_mb_plan.cpp", "rtfhe_trlwe_auto_plan.cpp"]
 SOURCES = HIP_SOURCES + CPP_SOURCES
 
 

@@ -95,6 +95,43 @@ def mbk_keygen(params, key0, key1, g, seed=None):
     return out
 
 
+def trlwe_ksk_keygen(params, key_from, key_to, t, seed=None):
+    """The TRLWE switching key from the lvl1 key key_from to the lvl1 key key_to for the exponents t (include/rtfhe.h:
+    rtfhe_trlwe_ksk_keygen): u32[n_t][l][2][N], row (e, j) a TRLWE under key_to of -sigma_{t[e]}(key_from) * 2^(32 - (j+1) bgbit) with
+    alpha = 2^-25.  key_from is key_to: automorphism keys; t = [1] with two keys: a re-keying key.  Engine.trlwe_switch_key uploads it.
+    seed None (production): OS CSPRNG; an integer seed = TEST-ONLY deterministic generation.  Refused: non-binary keys, more than 64 or no
+    exponents, an even t or one outside [1, 2N), an exponent given twice."""
+    key_from, key_to = _np(key_from, np.int32).reshape(-1), _np(key_to, np.int32).reshape(-1)
+    assert key_from.size == params.N and key_to.size == params.N
+    t = _np(t, np.int32).reshape(-1)
+    out = np.empty((t.size, params.l, 2, params.N), np.uint32)
+    _unseeded("rtfhe_trlwe_ksk_keygen", params, seed, 2, (_ptr(key_from), _ptr(key_to), _ptr(t), t.size, _ptr(out)),
+              " (non-binary key, or exponents that are not 1 .. 64 distinct odd numbers in [1, 2N))")
+    return out
+
+
+def trlwe_automorphism(x, t):
+    """sigma_t : X -> X^t on polynomials of u32 coefficients, on the CPU (rtfhe_trlwe_automorphism): x u32[..][N] -> the same shape, x[j] at
+    j t mod 2N mod N, negated when j t mod 2N >= N.  A TRLWE row u32[2][N] maps polynomial by polynomial; sigma_t of a plaintext is what a
+    replace step of Engine.trlwe_auto_batch makes of the row's message."""
+    x = _np(x, np.uint32)
+    N = x.shape[-1] if x.ndim else 0
+    out = np.empty_like(x)
+    rc = _ffi.load().rtfhe_trlwe_automorphism(int(N), int(t), _ptr(x), _ptr(out), x.size // N if N else 0)
+    if rc != 0:
+        raise RtfheError(rc, "rtfhe_trlwe_automorphism failed (N = %d not a power of two, or t = %d even or outside [1, 2N))" % (N, int(t)))
+    return out
+
+
+def trace_exponents(N, steps):
+    """The exponents of a partial trace of `steps` add steps: [N + 1, N/2 + 1, ...], step i being sigma_{N / 2^i + 1}.  After them exactly the
+    coefficients that are multiples of 2^steps survive, multiplied by 2^steps (Engine.trlwe_auto_batch with add = all ones)."""
+    N, steps = int(N), int(steps)
+    if not (N >= 2 and N & (N - 1) == 0 and 0 <= steps and (N >> steps) >= 1):
+        raise RtfheError(ERR_INVALID, "trace_exponents: N = %d must be a power of two and steps = %d within 0 .. log2 N" % (N, steps))
+    return [(N >> i) + 1 for i in range(steps)]
+
+
 def mb_roots(N):
     """The roots table of the multi-bit key combination (rtfhe_mb_roots): float64[2N][2], row t = (cos, sin) of pi t / N."""
     out = np.empty((2 * int(N) if 2 <= int(N) <= 1 << 20 else 1, 2), np.float64)      # (a refused N writes nothing)

@@ -359,6 +359,7 @@ void rtfhe_ctx_destroy(rtfhe_ctx* ctx) {
     orphan_all(ctx->plains, plain_release);
     orphan_all(ctx->denses, dense_release);
     orphan_all(ctx->mbks, mbk_release);
+    orphan_all(ctx->trlwe_ksks, trlwe_ksk_release);
     for (rtfhe_ctx* peer : ctx->peers) rtfhe_ctx_destroy(peer);
     ctx->peers.clear();
     (void)hipSetDevice(ctx->device);

@@ -38,6 +38,8 @@
 //   rtfhe_pbs_mb.hip         multi-bit blind rotation: multi-bit keys (spectra of 2^g - 1 TRGSW samples per group of g key bits, the roots table and
 //                            the point map beside them) and the programmable bootstrap over them, ceil(n / g) steps (its sizes, tables and argument
 //                            checks: rtfhe_mb_plan.cpp, host only)
+//   rtfhe_trlwe_auto.hip     TRLWE key switching: switching keys (rows of -sigma_t(key_from) times the gadget as spectra) and the automorphism /
+//                            re-keying programs over them, one launch of k_trlwe_auto (its argument checks: rtfhe_trlwe_auto_plan.cpp, host only)
 // Every kernel is instantiated in exactly one of them.  No CPU fallback anywhere: an entry point runs HIP kernels or fails.
 #pragma once
 
@@ -97,6 +99,7 @@ struct rtfhe_packing_key;
 struct rtfhe_plain;
 struct rtfhe_dense;
 struct rtfhe_mbk;
+struct rtfhe_trlwe_ksk;
 struct rtfhe_ctx {
     rtfhe_params p{};
     int device = 0;
@@ -178,13 +181,14 @@ struct rtfhe_ctx {
     std::vector<rtfhe_plain*> plains;      // live plain sets of this context: their spectra go with it, the handles stay
     std::vector<rtfhe_dense*> denses;      // live dense layers of this context: their matrices go with it, the handles stay
     std::vector<rtfhe_mbk*> mbks;          // live multi-bit keys of this context: their spectra go with it, the handles stay; counted by rtfhe_ctx_memory_bytes
+    std::vector<rtfhe_trlwe_ksk*> trlwe_ksks;      // live TRLWE switching keys of this context: their spectra go with it, the handles stay
     int num_cus = 256;
     int force_waves = 0;   // RTFHE_FORCE_WAVES=1|2|4|8: one kernel shape for every batch (the parity tests' second opinions)
     int wg_max = 512;      // RTFHE_WG_MAX_GATES: largest batch routed to the workgroup-per-gate kernel
     std::string err;
 };
 
-// The seven handle types below hang on their context by one rule.  `ctx` points back at it and the context lists the live handles of each type.
+// The eight handle types below hang on their context by one rule.  `ctx` points back at it and the context lists the live handles of each type.
 // A handle destroyed first detaches itself from that list (rtfhe_host::detach) and releases its device memory; a context destroyed first releases
 // the device memory of every listed handle and clears their `ctx` (rtfhe_host::orphan_all): the handle then only remains to be freed, and every
 // call made with it is refused by rtfhe_host::handles_ready.
@@ -255,6 +259,15 @@ struct rtfhe_mbk {
     int32_t* d_qmap = nullptr;          // [N/2] (rtfhe_mb_point_exponents)
     int32_t g = 0, n_trgsw = 0;
     size_t bytes = 0;                   // of the three together
+};
+
+// a TRLWE switching key (rtfhe_trlwe_ksk_create): the rows of every exponent as spectra on the primary device, with the exponents and the
+// inverses the kernel gathers by
+struct rtfhe_trlwe_ksk {
+    rtfhe_ctx* ctx = nullptr;
+    rtfhe::cplx* d_spec = nullptr;      // [n_t][l][2][R][64]: row j of entry e as (b, a) (rtfhe_kernels_trlwe_auto.hpp)
+    int32_t n_t = 0;
+    int32_t t[64] = {}, tinv[64] = {};  // t[e], and t[e]^-1 mod 2N
 };
 
 namespace rtfhe_host {
@@ -341,6 +354,7 @@ void packing_key_release(rtfhe_packing_key* k);                           // fre
 void plain_release(rtfhe_plain* w);                                       // frees a plain set's spectra (rtfhe_plain.hip)
 void dense_release(rtfhe_dense* w);                                       // frees a dense layer's matrix and correction words (rtfhe_dense.hip)
 void mbk_release(rtfhe_mbk* k);                                           // frees a multi-bit key's spectra and tables (rtfhe_pbs_mb.hip)
+void trlwe_ksk_release(rtfhe_trlwe_ksk* k);                               // frees a TRLWE switching key's spectra (rtfhe_trlwe_auto.hip)
 int prime_trgsw_mac(rtfhe_ctx* ctx);                                      // grants the TRLWE x TRGSW product's twins their LDS (rtfhe_trgsw_mac.hip)
 // ---- seeded ciphertexts (rtfhe_seeded.hip; the checks themselves: rtfhe_seeded.cpp, host only) ----
 // rtfhe_seeded_plan at the context's N with its refusal as the context's error (what: RTFHE_SEEDED_DEVICE / _UPLOAD of rtfhe_seeded_plan.h)
@@ -364,6 +378,7 @@ inline HandleRef ref(const rtfhe_packing_key* h) { return {"packing key", "rtfhe
 inline HandleRef ref(const rtfhe_plain* h) { return {"plain set", "rtfhe_plain", h != nullptr, h ? h->ctx : nullptr}; }
 inline HandleRef ref(const rtfhe_dense* h) { return {"dense layer", "rtfhe_dense", h != nullptr, h ? h->ctx : nullptr}; }
 inline HandleRef ref(const rtfhe_mbk* h) { return {"multi-bit key", "rtfhe_mbk", h != nullptr, h ? h->ctx : nullptr}; }
+inline HandleRef ref(const rtfhe_trlwe_ksk* h) { return {"switching key", "rtfhe_trlwe_ksk", h != nullptr, h ? h->ctx : nullptr}; }
 // The ownership check of the one or two handles of a call made on ctx (a call made through a handle alone passes that handle's own context,
 // null for a null handle): first every null one (RTFHE_ERR_INVALID "null NOUN (TYPE)"), then every one whose context is gone (RTFHE_ERR_STATE),
 // then every one of another context (RTFHE_ERR_INVALID).
@@ -402,7 +417,7 @@ int handle_publish(std::vector<H*>& live, NewHandle<H> h, H** out) {
     *out = h.release();
     return 0;
 }
-// THE body of the six rtfhe_*_destroy: a handle still attached leaves its context's list and, after before(ctx) -- what has to happen while its
+// THE body of the seven rtfhe_*_destroy: a handle still attached leaves its context's list and, after before(ctx) -- what has to happen while its
 // device memory still stands --, releases that memory; then it is freed
 template <typename H, typename Before>
 void handle_destroy(std::vector<H*> rtfhe_ctx::*live, H* h, void (*release)(H*), Before before) {

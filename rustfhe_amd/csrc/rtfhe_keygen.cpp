@@ -14,6 +14,7 @@
 
 #include "rtfhe_encrypt.hpp"
 #include "rtfhe_mb_plan.h"
+#include "rtfhe_trlwe_auto_plan.h"
 
 namespace {
 
@@ -48,6 +49,25 @@ int mbk_material(const rtfhe_params* p, const Source& src, int32_t g, const int3
         int32_t mu = 1;
         for (int q = 0; q < bits; q++) mu &= ((j >> q) & 1) ? key0[t * g + q] : 1 - key0[t * g + q];
         trgsw_rows(r, DRAWN, 0, p, key1, BitShare(p, mu), out + (size_t)e * trgsw, nullptr);
+    });
+    return 0;
+}
+
+// The TRLWE switching key (include/rtfhe.h: rtfhe_trlwe_ksk_keygen): entry e holds, for every gadget position j, a TRLWE row under key_to of
+// -sigma_{t[e]}(key_from) * 2^(32 - (j+1) bgbit) -- a zero encryption from the encryptor core, as a bootstrapping-key row, plus that message on b.
+// Entries in order, j ascending; one generator per entry (secure: ChaCha domain 6).  The exponent rules: rtfhe_trlwe_auto_exponents_bad (rtfhe_trlwe_auto_plan.h).
+int trlwe_ksk_material(const rtfhe_params* p, const Source& src, const int32_t* key_from, const int32_t* key_to, const int32_t* t, int32_t n_t, uint32_t* out) {
+    if (rtfhe_trlwe_auto_exponents_bad(p->N, t, n_t) || !binary(key_from, p->N) || !binary(key_to, p->N)) return RTFHE_ERR_INVALID;
+    const int N = p->N;
+    striped(src, 6, root_word(src, 5), 0xa0761d6478bd642full, n_t, [&](Rng& r, int e) {
+        std::vector<uint32_t> k((size_t)N), s((size_t)N);
+        for (int c = 0; c < N; c++) k[c] = (uint32_t)key_from[c];
+        rtfhe_trlwe_auto_permute(N, t[e], k.data(), s.data());      // sigma_t(key_from): +-1 and 0 as wrapping words
+        uint32_t* rows = out + (size_t)e * p->l * 2 * N;
+        for (int j = 0; j < p->l; j++) {
+            uint32_t* b = trlwe_row(r, DRAWN, (uint64_t)j, N, key_to, false, rows, nullptr);
+            for (int c = 0; c < N; c++) b[c] -= s[c] << (32 - (j + 1) * p->bgbit);
+        }
     });
     return 0;
 }
@@ -167,7 +187,30 @@ int rtfhe_mbk_keygen(const rtfhe_params* p, int32_t g, const int32_t* key0, cons
     return production_source(nullptr, [&](const Source& src) { return mbk_material(p, src, g, key0, key1, out); });
 }
 
+int rtfhe_trlwe_ksk_keygen(const rtfhe_params* p, const int32_t* key_from, const int32_t* key_to, const int32_t* t, int32_t n_t, uint32_t* out) {
+    if (!valid(p) || !key_from || !key_to || !t || !out) return RTFHE_ERR_INVALID;
+    return production_source(nullptr, [&](const Source& src) { return trlwe_ksk_material(p, src, key_from, key_to, t, n_t, out); });
+}
+
+// sigma_t on count polynomials: coefficient j goes to j t mod 2N, negated past N (the permutation the switching key's messages are made with,
+// rtfhe_trlwe_auto_plan.h).  `x` may be exactly `out`.
+int rtfhe_trlwe_automorphism(int32_t N, int32_t t, const uint32_t* x, uint32_t* out, size_t count) {
+    if (!x || !out || !rtfhe_trlwe_auto_ring_ok(N) || !rtfhe_trlwe_auto_exponent_ok(N, t)) return RTFHE_ERR_INVALID;
+    std::vector<uint32_t> tmp((size_t)N);
+    for (size_t g = 0; g < count; g++) {
+        rtfhe_trlwe_auto_permute(N, t, x + g * (size_t)N, tmp.data());
+        std::memcpy(out + g * (size_t)N, tmp.data(), (size_t)N * sizeof(uint32_t));
+    }
+    return 0;
+}
+
 // ---- TEST ONLY: reproducible from a 64-bit seed (xoshiro256**, not a CSPRNG) ----
+int rtfhe_trlwe_ksk_keygen_deterministic(const rtfhe_params* p, const int32_t* key_from, const int32_t* key_to, uint64_t seed, const int32_t* t, int32_t n_t,
+                                         uint32_t* out) {
+    if (!valid(p) || !key_from || !key_to || !t || !out) return RTFHE_ERR_INVALID;
+    return trlwe_ksk_material(p, Source::from_seed(seed), key_from, key_to, t, n_t, out);
+}
+
 int rtfhe_mbk_keygen_deterministic(const rtfhe_params* p, uint64_t seed, int32_t g, const int32_t* key0, const int32_t* key1, uint32_t* out) {
     if (!valid(p) || !key0 || !key1 || !out) return RTFHE_ERR_INVALID;
     return mbk_material(p, Source::from_seed(seed), g, key0, key1, out);

@@ -722,6 +722,39 @@ class Engine(_Handle):
         self._ck(self.L.rtfhe_trlwe_mul_trgsw_batch_dev(self.h, sel.h, self._dev(d_s_idx), self._dev(d_x), int(n_x), self._dev(d_x_idx), int(K),
                                                         1 if accumulate else 0, self._dev(d_out), count, _stream(stream)))
 
+    # ---- TRLWE key switching (include/rtfhe.h: rtfhe_trlwe_ksk_create, rtfhe_trlwe_auto_batch[_dev]) ------------------------------------------------
+    def trlwe_switch_key(self, words, t):
+        """Keeps a TRLWE switching key (client.trlwe_ksk_keygen: u32[n_t][l][2][N]) for the exponents t as spectra on the primary device; a
+        TrlweSwitchKey handle (.t, the exponents; .n entries), closed by close() or a with block.  Needs no key of the context."""
+        return TrlweSwitchKey(self, words, t)
+
+    @staticmethod
+    def _program(entry, add):
+        entry = _np(entry, np.int32).reshape(-1)
+        add = None if add is None else _np(add, np.int32).reshape(-1)
+        if add is not None and add.size != entry.size:
+            raise RtfheError(ERR_INVALID, "add has %d flags for %d steps" % (add.size, entry.size))
+        return entry, add
+
+    def trlwe_auto_batch(self, key, x, entry, add=None):
+        """Runs the program on every TRLWE row of x (u32[count][2][N]) and returns the rows: step k applies sigma_t and the key switch of entry
+        entry[k] of `key` (t = key.t[entry[k]]) and replaces the row with the result, or adds the result into it where add[k] is 1 (add None:
+        every step replaces).  1 .. 16 steps, shared by the batch.  A row that decrypts to mu under key_from then decrypts to sigma_t(mu) under
+        key_to; t = 1 is a plain re-keying.  FP64 mirror backend, in the leveled decomposition in force now.  Arguments are checked here: a bad
+        one raises RtfheError before anything runs."""
+        x = _np(x, np.uint32).reshape(-1, 2, self.p.N)
+        entry, add = self._program(entry, add)
+        out = np.empty_like(x)
+        self._ck(self.L.rtfhe_trlwe_auto_batch(self.h, key.h, _ptr(entry), _ptr(add), entry.size, _ptr(x), _ptr(out), x.shape[0]))
+        return out
+
+    def trlwe_auto_batch_dev(self, key, d_x, d_out, count, entry, add=None, stream=None):
+        """... on device buffers (d_x, d_out: [count][2][N] words; d_out may be d_x itself, a partial overlap is refused), asynchronous on
+        `stream`.  entry / add are host lists and are read before the call returns.  One launch, nothing allocated: it may be captured first
+        thing on a fresh stream."""
+        entry, add = self._program(entry, add)
+        self._ck(self.L.rtfhe_trlwe_auto_batch_dev(self.h, key.h, _ptr(entry), _ptr(add), entry.size, self._dev(d_x), self._dev(d_out), count, _stream(stream)))
+
     # ---- lvl0 dense layers (include/rtfhe.h: rtfhe_dense_create, rtfhe_tlwe_dense_batch[_dev]) -------------------------------------------------------
     def dense(self, W):
         """Keeps an integer matrix int[O][I], every entry in [-128, 127], on the primary device in the matrix pipe's operand order; a Dense
@@ -907,6 +940,21 @@ class MultibitKey(_Handle):
         assert need == 0 or words.size == need, "words must be u32[n_trgsw][2][2l][N] of this g (rustfhe_amd.mbk_keygen)"
         h = C.c_void_p()
         engine._ck(engine.L.rtfhe_mbk_create(engine.h, _ptr(words), int(g), C.byref(h)))
+        self.h = h
+
+
+class TrlweSwitchKey(_Handle):
+    """A TRLWE switching key on an Engine's primary device (rtfhe_trlwe_ksk), kept as spectra: the key of Engine.trlwe_auto_batch[_dev].
+    Closing it frees the device copy; one whose Engine was closed first only frees its handle."""
+
+    def __init__(self, engine, words, t):
+        self.t = [int(v) for v in np.asarray(t).reshape(-1)]
+        self.n = len(self.t)
+        words = _np(words, np.uint32).reshape(-1)
+        self.engine, self._destroy = engine, engine.L.rtfhe_trlwe_ksk_destroy
+        assert words.size == self.n * engine.p.l * 2 * engine.p.N, "words must be u32[n_t][l][2][N] (rustfhe_amd.trlwe_ksk_keygen)"
+        h = C.c_void_p()
+        engine._ck(engine.L.rtfhe_trlwe_ksk_create(engine.h, _ptr(words), _ptr(_np(self.t, np.int32)), self.n, C.byref(h)))
         self.h = h
 
 
