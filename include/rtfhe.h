@@ -1254,8 +1254,8 @@ int rtfhe_compressed_read(const char *path, int32_t *coef /* [P] */, uint32_t *w
  * rtfhe_mbk_destroy only frees the handle.  The bootstrapping key itself is not needed; the key-switching key is.
  *
  * The calls follow rtfhe_pbs_batch[_dev]: plain tables from rtfhe_lut_create (an encrypted one: RTFHE_ERR_INVALID), lut_idx NULL = table 0,
- * indices checked on the host before anything is launched / on the device (a gate with a bad index is skipped, its output row is not a valid
- * ciphertext, and the next rtfhe_sync returns RTFHE_ERR_INVALID); every check happens before any launch; the FP64 mirror backend only
+ * indices checked on the host before anything is launched / on the device (a gate with a bad index is skipped, its output row keeps the
+ * bytes it had on both routes to the key switch, and the next rtfhe_sync returns RTFHE_ERR_INVALID once); every check happens before any launch; the FP64 mirror backend only
  * (the exact backends: RTFHE_ERR_INVALID, the context stays usable); N = 1024 and 2048.  On a multi-device context the batch runs on the primary.
  * Inside a stream capture rtfhe_pbs_mb_batch_dev allocates nothing and needs no earlier call on the stream: there, and in a context without
  * the matrix form of the key-switching key (RTFHE_KS_MM_MIN=0), the kernel switches keys itself; otherwise the samples go through the stream's

@@ -48,6 +48,17 @@ __device__ __forceinline__ int mb_exponent(int j, int r0, int r1, int r2, int ma
     return (((j & 1) ? r0 : 0) + ((j & 2) ? r1 : 0) + ((j & 4) ? r2 : 0)) & mask;
 }
 
+// A skipped gate (table index out of range) in the extract form: the batch key switch behind the kernel writes every row (k_key_switch_mm adds
+// into a zeroed output), so the gate's threads park the n + 1 <= N words of its output row in the gate's own, otherwise unused, sample slots and
+// k_pbs_mb_restore, launched behind the key switch, puts them back (k_trgsw_rotate's rule, rtfhe_kernels_trgsw_rotate.hpp).  In the fused form
+// nothing is stored and the row keeps its words anyway.  This thread moves words t0, t0 + stride, ... <= n.
+template <int N>
+__device__ __forceinline__ void mb_park_row(const PbsMbArgs& a, int g, int t0, int stride) {
+    if (!a.ext) return;
+    const uint32_t* keep = a.out + (size_t)g * ((size_t)a.n + 1);
+    for (int c = t0; c <= a.n; c += stride) *ext_slot(a.ext, g, c, N) = keep[c];
+}
+
 // One multi-bit step on the wave-private accumulator in LDS.  group: the group's first TRGSW; J its subsets; r0 .. r2 its rotations (0 past
 // the group's bits); q: this lane's R point exponents.
 template <int LOGN, int L, int BGBIT, bool DUAL, bool ROUNDED>
@@ -174,7 +185,10 @@ __global__ __launch_bounds__(64 * MB_WAVES, 1) void k_pbs_mb(const PbsMbArgs a) 
     if (g >= a.count) return;
     const TvLut tvs{a.tv, a.tv_idx, a.n_tv, a.fault};
     const auto tv = tv_row(tvs, g, N);
-    if (!tv.ok()) return;      // skipped: nothing is stored, *fault is set
+    if (!tv.ok()) {            // skipped: the output row keeps its words, *fault is set
+        mb_park_row<N>(a, g, lane, 64);
+        return;
+    }
 
     unsigned char* wbase = smem + (size_t)TwStage<LOGN>::LDS_CPLX * sizeof(cplx) + (size_t)wave * bootstrap_wave_lds_bytes<LOGN>(a.npad, DUAL);
     double* xbuf = reinterpret_cast<double*>(wbase);
@@ -223,6 +237,18 @@ __global__ __launch_bounds__(64 * MB_WAVES, 1) void k_pbs_mb(const PbsMbArgs a) 
         return;
     }
     key_switch_wave<LOGN, MB_KS_T, MB_KS_BB, MB_KSQ>(accbuf + N, accbuf[0], a.ksk, a.ksw, n, io.out, lane);
+}
+
+// extract form, behind the batch key switch, for both kernel shapes: the output rows of skipped gates as they were before the call (a wave per
+// gate; the index is checked again, a good gate's wave returns at once).  Launched only where a.tv_idx and a.ext are given.
+template <int LOGN>
+__global__ __launch_bounds__(64 * MB_WAVES) void k_pbs_mb_restore(const PbsMbArgs a) {
+    constexpr int N = 1 << LOGN;
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * MB_WAVES + (threadIdx.x >> 6);
+    if (g >= a.count || (unsigned)a.tv_idx[g] < (unsigned)a.n_tv) return;
+    uint32_t* row = a.out + (size_t)g * ((size_t)a.n + 1);
+    for (int c = lane; c <= a.n; c += 64) row[c] = *ext_slot(a.ext, g, c, N);
 }
 
 }  // namespace rtfhe

@@ -40,7 +40,10 @@ __global__ __launch_bounds__(64 * MB_WG_WAVES, 1) void k_pbs_mb_wg(const PbsMbAr
     const int g = blockIdx.x;      // < count: the grid is count workgroups
     const TvLut tvs{a.tv, a.tv_idx, a.n_tv, a.fault};
     const auto tv = tv_row(tvs, g, N);
-    if (!tv.ok()) return;          // skipped, by all six waves alike: nothing is stored, *fault is set
+    if (!tv.ok()) {                // skipped, by all six waves alike: the output row keeps its words, *fault is set
+        mb_park_row<N>(a, g, tid, THREADS);
+        return;
+    }
 
     unsigned char* base = smem + ((size_t)TwStage<LOGN>::LDS_CPLX + 2 * N) * sizeof(cplx);
     double* xbuf = reinterpret_cast<double*>(base) + (size_t)wave * G::XSLOTS;

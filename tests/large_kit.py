@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE: what tests/test_gpu_large_buffers.py is written with -- device buffers past 2 GiB, 4 GiB and 8 GiB (DESIGN.md 6.2,
+"""TEST INFRASTRUCTURE: what tests/test_gpu_large_buffers.py (and its later siblings, tests/test_gpu_*_large.py) is written with -- device buffers past 2 GiB, 4 GiB and 8 GiB (DESIGN.md 6.2,
 "Address arithmetic").  torch is imported inside the functions, as in gpu_kit.py: the module imports without a GPU and its arithmetic half
 (boundaries, ks_segment, probe_items) is checked on the CPU by tests/test_large_plans_host.py.  Nothing here ever creates a large array on the
 host: the big buffers are made, filled, compared and probed on the device, and only the probe rows (a few hundred) come down."""
@@ -104,6 +104,35 @@ def same_as_chunks(call, inputs, out, count, chunk):
         assert torch.equal(d_chunk[:cnt * ow], d_out[off * ow:(off + cnt) * ow]), "items %d .. %d differ from the same call on a slice" % (off, off + cnt - 1)
         check_canary(d_chunk, chunk * ow)
     del d_chunk
+
+
+def _stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _tile_bytes(N):
+    return 16 * (N + 1) * 4           # 65,600 (N = 1024) or 131,136 (N = 2048) per tile of 16 samples
+
+
+def _split_path_taken(e, detail, samples, N, label, keys_only):
+    """The signs that the big call ran the batch key switch in more than one segment.  keys_only: what a context with the same keys holds
+    before any batch (the slice calls' context, measured at the start).  The library does not report a segment count -- it counts the whole
+    batch key switch as one launch --, so the figure printed here is DERIVED from the kit's restatement of seg_max; the evidence is the three
+    assertions below and the mutant of profiles/r32/README.md."""
+    ms, ks_ms, launches = detail
+    held = report(label, e) - keys_only
+    print("[large] %s: %.1f ms on the device, %.2f ms of it in the batch key switch, %d launches, ceil(samples / seg_max) = %d (derived), scratch %.2f GB" %
+          (label, ms, ks_ms, launches, -(-samples // ks_segment(N)), held / 1e9))
+    assert ks_ms > 0, "the batch key switch (launch_key_switch_mm) did not run: the batch stayed on the fused kernel"
+    assert launches >= 2, "a blind-rotation launch and the batch key switch"
+    assert samples > ks_segment(N), "more than one key-switch segment"
+    assert held >= -(-samples // 16) * _tile_bytes(N) > 1 << 31, "the context's scratch beyond its keys holds the batch's samples, and they lie across 2^31 bytes"
+
+
+def _chunk_samples(N):
+    """samples of a slice call whose sample buffer stays below 2^30 bytes"""
+    return (1 << 30) // ((N + 1) * 4) // 1024 * 1024
 
 
 def report(name, eng=None):

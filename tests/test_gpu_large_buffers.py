@@ -28,17 +28,13 @@ import tlwe_seeded_oracle as tso
 import trgsw_mac_oracle as tmo
 from extract_helpers import extract_formula
 from kit import random_words
+from large_kit import _chunk_samples, _split_path_taken, _stream, _tile_bytes
 from leveled_oracle import as_trlwe, oracle_cmux_net, oracle_cmux_tree, oracle_demux_tree, oracle_trgsw_rotate
 from pbs_oracle import oracle_pbs_many
 
 pytestmark = pytest.mark.gpu
 
 IN_ROWS = 64          # input rows of the netlist wave's wire table
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
 
 
 class World:
@@ -62,30 +58,6 @@ class World:
 @pytest.fixture(scope="module")
 def worlds(orc):
     return gk.Worlds(lambda N, n: World(orc, N, n), close=lambda w: None)
-
-
-def _tile_bytes(N):
-    return 16 * (N + 1) * 4           # 65,600 (N = 1024) or 131,136 (N = 2048) per tile of 16 samples
-
-
-def _split_path_taken(e, detail, samples, N, label, keys_only):
-    """The signs that the big call ran the batch key switch in more than one segment.  keys_only: what a context with the same keys holds
-    before any batch (the slice calls' context, measured at the start).  The library does not report a segment count -- it counts the whole
-    batch key switch as one launch --, so the figure printed here is DERIVED from the kit's restatement of seg_max; the evidence is the three
-    assertions below and the mutant of profiles/r32/README.md."""
-    ms, ks_ms, launches = detail
-    held = lk.report(label, e) - keys_only
-    print("[large] %s: %.1f ms on the device, %.2f ms of it in the batch key switch, %d launches, ceil(samples / seg_max) = %d (derived), scratch %.2f GB" %
-          (label, ms, ks_ms, launches, -(-samples // lk.ks_segment(N)), held / 1e9))
-    assert ks_ms > 0, "the batch key switch (launch_key_switch_mm) did not run: the batch stayed on the fused kernel"
-    assert launches >= 2, "a blind-rotation launch and the batch key switch"
-    assert samples > lk.ks_segment(N), "more than one key-switch segment"
-    assert held >= -(-samples // 16) * _tile_bytes(N) > 1 << 31, "the context's scratch beyond its keys holds the batch's samples, and they lie across 2^31 bytes"
-
-
-def _chunk_samples(N):
-    """samples of a slice call whose sample buffer stays below 2^30 bytes"""
-    return (1 << 30) // ((N + 1) * 4) // 1024 * 1024
 
 
 # ---- 1-3: plain gate batches, the split path in two and three key-switch segments --------------------------------------------------------

@@ -18,50 +18,10 @@ import pytest
 import gpu_kit as gk
 from kit import random_words
 from lut_circuit_kit import adder_inputs, create, decode, host_compose, random_circuit, replay
+from mask_kit import FORCED, FORCED_MASKS, ORDER, Mask, _picks
 from pbs_oracle import oracle_pbs, oracle_pbs_enc, oracle_pbs_many
 
 pytestmark = pytest.mark.gpu
-
-MASKS = {1024: (1, 2, 63, 64, 639, 640, 767), 2048: (1, 63, 64, 703, 704, 767)}
-ALL = [(N, n) for N in (1024, 2048) for n in MASKS[N]]
-# small first: a carve or ring defect shows at n = 63 / 64 before the degenerate step counts and the long masks run
-ORDER = sorted(ALL, key=lambda m: (m[1] in (1, 2), m[1] > 64, m[0], m[1]))
-RANDOM_PICKS = 8
-
-
-def _picks(count, N, C, rng):
-    """first and last gate, the last gate before and the first after every segment boundary the dispatch can make at this size (multiples of
-    4C: whole rounds, and where the time-sliced launch starts; N = 2048 also multiples of 3C: the whole rounds of the longest masks), and
-    RANDOM_PICKS more drawn at random"""
-    s = {0, count - 1}
-    for per in ((4,) if N == 1024 else (3, 4)):
-        for b in range(per * C, count, per * C):
-            s |= {b - 1, b}
-    rest = np.setdiff1d(np.arange(count), sorted(s))
-    s |= set(rng.choice(rest, min(RANDOM_PICKS, rest.size), replace=False).tolist())
-    return sorted(s)
-
-
-class Mask:
-    def __init__(self, orc, N, n):
-        import rustfhe_amd as R
-        self.orc, self.N, self.n = orc, N, n
-        self.P = orc.Params(n=n, N=N)
-        self.K = orc.Keys(self.P, 7000 + N + n)
-        self.p = R.Params(n=n, N=N)
-        self.C = gk.cus()
-        self.e = gk.engine(R, self.p, self.K.bk_t, self.K.ksk)
-
-    def engine(self, monkeypatch=None, env=None):
-        import rustfhe_amd as R
-        return gk.engine(R, self.p, self.K.bk_t, self.K.ksk, monkeypatch, env)
-
-    def gates(self, op, c0, c1, backend=None):
-        orc, K = self.orc, self.K
-        if backend is None:
-            return orc.gate_batch_mt(self.P, op, K.bk_f, None, K.ksk, c0, c1, nthreads=gk.THREADS)[0]
-        return orc.gate_batch_mt(self.P, op, None, K.bk_t, K.ksk, c0, c1, nthreads=gk.THREADS, backend=backend)[0]
-
 
 @pytest.fixture(scope="module", params=ORDER, ids=lambda m: "N%d-n%d" % m)
 def mask(request, orc):
@@ -122,12 +82,6 @@ def test_blind_rotation_prefixes_at_the_edges_of_the_step_count(mask):
 
 
 # ---- every other shape against the default engine, whole batches ------------------------------------------------------------------------
-FORCED = {1024: [{"RTFHE_FORCE_WAVES": "1"}, {"RTFHE_FORCE_WAVES": "2"}, {"RTFHE_FORCE_WAVES": "4"}, {"RTFHE_FORCE_WAVES": "8"},
-                 {"RTFHE_PAIR4": "0"}, {"RTFHE_PAIR_RR": "0"}, {"RTFHE_KS_MM_MIN": "0"}],
-          2048: [{"RTFHE_FORCE_WAVES": "4"}, {"RTFHE_N2048_EO4": "0"}]}
-FORCED_MASKS = {1024: (1, 63, 64, 640, 767), 2048: (1, 63, 64, 704, 767)}
-
-
 def test_forced_shapes_equal_the_default_engine(mask, monkeypatch):
     """One engine per forced shape, same keys: gate_batch, pbs_batch, pbs_many_batch(n_out = 4) and the encrypted table give the default
     engine's words on whole batches.  Mask lengths: 1, 63, 64 and the largest of the ring (the required subset) plus the first n past the
