@@ -198,11 +198,9 @@ int launch_rotate(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const int32_t* d_sel_i
     for (int k = 0; k < depth; k++) a.rot[k] = rot ? rot[k] : 2 * ctx->p.N - (1 << k);      // NULL: X^{-2^k}
     if (int rc = launch_leveled(ctx, rotate_twins(ctx), count, s, a)) return rc;
     if (!extract) return 0;
-    // identity_key_switch of the count samples, as the tree's extract form does it; then the rows of skipped lookups as they were
-    if (int rc = launch_key_switch_rows(ctx, samples->d[0], (uint32_t*)d_out, count, s)) return rc;
-    const dim3 grid((unsigned)((count + LEVELED_WAVES - 1) / LEVELED_WAVES)), block(64 * LEVELED_WAVES);
-    return ctx->logn == 11 ? launch_kernel(ctx, k_trgsw_rotate_restore<11, LEVELED_WAVES>, grid, block, 0, s, a)
-                           : launch_kernel(ctx, k_trgsw_rotate_restore<10, LEVELED_WAVES>, grid, block, 0, s, a);
+    // identity_key_switch of the count samples, as the tree's extract form does it; then the rows of skipped lookups as they were (counted, and
+    // launched with a null sel_idx too: a rotation with extraction is three launches)
+    return launch_key_switch_rows_restore(ctx, samples->d[0], (uint32_t*)d_out, count, d_sel_idx, depth, sel->n_sel, true, s);
 }
 
 int rotate_dev(rtfhe_ctx* ctx, const rtfhe_trgsw* sel, const void* d_sel_idx, int32_t depth, const int32_t* rot, const void* d_trlwe, void* d_out, size_t count,

@@ -508,6 +508,11 @@ int launch_key_switch_ext(rtfhe_ctx* ctx, uint32_t* samples, uint32_t* d_out, si
 // `rows` samples into d_out [rows][n+1] -- without the matrix key _ext, else d_out zeroed (the K-slices add into it) and _mm
 // (zero_out = false: d_out is zero already -- a LUT circuit's key-switched buffer, which k_lut_scatter clears)
 int launch_key_switch_rows(rtfhe_ctx* ctx, uint32_t* samples, uint32_t* d_out, size_t rows, hipStream_t s, bool zero_out = true);
+// ... and behind it the rows of skipped items as they were before the call (k_rows_restore, rtfhe_kernels.hpp: the one parked-row rule): row g
+// was skipped when one of d_idx[g][0 .. per_row) lies outside [0, bound).  d_idx null: no row was skipped and nothing is launched -- unless the
+// launch is `counted` (what rtfhe_timer_end reports): an entry point's count does not depend on its arguments, its restore is launched regardless.
+int launch_key_switch_rows_restore(rtfhe_ctx* ctx, uint32_t* samples, uint32_t* d_out, size_t rows, const int32_t* d_idx, int32_t per_row, int32_t bound,
+                                   bool counted, hipStream_t s);
 
 // ---- batches (rtfhe_batch.hip) ----
 int launch_bootstrap(rtfhe_ctx* ctx, int op, int mode, int steps, const void* d_in0, const void* d_in1, void* d_out,

@@ -8,6 +8,9 @@
 //   negacyclic rotate        utils/src/math.rs:85-132
 //   sample extract           hom_nand/src/trlwe.rs:110-121
 //   identity key switch      hom_nand/src/tlwe.rs:43-73
+//
+// Stated ONCE here for every kernel family: the digit-row loop of the external product (rtfhe_body_digit_rows.hpp, included by cmux_step below,
+// mac_forward and auto_step) and the parked-row rule behind the batch key switch (park_row, k_rows_restore, beside ext_slot).
 #pragma once
 
 #include "rtfhe_device.hpp"
@@ -58,6 +61,40 @@ __device__ __forceinline__ uint32_t* ext_slot(uint32_t* ext, int g, int c, int N
     if (c == N) return tile + 16 * N + (g & 15);
     const int quarter = N >> 2, q = c / quarter, kk = c & (quarter - 1);
     return tile + ((((kk >> 2) * 64 + q * 16 + (g & 15)) << 2) | (kk & 3));
+}
+
+// The rule for an item that is skipped (an index out of range) in front of the batch key switch, stated once for every kernel family with an
+// extract form.  The key switch writes every output row (k_key_switch_mm adds into a zeroed output), but a skipped item's row must keep its
+// words: the item's threads PARK the row's n + 1 <= N words in the item's own, otherwise unused, sample slots (park_row; this thread moves
+// words t0, t0 + stride, ... <= n), and k_rows_restore, launched behind the key switch (launch_key_switch_rows_restore, rtfhe_stages.hip),
+// puts them back.  What the key switch makes of the parked words is overwritten.
+template <int N, typename A>
+__device__ __forceinline__ void park_row(const A& a, const uint32_t* out, int g, int t0, int stride) {      // a: the kernel's arguments, for a.ext and a.n
+    if (!a.ext) return;      // not the extract form: nothing is stored and the row keeps its words anyway
+    const uint32_t* keep = out + (size_t)g * ((size_t)a.n + 1);
+    for (int c = t0; c <= a.n; c += stride) *ext_slot(a.ext, g, c, N) = keep[c];
+}
+// A wave per row.  Row g was skipped when one of its per_row entries of idx lies outside [0, bound): the rule of the kernel that parked it,
+// checked again (the rotation: sel_idx, depth, n_sel; the multi-bit PBS: tv_idx, 1, n_tv).  idx null: no row was skipped.
+struct RowsRestoreArgs {
+    const int32_t* idx;      // [count][per_row]
+    uint32_t* ext;           // the sample buffer the rows were parked in (ext_slot); read only
+    uint32_t* out;           // [count][n+1], the key switch's output
+    int32_t count, per_row, bound, n;
+};
+constexpr int ROWS_RESTORE_WAVES = 4;
+template <int LOGN>
+__global__ __launch_bounds__(64 * ROWS_RESTORE_WAVES) void k_rows_restore(const RowsRestoreArgs a) {
+    constexpr int N = 1 << LOGN;
+    const int lane = threadIdx.x & 63;
+    const unsigned g = blockIdx.x * ROWS_RESTORE_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // wave-uniform; count + 3 < 2^32
+    if (g >= (unsigned)a.count || !a.idx) return;
+    const int32_t* idx = a.idx + (size_t)g * (unsigned)a.per_row;
+    bool ok = true;
+    for (int k = 0; k < a.per_row; k++) ok = ok && (unsigned)idx[k] < (unsigned)a.bound;
+    if (ok) return;
+    uint32_t* row = a.out + (size_t)g * (unsigned)(a.n + 1);
+    for (int c = lane; c <= a.n; c += 64) row[c] = *ext_slot(a.ext, (int)g, c, N);
 }
 
 // gate pre-step on one TLWE word (a-part: isb = false, b-part: isb = true), hom_nand/src/tfhe.rs:27-71
@@ -255,39 +292,9 @@ __device__ __forceinline__ void cmux_step(uint32_t* __restrict__ accbuf, int r, 
             const uint32_t d = CMUX ? (rotated_coef<LOGN>(poly, c, r) - own) : own;
             u[mm] = (d + MA) ^ MX;
         }
-#pragma unroll 1
-        for (int jj = 0; jj < L; jj++) {
-            const cplx* bkj = bk_i + (size_t)((h * L + jj) * 2) * R * 64 + lane;
-            double re[R], im[R];
-#pragma unroll
-            for (int m = 0; m < R; m++) {
-                re[m] = (double)decomp_digit(u[m], BGBIT, jj);
-                im[m] = (double)decomp_digit(u[R + m], BGBIT, jj);
-            }
-            fft_forward_a<LOGN, DUAL>(re, im, twf, xbuf, lane);
-            // the two BK rows of this digit are requested here, not earlier: their 64 VGPRs would otherwise be
-            // live through the whole transform; the last exchange + in-register pass cover the L2 latency
-            __builtin_amdgcn_sched_barrier(0);
-            cplx b0[R], b1[R];
-#pragma unroll
-            for (int m = 0; m < R; m++) { b0[m] = bkj[m * 64]; b1[m] = bkj[(R + m) * 64]; }
-            __builtin_amdgcn_sched_barrier(0);
-            fft_forward_b<LOGN, DUAL>(re, im, twf, xbuf, lane);
-            // hadamard + fold-add from zero, utils/src/spqlios.rs:204-222, hom_nand/src/trgsw.rs:290-299
-#pragma unroll
-            for (int m = 0; m < R; m++) {
-                {
-                    const double ii = b0[m].y * im[m], rr = b0[m].x * re[m], ri = b0[m].x * im[m], ir = b0[m].y * re[m];
-                    s0re[m] = s0re[m] + (rr - ii);
-                    s0im[m] = s0im[m] + (ir + ri);
-                }
-                {
-                    const double ii = b1[m].y * im[m], rr = b1[m].x * re[m], ri = b1[m].x * im[m], ir = b1[m].y * re[m];
-                    s1re[m] = s1re[m] + (rr - ii);
-                    s1im[m] = s1im[m] + (ir + ri);
-                }
-            }
-        }
+        // the L digit rows of this polynomial, hadamard + fold-add from zero: the one body every external product includes
+#define RTFHE_DIGIT_ROW(jj) (bk_i + (size_t)((h * L + jj) * 2) * R * 64 + lane)
+#include "rtfhe_body_digit_rows.hpp"
     }
 
     // the 2/N input scaling of the reference (fft_processor_spqlios.cpp:158) is folded into the untwist twiddles

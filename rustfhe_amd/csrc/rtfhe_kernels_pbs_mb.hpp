@@ -9,13 +9,20 @@
 // data).  Exactly one subset -- or none -- holds 1, so the bracket encrypts X^e - 1 for the e of the bits that are set, and the step is the
 // product of the group's single-bit CMUX steps.
 //
-// mb_step is cmux_step<.., CMUX = false> (rtfhe_kernels.hpp) restated with the key combination where that one reads its row pair: the same
-// decomposition of acc itself, the same transforms, the same fold order, inverse and truncation, the truncated product ADDED into acc.  Every
+// mb_step is cmux_step<.., CMUX = false> (rtfhe_kernels.hpp) with the key combination where that one reads its row pair: the same
+// decomposition of acc itself, the same transforms, the same fold order, inverse and truncation, the truncated product ADDED into acc.  Its
+// digit loop MIRRORS rtfhe_body_digit_rows.hpp -- the loop cmux_step includes -- and keeps its own text because its fold differs; a change there
+// is made here too.  The key combination is rtfhe_body_mb_combine.hpp, one text for this file's fold and k_pbs_mb_wg's product.  The tail
+// (inverse, truncation, += into acc) is cmux_step<.., CMUX = true>'s, kept as its own text: worded as cmux_step's it changes k_pbs_mb<11>,
+// worded as this one it changes the N = 2048 kernels built on cmux_step (profiles/r37/README.md).  Every
 // product and sum is rounded on its own (the library is built without contraction), in this order per digit row, component and point:
 //   K = F_{e_1} B_1;  K = K + F_{e_j} B_j for j = 2 .. J;  each complex product (rr - ii, ir + ri) as in cmux_step's hadamard;
 // then K stands where cmux_step has b0 / b1.  No subset is skipped when e_j = 0 (F_0 = 0 exactly: W[0] = 1).
 // J and the e_j are wave-uniform and live in scalar registers; W is read by a computed index.  The row pair of subset 1 is requested where
 // cmux_step requests its pair, behind fft_forward_a; the others one component at a time as they are combined: at g = 3 seven pairs cannot be live.
+//
+// A skipped gate (table index out of range) in the extract form parks its output row for k_rows_restore: the one parked-row rule of
+// rtfhe_kernels.hpp (park_row), with (tv_idx, 1, n_tv) as the restore's index rule.  In the fused form nothing is stored and the row keeps its words.
 //
 // k_pbs_mb: a wave per gate in k_trgsw_rotate's launch shape (four waves per workgroup, the accumulator in LDS across all steps), N = 1024
 // and 2048, any count, the frame of rtfhe_gate_frame.hpp around the step loop.  Instantiated in rtfhe_pbs_mb.hip.
@@ -48,17 +55,6 @@ __device__ __forceinline__ int mb_exponent(int j, int r0, int r1, int r2, int ma
     return (((j & 1) ? r0 : 0) + ((j & 2) ? r1 : 0) + ((j & 4) ? r2 : 0)) & mask;
 }
 
-// A skipped gate (table index out of range) in the extract form: the batch key switch behind the kernel writes every row (k_key_switch_mm adds
-// into a zeroed output), so the gate's threads park the n + 1 <= N words of its output row in the gate's own, otherwise unused, sample slots and
-// k_pbs_mb_restore, launched behind the key switch, puts them back (k_trgsw_rotate's rule, rtfhe_kernels_trgsw_rotate.hpp).  In the fused form
-// nothing is stored and the row keeps its words anyway.  This thread moves words t0, t0 + stride, ... <= n.
-template <int N>
-__device__ __forceinline__ void mb_park_row(const PbsMbArgs& a, int g, int t0, int stride) {
-    if (!a.ext) return;
-    const uint32_t* keep = a.out + (size_t)g * ((size_t)a.n + 1);
-    for (int c = t0; c <= a.n; c += stride) *ext_slot(a.ext, g, c, N) = keep[c];
-}
-
 // One multi-bit step on the wave-private accumulator in LDS.  group: the group's first TRGSW; J its subsets; r0 .. r2 its rotations (0 past
 // the group's bits); q: this lane's R point exponents.
 template <int LOGN, int L, int BGBIT, bool DUAL, bool ROUNDED>
@@ -80,6 +76,7 @@ __device__ __forceinline__ void mb_step(uint32_t* __restrict__ accbuf, int J, in
         uint32_t u[2 * R];
 #pragma unroll
         for (int mm = 0; mm < 2 * R; mm++) u[mm] = (poly[lane + 64 * mm] + MA) ^ MX;
+        // rtfhe_body_digit_rows.hpp mirrored: the same loop with the key combination in the fold
 #pragma unroll 1
         for (int jj = 0; jj < L; jj++) {
             const cplx* row = group + (size_t)((h * L + jj) * 2) * R * 64 + lane;
@@ -100,28 +97,7 @@ __device__ __forceinline__ void mb_step(uint32_t* __restrict__ accbuf, int J, in
             // the key combination of one component, then its hadamard + fold-add (cmux_step's, K for b)
             auto fold = [&](double (&sre)[R], double (&sim)[R], const cplx (&b)[R], int comp) {
                 cplx K[R];
-#pragma unroll
-                for (int m = 0; m < R; m++) {
-                    const cplx w = roots[(r0 * q[m]) & MASK];
-                    const double fx = w.x - 1.0, fy = w.y;
-                    const double ii = fy * b[m].y, rr = fx * b[m].x, ri = fx * b[m].y, ir = fy * b[m].x;
-                    K[m].x = rr - ii;
-                    K[m].y = ir + ri;
-                }
-#pragma unroll 1
-                for (int j = 2; j <= J; j++) {
-                    const int e = mb_exponent(j, r0, r1, r2, MASK);
-                    const cplx* bj = row + (size_t)(j - 1) * TRGSW + (size_t)comp * R * 64;
-#pragma unroll
-                    for (int m = 0; m < R; m++) {
-                        const cplx v = bj[m * 64];
-                        const cplx w = roots[(e * q[m]) & MASK];
-                        const double fx = w.x - 1.0, fy = w.y;
-                        const double ii = fy * v.y, rr = fx * v.x, ri = fx * v.y, ir = fy * v.x;
-                        K[m].x = K[m].x + (rr - ii);
-                        K[m].y = K[m].y + (ir + ri);
-                    }
-                }
+#include "rtfhe_body_mb_combine.hpp"
 #pragma unroll
                 for (int m = 0; m < R; m++) {
                     const double ii = K[m].y * im[m], rr = K[m].x * re[m], ri = K[m].x * im[m], ir = K[m].y * re[m];
@@ -185,8 +161,8 @@ __global__ __launch_bounds__(64 * MB_WAVES, 1) void k_pbs_mb(const PbsMbArgs a) 
     if (g >= a.count) return;
     const TvLut tvs{a.tv, a.tv_idx, a.n_tv, a.fault};
     const auto tv = tv_row(tvs, g, N);
-    if (!tv.ok()) {            // skipped: the output row keeps its words, *fault is set
-        mb_park_row<N>(a, g, lane, 64);
+    if (!tv.ok()) {            // skipped: the output row keeps its words (extract form: parked for k_rows_restore, rtfhe_kernels.hpp), *fault is set
+        park_row<N>(a, a.out, g, lane, 64);
         return;
     }
 
@@ -237,18 +213,6 @@ __global__ __launch_bounds__(64 * MB_WAVES, 1) void k_pbs_mb(const PbsMbArgs a) 
         return;
     }
     key_switch_wave<LOGN, MB_KS_T, MB_KS_BB, MB_KSQ>(accbuf + N, accbuf[0], a.ksk, a.ksw, n, io.out, lane);
-}
-
-// extract form, behind the batch key switch, for both kernel shapes: the output rows of skipped gates as they were before the call (a wave per
-// gate; the index is checked again, a good gate's wave returns at once).  Launched only where a.tv_idx and a.ext are given.
-template <int LOGN>
-__global__ __launch_bounds__(64 * MB_WAVES) void k_pbs_mb_restore(const PbsMbArgs a) {
-    constexpr int N = 1 << LOGN;
-    const int lane = threadIdx.x & 63;
-    const int g = blockIdx.x * MB_WAVES + (threadIdx.x >> 6);
-    if (g >= a.count || (unsigned)a.tv_idx[g] < (unsigned)a.n_tv) return;
-    uint32_t* row = a.out + (size_t)g * ((size_t)a.n + 1);
-    for (int c = lane; c <= a.n; c += 64) row[c] = *ext_slot(a.ext, g, c, N);
 }
 
 }  // namespace rtfhe

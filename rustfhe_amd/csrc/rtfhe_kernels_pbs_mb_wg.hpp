@@ -1,6 +1,7 @@
 // rtfhe_kernels_pbs_mb_wg.hpp -- the latency shape of the multi-bit blind rotation (rtfhe_kernels_pbs_mb.hpp): N = 1024, one gate per workgroup
 // of six waves.  Wave r owns digit row (h, jj) = (r / 3, r % 3) of every step: it decomposes polynomial h of the accumulator, transforms digit
-// jj forward, combines its own two key rows over the group's subsets and multiplies -- one sixth of mb_step's forward work, side by side.
+// jj forward, combines its own two key rows over the group's subsets (rtfhe_body_mb_combine.hpp, the text mb_step's fold includes) and
+// multiplies -- one sixth of mb_step's forward work, side by side.
 //
 // The six products meet in cmux_step's fold order, so that every word equals k_pbs_mb's: one running sum per component and point in LDS, to
 // which wave 0 stores 0.0 + its product and waves 1 .. 5 add theirs in turn, a barrier between turns (row r of mb_step's loop is turn r).  Waves
@@ -41,7 +42,7 @@ __global__ __launch_bounds__(64 * MB_WG_WAVES, 1) void k_pbs_mb_wg(const PbsMbAr
     const TvLut tvs{a.tv, a.tv_idx, a.n_tv, a.fault};
     const auto tv = tv_row(tvs, g, N);
     if (!tv.ok()) {                // skipped, by all six waves alike: the output row keeps its words, *fault is set
-        mb_park_row<N>(a, g, tid, THREADS);
+        park_row<N>(a, a.out, g, tid, THREADS);
         return;
     }
 
@@ -99,28 +100,7 @@ __global__ __launch_bounds__(64 * MB_WG_WAVES, 1) void k_pbs_mb_wg(const PbsMbAr
         cplx p0[R], p1[R];
         auto product = [&](cplx (&p)[R], const cplx (&b)[R], int comp) {
             cplx K[R];
-#pragma unroll
-            for (int m = 0; m < R; m++) {
-                const cplx w = roots[(r0 * q[m]) & MASK];
-                const double fx = w.x - 1.0, fy = w.y;
-                const double ii = fy * b[m].y, rr = fx * b[m].x, ri = fx * b[m].y, ir = fy * b[m].x;
-                K[m].x = rr - ii;
-                K[m].y = ir + ri;
-            }
-#pragma unroll 1
-            for (int j = 2; j <= J; j++) {
-                const int e = mb_exponent(j, r0, r1, r2, MASK);
-                const cplx* bj = row + (size_t)(j - 1) * TRGSW + (size_t)comp * R * 64;
-#pragma unroll
-                for (int m = 0; m < R; m++) {
-                    const cplx v = bj[m * 64];
-                    const cplx w = roots[(e * q[m]) & MASK];
-                    const double fx = w.x - 1.0, fy = w.y;
-                    const double ii = fy * v.y, rr = fx * v.x, ri = fx * v.y, ir = fy * v.x;
-                    K[m].x = K[m].x + (rr - ii);
-                    K[m].y = K[m].y + (ir + ri);
-                }
-            }
+#include "rtfhe_body_mb_combine.hpp"
 #pragma unroll
             for (int m = 0; m < R; m++) {
                 const double ii = K[m].y * im[m], rr = K[m].x * re[m], ri = K[m].x * im[m], ir = K[m].y * re[m];

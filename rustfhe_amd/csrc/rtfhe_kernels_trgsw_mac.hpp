@@ -5,8 +5,9 @@
 //                                                                                                         fold-add carried over the K terms)
 // so that K products cost 6 K forward transforms, ONE pair of inverse transforms and one truncation.  The blocks are cmux_step's (rtfhe_kernels.hpp):
 // the same digits, the same forward transform in its two halves with the selector's rows requested in between, the same unfused rr - ii, ir + ri
-// fold-add in the same order (h = b, a; j = 0 .. l-1), the same inverse.  Its forward half is RESTATED here (mac_forward), not shared: cmux_step
-// and the kernels that existed before keep their text and compile to what they did.  ROUNDED is cmux_step's.  Instantiated in rtfhe_trgsw_mac.hip.
+// fold-add in the same order (h = b, a; j = 0 .. l-1), the same inverse.  Its forward half (mac_forward) includes the loop over the digit rows
+// that cmux_step includes, rtfhe_body_digit_rows.hpp: one text, and every kernel compiles to what it did when each file carried a copy.
+// ROUNDED is cmux_step's.  Instantiated in rtfhe_trgsw_mac.hip.
 //
 // The sum reaches K * 2l * N * (Bg/2) * 2^31 = 2^51.6 (N = 1024) and 2^52.6 (N = 2048) at K = 8: above the 2^51 trunc_to_torus is exact below,
 // inside the 2^53 of an exact double, so the conversion is trunc_to_torus_wide.
@@ -60,38 +61,8 @@ __device__ __forceinline__ void mac_forward(const uint32_t* __restrict__ rowbuf,
         uint32_t u[2 * R];
 #pragma unroll
         for (int mm = 0; mm < 2 * R; mm++) u[mm] = (poly[lane + 64 * mm] + MA) ^ MX;
-#pragma unroll 1
-        for (int jj = 0; jj < L; jj++) {
-            const cplx* sj = S + (size_t)((h * L + jj) * 2) * R * 64 + lane;
-            double re[R], im[R];
-#pragma unroll
-            for (int m = 0; m < R; m++) {
-                re[m] = (double)decomp_digit(u[m], BGBIT, jj);
-                im[m] = (double)decomp_digit(u[R + m], BGBIT, jj);
-            }
-            fft_forward_a<LOGN, DUAL>(re, im, twf, xbuf, lane);
-            // the selector's two rows of this digit are requested here, as cmux_step does: not live through the whole transform
-            __builtin_amdgcn_sched_barrier(0);
-            cplx b0[R], b1[R];
-#pragma unroll
-            for (int m = 0; m < R; m++) { b0[m] = sj[m * 64]; b1[m] = sj[(R + m) * 64]; }
-            __builtin_amdgcn_sched_barrier(0);
-            fft_forward_b<LOGN, DUAL>(re, im, twf, xbuf, lane);
-            // hadamard + fold-add, utils/src/spqlios.rs:204-222, hom_nand/src/trgsw.rs:290-299
-#pragma unroll
-            for (int m = 0; m < R; m++) {
-                {
-                    const double ii = b0[m].y * im[m], rr = b0[m].x * re[m], ri = b0[m].x * im[m], ir = b0[m].y * re[m];
-                    s0re[m] = s0re[m] + (rr - ii);
-                    s0im[m] = s0im[m] + (ir + ri);
-                }
-                {
-                    const double ii = b1[m].y * im[m], rr = b1[m].x * re[m], ri = b1[m].x * im[m], ir = b1[m].y * re[m];
-                    s1re[m] = s1re[m] + (rr - ii);
-                    s1im[m] = s1im[m] + (ir + ri);
-                }
-            }
-        }
+#define RTFHE_DIGIT_ROW(jj) (S + (size_t)((h * L + jj) * 2) * R * 64 + lane)
+#include "rtfhe_body_digit_rows.hpp"
     }
 }
 

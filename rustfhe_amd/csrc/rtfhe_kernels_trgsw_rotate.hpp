@@ -8,8 +8,9 @@
 // compile to what they did.  ROUNDED is cmux_step's, as in k_cmux_tree.  Instantiated in rtfhe_cmux_tree.hip.
 //
 // A lookup with a selector index outside the set is skipped whole and its output row stays as it was.  In the extract form the batch key
-// switch that follows writes every row: the skipped lookup's wave parks the row's n + 1 <= N words in its own (otherwise unused) sample slots,
-// and k_trgsw_rotate_restore, launched behind the key switch, puts them back.
+// switch that follows writes every row: the skipped lookup's wave parks the row in its own sample slots and k_rows_restore, launched behind the
+// key switch, puts it back -- the one parked-row rule of rtfhe_kernels.hpp (park_row, whose loop this kernel has to restate: see there), with
+// (sel_idx, depth, n_sel) as the restore's index rule.
 #pragma once
 
 #include "rtfhe_kernels_cmux_tree.hpp"
@@ -25,7 +26,7 @@ struct TrgswRotateArgs {
     const uint32_t* in;        // [count][2][N] (b then a); may be exactly `out`
     uint32_t* out;             // [count][2][N] (unused in the extract form)
     uint32_t* ext;             // extract form: lvl1 samples in the batch key switch's operand order
-    uint32_t* ks_out;          // extract form: the key switch's output [count][n+1], whose rows of skipped lookups are put back (k_trgsw_rotate_restore)
+    uint32_t* ks_out;          // extract form: the key switch's output [count][n+1], whose rows of skipped lookups are put back (k_rows_restore)
     int32_t* fault;            // set to 1 when a lookup was skipped for an out-of-range index
     int32_t count, depth;
     int32_t n_sel, n;
@@ -59,6 +60,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_trgsw_rotate(const TrgswRotat
     if (!trgsw_rotate_ok(a, g)) {
         if (a.fault) *a.fault = 1;
         if (a.ext) {
+            // park_row (rtfhe_kernels.hpp) restated: through the helper all four kernels come out with other code (scripts/isa/snapshot.py)
             const uint32_t* keep = a.ks_out + (size_t)g * (a.n + 1);
             for (int c = lane; c <= a.n; c += 64) *ext_slot(a.ext, (int)g, c, N) = keep[c];
         }
@@ -92,17 +94,6 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_trgsw_rotate(const TrgswRotat
     }
     uint32_t* o = a.out + (size_t)g * 2 * N;
     for (int c = lane; c < 2 * N; c += 64) o[c] = accbuf[c];
-}
-
-// extract form, behind the key switch: the output rows of skipped lookups as they were before the call (one wave per lookup)
-template <int LOGN, int WAVES>
-__global__ __launch_bounds__(64 * WAVES, 1) void k_trgsw_rotate_restore(const TrgswRotateArgs a) {
-    constexpr int N = 1 << LOGN;
-    const int lane = threadIdx.x & 63;
-    const long long g = (long long)blockIdx.x * WAVES + (threadIdx.x >> 6);
-    if (g >= a.count || trgsw_rotate_ok(a, g)) return;
-    uint32_t* row = a.ks_out + (size_t)g * (a.n + 1);
-    for (int c = lane; c <= a.n; c += 64) row[c] = *ext_slot(a.ext, (int)g, c, N);
 }
 
 }  // namespace rtfhe

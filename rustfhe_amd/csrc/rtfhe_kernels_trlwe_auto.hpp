@@ -9,8 +9,9 @@
 // (TRGSWRepF::cross, trgsw.rs:264-306).  The blocks are cmux_step's (rtfhe_kernels.hpp): the same digits, the same forward transform in its two
 // halves with the key's two rows of the digit requested in between, the same unfused rr - ii, ir + ri fold-add, the same inverse and the same
 // truncation -- a single product stays below l * N * (Bg/2) * 2^31 < 2^49, so the narrow trunc_to_torus is exact.  The forward half is
-// mac_forward's inner body (rtfhe_kernels_trgsw_mac.hpp) for ONE polynomial, RESTATED here, not shared: cmux_step, mac_forward and the kernels
-// that existed before keep their text and compile to what they did.  ROUNDED is cmux_step's.  Instantiated in rtfhe_trlwe_auto.hip.
+// the loop over the digit rows that cmux_step and mac_forward include (rtfhe_body_digit_rows.hpp), for ONE polynomial, the rows read from
+// K[e]: one text, and every kernel compiles to what it did when each file carried a copy.  ROUNDED is cmux_step's.  Instantiated in
+// rtfhe_trlwe_auto.hip.
 //
 // The program (entries, add flags) is the host's and was checked there (rtfhe_trlwe_auto_plan): the kernel has no index to refuse.
 #pragma once
@@ -60,38 +61,8 @@ __device__ __forceinline__ void auto_step(uint32_t* __restrict__ rowbuf, int tin
         uint32_t u[2 * R];
 #pragma unroll
         for (int mm = 0; mm < 2 * R; mm++) u[mm] = (auto_coef<LOGN>(rowbuf + N, lane + 64 * mm, tinv) + MA) ^ MX;
-#pragma unroll 1
-        for (int jj = 0; jj < L; jj++) {
-            const cplx* kj = K + (size_t)(jj * 2) * R * 64 + lane;
-            double re[R], im[R];
-#pragma unroll
-            for (int m = 0; m < R; m++) {
-                re[m] = (double)decomp_digit(u[m], BGBIT, jj);
-                im[m] = (double)decomp_digit(u[R + m], BGBIT, jj);
-            }
-            fft_forward_a<LOGN, DUAL>(re, im, twf, xbuf, lane);
-            // the entry's two rows of this digit are requested here, as cmux_step does: not live through the whole transform
-            __builtin_amdgcn_sched_barrier(0);
-            cplx b0[R], b1[R];
-#pragma unroll
-            for (int m = 0; m < R; m++) { b0[m] = kj[m * 64]; b1[m] = kj[(R + m) * 64]; }
-            __builtin_amdgcn_sched_barrier(0);
-            fft_forward_b<LOGN, DUAL>(re, im, twf, xbuf, lane);
-            // hadamard + fold-add, utils/src/spqlios.rs:204-222, hom_nand/src/trgsw.rs:290-299
-#pragma unroll
-            for (int m = 0; m < R; m++) {
-                {
-                    const double ii = b0[m].y * im[m], rr = b0[m].x * re[m], ri = b0[m].x * im[m], ir = b0[m].y * re[m];
-                    s0re[m] = s0re[m] + (rr - ii);
-                    s0im[m] = s0im[m] + (ir + ri);
-                }
-                {
-                    const double ii = b1[m].y * im[m], rr = b1[m].x * re[m], ri = b1[m].x * im[m], ir = b1[m].y * re[m];
-                    s1re[m] = s1re[m] + (rr - ii);
-                    s1im[m] = s1im[m] + (ir + ri);
-                }
-            }
-        }
+#define RTFHE_DIGIT_ROW(jj) (K + (size_t)(jj * 2) * R * 64 + lane)
+#include "rtfhe_body_digit_rows.hpp"
     }
 
     // the 2/N input scaling of the reference (fft_processor_spqlios.cpp:158) is folded into the untwist twiddles

@@ -2,8 +2,8 @@
 // every group of g key bits as spectra, converted as a selector set's are, with the roots table and the point map of the key combination beside
 // them --, the argument checks (rtfhe_mb_plan.cpp, host only), the choice between the two kernel shapes and the rules around stream captures.
 // One launch of k_pbs_mb or k_pbs_mb_wg (their ROUNDED twins under rtfhe_set_decomposition) runs all ceil(n / g) steps of all gates; behind it
-// the extract tail every entry point with lvl1 samples shares (launch_key_switch_rows) and, where table indices are given, k_pbs_mb_restore
-// for the rows of skipped gates; or the kernel's own key switch.
+// the extract tail every entry point with lvl1 samples shares (launch_key_switch_rows_restore: where table indices are given, k_rows_restore
+// puts back the rows of skipped gates); or the kernel's own key switch.
 #include "rtfhe_host.hpp"
 
 #include <cstdlib>
@@ -89,11 +89,8 @@ int launch_mb(rtfhe_ctx* ctx, const rtfhe_mbk* mbk, const rtfhe_lut* lut, const 
     const dim3 grid((unsigned)((count + k.gates_per_wg - 1) / k.gates_per_wg)), block(k.threads);
     if (int rc = launch_kernel(ctx, ctx->decomp == RTFHE_DECOMP_ROUNDED ? k.rounded : k.reference, grid, block, k.lds, s, a)) return rc;
     if (!samples) return 0;
-    if (int rc = launch_key_switch_rows(ctx, samples->d[0], (uint32_t*)d_out, count, s)) return rc;
-    if (!d_idx) return 0;
     // the key switch has written every row: the rows of skipped gates come back from where their gates parked them (not counted: no gate runs in it)
-    const dim3 rgrid((unsigned)((count + MB_WAVES - 1) / MB_WAVES)), rblock(64 * MB_WAVES);
-    return ctx->logn == 11 ? launch_kernel(ctx, k_pbs_mb_restore<11>, rgrid, rblock, 0, s, a, false) : launch_kernel(ctx, k_pbs_mb_restore<10>, rgrid, rblock, 0, s, a, false);
+    return launch_key_switch_rows_restore(ctx, samples->d[0], (uint32_t*)d_out, count, d_idx, 1, lut->n_lut, false, s);
 }
 
 }  // namespace

@@ -126,6 +126,15 @@ int launch_key_switch_rows(rtfhe_ctx* ctx, uint32_t* samples, uint32_t* d_out, s
     return launch_key_switch_mm(ctx, k, samples, s);
 }
 
+int launch_key_switch_rows_restore(rtfhe_ctx* ctx, uint32_t* samples, uint32_t* d_out, size_t rows, const int32_t* d_idx, int32_t per_row, int32_t bound,
+                                   bool counted, hipStream_t s) {
+    if (int rc = launch_key_switch_rows(ctx, samples, d_out, rows, s)) return rc;
+    if (!d_idx && !counted) return 0;
+    const RowsRestoreArgs a{d_idx, samples, d_out, (int32_t)rows, per_row, bound, ctx->p.n};
+    const dim3 grid((unsigned)((rows + ROWS_RESTORE_WAVES - 1) / ROWS_RESTORE_WAVES)), block(64 * ROWS_RESTORE_WAVES);
+    return launch_kernel(ctx, ctx->logn == 11 ? k_rows_restore<11> : k_rows_restore<10>, grid, block, 0, s, a, counted);
+}
+
 }  // namespace rtfhe_host
 
 extern "C" {

@@ -8,7 +8,7 @@ rtfhe_circuit.hip, rtfhe_batch.hip and rtfhe_stages.hip:
                                              k_key_switch_ext)
   demultiplexer, depth d         d           one k_demux_tree per level
   rotation                       1           all steps of all lookups in one k_trgsw_rotate
-  rotation with extraction       3           the rotation, the key switch, k_trgsw_rotate_restore
+  rotation with extraction       3           the rotation, the key switch, k_rows_restore
   Lut.accumulate_dev             1           k_trlwe_accumulate
   netlist of L levels            L + 2       k_cmux_net_check, one k_cmux_net per level, k_cmux_net_out; + 1 key switch in the extract form
   pack of P positions            1 + ceil(P / 512)      k_pack_ks_mm, then k_pack_combine per PACK_POS_MAX = 512 positions

@@ -182,7 +182,7 @@ def test_the_kernels_own_key_switch_gives_the_batch_key_switchs_words(world, mon
 def test_a_skipped_gate_among_odd_length_rows(world, monkeypatch):
     """n = 64 (rows of n + 1 = 65 words), _dev form, count = 6, table indices 3 and -1 on gates 0 and 4, both shapes: reported once by sync, the
     other four rows are the clean run's, the two skipped rows (parked in their sample slots across the batch key switch and put back by
-    k_pbs_mb_restore) and the words behind the output keep their fill."""
+    k_rows_restore) and the words behind the output keep their fill."""
     import torch
     w = world
     if w.n != 64:

@@ -180,10 +180,45 @@ def _bad_patterns(count, depth):
     return good, out
 
 
-@pytest.mark.parametrize("extract", [False, True], ids=["rows", "extract"])
-def test_skipped_lookups_leave_their_rows_untouched(world, extract):
+def _five_lookups_behind_both_key_switches(orc, w, monkeypatch):
+    """The extract form's restore kernel (k_rows_restore) on five lookups of depth 2 -- one more than a workgroup's four waves -- with lookups 0
+    and 4 out of range in their LAST step only, behind the batch key switch and behind the wave-per-sample one (RTFHE_KS_MM_MIN=0): rows 0 and 4
+    keep the bytes written before the call, rows 1 to 3 equal the oracle, the next sync reports the fault once."""
+    import torch
+    R = w.R
+    depth, count, width = 2, 5, w.rp.n + 1
+    st = torch.cuda.current_stream().cuda_stream
+    rows = w.rows[:count]
+    idx = np.tile(np.arange(depth, dtype=np.int32), (count, 1))
+    idx[0, depth - 1], idx[4, depth - 1] = -1, N_SEL
+    want = (0xC3000000 + 0x1001 * np.arange(count, dtype=np.uint32)[:, None] + np.arange(width, dtype=np.uint32)[None, :]).astype(np.uint32)
+    before = want.copy()
+    want[1:4] = _oracle(orc, w, idx[1:4], w.rot(depth), rows[1:4], extract=True)
+    ext = gk.engine(R, w.rp, w.bk, w.ksk, monkeypatch, {"RTFHE_KS_MM_MIN": "0"})
+    try:
+        with ext.selectors(w.sel_t) as ext_sel:
+            for name, e, sel in (("batch key switch", w.eng, w.sel), ("wave-per-sample key switch", ext, ext_sel)):
+                d_out = gk.to_device(before, np.uint32)
+                e.trgsw_rotate_extract_batch_dev(sel, gk.to_device(rows, np.uint32), depth, d_out, count, gk.to_device(idx), w.rot(depth), st)
+                with pytest.raises(R.RtfheError) as ei:
+                    e.sync(st)
+                assert ei.value.code == R._ffi.ERR_INVALID, name
+                e.sync(st)                                       # reported once
+                got = d_out.cpu().numpy().view(np.uint32)
+                assert np.array_equal(got[[0, 4]], before[[0, 4]]), (name, "a skipped lookup's row changed")
+                assert np.array_equal(got[1:4], want[1:4]), (name, np.flatnonzero((got != want).any(axis=1)))
+    finally:
+        ext.close()
+
+
+@pytest.mark.parametrize("form", ["rows", "extract", "extract-five"])
+def test_skipped_lookups_leave_their_rows_untouched(orc, world, monkeypatch, form):
     """Device-side sel_idx with entries outside [0, n_sel): the lookup is skipped whole, its output row and the guard rows around the output keep
-    every byte of a row-dependent sentinel, the valid rows equal the clean call's, sync raises exactly once and a clean call follows."""
+    every byte of a row-dependent sentinel, the valid rows equal the clean call's, sync raises exactly once and a clean call follows.
+    extract-five: _five_lookups_behind_both_key_switches."""
+    if form == "extract-five":
+        return _five_lookups_behind_both_key_switches(orc, world, monkeypatch)
+    extract = form == "extract"
     import torch
     w, R = world, world.R
     depth = 3
