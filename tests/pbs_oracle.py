@@ -10,19 +10,30 @@ import numpy as np
 U32 = 0xFFFFFFFF
 
 
+def switch_body(word, s, lt=0):
+    """the mod switch of a body word at s = SH + lt (tfhe.rs:97): floor, scaled back by 2^lt"""
+    return (int(word) >> s) << lt
+
+
+def switch_mask(word, s, lt=0):
+    """the mod switch of a mask word at s = SH + lt (tfhe.rs:107-108): round, the sum wrapping mod 2^32 as the reference's wrapping_add does,
+    scaled back by 2^lt"""
+    return (((int(word) + (1 << (s - 1))) & U32) >> s) << lt
+
+
 def oracle_pbs(orc, p, plan, bk_f, ksk, tv, t):
     """rtfhe.h's PBS semantics, word for word with the reference's arithmetic: acc = X^{-bbar} (tv, 0); n CMUX steps; extract; key switch."""
     L = orc.lib()
     N, n = p.N, p.n
     sh = 32 - p.nbit - 1
     t = np.ascontiguousarray(t, np.uint32)
-    bbar = int(t[n]) >> sh
+    bbar = switch_body(t[n], sh)
     acc = np.zeros(2 * N, np.uint32)
     acc[:N] = orc.rotate(np.ascontiguousarray(tv, np.uint32), -bbar)
     rot = np.empty(2 * N, np.uint32)
     trgsw = 2 * 2 * p.l * N
     for i in range(n):
-        abar = ((int(t[i]) + (1 << (sh - 1))) & U32) >> sh
+        abar = switch_mask(t[i], sh)
         rot[:N] = orc.rotate(acc[:N], abar)
         rot[N:] = orc.rotate(acc[N:], abar)
         bki = np.ascontiguousarray(bk_f[i * trgsw:(i + 1) * trgsw])
@@ -64,13 +75,13 @@ def oracle_pbs_many(orc, p, plan, bk_f, ksk, tv, t, n_out):
     assert n_out == 1 << lt, "n_out is a power of two"
     s = 32 - p.nbit - 1 + lt
     t = np.ascontiguousarray(t, np.uint32)
-    bbar = (int(t[n]) >> s) << lt
+    bbar = switch_body(t[n], s, lt)
     acc = np.zeros(2 * N, np.uint32)
     acc[:N] = orc.rotate(np.ascontiguousarray(tv, np.uint32), -bbar)
     rot = np.empty(2 * N, np.uint32)
     trgsw = 2 * 2 * p.l * N
     for i in range(n):
-        abar = ((((int(t[i]) + (1 << (s - 1))) & U32) >> s) << lt)
+        abar = switch_mask(t[i], s, lt)
         rot[:N] = orc.rotate(acc[:N], abar)
         rot[N:] = orc.rotate(acc[N:], abar)
         bki = np.ascontiguousarray(bk_f[i * trgsw:(i + 1) * trgsw])
@@ -90,14 +101,14 @@ def oracle_pbs_enc(orc, p, plan, bk_f, ksk, trlwe, t, n_out):
     s = 32 - p.nbit - 1 + lt
     t = np.ascontiguousarray(t, np.uint32)
     trlwe = np.ascontiguousarray(trlwe, np.uint32).reshape(2, N)
-    bbar = (int(t[n]) >> s) << lt
+    bbar = switch_body(t[n], s, lt)
     acc = np.zeros(2 * N, np.uint32)
     acc[:N] = orc.rotate(np.ascontiguousarray(trlwe[0]), -bbar)
     acc[N:] = orc.rotate(np.ascontiguousarray(trlwe[1]), -bbar)
     rot = np.empty(2 * N, np.uint32)
     trgsw = 2 * 2 * p.l * N
     for i in range(n):
-        abar = ((((int(t[i]) + (1 << (s - 1))) & U32) >> s) << lt)
+        abar = switch_mask(t[i], s, lt)
         rot[:N] = orc.rotate(acc[:N], abar)
         rot[N:] = orc.rotate(acc[N:], abar)
         bki = np.ascontiguousarray(bk_f[i * trgsw:(i + 1) * trgsw])
